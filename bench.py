@@ -20,8 +20,13 @@ N > 1 (one process per GPU, launched by torch.distributed.run, RCCL through torc
   strong        the single-tracer matrix (or --grid 1440x720x80 = configs[4]) cut into N latitude bands
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--grid IxJxK] [--adv ..] [--hmix ..] [--multi-gpu c4|weak|strong]
+                  [--dump-outputs DIR] [--full]
 
 Prints ONE JSON line on rank 0.  value = unknowns solved per second over the whole job.
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds everything else: the residual re-checked
+with torch's own SpMV, the per-kernel roofline, the batched and concurrent right-hand sides, the round-1 recipe and the CPU
+baseline.  --dump-outputs DIR writes the solution of the last timed step as DIR/x.npy (float64; a fixed, seeded sample of
+it beyond DUMP_BYTES), so that two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -68,7 +73,29 @@ def parse():
     ap.add_argument("--comm", choices=["rccl", "torch"], default="rccl",
                     help="N > 1 collectives: rccl = the library's own RCCL communicator (C only, no Python per iteration; "
                          "torch.distributed just carries the unique id), torch = torch.distributed callbacks")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: torch re-check of the residual, roofline and per-kernel timings, --rhs-batch, "
+                         "--round1-steps and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's solution to DIR/x.npy")
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return a
+
+
+DUMP_BYTES = 60 << 20               # all dumped arrays together stay under 64 MB, .npy headers included
+
+
+def dump_outputs(directory, arrays):
+    """DIR/<name>.npy in float64; an array beyond the byte budget is replaced by a fixed, seeded sample of its entries
+    (sorted indices, the same for every run with the same arguments)."""
+    os.makedirs(directory, exist_ok=True)
+    for name, v in arrays.items():
+        v = np.ascontiguousarray(v, dtype=np.float64).ravel()
+        cap = DUMP_BYTES // len(arrays) // v.itemsize
+        if v.size > cap:
+            v = v[np.sort(np.random.default_rng(0).choice(v.size, size=cap, replace=False))]
+        np.save(os.path.join(directory, name + ".npy"), v)
 
 
 def latest_profile(suffix):
@@ -346,82 +373,89 @@ def main():
         all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
 
-    # independent check of the last solution with torch's own SpMV (not the kernel under test)
-    relres_check = None
-    try:
-        if distributed:
-            sizes = [int(starts[r + 1] - starts[r]) for r in range(world)]
-            pad = max(sizes)
+    def gathered_solution():
+        """the last step's solution, all n_global rows of it (a collective when distributed: every rank calls it)"""
+        if not distributed:
+            return X[-1]
+        sizes = [int(starts[r + 1] - starts[r]) for r in range(world)]
+        pad = max(sizes)
+        mine = torch.zeros(pad, dtype=torch.float64, device="cuda")      # equal-size all_gather, then trim
+        mine[:n] = X[-1]
+        parts = [torch.empty(pad, dtype=torch.float64, device="cuda") for _ in range(world)]
+        all_gather(parts, mine)
+        return torch.cat([parts[r][:sizes[r]] for r in range(world)])
 
-            def gather_padded(v):                          # equal-size all_gather, then trim
-                mine = torch.zeros(pad, dtype=torch.float64, device="cuda")
-                mine[:v.numel()] = v
-                parts = [torch.empty(pad, dtype=torch.float64, device="cuda") for _ in range(world)]
-                all_gather(parts, mine)
-                return torch.cat([parts[r][:sizes[r]] for r in range(world)])
-            xg, bg = gather_padded(X[-1]), None
-        else:
-            xg, bg = X[-1], B[-1]
-        if distributed:
-            # every rank checks its own rows against the gathered solution; squared norms are summed over ranks
-            crow = torch.from_numpy(loc["rowptr"].astype(np.int64)).cuda()
-            ccol = torch.from_numpy(loc["colind"].astype(np.int64)).cuda()
-            cval = torch.from_numpy(loc["val"]).cuda()
-            At = torch.sparse_csr_tensor(crow, ccol, cval, size=(n, n_global))
-            r = B[-1] - (At @ xg.unsqueeze(1)).squeeze(1)
-            sq = torch.stack([torch.sum(r * r), torch.sum(B[-1] * B[-1])])
-            all_reduce(sq)
-            relres_check = float(torch.sqrt(sq[0] / sq[1]))
-            del At, crow, ccol, cval, r
-        else:
-            crow = torch.from_numpy(p.rowptr.astype(np.int64)).cuda()
-            ccol = torch.from_numpy(p.colind.astype(np.int64)).cuda()
-            cval = torch.from_numpy(p.nzval).cuda()
-            At = torch.sparse_csr_tensor(crow, ccol, cval, size=(n_global, n_global))
-            r = bg - (At @ xg.unsqueeze(1)).squeeze(1)
-            relres_check = float(torch.linalg.norm(r) / torch.linalg.norm(bg))
-            del At, crow, ccol, cval
-    except Exception as exc:
-        print(f"({rank}) residual re-check skipped: {exc!r}", file=sys.stderr)
+    if a.dump_outputs:
+        xg = gathered_solution()
+        if rank == 0:
+            dump_outputs(a.dump_outputs, {"x": xg.cpu().numpy()})
+        del xg
 
-    # dominant-kernel roofline: the CSR SpMV, timed with HIP events on the solver's own stream
-    spmv_ms = s.time_kernel(0, reps=200)
-    spmv_bytes = s.get_int("spmv_bytes")
-    achieved = spmv_bytes / spmv_ms / 1e6          # GB/s
-    pre_ms = s.time_kernel(1, reps=50)
-    it_ms = {f"j{j}": s.time_kernel(2, reps=10, arg=j) for j in (0, a.restart // 2, a.restart - 1)}
+    if a.full:
+        # independent check of the last solution with torch's own SpMV (not the kernel under test)
+        relres_check = None
+        try:
+            xg, bg = gathered_solution(), (None if distributed else B[-1])
+            if distributed:
+                # every rank checks its own rows against the gathered solution; squared norms are summed over ranks
+                crow = torch.from_numpy(loc["rowptr"].astype(np.int64)).cuda()
+                ccol = torch.from_numpy(loc["colind"].astype(np.int64)).cuda()
+                cval = torch.from_numpy(loc["val"]).cuda()
+                At = torch.sparse_csr_tensor(crow, ccol, cval, size=(n, n_global))
+                r = B[-1] - (At @ xg.unsqueeze(1)).squeeze(1)
+                sq = torch.stack([torch.sum(r * r), torch.sum(B[-1] * B[-1])])
+                all_reduce(sq)
+                relres_check = float(torch.sqrt(sq[0] / sq[1]))
+                del At, crow, ccol, cval, r
+            else:
+                crow = torch.from_numpy(p.rowptr.astype(np.int64)).cuda()
+                ccol = torch.from_numpy(p.colind.astype(np.int64)).cuda()
+                cval = torch.from_numpy(p.nzval).cuda()
+                At = torch.sparse_csr_tensor(crow, ccol, cval, size=(n_global, n_global))
+                r = bg - (At @ xg.unsqueeze(1)).squeeze(1)
+                relres_check = float(torch.linalg.norm(r) / torch.linalg.norm(bg))
+                del At, crow, ccol, cval
+        except Exception as exc:
+            print(f"({rank}) residual re-check skipped: {exc!r}", file=sys.stderr)
 
-    # HBM bytes per SpMV launch from the PMC counters: collected in separate rocprofv3 --pmc passes
-    # (FETCH_SIZE, WRITE_SIZE) and committed under profiles/; used only when it is this exact workload
-    traffic = None
-    try:
-        rec = json.load(open(latest_profile("spmv_pmc.json")))
-        if rec.get("n") == n_global and rec.get("nnz") == p.nnz and not distributed:
-            traffic = rec["traffic_bytes_per_launch"]
-    except Exception:
-        pass
-    # the kernels the solve actually spends its time in (HIP events on the solver's stream, compulsory bytes from the library)
-    kernels = []
-    if not distributed:
-        for label, which, key, reps in (("csr_spmv_pipe_kernel<1, float> (smoother residual rows, fine level, one colour)", 3, "smoother_spmv_bytes", 100),
-                                        ("colblock_apply_ldspack_kernel (water-column solves, fine level, one colour)", 4, "column_solve_bytes", 100),
-                                        ("whole V-cycle (all levels, 88 launches)", 1, "cycle_bytes", 50)):
-            ms = pre_ms if which == 1 else s.time_kernel(which, reps=reps)
-            nbytes = s.get_int(key)
-            if nbytes > 0 and ms > 0:
-                kernels.append({"kernel": label, "bound": "hbm", "algorithmic_bytes_per_launch": nbytes, "avg_launch_ms": ms,
-                                "achieved": nbytes / ms / 1e6, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": nbytes / ms / 1e6 / HBM_PEAK_GBS})
-    # HBM bytes per launch of those kernels from the PMC counters (separate rocprofv3 --pmc passes over tools/pmc_cycle.py,
-    # committed under profiles/); attached only when it is this exact workload
-    try:
-        rec = json.load(open(latest_profile("cycle_pmc.json")))
-        if rec.get("n") == n_global and rec.get("nnz") == p.nnz and not distributed:
-            for k in kernels:
-                for q in rec["kernels"]:
-                    if k["kernel"].split("<")[0].split(" ")[0] in q["kernel"] and abs(q["algorithmic_bytes_per_launch"] - k["algorithmic_bytes_per_launch"]) <= 0.01 * k["algorithmic_bytes_per_launch"]:
-                        k["traffic"] = q["traffic_bytes_per_launch"]
-    except Exception:
-        pass
+        # dominant-kernel roofline: the CSR SpMV, timed with HIP events on the solver's own stream
+        spmv_ms = s.time_kernel(0, reps=200)
+        spmv_bytes = s.get_int("spmv_bytes")
+        achieved = spmv_bytes / spmv_ms / 1e6          # GB/s
+        pre_ms = s.time_kernel(1, reps=50)
+        it_ms = {f"j{j}": s.time_kernel(2, reps=10, arg=j) for j in (0, a.restart // 2, a.restart - 1)}
+
+        # HBM bytes per SpMV launch from the PMC counters: collected in separate rocprofv3 --pmc passes
+        # (FETCH_SIZE, WRITE_SIZE) and committed under profiles/; used only when it is this exact workload
+        traffic = None
+        try:
+            rec = json.load(open(latest_profile("spmv_pmc.json")))
+            if rec.get("n") == n_global and rec.get("nnz") == p.nnz and not distributed:
+                traffic = rec["traffic_bytes_per_launch"]
+        except Exception:
+            pass
+        # the kernels the solve actually spends its time in (HIP events on the solver's stream, compulsory bytes from the library)
+        kernels = []
+        if not distributed:
+            for label, which, key, reps in (("csr_spmv_pipe_kernel<1, float> (smoother residual rows, fine level, one colour)", 3, "smoother_spmv_bytes", 100),
+                                            ("colblock_apply_ldspack_kernel (water-column solves, fine level, one colour)", 4, "column_solve_bytes", 100),
+                                            ("whole V-cycle (all levels, 88 launches)", 1, "cycle_bytes", 50)):
+                ms = pre_ms if which == 1 else s.time_kernel(which, reps=reps)
+                nbytes = s.get_int(key)
+                if nbytes > 0 and ms > 0:
+                    kernels.append({"kernel": label, "bound": "hbm", "algorithmic_bytes_per_launch": nbytes, "avg_launch_ms": ms,
+                                    "achieved": nbytes / ms / 1e6, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": nbytes / ms / 1e6 / HBM_PEAK_GBS})
+        # HBM bytes per launch of those kernels from the PMC counters (separate rocprofv3 --pmc passes over tools/pmc_cycle.py,
+        # committed under profiles/); attached only when it is this exact workload
+        try:
+            rec = json.load(open(latest_profile("cycle_pmc.json")))
+            if rec.get("n") == n_global and rec.get("nnz") == p.nnz and not distributed:
+                for k in kernels:
+                    for q in rec["kernels"]:
+                        if k["kernel"].split("<")[0].split(" ")[0] in q["kernel"] and abs(q["algorithmic_bytes_per_launch"] - k["algorithmic_bytes_per_launch"]) <= 0.01 * k["algorithmic_bytes_per_launch"]:
+                            k["traffic"] = q["traffic_bytes_per_launch"]
+        except Exception:
+            pass
     if rank != 0:
         if dist.is_initialized():
             dist.destroy_process_group()
@@ -451,7 +485,7 @@ def main():
             "multi_gpu": mode,
         },
         "solve": {"iterations": iters, "relres": [i["relres"] for i in infos], "berr": [i["berr"] for i in infos],
-                  "relres_checked_with_torch": relres_check, "setup_s": t_setup, "generate_s": t_gen,
+                  "setup_s": t_setup, "generate_s": t_gen,
                   # what the reference's factor-then-solve job waits for (src/solve_ABglobal.c:349-402): host arrays ready ->
                   # solver created (matrix upload, hierarchy, factors) -> first right-hand side solved, first-launch costs included
                   "first_solve_s": first_solve_s, "time_to_first_solution_s": t_setup + (first_solve_s or 0.0),
@@ -460,17 +494,18 @@ def main():
                   "levels": s.get_int("levels"), "precond_cycles_per_iteration": s.get_int("precond_steps"),
                   "device_MB": s.get_int("device_bytes") / 1e6,
                   "distributed": ({"halo_hidden_behind_interior_rows": s.get_int("dist_overlap"), "hierarchy_overlaps_neighbours": s.get_int("dist_ras"),
-                                   "overlap_rows_rank0": s.get_int("dist_ras_rows")} if distributed else None),
-                  "precond_apply_ms": pre_ms, "krylov_iteration_ms": it_ms},
-        "roofline": {"kernel": "csr_spmv_pipe_kernel<0, double, false>", "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS,
-                     "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
-                     "algorithmic_bytes_per_launch": spmv_bytes, "avg_launch_ms": spmv_ms,
-                     # context only: the guide's measured float4-copy ceiling (MI355X_MICROARCH.md: 6.29 TB/s)
-                     "measured_copy_ceiling": MEASURED_COPY_GBS, "frac_of_copy_ceiling": achieved / MEASURED_COPY_GBS,
-                     "hbm_traffic_rate": (traffic / spmv_ms / 1e6) if traffic else None,
-                     "kernels": kernels},
+                                   "overlap_rows_rank0": s.get_int("dist_ras_rows")} if distributed else None)},
     }
-    if not distributed and world == 1 and a.rhs_batch > 1:
+    if a.full:
+        out["solve"].update({"relres_checked_with_torch": relres_check, "precond_apply_ms": pre_ms, "krylov_iteration_ms": it_ms})
+        out["roofline"] = {"kernel": "csr_spmv_pipe_kernel<0, double, false>", "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS,
+                           "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
+                           "algorithmic_bytes_per_launch": spmv_bytes, "avg_launch_ms": spmv_ms,
+                           # context only: the guide's measured float4-copy ceiling (MI355X_MICROARCH.md: 6.29 TB/s)
+                           "measured_copy_ceiling": MEASURED_COPY_GBS, "frac_of_copy_ceiling": achieved / MEASURED_COPY_GBS,
+                           "hbm_traffic_rate": (traffic / spmv_ms / 1e6) if traffic else None,
+                           "kernels": kernels}
+    if a.full and not distributed and world == 1 and a.rhs_batch > 1:
         # the reference's RHS loop (src/solve_ABglobal.c:370-409) with R tracers per sweep of the matrix and the hierarchy
         # (nkp_solve_batch_device: one FGMRES recurrence per system, the operator and cycle applications shared); beside it the
         # round-2 way, R clones on R host threads
@@ -492,7 +527,7 @@ def main():
                             "how": "nkp_solve_batch_device: K interleaved right-hand sides per sweep (csrc/batch.hip); every column bit-identical to its single solve"}
         del Bb, Xb
         out["rhs_concurrent_clones"] = rhs_batch_throughput(torch, s, a.rhs_batch, a.steps, n)
-    if not distributed and world == 1 and k33 and a.round1_steps > 0:
+    if a.full and not distributed and world == 1 and k33 and a.round1_steps > 0:
         # continuity with round 1: the same solver on the round-1 synthetic recipe (reported beside `value`, never as it)
         s.close()
         p1 = synth.generate(imt=imt, jmt=jmt, km=km, adv=a.adv, hmix=a.hmix, seed=0, isop_k33=False)
@@ -512,7 +547,7 @@ def main():
                                 "round1_ms_per_step": 2861.96}
         s1.close()
         del p1
-    if not a.no_cpu_baseline:
+    if a.full and not a.no_cpu_baseline:
         # measured, not extrapolated: ONE complete solve of this very workload with the same algorithm on all host cores
         cs = cpu_complete_solve(p, blk, ci, cj, a.rtol, a.restart)
         out["cpu_baseline"] = {"value": cs["unknowns_per_s"], "unit": "unknowns/s", "cores": cs["cores"], "kind": "port",

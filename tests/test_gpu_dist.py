@@ -165,8 +165,9 @@ def test_bench_distributed_path_on_one_rank(tmp_path):
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT="29533", RANK="0", WORLD_SIZE="1", LOCAL_RANK="0")
+    import numpy as np
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--force-dist", "--grid", "40x46x20", "--steps", "2", "--warmup", "1",
-           "--no-cpu-baseline", "--rhs-batch", "0", "--round1-steps", "0"]
+           "--full", "--no-cpu-baseline", "--rhs-batch", "0", "--round1-steps", "0", "--dump-outputs", str(tmp_path / "out")]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=root)
     assert out.returncode == 0, out.stderr[-2000:]
     line = json.loads(out.stdout.strip().splitlines()[-1])
@@ -175,6 +176,10 @@ def test_bench_distributed_path_on_one_rank(tmp_path):
     assert "self-test" not in out.stderr, out.stderr[-2000:]
     assert line["value"] > 0 and max(line["solve"]["relres"]) <= 1e-10
     assert line["solve"]["relres_checked_with_torch"] <= 1.1e-10
+    assert line["steps"] == 2 and len(line["solve"]["iterations"]) == 2
+    x = np.load(tmp_path / "out" / "x.npy")
+    n = int(line["config"]["workload"].split(" n=")[1].split(",")[0])
+    assert x.dtype == np.float64 and x.shape == (n,) and np.all(np.isfinite(x)) and np.any(x != 0)
 
 
 def test_cell_major_order_on_one_gpu():
