@@ -253,6 +253,26 @@ int nkp_time_kernel (nkp_solver *s, int which, int arg, int reps, double *avg_ms
  * "dist_ras" (hierarchy overlaps the neighbouring ranks), "dist_ras_rows" (rows of other ranks in this rank's hierarchy). */
 int64_t nkp_get_int (nkp_solver *s, const char *key);
 
+/* New matrix values on the sparsity pattern the solver was created with (the analogue of SuperLU's
+ * Fact = SamePattern): val holds nnz values in the CSR order of nkp_create / nkp_create64 (host), d_val the same on
+ * the solver's device.  On success every later solve, nkp_spmv and nkp_precond_apply uses the new matrix.
+ *   flags = 0: the multilevel hierarchy keeps its coarse cells (the aggregation) and every allocation; all numeric
+ *     arrays (twin, Galerkin operators of every level, f32 copies, column factors, coarsest inverse, row scaling) are
+ *     recomputed on the device.  They are bit for bit what nkp_create builds from val whenever that create picks the
+ *     same coarse cells.  When a coupling the hierarchy dropped as an exact zero becomes non-zero, or a stored one
+ *     becomes exactly zero, the refactor notices before writing anything and rebuilds the hierarchy instead.
+ *   flags = NKP_REFACTOR_REBUILD: rebuild the hierarchy (coarse cells included) on the new values inside the same
+ *     solver; work vectors, stream and the SpMV's row blocks and codes are kept.  Bit for bit nkp_create(val).
+ * nkp_get_int: "refactor_count", "refactor_rebuilt" (1 if the last call rebuilt the hierarchy), "refactor_us".
+ * Returns 0, NKP_EINVAL (NULL argument, a clone, the row-distributed flavour, a rebuild while clones are alive),
+ * NKP_ESINGULAR (a zero or missing diagonal: the solver is unchanged), NKP_ENOMEM / NKP_EDEVICE.  An error before
+ * any value is written leaves the solver solving exactly as before; a zero pivot met while factoring the new values
+ * leaves it unusable (every later solve returns NKP_ESINGULAR naming the failed refactor).  No solve may be in
+ * flight on the solver or on any of its clones during the call. */
+#define NKP_REFACTOR_REBUILD 1
+int nkp_refactor (nkp_solver *s, const double *val, int flags);
+int nkp_refactor_device (nkp_solver *s, const void *d_val, int flags);
+
 /* Use an externally owned HIP stream (hipStream_t cast to void*) instead of the solver's own;
  * NULL = the device's default stream. */
 int nkp_set_stream (nkp_solver *s, void *hip_stream);
@@ -331,7 +351,10 @@ int nkp_permuted_rows (int64_t n, const int32_t *rowptr, const int32_t *colind, 
  * vectors and a second stream on the SAME device-resident matrix, factors and hierarchy (nothing is copied), so
  * that several right-hand sides can be in flight at once: one clone per host thread, each calling nkp_solve /
  * nkp_solve_device on its own handle.  Results are bit-identical to solving on the original.  Destroy clones
- * (nkp_destroy) before the solver they were cloned from.  Single-GPU solvers only. */
+ * (nkp_destroy) before the solver they were cloned from.  Single-GPU solvers only.  nkp_refactor on the source
+ * without NKP_REFACTOR_REBUILD updates the shared matrix and hierarchy in place, so every clone sees the new values;
+ * no solve may then be in flight on any of them.  A refactor that has to rebuild the hierarchy is refused while
+ * clones are alive. */
 int nkp_clone (nkp_solver *src, nkp_solver **out);
 
 /* hipSetDevice for host programs that do not link HIP themselves (call before nkp_comm_rccl_init). */

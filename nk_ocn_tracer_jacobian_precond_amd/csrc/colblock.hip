@@ -1524,6 +1524,31 @@ int colblock_build_lane_layout (ColBlocksDev &B, const int *h_blk_start, const i
    return (int) hipStreamSynchronize (st);
 }
 
+int colblock_group_columns (const ColBlocksDev &B, std::vector<int> &gcols)
+{
+   gcols.clear ();
+   const nkp_tuning &T = B.tune ? *B.tune : nkp_builtin_tuning ();
+   if (!(B.ldsres == 2 && T.col_sort_groups != 0) || B.ngrp == 0) return 0;      // groups of consecutive columns
+   // sorted groups: col_slot holds every lane's absolute first row and its length; the column is found from its first row
+   std::vector<int> slot ((size_t) 2 * B.ngrp * B.gw), start ((size_t) B.nblk + 1);
+   hipError_t e = hipMemcpy (slot.data (), B.col_slot, slot.size () * sizeof (int), hipMemcpyDeviceToHost);
+   if (e == hipSuccess) e = hipMemcpy (start.data (), B.blk_start, start.size () * sizeof (int), hipMemcpyDeviceToHost);
+   if (e != hipSuccess) return (int) e;
+   const size_t lanes = (size_t) B.ngrp * B.gw;
+   gcols.resize (lanes);
+   for (size_t q = 0; q < lanes; q++)
+      gcols[q] = slot[lanes + q] > 0 ? (int) (std::lower_bound (start.begin (), start.end (), slot[q]) - start.begin ()) : -1;
+   return 0;
+}
+
+int colblock_repack_lane_layout (const ColBlocksDev &B, const int *d_gcols, hipStream_t st)
+{
+   if (B.ngrp == 0 || !(B.fac_t || B.fac_tf)) return 0;
+   hipLaunchKernelGGL (colblock_transpose_kernel, dim3 (B.ngrp), dim3 (NKP_WAVE), 0, st, B.blk_start, B.grp_b0, B.grp_nb, B.grp_maxlen,
+                       B.grp_base, 2 * B.P + 1, B.n, B.fac, B.fac_t, B.gw, B.fac_tf, B.ldsres == 2 ? 4 : 1, d_gcols);
+   return (int) hipGetLastError ();
+}
+
 // Software-pipelined variant for the common shape (f32 factors, columns of at most 64 levels, 8 columns per wave,
 // half bandwidth <= 2).  SQ counters on the one-group-per-wave kernel above: a wave lives ~14 us, 46 % of it parked on
 // the staging loads, and LDS (14.5 KB per wave) caps a CU at 11 waves.  Here a persistent wave walks groups g,

@@ -27,6 +27,9 @@ struct MlLevel {
    int bcur[2] = { 0, 0 };
    double *bxbuf (int k) { return k ? bx2 : bx; }
    double *bxnow () { return bxbuf (bcur[0]); }
+   // host: natural row of this level -> its colour-major row (levels >= 1; level 0 has perm0).  nkp_refactor sums the
+   // Galerkin products in the natural order of the fine level, the order the setup used.
+   std::vector<int> nat_inv;
    double *xbuf (int k) { return k ? x2 : x; }
    double *xnow () { return xbuf (cur[0]); }      // valid when coherent
 };
@@ -50,6 +53,7 @@ struct MlHierarchy {
    double setup_seconds = 0.0;  // wall time of ml_setup
    int levels_on_device = 0;    // levels whose operator was built by the kernels of mlsetup.hip
    int batch_K = 0;             // the level vectors of ml_apply_batch exist for this many right-hand sides
+   int default_build = 0;       // built by the default construction (the one the setup kernels cover): nkp_refactor may keep the cells
 };
 
 // returns 0, or a negative nkp error code with a message in err
@@ -58,6 +62,11 @@ int ml_setup (MlHierarchy &H, int64_t n, const int *rowptr, const int *colind, c
               int tracer_cnt, int max_levels, int nu, int coarsest_rows, int verbose, int rank,
               hipStream_t st, char *err, size_t errlen, const nkp_tuning &tune, const CsrDev *A_dev = nullptr /* device copy of the same matrix, if the caller has one */);
 void ml_free (MlHierarchy &H);
+// dense inverse of the coarsest operator (colour-major host CSR) exactly as ml_setup computes it (blocked elimination, the
+// pivoted routine when a pivot is too small for it); new device buffers, *invf only in f32 storage mode.  0 (blocked), 1 (pivoted
+// routine), -2 (no memory), -4 (singular)
+int ml_coarse_inverse (const MlHierarchy &H, int n, const int *prow, const int *pcol, const double *pval, double **inv, float **invf,
+                       int *ldf, size_t *bytes, hipStream_t st);
 // z = V-cycle(r) in the ORIGINAL row order
 void ml_apply (MlHierarchy &H, const double *r, double *z, hipStream_t st);
 // the same cycle on K interleaved right-hand sides (r, z: n * K doubles, element (row, k) at row * K + k; K = 2 or 4); every

@@ -1120,6 +1120,7 @@ int finalize_host_level (MlHierarchy &H, int l, int nlev, Nat &N, Nat *Cn, int v
    T.up += secs_since (t_up0);
    if (!ok) ML_FAIL (-2, "multilevel setup: device allocation failed at level %d", l);
    if (l == 0 && !upload (&H.perm0, N.perm.data (), (size_t) nl, &H.device_bytes)) ML_FAIL (-2, "multilevel setup: device allocation failed");
+   if (l > 0) V.nat_inv = N.inv;
 
    const int dense_max = H.tune->ml_dense_max;
    // the last level is solved with a dense inverse when it is small enough; otherwise (rough bathymetry can leave
@@ -1164,13 +1165,10 @@ int finalize_host_level (MlHierarchy &H, int l, int nlev, Nat &N, Nat *Cn, int v
       } else {
          // blocked elimination on the matrix cores (dense.hip); a pivot it does not trust sends the level to the pivoted routine
          auto t_inv0 = setup_clk::now ();
-         const int brc = dense_inverse_blocked_device ((int) nl, prow.data (), pcol.data (), pval.data (), &H.coarse_inv, H.f32 ? &H.coarse_invf : nullptr,
-                                                       &H.coarse_ldf, &H.device_bytes, st);
-         if (brc < 0) ML_FAIL (-2, "multilevel setup: device allocation failed (dense inverse of %lld rows)", (long long) nl);
+         const int brc = ml_coarse_inverse (H, (int) nl, prow.data (), pcol.data (), pval.data (), &H.coarse_inv, &H.coarse_invf, &H.coarse_ldf, &H.device_bytes, st);
+         if (brc == -2) ML_FAIL (-2, "multilevel setup: device allocation failed (dense inverse of %lld rows)", (long long) nl);
+         if (brc == -4) ML_FAIL (-4, "multilevel setup: coarsest operator is singular (or the device is out of memory)");
          if (verbose) printf ("(%d) multilevel: dense inverse of %lld rows: %s, %.3f s\n", rank, (long long) nl, brc == 0 ? "blocked elimination" : "a pivot too small for it, pivoted routine instead", secs_since (t_inv0));
-         if (brc > 0) fill_dense ();
-         if (brc > 0 && !dense_inverse_device ((int) nl, dense, &H.coarse_inv, &H.device_bytes, st))
-            ML_FAIL (-4, "multilevel setup: coarsest operator is singular (or the device is out of memory)");
       }
    }
    if (verbose)
@@ -1281,6 +1279,11 @@ int finalize_device_level (MlHierarchy &H, int l, DevLevel &D, Nat &N, const int
       if (!upload (&H.perm0, (const int *) nullptr, (size_t) nl, &H.device_bytes) ||
           hipMemcpyAsync (H.perm0, D.perm, (size_t) nl * sizeof (int), hipMemcpyDeviceToDevice, st) != hipSuccess)
          ML_FAIL (-2, "multilevel setup: device allocation failed");
+   }
+   if (l > 0) {
+      V.nat_inv.resize ((size_t) nl);
+      if (hipMemcpyAsync (V.nat_inv.data (), D.inv, (size_t) nl * sizeof (int), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize (st) != hipSuccess)
+         ML_FAIL (-3, "multilevel setup: download of the colour-major order of level %d failed", l);
    }
    T.up += secs_since (t0);
    const int frc = finish_level_columns (H, V, l, D.pblk, ncol, N.ncol0, nullptr, st, err, errlen, T);
@@ -1477,6 +1480,7 @@ int ml_setup (MlHierarchy &H, int64_t n, const int *rowptr, const int *colind, c
    }
    H.setup_seconds = secs_since (t_begin);
    H.levels_on_device = ndev_levels;
+   H.default_build = device_ok && !tune.ml_host_inverse;
    if (verbose) {
       printf ("(%d) multilevel setup: %d of %d levels built on the device (%.3f s twin, %.3f s coarse cells, %.3f s Galerkin products); host levels: %.3f s twin, %.3f s "
               "column graphs + coarse cells, %.3f s Galerkin products; colour-major operators %.3f s, row blocks %.3f, uploads + f32 copies %.3f, column factors %.3f, "
@@ -1487,6 +1491,21 @@ int ml_setup (MlHierarchy &H, int64_t n, const int *rowptr, const int *colind, c
    return 0;
 }
 #undef ML_FAIL
+
+int ml_coarse_inverse (const MlHierarchy &H, int n, const int *prow, const int *pcol, const double *pval, double **inv, float **invf,
+                       int *ldf, size_t *bytes, hipStream_t st)
+{
+   *inv = nullptr;
+   *invf = nullptr;
+   // blocked elimination on the matrix cores (dense.hip); a pivot it does not trust sends the level to the pivoted routine
+   const int brc = dense_inverse_blocked_device (n, prow, pcol, pval, inv, H.f32 ? invf : nullptr, ldf, bytes, st);
+   if (brc < 0) return -2;
+   if (brc == 0) return 0;
+   std::vector<double> dense ((size_t) n * n, 0.0);
+   for (int64_t i = 0; i < n; i++)
+      for (int e = prow[i]; e < prow[i + 1]; e++) dense[(size_t) i * n + pcol[e]] = pval[e];
+   return dense_inverse_device (n, dense, inv, bytes, st) ? 1 : -4;
+}
 
 void ml_free (MlHierarchy &H)
 {

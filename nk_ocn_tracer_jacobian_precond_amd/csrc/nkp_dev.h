@@ -5,6 +5,8 @@
 
 #include "../../include/nkp.h"
 
+#include <vector>
+
 // the tuning a launcher uses when its object carries none: the plain defaults (no environment)
 const nkp_tuning &nkp_builtin_tuning ();
 
@@ -98,6 +100,11 @@ struct ColBlocksDev {
 // Returns 0 or a HIP error code cast to int.
 int colblock_build_lane_layout (ColBlocksDev &B, const int *h_blk_start, const int *ranges, int nranges,
                                 int *grp_first, size_t *device_bytes, hipStream_t st, int f32 = 0, const int *h_rowptr = nullptr);
+// new factors (B.fac) into the layout built above, which depends on the pattern only (nkp_refactor).  d_gcols: the
+// columns of every group when the groups were formed from sorted columns (colblock_group_columns gives them; an empty
+// list = groups of consecutive columns, pass NULL)
+int colblock_group_columns (const ColBlocksDev &B, std::vector<int> &gcols);
+int colblock_repack_lane_layout (const ColBlocksDev &B, const int *d_gcols, hipStream_t st);
 // one Gauss-Seidel half sweep over the groups [g0, g1) of one colour in ONE launch: r = b - L x on the groups' rows
 // (x rows < split from xa, the others from xb), column solves, xout_rows = x_rows + z.  Returns non-zero (and does
 // nothing) when the level cannot run the fused kernel.

@@ -10,6 +10,7 @@
 #include "../../include/nkp.h"
 #include "nkp_dev.h"
 #include "multilevel.h"
+#include "refactor.h"
 
 #include <math.h>
 #include <stdarg.h>
@@ -19,6 +20,8 @@
 #include <time.h>
 
 #include <algorithm>
+#include <atomic>
+#include <memory>
 #include <string>
 #include <thread>
 #include <vector>
@@ -206,6 +209,20 @@ struct nkp_solver {
    int batch_K = 0;
    size_t device_bytes = 0;
    double create_seconds = 0.0;     // wall time of nkp_create
+   // nkp_refactor: state shared by a solver and its clones (live clones, a refactor that failed after its commit point),
+   // the owner's work space, and the host arrays a rebuild of the hierarchy needs again
+   struct Shared {
+      std::atomic<int> clones { 0 };
+      bool broken = false;
+      std::string why;
+   };
+   std::shared_ptr<Shared> shared = std::make_shared<Shared> ();
+   RefactorWork *rf = nullptr;
+   std::vector<int> h_blk, h_col_i, h_col_j, h_col_t;
+   int tracer_cnt = 1;
+   int64_t refactor_count = 0;
+   int refactor_rebuilt = 0;
+   double refactor_seconds = 0.0;
    double *h_dev () { return dscal; }
    double *h2_dev () { return dscal + (m + 2); }
    double *misc_dev () { return dscal + 2 * (m + 2); }     // [0]=nrm2 [1]=inv [2]=dot out ...
@@ -238,6 +255,7 @@ static void solver_free (nkp_solver *s)
       }
       if (s->hpin) (void) hipHostFree (s->hpin);
       if (s->own_stream && s->stream) (void) hipStreamDestroy (s->stream);
+      s->shared->clones--;
       delete s;
       return;
    }
@@ -250,6 +268,7 @@ static void solver_free (nkp_solver *s)
    for (void *p : ptrs)
       if (p) (void) hipFree (p);
    ml_free (s->ml);
+   if (s->rf) { rf_free (*s->rf); delete s->rf; }
    if (s->dist.send_idx) (void) hipFree (s->dist.send_idx);
    if (s->dist.sendbuf) (void) hipFree (s->dist.sendbuf);
    if (s->dist.xe) (void) hipFree (s->dist.xe);
@@ -570,6 +589,16 @@ static int create_impl (nkp_solver **out, const nkp_options *opt_in, int64_t n, 
    TRYHIP (hipMemset (s->dscal, 0, (size_t) (3 * (m + 2) + 16 + 8) * sizeof (double)));
 
    const double t_work = since0 ();
+   if (opt.precond == NKP_PRECOND_MULTILEVEL && !pm) {
+      // what a rebuild of the hierarchy (nkp_refactor) passes to ml_setup again
+      s->h_blk.assign (blk_start, blk_start + nblk + 1);
+      s->tracer_cnt = coupled_tracer_cnt;
+      if (blk_default.empty ()) {
+         if (opt.col_i) s->h_col_i.assign (opt.col_i, opt.col_i + nblk);
+         if (opt.col_j) s->h_col_j.assign (opt.col_j, opt.col_j + nblk);
+         if (opt.col_t) s->h_col_t.assign (opt.col_t, opt.col_t + nblk);
+      }
+   }
    if (opt.precond == NKP_PRECOND_MULTILEVEL) {
       char err[256] = "";
       // developer switch: build the hierarchy without the couplings between tracers, i.e. exactly the
@@ -749,6 +778,9 @@ extern "C" int64_t nkp_get_int (nkp_solver *s, const char *key)
    if (!strcmp (key, "ml_levels_on_device")) return s->ml.levels_on_device;
    if (!strcmp (key, "ml_setup_us")) return (int64_t) (s->ml.setup_seconds * 1.0e6);
    if (!strcmp (key, "create_us")) return (int64_t) (s->create_seconds * 1.0e6);
+   if (!strcmp (key, "refactor_count")) return s->refactor_count;
+   if (!strcmp (key, "refactor_rebuilt")) return s->refactor_rebuilt;
+   if (!strcmp (key, "refactor_us")) return (int64_t) (s->refactor_seconds * 1.0e6);
    return -1;
 }
 
@@ -1078,8 +1110,11 @@ static int backward_error (nkp_solver *s, double *berr)
    return NKP_OK;
 }
 
+static int refactor_broken (const nkp_solver *s) { return fail (NKP_ESINGULAR, "%s", s->shared->why.c_str ()); }
+
 static int solve_resident (nkp_solver *s, double *berr, int *iters, double *relres)
 {
+   if (s->shared->broken) return refactor_broken (s);
    int it = 0;
    double rr = 0.0;
    s->stagnated = false;
@@ -1135,6 +1170,8 @@ extern "C" int nkp_clone (nkp_solver *src, nkp_solver **out)
    nkp_solver *s = new (std::nothrow) nkp_solver (*src);
    if (!s) return fail (NKP_ENOMEM, "nkp_clone: out of host memory");
    s->borrowed = true;
+   s->rf = nullptr;
+   s->shared->clones++;
    s->stagnated = false;
    s->batch_members.clear ();
    s->bvin = s->bz = s->bw = nullptr;
@@ -1304,6 +1341,7 @@ extern "C" int nkp_solve_batch_device (nkp_solver *s, int nrhs, const void *d_B,
 {
    if (!s || nrhs < 0 || (nrhs > 0 && (!d_B || !d_X))) return fail (NKP_EINVAL, "nkp_solve_batch_device: NULL argument");
    if (nrhs > 0 && ldb < s->n) return fail (NKP_EINVAL, "nkp_solve_batch_device: ldb < n");
+   if (s->shared->broken) return refactor_broken (s);
    HIPCHK (hipSetDevice (s->device));
    const double *B = (const double *) d_B;
    double *X = (double *) d_X;
@@ -1409,6 +1447,168 @@ extern "C" int nkp_solve (nkp_solver *s, double *b_in_x_out, int nrhs, int64_t l
    return worst;
 }
 
+// ---------------------------------------------------------------- new values on the same pattern (refactor.hip)
+// Nothing a solve reads is written before the last check that can refuse the call: the new values are staged and their
+// diagonals checked on the device; then either (fast path) the hierarchy's new values are computed into work buffers and
+// their pattern drift counted, or (rebuild: asked for, drift, or a construction the fast path does not cover) a whole new
+// hierarchy is built beside the old one.  Only then are the matrix, the row scaling and the hierarchy overwritten.
+static int refactor_impl (nkp_solver *s, const double *h_val, const void *d_val, int flags, const char *who)
+{
+   if (!s || (!h_val && !d_val)) return fail (NKP_EINVAL, "%s: NULL argument", who);
+   if (s->borrowed) return fail (NKP_EINVAL, "%s: a clone shares its matrix; refactor the solver it was cloned from", who);
+   if (s->dist.on) return fail (NKP_EINVAL, "%s: not available for the row-distributed flavour (overlap rows would need the neighbours' new values)", who);
+   if (flags & ~NKP_REFACTOR_REBUILD) return fail (NKP_EINVAL, "%s: unknown flags 0x%x", who, flags);
+   HIPCHK (hipSetDevice (s->device));
+   struct timespec ts0;
+   clock_gettime (CLOCK_MONOTONIC, &ts0);
+   const int64_t n = s->n, nnz = s->A.nnz;
+   hipStream_t st = s->stream;
+   HIPCHK (hipStreamSynchronize (st));
+   if (!s->rf) s->rf = new RefactorWork;
+   RefactorWork &W = *s->rf;
+   const bool staged = W.aval != nullptr;
+   if (rf_stage (W, nnz, (int) s->ml.lev.size ()) != 0) return fail (NKP_ENOMEM, "%s: no device memory for the staged values", who);
+   if (!staged) s->device_bytes += ((size_t) nnz + 2) * sizeof (double) + (4 + 2 * 64) * sizeof (int);
+   if (nnz) HIPCHK (hipMemcpyAsync (W.aval, h_val ? (const void *) h_val : d_val, (size_t) nnz * sizeof (double), h_val ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, st));
+   if (s->opt.precond != NKP_PRECOND_NONE) {
+      rf_launch_diag_check (s->A, W.aval, W.dcnt, st);
+      int c[3] = { 0, 0, 0 };
+      HIPCHK (hipMemcpyAsync (c, W.dcnt, sizeof c, hipMemcpyDeviceToHost, st));
+      HIPCHK (hipStreamSynchronize (st));
+      if (c[1]) return fail (NKP_ESINGULAR, "%s: row %d has no (or a zero) diagonal entry (%d such rows); the solver is unchanged", who, c[2] - 1, c[1]);
+   }
+   const bool multilevel = s->opt.precond == NKP_PRECOND_MULTILEVEL;
+   bool rebuild = multilevel && (flags & NKP_REFACTOR_REBUILD);
+   if (multilevel && !rebuild) {
+      // the fast path covers the default construction of the whole matrix (filtered inter-tracer couplings: rebuild)
+      if (s->tune.ml_drop_intertracer && s->tracer_cnt > 1) rebuild = true;
+      if (!rebuild && !W.maps) {
+         const int mrc = rf_build_maps (W, s->ml, s->A, st);
+         if (mrc == 0) s->device_bytes += W.bytes;
+         else {
+            rf_free_maps (W);
+            if (mrc < 0) return fail (mrc == -2 ? NKP_ENOMEM : NKP_EDEVICE, "%s: the value maps of the hierarchy could not be built (%s)", who, mrc == -2 ? "out of device memory" : "HIP failure");
+            rebuild = true;
+         }
+      }
+      if (!rebuild) {
+         rf_values (W, s->ml, s->A, st);
+         int drift = 0;
+         HIPCHK (hipMemcpyAsync (&drift, W.dcnt, sizeof drift, hipMemcpyDeviceToHost, st));
+         HIPCHK (hipStreamSynchronize (st));
+         HIPCHK (hipGetLastError ());
+         if (drift) {
+            msg (s, 1, "%s: %d couplings of the hierarchy appear or vanish with the new values: rebuilding it\n", who, drift);
+            rebuild = true;
+         }
+      }
+      if (!rebuild) {
+         // the coarsest inverse of the new values, before the commit point: a singular operator, or one whose inverse needs
+         // other storage than the clones point at, is refused with the solver unchanged
+         char err[256] = "";
+         const int irc = rf_prepare_inverse (W, s->ml, st, err, sizeof err);
+         if (irc) return fail (irc == -4 ? NKP_ESINGULAR : irc == -2 ? NKP_ENOMEM : NKP_EDEVICE, "%s", err);
+         const int live = s->shared->clones.load () - (int) s->batch_members.size ();
+         if (live > 0 && !rf_inverse_same_storage (W, s->ml)) {
+            rf_drop_inverse (W);
+            return fail (NKP_EINVAL, "%s: the coarsest inverse of the new values needs other storage, which %d live clone(s) would not see; destroy them first", who, live);
+         }
+      }
+   }
+   MlHierarchy H2;
+   if (rebuild) {
+      const int live = s->shared->clones.load () - (int) s->batch_members.size ();
+      if (live > 0) return fail (NKP_EINVAL, "%s: the hierarchy has to be rebuilt, which %d live clone(s) would not see; destroy them first", who, live);
+      std::vector<int32_t> rp ((size_t) n + 1), ci ((size_t) nnz);
+      std::vector<double> v ((size_t) nnz);
+      HIPCHK (hipMemcpy (rp.data (), s->A.rowptr, rp.size () * sizeof (int32_t), hipMemcpyDeviceToHost));
+      if (nnz) {
+         HIPCHK (hipMemcpy (ci.data (), s->A.colind, ci.size () * sizeof (int32_t), hipMemcpyDeviceToHost));
+         HIPCHK (hipMemcpy (v.data (), W.aval, v.size () * sizeof (double), hipMemcpyDeviceToHost));
+      }
+      // nkp_create's filter (developer switch ml_drop_intertracer)
+      std::vector<int32_t> f_rowptr, f_colind;
+      std::vector<double> f_val;
+      const int32_t *rowptr = rp.data (), *colind = ci.data ();
+      const double *val = v.data ();
+      if (s->tune.ml_drop_intertracer && s->tracer_cnt > 1) {
+         const int64_t tsl = n / s->tracer_cnt;
+         f_rowptr.assign ((size_t) n + 1, 0);
+         for (int64_t i = 0; i < n; i++) {
+            for (int32_t e = rowptr[i]; e < rowptr[i + 1]; e++)
+               if (colind[e] / tsl == i / tsl) { f_colind.push_back (colind[e]); f_val.push_back (val[e]); }
+            f_rowptr[(size_t) i + 1] = (int32_t) f_colind.size ();
+         }
+         rowptr = f_rowptr.data ();
+         colind = f_colind.data ();
+         val = f_val.data ();
+      }
+      char err[256] = "";
+      auto opt_ptr = [] (const std::vector<int> &a) { return a.empty () ? nullptr : a.data (); };
+      // the staged values on the device stand in for A's (as A does in nkp_create), so the device passes need no upload
+      CsrDev staged_A = s->A;
+      staged_A.val = W.aval;
+      const int mrc = ml_setup (H2, n, rowptr, colind, val, s->h_blk.data (), (int64_t) s->h_blk.size () - 1, opt_ptr (s->h_col_i), opt_ptr (s->h_col_j), opt_ptr (s->h_col_t),
+                                s->tracer_cnt, s->opt.ml_levels, s->opt.ml_smooth, s->tune.ml_coarsest_rows, s->opt.verbose, s->opt.rank, st, err, sizeof err, s->tune,
+                                f_rowptr.empty () ? &staged_A : nullptr);
+      if (mrc != 0) {
+         (void) hipStreamSynchronize (st);
+         ml_free (H2);
+         (void) hipGetLastError ();
+         return fail (mrc, "%s: %s (the solver is unchanged)", who, err);
+      }
+   }
+
+   // ---- commit point: from here on the solver's own buffers are written
+   if (nnz) HIPCHK (hipMemcpyAsync (s->A.val, W.aval, (size_t) nnz * sizeof (double), hipMemcpyDeviceToDevice, st));
+   if (s->equil) rf_launch_row_scale (s->A, W.aval, s->rscale, s->rinv, st);
+   int rc = 0;
+   char err[256] = "";
+   if (multilevel && rebuild) {
+      for (nkp_solver *c : s->batch_members) solver_free (c);      // they copied the old hierarchy; batch_prepare makes new ones
+      s->batch_members.clear ();
+      (void) hipStreamSynchronize (st);
+      s->device_bytes -= s->ml.device_bytes;
+      ml_free (s->ml);
+      s->ml = H2;
+      s->device_bytes += s->ml.device_bytes;
+      s->device_bytes -= rf_free_maps (W);
+   } else if (multilevel) {
+      int replaced = 0;
+      const size_t before = s->ml.device_bytes;
+      rc = rf_commit (W, s->ml, st, err, sizeof err, &replaced);
+      s->device_bytes += s->ml.device_bytes - before;
+      if (replaced) {                                                 // new coarsest buffers: the batch members copied the old pointers
+         for (nkp_solver *c : s->batch_members) solver_free (c);
+         s->batch_members.clear ();
+      }
+   } else if (s->opt.precond == NKP_PRECOND_COLUMN_JACOBI) {
+      const size_t before = W.bytes;
+      rc = rf_column_factor (W, s->A, s->B, st, err, sizeof err);
+      s->device_bytes += W.bytes - before;
+   }
+   if (hipStreamSynchronize (st) != hipSuccess || hipGetLastError () != hipSuccess) {
+      if (!rc) { rc = -3; snprintf (err, sizeof err, "a HIP call failed"); }
+   }
+   if (rc) {
+      s->shared->broken = true;
+      s->shared->why = std::string (who) + " failed after writing part of the new values (" + err + "); this solver and its clones cannot solve until a refactor succeeds";
+      return fail (rc == -4 ? NKP_ESINGULAR : rc == -2 ? NKP_ENOMEM : NKP_EDEVICE, "%s: %s", who, err);
+   }
+   s->shared->broken = false;
+   s->refactor_count++;
+   s->refactor_rebuilt = rebuild ? 1 : 0;
+   struct timespec ts1;
+   clock_gettime (CLOCK_MONOTONIC, &ts1);
+   s->refactor_seconds = (double) (ts1.tv_sec - ts0.tv_sec) + 1e-9 * (double) (ts1.tv_nsec - ts0.tv_nsec);
+   msg (s, 1, "%s: %s, %.3f s\n", who, rebuild ? "hierarchy rebuilt" : "coarse cells kept", s->refactor_seconds);
+   return NKP_OK;
+}
+
+extern "C" int nkp_refactor (nkp_solver *s, const double *val, int flags) { return refactor_impl (s, val, nullptr, flags, "nkp_refactor"); }
+
+extern "C" int nkp_refactor_device (nkp_solver *s, const void *d_val, int flags) { return refactor_impl (s, nullptr, d_val, flags, "nkp_refactor_device"); }
+
 // ---------------------------------------------------------------- exposed pieces (parity / roofline)
 extern "C" int nkp_spmv_device (nkp_solver *s, const void *d_x, void *d_y)
 {
@@ -1436,6 +1636,7 @@ extern "C" int nkp_spmv (nkp_solver *s, const double *x, double *y)
 extern "C" int nkp_precond_apply (nkp_solver *s, const double *r, double *z)
 {
    if (!s || !r || !z) return fail (NKP_EINVAL, "nkp_precond_apply: NULL argument");
+   if (s->shared->broken) return refactor_broken (s);
    HIPCHK (hipSetDevice (s->device));
    const size_t bytes = (size_t) s->n * sizeof (double);
    HIPCHK (hipMemcpyAsync (s->t1, r, bytes, hipMemcpyHostToDevice, s->stream));

@@ -19,6 +19,7 @@ HOST_LIB_PATH = os.path.join(_HERE, "host", "libnkp_host.so")
 PRECOND_NONE, PRECOND_COLUMN_JACOBI, PRECOND_MULTILEVEL = 0, 1, 3
 KRYLOV_FGMRES, KRYLOV_BICGSTAB = 0, 1
 NKP_OK, NKP_NOT_CONVERGED, NKP_BREAKDOWN, NKP_OK_BERR = 0, 1, 2, 3
+REFACTOR_REBUILD = 1
 
 # every symbol include/nkp.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = [
@@ -29,6 +30,7 @@ ABI_SYMBOLS = [
     "nkp_gather_root", "nkp_clone", "nkp_ml_plan_host", "nkp_comm_file_init", "nkp_comm_file_free",
     "nkp_create64", "nkp_cell_major_order", "nkp_permuted_rows", "nkp_dist_overlap_plan_host", "nkp_dist_plan_size",
     "nkp_dist_plan_copy", "nkp_dist_plan_free", "nkp_ml_level_array", "nkp_default_tuning", "nkp_solve_batch_device",
+    "nkp_refactor", "nkp_refactor_device",
 ]
 
 _ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p)
@@ -120,6 +122,8 @@ def load_library(path=None):
     lib.nkp_set_device.argtypes = [C.c_int]
     lib.nkp_gather_root.argtypes = [vp, f64p, f64p]
     lib.nkp_clone.argtypes = [vp, C.POINTER(vp)]
+    lib.nkp_refactor.argtypes = [vp, f64p, C.c_int]
+    lib.nkp_refactor_device.argtypes = [vp, vp, C.c_int]
     lib.nkp_dist_plan_host.argtypes = [C.c_int64, C.c_int64, i32p, i32p, C.c_int, C.c_int, C.POINTER(C.c_int64), i32p, i32p,
                                        C.POINTER(C.c_int64), i32p]
     lib.nkp_ml_plan_host.argtypes = [C.c_int64, i32p, i32p, f64p, i32p, C.c_int64, i32p, i32p, C.c_int, C.c_int, C.c_int, C.c_int64,
@@ -321,6 +325,19 @@ class NkpSolver:
         rc = self._lib.nkp_solve(self._h, _p(X, C.c_double), nrhs, X.shape[1], berr, iters, relres)
         self._check(rc, (0,) if raise_on_fail else (0, 1, 2, 3))
         return X, [dict(status=rc, iters=iters[c], relres=relres[c], berr=berr[c]) for c in range(nrhs)]
+
+    def refactor(self, val, rebuild=False):
+        """nkp_refactor: new values (nnz, in the CSR order the solver was created with) on the same pattern.  The hierarchy keeps
+        its coarse cells unless rebuild=True or the new values add or remove a coupling it stores; get_int("refactor_rebuilt")
+        tells which happened."""
+        val = np.ascontiguousarray(val, np.float64).reshape(-1)
+        if val.size != self.nnz:
+            raise ValueError(f"val has {val.size} entries, expected {self.nnz}")
+        self._check(self._lib.nkp_refactor(self._h, _p(val, C.c_double), REFACTOR_REBUILD if rebuild else 0))
+
+    def refactor_device(self, d_val, rebuild=False):
+        """nkp_refactor_device: d_val = integer device address (e.g. torch tensor .data_ptr()) of nnz float64 on the solver's device."""
+        self._check(self._lib.nkp_refactor_device(self._h, C.c_void_p(d_val), REFACTOR_REBUILD if rebuild else 0))
 
     def spmv(self, x):
         x = np.ascontiguousarray(x, np.float64)
