@@ -264,7 +264,8 @@ int64_t nkp_get_int (nkp_solver *s, const char *key);
  *   flags = NKP_REFACTOR_REBUILD: rebuild the hierarchy (coarse cells included) on the new values inside the same
  *     solver; work vectors, stream and the SpMV's row blocks and codes are kept.  Bit for bit nkp_create(val).
  * nkp_get_int: "refactor_count", "refactor_rebuilt" (1 if the last call rebuilt the hierarchy), "refactor_us".
- * Returns 0, NKP_EINVAL (NULL argument, a clone, the row-distributed flavour, a rebuild while clones are alive),
+ * Returns 0, NKP_EINVAL (NULL argument, a clone, the row-distributed flavour: use nkp_refactor_dist there, a rebuild
+ * while clones are alive),
  * NKP_ESINGULAR (a zero or missing diagonal: the solver is unchanged), NKP_ENOMEM / NKP_EDEVICE.  An error before
  * any value is written leaves the solver solving exactly as before; a zero pivot met while factoring the new values
  * leaves it unusable (every later solve returns NKP_ESINGULAR naming the failed refactor).  No solve may be in
@@ -272,6 +273,33 @@ int64_t nkp_get_int (nkp_solver *s, const char *key);
 #define NKP_REFACTOR_REBUILD 1
 int nkp_refactor (nkp_solver *s, const double *val, int flags);
 int nkp_refactor_device (nkp_solver *s, const void *d_val, int flags);
+
+/* nkp_refactor for the row-distributed flavour (nkp_create_dist).  COLLECTIVE: every rank calls it with its own slice.
+ * val_loc holds this rank's nnz_loc values in the order of the rowptr_loc / colind_glob it passed to nkp_create_dist (same
+ * pattern); d_val_loc is the same array on the solver's device.  flags as for nkp_refactor (0 or NKP_REFACTOR_REBUILD).
+ * The reference rebuilds its distributed matrix around pdgssvx (src/solve_ABdist.c:482-483, 539, 571); with these calls a
+ * Newton-Krylov driver keeps its solver on every rank and hands it the next Jacobian.
+ *   Each rank refreshes its SpMV matrix, its row scaling (equil), its column-block factors (column Jacobi) and its
+ *   hierarchy.  The hierarchy's matrix is the diagonal block without overlap, or the [own rows | overlap rows] matrix of
+ *   restricted additive Schwarz: the overlap rows' new values come from their owners through ONE alltoallv of device doubles
+ *   on the solver's stream.  With flags = 0 the values are recomputed on the kept coarse cells, bit for bit what
+ *   nkp_create_dist builds from the new values whenever it picks the same cells; drift in a rank's own or overlap rows, or
+ *   NKP_REFACTOR_REBUILD, rebuilds that rank's hierarchy (hierarchies are rank-local, so only the ranks concerned rebuild).
+ *   The maps that tie every value to its slot are kept by nkp_create_dist in host memory and uploaded by the first call
+ *   (counted in "device_bytes"); after that a device-value call moves no values through the host but the coarsest level's
+ *   (dense inverse) and whatever the transport itself stages.
+ *   The callbacks of nkp_comm_ops are reached in the same order on every rank (allgather_i64_host, alltoallv when any rank
+ *   has overlap rows, allgather_i64_host, allgather_i64_host), whatever path each rank takes locally.
+ * nkp_get_int (per rank): "refactor_count", "refactor_rebuilt", "refactor_us", and "refactor_halo_values" (values this rank
+ * received in the last call's overlap exchange, 0 without overlap).
+ * Returns the codes of nkp_refactor plus NKP_ECOMM, and all ranks agree on success or failure: a rank whose own check fails
+ * returns its own code and message (NKP_ESINGULAR for a zero diagonal in its rows, ...), every other rank NKP_ECOMM naming
+ * the failed rank.  A failure before the commit point leaves every rank's solver exactly as it was; one after it leaves
+ * every rank's solver unusable until a later call succeeds.  A NULL handle or NULL values are refused at once on the calling
+ * rank, before any collective.  On a solver nkp_create_dist made for one rank without force_dist (a plain solver) the calls
+ * are nkp_refactor / nkp_refactor_device.  No solve may be in flight on the solver during the call. */
+int nkp_refactor_dist (nkp_solver *s, const double *val_loc, int flags);
+int nkp_refactor_dist_device (nkp_solver *s, const void *d_val_loc, int flags);
 
 /* Use an externally owned HIP stream (hipStream_t cast to void*) instead of the solver's own;
  * NULL = the device's default stream. */

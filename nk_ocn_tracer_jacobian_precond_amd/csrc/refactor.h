@@ -42,8 +42,9 @@ void rf_launch_row_scale (const CsrDev &A, const double *val, double *rscale, do
 // the maps of the fast path (host work + uploads, once per hierarchy); 0, -2 (no memory), -3 (HIP failure), 1 (the hierarchy is
 // not one the fast path covers)
 int rf_build_maps (RefactorWork &W, const MlHierarchy &H, const CsrDev &A, hipStream_t st);
-// twin and Galerkin values of every level from W.aval into W.lev[l].nv; pattern drift counted into W.dcnt[0] (enqueued only)
-void rf_values (RefactorWork &W, const MlHierarchy &H, const CsrDev &A, hipStream_t st);
+// twin and Galerkin values of every level from the values val of A (the matrix the hierarchy was built from) into
+// W.lev[l].nv; pattern drift counted into W.dcnt[0] (enqueued only)
+void rf_values (RefactorWork &W, const MlHierarchy &H, const CsrDev &A, const double *val, hipStream_t st);
 // dense inverse of the new coarsest operator into W.inv_new / invf_new (before the commit point); 0, -4 (singular), -2 / -3
 int rf_prepare_inverse (RefactorWork &W, const MlHierarchy &H, hipStream_t st, char *err, size_t errlen);
 // the prepared inverse fits the buffers the hierarchy (and its clones) point at
@@ -54,3 +55,31 @@ void rf_drop_inverse (RefactorWork &W);
 int rf_commit (RefactorWork &W, MlHierarchy &H, hipStream_t st, char *err, size_t errlen, int *replaced);
 // column-block preconditioner: factors of A (new values already in A.val) + their lane layout; 0 or -4 (zero pivot, row in err)
 int rf_column_factor (RefactorWork &W, const CsrDev &A, ColBlocksDev &B, hipStream_t st, char *err, size_t errlen);
+
+// nkp_refactor_dist (refactor_dist.hip): where every value of a distributed rank's hierarchy source comes from.  The source is
+// the diagonal block (no overlap) or the [own rows | overlap rows] matrix of restricted additive Schwarz; nkp_create_dist keeps
+// this plan in host memory, the first nkp_refactor_dist uploads it.
+struct DistRefactorPlan {
+   int64_t n_src = 0, nnz_src = 0;               // rows / entries of the hierarchy's source matrix
+   std::vector<int32_t> src_rowptr, src_colind;  // its pattern on the host until the first refactor uploads it (then read back)
+   std::vector<int32_t> origin;                  // [nnz_src] >= 0: own local entry e (caller's order); < 0: -1 - position in the received overlap values
+   std::vector<int32_t> ship;                    // own local entries of the overlap rows this rank ships, in shipping order
+   std::vector<int> ship_counts, recv_counts;    // values per rank sent / received (restricted additive Schwarz only)
+   int64_t n_recv = 0;
+   bool exchange = false;                        // the source has overlap rows somewhere: every rank takes part in the value exchange
+   // device, from the first nkp_refactor_dist on
+   bool uploaded = false;
+   CsrDev src;                                   // pattern of the source (val unused)
+   double *sval = nullptr;                       // [nnz_src] its new values
+   double *sendbuf = nullptr, *recvbuf = nullptr;
+   int *d_origin = nullptr, *d_ship = nullptr;
+   size_t bytes = 0;                             // device bytes of the above (counted in the solver's device_bytes)
+};
+
+// device copies of the plan; 0 or -2 (no memory) / -3 (HIP failure).  The host pattern is released once uploaded.
+int rf_dist_upload (DistRefactorPlan &Q, hipStream_t st);
+void rf_dist_free (DistRefactorPlan &Q);
+// sendbuf[k] = aval[ship[k]]
+void rf_dist_launch_pack (const DistRefactorPlan &Q, const double *aval, hipStream_t st);
+// sval[k] = origin[k] >= 0 ? aval[origin[k]] : recvbuf[-1 - origin[k]]
+void rf_dist_launch_assemble (const DistRefactorPlan &Q, const double *aval, hipStream_t st);

@@ -353,10 +353,10 @@ int rf_build_maps (RefactorWork &W, const MlHierarchy &H, const CsrDev &A, hipSt
    return 0;
 }
 
-void rf_values (RefactorWork &W, const MlHierarchy &H, const CsrDev &A, hipStream_t st)
+void rf_values (RefactorWork &W, const MlHierarchy &H, const CsrDev &A, const double *val, hipStream_t st)
 {
    (void) hipMemsetAsync (W.dcnt, 0, sizeof (int), st);
-   if (A.n) hipLaunchKernelGGL (rf_twin_kernel, rows_grid (A.n), dim3 (RF_T), 0, st, A.n, A.rowptr, A.colind, (const double *) W.aval, (const int *) W.tslot, W.lev[0].nv, W.dcnt);
+   if (A.n) hipLaunchKernelGGL (rf_twin_kernel, rows_grid (A.n), dim3 (RF_T), 0, st, A.n, A.rowptr, A.colind, val, (const int *) W.tslot, W.lev[0].nv, W.dcnt);
    for (size_t l = 1; l < H.lev.size (); l++) {
       const MlLevel &V = H.lev[l];
       const RefactorWork::Lev &L = W.lev[l];

@@ -223,6 +223,9 @@ struct nkp_solver {
    int64_t refactor_count = 0;
    int refactor_rebuilt = 0;
    double refactor_seconds = 0.0;
+   // nkp_refactor_dist: where the values of the hierarchy's source come from (kept by nkp_create_dist, multilevel only)
+   DistRefactorPlan *dplan = nullptr;
+   int64_t refactor_halo_values = 0;
    double *h_dev () { return dscal; }
    double *h2_dev () { return dscal + (m + 2); }
    double *misc_dev () { return dscal + 2 * (m + 2); }     // [0]=nrm2 [1]=inv [2]=dot out ...
@@ -269,6 +272,7 @@ static void solver_free (nkp_solver *s)
       if (p) (void) hipFree (p);
    ml_free (s->ml);
    if (s->rf) { rf_free (*s->rf); delete s->rf; }
+   if (s->dplan) { rf_dist_free (*s->dplan); delete s->dplan; }
    if (s->dist.send_idx) (void) hipFree (s->dist.send_idx);
    if (s->dist.sendbuf) (void) hipFree (s->dist.sendbuf);
    if (s->dist.xe) (void) hipFree (s->dist.xe);
@@ -781,6 +785,7 @@ extern "C" int64_t nkp_get_int (nkp_solver *s, const char *key)
    if (!strcmp (key, "refactor_count")) return s->refactor_count;
    if (!strcmp (key, "refactor_rebuilt")) return s->refactor_rebuilt;
    if (!strcmp (key, "refactor_us")) return (int64_t) (s->refactor_seconds * 1.0e6);
+   if (!strcmp (key, "refactor_halo_values")) return s->refactor_halo_values;
    return -1;
 }
 
@@ -1448,6 +1453,79 @@ extern "C" int nkp_solve (nkp_solver *s, double *b_in_x_out, int nrhs, int64_t l
 }
 
 // ---------------------------------------------------------------- new values on the same pattern (refactor.hip)
+// A new hierarchy H2 from a host copy of the matrix the hierarchy is built from, with new values, exactly as nkp_create builds
+// it (with its inter-tracer filter when `filter`; dev = a device copy of the unfiltered matrix, or NULL).  0 or an nkp error
+// code with the message in err; H2 is empty on failure.
+static int rebuild_hierarchy (nkp_solver *s, MlHierarchy &H2, int64_t n, const int32_t *rowptr, const int32_t *colind, const double *val, bool filter,
+                              const CsrDev *dev, char *err, size_t errlen)
+{
+   // nkp_create's filter (developer switch ml_drop_intertracer)
+   std::vector<int32_t> f_rowptr, f_colind;
+   std::vector<double> f_val;
+   if (filter) {
+      const int64_t tsl = n / s->tracer_cnt;
+      f_rowptr.assign ((size_t) n + 1, 0);
+      for (int64_t i = 0; i < n; i++) {
+         for (int32_t e = rowptr[i]; e < rowptr[i + 1]; e++)
+            if (colind[e] / tsl == i / tsl) { f_colind.push_back (colind[e]); f_val.push_back (val[e]); }
+         f_rowptr[(size_t) i + 1] = (int32_t) f_colind.size ();
+      }
+      rowptr = f_rowptr.data ();
+      colind = f_colind.data ();
+      val = f_val.data ();
+   }
+   auto opt_ptr = [] (const std::vector<int> &a) { return a.empty () ? nullptr : a.data (); };
+   const int mrc = ml_setup (H2, n, rowptr, colind, val, s->h_blk.data (), (int64_t) s->h_blk.size () - 1, opt_ptr (s->h_col_i), opt_ptr (s->h_col_j), opt_ptr (s->h_col_t),
+                             s->tracer_cnt, s->opt.ml_levels, s->opt.ml_smooth, s->tune.ml_coarsest_rows, s->opt.verbose, s->opt.rank, s->stream, err, errlen, s->tune,
+                             f_rowptr.empty () ? dev : nullptr);
+   if (mrc != 0) {
+      (void) hipStreamSynchronize (s->stream);
+      ml_free (H2);
+      (void) hipGetLastError ();
+   }
+   return mrc;
+}
+
+// Everything after the commit point but A's values (already copied from W.aval): row scaling, the hierarchy (rebuild: H2
+// replaces it; otherwise rf_commit writes the prepared values), the column factors.  0 or -2 / -3 / -4 with a message in err.
+static int refactor_commit (nkp_solver *s, bool rebuilt, MlHierarchy &H2, char *err, size_t errlen)
+{
+   RefactorWork &W = *s->rf;
+   hipStream_t st = s->stream;
+   const bool multilevel = s->opt.precond == NKP_PRECOND_MULTILEVEL;
+   if (s->equil) rf_launch_row_scale (s->A, W.aval, s->rscale, s->rinv, st);
+   int rc = 0;
+   if (multilevel && rebuilt) {
+      for (nkp_solver *c : s->batch_members) solver_free (c);      // they copied the old hierarchy; batch_prepare makes new ones
+      s->batch_members.clear ();
+      (void) hipStreamSynchronize (st);
+      s->device_bytes -= s->ml.device_bytes;
+      ml_free (s->ml);
+      s->ml = H2;
+      s->device_bytes += s->ml.device_bytes;
+      s->device_bytes -= rf_free_maps (W);
+   } else if (multilevel) {
+      int replaced = 0;
+      const size_t before = s->ml.device_bytes;
+      rc = rf_commit (W, s->ml, st, err, errlen, &replaced);
+      s->device_bytes += s->ml.device_bytes - before;
+      if (replaced) {                                                 // new coarsest buffers: the batch members copied the old pointers
+         for (nkp_solver *c : s->batch_members) solver_free (c);
+         s->batch_members.clear ();
+      }
+   } else if (s->opt.precond == NKP_PRECOND_COLUMN_JACOBI) {
+      // the distributed flavour's A also holds the halo columns: they lie outside every water-column block, and the factor
+      // kernel skips columns outside the block (colblock_factor_kernel), as it did in nkp_create_dist
+      const size_t before = W.bytes;
+      rc = rf_column_factor (W, s->A, s->B, st, err, errlen);
+      s->device_bytes += W.bytes - before;
+   }
+   if (hipStreamSynchronize (st) != hipSuccess || hipGetLastError () != hipSuccess) {
+      if (!rc) { rc = -3; snprintf (err, errlen, "a HIP call failed"); }
+   }
+   return rc;
+}
+
 // Nothing a solve reads is written before the last check that can refuse the call: the new values are staged and their
 // diagonals checked on the device; then either (fast path) the hierarchy's new values are computed into work buffers and
 // their pattern drift counted, or (rebuild: asked for, drift, or a construction the fast path does not cover) a whole new
@@ -1456,7 +1534,7 @@ static int refactor_impl (nkp_solver *s, const double *h_val, const void *d_val,
 {
    if (!s || (!h_val && !d_val)) return fail (NKP_EINVAL, "%s: NULL argument", who);
    if (s->borrowed) return fail (NKP_EINVAL, "%s: a clone shares its matrix; refactor the solver it was cloned from", who);
-   if (s->dist.on) return fail (NKP_EINVAL, "%s: not available for the row-distributed flavour (overlap rows would need the neighbours' new values)", who);
+   if (s->dist.on) return fail (NKP_EINVAL, "%s: not available for the row-distributed flavour; every rank calls nkp_refactor_dist instead", who);
    if (flags & ~NKP_REFACTOR_REBUILD) return fail (NKP_EINVAL, "%s: unknown flags 0x%x", who, flags);
    HIPCHK (hipSetDevice (s->device));
    struct timespec ts0;
@@ -1492,7 +1570,7 @@ static int refactor_impl (nkp_solver *s, const double *h_val, const void *d_val,
          }
       }
       if (!rebuild) {
-         rf_values (W, s->ml, s->A, st);
+         rf_values (W, s->ml, s->A, W.aval, st);
          int drift = 0;
          HIPCHK (hipMemcpyAsync (&drift, W.dcnt, sizeof drift, hipMemcpyDeviceToHost, st));
          HIPCHK (hipStreamSynchronize (st));
@@ -1526,70 +1604,18 @@ static int refactor_impl (nkp_solver *s, const double *h_val, const void *d_val,
          HIPCHK (hipMemcpy (ci.data (), s->A.colind, ci.size () * sizeof (int32_t), hipMemcpyDeviceToHost));
          HIPCHK (hipMemcpy (v.data (), W.aval, v.size () * sizeof (double), hipMemcpyDeviceToHost));
       }
-      // nkp_create's filter (developer switch ml_drop_intertracer)
-      std::vector<int32_t> f_rowptr, f_colind;
-      std::vector<double> f_val;
-      const int32_t *rowptr = rp.data (), *colind = ci.data ();
-      const double *val = v.data ();
-      if (s->tune.ml_drop_intertracer && s->tracer_cnt > 1) {
-         const int64_t tsl = n / s->tracer_cnt;
-         f_rowptr.assign ((size_t) n + 1, 0);
-         for (int64_t i = 0; i < n; i++) {
-            for (int32_t e = rowptr[i]; e < rowptr[i + 1]; e++)
-               if (colind[e] / tsl == i / tsl) { f_colind.push_back (colind[e]); f_val.push_back (val[e]); }
-            f_rowptr[(size_t) i + 1] = (int32_t) f_colind.size ();
-         }
-         rowptr = f_rowptr.data ();
-         colind = f_colind.data ();
-         val = f_val.data ();
-      }
       char err[256] = "";
-      auto opt_ptr = [] (const std::vector<int> &a) { return a.empty () ? nullptr : a.data (); };
       // the staged values on the device stand in for A's (as A does in nkp_create), so the device passes need no upload
       CsrDev staged_A = s->A;
       staged_A.val = W.aval;
-      const int mrc = ml_setup (H2, n, rowptr, colind, val, s->h_blk.data (), (int64_t) s->h_blk.size () - 1, opt_ptr (s->h_col_i), opt_ptr (s->h_col_j), opt_ptr (s->h_col_t),
-                                s->tracer_cnt, s->opt.ml_levels, s->opt.ml_smooth, s->tune.ml_coarsest_rows, s->opt.verbose, s->opt.rank, st, err, sizeof err, s->tune,
-                                f_rowptr.empty () ? &staged_A : nullptr);
-      if (mrc != 0) {
-         (void) hipStreamSynchronize (st);
-         ml_free (H2);
-         (void) hipGetLastError ();
-         return fail (mrc, "%s: %s (the solver is unchanged)", who, err);
-      }
+      const int mrc = rebuild_hierarchy (s, H2, n, rp.data (), ci.data (), v.data (), s->tune.ml_drop_intertracer && s->tracer_cnt > 1, &staged_A, err, sizeof err);
+      if (mrc != 0) return fail (mrc, "%s: %s (the solver is unchanged)", who, err);
    }
 
    // ---- commit point: from here on the solver's own buffers are written
    if (nnz) HIPCHK (hipMemcpyAsync (s->A.val, W.aval, (size_t) nnz * sizeof (double), hipMemcpyDeviceToDevice, st));
-   if (s->equil) rf_launch_row_scale (s->A, W.aval, s->rscale, s->rinv, st);
-   int rc = 0;
    char err[256] = "";
-   if (multilevel && rebuild) {
-      for (nkp_solver *c : s->batch_members) solver_free (c);      // they copied the old hierarchy; batch_prepare makes new ones
-      s->batch_members.clear ();
-      (void) hipStreamSynchronize (st);
-      s->device_bytes -= s->ml.device_bytes;
-      ml_free (s->ml);
-      s->ml = H2;
-      s->device_bytes += s->ml.device_bytes;
-      s->device_bytes -= rf_free_maps (W);
-   } else if (multilevel) {
-      int replaced = 0;
-      const size_t before = s->ml.device_bytes;
-      rc = rf_commit (W, s->ml, st, err, sizeof err, &replaced);
-      s->device_bytes += s->ml.device_bytes - before;
-      if (replaced) {                                                 // new coarsest buffers: the batch members copied the old pointers
-         for (nkp_solver *c : s->batch_members) solver_free (c);
-         s->batch_members.clear ();
-      }
-   } else if (s->opt.precond == NKP_PRECOND_COLUMN_JACOBI) {
-      const size_t before = W.bytes;
-      rc = rf_column_factor (W, s->A, s->B, st, err, sizeof err);
-      s->device_bytes += W.bytes - before;
-   }
-   if (hipStreamSynchronize (st) != hipSuccess || hipGetLastError () != hipSuccess) {
-      if (!rc) { rc = -3; snprintf (err, sizeof err, "a HIP call failed"); }
-   }
+   int rc = refactor_commit (s, multilevel && rebuild, H2, err, sizeof err);
    if (rc) {
       s->shared->broken = true;
       s->shared->why = std::string (who) + " failed after writing part of the new values (" + err + "); this solver and its clones cannot solve until a refactor succeeds";
@@ -1608,6 +1634,169 @@ static int refactor_impl (nkp_solver *s, const double *h_val, const void *d_val,
 extern "C" int nkp_refactor (nkp_solver *s, const double *val, int flags) { return refactor_impl (s, val, nullptr, flags, "nkp_refactor"); }
 
 extern "C" int nkp_refactor_device (nkp_solver *s, const void *d_val, int flags) { return refactor_impl (s, nullptr, d_val, flags, "nkp_refactor_device"); }
+
+// ---------------------------------------------------------------- new values on a row-distributed solver (refactor_dist.hip)
+// Collective.  Every rank stages its own rows' values and checks them; the overlap rows of restricted additive Schwarz get their
+// values from their owners through one alltoallv of device doubles; then each rank runs the single-GPU value passes (or a
+// rebuild) on its hierarchy's source matrix.  Three agreements through allgather_i64_host keep the ranks together:
+//   (a) arguments, staged values, own diagonals, device maps      a failure anywhere: every rank unchanged
+//   (b) new values of the hierarchy, drift, coarsest inverse, or a rebuilt hierarchy beside the old one: the same
+//   (c) the commit                                                a failure anywhere: every rank's solver unusable
+// A rank whose own step failed returns its code and message, every other rank NKP_ECOMM naming it.  The callbacks are reached
+// in the same order on every rank (allgather, [alltoallv], allgather, allgather) whatever path each rank takes locally.
+static int dist_agree (nkp_solver *s, int local_rc, const char *who, const char *where)
+{
+   const nkp_comm_ops &c = s->dist.ops;
+   std::vector<int64_t> all ((size_t) c.nranks + 1, 0);
+   const std::string mine = local_rc ? g_last_error : std::string ();
+   const bool comm_ok = c.allgather_i64_host (c.ctx, local_rc ? 1 : 0, all.data ()) == 0;
+   if (local_rc) { g_last_error = mine; return local_rc; }
+   if (!comm_ok) return fail (NKP_ECOMM, "%s: allgather failed (%s)", who, where);
+   for (int p = 0; p < c.nranks; p++)
+      if (all[(size_t) p]) return fail (NKP_ECOMM, "%s: rank %d failed (%s); see its message", who, p, where);
+   return NKP_OK;
+}
+
+static int refactor_dist_impl (nkp_solver *s, const double *h_val, const void *d_val, int flags, const char *who)
+{
+   if (!s || (!h_val && !d_val)) return fail (NKP_EINVAL, "%s: NULL argument", who);
+   if (!s->dist.on) return refactor_impl (s, h_val, d_val, flags, who);      // nkp_create_dist made a plain solver
+   struct timespec ts0;
+   clock_gettime (CLOCK_MONOTONIC, &ts0);
+   const int64_t nnz = s->A.nnz;
+   hipStream_t st = s->stream;
+   const bool multilevel = s->opt.precond == NKP_PRECOND_MULTILEVEL;
+   DistRefactorPlan *Q = s->dplan;
+   if (!s->rf) s->rf = new RefactorWork;
+   RefactorWork &W = *s->rf;
+
+   // ---- (a) this rank's arguments, its staged values and their diagonals, the device copies of the plan
+   int rc = [&] () -> int {
+      if (flags & ~NKP_REFACTOR_REBUILD) return fail (NKP_EINVAL, "%s: unknown flags 0x%x", who, flags);
+      if (multilevel && !Q) return fail (NKP_EINVAL, "%s: the solver kept no plan of its hierarchy's matrix", who);
+      HIPCHK (hipSetDevice (s->device));
+      HIPCHK (hipStreamSynchronize (st));
+      const bool staged = W.aval != nullptr;
+      if (rf_stage (W, nnz, (int) s->ml.lev.size ()) != 0) return fail (NKP_ENOMEM, "%s: no device memory for the staged values", who);
+      if (!staged) s->device_bytes += ((size_t) nnz + 2) * sizeof (double) + (4 + 2 * 64) * sizeof (int);
+      if (nnz) HIPCHK (hipMemcpyAsync (W.aval, h_val ? (const void *) h_val : d_val, (size_t) nnz * sizeof (double), h_val ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, st));
+      if (s->opt.precond != NKP_PRECOND_NONE) {
+         // own rows only: the halo columns (>= m_loc) are never a diagonal; an overlap row's diagonal is checked by its owner
+         rf_launch_diag_check (s->A, W.aval, W.dcnt, st);
+         int c[3] = { 0, 0, 0 };
+         HIPCHK (hipMemcpyAsync (c, W.dcnt, sizeof c, hipMemcpyDeviceToHost, st));
+         HIPCHK (hipStreamSynchronize (st));
+         if (c[1]) return fail (NKP_ESINGULAR, "%s: row %lld (global) has no (or a zero) diagonal entry (%d such rows on rank %d); no rank's solver is changed", who,
+                                (long long) (s->dist.fst + c[2] - 1), c[1], s->dist.ops.rank);
+      }
+      if (multilevel && !Q->uploaded) {
+         const int urc = rf_dist_upload (*Q, st);
+         if (urc) return fail (urc == -2 ? NKP_ENOMEM : NKP_EDEVICE, "%s: the value maps of the hierarchy's matrix could not be uploaded", who);
+         s->device_bytes += Q->bytes;
+      }
+      return NKP_OK;
+   } ();
+   if ((rc = dist_agree (s, rc, who, "arguments and own diagonals"))) return rc;
+
+   // ---- (b) the overlap values from their owners, then the hierarchy's new values beside the current ones
+   bool rebuild = multilevel && (flags & NKP_REFACTOR_REBUILD);
+   MlHierarchy H2;
+   bool built = false;
+   int64_t halo_values = 0;
+   if (multilevel) {
+      if (Q->exchange) {
+         rf_dist_launch_pack (*Q, W.aval, st);
+         if (s->dist.ops.alltoallv (s->dist.ops.ctx, Q->sendbuf, Q->ship_counts.data (), Q->recvbuf, Q->recv_counts.data (), (void *) st))
+            rc = fail (NKP_ECOMM, "%s: the exchange of the overlap values failed", who);
+         halo_values = Q->n_recv;
+      }
+      if (!rc) rc = [&] () -> int {
+         rf_dist_launch_assemble (*Q, W.aval, st);
+         // nkp_create's inter-tracer filter (developer switch) applies to the diagonal block only; its hierarchy is always rebuilt
+         const bool filtered = s->tune.ml_drop_intertracer && s->tracer_cnt > 1 && !s->dist.ras;
+         if (filtered) rebuild = true;
+         if (!rebuild && !W.maps) {
+            const int mrc = rf_build_maps (W, s->ml, Q->src, st);
+            if (mrc == 0) s->device_bytes += W.bytes;
+            else {
+               rf_free_maps (W);
+               if (mrc < 0) return fail (mrc == -2 ? NKP_ENOMEM : NKP_EDEVICE, "%s: the value maps of the hierarchy could not be built (%s)", who, mrc == -2 ? "out of device memory" : "HIP failure");
+               rebuild = true;
+            }
+         }
+         if (!rebuild) {
+            rf_values (W, s->ml, Q->src, Q->sval, st);
+            int drift = 0;
+            HIPCHK (hipMemcpyAsync (&drift, W.dcnt, sizeof drift, hipMemcpyDeviceToHost, st));
+            HIPCHK (hipStreamSynchronize (st));
+            HIPCHK (hipGetLastError ());
+            if (drift) {
+               msg (s, 1, "%s: %d couplings of this rank's hierarchy appear or vanish with the new values: rebuilding it\n", who, drift);
+               rebuild = true;
+            }
+         }
+         if (!rebuild) {
+            char err[256] = "";
+            const int irc = rf_prepare_inverse (W, s->ml, st, err, sizeof err);
+            if (irc) return fail (irc == -4 ? NKP_ESINGULAR : irc == -2 ? NKP_ENOMEM : NKP_EDEVICE, "%s", err);
+            return NKP_OK;
+         }
+         // rebuild: the hierarchy's matrix read back from the device, as nkp_create_dist passed it to ml_setup
+         std::vector<int32_t> rp ((size_t) Q->n_src + 1), ci ((size_t) Q->nnz_src);
+         std::vector<double> v ((size_t) Q->nnz_src);
+         HIPCHK (hipStreamSynchronize (st));
+         HIPCHK (hipMemcpy (rp.data (), Q->src.rowptr, rp.size () * sizeof (int32_t), hipMemcpyDeviceToHost));
+         if (Q->nnz_src) {
+            HIPCHK (hipMemcpy (ci.data (), Q->src.colind, ci.size () * sizeof (int32_t), hipMemcpyDeviceToHost));
+            HIPCHK (hipMemcpy (v.data (), Q->sval, v.size () * sizeof (double), hipMemcpyDeviceToHost));
+         }
+         char err[256] = "";
+         const int mrc = rebuild_hierarchy (s, H2, Q->n_src, rp.data (), ci.data (), v.data (), filtered, nullptr, err, sizeof err);
+         if (mrc != 0) return fail (mrc, "%s: %s (no rank's solver is changed)", who, err);
+         built = true;
+         return NKP_OK;
+      } ();
+   }
+   if ((rc = dist_agree (s, rc, who, "new values of the hierarchy"))) {
+      if (built) {
+         (void) hipStreamSynchronize (st);
+         ml_free (H2);
+      }
+      rf_drop_inverse (W);
+      return rc;
+   }
+
+   // ---- commit point: from here on the solver's own buffers are written
+   char err[256] = "";
+   int lrc = 0;
+   if (nnz && hipMemcpyAsync (s->A.val, W.aval, (size_t) nnz * sizeof (double), hipMemcpyDeviceToDevice, st) != hipSuccess) {
+      lrc = -3;
+      snprintf (err, sizeof err, "copy of the new values failed");
+      if (built) ml_free (H2);
+   } else
+      lrc = refactor_commit (s, multilevel && rebuild, H2, err, sizeof err);
+   rc = lrc ? fail (lrc == -4 ? NKP_ESINGULAR : lrc == -2 ? NKP_ENOMEM : NKP_EDEVICE, "%s: %s", who, err) : NKP_OK;
+   // ---- (c) all ranks committed, or none of them solves
+   if ((rc = dist_agree (s, rc, who, "commit"))) {
+      s->shared->broken = true;
+      s->shared->why = lrc ? std::string (who) + " failed after writing part of the new values (" + err + "); this solver cannot solve until nkp_refactor_dist succeeds on every rank"
+                           : g_last_error + "; the new values are written on this rank, so it cannot solve until nkp_refactor_dist succeeds on every rank";
+      return rc;
+   }
+   s->shared->broken = false;
+   s->refactor_count++;
+   s->refactor_rebuilt = rebuild ? 1 : 0;
+   s->refactor_halo_values = halo_values;
+   struct timespec ts1;
+   clock_gettime (CLOCK_MONOTONIC, &ts1);
+   s->refactor_seconds = (double) (ts1.tv_sec - ts0.tv_sec) + 1e-9 * (double) (ts1.tv_nsec - ts0.tv_nsec);
+   msg (s, 1, "%s: %s, %lld overlap values received, %.3f s\n", who, rebuild ? "hierarchy rebuilt" : "coarse cells kept", (long long) halo_values, s->refactor_seconds);
+   return NKP_OK;
+}
+
+extern "C" int nkp_refactor_dist (nkp_solver *s, const double *val_loc, int flags) { return refactor_dist_impl (s, val_loc, nullptr, flags, "nkp_refactor_dist"); }
+
+extern "C" int nkp_refactor_dist_device (nkp_solver *s, const void *d_val_loc, int flags) { return refactor_dist_impl (s, nullptr, d_val_loc, flags, "nkp_refactor_dist_device"); }
 
 // ---------------------------------------------------------------- exposed pieces (parity / roofline)
 extern "C" int nkp_spmv_device (nkp_solver *s, const void *d_x, void *d_y)
@@ -1761,6 +1950,10 @@ struct DistPlan {
    std::vector<double> e_val;
    int64_t n_sel = 0;
    bool ras = false;
+   // what nkp_refactor_dist needs to redo the value part: where every entry of e_* comes from (own local entry e, or
+   // -1 - position in the received overlap values), the own entries shipped (in val_s order) and the entry counts per rank
+   std::vector<int32_t> e_org, ship_e;
+   std::vector<int> ent_give, ent_need;
 };
 
 static int dist_plan (DistPlan &D, const nkp_comm_ops *comm, const nkp_options &o, const std::vector<int64_t> &starts, int64_t fst_row, int64_t m_loc,
@@ -1921,6 +2114,7 @@ static int dist_plan (DistPlan &D, const nkp_comm_ops *comm, const nkp_options &
                   len_s.push_back (rowptr_loc[r + 1] - rowptr_loc[r]);
                   erow_give[p]++;
                   for (int e = rowptr_loc[r]; e < rowptr_loc[r + 1]; e++) {
+                     D.ship_e.push_back ((int32_t) e);
                      col_s.push_back (colind_glob[e]);
                      int32_t w[2];
                      memcpy (w, &val[e], sizeof (double));
@@ -1948,6 +2142,8 @@ static int dist_plan (DistPlan &D, const nkp_comm_ops *comm, const nkp_options &
          }
          if ((rc = agree (rc, "overlap sizes"))) return rc;
          for (int p = 0; p < P; p++) { ent2_give[p] = 2 * ent_give[p]; ent2_need[p] = 2 * ent_need[p]; }
+         D.ent_give = ent_give;
+         D.ent_need = ent_need;
       }
       std::vector<int32_t> col_r ((size_t) n_eent + 1), val_r (2 * (size_t) n_eent + 2);
       col_s.push_back (0);
@@ -1995,23 +2191,26 @@ static int dist_plan (DistPlan &D, const nkp_comm_ops *comm, const nkp_options &
       e_rowptr.assign ((size_t) (m_loc + n_sel) + 1, 0);
       e_colind.reserve ((size_t) (nnz_loc + n_eent));
       e_val.reserve ((size_t) (nnz_loc + n_eent));
-      std::vector<std::pair<int32_t, double>> rowbuf;
+      D.e_org.reserve ((size_t) (nnz_loc + n_eent));
+      // (column, value, origin); columns are unique within a row, so the sort puts the origins where it puts the values
+      struct Ent { int32_t col; double v; int32_t org; };
+      std::vector<Ent> rowbuf;
       auto flush_row = [&] (int64_t r) {
          bool sorted = true;
-         for (size_t k = 1; k < rowbuf.size () && sorted; k++) sorted = rowbuf[k].first > rowbuf[k - 1].first;
-         if (!sorted) std::sort (rowbuf.begin (), rowbuf.end (), [] (const std::pair<int32_t, double> &a, const std::pair<int32_t, double> &b) { return a.first < b.first; });
-         for (const auto &pr : rowbuf) { e_colind.push_back (pr.first); e_val.push_back (pr.second); }
+         for (size_t k = 1; k < rowbuf.size () && sorted; k++) sorted = rowbuf[k].col > rowbuf[k - 1].col;
+         if (!sorted) std::sort (rowbuf.begin (), rowbuf.end (), [] (const Ent &a, const Ent &b) { return a.col < b.col; });
+         for (const Ent &pr : rowbuf) { e_colind.push_back (pr.col); e_val.push_back (pr.v); D.e_org.push_back (pr.org); }
          e_rowptr[(size_t) r + 1] = (int32_t) e_colind.size ();
          rowbuf.clear ();
       };
       for (int64_t r = 0; r < m_loc; r++) {
          for (int e = rowptr_loc[r]; e < rowptr_loc[r + 1]; e++) {
             const int32_t x = colind_ext[(size_t) e];
-            if (x < m_loc) rowbuf.push_back ({ x, val[e] });
+            if (x < m_loc) rowbuf.push_back ({ x, val[e], (int32_t) e });
             else {
                const int32_t q = sel_of_hpos[(size_t) (x - m_loc)];
                if (q >= 0) {
-                  rowbuf.push_back ({ (int32_t) (m_loc + q), val[e] });
+                  rowbuf.push_back ({ (int32_t) (m_loc + q), val[e], (int32_t) e });
                   e_ct[(size_t) selcol_of_hpos[(size_t) (x - m_loc)]] = e_ct[(size_t) col_of[(size_t) r]];   // an overlap column carries the tracer of the rows that see it
                }
             }
@@ -2026,7 +2225,7 @@ static int dist_plan (DistPlan &D, const nkp_comm_ops *comm, const nkp_options &
                if (x < 0) continue;
                double v;
                memcpy (&v, &val_r[2 * q], sizeof (double));
-               rowbuf.push_back ({ (int32_t) x, v });
+               rowbuf.push_back ({ (int32_t) x, v, (int32_t) (-1 - (int64_t) q) });
             }
             flush_row (m_loc + k);
          }
@@ -2204,6 +2403,36 @@ extern "C" int nkp_create_dist (nkp_solver **out, const nkp_options *opt, int64_
          s->dist.overlap = true;
    }
    s->dist.on = true;
+   if (s->opt.precond == NKP_PRECOND_MULTILEVEL) {
+      // nkp_refactor_dist: the hierarchy's source matrix and where its values come from (host memory only until the first call)
+      DistRefactorPlan *Q = new DistRefactorPlan;
+      if (ras) {
+         Q->n_src = m_loc + n_sel;
+         Q->src_rowptr.swap (e_rowptr);
+         Q->src_colind.swap (e_colind);
+         Q->origin.swap (D.e_org);
+         Q->ship.swap (D.ship_e);
+         Q->ship_counts = D.ent_give;
+         Q->recv_counts = D.ent_need;
+         for (int c : Q->recv_counts) Q->n_recv += c;
+         Q->exchange = true;
+         // what a rebuild passes to ml_setup again (nkp_create's own copies are made for the diagonal block only)
+         s->h_blk.swap (e_blk);
+         s->h_col_i.swap (e_ci);
+         s->h_col_j.swap (e_cj);
+         s->h_col_t.swap (e_ct);
+         s->tracer_cnt = coupled_tracer_cnt;
+      } else {
+         Q->n_src = m_loc;
+         Q->origin.reserve (dcol.size ());
+         for (int64_t e = 0; e < nnz_loc; e++)
+            if (colind_ext[(size_t) e] < m_loc) Q->origin.push_back ((int32_t) e);
+         Q->src_rowptr.swap (drow);
+         Q->src_colind.swap (dcol);
+      }
+      Q->nnz_src = (int64_t) Q->src_colind.size ();
+      s->dplan = Q;
+   }
    msg (s, 1, "nkp_create_dist: %d of %d SpMV row blocks are interior (multiplied while the halo travels: %s)\n", s->dist.seg_rb[2] - s->dist.seg_rb[1],
         s->dist.seg_rb[3], s->dist.overlap ? "yes" : "no");
    msg (s, 1, "nkp_create_dist: rows [%lld, %lld) of %lld, %lld halo rows in, %lld rows out; overlap (restricted additive Schwarz): %s, %lld rows of other ranks in this rank's hierarchy\n",

@@ -378,3 +378,21 @@ class NkpDistSolver(_solver.NkpSolver):
         if rc != 0:
             raise _solver.NkpError(rc, lib.nkp_last_error().decode() + (" | comm: " + "; ".join(comm.errors) if comm.errors else ""))
         self._lib, self._h, self.n, self.nnz, self.options = lib, h, int(loc["m_loc"]), int(ci.size), opt
+
+    def _check_dist(self, rc):
+        if rc != 0:
+            comm = self._comm
+            raise _solver.NkpError(rc, self._lib.nkp_last_error().decode() + (" | comm: " + "; ".join(comm.errors) if comm.errors else ""))
+
+    def refactor_dist(self, val_loc, rebuild=False):
+        """nkp_refactor_dist (collective: every rank calls it): this rank's new values, nnz_loc of them in the order of the
+        local rows it was created with.  The overlap rows' values come from their owners; get_int("refactor_halo_values")
+        counts them, get_int("refactor_rebuilt") tells whether this rank rebuilt its hierarchy."""
+        val = np.ascontiguousarray(val_loc, np.float64).reshape(-1)
+        if val.size != self.nnz:
+            raise ValueError(f"val_loc has {val.size} entries, expected {self.nnz}")
+        self._check_dist(self._lib.nkp_refactor_dist(self._h, _solver._p(val, C.c_double), _solver.REFACTOR_REBUILD if rebuild else 0))
+
+    def refactor_dist_device(self, d_val_loc, rebuild=False):
+        """nkp_refactor_dist_device (collective): d_val_loc = integer device address of this rank's nnz_loc float64 values."""
+        self._check_dist(self._lib.nkp_refactor_dist_device(self._h, C.c_void_p(d_val_loc), _solver.REFACTOR_REBUILD if rebuild else 0))
