@@ -209,7 +209,9 @@ int nkp_create64 (nkp_solver **out, const nkp_options *opt, int64_t n, const int
  * stops the residual above rtol (badly scaled rows: even a direct solve with refinement then stays above it) the solve
  * ends after a few restart cycles instead of running to max_iters and returns NKP_OK_BERR if the componentwise
  * backward error -- the accuracy measure the reference itself reports (berr, src/solve_ABglobal.c:396-398) -- is
- * <= max (1e-14, rtol / 100), else NKP_NOT_CONVERGED. */
+ * <= max (1e-14, rtol / 100), else NKP_NOT_CONVERGED.
+ * nrhs >= 2 right-hand sides share the sweeps and, on a row-distributed solver, the collectives of every Krylov step
+ * (nkp_solve_batch_device below; there the call is collective: the same nrhs on every rank, ldb >= m_loc). */
 int nkp_solve (nkp_solver *s, double *b_in_x_out, int nrhs, int64_t ldb,
                double *berr, int *iters, double *relres);
 
@@ -219,8 +221,20 @@ int nkp_solve (nkp_solver *s, double *b_in_x_out, int nrhs, int64_t ldb,
  * operator and preconditioner applications of a Krylov step are one pass for the group.  Column c of the result has the bits
  * nkp_solve_device gives for that right-hand side alone, iters[c] / relres[c] / berr[c] likewise; the return code is the worst of
  * the columns'.  Needs K - 1 more sets of work vectors (kept for later calls).  Falls back to one at a time where the batched path
- * does not apply (BiCGStab, row equilibration, chained cycles, the distributed flavour) or with nkp_tuning.rhs_batch = 0.
- * nkp_solve with nrhs >= 2 takes the same path. */
+ * does not apply (BiCGStab, row equilibration, chained cycles, an f32 basis) or with nkp_tuning.rhs_batch = 0.
+ * nkp_solve with nrhs >= 2 takes the same path.
+ *
+ * On a solver made by nkp_create_dist with more than one rank the call is collective for nrhs >= 2 exactly as nkp_solve is
+ * for one system: every rank calls with the same nrhs and passes its own rows of every vector (ldb >= m_loc).  A group of K
+ * systems then runs in lockstep on every rank with the collectives of ONE system per Krylov step: one alltoallv of K-wide
+ * rows for the overlap rows of the preconditioner, one for the halo of the SpMV, and one allreduce per Gram-Schmidt pass
+ * (plus one for the norms) whose message holds the K systems' dot products.  The interleave width is agreed between the ranks
+ * (allgather_i64_host): all of them take the narrowest one any rank has device memory for; a rank with another failure returns
+ * its code, the others NKP_ECOMM naming it (nkp_solve agrees likewise on having staged its host vectors on the device).  Bits: column c has the bits of nkp_solve_device on right-hand side c alone
+ * (solution, iters, relres, berr) whenever the transport's allreduce gives an element the same bits whatever the length of the
+ * message it travels in -- the file transport (fixed rank order) with any number of ranks, any transport with two ranks.  On
+ * other transports (gloo or RCCL with three or more ranks) every column meets the same stopping test on the true residual;
+ * bit identity is not promised there. */
 int nkp_solve_batch_device (nkp_solver *s, int nrhs, const void *d_B, void *d_X, int64_t ldb, double *berr, int *iters, double *relres);
 
 /* Same, with b and x already resident on the solver's device (x may alias b); x_inout is also
@@ -250,7 +264,11 @@ int nkp_time_kernel (nkp_solver *s, int which, int arg, int reps, double *avg_ms
  * the setup kernels built; the smaller ones are built on the host);
  * compulsory HBM bytes of the pieces nkp_time_kernel times: "smoother_spmv_bytes", "column_solve_bytes", "cycle_bytes";
  * distributed flavour: "dist_overlap" (halo exchange hidden behind the interior rows), "dist_interior_rowblocks",
- * "dist_ras" (hierarchy overlaps the neighbouring ranks), "dist_ras_rows" (rows of other ranks in this rank's hierarchy). */
+ * "dist_ras" (hierarchy overlaps the neighbouring ranks), "dist_ras_rows" (rows of other ranks in this rank's hierarchy);
+ * counters, cumulative over the solver's life, per rank: "dist_alltoallv_calls", "dist_allreduce_calls" (every call of the two
+ * device collectives made by solves, single or batched; 0 on a single-GPU solver), "batch_steps" (batched operator
+ * applications = lockstep Krylov steps of a group of right-hand sides), "batch_width" (K of the last batched group, 0 if
+ * none ran).  An unknown key returns -1. */
 int64_t nkp_get_int (nkp_solver *s, const char *key);
 
 /* New matrix values on the sparsity pattern the solver was created with (the analogue of SuperLU's

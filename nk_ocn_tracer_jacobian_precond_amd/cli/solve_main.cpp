@@ -520,14 +520,15 @@ int main (int argc, char *argv[])
       int v;
       if (e && !parse_to_int ((char *) e, &v) && v > 1 && !use_comm) concurrency = v;
    }
-   // NKP_RHS_BLOCK=K (2..4, single-GPU flavour): K right-hand sides per nkp_solve call -- they share every sweep over the matrix
+   // NKP_RHS_BLOCK=K (2..4): K right-hand sides per nkp_solve call -- they share every sweep over the matrix
    // and the hierarchy (nkp.h, nkp_solve_batch_device), each with its own recurrence and stopping test, so every tracer
-   // gets the bits of its own solve.  Written back in the order given, up to the first failure.
+   // gets the bits of its own solve.  Written back in the order given, up to the first failure.  With a communicator every
+   // rank passes its slice of the K tracers (ldb = m_loc) and the K systems also share every collective of a Krylov step.
    int rhs_block = 1;
    {
       const char *e = getenv ("NKP_RHS_BLOCK");
       int v;
-      if (e && !parse_to_int ((char *) e, &v) && v > 1 && !use_comm) rhs_block = v > 4 ? 4 : v;
+      if (e && !parse_to_int ((char *) e, &v) && v > 1) rhs_block = v > 4 ? 4 : v;
    }
    if (rhs_block > 1) concurrency = 1;
    if (concurrency > 1 || rhs_block > 1) {
@@ -552,6 +553,12 @@ int main (int argc, char *argv[])
          Bs[g].resize ((size_t) (flat_len ? flat_len : 1));
          if (get_B_global (groups[g].data (), Bs[g].data ()))
             exit (EXIT_FAILURE);
+#ifdef NKP_DIST
+         if (cm_perm) {                                  // the solver's rows are in cell-major order
+            std::vector<double> T (Bs[g]);
+            for (int r = 0; r < flat_len; r++) Bs[g][r] = T[cm_perm[r]];
+         }
+#endif
       }
       struct result { int info = 0, iters = 0; double berr = 0.0, relres = 0.0; std::string err; };
       std::vector<result> res (ng);
@@ -559,13 +566,15 @@ int main (int argc, char *argv[])
       if (rhs_block > 1) {
          printf ("(%d) calling nkp_solve for %zu right-hand sides, %d per call\n", iam, ng, rhs_block);
          fflush (stdout);
-         const size_t ldb = (size_t) (flat_len ? flat_len : 1);
+         // with a communicator every rank flattened the whole B and solves for its own slice (ldb = m_loc, src/solve_ABdist.c:571)
+         const size_t ldb = use_comm ? (size_t) (m_loc ? m_loc : 1) : (size_t) (flat_len ? flat_len : 1);
+         const size_t off = use_comm ? (size_t) fst_row : 0, len = use_comm ? (size_t) m_loc : ldb;
          std::vector<double> blockB ((size_t) rhs_block * ldb);
          for (size_t g0 = 0; g0 < ng; g0 += (size_t) rhs_block) {
             const int k = (int) (ng - g0 < (size_t) rhs_block ? ng - g0 : (size_t) rhs_block);
             double berr_k[4] = { 0, 0, 0, 0 }, relres_k[4] = { 0, 0, 0, 0 };
             int iters_k[4] = { 0, 0, 0, 0 };
-            for (int c = 0; c < k; c++) memcpy (blockB.data () + (size_t) c * ldb, Bs[g0 + c].data (), ldb * sizeof (double));
+            for (int c = 0; c < k; c++) memcpy (blockB.data () + (size_t) c * ldb, Bs[g0 + c].data () + off, len * sizeof (double));
             const int rc = nkp_solve (solver, blockB.data (), k, (int64_t) ldb, berr_k, iters_k, relres_k);
             const std::string err = rc ? nkp_last_error () : "";
             for (int c = 0; c < k; c++) {
@@ -575,7 +584,7 @@ int main (int argc, char *argv[])
                // (nothing of the block is written: conservative next to the one-at-a-time loop, which would write the ones before it)
                r.info = rc;
                r.err = err;
-               if (rc >= 0) memcpy (Bs[g0 + c].data (), blockB.data () + (size_t) c * ldb, ldb * sizeof (double));
+               if (rc >= 0) memcpy (Bs[g0 + c].data () + off, blockB.data () + (size_t) c * ldb, len * sizeof (double));
             }
             if (rc < 0) break;
          }
@@ -614,7 +623,23 @@ int main (int argc, char *argv[])
                      groups[g][0], inout_fname);
             exit (EXIT_FAILURE);
          }
-         if (put_B_global (groups[g].data (), Bs[g].data ()))
+         if (use_comm) {
+            // slices back to rank 0 (reference put_B_dist, src/solve_ABdist.c:377-406)
+            std::vector<double> X (iam == 0 ? (size_t) (flat_len ? flat_len : 1) : 0);
+            if (nkp_gather_root (solver, Bs[g].data () + fst_row, iam == 0 ? X.data () : NULL)) {
+               fprintf (stderr, "(%d) %s\n", iam, nkp_last_error ());
+               exit (EXIT_FAILURE);
+            }
+            if (iam == 0) {
+#ifdef NKP_DIST
+               if (cm_perm)
+                  for (int r = 0; r < flat_len; r++) Bs[g][cm_perm[r]] = X[r];       // back to the file's tracer-major order
+               else
+#endif
+               memcpy (Bs[g].data (), X.data (), (size_t) flat_len * sizeof (double));
+            }
+         }
+         if ((!use_comm || iam == 0) && put_B_global (groups[g].data (), Bs[g].data ()))
             exit (EXIT_FAILURE);
       }
    } else {

@@ -263,19 +263,25 @@ void launch_csr_spmv_batch (int K, const CsrDev &A, int rb0, int rb1, const doub
 #undef BSPMV
 }
 
-// y_k = A x_k for the K interleaved columns of x, every result in its own vector (dst[k] NULL: not wanted)
-void launch_csr_spmv_batch_split (int K, const CsrDev &A, const double *x, double *const *dst, hipStream_t st)
+// y_k = A x_k for the K interleaved columns of x, every result in its own vector (dst[k] NULL: not wanted); row blocks
+// [rb0, rb1) only (the row-distributed flavour multiplies its interior rows while the halo of x travels)
+void launch_csr_spmv_batch_split_range (int K, const CsrDev &A, int rb0, int rb1, const double *x, double *const *dst, hipStream_t st)
 {
-   const int cnt = A.nrowblk;
+   const int cnt = rb1 - rb0;
    if (cnt <= 0) return;
    const int per_xcd = (cnt + 7) / 8;
    BatchOutPtrs P;
    for (int k = 0; k < NKP_BATCH_MAX; k++) P.p[k] = k < K ? dst[k] : nullptr;
 #define BSPLIT(VT_, K_, VAL_) hipLaunchKernelGGL ((csr_spmv_batch_rows_kernel<0, VT_, K_, true>), dim3 (per_xcd * 8), dim3 (BT_THREADS), 0, st, \
-                                                  A.rowblk, 0, cnt, per_xcd, A.rowptr, A.colind, VAL_, x, (double *) nullptr, (const double *) nullptr, P)
+                                                  A.rowblk, rb0, cnt, per_xcd, A.rowptr, A.colind, VAL_, x, (double *) nullptr, (const double *) nullptr, P)
    if (A.valf) { if (K == 2) BSPLIT (float, 2, A.valf); else if (K == 4) BSPLIT (float, 4, A.valf); else BSPLIT (float, 8, A.valf); }
    else { if (K == 2) BSPLIT (double, 2, A.val); else if (K == 4) BSPLIT (double, 4, A.val); else BSPLIT (double, 8, A.val); }
 #undef BSPLIT
+}
+
+void launch_csr_spmv_batch_split (int K, const CsrDev &A, const double *x, double *const *dst, hipStream_t st)
+{
+   launch_csr_spmv_batch_split_range (K, A, 0, A.nrowblk, x, dst, st);
 }
 
 // ---------------------------------------------------------------- grid transfer / permutation / coarsest solve, K columns
@@ -345,6 +351,62 @@ void scatter_split_kernel (const int *__restrict__ perm, const double *__restric
    }
 }
 
+// ---------------------------------------------------------------- row-distributed flavour: K-wide messages and the overlap rows
+// One message row carries the K systems' values of one matrix row (8 K bytes, consecutive lanes write consecutive rows:
+// coalesced 16- / 32- / 64-byte stores), so that ONE alltoallv with K times the plan's counts serves the whole group and
+// the receiver's halo part is K-interleaved as it arrives.
+//   out[i * K + k] = src_k[idx[i]]   (a system without a vector sends zeros)
+template <int K>
+__global__ __launch_bounds__ (BT_THREADS)
+void pack_rows_split_kernel (const int *__restrict__ idx, BatchPtrs src, double *__restrict__ out, int64_t nrows)
+{
+   const int64_t stride = (int64_t) gridDim.x * BT_THREADS;
+   for (int64_t i = (int64_t) blockIdx.x * BT_THREADS + threadIdx.x; i < nrows; i += stride) {
+      const int64_t r = idx[i];
+#pragma unroll
+      for (int k = 0; k < K; k++) out[i * K + k] = src.p[k] ? src.p[k][r] : 0.0;
+   }
+}
+
+// gather_interleave_kernel on the extended rows [own rows | overlap rows] of a rank's hierarchy: row perm[i] < n_own comes
+// from the systems' own vectors, the others from the K-interleaved halo rows that have just arrived (sel[.] = halo position)
+template <int K>
+__global__ __launch_bounds__ (BT_THREADS)
+void gather_interleave_ext_kernel (const int *__restrict__ perm, BatchPtrs src, const double *__restrict__ halo, const int *__restrict__ sel,
+                                   int64_t n_own, double *__restrict__ out, int64_t n)
+{
+   const int64_t stride = (int64_t) gridDim.x * BT_THREADS;
+   for (int64_t i = (int64_t) blockIdx.x * BT_THREADS + threadIdx.x; i < n; i += stride) {
+      const int64_t pi = perm[i];
+      if (pi < n_own) {
+#pragma unroll
+         for (int k = 0; k < K; k++) out[i * K + k] = src.p[k] ? src.p[k][pi] : 0.0;
+      } else {
+         const double *h = halo + (int64_t) sel[pi - n_own] * K;
+#pragma unroll
+         for (int k = 0; k < K; k++) out[i * K + k] = src.p[k] ? h[k] : 0.0;
+      }
+   }
+}
+
+// scatter_split_kernel that keeps the own rows only (the correction on the overlap rows belongs to their owners)
+template <int K>
+__global__ __launch_bounds__ (BT_THREADS)
+void scatter_split_own_kernel (const int *__restrict__ perm, const double *__restrict__ in, double *__restrict__ z, BatchOutPtrs dst, int64_t n_own, int64_t n)
+{
+   const int64_t stride = (int64_t) gridDim.x * BT_THREADS;
+   for (int64_t i = (int64_t) blockIdx.x * BT_THREADS + threadIdx.x; i < n; i += stride) {
+      const int64_t pi = perm[i];
+      if (pi >= n_own) continue;
+#pragma unroll
+      for (int k = 0; k < K; k++) {
+         const double v = in[i * K + k];
+         z[pi * K + k] = v;
+         if (dst.p[k]) dst.p[k][pi] = v;
+      }
+   }
+}
+
 // one wave per output row, the K columns one after the other (each summed like dense_matvec_kernel sums its one)
 template <int K>
 __global__ __launch_bounds__ (BT_THREADS)
@@ -401,6 +463,25 @@ void launch_scatter_split (int K, const int *perm, const double *in, double *z, 
    BatchOutPtrs P;
    for (int k = 0; k < NKP_BATCH_MAX; k++) P.p[k] = k < K ? dst[k] : nullptr;
    if (n > 0) BT_K (scatter_split_kernel, dim3 (bt_grid (n)), perm, in, z, P, n);
+}
+void launch_pack_rows_split (int K, const int *idx, const double *const *src, double *out, int64_t nrows, hipStream_t st)
+{
+   BatchPtrs P;
+   for (int k = 0; k < NKP_BATCH_MAX; k++) P.p[k] = k < K ? src[k] : nullptr;
+   if (nrows > 0) BT_K (pack_rows_split_kernel, dim3 (bt_grid (nrows)), idx, P, out, nrows);
+}
+void launch_gather_interleave_ext (int K, const int *perm, const double *const *src, const double *halo, const int *sel, int64_t n_own, double *out, int64_t n,
+                                   hipStream_t st)
+{
+   BatchPtrs P;
+   for (int k = 0; k < NKP_BATCH_MAX; k++) P.p[k] = k < K ? src[k] : nullptr;
+   if (n > 0) BT_K (gather_interleave_ext_kernel, dim3 (bt_grid (n)), perm, P, halo, sel, n_own, out, n);
+}
+void launch_scatter_split_own (int K, const int *perm, const double *in, double *z, double *const *dst, int64_t n_own, int64_t n, hipStream_t st)
+{
+   BatchOutPtrs P;
+   for (int k = 0; k < NKP_BATCH_MAX; k++) P.p[k] = k < K ? dst[k] : nullptr;
+   if (n > 0) BT_K (scatter_split_own_kernel, dim3 (bt_grid (n)), perm, in, z, P, n_own, n);
 }
 void launch_dense_matvec_batch (int K, const double *Minv, const double *x, double *y, int n, hipStream_t st)
 {

@@ -47,11 +47,9 @@ static inline int red_grid (int64_t n)
 // ---------------------------------------------------------------- multi-dot
 // grid (nblk, nchunk).  partial[(chunk*nblk + blk)*(CHUNK+1) + c]; slot CHUNK of chunk 0 = w.w
 template <class VT, class VT2>
-__global__ __launch_bounds__ (B1_THREADS)
-void multi_dot_kernel (const VT *__restrict__ V, int64_t ld, int k, const double *__restrict__ w,
-                       int64_t n, double *__restrict__ partial)
+__device__ __forceinline__ void multi_dot_body (const VT *__restrict__ V, int64_t ld, int k, const double *__restrict__ w,
+                                                int64_t n, double *__restrict__ partial, double *sh)
 {
-   __shared__ double sh[B1_THREADS / NKP_WAVE];
    const int chunk = blockIdx.y;
    const int j0 = chunk * NKP_DOT_CHUNK;
    const int kc = (k - j0) < NKP_DOT_CHUNK ? (k - j0) : NKP_DOT_CHUNK;
@@ -89,9 +87,26 @@ void multi_dot_kernel (const VT *__restrict__ V, int64_t ld, int k, const double
    if (threadIdx.x == 0) out[NKP_DOT_CHUNK] = sw;
 }
 
+template <class VT, class VT2>
+__global__ __launch_bounds__ (B1_THREADS)
+void multi_dot_kernel (const VT *__restrict__ V, int64_t ld, int k, const double *__restrict__ w,
+                       int64_t n, double *__restrict__ partial)
+{
+   __shared__ double sh[B1_THREADS / NKP_WAVE];
+   multi_dot_body<VT, VT2> (V, ld, k, w, n, partial, sh);
+}
+
+// the same for system blockIdx.z of a group
+__global__ __launch_bounds__ (B1_THREADS)
+void multi_dot_group_kernel (GsGroup G, int64_t ld, int k, int64_t n)
+{
+   __shared__ double sh[B1_THREADS / NKP_WAVE];
+   const int r = blockIdx.z;
+   multi_dot_body<double, double2> (G.V[r], ld, k, G.w[r], n, G.partial[r], sh);
+}
+
 // one wave per output: out[j] = sum_blk partial[...], fixed order.  out[k] = w.w (chunk 0)
-__global__ __launch_bounds__ (NKP_WAVE)
-void multi_dot_finish_kernel (const double *__restrict__ partial, int nblk, int k, double *__restrict__ out)
+__device__ __forceinline__ void multi_dot_finish_body (const double *__restrict__ partial, int nblk, int k, double *__restrict__ out)
 {
    const int j = blockIdx.x;                   // 0..k  (k = the w.w slot)
    const int chunk = (j < k) ? j / NKP_DOT_CHUNK : 0;
@@ -103,6 +118,18 @@ void multi_dot_finish_kernel (const double *__restrict__ partial, int nblk, int 
    if (threadIdx.x == 0) out[j] = s;
 }
 
+__global__ __launch_bounds__ (NKP_WAVE)
+void multi_dot_finish_kernel (const double *__restrict__ partial, int nblk, int k, double *__restrict__ out)
+{
+   multi_dot_finish_body (partial, nblk, k, out);
+}
+
+__global__ __launch_bounds__ (NKP_WAVE)
+void multi_dot_finish_group_kernel (GsGroup G, int nblk, int k, double *__restrict__ msg)
+{
+   multi_dot_finish_body (G.partial[blockIdx.y], nblk, k, msg + (int64_t) blockIdx.y * (k + 1));
+}
+
 void launch_multi_dot (const void *V, int v_f32, int64_t ld, int k, const double *w, int64_t n, double *partial, double *out, hipStream_t st)
 {
    const int g = red_grid (n);
@@ -112,15 +139,21 @@ void launch_multi_dot (const void *V, int v_f32, int64_t ld, int k, const double
    hipLaunchKernelGGL (multi_dot_finish_kernel, dim3 (k + 1), dim3 (NKP_WAVE), 0, st, partial, g, k, out);
 }
 
+void launch_multi_dot_group (int R, const GsGroup &G, int64_t ld, int k, int64_t n, double *msg, hipStream_t st)
+{
+   if (R <= 0) return;
+   const int g = red_grid (n);
+   const int nchunk = k > 0 ? (k + NKP_DOT_CHUNK - 1) / NKP_DOT_CHUNK : 1;
+   hipLaunchKernelGGL (multi_dot_group_kernel, dim3 (g, nchunk, R), dim3 (B1_THREADS), 0, st, G, ld, k, n);
+   hipLaunchKernelGGL (multi_dot_finish_group_kernel, dim3 (k + 1, R), dim3 (NKP_WAVE), 0, st, G, g, k, msg);
+}
+
 // ---------------------------------------------------------------- w -= V h, with ||w||^2
 #define B1_MAX_K NKP_MAX_K
 template <class VT, class VT2>
-__global__ __launch_bounds__ (B1_THREADS)
-void update_w_kernel (const VT *__restrict__ V, int64_t ld, int k, const double *__restrict__ h,
-                      double *__restrict__ w, int64_t n, double *__restrict__ partial, double sign)
+__device__ __forceinline__ void update_w_body (const VT *__restrict__ V, int64_t ld, int k, const double *__restrict__ h,
+                                               double *__restrict__ w, int64_t n, double *__restrict__ partial, double sign, double *hs, double *sh)
 {
-   __shared__ double hs[B1_MAX_K];
-   __shared__ double sh[B1_THREADS / NKP_WAVE];
    for (int j = threadIdx.x; j < k; j += B1_THREADS) hs[j] = sign * h[j];
    __syncthreads ();
    double nrm = 0.0;
@@ -158,13 +191,43 @@ void update_w_kernel (const VT *__restrict__ V, int64_t ld, int k, const double 
    }
 }
 
-__global__ __launch_bounds__ (NKP_WAVE)
-void sum_partials_kernel (const double *__restrict__ partial, int nblk, double *__restrict__ out)
+template <class VT, class VT2>
+__global__ __launch_bounds__ (B1_THREADS)
+void update_w_kernel (const VT *__restrict__ V, int64_t ld, int k, const double *__restrict__ h,
+                      double *__restrict__ w, int64_t n, double *__restrict__ partial, double sign)
+{
+   __shared__ double hs[B1_MAX_K];
+   __shared__ double sh[B1_THREADS / NKP_WAVE];
+   update_w_body<VT, VT2> (V, ld, k, h, w, n, partial, sign, hs, sh);
+}
+
+__global__ __launch_bounds__ (B1_THREADS)
+void update_w_group_kernel (GsGroup G, int64_t ld, int k, const double *__restrict__ msg, int64_t n)
+{
+   __shared__ double hs[B1_MAX_K];
+   __shared__ double sh[B1_THREADS / NKP_WAVE];
+   const int r = blockIdx.y;
+   update_w_body<double, double2> (G.V[r], ld, k, msg + (int64_t) r * (k + 1), G.w[r], n, G.partial[r], -1.0, hs, sh);
+}
+
+__device__ __forceinline__ void sum_partials_body (const double *__restrict__ partial, int nblk, double *__restrict__ out)
 {
    double s = 0.0;
    for (int b = threadIdx.x; b < nblk; b += NKP_WAVE) s += partial[b];
    s = wave_sum (s);
    if (threadIdx.x == 0) out[0] = s;
+}
+
+__global__ __launch_bounds__ (NKP_WAVE)
+void sum_partials_kernel (const double *__restrict__ partial, int nblk, double *__restrict__ out)
+{
+   sum_partials_body (partial, nblk, out);
+}
+
+__global__ __launch_bounds__ (NKP_WAVE)
+void sum_partials_group_kernel (GsGroup G, int nblk, double *__restrict__ out)
+{
+   sum_partials_body (G.partial[blockIdx.x], nblk, out + blockIdx.x);
 }
 
 void launch_update_w (const void *V, int v_f32, int64_t ld, int k, const double *h, double *w, int64_t n, double *partial, double *out_nrm2, hipStream_t st)
@@ -175,6 +238,14 @@ void launch_update_w (const void *V, int v_f32, int64_t ld, int k, const double 
    hipLaunchKernelGGL (sum_partials_kernel, dim3 (1), dim3 (NKP_WAVE), 0, st, partial, g, out_nrm2);
 }
 
+void launch_update_w_group (int R, const GsGroup &G, int64_t ld, int k, const double *msg, int64_t n, double *nrm2, hipStream_t st)
+{
+   if (R <= 0) return;
+   const int g = red_grid (n);
+   hipLaunchKernelGGL (update_w_group_kernel, dim3 (g, R), dim3 (B1_THREADS), 0, st, G, ld, k, msg, n);
+   hipLaunchKernelGGL (sum_partials_group_kernel, dim3 (R), dim3 (NKP_WAVE), 0, st, G, g, nrm2);
+}
+
 void launch_axpy_multi (const double *Z, int64_t ld, int k, const double *c, double *x, int64_t n, hipStream_t st)
 {
    const int g = red_grid (n);
@@ -183,8 +254,7 @@ void launch_axpy_multi (const double *Z, int64_t ld, int k, const double *c, dou
 
 // ---------------------------------------------------------------- simple streams
 // y = alpha x ; optionally also yf = (float) (alpha x)  (f32 copy of a Krylov basis vector)
-__global__ __launch_bounds__ (B1_THREADS)
-void scale_to_kernel (const double *__restrict__ x, const double *__restrict__ alpha, double *__restrict__ y, float *__restrict__ yf, int64_t n)
+__device__ __forceinline__ void scale_to_body (const double *__restrict__ x, const double *__restrict__ alpha, double *__restrict__ y, float *__restrict__ yf, int64_t n)
 {
    const double a = alpha[0];
    const int64_t stride = (int64_t) gridDim.x * B1_THREADS * 2;
@@ -201,9 +271,27 @@ void scale_to_kernel (const double *__restrict__ x, const double *__restrict__ a
    }
 }
 
+__global__ __launch_bounds__ (B1_THREADS)
+void scale_to_kernel (const double *__restrict__ x, const double *__restrict__ alpha, double *__restrict__ y, float *__restrict__ yf, int64_t n)
+{
+   scale_to_body (x, alpha, y, yf, n);
+}
+
+__global__ __launch_bounds__ (B1_THREADS)
+void scale_to_group_kernel (GsGroup G, const double *__restrict__ inv, int64_t n)
+{
+   const int r = blockIdx.y;
+   scale_to_body (G.w[r], inv + r, G.vnext[r], nullptr, n);
+}
+
 void launch_scale_to (const double *x, const double *alpha_dev, double *y, float *yf, int64_t n, hipStream_t st)
 {
    hipLaunchKernelGGL (scale_to_kernel, dim3 (red_grid (n)), dim3 (B1_THREADS), 0, st, x, alpha_dev, y, yf, n);
+}
+
+void launch_scale_to_group (int R, const GsGroup &G, const double *inv, int64_t n, hipStream_t st)
+{
+   if (R > 0) hipLaunchKernelGGL (scale_to_group_kernel, dim3 (red_grid (n), R), dim3 (B1_THREADS), 0, st, G, inv, n);
 }
 
 __global__ __launch_bounds__ (B1_THREADS)
@@ -328,9 +416,8 @@ void launch_berr (const double *r, const double *den, int64_t n, double *partial
 }
 
 // ---------------------------------------------------------------- Hessenberg column epilogue
-__global__ __launch_bounds__ (NKP_WAVE)
-void finish_column_kernel (double *__restrict__ h, const double *__restrict__ h2, int k,
-                           const double *__restrict__ nrm2, double *__restrict__ inv)
+__device__ __forceinline__ void finish_column_body (double *__restrict__ h, const double *__restrict__ h2, int k,
+                                                    const double *__restrict__ nrm2, double *__restrict__ inv)
 {
    if (h2)
       for (int j = threadIdx.x; j < k; j += NKP_WAVE) h[j] += h2[j];
@@ -341,12 +428,18 @@ void finish_column_kernel (double *__restrict__ h, const double *__restrict__ h2
    }
 }
 
+__global__ __launch_bounds__ (NKP_WAVE)
+void finish_column_kernel (double *__restrict__ h, const double *__restrict__ h2, int k,
+                           const double *__restrict__ nrm2, double *__restrict__ inv)
+{
+   finish_column_body (h, h2, k, nrm2, inv);
+}
+
 // distributed flavour: ||w - V h||^2 = w.w - sum h_i^2 from the ALREADY reduced multi-dot message (h[0..k-1], h[k] = w.w), so
 // that an Arnoldi step needs one allreduce instead of two.  The difference loses log10 (w.w / result) digits; below 1e-8 of
 // w.w (the new direction is numerically inside the old space) h[k] is returned NEGATIVE: the host takes its magnitude and ends
 // the restart cycle there, and the true residual of the restart decides.  One wave, fixed order.
-__global__ __launch_bounds__ (NKP_WAVE)
-void finish_column_pythagoras_kernel (double *__restrict__ h, int k, double *__restrict__ inv)
+__device__ __forceinline__ void finish_column_pythagoras_body (double *__restrict__ h, int k, double *__restrict__ inv)
 {
    double s = 0.0;
    for (int j = threadIdx.x; j < k; j += NKP_WAVE) s += h[j] * h[j];
@@ -360,6 +453,26 @@ void finish_column_pythagoras_kernel (double *__restrict__ h, int k, double *__r
       h[k] = weak ? -t : t;
       inv[0] = (t > 0.0) ? 1.0 / t : 0.0;
    }
+}
+
+__global__ __launch_bounds__ (NKP_WAVE)
+void finish_column_pythagoras_kernel (double *__restrict__ h, int k, double *__restrict__ inv)
+{
+   finish_column_pythagoras_body (h, k, inv);
+}
+
+// row blockIdx.x of a group's message
+__global__ __launch_bounds__ (NKP_WAVE)
+void finish_column_group_kernel (double *__restrict__ msg, const double *__restrict__ msg2, int k, const double *__restrict__ nrm2, double *__restrict__ inv)
+{
+   const int64_t r = blockIdx.x;
+   if (nrm2) finish_column_body (msg + r * (k + 1), msg2 ? msg2 + r * (k + 1) : nullptr, k, nrm2 + r, inv + r);
+   else finish_column_pythagoras_body (msg + r * (k + 1), k, inv + r);
+}
+
+void launch_finish_column_group (int R, double *msg, const double *msg2, int k, const double *nrm2, double *inv, hipStream_t st)
+{
+   if (R > 0) hipLaunchKernelGGL (finish_column_group_kernel, dim3 (R), dim3 (NKP_WAVE), 0, st, msg, msg2, k, nrm2, inv);
 }
 
 void launch_finish_column_pythagoras (double *h, int k, double *inv, hipStream_t st)

@@ -1622,12 +1622,31 @@ int ml_batch_prepare (MlHierarchy &H, int K)
 {
    if (K != 2 && K != 4 && K != 8) return -1;
    if (H.batch_K >= K) return 0;
+   // all or nothing: the narrower vectors go first, and a failure leaves none behind (batch_K = 0 says so to the retry)
+   auto drop = [&H] () {
+      for (MlLevel &V : H.lev)
+         for (double **p : { &V.bx, &V.bx2, &V.bb, &V.br })
+            if (*p) {
+               (void) hipFree (*p);
+               *p = nullptr;
+               H.device_bytes -= (size_t) (V.n ? V.n : 1) * (size_t) H.batch_K * sizeof (double);
+            }
+      H.batch_K = 0;
+   };
+   drop ();
    for (MlLevel &V : H.lev) {
       for (double **p : { &V.bx, &V.bx2, &V.bb, &V.br }) {
-         if (*p) { (void) hipFree (*p); *p = nullptr; }
          const size_t bytes = (size_t) (V.n ? V.n : 1) * (size_t) K * sizeof (double);
-         if (hipMalloc ((void **) p, bytes) != hipSuccess) return -2;
-         if (hipMemset (*p, 0, bytes) != hipSuccess) return -2;
+         void *q = nullptr;
+         if (hipMalloc (&q, bytes) != hipSuccess || hipMemset (q, 0, bytes) != hipSuccess) {
+            if (q) (void) hipFree (q);
+            // the vectors made so far were sized for K
+            H.batch_K = K;
+            drop ();
+            (void) hipGetLastError ();      // the out-of-memory error is answered here, not by the next call that looks
+            return -2;
+         }
+         *p = (double *) q;
          H.device_bytes += bytes;
       }
    }
@@ -1717,6 +1736,17 @@ void ml_apply_batch_split (MlHierarchy &H, int K, const double *const *src, doub
    launch_gather_interleave (K, H.perm0, src, V.bb, V.n, st);
    ml_cycle_batch (H, K, 0, st);
    launch_scatter_split (K, H.perm0, V.bxnow (), z, dst, V.n, st);
+}
+
+// the same on the extended rows of a rank of the row-distributed flavour: level 0 has n_own own rows followed by the overlap
+// rows, whose residuals are the K-interleaved halo rows halo[sel[.] * K + k]; z and dst receive the own rows only
+void ml_apply_batch_split_ext (MlHierarchy &H, int K, const double *const *src, const double *halo, const int *sel, int64_t n_own, double *z,
+                               double *const *dst, hipStream_t st)
+{
+   MlLevel &V = H.lev[0];
+   launch_gather_interleave_ext (K, H.perm0, src, halo, sel, n_own, V.bb, V.n, st);
+   ml_cycle_batch (H, K, 0, st);
+   launch_scatter_split_own (K, H.perm0, V.bxnow (), z, dst, n_own, V.n, st);
 }
 
 // ================================================================ measurement helpers (bench.py, probes)

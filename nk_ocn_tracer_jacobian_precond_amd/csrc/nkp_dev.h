@@ -150,6 +150,22 @@ void launch_berr (const double *r, const double *den, int64_t n, double *partial
 // h[j] += h2[j] (j<k); h[k] = sqrt(nrm2); inv[0] = 1/h[k] (0 if h[k]==0)
 void launch_finish_column (double *h, const double *h2, int k, const double *nrm2, double *inv, hipStream_t st);
 void launch_finish_column_pythagoras (double *h, int k, double *inv, hipStream_t st);
+// The Gram-Schmidt kernels above for a group of R systems in one launch each (batched solve of the row-distributed flavour):
+// system r has its own basis, w and partial sums; its dots form row r of ONE message msg[r * (k + 1) + j] (j <= k) that a
+// single allreduce reduces for the group.  Per system the operations and their order are those of the kernels above.
+struct GsGroup {
+   const double *V[NKP_BATCH_MAX];
+   double *w[NKP_BATCH_MAX];
+   double *partial[NKP_BATCH_MAX];
+   double *vnext[NKP_BATCH_MAX];
+};
+void launch_multi_dot_group (int R, const GsGroup &G, int64_t ld, int k, int64_t n, double *msg, hipStream_t st);
+// w_r -= V_r msg[r]; nrm2[r] = ||w_r||^2
+void launch_update_w_group (int R, const GsGroup &G, int64_t ld, int k, const double *msg, int64_t n, double *nrm2, hipStream_t st);
+// msg[r][j] += msg2[r][j] (msg2 != NULL); msg[r][k] = sqrt (nrm2[r]); inv[r] = 1 / msg[r][k]; or the Pythagoras form (nrm2 NULL)
+void launch_finish_column_group (int R, double *msg, const double *msg2, int k, const double *nrm2, double *inv, hipStream_t st);
+// vnext_r = inv[r] * w_r
+void launch_scale_to_group (int R, const GsGroup &G, const double *inv, int64_t n, hipStream_t st);
 // y = a*x + b*y style helpers for BiCGStab
 void launch_axpby (double a, const double *x, double b, double *y, int64_t n, hipStream_t st);
 void launch_copy (const double *x, double *y, int64_t n, hipStream_t st);
@@ -185,6 +201,13 @@ void launch_scatter_batch (int K, const int *perm, const double *in, double *out
 void launch_gather_interleave (int K, const int *perm, const double *const *src, double *out, int64_t n, hipStream_t st);
 void launch_scatter_split (int K, const int *perm, const double *in, double *z, double *const *dst, int64_t n, hipStream_t st);
 void launch_csr_spmv_batch_split (int K, const CsrDev &A, const double *x, double *const *dst, hipStream_t st);
+void launch_csr_spmv_batch_split_range (int K, const CsrDev &A, int rb0, int rb1, const double *x, double *const *dst, hipStream_t st);
+// row-distributed flavour: K-wide message rows out[i * K + k] = src_k[idx[i]]; the entry / exit of a batched cycle on the
+// extended rows [own | overlap] (overlap rows read from the K-interleaved halo at sel[.], only own rows written back)
+void launch_pack_rows_split (int K, const int *idx, const double *const *src, double *out, int64_t nrows, hipStream_t st);
+void launch_gather_interleave_ext (int K, const int *perm, const double *const *src, const double *halo, const int *sel, int64_t n_own, double *out, int64_t n,
+                                   hipStream_t st);
+void launch_scatter_split_own (int K, const int *perm, const double *in, double *z, double *const *dst, int64_t n_own, int64_t n, hipStream_t st);
 void launch_dense_matvec_batch (int K, const double *Minv, const double *x, double *y, int n, hipStream_t st);
 // water-column solves of blocks [b0, b1), one column per wave / the fused half sweep, K columns
 void launch_colblock_apply_wave_batch (int K, const ColBlocksDev &B, int b0, int b1, const double *r, double *z, int accumulate, int r32, hipStream_t st);

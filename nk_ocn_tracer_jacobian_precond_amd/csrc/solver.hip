@@ -184,6 +184,13 @@ struct nkp_solver {
       int64_t n_ext = 0, n_sel = 0;
       int *sel_idx = nullptr;         // position in the halo of every overlap row
       double *rext = nullptr, *zext = nullptr;
+      // K right-hand sides in lockstep: the K-interleaved operator input [own rows | halo rows] x K, the
+      // K-wide send rows, the plan's counts times K, and the group's Gram-Schmidt messages
+      // gmsg = dots [K x (m + 2)] | second pass [K x (m + 2)] | norms [K] | 1 / norms [K], ghpin its pinned host mirror
+      double *bxe = nullptr, *bsend = nullptr, *gmsg = nullptr, *ghpin = nullptr;
+      int bK = 0;                     // width these buffers exist for
+      int agreed_K = 0;               // widest interleave every rank is known to have buffers for
+      std::vector<int> send_counts_k, recv_counts_k;
    } dist;
    int64_t n = 0, ld = 0;
    int m = 0;
@@ -207,12 +214,15 @@ struct nkp_solver {
    std::vector<nkp_solver *> batch_members;
    double *bvin = nullptr, *bz = nullptr, *bw = nullptr;
    int batch_K = 0;
+   int64_t batch_steps = 0;         // batched operator applications (lockstep Krylov steps) over the solver's life
+   int batch_width = 0;             // K of the last batched group
    size_t device_bytes = 0;
    double create_seconds = 0.0;     // wall time of nkp_create
    // nkp_refactor: state shared by a solver and its clones (live clones, a refactor that failed after its commit point),
    // the owner's work space, and the host arrays a rebuild of the hierarchy needs again
    struct Shared {
       std::atomic<int> clones { 0 };
+      std::atomic<int64_t> alltoallv_calls { 0 }, allreduce_calls { 0 };      // device collectives of solves (a batch's members count here too)
       bool broken = false;
       std::string why;
    };
@@ -279,6 +289,9 @@ static void solver_free (nkp_solver *s)
    if (s->dist.sel_idx) (void) hipFree (s->dist.sel_idx);
    if (s->dist.rext) (void) hipFree (s->dist.rext);
    if (s->dist.zext) (void) hipFree (s->dist.zext);
+   for (double *p : { s->dist.bxe, s->dist.bsend, s->dist.gmsg })
+      if (p) (void) hipFree (p);
+   if (s->dist.ghpin) (void) hipHostFree (s->dist.ghpin);
    if (s->dist.ev_packed) (void) hipEventDestroy (s->dist.ev_packed);
    if (s->dist.ev_halo) (void) hipEventDestroy (s->dist.ev_halo);
    if (s->dist.comm_stream) (void) hipStreamDestroy (s->dist.comm_stream);
@@ -300,15 +313,20 @@ static void msg (const nkp_solver *s, int lvl, const char *fmt, ...)
    fflush (stdout);
 }
 
+// the two device collectives of a solve; a failure leaves stale data behind and is checked before any verdict is returned
+static inline void alltoallv_dev (nkp_solver *s, const double *send, const int *send_counts, double *recv, const int *recv_counts, hipStream_t st)
+{
+   s->shared->alltoallv_calls++;
+   if (s->dist.ops.alltoallv (s->dist.ops.ctx, send, send_counts, recv, recv_counts, (void *) st)) s->comm_failed = true;
+}
+
 static void apply_precond_once (nkp_solver *s, const double *rin, double *zout)
 {
    if (s->opt.precond == NKP_PRECOND_NONE) launch_copy (rin, zout, s->n, s->stream);
    else if (s->opt.precond == NKP_PRECOND_MULTILEVEL && s->dist.ras) {
       // the residual on the overlap rows comes from their owners (same exchange pattern as the SpMV's halo)
       if (s->dist.nsend) launch_gather (s->dist.send_idx, rin, s->dist.sendbuf, s->dist.nsend, s->stream);
-      if (s->dist.ops.alltoallv (s->dist.ops.ctx, s->dist.sendbuf, s->dist.send_counts.data (), s->dist.xe + s->n,
-                                 s->dist.recv_counts.data (), (void *) s->stream))
-         s->comm_failed = true;
+      alltoallv_dev (s, s->dist.sendbuf, s->dist.send_counts.data (), s->dist.xe + s->n, s->dist.recv_counts.data (), s->stream);
       launch_copy (rin, s->dist.rext, s->n, s->stream);
       if (s->dist.n_sel) launch_gather (s->dist.sel_idx, s->dist.xe + s->n, s->dist.rext + s->n, s->dist.n_sel, s->stream);
       ml_apply (s->ml, s->dist.rext, s->dist.zext, s->stream);
@@ -346,9 +364,7 @@ static void spmv_op (nkp_solver *s, const double *x, double *y, const double *b,
          // result is the bit pattern of the serial version
          (void) hipEventRecord (s->dist.ev_packed, s->stream);
          (void) hipStreamWaitEvent (s->dist.comm_stream, s->dist.ev_packed, 0);
-         if (s->dist.ops.alltoallv (s->dist.ops.ctx, s->dist.sendbuf, s->dist.send_counts.data (), s->dist.xe + s->n,
-                                    s->dist.recv_counts.data (), (void *) s->dist.comm_stream))
-            s->comm_failed = true;
+         alltoallv_dev (s, s->dist.sendbuf, s->dist.send_counts.data (), s->dist.xe + s->n, s->dist.recv_counts.data (), s->dist.comm_stream);
          (void) hipEventRecord (s->dist.ev_halo, s->dist.comm_stream);
          launch_csr_spmv_range (s->A, s->dist.seg_rb[1], s->dist.seg_rb[2], xin, y, b, mode, s->stream);
          (void) hipStreamWaitEvent (s->stream, s->dist.ev_halo, 0);
@@ -356,9 +372,7 @@ static void spmv_op (nkp_solver *s, const double *x, double *y, const double *b,
          launch_csr_spmv_range (s->A, s->dist.seg_rb[2], s->dist.seg_rb[3], xin, y, b, mode, s->stream);
          return;
       }
-      if (s->dist.ops.alltoallv (s->dist.ops.ctx, s->dist.sendbuf, s->dist.send_counts.data (), s->dist.xe + s->n,
-                                 s->dist.recv_counts.data (), (void *) s->stream))
-         s->comm_failed = true;      // stale halo rows: checked before any verdict is returned
+      alltoallv_dev (s, s->dist.sendbuf, s->dist.send_counts.data (), s->dist.xe + s->n, s->dist.recv_counts.data (), s->stream);
    }
    if (mode == 2) launch_csr_abs_spmv (s->A, xin, b, y, s->stream);
    else launch_csr_spmv (s->A, xin, y, b, mode, s->stream);
@@ -366,7 +380,9 @@ static void spmv_op (nkp_solver *s, const double *x, double *y, const double *b,
 
 static inline void allreduce_dev (nkp_solver *s, double *dev, int count, int op)
 {
-   if (s->dist.on && s->dist.ops.allreduce (s->dist.ops.ctx, dev, count, op, (void *) s->stream)) s->comm_failed = true;
+   if (!s->dist.on) return;
+   s->shared->allreduce_calls++;
+   if (s->dist.ops.allreduce (s->dist.ops.ctx, dev, count, op, (void *) s->stream)) s->comm_failed = true;
 }
 
 // the SpMV matrix (device copy; columns may address halo slots >= n) and the matrix the preconditioner
@@ -786,6 +802,10 @@ extern "C" int64_t nkp_get_int (nkp_solver *s, const char *key)
    if (!strcmp (key, "refactor_rebuilt")) return s->refactor_rebuilt;
    if (!strcmp (key, "refactor_us")) return (int64_t) (s->refactor_seconds * 1.0e6);
    if (!strcmp (key, "refactor_halo_values")) return s->refactor_halo_values;
+   if (!strcmp (key, "dist_alltoallv_calls")) return s->shared->alltoallv_calls.load ();
+   if (!strcmp (key, "dist_allreduce_calls")) return s->shared->allreduce_calls.load ();
+   if (!strcmp (key, "batch_steps")) return s->batch_steps;
+   if (!strcmp (key, "batch_width")) return s->batch_width;
    return -1;
 }
 
@@ -1165,11 +1185,15 @@ extern "C" int nkp_solve_device (nkp_solver *s, const void *d_b, void *d_x, int 
 // A second set of work vectors (Krylov basis, level vectors, scalars) and a second stream on the SAME device-resident
 // matrix, factors and hierarchy: several right-hand sides can then be solved concurrently from different host threads,
 // one clone per thread.  Single-GPU solvers only.
-extern "C" int nkp_clone (nkp_solver *src, nkp_solver **out)
+//
+// member: the work vectors of one more system of a batched solve.  A member of a row-distributed solver shares its parent's
+// matrix, hierarchy, stream, plan and exchange buffers (all of its work is ordered on that one stream) and is only ever driven
+// from inside the parent's collective calls, so it adds no collective of its own.
+static int clone_impl (nkp_solver *src, nkp_solver **out, bool member)
 {
    if (!src || !out) return fail (NKP_EINVAL, "nkp_clone: NULL argument");
    *out = nullptr;
-   if (src->dist.on) return fail (NKP_EINVAL, "nkp_clone: not available for the row-distributed flavour");
+   if (src->dist.on && !member) return fail (NKP_EINVAL, "nkp_clone: not available for the row-distributed flavour");
    if (src->borrowed) return fail (NKP_EINVAL, "nkp_clone: clone the original solver, not a clone");
    HIPCHK (hipSetDevice (src->device));
    nkp_solver *s = new (std::nothrow) nkp_solver (*src);
@@ -1181,6 +1205,9 @@ extern "C" int nkp_clone (nkp_solver *src, nkp_solver **out)
    s->batch_members.clear ();
    s->bvin = s->bz = s->bw = nullptr;
    s->batch_K = 0;
+   s->dist.bxe = s->dist.bsend = s->dist.gmsg = s->dist.ghpin = nullptr;
+   s->dist.bK = s->dist.agreed_K = 0;
+   s->dplan = nullptr;
    s->A.tune = &s->tune;
    s->B.tune = &s->tune;
    s->ml.tune = &s->tune;
@@ -1232,6 +1259,8 @@ extern "C" int nkp_clone (nkp_solver *src, nkp_solver **out)
    return NKP_OK;
 }
 
+extern "C" int nkp_clone (nkp_solver *src, nkp_solver **out) { return clone_impl (src, out, false); }
+
 // ---------------------------------------------------------------- K right-hand sides in lockstep
 // The reference's RHS loop (src/solve_ABglobal.c:370-409) as ONE pass over the matrix and the hierarchy per Krylov step for K
 // systems: every system keeps its own FGMRES recurrence (own basis, own Hessenberg matrix, own restart decisions -- the state
@@ -1239,7 +1268,6 @@ extern "C" int nkp_clone (nkp_solver *src, nkp_solver **out)
 // (batch.hip).  Per system the operations and their order are those of a solve done alone, so are the bits.
 static const char *batch_unsupported (const nkp_solver *s)
 {
-   if (s->dist.on) return "the row-distributed flavour";
    if (s->borrowed) return "a clone";
    if (s->opt.krylov != NKP_KRYLOV_FGMRES) return "BiCGStab";
    if (s->equil) return "row equilibration";
@@ -1248,33 +1276,143 @@ static const char *batch_unsupported (const nkp_solver *s)
    return nullptr;
 }
 
+// Everything K systems in flight need.  Transactional per buffer set: after a failed allocation the set is gone and its
+// recorded width is 0 (never a width whose buffers are missing or short), and the sticky out-of-memory error is cleared, so
+// the narrower retry of the caller starts clean.
 static int batch_prepare (nkp_solver *s, int K)
 {
    while ((int) s->batch_members.size () < K - 1) {
       nkp_solver *c = nullptr;
-      const int rc = nkp_clone (s, &c);
-      if (rc) return rc;
+      const int rc = clone_impl (s, &c, true);
+      if (rc) { (void) hipGetLastError (); return rc; }
       if (c->own_stream && c->stream) (void) hipStreamDestroy (c->stream);
       c->stream = s->stream;
       c->own_stream = false;
       s->batch_members.push_back (c);
    }
-   if (s->batch_K < K) {
-      for (double **p : { &s->bvin, &s->bz, &s->bw }) {
-         if (*p) { (void) hipFree (*p); *p = nullptr; }
-         const int rc = dev_alloc (s, p, (size_t) s->ld * (size_t) K);
-         if (rc) return rc;
-         HIPCHK (hipMemset (*p, 0, (size_t) s->ld * (size_t) K * sizeof (double)));
+   // a set of device buffers of `count` doubles each, all or nothing
+   auto buffer_set = [s] (std::initializer_list<std::pair<double **, size_t>> set, int *width, int K_new) -> int {
+      auto drop = [s, &set] (int K_old) {
+         for (auto &e : set)
+            if (*e.first) {
+               const size_t count = e.second * (size_t) K_old;
+               (void) hipFree (*e.first);
+               *e.first = nullptr;
+               s->device_bytes -= (count ? count : 1) * sizeof (double);      // what dev_alloc added
+            }
+      };
+      drop (*width);
+      *width = 0;
+      int rc = NKP_OK;
+      for (auto &e : set) {
+         const size_t count = e.second * (size_t) K_new;
+         if ((rc = dev_alloc (s, e.first, count)) != NKP_OK) break;
+         if (hipMemset (*e.first, 0, (count ? count : 1) * sizeof (double)) != hipSuccess) { rc = fail (NKP_EDEVICE, "nkp_solve_batch: hipMemset failed"); break; }
       }
-      s->batch_K = K;
+      if (rc == NKP_OK) { *width = K_new; return NKP_OK; }
+      drop (K_new);
+      (void) hipGetLastError ();
+      return rc;
+   };
+   if (s->batch_K < K) {
+      const int rc = buffer_set ({ { &s->bvin, (size_t) s->ld }, { &s->bz, (size_t) s->ld }, { &s->bw, (size_t) s->ld } }, &s->batch_K, K);
+      if (rc) return rc;
+   }
+   if (s->dist.on && s->dist.bK < K) {
+      // the host mirror of the Hessenberg columns is small: made once for the widest group
+      if (!s->dist.ghpin && hipHostMalloc ((void **) &s->dist.ghpin, (size_t) NKP_BATCH_MAX * (size_t) (s->m + 2) * sizeof (double), hipHostMallocDefault) != hipSuccess) {
+         s->dist.ghpin = nullptr;
+         (void) hipGetLastError ();
+         return fail (NKP_ENOMEM, "nkp_solve_batch: pinned host memory for the Gram-Schmidt messages");
+      }
+      const size_t gcount = 2 * (size_t) (s->m + 2) + 2;
+      const int rc = buffer_set ({ { &s->dist.bxe, (size_t) (s->n + s->dist.n_halo) }, { &s->dist.bsend, (size_t) s->dist.nsend }, { &s->dist.gmsg, gcount } }, &s->dist.bK, K);
+      if (rc) return rc;
    }
    if (s->opt.precond == NKP_PRECOND_MULTILEVEL) {
       const size_t before = s->ml.device_bytes;
       const int mrc = ml_batch_prepare (s->ml, K);
+      s->device_bytes += s->ml.device_bytes - before;      // (unsigned wrap-around on a shrink is the intended subtraction)
       if (mrc) return fail (NKP_ENOMEM, "nkp_solve_batch: device memory for the level vectors of %d right-hand sides", K);
-      s->device_bytes += s->ml.device_bytes - before;
    }
    return NKP_OK;
+}
+
+// The group's operator application in the row-distributed flavour: ONE exchange of K-wide rows for the overlap rows of the
+// preconditioner and ONE for the halo of the SpMV, whatever K is.  The interleaved operator input is bxe = [own | halo] x K, so
+// the column indices of A (halo slots at >= n) address it unchanged; its halo part also receives the overlap residuals
+// (it is rewritten by the second exchange before A reads it).
+static void batch_apply_dist (nkp_solver *s, int K, const double *const *src, double *const *dz, double *const *dw)
+{
+   const int64_t n = s->n;
+   hipStream_t st = s->stream;
+   auto &D = s->dist;
+   D.send_counts_k.resize (D.send_counts.size ());
+   D.recv_counts_k.resize (D.recv_counts.size ());
+   for (size_t p = 0; p < D.send_counts.size (); p++) D.send_counts_k[p] = D.send_counts[p] * K;
+   for (size_t p = 0; p < D.recv_counts.size (); p++) D.recv_counts_k[p] = D.recv_counts[p] * K;
+   double *halo = D.bxe + n * K;
+   if (s->opt.precond == NKP_PRECOND_MULTILEVEL && D.ras) {
+      if (D.nsend) launch_pack_rows_split (K, D.send_idx, src, D.bsend, D.nsend, st);
+      alltoallv_dev (s, D.bsend, D.send_counts_k.data (), halo, D.recv_counts_k.data (), st);
+      ml_apply_batch_split_ext (s->ml, K, src, halo, D.sel_idx, n, D.bxe, dz, st);
+   } else if (s->opt.precond == NKP_PRECOND_MULTILEVEL) ml_apply_batch_split (s->ml, K, src, D.bxe, dz, st);
+   else {
+      launch_interleave (K, src, s->bvin, n, st);
+      if (s->opt.precond == NKP_PRECOND_COLUMN_JACOBI) {
+         if (launch_colblock_apply_lanes_batch (K, s->B, 0, s->B.ngrp, s->bvin, D.bxe, 0, st) != 0)
+            launch_colblock_apply_wave_batch (K, s->B, 0, s->B.nblk, s->bvin, D.bxe, 0, s->B.fac_tf ? 1 : 0, st);
+      } else
+         launch_copy (s->bvin, D.bxe, n * K, st);
+      launch_deinterleave (K, D.bxe, dz, n, st);
+   }
+   // w_k = A z_k: the rows other ranks need, K wide, then as spmv_op does it for one vector
+   if (D.nsend) launch_gather_batch (K, D.send_idx, D.bxe, D.bsend, D.nsend, st);
+   auto rows = [&] (int rb0, int rb1) {
+      if (s->tune.batch_spmv_rows) launch_csr_spmv_batch_split_range (K, s->A, rb0, rb1, D.bxe, dw, st);
+      else launch_csr_spmv_batch (K, s->A, rb0, rb1, D.bxe, s->bw, nullptr, 0, st);
+   };
+   if (D.overlap) {
+      (void) hipEventRecord (D.ev_packed, st);
+      (void) hipStreamWaitEvent (D.comm_stream, D.ev_packed, 0);
+      alltoallv_dev (s, D.bsend, D.send_counts_k.data (), halo, D.recv_counts_k.data (), D.comm_stream);
+      (void) hipEventRecord (D.ev_halo, D.comm_stream);
+      rows (D.seg_rb[1], D.seg_rb[2]);
+      (void) hipStreamWaitEvent (st, D.ev_halo, 0);
+      rows (D.seg_rb[0], D.seg_rb[1]);
+      rows (D.seg_rb[2], D.seg_rb[3]);
+   } else {
+      alltoallv_dev (s, D.bsend, D.send_counts_k.data (), halo, D.recv_counts_k.data (), st);
+      rows (0, s->A.nrowblk);
+   }
+   if (!s->tune.batch_spmv_rows) launch_deinterleave (K, s->bw, dw, n, st);
+}
+
+// Gram-Schmidt of the running systems (run[0 .. R-1], at column j) with the allreduces of ONE system: row r of each message
+// belongs to system run[r].  Per system this is arnoldi_orthogonalise, operation by operation.
+static void orthogonalise_group (nkp_solver *s, int R, nkp_solver *const *run, int j)
+{
+   const int64_t ld = s->ld, n = s->n;
+   hipStream_t st = s->stream;
+   const int k = j + 1, K = s->dist.bK;
+   double *msg = s->dist.gmsg, *msg2 = msg + (size_t) K * (size_t) (s->m + 2), *nrm = msg2 + (size_t) K * (size_t) (s->m + 2), *inv = nrm + K;
+   GsGroup G = {};
+   for (int r = 0; r < R; r++) { G.V[r] = run[r]->V; G.w[r] = run[r]->w; G.partial[r] = run[r]->partial; G.vnext[r] = run[r]->V + (int64_t) (j + 1) * ld; }
+   launch_multi_dot_group (R, G, ld, k, n, msg, st);
+   allreduce_dev (s, msg, R * (k + 1), 0);
+   launch_update_w_group (R, G, ld, k, msg, n, nrm, st);
+   if (s->opt.reorth) {
+      launch_multi_dot_group (R, G, ld, k, n, msg2, st);
+      allreduce_dev (s, msg2, R * (k + 1), 0);
+      launch_update_w_group (R, G, ld, k, msg2, n, nrm, st);
+      allreduce_dev (s, nrm, R, 0);
+      launch_finish_column_group (R, msg, msg2, k, nrm, inv, st);
+   } else if (s->tune.dist_one_reduce) launch_finish_column_group (R, msg, nullptr, k, nullptr, inv, st);
+   else {
+      allreduce_dev (s, nrm, R, 0);
+      launch_finish_column_group (R, msg, nullptr, k, nrm, inv, st);
+   }
+   launch_scale_to_group (R, G, inv, n, st);
 }
 
 // z_k = M^-1 v_k, w_k = A z_k for the running systems; v, z, w per system, the application batched
@@ -1323,6 +1461,26 @@ static int fgmres_batch (nkp_solver *s, int K, int nact, nkp_solver *const *mem,
       if (!nrun) break;
       // the running systems advance together: all of them are at column j of their cycle
       for (int j = 0; nrun; j++) {
+         s->batch_steps++;
+         if (s->dist.on) {
+            const int64_t ld = s->ld;
+            const double *src[NKP_BATCH_MAX] = {};
+            double *dz[NKP_BATCH_MAX] = {}, *dw[NKP_BATCH_MAX] = {};
+            nkp_solver *run[NKP_BATCH_MAX] = {};
+            int R = 0;
+            for (int k = 0; k < nact; k++)
+               if (running[k]) { src[k] = mem[k]->V + (int64_t) j * ld; dz[k] = mem[k]->Z + (int64_t) j * ld; dw[k] = mem[k]->w; run[R++] = mem[k]; }
+            batch_apply_dist (s, K, src, dz, dw);
+            orthogonalise_group (s, R, run, j);
+            HIPCHK (hipMemcpyAsync (s->dist.ghpin, s->dist.gmsg, (size_t) R * (size_t) (j + 2) * sizeof (double), hipMemcpyDeviceToHost, s->stream));
+            HIPCHK (hipStreamSynchronize (s->stream));
+            // stale halo rows or partial sums: no verdict is taken from them (the ranks' sequences of collectives would part)
+            if (s->comm_failed) return fail (NKP_ECOMM, "nkp_solve_batch: a collective of the distributed solve failed (lockstep step %lld)", (long long) s->batch_steps);
+            for (int r = 0; r < R; r++) memcpy (run[r]->hpin, s->dist.ghpin + (size_t) r * (size_t) (j + 2), (size_t) (j + 2) * sizeof (double));
+            for (int k = 0; k < nact; k++)
+               if (running[k] && fg_post_step (mem[k], F[k])) { running[k] = false; nrun--; }
+            continue;
+         }
          batch_apply (s, K, mem, running, j);
          for (int k = 0; k < nact; k++) {
             if (!running[k]) continue;
@@ -1339,6 +1497,8 @@ static int fgmres_batch (nkp_solver *s, int K, int nact, nkp_solver *const *mem,
    HIPCHK (hipGetLastError ());
    return NKP_OK;
 }
+
+static int dist_agree (nkp_solver *s, int local_rc, const char *who, const char *where);
 
 static int sev_of (int c) { return c == NKP_OK ? 0 : c == NKP_OK_BERR ? 1 : c == NKP_NOT_CONVERGED ? 2 : 3; }
 
@@ -1373,16 +1533,39 @@ extern "C" int nkp_solve_batch_device (nkp_solver *s, int nrhs, const void *d_B,
          continue;
       }
       int K = nact <= 2 ? 2 : nact <= 4 ? 4 : 8;
-      int rc = batch_prepare (s, K);
-      // every further system in flight costs a set of work vectors: out of device memory => narrower interleave, then one at a time
-      while (rc == NKP_ENOMEM && K > 2) {
-         K /= 2;
-         kmax = K;
-         if (nact > K) nact = K;
+      const int K_wanted = K;
+      int rc = NKP_OK;
+      if (!s->dist.on || K > s->dist.agreed_K) {
          rc = batch_prepare (s, K);
+         // every further system in flight costs a set of work vectors: out of device memory => narrower interleave, then one at a time
+         while (rc == NKP_ENOMEM && K > 2) {
+            K /= 2;
+            rc = batch_prepare (s, K);
+         }
+         if (rc == NKP_ENOMEM) { K = 1; rc = NKP_OK; }
       }
-      if (rc == NKP_ENOMEM) { kmax = 1; nact = 0; continue; }
+      if (s->dist.on && K_wanted > s->dist.agreed_K) {
+         // the width is a collective decision: every rank takes the narrowest one any rank reached, so that all of them run the
+         // same sequence of collectives; a rank with a hard failure returns its code, the others NKP_ECOMM naming it
+         const nkp_comm_ops &c = s->dist.ops;
+         std::vector<int64_t> all ((size_t) c.nranks + 1, 0);
+         const std::string mine = rc ? g_last_error : std::string ();
+         const bool comm_ok = c.allgather_i64_host (c.ctx, rc ? -1 : K, all.data ()) == 0;
+         if (rc) { g_last_error = mine; return rc; }
+         if (!comm_ok) return fail (NKP_ECOMM, "nkp_solve_batch: allgather failed (interleave width)");
+         for (int p = 0; p < c.nranks; p++) {
+            if (all[(size_t) p] < 0) return fail (NKP_ECOMM, "nkp_solve_batch: rank %d failed while preparing %d right-hand sides; see its message", p, K_wanted);
+            if (all[(size_t) p] < K) K = (int) all[(size_t) p];
+         }
+         if (K == K_wanted) s->dist.agreed_K = K;
+      }
       if (rc) return rc;
+      if (K < K_wanted) {
+         kmax = K;
+         if (K == 1) { nact = 0; continue; }
+         if (nact > K) nact = K;
+      }
+      s->batch_width = K;
       nkp_solver *mem[NKP_BATCH_MAX] = { s };
       for (int k = 1; k < K; k++) mem[k] = s->batch_members[(size_t) k - 1];
       for (int k = 0; k < nact; k++) {
@@ -1392,6 +1575,8 @@ extern "C" int nkp_solve_batch_device (nkp_solver *s, int nrhs, const void *d_B,
       }
       FgmresState F[NKP_BATCH_MAX];
       if ((rc = fgmres_batch (s, K, nact, mem, F)) < 0) return rc;
+      for (int k = 0; k < nact; k++)
+         if (mem[k]->comm_failed) return fail (NKP_ECOMM, "nkp_solve_batch: a collective of the distributed solve failed");
       for (int k = 0; k < nact; k++) {
          // the verdict of one system, exactly as solve_resident gives it for a solve done alone
          nkp_solver *q = mem[k];
@@ -1399,6 +1584,7 @@ extern "C" int nkp_solve_batch_device (nkp_solver *s, int nrhs, const void *d_B,
          double be = 0.0;
          if (berr || q->stagnated) {
             if ((rc = backward_error (q, &be))) return rc;
+            if (q->comm_failed) return fail (NKP_ECOMM, "nkp_solve_batch: a collective of the distributed solve failed");
             if (berr) berr[c0 + k] = be;
          }
          if (status == NKP_NOT_CONVERGED && q->stagnated && be <= fmax (NKP_BERR_ROUNDING_LEVEL, 1.0e-2 * s->opt.rtol)) status = NKP_OK_BERR;
@@ -1427,10 +1613,17 @@ extern "C" int nkp_solve (nkp_solver *s, double *b_in_x_out, int nrhs, int64_t l
       // several right-hand sides share the sweeps over the matrix and the hierarchy (same bits per column as one at a time)
       double *dB = nullptr;
       const int64_t ldd = s->ld;
-      if (hipMalloc ((void **) &dB, (size_t) ldd * (size_t) nrhs * sizeof (double)) != hipSuccess) return fail (NKP_ENOMEM, "nkp_solve: device memory for %d right-hand sides", nrhs);
       int status = NKP_OK;
+      if (hipMalloc ((void **) &dB, (size_t) ldd * (size_t) nrhs * sizeof (double)) != hipSuccess) {
+         dB = nullptr;
+         (void) hipGetLastError ();
+         status = fail (NKP_ENOMEM, "nkp_solve: device memory for %d right-hand sides", nrhs);
+      }
       for (int c = 0; c < nrhs && status == NKP_OK; c++)
          if (hipMemcpy (dB + (size_t) c * (size_t) ldd, b_in_x_out + (size_t) c * (size_t) ldb, bytes, hipMemcpyHostToDevice) != hipSuccess) status = fail (NKP_EDEVICE, "nkp_solve: upload of right-hand side %d failed", c);
+      // row-distributed: a rank that could not stage its right-hand sides must not leave the others alone in the collectives
+      if (s->dist.on) status = dist_agree (s, status, "nkp_solve", "staging the right-hand sides on the device");
+      if (status != NKP_OK) { if (dB) (void) hipFree (dB); return status; }
       if (status == NKP_OK) status = nkp_solve_batch_device (s, nrhs, dB, dB, ldd, berr, iters, relres);
       if (status >= 0)
          for (int c = 0; c < nrhs; c++)
@@ -1661,6 +1854,9 @@ static int refactor_dist_impl (nkp_solver *s, const double *h_val, const void *d
 {
    if (!s || (!h_val && !d_val)) return fail (NKP_EINVAL, "%s: NULL argument", who);
    if (!s->dist.on) return refactor_impl (s, h_val, d_val, flags, who);      // nkp_create_dist made a plain solver
+   // a rank that rebuilds its hierarchy drops its batch members (refactor_commit) and has to allocate them again, which can
+   // fail on that rank alone: the next batched solve agrees on its width anew on every rank
+   s->dist.agreed_K = 0;
    struct timespec ts0;
    clock_gettime (CLOCK_MONOTONIC, &ts0);
    const int64_t nnz = s->A.nnz;

@@ -364,7 +364,11 @@ class NkpDistSolver(_solver.NkpSolver):
     def __init__(self, loc, n_global, comm, coupled_tracer_cnt=1, **options):
         lib = _solver.load_library()
         self._comm = comm                      # keeps the callbacks alive
+        tuning = options.pop("tuning", None)   # an NkpTuning or a dict of overrides, as NkpSolver takes it; the same on every rank
         opt = _solver.default_options(**options)
+        if tuning is not None:
+            self._tuning = tuning if isinstance(tuning, _solver.NkpTuning) else _solver.default_tuning(**tuning)
+            opt.tuning = C.pointer(self._tuning)
         rp, ci, v, bs = loc["rowptr"], loc["colind"], loc["val"], loc["blk_start"]
         self._keep = (rp, ci, v, bs, loc.get("col_i"), loc.get("col_j"), loc.get("col_t"))
         if loc.get("col_i") is not None:
@@ -383,6 +387,20 @@ class NkpDistSolver(_solver.NkpSolver):
         if rc != 0:
             comm = self._comm
             raise _solver.NkpError(rc, self._lib.nkp_last_error().decode() + (" | comm: " + "; ".join(comm.errors) if comm.errors else ""))
+
+    def solve_many(self, B, raise_on_fail=True):
+        """nkp_solve with nrhs = B.shape[0] right-hand sides, collective: every rank calls it with the same number of rows,
+        each passing its own m_loc entries of every vector (ldb = m_loc).  Groups of 2 / 4 (8 with rhs_batch = 8) systems run in
+        lockstep with the collectives of one system per Krylov step; get_int("batch_steps") / ("batch_width") /
+        ("dist_alltoallv_calls") / ("dist_allreduce_calls") count them.  Returns (X, infos) for the local rows."""
+        B = np.asarray(B, np.float64)
+        if B.ndim != 2 or B.shape[1] != self.n:
+            raise ValueError(f"B must have shape (nrhs, {self.n}): this rank's rows of every right-hand side")
+        return super().solve_many(B, raise_on_fail)
+
+    def solve_batch_device(self, d_B, d_X, nrhs, ldb, raise_on_fail=True):
+        """nkp_solve_batch_device on this rank's device-resident rows (ldb >= m_loc); collective like solve_many."""
+        return super().solve_batch_device(d_B, d_X, nrhs, ldb, raise_on_fail)
 
     def refactor_dist(self, val_loc, rebuild=False):
         """nkp_refactor_dist (collective: every rank calls it): this rank's new values, nnz_loc of them in the order of the
