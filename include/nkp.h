@@ -135,6 +135,12 @@ typedef struct nkp_tuning {
    int col_sort_groups;      /* NKP_COL_SORT_GROUPS (1): packed column layout groups a colour's columns by length (less zero padding) */
    int batch_spmv_rows;      /* NKP_BATCH_SPMV_ROWS (1): batched SpMV stages the (value, column) stream in LDS and lets each row's lane gather
                                 its own K-wide rows of x; 0 = products parked in LDS, K / 2 passes */
+   int dist_ras_rings;       /* NKP_DIST_RAS_RINGS (1): depth of the overlap that dist_ras gives each rank's hierarchy, in rings of other
+                                ranks' water columns (ring k + 1 = the lateral columns that rows of ring k couple to); 2 .. 4 ask for that
+                                many, 0 = the default, anything else is NKP_EINVAL.  The ranks take the smallest depth any of them asks for.
+                                With two or more rings the overlap residual travels in an exchange of its own (still one per preconditioner
+                                application) instead of riding on the SpMV halo.  No effect without dist_ras, grid positions or a lateral
+                                cut (a tracer partition has no overlap) */
 } nkp_tuning;
 
 /* defaults, then the NKP_* environment overrides listed above */
@@ -264,7 +270,9 @@ int nkp_time_kernel (nkp_solver *s, int which, int arg, int reps, double *avg_ms
  * the setup kernels built; the smaller ones are built on the host);
  * compulsory HBM bytes of the pieces nkp_time_kernel times: "smoother_spmv_bytes", "column_solve_bytes", "cycle_bytes";
  * distributed flavour: "dist_overlap" (halo exchange hidden behind the interior rows), "dist_interior_rowblocks",
- * "dist_ras" (hierarchy overlaps the neighbouring ranks), "dist_ras_rows" (rows of other ranks in this rank's hierarchy);
+ * "dist_ras" (hierarchy overlaps the neighbouring ranks), "dist_ras_rows" (rows of other ranks in this rank's hierarchy, all rings),
+ * "dist_ras_rings" (the depth the ranks agreed on, 0 without overlap), "dist_halo_rows" (rows received before every SpMV),
+ * "dist_ras_recv_rows" (rows received per preconditioner application: the SpMV halo with one ring, the overlap rows with more);
  * counters, cumulative over the solver's life, per rank: "dist_alltoallv_calls", "dist_allreduce_calls" (every call of the two
  * device collectives made by solves, single or batched; 0 on a single-GPU solver), "batch_steps" (batched operator
  * applications = lockstep Krylov steps of a group of right-hand sides), "batch_width" (K of the last batched group, 0 if
@@ -417,7 +425,11 @@ int nkp_gather_root (nkp_solver *s, const double *x_loc, double *x_global);
  * "halo_rows" (global rows received before every SpMV; with grid positions in opt the halo is completed to whole water
  * columns), "send_rows" (own rows sent, grouped by destination), "need" / "give" (per-rank counts); hierarchy side, filled
  * when the overlap is on (nkp_dist_plan_size (p, "ras") == 1) -- the matrix on [own rows | overlap rows]: "rowptr",
- * "colind", "val" (double), "blk_start", "col_i", "col_j", "col_t", and "sel_hpos" (position in the halo of every overlap row). */
+ * "colind", "val" (double), "blk_start", "col_i", "col_j", "col_t", and "sel_hpos" (position in the halo of every overlap row, -1
+ * for rows of ring 2 and beyond, which the SpMV never reads).  The overlap rows follow the own rows in ascending global row order.
+ * "ras_rings" (size only) is the depth the ranks agreed on (0 without overlap); with two or more rings the overlap residual has
+ * an exchange of its own: "ras_send_rows" (own local rows sent, grouped by destination, ascending within each), "ras_need" /
+ * "ras_give" (per-rank row counts; the rows from rank p arrive in hierarchy order). */
 typedef struct nkp_dist_plan nkp_dist_plan;
 int nkp_dist_overlap_plan_host (nkp_dist_plan **out, const nkp_options *opt, int64_t n_global, int64_t fst_row, int64_t m_loc,
                                 int64_t nnz_loc, const int32_t *rowptr_loc, const int32_t *colind_glob, const double *val,

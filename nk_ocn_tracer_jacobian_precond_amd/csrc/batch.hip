@@ -389,6 +389,27 @@ void gather_interleave_ext_kernel (const int *__restrict__ perm, BatchPtrs src, 
    }
 }
 
+// the same when the overlap rows arrive on their own, in the hierarchy's order (two or more rings): row perm[i] >= n_own is
+// row perm[i] - n_own of the K-interleaved receive block
+template <int K>
+__global__ __launch_bounds__ (BT_THREADS)
+void gather_interleave_ext_block_kernel (const int *__restrict__ perm, BatchPtrs src, const double *__restrict__ recv, int64_t n_own,
+                                         double *__restrict__ out, int64_t n)
+{
+   const int64_t stride = (int64_t) gridDim.x * BT_THREADS;
+   for (int64_t i = (int64_t) blockIdx.x * BT_THREADS + threadIdx.x; i < n; i += stride) {
+      const int64_t pi = perm[i];
+      if (pi < n_own) {
+#pragma unroll
+         for (int k = 0; k < K; k++) out[i * K + k] = src.p[k] ? src.p[k][pi] : 0.0;
+      } else {
+         const double *h = recv + (pi - n_own) * K;
+#pragma unroll
+         for (int k = 0; k < K; k++) out[i * K + k] = src.p[k] ? h[k] : 0.0;
+      }
+   }
+}
+
 // scatter_split_kernel that keeps the own rows only (the correction on the overlap rows belongs to their owners)
 template <int K>
 __global__ __launch_bounds__ (BT_THREADS)
@@ -476,6 +497,12 @@ void launch_gather_interleave_ext (int K, const int *perm, const double *const *
    BatchPtrs P;
    for (int k = 0; k < NKP_BATCH_MAX; k++) P.p[k] = k < K ? src[k] : nullptr;
    if (n > 0) BT_K (gather_interleave_ext_kernel, dim3 (bt_grid (n)), perm, P, halo, sel, n_own, out, n);
+}
+void launch_gather_interleave_ext_block (int K, const int *perm, const double *const *src, const double *recv, int64_t n_own, double *out, int64_t n, hipStream_t st)
+{
+   BatchPtrs P;
+   for (int k = 0; k < NKP_BATCH_MAX; k++) P.p[k] = k < K ? src[k] : nullptr;
+   if (n > 0) BT_K (gather_interleave_ext_block_kernel, dim3 (bt_grid (n)), perm, P, recv, n_own, out, n);
 }
 void launch_scatter_split_own (int K, const int *perm, const double *in, double *z, double *const *dst, int64_t n_own, int64_t n, hipStream_t st)
 {

@@ -1739,12 +1739,14 @@ void ml_apply_batch_split (MlHierarchy &H, int K, const double *const *src, doub
 }
 
 // the same on the extended rows of a rank of the row-distributed flavour: level 0 has n_own own rows followed by the overlap
-// rows, whose residuals are the K-interleaved halo rows halo[sel[.] * K + k]; z and dst receive the own rows only
+// rows, whose residuals are the K-interleaved halo rows halo[sel[.] * K + k] (sel NULL: halo is the K-interleaved block of the
+// overlap rows in their own order); z and dst receive the own rows only
 void ml_apply_batch_split_ext (MlHierarchy &H, int K, const double *const *src, const double *halo, const int *sel, int64_t n_own, double *z,
                                double *const *dst, hipStream_t st)
 {
    MlLevel &V = H.lev[0];
-   launch_gather_interleave_ext (K, H.perm0, src, halo, sel, n_own, V.bb, V.n, st);
+   if (sel) launch_gather_interleave_ext (K, H.perm0, src, halo, sel, n_own, V.bb, V.n, st);
+   else launch_gather_interleave_ext_block (K, H.perm0, src, halo, n_own, V.bb, V.n, st);
    ml_cycle_batch (H, K, 0, st);
    launch_scatter_split_own (K, H.perm0, V.bxnow (), z, dst, n_own, V.n, st);
 }

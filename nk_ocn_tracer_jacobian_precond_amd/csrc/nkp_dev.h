@@ -207,6 +207,7 @@ void launch_csr_spmv_batch_split_range (int K, const CsrDev &A, int rb0, int rb1
 void launch_pack_rows_split (int K, const int *idx, const double *const *src, double *out, int64_t nrows, hipStream_t st);
 void launch_gather_interleave_ext (int K, const int *perm, const double *const *src, const double *halo, const int *sel, int64_t n_own, double *out, int64_t n,
                                    hipStream_t st);
+void launch_gather_interleave_ext_block (int K, const int *perm, const double *const *src, const double *recv, int64_t n_own, double *out, int64_t n, hipStream_t st);
 void launch_scatter_split_own (int K, const int *perm, const double *in, double *z, double *const *dst, int64_t n_own, int64_t n, hipStream_t st);
 void launch_dense_matvec_batch (int K, const double *Minv, const double *x, double *y, int n, hipStream_t st);
 // water-column solves of blocks [b0, b1), one column per wave / the fused half sweep, K columns

@@ -90,7 +90,7 @@ static void builtin_tuning (nkp_tuning *t)
    t->col_group = 8; t->col_pipe_min = 0; t->col_ldsres_early = 0; t->col_ldsres_packed = 1; t->col_sort_groups = 1;
    t->spmv_variant = 4; t->spmv_compress = 0; t->spmv_pipe_min = 1024; t->spmv_run = 1; t->spmv_wgs = 256;
    t->rhs_batch = 1; t->batch_spmv_rows = 1; t->precond_steps = 0; t->equil = -1; t->dist_overlap = 1; t->dist_ras = 1; t->dist_one_reduce = 0; t->force_dist = 0; t->setup_threads = 0; t->plan_times = 0;
-   t->ml_drop_intertracer = 0; t->ml_huge_from = -1;
+   t->ml_drop_intertracer = 0; t->ml_huge_from = -1; t->dist_ras_rings = 1;
 }
 
 const nkp_tuning &nkp_builtin_tuning ()
@@ -131,6 +131,7 @@ extern "C" int nkp_default_tuning (nkp_tuning *t)
    ENV_POS ("NKP_SETUP_THREADS", setup_threads);
    if (getenv ("NKP_ML_PLAN_TIMES")) t->plan_times = 1;
    ENV_FLAG ("NKP_ML_DROP_INTERTRACER", ml_drop_intertracer);
+   ENV_INT ("NKP_DIST_RAS_RINGS", dist_ras_rings);
 #undef ENV_INT
 #undef ENV_POS
 #undef ENV_FLAG
@@ -138,15 +139,23 @@ extern "C" int nkp_default_tuning (nkp_tuning *t)
    return NKP_OK;
 }
 
-// the caller's knobs, or the defaults + environment (the one place a solver looks at the environment)
-static int resolve_tuning (const nkp_options *opt, nkp_tuning *out)
+// the caller's knobs, or the defaults + environment (the one place a solver looks at the environment); *range_error tells a
+// value out of range (out is filled) from a struct of the wrong size (out is not)
+static int resolve_tuning (const nkp_options *opt, nkp_tuning *out, bool *range_error = nullptr)
 {
+   if (range_error) *range_error = false;
    if (opt && opt->tuning) {
       if (opt->tuning->struct_size != (int) sizeof (nkp_tuning)) return fail (NKP_EINVAL, "nkp_tuning.struct_size mismatch (%d != %zu)", opt->tuning->struct_size, sizeof (nkp_tuning));
       *out = *opt->tuning;
-      return NKP_OK;
+   } else {
+      const int rc = nkp_default_tuning (out);
+      if (rc) return rc;
    }
-   return nkp_default_tuning (out);
+   if (out->dist_ras_rings < 0 || out->dist_ras_rings > 4) {
+      if (range_error) *range_error = true;
+      return fail (NKP_EINVAL, "nkp_tuning.dist_ras_rings = %d is out of range (0 = default, 1 .. 4 rings)", out->dist_ras_rings);
+   }
+   return NKP_OK;
 }
 
 // ---------------------------------------------------------------- solver object
@@ -182,8 +191,17 @@ struct nkp_solver {
       // couple to laterally (one ring); a cycle runs on [own rows | those halo rows] and only the own part is kept
       bool ras = false;
       int64_t n_ext = 0, n_sel = 0;
-      int *sel_idx = nullptr;         // position in the halo of every overlap row
+      int *sel_idx = nullptr;         // position in the halo of every overlap row (one ring)
       double *rext = nullptr, *zext = nullptr;
+      // two or more rings (tuning dist_ras_rings): rows of ring 2 and beyond are not in the SpMV halo, so the overlap residual has
+      // an exchange of its own -- own rows sent (by destination), their packed values, per-rank counts; the rows arrive at
+      // rext + n in the hierarchy's order.  bras_send / bras_recv: the same K wide (batch_prepare)
+      int ras_rings = 0;              // the depth the ranks agreed on, 0 without overlap
+      bool ras_sep = false;
+      int64_t ras_nsend = 0;
+      int *ras_send_idx = nullptr;
+      double *ras_sendbuf = nullptr, *bras_send = nullptr, *bras_recv = nullptr;
+      std::vector<int> ras_send_counts, ras_recv_counts, ras_send_counts_k, ras_recv_counts_k;
       // K right-hand sides in lockstep: the K-interleaved operator input [own rows | halo rows] x K, the
       // K-wide send rows, the plan's counts times K, and the group's Gram-Schmidt messages
       // gmsg = dots [K x (m + 2)] | second pass [K x (m + 2)] | norms [K] | 1 / norms [K], ghpin its pinned host mirror
@@ -287,9 +305,11 @@ static void solver_free (nkp_solver *s)
    if (s->dist.sendbuf) (void) hipFree (s->dist.sendbuf);
    if (s->dist.xe) (void) hipFree (s->dist.xe);
    if (s->dist.sel_idx) (void) hipFree (s->dist.sel_idx);
+   if (s->dist.ras_send_idx) (void) hipFree (s->dist.ras_send_idx);
+   if (s->dist.ras_sendbuf) (void) hipFree (s->dist.ras_sendbuf);
    if (s->dist.rext) (void) hipFree (s->dist.rext);
    if (s->dist.zext) (void) hipFree (s->dist.zext);
-   for (double *p : { s->dist.bxe, s->dist.bsend, s->dist.gmsg })
+   for (double *p : { s->dist.bxe, s->dist.bsend, s->dist.gmsg, s->dist.bras_send, s->dist.bras_recv })
       if (p) (void) hipFree (p);
    if (s->dist.ghpin) (void) hipHostFree (s->dist.ghpin);
    if (s->dist.ev_packed) (void) hipEventDestroy (s->dist.ev_packed);
@@ -324,11 +344,18 @@ static void apply_precond_once (nkp_solver *s, const double *rin, double *zout)
 {
    if (s->opt.precond == NKP_PRECOND_NONE) launch_copy (rin, zout, s->n, s->stream);
    else if (s->opt.precond == NKP_PRECOND_MULTILEVEL && s->dist.ras) {
-      // the residual on the overlap rows comes from their owners (same exchange pattern as the SpMV's halo)
-      if (s->dist.nsend) launch_gather (s->dist.send_idx, rin, s->dist.sendbuf, s->dist.nsend, s->stream);
-      alltoallv_dev (s, s->dist.sendbuf, s->dist.send_counts.data (), s->dist.xe + s->n, s->dist.recv_counts.data (), s->stream);
-      launch_copy (rin, s->dist.rext, s->n, s->stream);
-      if (s->dist.n_sel) launch_gather (s->dist.sel_idx, s->dist.xe + s->n, s->dist.rext + s->n, s->dist.n_sel, s->stream);
+      if (s->dist.ras_sep) {
+         // several rings: the overlap rows alone, straight into place behind the own rows
+         if (s->dist.ras_nsend) launch_gather (s->dist.ras_send_idx, rin, s->dist.ras_sendbuf, s->dist.ras_nsend, s->stream);
+         alltoallv_dev (s, s->dist.ras_sendbuf, s->dist.ras_send_counts.data (), s->dist.rext + s->n, s->dist.ras_recv_counts.data (), s->stream);
+         launch_copy (rin, s->dist.rext, s->n, s->stream);
+      } else {
+         // the residual on the overlap rows comes from their owners (same exchange pattern as the SpMV's halo)
+         if (s->dist.nsend) launch_gather (s->dist.send_idx, rin, s->dist.sendbuf, s->dist.nsend, s->stream);
+         alltoallv_dev (s, s->dist.sendbuf, s->dist.send_counts.data (), s->dist.xe + s->n, s->dist.recv_counts.data (), s->stream);
+         launch_copy (rin, s->dist.rext, s->n, s->stream);
+         if (s->dist.n_sel) launch_gather (s->dist.sel_idx, s->dist.xe + s->n, s->dist.rext + s->n, s->dist.n_sel, s->stream);
+      }
       ml_apply (s->ml, s->dist.rext, s->dist.zext, s->stream);
       launch_copy (s->dist.zext, zout, s->n, s->stream);
    } else if (s->opt.precond == NKP_PRECOND_MULTILEVEL) ml_apply (s->ml, rin, zout, s->stream);
@@ -791,6 +818,10 @@ extern "C" int64_t nkp_get_int (nkp_solver *s, const char *key)
    if (!strcmp (key, "dist_overlap")) return s->dist.overlap ? 1 : 0;
    if (!strcmp (key, "dist_ras")) return s->dist.ras ? 1 : 0;
    if (!strcmp (key, "dist_ras_rows")) return s->dist.n_sel;
+   if (!strcmp (key, "dist_ras_rings")) return s->dist.ras ? s->dist.ras_rings : 0;
+   if (!strcmp (key, "dist_halo_rows")) return s->dist.n_halo;
+   // rows received per preconditioner application: the SpMV halo with one ring, the overlap rows alone with more
+   if (!strcmp (key, "dist_ras_recv_rows")) return !s->dist.ras ? 0 : s->dist.ras_sep ? s->dist.n_sel : s->dist.n_halo;
    if (!strcmp (key, "dist_interior_rowblocks")) return s->dist.seg_rb[2] - s->dist.seg_rb[1];
    if (!strcmp (key, "smoother_spmv_bytes")) return s->opt.precond == NKP_PRECOND_MULTILEVEL ? ml_bytes (s->ml, 0) : 0;
    if (!strcmp (key, "column_solve_bytes")) return s->opt.precond == NKP_PRECOND_MULTILEVEL ? ml_bytes (s->ml, 1) : 0;
@@ -1205,7 +1236,7 @@ static int clone_impl (nkp_solver *src, nkp_solver **out, bool member)
    s->batch_members.clear ();
    s->bvin = s->bz = s->bw = nullptr;
    s->batch_K = 0;
-   s->dist.bxe = s->dist.bsend = s->dist.gmsg = s->dist.ghpin = nullptr;
+   s->dist.bxe = s->dist.bsend = s->dist.gmsg = s->dist.ghpin = s->dist.bras_send = s->dist.bras_recv = nullptr;
    s->dist.bK = s->dist.agreed_K = 0;
    s->dplan = nullptr;
    s->A.tune = &s->tune;
@@ -1326,7 +1357,10 @@ static int batch_prepare (nkp_solver *s, int K)
          return fail (NKP_ENOMEM, "nkp_solve_batch: pinned host memory for the Gram-Schmidt messages");
       }
       const size_t gcount = 2 * (size_t) (s->m + 2) + 2;
-      const int rc = buffer_set ({ { &s->dist.bxe, (size_t) (s->n + s->dist.n_halo) }, { &s->dist.bsend, (size_t) s->dist.nsend }, { &s->dist.gmsg, gcount } }, &s->dist.bK, K);
+      const int rc = s->dist.ras_sep
+                        ? buffer_set ({ { &s->dist.bxe, (size_t) (s->n + s->dist.n_halo) }, { &s->dist.bsend, (size_t) s->dist.nsend }, { &s->dist.gmsg, gcount },
+                                        { &s->dist.bras_send, (size_t) s->dist.ras_nsend }, { &s->dist.bras_recv, (size_t) s->dist.n_sel } }, &s->dist.bK, K)
+                        : buffer_set ({ { &s->dist.bxe, (size_t) (s->n + s->dist.n_halo) }, { &s->dist.bsend, (size_t) s->dist.nsend }, { &s->dist.gmsg, gcount } }, &s->dist.bK, K);
       if (rc) return rc;
    }
    if (s->opt.precond == NKP_PRECOND_MULTILEVEL) {
@@ -1352,7 +1386,16 @@ static void batch_apply_dist (nkp_solver *s, int K, const double *const *src, do
    for (size_t p = 0; p < D.send_counts.size (); p++) D.send_counts_k[p] = D.send_counts[p] * K;
    for (size_t p = 0; p < D.recv_counts.size (); p++) D.recv_counts_k[p] = D.recv_counts[p] * K;
    double *halo = D.bxe + n * K;
-   if (s->opt.precond == NKP_PRECOND_MULTILEVEL && D.ras) {
+   if (s->opt.precond == NKP_PRECOND_MULTILEVEL && D.ras_sep) {
+      // several rings: the overlap rows alone, K wide, into a block of their own in the hierarchy's order
+      D.ras_send_counts_k.resize (D.ras_send_counts.size ());
+      D.ras_recv_counts_k.resize (D.ras_recv_counts.size ());
+      for (size_t p = 0; p < D.ras_send_counts.size (); p++) D.ras_send_counts_k[p] = D.ras_send_counts[p] * K;
+      for (size_t p = 0; p < D.ras_recv_counts.size (); p++) D.ras_recv_counts_k[p] = D.ras_recv_counts[p] * K;
+      if (D.ras_nsend) launch_pack_rows_split (K, D.ras_send_idx, src, D.bras_send, D.ras_nsend, st);
+      alltoallv_dev (s, D.bras_send, D.ras_send_counts_k.data (), D.bras_recv, D.ras_recv_counts_k.data (), st);
+      ml_apply_batch_split_ext (s->ml, K, src, D.bras_recv, nullptr, n, D.bxe, dz, st);
+   } else if (s->opt.precond == NKP_PRECOND_MULTILEVEL && D.ras) {
       if (D.nsend) launch_pack_rows_split (K, D.send_idx, src, D.bsend, D.nsend, st);
       alltoallv_dev (s, D.bsend, D.send_counts_k.data (), halo, D.recv_counts_k.data (), st);
       ml_apply_batch_split_ext (s->ml, K, src, halo, D.sel_idx, n, D.bxe, dz, st);
@@ -2150,6 +2193,11 @@ struct DistPlan {
    // -1 - position in the received overlap values), the own entries shipped (in val_s order) and the entry counts per rank
    std::vector<int32_t> e_org, ship_e;
    std::vector<int> ent_give, ent_need;
+   // the depth the ranks agreed on (0: no overlap); with two or more rings the overlap rows are not all in the SpMV halo and
+   // the residual of the cycle has an exchange of its own: own local rows sent (by destination, ascending), rows per rank
+   int rings = 0;
+   std::vector<int32_t> ras_send_rows;
+   std::vector<int> ras_need, ras_give;
 };
 
 static int dist_plan (DistPlan &D, const nkp_comm_ops *comm, const nkp_options &o, const std::vector<int64_t> &starts, int64_t fst_row, int64_t m_loc,
@@ -2205,16 +2253,28 @@ static int dist_plan (DistPlan &D, const nkp_comm_ops *comm, const nkp_options &
    // residual of the overlap rows fetched from their owners, and only the own part of the result is kept (prototype:
    // 36 / 43 / 55).  Columns of OTHER TRACERS at a cell this rank owns are not overlap (a tracer-per-rank partition keeps
    // its block-Jacobi preconditioner): a halo column joins only if its (i, j) is not the position of an own column.
+   // dist_ras_rings > 1 deepens the overlap ring by ring (prototype, 3 degrees, 4 bands: 63 / 56 / 53 / 51 iterations for 1-4
+   // rings); each ring is one more round of the fetch below.
    const bool geo = o.col_i && o.col_j && blk_start_loc && nblk_loc > 0;
    int64_t want_ras = (o.precond == NKP_PRECOND_MULTILEVEL && geo) ? 1 : 0;
+   int64_t rings = 1;
    {
+      // the depth this rank asks for rides on the message that decides the overlap (0 = none); the ranks take the smallest.
+      // -1 = a depth out of range: every rank refuses it together
       nkp_tuning tune;
-      if (resolve_tuning (&o, &tune) == NKP_OK && !tune.dist_ras) want_ras = 0;      // a bad tuning struct is reported by the create call itself
-   }
-   {
+      bool range_error = false;
+      if (resolve_tuning (&o, &tune, &range_error) == NKP_OK) {      // a struct of the wrong size is reported by the create call itself
+         if (!tune.dist_ras) want_ras = 0;
+         rings = tune.dist_ras_rings > 0 ? tune.dist_ras_rings : 1;
+      }
+      const std::string mine = range_error ? g_last_error : std::string ();
       std::vector<int64_t> all (P + 1, 0);
-      if (comm->allgather_i64_host (comm->ctx, want_ras, all.data ())) return fail (NKP_ECOMM, "nkp_create_dist: allgather failed");
-      for (int p = 0; p < P; p++) want_ras = want_ras && all[p];
+      if (comm->allgather_i64_host (comm->ctx, range_error ? -1 : want_ras * rings, all.data ())) return fail (NKP_ECOMM, "nkp_create_dist: allgather failed");
+      if (range_error) { g_last_error = mine; return NKP_EINVAL; }
+      for (int p = 0; p < P; p++)
+         if (all[p] < 0) return fail (NKP_ECOMM, "nkp_create_dist: rank %d failed its checks (tuning); see its message", p);
+      for (int p = 0; p < P; p++) rings = std::min (rings, all[p]);
+      want_ras = rings > 0 ? 1 : 0;
    }
    if (want_ras) {
 #define XCHG(sendp, scnt, recvp, rcnt, what) do { if (comm->alltoallv_i32_host (comm->ctx, (sendp), (scnt), (recvp), (rcnt))) return fail (NKP_ECOMM, "nkp_create_dist: %s exchange failed", what); } while (0)
@@ -2250,12 +2310,15 @@ static int dist_plan (DistPlan &D, const nkp_comm_ops *comm, const nkp_options &
       std::vector<int> give3 (P), need3 (P);
       for (int p = 0; p < P; p++) { give3[p] = 3 * give_cols[p]; need3[p] = 3 * need_cols[p]; }
       std::vector<int32_t> meta_s (3 * out_cols.size () + 1), meta_r (3 * (size_t) n_hcol + 1);
-      for (size_t k = 0; k < out_cols.size (); k++) {
-         const int c = out_cols[k];
-         meta_s[3 * k] = blk_start_loc[c + 1] - blk_start_loc[c];
-         meta_s[3 * k + 1] = o.col_i[c];
-         meta_s[3 * k + 2] = o.col_j[c];
-      }
+      auto fill_meta = [&] () {
+         for (size_t k = 0; k < out_cols.size (); k++) {
+            const int c = out_cols[k];
+            meta_s[3 * k] = blk_start_loc[c + 1] - blk_start_loc[c];
+            meta_s[3 * k + 1] = o.col_i[c];
+            meta_s[3 * k + 2] = o.col_j[c];
+         }
+      };
+      fill_meta ();
       XCHG (meta_s.data (), give3.data (), meta_r.data (), need3.data (), "overlap column");
       // sanity of what arrived: ascending rows, every originally needed row present, lengths adding up
       {
@@ -2281,74 +2344,218 @@ static int dist_plan (DistPlan &D, const nkp_comm_ops *comm, const nkp_options &
       nsend = (int64_t) out_rows.size ();
       send_rows.assign (out_rows.begin (), out_rows.end ());
       send_rows.push_back (0);
-      // requester: which halo columns are lateral neighbours (position not owned here)
       std::vector<int64_t> own_pos ((size_t) nblk_loc);
       for (int64_t c = 0; c < nblk_loc; c++) own_pos[(size_t) c] = ((int64_t) o.col_j[c] << 32) | (uint32_t) o.col_i[c];
       std::sort (own_pos.begin (), own_pos.end ());
-      std::vector<int32_t> flag_s ((size_t) n_hcol + 1, 0), flag_r (out_cols.size () + 1, 0);
-      std::vector<int> erow_need (P, 0), erow_give (P, 0);
-      {
-         size_t c = 0;
-         for (int p = 0; p < P; p++)
-            for (int k = 0; k < need_cols[p]; k++, c++) {
-               const int64_t key = ((int64_t) meta_r[3 * c + 2] << 32) | (uint32_t) meta_r[3 * c + 1];
-               flag_s[c] = std::binary_search (own_pos.begin (), own_pos.end (), key) ? 0 : 1;
-               if (flag_s[c]) erow_need[p] += meta_r[3 * c];
-            }
-      }
-      XCHG (flag_s.data (), need_cols.data (), flag_r.data (), give_cols.data (), "overlap selection");
-      // owner: ship the rows of the selected columns (entries per row, global columns, values as pairs of int32)
-      std::vector<int32_t> len_s, col_s, val_s;
-      std::vector<int> ent_give (P, 0), ent_need (P, 0), ent2_give (P, 0), ent2_need (P, 0);
-      {
-         size_t c = 0;
-         for (int p = 0; p < P; p++)
-            for (int k = 0; k < give_cols[p]; k++, c++) {
-               if (!flag_r[c]) continue;
-               const int col = out_cols[c];
-               for (int r = blk_start_loc[col]; r < blk_start_loc[col + 1]; r++) {
-                  len_s.push_back (rowptr_loc[r + 1] - rowptr_loc[r]);
-                  erow_give[p]++;
-                  for (int e = rowptr_loc[r]; e < rowptr_loc[r + 1]; e++) {
-                     D.ship_e.push_back ((int32_t) e);
-                     col_s.push_back (colind_glob[e]);
-                     int32_t w[2];
-                     memcpy (w, &val[e], sizeof (double));
-                     val_s.push_back (w[0]);
-                     val_s.push_back (w[1]);
-                  }
-                  ent_give[p] += rowptr_loc[r + 1] - rowptr_loc[r];
+
+      // ---- the rings.  Ring 1 = the lateral columns of the completed halo; ring k + 1 = the lateral columns of other ranks,
+      // in no earlier ring, that rows of ring k couple to.  Every ring is one round of: owner completes the requested rows to
+      // whole columns and ships (rows, length, i, j) [ring 1: the halo exchange above], requester selects, owner ships the
+      // selected rows (lengths, global columns, values).  What arrives is kept per row and ordered once all rings are in.
+      struct OvCol { int32_t g0; int len, ci, cj, ring; int64_t row0; };
+      std::vector<OvCol> ocols;
+      std::vector<int32_t> arr_gid, arr_col;                  // per arrived row: global id; per entry: global column
+      std::vector<int64_t> arr_ptr (1, 0);
+      std::vector<double> arr_val;
+      std::vector<int32_t> ov_sorted;                         // global rows of the overlap so far, ascending
+      std::vector<std::vector<int32_t>> shipped ((size_t) P); // owner: own local rows shipped to each rank over all rings
+      // rows_r: global ids of the completed rows, column after column; meta_r: (length, i, j) per column, need_cols[p] from rank p
+      auto select_and_fetch = [&] (int ring, const std::vector<int32_t> &rows_r, int64_t *n_new) -> int {
+         int64_t ncol_r = 0;
+         for (int p = 0; p < P; p++) ncol_r += need_cols[p];
+         // requester: which completed columns join this ring (position not owned here, not in an earlier ring)
+         std::vector<int32_t> flag_s ((size_t) ncol_r + 1, 0), flag_r (out_cols.size () + 1, 0);
+         std::vector<int> erow_need (P, 0), erow_give (P, 0);
+         {
+            size_t c = 0;
+            int64_t hpos = 0;
+            for (int p = 0; p < P; p++)
+               for (int k = 0; k < need_cols[p]; k++, c++) {
+                  const int64_t key = ((int64_t) meta_r[3 * c + 2] << 32) | (uint32_t) meta_r[3 * c + 1];
+                  flag_s[c] = std::binary_search (own_pos.begin (), own_pos.end (), key) ? 0 : 1;
+                  if (flag_s[c] && std::binary_search (ov_sorted.begin (), ov_sorted.end (), rows_r[(size_t) hpos])) flag_s[c] = 0;
+                  if (flag_s[c]) erow_need[p] += meta_r[3 * c];
+                  hpos += meta_r[3 * c];
                }
-            }
-      }
-      int64_t n_erow = 0;
-      for (int p = 0; p < P; p++) n_erow += erow_need[p];
-      std::vector<int32_t> len_r ((size_t) n_erow + 1);
-      len_s.push_back (0);
-      XCHG (len_s.data (), erow_give.data (), len_r.data (), erow_need.data (), "overlap row length");
-      int64_t n_eent = 0;
-      {
-         size_t q = 0;
-         for (int p = 0; p < P; p++) {
-            int64_t t = 0;
-            for (int k = 0; k < erow_need[p]; k++, q++) t += len_r[q];
-            if (2 * t >= 2147483647LL || 2 * (int64_t) ent_give[p] >= 2147483647LL) { rc = fail (NKP_EINVAL, "nkp_create_dist: overlap rows exceed the int32 exchange counts"); t = 0; ent_give[p] = 0; }
-            ent_need[p] = (int) t;
-            n_eent += t;
          }
-         if ((rc = agree (rc, "overlap sizes"))) return rc;
-         for (int p = 0; p < P; p++) { ent2_give[p] = 2 * ent_give[p]; ent2_need[p] = 2 * ent_need[p]; }
-         D.ent_give = ent_give;
-         D.ent_need = ent_need;
+         XCHG (flag_s.data (), need_cols.data (), flag_r.data (), give_cols.data (), "overlap selection");
+         // owner: ship the rows of the selected columns (entries per row, global columns, values as pairs of int32)
+         std::vector<int32_t> len_s, col_s, val_s;
+         std::vector<int> ent_give (P, 0), ent_need (P, 0), ent2_give (P, 0), ent2_need (P, 0);
+         {
+            size_t c = 0;
+            for (int p = 0; p < P; p++)
+               for (int k = 0; k < give_cols[p]; k++, c++) {
+                  if (!flag_r[c]) continue;
+                  const int col = out_cols[c];
+                  for (int r = blk_start_loc[col]; r < blk_start_loc[col + 1]; r++) {
+                     len_s.push_back (rowptr_loc[r + 1] - rowptr_loc[r]);
+                     erow_give[p]++;
+                     shipped[(size_t) p].push_back (r);
+                     for (int e = rowptr_loc[r]; e < rowptr_loc[r + 1]; e++) {
+                        col_s.push_back (colind_glob[e]);
+                        int32_t w[2];
+                        memcpy (w, &val[e], sizeof (double));
+                        val_s.push_back (w[0]);
+                        val_s.push_back (w[1]);
+                     }
+                     ent_give[p] += rowptr_loc[r + 1] - rowptr_loc[r];
+                  }
+               }
+         }
+         int64_t n_erow = 0;
+         for (int p = 0; p < P; p++) n_erow += erow_need[p];
+         std::vector<int32_t> len_r ((size_t) n_erow + 1);
+         len_s.push_back (0);
+         XCHG (len_s.data (), erow_give.data (), len_r.data (), erow_need.data (), "overlap row length");
+         int64_t n_eent = 0;
+         {
+            size_t q = 0;
+            int lrc = NKP_OK;
+            for (int p = 0; p < P; p++) {
+               int64_t t = 0;
+               for (int k = 0; k < erow_need[p]; k++, q++) t += len_r[q];
+               if (2 * t >= 2147483647LL || 2 * (int64_t) ent_give[p] >= 2147483647LL) { lrc = fail (NKP_EINVAL, "nkp_create_dist: overlap rows exceed the int32 exchange counts"); t = 0; ent_give[p] = 0; }
+               ent_need[p] = (int) t;
+               n_eent += t;
+            }
+            int arc;
+            if ((arc = agree (lrc, "overlap sizes"))) return arc;
+            for (int p = 0; p < P; p++) { ent2_give[p] = 2 * ent_give[p]; ent2_need[p] = 2 * ent_need[p]; }
+         }
+         std::vector<int32_t> col_r ((size_t) n_eent + 1), val_r (2 * (size_t) n_eent + 2);
+         col_s.push_back (0);
+         val_s.push_back (0);
+         XCHG (col_s.data (), ent_give.data (), col_r.data (), ent_need.data (), "overlap column index");
+         XCHG (val_s.data (), ent2_give.data (), val_r.data (), ent2_need.data (), "overlap value");
+         // requester: keep the selected columns and their rows
+         int64_t got = 0;
+         {
+            size_t c = 0, q = 0, rrow = 0;
+            int64_t hpos = 0;
+            for (int p = 0; p < P; p++)
+               for (int k = 0; k < need_cols[p]; k++, c++) {
+                  const int len = meta_r[3 * c];
+                  if (flag_s[c]) {
+                     ocols.push_back ({ rows_r[(size_t) hpos], len, meta_r[3 * c + 1], meta_r[3 * c + 2], ring, (int64_t) arr_gid.size () });
+                     for (int t = 0; t < len && rrow < (size_t) n_erow; t++, rrow++) {
+                        arr_gid.push_back (rows_r[(size_t) (hpos + t)]);
+                        for (int u = 0; u < len_r[rrow]; u++, q++) {
+                           double v;
+                           memcpy (&v, &val_r[2 * q], sizeof (double));
+                           arr_col.push_back (col_r[q]);
+                           arr_val.push_back (v);
+                        }
+                        arr_ptr.push_back ((int64_t) arr_col.size ());
+                        got++;
+                     }
+                  }
+                  hpos += len;
+               }
+         }
+         *n_new = got;
+         return NKP_OK;
+      };
+
+      int64_t got = 0;
+      if ((rc = select_and_fetch (1, halo2, &got))) return rc;
+      int64_t n_sel_all = got;
+      {
+         int64_t n_erow = 0;
+         for (const OvCol &c : ocols) n_erow += c.len;
+         if ((rc = agree (n_sel_all != n_erow ? fail (NKP_ECOMM, "nkp_create_dist: overlap rows announced and received differ") : NKP_OK, "overlap rows"))) return rc;
       }
-      std::vector<int32_t> col_r ((size_t) n_eent + 1), val_r (2 * (size_t) n_eent + 2);
-      col_s.push_back (0);
-      val_s.push_back (0);
-      XCHG (col_s.data (), ent_give.data (), col_r.data (), ent_need.data (), "overlap column index");
-      XCHG (val_s.data (), ent2_give.data (), val_r.data (), ent2_need.data (), "overlap value");
+      std::vector<int> ring_first (1, 0);                    // first arrived row of every ring
+      ring_first.push_back ((int) arr_gid.size ());
+      for (int ring = 2; ring <= rings; ring++) {
+         // a ring that came out empty everywhere ends the selection
+         {
+            std::vector<int64_t> all (P + 1, 0);
+            if (comm->allgather_i64_host (comm->ctx, got, all.data ())) return fail (NKP_ECOMM, "nkp_create_dist: allgather failed");
+            int64_t any = 0;
+            for (int p = 0; p < P; p++) any += all[p];
+            if (!any) break;
+         }
+         ov_sorted.assign (arr_gid.begin (), arr_gid.end ());
+         std::sort (ov_sorted.begin (), ov_sorted.end ());
+         // requester: the rows of other ranks that the last ring couples to, in no ring yet, by owner
+         std::vector<int32_t> cand;
+         for (int a = ring_first[ring - 2]; a < ring_first[ring - 1]; a++)
+            for (int64_t e = arr_ptr[a]; e < arr_ptr[a + 1]; e++) {
+               const int32_t g = arr_col[(size_t) e];
+               if ((g >= fst_row && g < fst_row + m_loc) || std::binary_search (ov_sorted.begin (), ov_sorted.end (), g)) continue;
+               cand.push_back (g);
+            }
+         std::sort (cand.begin (), cand.end ());
+         cand.erase (std::unique (cand.begin (), cand.end ()), cand.end ());
+         std::vector<int> req_need (P, 0), req_give (P, 0);
+         for (int32_t g : cand) req_need[(size_t) (std::upper_bound (starts.begin (), starts.begin () + P, (int64_t) g) - starts.begin () - 1)]++;
+         XCHG (req_need.data (), ones.data (), req_give.data (), ones.data (), "ring request count");
+         int64_t n_req = 0;
+         for (int p = 0; p < P; p++) n_req += req_give[p];
+         std::vector<int32_t> req ((size_t) n_req + 1);
+         cand.push_back (0);
+         XCHG (cand.data (), req_need.data (), req.data (), req_give.data (), "ring request");
+         rc = NKP_OK;
+         for (int64_t q = 0; q < n_req; q++) {
+            req[(size_t) q] -= (int32_t) fst_row;
+            if (req[(size_t) q] < 0 || req[(size_t) q] >= m_loc) rc = fail (NKP_ECOMM, "nkp_create_dist: a peer asked for a ring row this rank does not own");
+         }
+         if ((rc = agree (rc, "ring requests"))) return rc;
+         // owner: complete the requested rows to whole columns
+         out_rows.clear ();
+         out_cols.clear ();
+         {
+            size_t q = 0;
+            for (int p = 0; p < P; p++) {
+               int last = -1;
+               give_rows[p] = give_cols[p] = 0;
+               for (int k = 0; k < req_give[p]; k++, q++) {
+                  const int c = col_of[(size_t) req[q]];
+                  if (c == last) continue;
+                  last = c;
+                  out_cols.push_back (c);
+                  give_cols[p]++;
+                  for (int r = blk_start_loc[c]; r < blk_start_loc[c + 1]; r++) { out_rows.push_back (r); give_rows[p]++; }
+               }
+               pair_s[2 * (size_t) p] = give_rows[p];
+               pair_s[2 * (size_t) p + 1] = give_cols[p];
+            }
+         }
+         XCHG (pair_s.data (), twos.data (), pair_r.data (), twos.data (), "ring count");
+         int64_t n_rows = 0, n_cols = 0;
+         for (int p = 0; p < P; p++) { need_rows[p] = pair_r[2 * (size_t) p]; need_cols[p] = pair_r[2 * (size_t) p + 1]; n_rows += need_rows[p]; n_cols += need_cols[p]; }
+         ids_s.assign (out_rows.size () + 1, 0);
+         for (size_t k = 0; k < out_rows.size (); k++) ids_s[k] = out_rows[k] + (int32_t) fst_row;
+         std::vector<int32_t> rows_r ((size_t) n_rows + 1);
+         XCHG (ids_s.data (), give_rows.data (), rows_r.data (), need_rows.data (), "ring row");
+         for (int p = 0; p < P; p++) { give3[p] = 3 * give_cols[p]; need3[p] = 3 * need_cols[p]; }
+         meta_s.assign (3 * out_cols.size () + 1, 0);
+         meta_r.assign (3 * (size_t) n_cols + 1, 0);
+         fill_meta ();
+         XCHG (meta_s.data (), give3.data (), meta_r.data (), need3.data (), "ring column");
+         {
+            int64_t sum = 0;
+            for (int64_t c = 0; c < n_cols; c++) sum += meta_r[3 * (size_t) c];
+            bool good = sum == n_rows;
+            for (int64_t k = 1; k < n_rows && good; k++) good = rows_r[(size_t) k] > rows_r[(size_t) k - 1];
+            for (size_t k = 0; k + 1 < cand.size () && good; k++) good = std::binary_search (rows_r.begin (), rows_r.begin () + n_rows, cand[k]);
+            if ((rc = agree (good ? NKP_OK : fail (NKP_ECOMM, "nkp_create_dist: ring %d is inconsistent (a water column straddles two ranks?)", ring), "ring columns"))) return rc;
+         }
+         const int64_t before = (int64_t) ocols.size ();
+         if ((rc = select_and_fetch (ring, rows_r, &got))) return rc;
+         int64_t n_erow = 0;
+         for (size_t c = (size_t) before; c < ocols.size (); c++) n_erow += ocols[c].len;
+         if ((rc = agree (got != n_erow ? fail (NKP_ECOMM, "nkp_create_dist: ring rows announced and received differ") : NKP_OK, "ring rows"))) return rc;
+         n_sel_all += got;
+         ring_first.push_back ((int) arr_gid.size ());
+      }
 #undef XCHG
-      // ---- the matrix of the hierarchy: own rows, then the selected halo rows; columns renumbered, everything else dropped
-      std::vector<int32_t> sel_of_hpos ((size_t) n_halo2 + 1, -1);
+      // ---- the matrix of the hierarchy: own rows, then the overlap rows in ascending global row order (grouped by owner, so
+      // that an exchange lands them in place); columns renumbered, couplings that leave [own | overlap] dropped
+      std::vector<size_t> cord (ocols.size ());
+      for (size_t c = 0; c < cord.size (); c++) cord[c] = c;
+      std::sort (cord.begin (), cord.end (), [&] (size_t a, size_t b) { return ocols[a].g0 < ocols[b].g0; });
       e_blk.assign (blk_start_loc, blk_start_loc + nblk_loc + 1);
       e_ci.assign (o.col_i, o.col_i + nblk_loc);
       e_cj.assign (o.col_j, o.col_j + nblk_loc);
@@ -2357,33 +2564,31 @@ static int dist_plan (DistPlan &D, const nkp_comm_ops *comm, const nkp_options &
          e_ct.resize ((size_t) nblk_loc);
          for (int64_t c = 0; c < nblk_loc; c++) e_ct[(size_t) c] = o.col_t ? o.col_t[c] : (int32_t) (c / per);
       }
-      std::vector<int32_t> selcol_of_hpos ((size_t) n_halo2 + 1, -1);
-      {
-         int64_t hpos = 0;
-         for (int64_t c = 0; c < n_hcol; c++) {
-            const int len = meta_r[3 * (size_t) c];
-            if (flag_s[(size_t) c]) {
-               for (int k = 0; k < len; k++) {
-                  sel_of_hpos[(size_t) (hpos + k)] = (int32_t) n_sel++;
-                  selcol_of_hpos[(size_t) (hpos + k)] = (int32_t) e_ci.size ();
-                  sel_hpos.push_back ((int32_t) (hpos + k));
-               }
-               e_blk.push_back ((int32_t) (m_loc + n_sel));
-               e_ci.push_back (meta_r[3 * (size_t) c + 1]);
-               e_cj.push_back (meta_r[3 * (size_t) c + 2]);
-               e_ct.push_back (0);
-            }
-            hpos += len;
+      std::vector<int32_t> ov_gid, ov_ecol, ov_ring;          // per overlap row (hierarchy order): global id, its column in e_*, ring
+      std::vector<int64_t> ov_arr;                            // its arrived row
+      for (size_t k = 0; k < cord.size (); k++) {
+         const OvCol &c = ocols[cord[k]];
+         for (int t = 0; t < c.len; t++) {
+            ov_gid.push_back (arr_gid[(size_t) (c.row0 + t)]);
+            ov_arr.push_back (c.row0 + t);
+            ov_ecol.push_back ((int32_t) e_ci.size ());
+            ov_ring.push_back (c.ring);
+            const auto it = std::lower_bound (halo2.begin (), halo2.begin () + n_halo2, ov_gid.back ());
+            sel_hpos.push_back ((it != halo2.begin () + n_halo2 && *it == ov_gid.back ()) ? (int32_t) (it - halo2.begin ()) : -1);
          }
+         n_sel += c.len;
+         e_blk.push_back ((int32_t) (m_loc + n_sel));
+         e_ci.push_back (c.ci);
+         e_cj.push_back (c.cj);
+         e_ct.push_back (0);
       }
-      if ((rc = agree (n_sel != n_erow ? fail (NKP_ECOMM, "nkp_create_dist: overlap rows announced and received differ") : NKP_OK, "overlap rows"))) return rc;
       auto ext_of_global = [&] (int64_t g) -> int64_t {
          if (g >= fst_row && g < fst_row + m_loc) return g - fst_row;
-         const auto it = std::lower_bound (halo2.begin (), halo2.begin () + n_halo2, (int32_t) g);
-         if (it == halo2.begin () + n_halo2 || *it != (int32_t) g) return -1;
-         const int32_t q = sel_of_hpos[(size_t) (it - halo2.begin ())];
-         return q < 0 ? -1 : m_loc + q;
+         const auto it = std::lower_bound (ov_gid.begin (), ov_gid.end (), (int32_t) g);
+         if (it == ov_gid.end () || *it != (int32_t) g) return -1;
+         return m_loc + (it - ov_gid.begin ());
       };
+      const int64_t n_eent = (int64_t) arr_col.size ();
       e_rowptr.assign ((size_t) (m_loc + n_sel) + 1, 0);
       e_colind.reserve ((size_t) (nnz_loc + n_eent));
       e_val.reserve ((size_t) (nnz_loc + n_eent));
@@ -2404,32 +2609,75 @@ static int dist_plan (DistPlan &D, const nkp_comm_ops *comm, const nkp_options &
             const int32_t x = colind_ext[(size_t) e];
             if (x < m_loc) rowbuf.push_back ({ x, val[e], (int32_t) e });
             else {
-               const int32_t q = sel_of_hpos[(size_t) (x - m_loc)];
+               const int64_t q = ext_of_global (colind_glob[e]);
                if (q >= 0) {
-                  rowbuf.push_back ({ (int32_t) (m_loc + q), val[e], (int32_t) e });
-                  e_ct[(size_t) selcol_of_hpos[(size_t) (x - m_loc)]] = e_ct[(size_t) col_of[(size_t) r]];   // an overlap column carries the tracer of the rows that see it
+                  rowbuf.push_back ({ (int32_t) q, val[e], (int32_t) e });
+                  e_ct[(size_t) ov_ecol[(size_t) (q - m_loc)]] = e_ct[(size_t) col_of[(size_t) r]];   // an overlap column carries the tracer of the rows that see it
                }
             }
          }
          flush_row (r);
       }
-      {
-         size_t q = 0;
+      // ... and a column of ring k + 1 that of the rows of ring k
+      for (int ring = 1; ring < rings; ring++)
          for (int64_t k = 0; k < n_sel; k++) {
-            for (int t = 0; t < len_r[(size_t) k]; t++, q++) {
-               const int64_t x = ext_of_global (col_r[q]);
-               if (x < 0) continue;
-               double v;
-               memcpy (&v, &val_r[2 * q], sizeof (double));
-               rowbuf.push_back ({ (int32_t) x, v, (int32_t) (-1 - (int64_t) q) });
+            if (ov_ring[(size_t) k] != ring) continue;
+            for (int64_t e = arr_ptr[(size_t) ov_arr[(size_t) k]]; e < arr_ptr[(size_t) ov_arr[(size_t) k] + 1]; e++) {
+               const int64_t q = ext_of_global (arr_col[(size_t) e]);
+               if (q >= m_loc && ov_ring[(size_t) (q - m_loc)] == ring + 1) e_ct[(size_t) ov_ecol[(size_t) (q - m_loc)]] = e_ct[(size_t) ov_ecol[(size_t) k]];
             }
+         }
+      // overlap rows; an entry's origin is its position in the value stream of all overlap rows in this order, which is the
+      // order the owners ship them in (ascending rows per destination)
+      std::vector<int> ent_need (P, 0), ras_need (P, 0);
+      {
+         int64_t q = 0;
+         int p = 0;
+         for (int64_t k = 0; k < n_sel; k++) {
+            while (ov_gid[(size_t) k] >= starts[(size_t) p + 1]) p++;
+            const int64_t a = ov_arr[(size_t) k];
+            for (int64_t e = arr_ptr[(size_t) a]; e < arr_ptr[(size_t) a + 1]; e++, q++) {
+               const int64_t x = ext_of_global (arr_col[(size_t) e]);
+               if (x < 0) continue;
+               rowbuf.push_back ({ (int32_t) x, arr_val[(size_t) e], (int32_t) (-1 - q) });
+            }
+            ent_need[p] += (int) (arr_ptr[(size_t) a + 1] - arr_ptr[(size_t) a]);
+            ras_need[p]++;
             flush_row (m_loc + k);
          }
       }
+      // owner: the entries shipped over all rings, ascending rows per destination
+      std::vector<int> ent_give (P, 0), ras_give (P, 0);
+      std::vector<int32_t> ras_send;
+      int64_t ent_total = 0;
+      for (int p = 0; p < P; p++) {
+         std::vector<int32_t> &rows = shipped[(size_t) p];
+         std::sort (rows.begin (), rows.end ());
+         for (int32_t r : rows) {
+            for (int e = rowptr_loc[r]; e < rowptr_loc[r + 1]; e++) D.ship_e.push_back ((int32_t) e);
+            ent_give[p] += rowptr_loc[r + 1] - rowptr_loc[r];
+            ras_send.push_back (r);
+         }
+         ras_give[p] = (int) rows.size ();
+         ent_total += ent_give[p];
+      }
+      if (rings >= 2) {
+         int64_t recv_total = 0;
+         for (int p = 0; p < P; p++) recv_total += ent_need[p];
+         rc = n_sel != n_sel_all ? fail (NKP_ECOMM, "nkp_create_dist: overlap rows announced and received differ")
+              : std::max (ent_total, recv_total) >= 2147483647LL ? fail (NKP_EINVAL, "nkp_create_dist: overlap rows of all rings exceed the int32 exchange counts") : NKP_OK;
+         if ((rc = agree (rc, "overlap rows of all rings"))) return rc;
+         D.ras_send_rows.swap (ras_send);
+         D.ras_need = ras_need;
+         D.ras_give = ras_give;
+      }
+      D.ent_give = ent_give;
+      D.ent_need = ent_need;
       // overlap is worth its exchange only if some rank has any: same decision everywhere
       std::vector<int64_t> all (P + 1, 0);
       if (comm->allgather_i64_host (comm->ctx, n_sel, all.data ())) return fail (NKP_ECOMM, "nkp_create_dist: allgather failed");
       for (int p = 0; p < P; p++) ras = ras || all[p] > 0;
+      D.rings = ras ? (int) rings : 0;
    }
 
    return NKP_OK;
@@ -2473,6 +2721,8 @@ static bool dist_plan_field (const nkp_dist_plan *p, const char *what, const voi
       { "val", D.e_val.data (), (int64_t) D.e_val.size (), 8 }, { "blk_start", D.e_blk.data (), (int64_t) D.e_blk.size (), 4 },
       { "col_i", D.e_ci.data (), (int64_t) D.e_ci.size (), 4 }, { "col_j", D.e_cj.data (), (int64_t) D.e_cj.size (), 4 }, { "col_t", D.e_ct.data (), (int64_t) D.e_ct.size (), 4 },
       { "sel_hpos", D.sel_hpos.data (), D.n_sel, 4 },
+      { "ras_send_rows", D.ras_send_rows.data (), (int64_t) D.ras_send_rows.size (), 4 }, { "ras_need", D.ras_need.data (), (int64_t) D.ras_need.size (), 4 },
+      { "ras_give", D.ras_give.data (), (int64_t) D.ras_give.size (), 4 },
    };
    for (const F &f : fields)
       if (!strcmp (what, f.name)) { *ptr = f.ptr; *count = f.count; *elem = f.elem; return true; }
@@ -2485,6 +2735,7 @@ extern "C" int64_t nkp_dist_plan_size (const nkp_dist_plan *p, const char *what)
    if (!strcmp (what, "ras")) return p->D.ras ? 1 : 0;
    if (!strcmp (what, "n_sel")) return p->D.n_sel;
    if (!strcmp (what, "n_halo")) return p->D.n_halo;
+   if (!strcmp (what, "ras_rings")) return p->D.rings;
    const void *ptr; int64_t count; size_t elem;
    return dist_plan_field (p, what, &ptr, &count, &elem) ? count : -1;
 }
@@ -2506,7 +2757,12 @@ extern "C" int nkp_create_dist (nkp_solver **out, const nkp_options *opt, int64_
    if (!out) return fail (NKP_EINVAL, "nkp_create_dist: out is NULL");
    *out = nullptr;
    nkp_tuning tune;
-   { const int trc = resolve_tuning (opt, &tune); if (trc) return trc; }
+   {
+      // a dist_ras_rings out of range is refused by every rank together (dist_plan) when there are peers to tell
+      bool range_error = false;
+      const int trc = resolve_tuning (opt, &tune, &range_error);
+      if (trc && !(range_error && comm && comm->nranks > 1)) return trc;
+   }
    if (!comm || (comm->nranks <= 1 && !tune.force_dist)) {
       if (fst_row != 0 || m_loc != n_global) return fail (NKP_EINVAL, "nkp_create_dist: a single rank must own all rows");
       return create_impl (out, opt, n_global, nnz_loc, rowptr_loc, colind_glob, val, blk_start_loc, nblk_loc, coupled_tracer_cnt, nullptr);
@@ -2573,9 +2829,20 @@ extern "C" int nkp_create_dist (nkp_solver **out, const nkp_options *opt, int64_
    if (ok && ras) {
       s->dist.n_sel = n_sel;
       s->dist.n_ext = m_loc + n_sel;
-      ok = dev_alloc (s, &s->dist.sel_idx, (size_t) n_sel) == NKP_OK && dev_alloc (s, &s->dist.rext, (size_t) (m_loc + n_sel)) == NKP_OK &&
-           dev_alloc (s, &s->dist.zext, (size_t) (m_loc + n_sel)) == NKP_OK;
-      if (ok && n_sel) ok = hipMemcpy (s->dist.sel_idx, sel_hpos.data (), (size_t) n_sel * sizeof (int), hipMemcpyHostToDevice) == hipSuccess;
+      s->dist.ras_rings = D.rings;
+      s->dist.ras_sep = D.rings >= 2;
+      ok = dev_alloc (s, &s->dist.rext, (size_t) (m_loc + n_sel)) == NKP_OK && dev_alloc (s, &s->dist.zext, (size_t) (m_loc + n_sel)) == NKP_OK;
+      if (!s->dist.ras_sep) {
+         ok = ok && dev_alloc (s, &s->dist.sel_idx, (size_t) n_sel) == NKP_OK;
+         if (ok && n_sel) ok = hipMemcpy (s->dist.sel_idx, sel_hpos.data (), (size_t) n_sel * sizeof (int), hipMemcpyHostToDevice) == hipSuccess;
+      } else {
+         s->dist.ras_nsend = (int64_t) D.ras_send_rows.size ();
+         s->dist.ras_send_counts.assign (D.ras_give.begin (), D.ras_give.end ());
+         s->dist.ras_recv_counts.assign (D.ras_need.begin (), D.ras_need.end ());
+         ok = ok && dev_alloc (s, &s->dist.ras_send_idx, (size_t) s->dist.ras_nsend) == NKP_OK && dev_alloc (s, &s->dist.ras_sendbuf, (size_t) s->dist.ras_nsend) == NKP_OK;
+         if (ok && s->dist.ras_nsend)
+            ok = hipMemcpy (s->dist.ras_send_idx, D.ras_send_rows.data (), (size_t) s->dist.ras_nsend * sizeof (int), hipMemcpyHostToDevice) == hipSuccess;
+      }
       s->dist.ras = ok;
    }
    {
@@ -2631,8 +2898,9 @@ extern "C" int nkp_create_dist (nkp_solver **out, const nkp_options *opt, int64_
    }
    msg (s, 1, "nkp_create_dist: %d of %d SpMV row blocks are interior (multiplied while the halo travels: %s)\n", s->dist.seg_rb[2] - s->dist.seg_rb[1],
         s->dist.seg_rb[3], s->dist.overlap ? "yes" : "no");
-   msg (s, 1, "nkp_create_dist: rows [%lld, %lld) of %lld, %lld halo rows in, %lld rows out; overlap (restricted additive Schwarz): %s, %lld rows of other ranks in this rank's hierarchy\n",
-        (long long) fst_row, (long long) (fst_row + m_loc), (long long) n_global, (long long) n_halo, (long long) nsend, s->dist.ras ? "on" : "off", (long long) s->dist.n_sel);
+   msg (s, 1, "nkp_create_dist: rows [%lld, %lld) of %lld, %lld halo rows in, %lld rows out; overlap (restricted additive Schwarz): %s, %lld rows of other ranks in this rank's hierarchy (overlap depth %d)\n",
+        (long long) fst_row, (long long) (fst_row + m_loc), (long long) n_global, (long long) n_halo, (long long) nsend, s->dist.ras ? "on" : "off", (long long) s->dist.n_sel,
+        s->dist.ras ? s->dist.ras_rings : 0);
    *out = s;
    return NKP_OK;
 }

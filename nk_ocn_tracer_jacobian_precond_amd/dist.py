@@ -105,11 +105,15 @@ def plan_host(rowptr_loc, colind_glob, starts, rank):
     return ext[:ci.size], halo[:nh.value].copy(), need
 
 
-def overlap_plan_host(loc, n_global, comm, coupled_tracer_cnt=1):
+def overlap_plan_host(loc, n_global, comm, coupled_tracer_cnt=1, tuning=None):
     """nkp_dist_overlap_plan_host: everything nkp_create_dist decides on the host (halo of the SpMV, overlap of the
-    hierarchy), as a dict of numpy arrays.  Collective; needs no GPU (the callbacks used are the host ones)."""
+    hierarchy), as a dict of numpy arrays.  Collective; needs no GPU (the callbacks used are the host ones).  tuning: an
+    NkpTuning or a dict of overrides (e.g. dict(dist_ras_rings=2)), as NkpDistSolver takes it."""
     lib = _solver.load_library()
     opt = _solver.default_options()
+    if tuning is not None:
+        tun = tuning if isinstance(tuning, _solver.NkpTuning) else _solver.default_tuning(**tuning)
+        opt.tuning = C.pointer(tun)
     rp, ci, v, bs = loc["rowptr"], loc["colind"], loc["val"], loc["blk_start"]
     keep = [np.ascontiguousarray(loc[k], np.int32) for k in ("col_i", "col_j", "col_t") if loc.get(k) is not None]
     if loc.get("col_i") is not None:
@@ -128,8 +132,9 @@ def overlap_plan_host(loc, n_global, comm, coupled_tracer_cnt=1):
                                         int(bs.size - 1), int(coupled_tracer_cnt), C.cast(C.byref(comm.ops), C.c_void_p))
     if rc != 0:
         raise _solver.NkpError(rc, lib.nkp_last_error().decode() + (" | comm: " + "; ".join(comm.errors) if comm.errors else ""))
-    out = dict(ras=int(lib.nkp_dist_plan_size(h, b"ras")))
-    for name in ("colind_ext", "halo_rows", "send_rows", "need", "give", "rowptr", "colind", "val", "blk_start", "col_i", "col_j", "col_t", "sel_hpos"):
+    out = dict(ras=int(lib.nkp_dist_plan_size(h, b"ras")), ras_rings=int(lib.nkp_dist_plan_size(h, b"ras_rings")))
+    for name in ("colind_ext", "halo_rows", "send_rows", "need", "give", "rowptr", "colind", "val", "blk_start", "col_i", "col_j", "col_t", "sel_hpos",
+                 "ras_send_rows", "ras_need", "ras_give"):
         cnt = int(lib.nkp_dist_plan_size(h, name.encode()))
         arr = np.empty(max(cnt, 0), np.float64 if name == "val" else np.int32)
         if cnt > 0:
