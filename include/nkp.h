@@ -429,7 +429,9 @@ int nkp_gather_root (nkp_solver *s, const double *x_loc, double *x_global);
  * for rows of ring 2 and beyond, which the SpMV never reads).  The overlap rows follow the own rows in ascending global row order.
  * "ras_rings" (size only) is the depth the ranks agreed on (0 without overlap); with two or more rings the overlap residual has
  * an exchange of its own: "ras_send_rows" (own local rows sent, grouped by destination, ascending within each), "ras_need" /
- * "ras_give" (per-rank row counts; the rows from rank p arrive in hierarchy order). */
+ * "ras_give" (per-rank row counts; the rows from rank p arrive in hierarchy order).  What nkp_refactor_dist redoes the values
+ * from: "origin" (per entry of "colind": the own local entry it comes from, or -1 - position in the received overlap values),
+ * "ship" (own local entries shipped, grouped by destination), "ent_need" / "ent_give" (per-rank entry counts). */
 typedef struct nkp_dist_plan nkp_dist_plan;
 int nkp_dist_overlap_plan_host (nkp_dist_plan **out, const nkp_options *opt, int64_t n_global, int64_t fst_row, int64_t m_loc,
                                 int64_t nnz_loc, const int32_t *rowptr_loc, const int32_t *colind_glob, const double *val,

@@ -1,0 +1,52 @@
+// Host-side plan of the row-distributed flavour (dist_plan.cpp): plain C++, no HIP.  Private to the library: nothing here is
+// part of the C ABI, so everything is hidden from the dynamic symbol table.
+#pragma once
+#include "../../include/nkp.h"
+
+#include <stdint.h>
+
+#include <string>
+#include <vector>
+
+#define NKP_PRIVATE __attribute__ ((visibility ("hidden")))
+
+// ---- what the plan needs from solver.hip (defined there, once) -------------------------------------------------------------
+// the error reporter behind nkp_last_error: formats the calling thread's message and returns `code`
+NKP_PRIVATE int fail (int code, const char *fmt, ...) __attribute__ ((format (printf, 2, 3)));
+// a step that reports on behalf of all ranks keeps a rank's own message across the collective
+NKP_PRIVATE std::string last_error_message ();
+NKP_PRIVATE void restore_error_message (const std::string &text);
+// solver.hip's resolve_tuning: the caller's knobs, or the defaults + environment; *range_error tells a value out of range (out
+// is filled) from a struct of the wrong size (out is not)
+NKP_PRIVATE int dist_resolve_tuning (const nkp_options *opt, nkp_tuning *out, bool *range_error);
+
+// ---- the plan ---------------------------------------------------------------------------------------------------------------
+struct DistPlan {
+   std::vector<int32_t> colind_ext, halo_rows, send_rows, need, give;     // SpMV: renumbered columns, halo rows in, own rows out
+   int64_t n_halo = 0, nsend = 0;
+   std::vector<int32_t> e_rowptr, e_colind, e_blk, e_ci, e_cj, e_ct, sel_hpos;   // hierarchy on [own rows | overlap rows]
+   std::vector<double> e_val;
+   int64_t n_sel = 0;
+   bool ras = false;
+   // what nkp_refactor_dist needs to redo the value part: where every entry of e_* comes from (own local entry e, or
+   // -1 - position in the received overlap values), the own entries shipped (in val_s order) and the entry counts per rank
+   std::vector<int32_t> e_org, ship_e;
+   std::vector<int> ent_give, ent_need;
+   // the depth the ranks agreed on (0: no overlap); with two or more rings the overlap rows are not all in the SpMV halo and
+   // the residual of the cycle has an exchange of its own: own local rows sent (by destination, ascending), rows per rank
+   int rings = 0;
+   std::vector<int32_t> ras_send_rows;
+   std::vector<int> ras_need, ras_give;
+};
+
+// Everything nkp_create_dist decides before a byte goes to the device.  Collective over the ranks through the host callbacks
+// of `comm`; starts[nranks + 1] are the first rows of all ranks.
+NKP_PRIVATE int dist_plan (DistPlan &D, const nkp_comm_ops *comm, const nkp_options &o, const std::vector<int64_t> &starts, int64_t fst_row,
+                           int64_t m_loc, int64_t nnz_loc, const int32_t *rowptr_loc, const int32_t *colind_glob, const double *val,
+                           const int32_t *blk_start_loc, int64_t nblk_loc, int coupled_tracer_cnt);
+
+// All ranks learn whether any rank failed a check that only one rank can fail, and leave together: a rank that returned alone
+// would leave its peers blocked in the next exchange, for good with a transport that has no deadline (RCCL).  A rank that failed
+// keeps its code and message; the others get NKP_ECOMM "<who>: rank <p> failed its checks (<where>); see its message".  A
+// failed allgather is NKP_ECOMM on every rank.
+NKP_PRIVATE int dist_agree_checks (const nkp_comm_ops *comm, int local_rc, const char *who, const char *where);

@@ -11,6 +11,7 @@
 #include "nkp_dev.h"
 #include "multilevel.h"
 #include "refactor.h"
+#include "dist_plan.h"
 
 #include <math.h>
 #include <stdarg.h>
@@ -28,7 +29,7 @@
 
 static thread_local std::string g_last_error;
 
-static int fail (int code, const char *fmt, ...)
+int fail (int code, const char *fmt, ...)      // shared with dist_plan.cpp (dist_plan.h)
 {
    char buf[512];
    va_list ap;
@@ -46,6 +47,8 @@ static int fail (int code, const char *fmt, ...)
    } while (0)
 
 extern "C" const char *nkp_last_error (void) { return g_last_error.c_str (); }
+std::string last_error_message () { return g_last_error; }
+void restore_error_message (const std::string &text) { g_last_error = text; }
 
 extern "C" int nkp_device_count (void)
 {
@@ -157,6 +160,8 @@ static int resolve_tuning (const nkp_options *opt, nkp_tuning *out, bool *range_
    }
    return NKP_OK;
 }
+
+int dist_resolve_tuning (const nkp_options *opt, nkp_tuning *out, bool *range_error) { return resolve_tuning (opt, out, range_error); }
 
 // ---------------------------------------------------------------- solver object
 #define NKP_BERR_ROUNDING_LEVEL 1.0e-14     // 45 eps
@@ -2139,617 +2144,7 @@ extern "C" int nkp_time_kernel (nkp_solver *s, int which, int arg, int reps, dou
    return NKP_OK;
 }
 
-// ---------------------------------------------------------------- distributed flavour
-extern "C" int nkp_dist_plan_host (int64_t m_loc, int64_t nnz_loc, const int32_t *rowptr_loc, const int32_t *colind_glob,
-                                   int rank, int nranks, const int64_t *starts, int32_t *colind_ext, int32_t *halo_rows,
-                                   int64_t *n_halo, int32_t *need_counts)
-{
-   if (!rowptr_loc || !starts || !colind_ext || !halo_rows || !n_halo || !need_counts || rank < 0 || rank >= nranks)
-      return fail (NKP_EINVAL, "nkp_dist_plan_host: bad argument");
-   if (nnz_loc > 0 && !colind_glob) return fail (NKP_EINVAL, "nkp_dist_plan_host: bad argument");
-   const int64_t fst = starts[rank], n_global = starts[nranks];
-   if (starts[rank + 1] - fst != m_loc || rowptr_loc[0] != 0 || rowptr_loc[m_loc] != nnz_loc)
-      return fail (NKP_EINVAL, "nkp_dist_plan_host: starts[] / rowptr_loc inconsistent with m_loc, nnz_loc");
-   // sorted unique off-rank columns
-   std::vector<int32_t> off;
-   for (int64_t e = 0; e < nnz_loc; e++) {
-      const int64_t c = colind_glob[e];
-      if (c < 0 || c >= n_global) return fail (NKP_EINVAL, "nkp_dist_plan_host: column index %lld out of range", (long long) c);
-      if (c < fst || c >= fst + m_loc) off.push_back ((int32_t) c);
-   }
-   std::sort (off.begin (), off.end ());
-   off.erase (std::unique (off.begin (), off.end ()), off.end ());
-   *n_halo = (int64_t) off.size ();
-   for (int p = 0; p < nranks; p++) need_counts[p] = 0;
-   {
-      int p = 0;
-      for (size_t q = 0; q < off.size (); q++) {
-         while (off[q] >= starts[p + 1]) p++;           // sorted rows, ascending owners
-         need_counts[p]++;
-         halo_rows[q] = off[q];
-      }
-   }
-   for (int64_t e = 0; e < nnz_loc; e++) {
-      const int64_t c = colind_glob[e];
-      if (c >= fst && c < fst + m_loc) colind_ext[e] = (int32_t) (c - fst);
-      else colind_ext[e] = (int32_t) (m_loc + (std::lower_bound (off.begin (), off.end (), (int32_t) c) - off.begin ()));
-   }
-   return NKP_OK;
-}
-
-// ---------------------------------------------------------------- host-side plan of the distributed flavour
-// Everything nkp_create_dist decides before a byte goes to the device: the halo of the SpMV, and -- with grid positions --
-// the overlap of the hierarchy (completed halo columns, which of them are lateral neighbours, their matrix rows fetched
-// from the owners).  Collective over the ranks through the host callbacks of nkp_comm_ops; no HIP call, so the N > 1 logic
-// is testable without a GPU (nkp_dist_overlap_plan_host, tests/test_dist_gloo.py).
-struct DistPlan {
-   std::vector<int32_t> colind_ext, halo_rows, send_rows, need, give;     // SpMV: renumbered columns, halo rows in, own rows out
-   int64_t n_halo = 0, nsend = 0;
-   std::vector<int32_t> e_rowptr, e_colind, e_blk, e_ci, e_cj, e_ct, sel_hpos;   // hierarchy on [own rows | overlap rows]
-   std::vector<double> e_val;
-   int64_t n_sel = 0;
-   bool ras = false;
-   // what nkp_refactor_dist needs to redo the value part: where every entry of e_* comes from (own local entry e, or
-   // -1 - position in the received overlap values), the own entries shipped (in val_s order) and the entry counts per rank
-   std::vector<int32_t> e_org, ship_e;
-   std::vector<int> ent_give, ent_need;
-   // the depth the ranks agreed on (0: no overlap); with two or more rings the overlap rows are not all in the SpMV halo and
-   // the residual of the cycle has an exchange of its own: own local rows sent (by destination, ascending), rows per rank
-   int rings = 0;
-   std::vector<int32_t> ras_send_rows;
-   std::vector<int> ras_need, ras_give;
-};
-
-static int dist_plan (DistPlan &D, const nkp_comm_ops *comm, const nkp_options &o, const std::vector<int64_t> &starts, int64_t fst_row, int64_t m_loc,
-                      int64_t nnz_loc, const int32_t *rowptr_loc, const int32_t *colind_glob, const double *val, const int32_t *blk_start_loc,
-                      int64_t nblk_loc, int coupled_tracer_cnt)
-{
-   const int P = comm->nranks, rank = comm->rank;
-   auto &colind_ext = D.colind_ext; auto &halo_rows = D.halo_rows; auto &send_rows = D.send_rows; auto &need = D.need; auto &give = D.give;
-   auto &n_halo = D.n_halo; auto &nsend = D.nsend;
-   auto &e_rowptr = D.e_rowptr; auto &e_colind = D.e_colind; auto &e_blk = D.e_blk; auto &e_ci = D.e_ci; auto &e_cj = D.e_cj; auto &e_ct = D.e_ct;
-   auto &sel_hpos = D.sel_hpos; auto &e_val = D.e_val; auto &n_sel = D.n_sel; auto &ras = D.ras;
-   n_halo = nsend = n_sel = 0;
-   ras = false;
-   colind_ext.assign ((size_t) nnz_loc + 1, 0);
-   halo_rows.assign ((size_t) nnz_loc + 1, 0);
-   need.assign (P, 0);
-   give.assign (P, 0);
-   std::vector<int32_t> ones (P, 1);
-   // Checks that only one rank can fail (its own arguments, what its peers sent it) are followed by an agreement: every
-   // rank learns whether any rank failed and all of them leave together -- a rank that returned alone would leave its
-   // peers blocked in the next exchange, for good with a transport that has no deadline (RCCL).
-   auto agree = [&] (int local_rc, const char *where) -> int {
-      std::vector<int64_t> all (P + 1, 0);
-      std::string mine = local_rc ? g_last_error : std::string ();
-      if (comm->allgather_i64_host (comm->ctx, local_rc ? 1 : 0, all.data ())) return fail (NKP_ECOMM, "nkp_create_dist: allgather failed (%s)", where);
-      if (local_rc) { g_last_error = mine; return local_rc; }
-      for (int p = 0; p < P; p++)
-         if (all[p]) return fail (NKP_ECOMM, "nkp_create_dist: rank %d failed its checks (%s); see its message", p, where);
-      return NKP_OK;
-   };
-   int rc = (starts[(size_t) rank + 1] - starts[(size_t) rank] != m_loc)
-               ? fail (NKP_EINVAL, "nkp_create_dist: m_loc = %lld does not match the next rank's fst_row", (long long) m_loc)
-               : nkp_dist_plan_host (m_loc, nnz_loc, rowptr_loc, colind_glob, rank, P, starts.data (), colind_ext.data (), halo_rows.data (), &n_halo, need.data ());
-   if ((rc = agree (rc, "local rows and halo plan"))) return rc;
-   // tell every owner how many and which of its rows this rank reads
-   if (comm->alltoallv_i32_host (comm->ctx, need.data (), ones.data (), give.data (), ones.data ())) return fail (NKP_ECOMM, "nkp_create_dist: count exchange failed");
-   for (int p = 0; p < P; p++) nsend += give[p];
-   send_rows.assign ((size_t) nsend + 1, 0);
-   if (comm->alltoallv_i32_host (comm->ctx, halo_rows.data (), need.data (), send_rows.data (), give.data ())) return fail (NKP_ECOMM, "nkp_create_dist: index exchange failed");
-   rc = NKP_OK;
-   for (int64_t q = 0; q < nsend; q++) {
-      send_rows[q] -= (int32_t) fst_row;
-      if (send_rows[q] < 0 || send_rows[q] >= m_loc) rc = fail (NKP_ECOMM, "nkp_create_dist: a peer asked for a row this rank does not own");
-   }
-   if ((rc = agree (rc, "requested rows"))) return rc;
-
-   // ---- restricted additive Schwarz (overlap of one ring of water columns) -------------------------------------------
-   // A hierarchy built from the rank's diagonal block alone treats the cut through the ocean as a wall: latitude bands cost
-   // 2-3 times the iterations of the undivided solve (1 degree: 78 / 157 / 238 for 1 / 2 / 4 bands), and a global coarsest
-   // level does not repair that (scipy prototype tools/proto_bands.py: 36 / 58 / 89 without, 57 / 87 with it).  What does is
-   // the classical remedy: every rank's hierarchy also covers the water columns of other ranks that its own rows couple to
-   // LATERALLY (the halo of the SpMV, completed to whole columns), a cycle runs on [own rows | overlap rows] with the
-   // residual of the overlap rows fetched from their owners, and only the own part of the result is kept (prototype:
-   // 36 / 43 / 55).  Columns of OTHER TRACERS at a cell this rank owns are not overlap (a tracer-per-rank partition keeps
-   // its block-Jacobi preconditioner): a halo column joins only if its (i, j) is not the position of an own column.
-   // dist_ras_rings > 1 deepens the overlap ring by ring (prototype, 3 degrees, 4 bands: 63 / 56 / 53 / 51 iterations for 1-4
-   // rings); each ring is one more round of the fetch below.
-   const bool geo = o.col_i && o.col_j && blk_start_loc && nblk_loc > 0;
-   int64_t want_ras = (o.precond == NKP_PRECOND_MULTILEVEL && geo) ? 1 : 0;
-   int64_t rings = 1;
-   {
-      // the depth this rank asks for rides on the message that decides the overlap (0 = none); the ranks take the smallest.
-      // -1 = a depth out of range: every rank refuses it together
-      nkp_tuning tune;
-      bool range_error = false;
-      if (resolve_tuning (&o, &tune, &range_error) == NKP_OK) {      // a struct of the wrong size is reported by the create call itself
-         if (!tune.dist_ras) want_ras = 0;
-         rings = tune.dist_ras_rings > 0 ? tune.dist_ras_rings : 1;
-      }
-      const std::string mine = range_error ? g_last_error : std::string ();
-      std::vector<int64_t> all (P + 1, 0);
-      if (comm->allgather_i64_host (comm->ctx, range_error ? -1 : want_ras * rings, all.data ())) return fail (NKP_ECOMM, "nkp_create_dist: allgather failed");
-      if (range_error) { g_last_error = mine; return NKP_EINVAL; }
-      for (int p = 0; p < P; p++)
-         if (all[p] < 0) return fail (NKP_ECOMM, "nkp_create_dist: rank %d failed its checks (tuning); see its message", p);
-      for (int p = 0; p < P; p++) rings = std::min (rings, all[p]);
-      want_ras = rings > 0 ? 1 : 0;
-   }
-   if (want_ras) {
-#define XCHG(sendp, scnt, recvp, rcnt, what) do { if (comm->alltoallv_i32_host (comm->ctx, (sendp), (scnt), (recvp), (rcnt))) return fail (NKP_ECOMM, "nkp_create_dist: %s exchange failed", what); } while (0)
-      std::vector<int32_t> col_of ((size_t) m_loc + 1);
-      for (int64_t c = 0; c < nblk_loc; c++)
-         for (int r = blk_start_loc[c]; r < blk_start_loc[c + 1]; r++) col_of[(size_t) r] = (int32_t) c;
-      // owner: complete every requested row to its water column
-      std::vector<int> give_rows (P, 0), give_cols (P, 0), need_rows (P, 0), need_cols (P, 0), twos (P, 2), pair_s (2 * (size_t) P), pair_r (2 * (size_t) P);
-      std::vector<int32_t> out_rows, out_cols;
-      {
-         size_t q = 0;
-         for (int p = 0; p < P; p++) {
-            int last = -1;
-            for (int k = 0; k < give[p]; k++, q++) {
-               const int c = col_of[(size_t) send_rows[q]];
-               if (c == last) continue;
-               last = c;
-               out_cols.push_back (c);
-               give_cols[p]++;
-               for (int r = blk_start_loc[c]; r < blk_start_loc[c + 1]; r++) { out_rows.push_back (r); give_rows[p]++; }
-            }
-            pair_s[2 * (size_t) p] = give_rows[p];
-            pair_s[2 * (size_t) p + 1] = give_cols[p];
-         }
-      }
-      XCHG (pair_s.data (), twos.data (), pair_r.data (), twos.data (), "overlap count");
-      int64_t n_halo2 = 0, n_hcol = 0;
-      for (int p = 0; p < P; p++) { need_rows[p] = pair_r[2 * (size_t) p]; need_cols[p] = pair_r[2 * (size_t) p + 1]; n_halo2 += need_rows[p]; n_hcol += need_cols[p]; }
-      // the completed halo: global row ids, then (length, i, j) of every halo column
-      std::vector<int32_t> ids_s (out_rows.size () + 1), halo2 ((size_t) n_halo2 + 1);
-      for (size_t k = 0; k < out_rows.size (); k++) ids_s[k] = out_rows[k] + (int32_t) fst_row;
-      XCHG (ids_s.data (), give_rows.data (), halo2.data (), need_rows.data (), "overlap row");
-      std::vector<int> give3 (P), need3 (P);
-      for (int p = 0; p < P; p++) { give3[p] = 3 * give_cols[p]; need3[p] = 3 * need_cols[p]; }
-      std::vector<int32_t> meta_s (3 * out_cols.size () + 1), meta_r (3 * (size_t) n_hcol + 1);
-      auto fill_meta = [&] () {
-         for (size_t k = 0; k < out_cols.size (); k++) {
-            const int c = out_cols[k];
-            meta_s[3 * k] = blk_start_loc[c + 1] - blk_start_loc[c];
-            meta_s[3 * k + 1] = o.col_i[c];
-            meta_s[3 * k + 2] = o.col_j[c];
-         }
-      };
-      fill_meta ();
-      XCHG (meta_s.data (), give3.data (), meta_r.data (), need3.data (), "overlap column");
-      // sanity of what arrived: ascending rows, every originally needed row present, lengths adding up
-      {
-         int64_t sum = 0;
-         for (int64_t c = 0; c < n_hcol; c++) sum += meta_r[3 * (size_t) c];
-         bool good = sum == n_halo2;
-         for (int64_t k = 1; k < n_halo2 && good; k++) good = halo2[(size_t) k] > halo2[(size_t) k - 1];
-         for (int64_t k = 0; k < n_halo && good; k++) good = std::binary_search (halo2.begin (), halo2.begin () + n_halo2, halo_rows[(size_t) k]);
-         if ((rc = agree (good ? NKP_OK : fail (NKP_ECOMM, "nkp_create_dist: the completed halo is inconsistent (a water column straddles two ranks?)"), "completed halo"))) return rc;
-      }
-      // the SpMV addresses the completed halo from here on
-      for (int64_t r = 0; r < m_loc; r++)
-         for (int e = rowptr_loc[r]; e < rowptr_loc[r + 1]; e++) {
-            const int64_t g = colind_glob[e];
-            if (g >= fst_row && g < fst_row + m_loc) continue;
-            colind_ext[(size_t) e] = (int32_t) (m_loc + (std::lower_bound (halo2.begin (), halo2.begin () + n_halo2, (int32_t) g) - halo2.begin ()));
-         }
-      n_halo = n_halo2;
-      halo_rows.assign (halo2.begin (), halo2.begin () + n_halo2);
-      halo_rows.push_back (0);
-      need.assign (need_rows.begin (), need_rows.end ());
-      give.assign (give_rows.begin (), give_rows.end ());
-      nsend = (int64_t) out_rows.size ();
-      send_rows.assign (out_rows.begin (), out_rows.end ());
-      send_rows.push_back (0);
-      std::vector<int64_t> own_pos ((size_t) nblk_loc);
-      for (int64_t c = 0; c < nblk_loc; c++) own_pos[(size_t) c] = ((int64_t) o.col_j[c] << 32) | (uint32_t) o.col_i[c];
-      std::sort (own_pos.begin (), own_pos.end ());
-
-      // ---- the rings.  Ring 1 = the lateral columns of the completed halo; ring k + 1 = the lateral columns of other ranks,
-      // in no earlier ring, that rows of ring k couple to.  Every ring is one round of: owner completes the requested rows to
-      // whole columns and ships (rows, length, i, j) [ring 1: the halo exchange above], requester selects, owner ships the
-      // selected rows (lengths, global columns, values).  What arrives is kept per row and ordered once all rings are in.
-      struct OvCol { int32_t g0; int len, ci, cj, ring; int64_t row0; };
-      std::vector<OvCol> ocols;
-      std::vector<int32_t> arr_gid, arr_col;                  // per arrived row: global id; per entry: global column
-      std::vector<int64_t> arr_ptr (1, 0);
-      std::vector<double> arr_val;
-      std::vector<int32_t> ov_sorted;                         // global rows of the overlap so far, ascending
-      std::vector<std::vector<int32_t>> shipped ((size_t) P); // owner: own local rows shipped to each rank over all rings
-      // rows_r: global ids of the completed rows, column after column; meta_r: (length, i, j) per column, need_cols[p] from rank p
-      auto select_and_fetch = [&] (int ring, const std::vector<int32_t> &rows_r, int64_t *n_new) -> int {
-         int64_t ncol_r = 0;
-         for (int p = 0; p < P; p++) ncol_r += need_cols[p];
-         // requester: which completed columns join this ring (position not owned here, not in an earlier ring)
-         std::vector<int32_t> flag_s ((size_t) ncol_r + 1, 0), flag_r (out_cols.size () + 1, 0);
-         std::vector<int> erow_need (P, 0), erow_give (P, 0);
-         {
-            size_t c = 0;
-            int64_t hpos = 0;
-            for (int p = 0; p < P; p++)
-               for (int k = 0; k < need_cols[p]; k++, c++) {
-                  const int64_t key = ((int64_t) meta_r[3 * c + 2] << 32) | (uint32_t) meta_r[3 * c + 1];
-                  flag_s[c] = std::binary_search (own_pos.begin (), own_pos.end (), key) ? 0 : 1;
-                  if (flag_s[c] && std::binary_search (ov_sorted.begin (), ov_sorted.end (), rows_r[(size_t) hpos])) flag_s[c] = 0;
-                  if (flag_s[c]) erow_need[p] += meta_r[3 * c];
-                  hpos += meta_r[3 * c];
-               }
-         }
-         XCHG (flag_s.data (), need_cols.data (), flag_r.data (), give_cols.data (), "overlap selection");
-         // owner: ship the rows of the selected columns (entries per row, global columns, values as pairs of int32)
-         std::vector<int32_t> len_s, col_s, val_s;
-         std::vector<int> ent_give (P, 0), ent_need (P, 0), ent2_give (P, 0), ent2_need (P, 0);
-         {
-            size_t c = 0;
-            for (int p = 0; p < P; p++)
-               for (int k = 0; k < give_cols[p]; k++, c++) {
-                  if (!flag_r[c]) continue;
-                  const int col = out_cols[c];
-                  for (int r = blk_start_loc[col]; r < blk_start_loc[col + 1]; r++) {
-                     len_s.push_back (rowptr_loc[r + 1] - rowptr_loc[r]);
-                     erow_give[p]++;
-                     shipped[(size_t) p].push_back (r);
-                     for (int e = rowptr_loc[r]; e < rowptr_loc[r + 1]; e++) {
-                        col_s.push_back (colind_glob[e]);
-                        int32_t w[2];
-                        memcpy (w, &val[e], sizeof (double));
-                        val_s.push_back (w[0]);
-                        val_s.push_back (w[1]);
-                     }
-                     ent_give[p] += rowptr_loc[r + 1] - rowptr_loc[r];
-                  }
-               }
-         }
-         int64_t n_erow = 0;
-         for (int p = 0; p < P; p++) n_erow += erow_need[p];
-         std::vector<int32_t> len_r ((size_t) n_erow + 1);
-         len_s.push_back (0);
-         XCHG (len_s.data (), erow_give.data (), len_r.data (), erow_need.data (), "overlap row length");
-         int64_t n_eent = 0;
-         {
-            size_t q = 0;
-            int lrc = NKP_OK;
-            for (int p = 0; p < P; p++) {
-               int64_t t = 0;
-               for (int k = 0; k < erow_need[p]; k++, q++) t += len_r[q];
-               if (2 * t >= 2147483647LL || 2 * (int64_t) ent_give[p] >= 2147483647LL) { lrc = fail (NKP_EINVAL, "nkp_create_dist: overlap rows exceed the int32 exchange counts"); t = 0; ent_give[p] = 0; }
-               ent_need[p] = (int) t;
-               n_eent += t;
-            }
-            int arc;
-            if ((arc = agree (lrc, "overlap sizes"))) return arc;
-            for (int p = 0; p < P; p++) { ent2_give[p] = 2 * ent_give[p]; ent2_need[p] = 2 * ent_need[p]; }
-         }
-         std::vector<int32_t> col_r ((size_t) n_eent + 1), val_r (2 * (size_t) n_eent + 2);
-         col_s.push_back (0);
-         val_s.push_back (0);
-         XCHG (col_s.data (), ent_give.data (), col_r.data (), ent_need.data (), "overlap column index");
-         XCHG (val_s.data (), ent2_give.data (), val_r.data (), ent2_need.data (), "overlap value");
-         // requester: keep the selected columns and their rows
-         int64_t got = 0;
-         {
-            size_t c = 0, q = 0, rrow = 0;
-            int64_t hpos = 0;
-            for (int p = 0; p < P; p++)
-               for (int k = 0; k < need_cols[p]; k++, c++) {
-                  const int len = meta_r[3 * c];
-                  if (flag_s[c]) {
-                     ocols.push_back ({ rows_r[(size_t) hpos], len, meta_r[3 * c + 1], meta_r[3 * c + 2], ring, (int64_t) arr_gid.size () });
-                     for (int t = 0; t < len && rrow < (size_t) n_erow; t++, rrow++) {
-                        arr_gid.push_back (rows_r[(size_t) (hpos + t)]);
-                        for (int u = 0; u < len_r[rrow]; u++, q++) {
-                           double v;
-                           memcpy (&v, &val_r[2 * q], sizeof (double));
-                           arr_col.push_back (col_r[q]);
-                           arr_val.push_back (v);
-                        }
-                        arr_ptr.push_back ((int64_t) arr_col.size ());
-                        got++;
-                     }
-                  }
-                  hpos += len;
-               }
-         }
-         *n_new = got;
-         return NKP_OK;
-      };
-
-      int64_t got = 0;
-      if ((rc = select_and_fetch (1, halo2, &got))) return rc;
-      int64_t n_sel_all = got;
-      {
-         int64_t n_erow = 0;
-         for (const OvCol &c : ocols) n_erow += c.len;
-         if ((rc = agree (n_sel_all != n_erow ? fail (NKP_ECOMM, "nkp_create_dist: overlap rows announced and received differ") : NKP_OK, "overlap rows"))) return rc;
-      }
-      std::vector<int> ring_first (1, 0);                    // first arrived row of every ring
-      ring_first.push_back ((int) arr_gid.size ());
-      for (int ring = 2; ring <= rings; ring++) {
-         // a ring that came out empty everywhere ends the selection
-         {
-            std::vector<int64_t> all (P + 1, 0);
-            if (comm->allgather_i64_host (comm->ctx, got, all.data ())) return fail (NKP_ECOMM, "nkp_create_dist: allgather failed");
-            int64_t any = 0;
-            for (int p = 0; p < P; p++) any += all[p];
-            if (!any) break;
-         }
-         ov_sorted.assign (arr_gid.begin (), arr_gid.end ());
-         std::sort (ov_sorted.begin (), ov_sorted.end ());
-         // requester: the rows of other ranks that the last ring couples to, in no ring yet, by owner
-         std::vector<int32_t> cand;
-         for (int a = ring_first[ring - 2]; a < ring_first[ring - 1]; a++)
-            for (int64_t e = arr_ptr[a]; e < arr_ptr[a + 1]; e++) {
-               const int32_t g = arr_col[(size_t) e];
-               if ((g >= fst_row && g < fst_row + m_loc) || std::binary_search (ov_sorted.begin (), ov_sorted.end (), g)) continue;
-               cand.push_back (g);
-            }
-         std::sort (cand.begin (), cand.end ());
-         cand.erase (std::unique (cand.begin (), cand.end ()), cand.end ());
-         std::vector<int> req_need (P, 0), req_give (P, 0);
-         for (int32_t g : cand) req_need[(size_t) (std::upper_bound (starts.begin (), starts.begin () + P, (int64_t) g) - starts.begin () - 1)]++;
-         XCHG (req_need.data (), ones.data (), req_give.data (), ones.data (), "ring request count");
-         int64_t n_req = 0;
-         for (int p = 0; p < P; p++) n_req += req_give[p];
-         std::vector<int32_t> req ((size_t) n_req + 1);
-         cand.push_back (0);
-         XCHG (cand.data (), req_need.data (), req.data (), req_give.data (), "ring request");
-         rc = NKP_OK;
-         for (int64_t q = 0; q < n_req; q++) {
-            req[(size_t) q] -= (int32_t) fst_row;
-            if (req[(size_t) q] < 0 || req[(size_t) q] >= m_loc) rc = fail (NKP_ECOMM, "nkp_create_dist: a peer asked for a ring row this rank does not own");
-         }
-         if ((rc = agree (rc, "ring requests"))) return rc;
-         // owner: complete the requested rows to whole columns
-         out_rows.clear ();
-         out_cols.clear ();
-         {
-            size_t q = 0;
-            for (int p = 0; p < P; p++) {
-               int last = -1;
-               give_rows[p] = give_cols[p] = 0;
-               for (int k = 0; k < req_give[p]; k++, q++) {
-                  const int c = col_of[(size_t) req[q]];
-                  if (c == last) continue;
-                  last = c;
-                  out_cols.push_back (c);
-                  give_cols[p]++;
-                  for (int r = blk_start_loc[c]; r < blk_start_loc[c + 1]; r++) { out_rows.push_back (r); give_rows[p]++; }
-               }
-               pair_s[2 * (size_t) p] = give_rows[p];
-               pair_s[2 * (size_t) p + 1] = give_cols[p];
-            }
-         }
-         XCHG (pair_s.data (), twos.data (), pair_r.data (), twos.data (), "ring count");
-         int64_t n_rows = 0, n_cols = 0;
-         for (int p = 0; p < P; p++) { need_rows[p] = pair_r[2 * (size_t) p]; need_cols[p] = pair_r[2 * (size_t) p + 1]; n_rows += need_rows[p]; n_cols += need_cols[p]; }
-         ids_s.assign (out_rows.size () + 1, 0);
-         for (size_t k = 0; k < out_rows.size (); k++) ids_s[k] = out_rows[k] + (int32_t) fst_row;
-         std::vector<int32_t> rows_r ((size_t) n_rows + 1);
-         XCHG (ids_s.data (), give_rows.data (), rows_r.data (), need_rows.data (), "ring row");
-         for (int p = 0; p < P; p++) { give3[p] = 3 * give_cols[p]; need3[p] = 3 * need_cols[p]; }
-         meta_s.assign (3 * out_cols.size () + 1, 0);
-         meta_r.assign (3 * (size_t) n_cols + 1, 0);
-         fill_meta ();
-         XCHG (meta_s.data (), give3.data (), meta_r.data (), need3.data (), "ring column");
-         {
-            int64_t sum = 0;
-            for (int64_t c = 0; c < n_cols; c++) sum += meta_r[3 * (size_t) c];
-            bool good = sum == n_rows;
-            for (int64_t k = 1; k < n_rows && good; k++) good = rows_r[(size_t) k] > rows_r[(size_t) k - 1];
-            for (size_t k = 0; k + 1 < cand.size () && good; k++) good = std::binary_search (rows_r.begin (), rows_r.begin () + n_rows, cand[k]);
-            if ((rc = agree (good ? NKP_OK : fail (NKP_ECOMM, "nkp_create_dist: ring %d is inconsistent (a water column straddles two ranks?)", ring), "ring columns"))) return rc;
-         }
-         const int64_t before = (int64_t) ocols.size ();
-         if ((rc = select_and_fetch (ring, rows_r, &got))) return rc;
-         int64_t n_erow = 0;
-         for (size_t c = (size_t) before; c < ocols.size (); c++) n_erow += ocols[c].len;
-         if ((rc = agree (got != n_erow ? fail (NKP_ECOMM, "nkp_create_dist: ring rows announced and received differ") : NKP_OK, "ring rows"))) return rc;
-         n_sel_all += got;
-         ring_first.push_back ((int) arr_gid.size ());
-      }
-#undef XCHG
-      // ---- the matrix of the hierarchy: own rows, then the overlap rows in ascending global row order (grouped by owner, so
-      // that an exchange lands them in place); columns renumbered, couplings that leave [own | overlap] dropped
-      std::vector<size_t> cord (ocols.size ());
-      for (size_t c = 0; c < cord.size (); c++) cord[c] = c;
-      std::sort (cord.begin (), cord.end (), [&] (size_t a, size_t b) { return ocols[a].g0 < ocols[b].g0; });
-      e_blk.assign (blk_start_loc, blk_start_loc + nblk_loc + 1);
-      e_ci.assign (o.col_i, o.col_i + nblk_loc);
-      e_cj.assign (o.col_j, o.col_j + nblk_loc);
-      {
-         const int64_t per = (coupled_tracer_cnt > 1 && nblk_loc % coupled_tracer_cnt == 0) ? nblk_loc / coupled_tracer_cnt : nblk_loc;
-         e_ct.resize ((size_t) nblk_loc);
-         for (int64_t c = 0; c < nblk_loc; c++) e_ct[(size_t) c] = o.col_t ? o.col_t[c] : (int32_t) (c / per);
-      }
-      std::vector<int32_t> ov_gid, ov_ecol, ov_ring;          // per overlap row (hierarchy order): global id, its column in e_*, ring
-      std::vector<int64_t> ov_arr;                            // its arrived row
-      for (size_t k = 0; k < cord.size (); k++) {
-         const OvCol &c = ocols[cord[k]];
-         for (int t = 0; t < c.len; t++) {
-            ov_gid.push_back (arr_gid[(size_t) (c.row0 + t)]);
-            ov_arr.push_back (c.row0 + t);
-            ov_ecol.push_back ((int32_t) e_ci.size ());
-            ov_ring.push_back (c.ring);
-            const auto it = std::lower_bound (halo2.begin (), halo2.begin () + n_halo2, ov_gid.back ());
-            sel_hpos.push_back ((it != halo2.begin () + n_halo2 && *it == ov_gid.back ()) ? (int32_t) (it - halo2.begin ()) : -1);
-         }
-         n_sel += c.len;
-         e_blk.push_back ((int32_t) (m_loc + n_sel));
-         e_ci.push_back (c.ci);
-         e_cj.push_back (c.cj);
-         e_ct.push_back (0);
-      }
-      auto ext_of_global = [&] (int64_t g) -> int64_t {
-         if (g >= fst_row && g < fst_row + m_loc) return g - fst_row;
-         const auto it = std::lower_bound (ov_gid.begin (), ov_gid.end (), (int32_t) g);
-         if (it == ov_gid.end () || *it != (int32_t) g) return -1;
-         return m_loc + (it - ov_gid.begin ());
-      };
-      const int64_t n_eent = (int64_t) arr_col.size ();
-      e_rowptr.assign ((size_t) (m_loc + n_sel) + 1, 0);
-      e_colind.reserve ((size_t) (nnz_loc + n_eent));
-      e_val.reserve ((size_t) (nnz_loc + n_eent));
-      D.e_org.reserve ((size_t) (nnz_loc + n_eent));
-      // (column, value, origin); columns are unique within a row, so the sort puts the origins where it puts the values
-      struct Ent { int32_t col; double v; int32_t org; };
-      std::vector<Ent> rowbuf;
-      auto flush_row = [&] (int64_t r) {
-         bool sorted = true;
-         for (size_t k = 1; k < rowbuf.size () && sorted; k++) sorted = rowbuf[k].col > rowbuf[k - 1].col;
-         if (!sorted) std::sort (rowbuf.begin (), rowbuf.end (), [] (const Ent &a, const Ent &b) { return a.col < b.col; });
-         for (const Ent &pr : rowbuf) { e_colind.push_back (pr.col); e_val.push_back (pr.v); D.e_org.push_back (pr.org); }
-         e_rowptr[(size_t) r + 1] = (int32_t) e_colind.size ();
-         rowbuf.clear ();
-      };
-      for (int64_t r = 0; r < m_loc; r++) {
-         for (int e = rowptr_loc[r]; e < rowptr_loc[r + 1]; e++) {
-            const int32_t x = colind_ext[(size_t) e];
-            if (x < m_loc) rowbuf.push_back ({ x, val[e], (int32_t) e });
-            else {
-               const int64_t q = ext_of_global (colind_glob[e]);
-               if (q >= 0) {
-                  rowbuf.push_back ({ (int32_t) q, val[e], (int32_t) e });
-                  e_ct[(size_t) ov_ecol[(size_t) (q - m_loc)]] = e_ct[(size_t) col_of[(size_t) r]];   // an overlap column carries the tracer of the rows that see it
-               }
-            }
-         }
-         flush_row (r);
-      }
-      // ... and a column of ring k + 1 that of the rows of ring k
-      for (int ring = 1; ring < rings; ring++)
-         for (int64_t k = 0; k < n_sel; k++) {
-            if (ov_ring[(size_t) k] != ring) continue;
-            for (int64_t e = arr_ptr[(size_t) ov_arr[(size_t) k]]; e < arr_ptr[(size_t) ov_arr[(size_t) k] + 1]; e++) {
-               const int64_t q = ext_of_global (arr_col[(size_t) e]);
-               if (q >= m_loc && ov_ring[(size_t) (q - m_loc)] == ring + 1) e_ct[(size_t) ov_ecol[(size_t) (q - m_loc)]] = e_ct[(size_t) ov_ecol[(size_t) k]];
-            }
-         }
-      // overlap rows; an entry's origin is its position in the value stream of all overlap rows in this order, which is the
-      // order the owners ship them in (ascending rows per destination)
-      std::vector<int> ent_need (P, 0), ras_need (P, 0);
-      {
-         int64_t q = 0;
-         int p = 0;
-         for (int64_t k = 0; k < n_sel; k++) {
-            while (ov_gid[(size_t) k] >= starts[(size_t) p + 1]) p++;
-            const int64_t a = ov_arr[(size_t) k];
-            for (int64_t e = arr_ptr[(size_t) a]; e < arr_ptr[(size_t) a + 1]; e++, q++) {
-               const int64_t x = ext_of_global (arr_col[(size_t) e]);
-               if (x < 0) continue;
-               rowbuf.push_back ({ (int32_t) x, arr_val[(size_t) e], (int32_t) (-1 - q) });
-            }
-            ent_need[p] += (int) (arr_ptr[(size_t) a + 1] - arr_ptr[(size_t) a]);
-            ras_need[p]++;
-            flush_row (m_loc + k);
-         }
-      }
-      // owner: the entries shipped over all rings, ascending rows per destination
-      std::vector<int> ent_give (P, 0), ras_give (P, 0);
-      std::vector<int32_t> ras_send;
-      int64_t ent_total = 0;
-      for (int p = 0; p < P; p++) {
-         std::vector<int32_t> &rows = shipped[(size_t) p];
-         std::sort (rows.begin (), rows.end ());
-         for (int32_t r : rows) {
-            for (int e = rowptr_loc[r]; e < rowptr_loc[r + 1]; e++) D.ship_e.push_back ((int32_t) e);
-            ent_give[p] += rowptr_loc[r + 1] - rowptr_loc[r];
-            ras_send.push_back (r);
-         }
-         ras_give[p] = (int) rows.size ();
-         ent_total += ent_give[p];
-      }
-      if (rings >= 2) {
-         int64_t recv_total = 0;
-         for (int p = 0; p < P; p++) recv_total += ent_need[p];
-         rc = n_sel != n_sel_all ? fail (NKP_ECOMM, "nkp_create_dist: overlap rows announced and received differ")
-              : std::max (ent_total, recv_total) >= 2147483647LL ? fail (NKP_EINVAL, "nkp_create_dist: overlap rows of all rings exceed the int32 exchange counts") : NKP_OK;
-         if ((rc = agree (rc, "overlap rows of all rings"))) return rc;
-         D.ras_send_rows.swap (ras_send);
-         D.ras_need = ras_need;
-         D.ras_give = ras_give;
-      }
-      D.ent_give = ent_give;
-      D.ent_need = ent_need;
-      // overlap is worth its exchange only if some rank has any: same decision everywhere
-      std::vector<int64_t> all (P + 1, 0);
-      if (comm->allgather_i64_host (comm->ctx, n_sel, all.data ())) return fail (NKP_ECOMM, "nkp_create_dist: allgather failed");
-      for (int p = 0; p < P; p++) ras = ras || all[p] > 0;
-      D.rings = ras ? (int) rings : 0;
-   }
-
-   return NKP_OK;
-}
-
-struct nkp_dist_plan { DistPlan D; int nranks = 0; int64_t m_loc = 0, nnz_loc = 0; };
-
-extern "C" int nkp_dist_overlap_plan_host (nkp_dist_plan **out, const nkp_options *opt, int64_t n_global, int64_t fst_row, int64_t m_loc, int64_t nnz_loc,
-                                           const int32_t *rowptr_loc, const int32_t *colind_glob, const double *val, const int32_t *blk_start_loc,
-                                           int64_t nblk_loc, int coupled_tracer_cnt, const nkp_comm_ops *comm)
-{
-   if (!out || !comm || !rowptr_loc || !comm->alltoallv_i32_host || !comm->allgather_i64_host) return fail (NKP_EINVAL, "nkp_dist_overlap_plan_host: bad arguments");
-   *out = nullptr;
-   const int P = comm->nranks;
-   std::vector<int64_t> starts (P + 1, 0);
-   if (comm->allgather_i64_host (comm->ctx, fst_row, starts.data ())) return fail (NKP_ECOMM, "nkp_dist_overlap_plan_host: allgather failed");
-   starts[P] = n_global;
-   nkp_options o;
-   if (opt) o = *opt;
-   else nkp_default_options (&o);
-   nkp_dist_plan *pl = new nkp_dist_plan;
-   pl->nranks = P;
-   pl->m_loc = m_loc;
-   pl->nnz_loc = nnz_loc;
-   const int rc = dist_plan (pl->D, comm, o, starts, fst_row, m_loc, nnz_loc, rowptr_loc, colind_glob, val, blk_start_loc, nblk_loc, coupled_tracer_cnt);
-   if (rc) { delete pl; return rc; }
-   *out = pl;
-   return NKP_OK;
-}
-
-// one table for sizes and copies: name -> (pointer, element count, element size)
-static bool dist_plan_field (const nkp_dist_plan *p, const char *what, const void **ptr, int64_t *count, size_t *elem)
-{
-   const DistPlan &D = p->D;
-   const int64_t n_ext = p->m_loc + D.n_sel;
-   struct F { const char *name; const void *ptr; int64_t count; size_t elem; };
-   const F fields[] = {
-      { "colind_ext", D.colind_ext.data (), p->nnz_loc, 4 }, { "halo_rows", D.halo_rows.data (), D.n_halo, 4 }, { "send_rows", D.send_rows.data (), D.nsend, 4 },
-      { "need", D.need.data (), p->nranks, 4 }, { "give", D.give.data (), p->nranks, 4 },
-      { "rowptr", D.e_rowptr.data (), D.e_rowptr.empty () ? 0 : n_ext + 1, 4 }, { "colind", D.e_colind.data (), (int64_t) D.e_colind.size (), 4 },
-      { "val", D.e_val.data (), (int64_t) D.e_val.size (), 8 }, { "blk_start", D.e_blk.data (), (int64_t) D.e_blk.size (), 4 },
-      { "col_i", D.e_ci.data (), (int64_t) D.e_ci.size (), 4 }, { "col_j", D.e_cj.data (), (int64_t) D.e_cj.size (), 4 }, { "col_t", D.e_ct.data (), (int64_t) D.e_ct.size (), 4 },
-      { "sel_hpos", D.sel_hpos.data (), D.n_sel, 4 },
-      { "ras_send_rows", D.ras_send_rows.data (), (int64_t) D.ras_send_rows.size (), 4 }, { "ras_need", D.ras_need.data (), (int64_t) D.ras_need.size (), 4 },
-      { "ras_give", D.ras_give.data (), (int64_t) D.ras_give.size (), 4 },
-   };
-   for (const F &f : fields)
-      if (!strcmp (what, f.name)) { *ptr = f.ptr; *count = f.count; *elem = f.elem; return true; }
-   return false;
-}
-
-extern "C" int64_t nkp_dist_plan_size (const nkp_dist_plan *p, const char *what)
-{
-   if (!p || !what) return -1;
-   if (!strcmp (what, "ras")) return p->D.ras ? 1 : 0;
-   if (!strcmp (what, "n_sel")) return p->D.n_sel;
-   if (!strcmp (what, "n_halo")) return p->D.n_halo;
-   if (!strcmp (what, "ras_rings")) return p->D.rings;
-   const void *ptr; int64_t count; size_t elem;
-   return dist_plan_field (p, what, &ptr, &count, &elem) ? count : -1;
-}
-
-extern "C" int nkp_dist_plan_copy (const nkp_dist_plan *p, const char *what, void *dst)
-{
-   const void *ptr; int64_t count; size_t elem;
-   if (!p || !what || !dst || !dist_plan_field (p, what, &ptr, &count, &elem)) return fail (NKP_EINVAL, "nkp_dist_plan_copy: unknown field");
-   if (count > 0) memcpy (dst, ptr, (size_t) count * elem);
-   return NKP_OK;
-}
-
-extern "C" void nkp_dist_plan_free (nkp_dist_plan *p) { delete p; }
-
+// ---------------------------------------------------------------- distributed flavour (its host-side plan: dist_plan.cpp)
 extern "C" int nkp_create_dist (nkp_solver **out, const nkp_options *opt, int64_t n_global, int64_t fst_row, int64_t m_loc,
                                 int64_t nnz_loc, const int32_t *rowptr_loc, const int32_t *colind_glob, const double *val,
                                 const int32_t *blk_start_loc, int64_t nblk_loc, int coupled_tracer_cnt, const nkp_comm_ops *comm)
@@ -2786,11 +2181,6 @@ extern "C" int nkp_create_dist (nkp_solver **out, const nkp_options *opt, int64_
    DistPlan D;
    int rc = dist_plan (D, comm, o, starts, fst_row, m_loc, nnz_loc, rowptr_loc, colind_glob, val, blk_start_loc, nblk_loc, coupled_tracer_cnt);
    if (rc) return rc;
-   auto &colind_ext = D.colind_ext; auto &send_rows = D.send_rows; auto &need = D.need; auto &give = D.give;
-   const int64_t n_halo = D.n_halo, nsend = D.nsend, n_sel = D.n_sel;
-   auto &e_rowptr = D.e_rowptr; auto &e_colind = D.e_colind; auto &e_blk = D.e_blk; auto &e_ci = D.e_ci; auto &e_cj = D.e_cj; auto &e_ct = D.e_ct;
-   auto &sel_hpos = D.sel_hpos; auto &e_val = D.e_val;
-   const bool ras = D.ras;
    // diagonal block: what the create path validates and what the hierarchy is built from without overlap
    std::vector<int32_t> drow ((size_t) m_loc + 1, 0), dcol;
    std::vector<double> dval;
@@ -2798,13 +2188,13 @@ extern "C" int nkp_create_dist (nkp_solver **out, const nkp_options *opt, int64_
    dval.reserve ((size_t) nnz_loc);
    for (int64_t r = 0; r < m_loc; r++) {
       for (int e = rowptr_loc[r]; e < rowptr_loc[r + 1]; e++)
-         if (colind_ext[e] < m_loc) { dcol.push_back (colind_ext[e]); dval.push_back (val[e]); }
+         if (D.colind_ext[e] < m_loc) { dcol.push_back (D.colind_ext[e]); dval.push_back (val[e]); }
       drow[r + 1] = (int32_t) dcol.size ();
    }
-   SpmvMatrixHost M = { nnz_loc, m_loc + n_halo, rowptr_loc, colind_ext.data (), val };
-   PrecondMatrixHost PM = { m_loc + n_sel, (int64_t) e_blk.size () - 1, e_rowptr.data (), e_colind.data (), e_val.data (), e_blk.data (), e_ci.data (), e_cj.data (), e_ct.data () };
+   SpmvMatrixHost M = { nnz_loc, m_loc + D.n_halo, rowptr_loc, D.colind_ext.data (), val };
+   PrecondMatrixHost PM = { m_loc + D.n_sel, (int64_t) D.e_blk.size () - 1, D.e_rowptr.data (), D.e_colind.data (), D.e_val.data (), D.e_blk.data (), D.e_ci.data (), D.e_cj.data (), D.e_ct.data () };
    nkp_solver *s = nullptr;
-   rc = create_impl (&s, &o, m_loc, (int64_t) dcol.size (), drow.data (), dcol.data (), dval.data (), blk_start_loc, nblk_loc, coupled_tracer_cnt, &M, ras ? &PM : nullptr);
+   rc = create_impl (&s, &o, m_loc, (int64_t) dcol.size (), drow.data (), dcol.data (), dval.data (), blk_start_loc, nblk_loc, coupled_tracer_cnt, &M, D.ras ? &PM : nullptr);
    // every rank must reach the collectives below even if its own setup failed: agree on success first
    {
       int64_t flag = rc ? 1 : 0;
@@ -2819,22 +2209,22 @@ extern "C" int nkp_create_dist (nkp_solver **out, const nkp_options *opt, int64_
    s->dist.ops = *comm;
    s->dist.n_global = n_global;
    s->dist.fst = fst_row;
-   s->dist.n_halo = n_halo;
-   s->dist.nsend = nsend;
-   s->dist.send_counts.assign (give.begin (), give.end ());
-   s->dist.recv_counts.assign (need.begin (), need.end ());
-   bool ok = dev_alloc (s, &s->dist.send_idx, (size_t) nsend) == NKP_OK && dev_alloc (s, &s->dist.sendbuf, (size_t) nsend) == NKP_OK &&
-             dev_alloc (s, &s->dist.xe, (size_t) (m_loc + n_halo)) == NKP_OK;
-   if (ok && nsend) ok = hipMemcpy (s->dist.send_idx, send_rows.data (), (size_t) nsend * sizeof (int), hipMemcpyHostToDevice) == hipSuccess;
-   if (ok && ras) {
-      s->dist.n_sel = n_sel;
-      s->dist.n_ext = m_loc + n_sel;
+   s->dist.n_halo = D.n_halo;
+   s->dist.nsend = D.nsend;
+   s->dist.send_counts.assign (D.give.begin (), D.give.end ());
+   s->dist.recv_counts.assign (D.need.begin (), D.need.end ());
+   bool ok = dev_alloc (s, &s->dist.send_idx, (size_t) D.nsend) == NKP_OK && dev_alloc (s, &s->dist.sendbuf, (size_t) D.nsend) == NKP_OK &&
+             dev_alloc (s, &s->dist.xe, (size_t) (m_loc + D.n_halo)) == NKP_OK;
+   if (ok && D.nsend) ok = hipMemcpy (s->dist.send_idx, D.send_rows.data (), (size_t) D.nsend * sizeof (int), hipMemcpyHostToDevice) == hipSuccess;
+   if (ok && D.ras) {
+      s->dist.n_sel = D.n_sel;
+      s->dist.n_ext = m_loc + D.n_sel;
       s->dist.ras_rings = D.rings;
       s->dist.ras_sep = D.rings >= 2;
-      ok = dev_alloc (s, &s->dist.rext, (size_t) (m_loc + n_sel)) == NKP_OK && dev_alloc (s, &s->dist.zext, (size_t) (m_loc + n_sel)) == NKP_OK;
+      ok = dev_alloc (s, &s->dist.rext, (size_t) (m_loc + D.n_sel)) == NKP_OK && dev_alloc (s, &s->dist.zext, (size_t) (m_loc + D.n_sel)) == NKP_OK;
       if (!s->dist.ras_sep) {
-         ok = ok && dev_alloc (s, &s->dist.sel_idx, (size_t) n_sel) == NKP_OK;
-         if (ok && n_sel) ok = hipMemcpy (s->dist.sel_idx, sel_hpos.data (), (size_t) n_sel * sizeof (int), hipMemcpyHostToDevice) == hipSuccess;
+         ok = ok && dev_alloc (s, &s->dist.sel_idx, (size_t) D.n_sel) == NKP_OK;
+         if (ok && D.n_sel) ok = hipMemcpy (s->dist.sel_idx, D.sel_hpos.data (), (size_t) D.n_sel * sizeof (int), hipMemcpyHostToDevice) == hipSuccess;
       } else {
          s->dist.ras_nsend = (int64_t) D.ras_send_rows.size ();
          s->dist.ras_send_counts.assign (D.ras_give.begin (), D.ras_give.end ());
@@ -2869,10 +2259,10 @@ extern "C" int nkp_create_dist (nkp_solver **out, const nkp_options *opt, int64_
    if (s->opt.precond == NKP_PRECOND_MULTILEVEL) {
       // nkp_refactor_dist: the hierarchy's source matrix and where its values come from (host memory only until the first call)
       DistRefactorPlan *Q = new DistRefactorPlan;
-      if (ras) {
-         Q->n_src = m_loc + n_sel;
-         Q->src_rowptr.swap (e_rowptr);
-         Q->src_colind.swap (e_colind);
+      if (D.ras) {
+         Q->n_src = m_loc + D.n_sel;
+         Q->src_rowptr.swap (D.e_rowptr);
+         Q->src_colind.swap (D.e_colind);
          Q->origin.swap (D.e_org);
          Q->ship.swap (D.ship_e);
          Q->ship_counts = D.ent_give;
@@ -2880,16 +2270,16 @@ extern "C" int nkp_create_dist (nkp_solver **out, const nkp_options *opt, int64_
          for (int c : Q->recv_counts) Q->n_recv += c;
          Q->exchange = true;
          // what a rebuild passes to ml_setup again (nkp_create's own copies are made for the diagonal block only)
-         s->h_blk.swap (e_blk);
-         s->h_col_i.swap (e_ci);
-         s->h_col_j.swap (e_cj);
-         s->h_col_t.swap (e_ct);
+         s->h_blk.swap (D.e_blk);
+         s->h_col_i.swap (D.e_ci);
+         s->h_col_j.swap (D.e_cj);
+         s->h_col_t.swap (D.e_ct);
          s->tracer_cnt = coupled_tracer_cnt;
       } else {
          Q->n_src = m_loc;
          Q->origin.reserve (dcol.size ());
          for (int64_t e = 0; e < nnz_loc; e++)
-            if (colind_ext[(size_t) e] < m_loc) Q->origin.push_back ((int32_t) e);
+            if (D.colind_ext[(size_t) e] < m_loc) Q->origin.push_back ((int32_t) e);
          Q->src_rowptr.swap (drow);
          Q->src_colind.swap (dcol);
       }
@@ -2899,62 +2289,9 @@ extern "C" int nkp_create_dist (nkp_solver **out, const nkp_options *opt, int64_
    msg (s, 1, "nkp_create_dist: %d of %d SpMV row blocks are interior (multiplied while the halo travels: %s)\n", s->dist.seg_rb[2] - s->dist.seg_rb[1],
         s->dist.seg_rb[3], s->dist.overlap ? "yes" : "no");
    msg (s, 1, "nkp_create_dist: rows [%lld, %lld) of %lld, %lld halo rows in, %lld rows out; overlap (restricted additive Schwarz): %s, %lld rows of other ranks in this rank's hierarchy (overlap depth %d)\n",
-        (long long) fst_row, (long long) (fst_row + m_loc), (long long) n_global, (long long) n_halo, (long long) nsend, s->dist.ras ? "on" : "off", (long long) s->dist.n_sel,
+        (long long) fst_row, (long long) (fst_row + m_loc), (long long) n_global, (long long) D.n_halo, (long long) D.nsend, s->dist.ras ? "on" : "off", (long long) s->dist.n_sel,
         s->dist.ras ? s->dist.ras_rings : 0);
    *out = s;
-   return NKP_OK;
-}
-
-extern "C" int nkp_cell_major_order (int64_t nblk, const int32_t *blk_start, int cnt, int32_t *perm, int32_t *blk_start_new, int32_t *col_t, int32_t *col_src)
-{
-   if (!blk_start || !perm || !blk_start_new || !col_t || !col_src || cnt < 1 || nblk < 0 || nblk % cnt != 0)
-      return fail (NKP_EINVAL, "nkp_cell_major_order: bad arguments (nblk = %lld must be a multiple of the tracer count %d)", (long long) nblk, cnt);
-   const int64_t per = nblk / cnt;
-   for (int t = 1; t < cnt; t++)
-      for (int64_t c = 0; c <= per; c++)
-         if (blk_start[t * per + c] - blk_start[t * per] != blk_start[c] - blk_start[0])
-            return fail (NKP_EINVAL, "nkp_cell_major_order: tracer %d does not have the water columns of tracer 0 (block %lld)", t, (long long) c);
-   int64_t row = 0, b = 0;
-   blk_start_new[0] = 0;
-   for (int64_t c = 0; c < per; c++)
-      for (int t = 0; t < cnt; t++, b++) {
-         const int64_t old = t * per + c;
-         for (int r = blk_start[old]; r < blk_start[old + 1]; r++) perm[row++] = r;
-         blk_start_new[b + 1] = (int32_t) row;
-         col_t[b] = t;
-         col_src[b] = (int32_t) old;
-      }
-   return NKP_OK;
-}
-
-extern "C" int nkp_permuted_rows (int64_t n, const int32_t *rowptr, const int32_t *colind, const double *val, const int32_t *perm, const int32_t *inv,
-                                  int64_t r0, int64_t r1, int32_t *rowptr_loc, int32_t *colind_loc, double *val_loc)
-{
-   if (!rowptr || !perm || !inv || !rowptr_loc || r0 < 0 || r1 < r0 || r1 > n) return fail (NKP_EINVAL, "nkp_permuted_rows: bad arguments");
-   rowptr_loc[0] = 0;
-   for (int64_t r = r0; r < r1; r++) {
-      const int old = perm[r];
-      rowptr_loc[r - r0 + 1] = rowptr_loc[r - r0] + (rowptr[old + 1] - rowptr[old]);
-   }
-   const int nt = (r1 - r0 >= 200000) ? (int) std::min (16u, std::max (1u, std::thread::hardware_concurrency ())) : 1;
-   auto work = [&] (int t) {
-      std::vector<std::pair<int32_t, double>> buf;
-      const int64_t a = r0 + (r1 - r0) * t / nt, b = r0 + (r1 - r0) * (t + 1) / nt;
-      for (int64_t r = a; r < b; r++) {
-         const int old = perm[r];
-         buf.clear ();
-         for (int e = rowptr[old]; e < rowptr[old + 1]; e++) buf.push_back ({ inv[colind[e]], val[e] });
-         std::sort (buf.begin (), buf.end (), [] (const std::pair<int32_t, double> &x, const std::pair<int32_t, double> &y) { return x.first < y.first; });
-         int64_t o = rowptr_loc[r - r0];
-         for (const auto &pr : buf) { colind_loc[o] = pr.first; val_loc[o] = pr.second; o++; }
-      }
-   };
-   if (nt == 1) work (0);
-   else {
-      std::vector<std::thread> pool;
-      for (int t = 0; t < nt; t++) pool.emplace_back (work, t);
-      for (std::thread &th : pool) th.join ();
-   }
    return NKP_OK;
 }
 

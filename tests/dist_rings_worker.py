@@ -3,7 +3,7 @@
 
   --mode plan      the plan at --rings against ring sets computed here from the global matrix, the column coordinates and
                    the partition; the residual exchange of the plan (ras_send_rows / ras_need / ras_give) run over gloo
-  --mode hash      sha256 of every field of the plan (depth 1: compared with the recorded plan of the one-ring code)
+  --mode hash      sha256 and size of every exported field of the plan and its scalars (compared with recorded plans)
   --mode mismatch  rank r asks for --rings + (r % 2) rings: every rank must end with the smallest depth
   --mode refuse    rank --bad-rank (-1: every rank) asks for --rings (out of range): every rank must refuse
 """
@@ -20,6 +20,9 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 FIELDS = ("colind_ext", "halo_rows", "send_rows", "need", "give", "rowptr", "colind", "val", "blk_start", "col_i", "col_j", "col_t", "sel_hpos")
+# everything the plan exports: also the residual exchange of two or more rings and what nkp_refactor_dist redoes the values from
+ALL_FIELDS = FIELDS + ("ras_send_rows", "ras_need", "ras_give", "origin", "ship", "ent_give", "ent_need")
+SCALARS = ("ras", "n_sel", "n_halo", "ras_rings")
 
 
 def ring_sets(A, col_of, gblk, gci, gcj, f, m, depth):
@@ -95,8 +98,9 @@ def main():
     if a.mode == "hash":
         pl = nd.overlap_plan_host(loc, n, comm, cnt) if tuning is None else nd.overlap_plan_host(loc, n, comm, cnt, tuning=tuning)
         res["ras"] = int(pl["ras"])
-        res["sha256"] = {k: hashlib.sha256(np.ascontiguousarray(pl[k]).tobytes()).hexdigest() for k in FIELDS}
-        res["sizes"] = {k: int(np.asarray(pl[k]).size) for k in FIELDS}
+        res["sha256"] = {k: hashlib.sha256(np.ascontiguousarray(pl[k]).tobytes()).hexdigest() for k in ALL_FIELDS}
+        res["sizes"] = {k: int(np.asarray(pl[k]).size) for k in ALL_FIELDS}
+        res["scalars"] = {k: int(pl[k]) for k in SCALARS}
     elif a.mode == "refuse":
         bad = a.bad_rank < 0 or rank == a.bad_rank
         try:

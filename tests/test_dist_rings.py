@@ -80,6 +80,35 @@ def test_depth_one_plan_equals_the_one_ring_plan(tmp_path, world, partition, gri
             assert r["sha256"][k] == h, (r["rank"], k, r["sizes"][k], w["sizes"][k])
 
 
+GOLDEN_RINGS = os.path.join(HERE, "golden", "ras_plan_rings_sha256.json")
+LAYOUTS = [(2, "bands", "24x20x10"), (3, "bands", "24x20x10"), (2, "cells", "24x20x10"), (3, "cells", "24x20x10"), (2, "tracers", "24x20x10"),
+           (8, "bands", "24x40x8")]
+
+
+def plan_record(res):
+    """What the recorded file keeps of every rank's plan: the scalars, and per exported field the element count and the first
+    16 hex digits of its SHA-256."""
+    return [dict(scalars=r["scalars"], fields={k: [r["sizes"][k], h[:16]] for k, h in sorted(r["sha256"].items())}) for r in res]
+
+
+@pytest.mark.parametrize("depth", [1, 2, 3])
+@pytest.mark.parametrize("world,partition,grid", LAYOUTS, ids=[f"{w}-{p}-{g}" for w, p, g in LAYOUTS])
+def test_plan_equals_the_recorded_plan(tmp_path, world, partition, grid, depth):
+    """Every exported field and scalar of every rank's plan at depths 1-3 against tests/golden/ras_plan_rings_sha256.json, which
+    was recorded from the single-function planner that preceded csrc/dist_plan.cpp (with only its field table extended by
+    origin / ship / ent_give / ent_need): the planner may be reshaped, the plan may not change."""
+    res = launch(world, "hash", str(tmp_path / "h"), extra=("--partition", partition, "--grid", grid, "--rings", str(depth)))
+    with open(GOLDEN_RINGS) as fh:
+        want = json.load(fh)[f"{world}-{partition}-{grid}"][str(depth)]
+    got = plan_record(res)
+    assert len(got) == len(want) == world
+    for rank, (g, w) in enumerate(zip(got, want)):
+        assert g["scalars"] == w["scalars"], (rank, g["scalars"], w["scalars"])
+        assert sorted(g["fields"]) == sorted(w["fields"]), rank
+        for k in w["fields"]:
+            assert g["fields"][k] == w["fields"][k], (rank, k, g["fields"][k], w["fields"][k])
+
+
 def test_tracer_partition_gets_no_overlap_at_depth_3(tmp_path):
     res = launch(2, "plan", str(tmp_path / "t"), extra=("--partition", "tracers", "--grid", "24x20x10", "--rings", "3"))
     assert all(r["ras"] == 0 and r["n_sel"] == 0 and r["ras_rings"] == 0 and r["ring_cols"] == [] for r in res), res
