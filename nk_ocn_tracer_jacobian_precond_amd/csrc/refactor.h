@@ -1,5 +1,6 @@
 // New matrix values on an existing solver's pattern (nkp_refactor, refactor.hip): the value passes of the hierarchy on the
-// device, with the maps that tie every value to the slot the setup gave it.  Not part of the C ABI.
+// device, with the maps that tie every value to the slot the setup gave it.  Not part of the C ABI.  The entry points and the
+// order these passes run in are refactor_api.hip.
 #pragma once
 #include "multilevel.h"
 #include "nkp_dev.h"

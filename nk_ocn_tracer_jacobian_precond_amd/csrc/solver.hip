@@ -7,11 +7,10 @@
 //
 // There is NO CPU fallback in this library: every entry point that computes needs a gfx950
 // device and fails with NKP_EDEVICE otherwise.
-#include "../../include/nkp.h"
-#include "nkp_dev.h"
-#include "multilevel.h"
-#include "refactor.h"
-#include "dist_plan.h"
+//
+// New matrix values on an existing solver (nkp_refactor and its kin) are refactor_api.hip; the solver object both units work on
+// is solver_impl.h.
+#include "solver_impl.h"
 
 #include <math.h>
 #include <stdarg.h>
@@ -21,15 +20,13 @@
 #include <time.h>
 
 #include <algorithm>
-#include <atomic>
-#include <memory>
 #include <string>
 #include <thread>
 #include <vector>
 
 static thread_local std::string g_last_error;
 
-int fail (int code, const char *fmt, ...)      // shared with dist_plan.cpp (dist_plan.h)
+int fail (int code, const char *fmt, ...)      // shared with dist_plan.cpp and refactor_api.hip (dist_plan.h)
 {
    char buf[512];
    va_list ap;
@@ -39,12 +36,6 @@ int fail (int code, const char *fmt, ...)      // shared with dist_plan.cpp (dis
    g_last_error = buf;
    return code;
 }
-
-#define HIPCHK(call)                                                                             \
-   do {                                                                                          \
-      hipError_t e_ = (call);                                                                    \
-      if (e_ != hipSuccess) return fail (NKP_EDEVICE, "%s failed: %s (%s:%d)", #call, hipGetErrorString (e_), __FILE__, __LINE__); \
-   } while (0)
 
 extern "C" const char *nkp_last_error (void) { return g_last_error.c_str (); }
 std::string last_error_message () { return g_last_error; }
@@ -166,118 +157,7 @@ int dist_resolve_tuning (const nkp_options *opt, nkp_tuning *out, bool *range_er
 // ---------------------------------------------------------------- solver object
 #define NKP_BERR_ROUNDING_LEVEL 1.0e-14     // 45 eps
 
-struct nkp_solver {
-   nkp_options opt;
-   nkp_tuning tune;             // resolved once in nkp_create; the matrix, column-block and hierarchy objects point at it
-   int device = 0;
-   bool stagnated = false;      // last solve stopped by the attainable-accuracy guard
-   bool borrowed = false;       // nkp_clone: matrix, factors and hierarchy belong to the solver this one was cloned from
-   hipStream_t stream = nullptr;
-   bool own_stream = false;
-   CsrDev A;
-   ColBlocksDev B;
-   MlHierarchy ml;
-   // row-distributed flavour: halo exchange before every SpMV, allreduce after every local reduction
-   struct {
-      bool on = false;
-      nkp_comm_ops ops;
-      int64_t n_global = 0, fst = 0, n_halo = 0, nsend = 0;
-      std::vector<int> send_counts, recv_counts;
-      int *send_idx = nullptr;        // local rows other ranks need, grouped by destination rank
-      double *sendbuf = nullptr;      // packed values for them
-      double *xe = nullptr;           // [n + n_halo] extended SpMV input: own rows then halo rows
-      // overlap of the halo exchange with the SpMV of the interior rows (rows without off-rank columns): the row blocks
-      // are built per segment [head boundary rows | interior | tail boundary rows]; seg_rb[q] = first row block of segment q
-      int seg_rb[4] = { 0, 0, 0, 0 };
-      bool overlap = false;
-      hipStream_t comm_stream = nullptr;
-      hipEvent_t ev_packed = nullptr, ev_halo = nullptr;
-      // restricted additive Schwarz: the hierarchy of this rank also covers the neighbouring ranks' water columns its rows
-      // couple to laterally (one ring); a cycle runs on [own rows | those halo rows] and only the own part is kept
-      bool ras = false;
-      int64_t n_ext = 0, n_sel = 0;
-      int *sel_idx = nullptr;         // position in the halo of every overlap row (one ring)
-      double *rext = nullptr, *zext = nullptr;
-      // two or more rings (tuning dist_ras_rings): rows of ring 2 and beyond are not in the SpMV halo, so the overlap residual has
-      // an exchange of its own -- own rows sent (by destination), their packed values, per-rank counts; the rows arrive at
-      // rext + n in the hierarchy's order.  bras_send / bras_recv: the same K wide (batch_prepare)
-      int ras_rings = 0;              // the depth the ranks agreed on, 0 without overlap
-      bool ras_sep = false;
-      int64_t ras_nsend = 0;
-      int *ras_send_idx = nullptr;
-      double *ras_sendbuf = nullptr, *bras_send = nullptr, *bras_recv = nullptr;
-      std::vector<int> ras_send_counts, ras_recv_counts, ras_send_counts_k, ras_recv_counts_k;
-      // K right-hand sides in lockstep: the K-interleaved operator input [own rows | halo rows] x K, the
-      // K-wide send rows, the plan's counts times K, and the group's Gram-Schmidt messages
-      // gmsg = dots [K x (m + 2)] | second pass [K x (m + 2)] | norms [K] | 1 / norms [K], ghpin its pinned host mirror
-      double *bxe = nullptr, *bsend = nullptr, *gmsg = nullptr, *ghpin = nullptr;
-      int bK = 0;                     // width these buffers exist for
-      int agreed_K = 0;               // widest interleave every rank is known to have buffers for
-      std::vector<int> send_counts_k, recv_counts_k;
-   } dist;
-   int64_t n = 0, ld = 0;
-   int m = 0;
-   // work vectors
-   bool vf32 = false;              // Krylov basis stored as float (stride ld floats inside the V allocation)
-   double *vcur = nullptr;         // f64 copy of the newest basis vector (input of the next preconditioner call)
-   double *V = nullptr, *Z = nullptr, *w = nullptr, *r = nullptr, *x = nullptr, *b = nullptr, *t1 = nullptr, *t2 = nullptr;
-   double *p1 = nullptr, *p2 = nullptr;   // scratch of the multi-step preconditioner (NKP_PRECOND_STEPS > 1)
-   int precond_steps = 1;        // configured cycles per application
-   int steps_now = 1;            // cycles per application of the running solve (the run-time guard may lower it for one solve)
-   bool equil = false;           // row-weighted FGMRES
-   double *rscale = nullptr, *rinv = nullptr;   // R and R^-1 (device), R_i = 1 / max_j |a_ij|
-   double *eqtmp = nullptr;      // R^-1 v_j, the input of the preconditioner in the row-weighted iteration
-   bool comm_failed = false;     // a collective callback returned non-zero: every verdict after that is NKP_ECOMM
-   double *partial = nullptr;       // reduction scratch
-   double *dscal = nullptr;         // device scalars: h[m+2] | h2[m+2] | misc[16] | ycoef[m+1]
-   double *hpin = nullptr;          // pinned host mirror
-   int *dint = nullptr;             // device ints
-   // K right-hand sides at once (nkp_solve_batch_device): K - 1 more sets of work vectors (clones sharing this solver's stream)
-   // and three K-interleaved vectors around the batched operator / cycle application
-   std::vector<nkp_solver *> batch_members;
-   double *bvin = nullptr, *bz = nullptr, *bw = nullptr;
-   int batch_K = 0;
-   int64_t batch_steps = 0;         // batched operator applications (lockstep Krylov steps) over the solver's life
-   int batch_width = 0;             // K of the last batched group
-   size_t device_bytes = 0;
-   double create_seconds = 0.0;     // wall time of nkp_create
-   // nkp_refactor: state shared by a solver and its clones (live clones, a refactor that failed after its commit point),
-   // the owner's work space, and the host arrays a rebuild of the hierarchy needs again
-   struct Shared {
-      std::atomic<int> clones { 0 };
-      std::atomic<int64_t> alltoallv_calls { 0 }, allreduce_calls { 0 };      // device collectives of solves (a batch's members count here too)
-      bool broken = false;
-      std::string why;
-   };
-   std::shared_ptr<Shared> shared = std::make_shared<Shared> ();
-   RefactorWork *rf = nullptr;
-   std::vector<int> h_blk, h_col_i, h_col_j, h_col_t;
-   int tracer_cnt = 1;
-   int64_t refactor_count = 0;
-   int refactor_rebuilt = 0;
-   double refactor_seconds = 0.0;
-   // nkp_refactor_dist: where the values of the hierarchy's source come from (kept by nkp_create_dist, multilevel only)
-   DistRefactorPlan *dplan = nullptr;
-   int64_t refactor_halo_values = 0;
-   double *h_dev () { return dscal; }
-   double *h2_dev () { return dscal + (m + 2); }
-   double *misc_dev () { return dscal + 2 * (m + 2); }     // [0]=nrm2 [1]=inv [2]=dot out ...
-   double *y_dev () { return dscal + 2 * (m + 2) + 16; }
-};
-
-template <class T>
-static int dev_alloc (nkp_solver *s, T **p, size_t count)
-{
-   void *q = nullptr;
-   size_t bytes = (count ? count : 1) * sizeof (T);
-   hipError_t e = hipMalloc (&q, bytes);
-   if (e != hipSuccess) return fail (NKP_ENOMEM, "hipMalloc of %zu bytes failed: %s", bytes, hipGetErrorString (e));
-   *p = (T *) q;
-   s->device_bytes += bytes;
-   return NKP_OK;
-}
-
-static void solver_free (nkp_solver *s)
+void solver_free (nkp_solver *s)
 {
    if (!s) return;
    if (s->borrowed) {           // a clone owns its work vectors, its level vectors and its stream, nothing else
@@ -327,7 +207,7 @@ static void solver_free (nkp_solver *s)
 
 extern "C" void nkp_destroy (nkp_solver *s) { solver_free (s); }
 
-static void msg (const nkp_solver *s, int lvl, const char *fmt, ...)
+void msg (const nkp_solver *s, int lvl, const char *fmt, ...)
 {
    if (s->opt.verbose < lvl) return;
    va_list ap;
@@ -433,6 +313,41 @@ struct PrecondMatrixHost {
    const int32_t *blk_start, *col_i, *col_j, *col_t;
 };
 
+// nkp_create's developer switch ml_drop_intertracer, again in a rebuild of the hierarchy (solver_impl.h)
+void drop_intertracer (int64_t n, int tracer_cnt, const int32_t *rowptr, const int32_t *colind, const double *val,
+                       std::vector<int32_t> &f_rowptr, std::vector<int32_t> &f_colind, std::vector<double> &f_val)
+{
+   const int64_t tsl = n / tracer_cnt;
+   f_rowptr.assign ((size_t) n + 1, 0);
+   for (int64_t i = 0; i < n; i++) {
+      for (int32_t e = rowptr[i]; e < rowptr[i + 1]; e++)
+         if (colind[e] / tsl == i / tsl) { f_colind.push_back (colind[e]); f_val.push_back (val[e]); }
+      f_rowptr[(size_t) i + 1] = (int32_t) f_colind.size ();
+   }
+}
+
+// The work vectors of one system in flight (a solver's own, a clone's, a batch member's), for s->m, s->ld, s->precond_steps and
+// s->equil as they stand.  A failure leaves what was allocated to solver_free.
+static int alloc_work_vectors (nkp_solver *s)
+{
+   const size_t ld = (size_t) s->ld, m = (size_t) s->m, nscal = 3 * (m + 2) + 16 + 8;
+   const struct { double **p; size_t count; } vec[] = {
+      { &s->V, ld * (m + 1) }, { &s->vcur, ld }, { &s->Z, ld * m }, { &s->w, ld }, { &s->r, ld }, { &s->x, ld }, { &s->b, ld }, { &s->t1, ld }, { &s->t2, ld },
+      { &s->p1, s->precond_steps > 1 ? ld : 0 }, { &s->p2, s->precond_steps > 1 ? ld : 0 }, { &s->eqtmp, s->equil ? ld : 0 },
+      { &s->partial, ((m + 1 + NKP_DOT_CHUNK) / NKP_DOT_CHUNK + 1) * NKP_RED_BLOCKS * (NKP_DOT_CHUNK + 1) }, { &s->dscal, nscal } };
+   int rc = NKP_OK;
+   for (const auto &v : vec)
+      if (v.count && (rc = dev_alloc (s, v.p, v.count))) return rc;
+   if ((rc = dev_alloc (s, &s->dint, 8))) return rc;
+   HIPCHK (hipHostMalloc ((void **) &s->hpin, (m + 16) * sizeof (double), hipHostMallocDefault));
+   HIPCHK (hipMemset (s->dscal, 0, nscal * sizeof (double)));
+   return NKP_OK;
+}
+
+// create_impl and clone_impl: a failed step frees the solver under construction and returns its code
+#define TRY(x) do { rc = (x); if (rc != NKP_OK) { solver_free (s); return rc; } } while (0)
+#define TRYHIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { rc = fail (NKP_EDEVICE, "%s failed: %s", #call, hipGetErrorString (e_)); solver_free (s); return rc; } } while (0)
+
 static int create_impl (nkp_solver **out, const nkp_options *opt_in, int64_t n, int64_t nnz,
                         const int32_t *rowptr, const int32_t *colind, const double *val,
                         const int32_t *blk_start, int64_t nblk, int coupled_tracer_cnt, const SpmvMatrixHost *spmv_mat,
@@ -529,8 +444,6 @@ static int create_impl (nkp_solver **out, const nkp_options *opt_in, int64_t n, 
    struct timespec ts0_;
    clock_gettime (CLOCK_MONOTONIC, &ts0_);
    auto since0 = [&] () { struct timespec t; clock_gettime (CLOCK_MONOTONIC, &t); return (double) (t.tv_sec - ts0_.tv_sec) + 1e-9 * (double) (t.tv_nsec - ts0_.tv_nsec); };
-#define TRY(x) do { rc = (x); if (rc != NKP_OK) { solver_free (s); return rc; } } while (0)
-#define TRYHIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { rc = fail (NKP_EDEVICE, "%s failed: %s", #call, hipGetErrorString (e_)); solver_free (s); return rc; } } while (0)
    TRYHIP (hipStreamCreateWithFlags (&s->stream, hipStreamNonBlocking));
    s->own_stream = true;
    s->n = n;
@@ -618,27 +531,8 @@ static int create_impl (nkp_solver **out, const nkp_options *opt_in, int64_t n, 
 
    const double t_matrix = since0 ();
    // work space
-   const int m = s->m;
-   TRY (dev_alloc (s, &s->V, (size_t) s->ld * (size_t) (m + 1)));
-   TRY (dev_alloc (s, &s->vcur, (size_t) s->ld));
    s->vf32 = opt.basis_f32 != 0;
-   TRY (dev_alloc (s, &s->Z, (size_t) s->ld * (size_t) m));
-   TRY (dev_alloc (s, &s->w, (size_t) s->ld));
-   TRY (dev_alloc (s, &s->r, (size_t) s->ld));
-   TRY (dev_alloc (s, &s->x, (size_t) s->ld));
-   TRY (dev_alloc (s, &s->b, (size_t) s->ld));
-   TRY (dev_alloc (s, &s->t1, (size_t) s->ld));
-   TRY (dev_alloc (s, &s->t2, (size_t) s->ld));
-   if (s->precond_steps > 1) {
-      TRY (dev_alloc (s, &s->p1, (size_t) s->ld));
-      TRY (dev_alloc (s, &s->p2, (size_t) s->ld));
-   }
-   if (s->equil) TRY (dev_alloc (s, &s->eqtmp, (size_t) s->ld));
-   TRY (dev_alloc (s, &s->partial, (size_t) ((m + 1 + NKP_DOT_CHUNK) / NKP_DOT_CHUNK + 1) * NKP_RED_BLOCKS * (NKP_DOT_CHUNK + 1)));
-   TRY (dev_alloc (s, &s->dscal, (size_t) (3 * (m + 2) + 16 + 8)));
-   TRY (dev_alloc (s, &s->dint, 8));
-   TRYHIP (hipHostMalloc ((void **) &s->hpin, (size_t) (m + 16) * sizeof (double), hipHostMallocDefault));
-   TRYHIP (hipMemset (s->dscal, 0, (size_t) (3 * (m + 2) + 16 + 8) * sizeof (double)));
+   TRY (alloc_work_vectors (s));
 
    const double t_work = since0 ();
    if (opt.precond == NKP_PRECOND_MULTILEVEL && !pm) {
@@ -659,13 +553,7 @@ static int create_impl (nkp_solver **out, const nkp_options *opt_in, int64_t n, 
       std::vector<int32_t> f_rowptr, f_colind;
       std::vector<double> f_val;
       if (tune.ml_drop_intertracer && coupled_tracer_cnt > 1) {
-         const int64_t tsl = n / coupled_tracer_cnt;
-         f_rowptr.assign ((size_t) n + 1, 0);
-         for (int64_t i = 0; i < n; i++) {
-            for (int32_t e = rowptr[i]; e < rowptr[i + 1]; e++)
-               if (colind[e] / tsl == i / tsl) { f_colind.push_back (colind[e]); f_val.push_back (val[e]); }
-            f_rowptr[(size_t) i + 1] = (int32_t) f_colind.size ();
-         }
+         drop_intertracer (n, coupled_tracer_cnt, rowptr, colind, val, f_rowptr, f_colind, f_val);
          rowptr = f_rowptr.data ();
          colind = f_colind.data ();
          val = f_val.data ();
@@ -734,8 +622,6 @@ static int create_impl (nkp_solver **out, const nkp_options *opt_in, int64_t n, 
    s->create_seconds = since0 ();
    *out = s;
    return NKP_OK;
-#undef TRY
-#undef TRYHIP
 }
 
 // ---------------------------------------------------------------- hierarchy introspection (tests)
@@ -1255,30 +1141,9 @@ static int clone_impl (nkp_solver *src, nkp_solver **out, bool member)
    s->dint = nullptr;
    for (MlLevel &L : s->ml.lev) L.x = L.x2 = L.b = L.r = nullptr;
    int rc = NKP_OK;
-#define TRY(x) do { rc = (x); if (rc != NKP_OK) { solver_free (s); return rc; } } while (0)
-#define TRYHIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { rc = fail (NKP_EDEVICE, "%s failed: %s", #call, hipGetErrorString (e_)); solver_free (s); return rc; } } while (0)
    TRYHIP (hipStreamCreateWithFlags (&s->stream, hipStreamNonBlocking));
    s->own_stream = true;
-   const int m = s->m;
-   TRY (dev_alloc (s, &s->V, (size_t) s->ld * (size_t) (m + 1)));
-   TRY (dev_alloc (s, &s->vcur, (size_t) s->ld));
-   TRY (dev_alloc (s, &s->Z, (size_t) s->ld * (size_t) m));
-   TRY (dev_alloc (s, &s->w, (size_t) s->ld));
-   TRY (dev_alloc (s, &s->r, (size_t) s->ld));
-   TRY (dev_alloc (s, &s->x, (size_t) s->ld));
-   TRY (dev_alloc (s, &s->b, (size_t) s->ld));
-   TRY (dev_alloc (s, &s->t1, (size_t) s->ld));
-   TRY (dev_alloc (s, &s->t2, (size_t) s->ld));
-   if (s->precond_steps > 1) {
-      TRY (dev_alloc (s, &s->p1, (size_t) s->ld));
-      TRY (dev_alloc (s, &s->p2, (size_t) s->ld));
-   }
-   if (s->equil) TRY (dev_alloc (s, &s->eqtmp, (size_t) s->ld));
-   TRY (dev_alloc (s, &s->partial, (size_t) ((m + 1 + NKP_DOT_CHUNK) / NKP_DOT_CHUNK + 1) * NKP_RED_BLOCKS * (NKP_DOT_CHUNK + 1)));
-   TRY (dev_alloc (s, &s->dscal, (size_t) (3 * (m + 2) + 16 + 8)));
-   TRY (dev_alloc (s, &s->dint, 8));
-   TRYHIP (hipHostMalloc ((void **) &s->hpin, (size_t) (m + 16) * sizeof (double), hipHostMallocDefault));
-   TRYHIP (hipMemset (s->dscal, 0, (size_t) (3 * (m + 2) + 16 + 8) * sizeof (double)));
+   TRY (alloc_work_vectors (s));
    for (MlLevel &L : s->ml.lev) {
       TRY (dev_alloc (s, &L.x, (size_t) L.n));
       TRY (dev_alloc (s, &L.x2, (size_t) L.n));
@@ -1289,11 +1154,12 @@ static int clone_impl (nkp_solver *src, nkp_solver **out, bool member)
       TRYHIP (hipMemset (L.b, 0, (size_t) (L.n ? L.n : 1) * sizeof (double)));
       TRYHIP (hipMemset (L.r, 0, (size_t) (L.n ? L.n : 1) * sizeof (double)));
    }
-#undef TRY
-#undef TRYHIP
    *out = s;
    return NKP_OK;
 }
+
+#undef TRY
+#undef TRYHIP
 
 extern "C" int nkp_clone (nkp_solver *src, nkp_solver **out) { return clone_impl (src, out, false); }
 
@@ -1546,7 +1412,19 @@ static int fgmres_batch (nkp_solver *s, int K, int nact, nkp_solver *const *mem,
    return NKP_OK;
 }
 
-static int dist_agree (nkp_solver *s, int local_rc, const char *who, const char *where);
+// all ranks leave a step together (solver_impl.h)
+int dist_agree (nkp_solver *s, int local_rc, const char *who, const char *where)
+{
+   const nkp_comm_ops &c = s->dist.ops;
+   std::vector<int64_t> all ((size_t) c.nranks + 1, 0);
+   const std::string mine = local_rc ? g_last_error : std::string ();
+   const bool comm_ok = c.allgather_i64_host (c.ctx, local_rc ? 1 : 0, all.data ()) == 0;
+   if (local_rc) { g_last_error = mine; return local_rc; }
+   if (!comm_ok) return fail (NKP_ECOMM, "%s: allgather failed (%s)", who, where);
+   for (int p = 0; p < c.nranks; p++)
+      if (all[(size_t) p]) return fail (NKP_ECOMM, "%s: rank %d failed (%s); see its message", who, p, where);
+   return NKP_OK;
+}
 
 static int sev_of (int c) { return c == NKP_OK ? 0 : c == NKP_OK_BERR ? 1 : c == NKP_NOT_CONVERGED ? 2 : 3; }
 
@@ -1692,355 +1570,6 @@ extern "C" int nkp_solve (nkp_solver *s, double *b_in_x_out, int nrhs, int64_t l
    }
    return worst;
 }
-
-// ---------------------------------------------------------------- new values on the same pattern (refactor.hip)
-// A new hierarchy H2 from a host copy of the matrix the hierarchy is built from, with new values, exactly as nkp_create builds
-// it (with its inter-tracer filter when `filter`; dev = a device copy of the unfiltered matrix, or NULL).  0 or an nkp error
-// code with the message in err; H2 is empty on failure.
-static int rebuild_hierarchy (nkp_solver *s, MlHierarchy &H2, int64_t n, const int32_t *rowptr, const int32_t *colind, const double *val, bool filter,
-                              const CsrDev *dev, char *err, size_t errlen)
-{
-   // nkp_create's filter (developer switch ml_drop_intertracer)
-   std::vector<int32_t> f_rowptr, f_colind;
-   std::vector<double> f_val;
-   if (filter) {
-      const int64_t tsl = n / s->tracer_cnt;
-      f_rowptr.assign ((size_t) n + 1, 0);
-      for (int64_t i = 0; i < n; i++) {
-         for (int32_t e = rowptr[i]; e < rowptr[i + 1]; e++)
-            if (colind[e] / tsl == i / tsl) { f_colind.push_back (colind[e]); f_val.push_back (val[e]); }
-         f_rowptr[(size_t) i + 1] = (int32_t) f_colind.size ();
-      }
-      rowptr = f_rowptr.data ();
-      colind = f_colind.data ();
-      val = f_val.data ();
-   }
-   auto opt_ptr = [] (const std::vector<int> &a) { return a.empty () ? nullptr : a.data (); };
-   const int mrc = ml_setup (H2, n, rowptr, colind, val, s->h_blk.data (), (int64_t) s->h_blk.size () - 1, opt_ptr (s->h_col_i), opt_ptr (s->h_col_j), opt_ptr (s->h_col_t),
-                             s->tracer_cnt, s->opt.ml_levels, s->opt.ml_smooth, s->tune.ml_coarsest_rows, s->opt.verbose, s->opt.rank, s->stream, err, errlen, s->tune,
-                             f_rowptr.empty () ? dev : nullptr);
-   if (mrc != 0) {
-      (void) hipStreamSynchronize (s->stream);
-      ml_free (H2);
-      (void) hipGetLastError ();
-   }
-   return mrc;
-}
-
-// Everything after the commit point but A's values (already copied from W.aval): row scaling, the hierarchy (rebuild: H2
-// replaces it; otherwise rf_commit writes the prepared values), the column factors.  0 or -2 / -3 / -4 with a message in err.
-static int refactor_commit (nkp_solver *s, bool rebuilt, MlHierarchy &H2, char *err, size_t errlen)
-{
-   RefactorWork &W = *s->rf;
-   hipStream_t st = s->stream;
-   const bool multilevel = s->opt.precond == NKP_PRECOND_MULTILEVEL;
-   if (s->equil) rf_launch_row_scale (s->A, W.aval, s->rscale, s->rinv, st);
-   int rc = 0;
-   if (multilevel && rebuilt) {
-      for (nkp_solver *c : s->batch_members) solver_free (c);      // they copied the old hierarchy; batch_prepare makes new ones
-      s->batch_members.clear ();
-      (void) hipStreamSynchronize (st);
-      s->device_bytes -= s->ml.device_bytes;
-      ml_free (s->ml);
-      s->ml = H2;
-      s->device_bytes += s->ml.device_bytes;
-      s->device_bytes -= rf_free_maps (W);
-   } else if (multilevel) {
-      int replaced = 0;
-      const size_t before = s->ml.device_bytes;
-      rc = rf_commit (W, s->ml, st, err, errlen, &replaced);
-      s->device_bytes += s->ml.device_bytes - before;
-      if (replaced) {                                                 // new coarsest buffers: the batch members copied the old pointers
-         for (nkp_solver *c : s->batch_members) solver_free (c);
-         s->batch_members.clear ();
-      }
-   } else if (s->opt.precond == NKP_PRECOND_COLUMN_JACOBI) {
-      // the distributed flavour's A also holds the halo columns: they lie outside every water-column block, and the factor
-      // kernel skips columns outside the block (colblock_factor_kernel), as it did in nkp_create_dist
-      const size_t before = W.bytes;
-      rc = rf_column_factor (W, s->A, s->B, st, err, errlen);
-      s->device_bytes += W.bytes - before;
-   }
-   if (hipStreamSynchronize (st) != hipSuccess || hipGetLastError () != hipSuccess) {
-      if (!rc) { rc = -3; snprintf (err, errlen, "a HIP call failed"); }
-   }
-   return rc;
-}
-
-// Nothing a solve reads is written before the last check that can refuse the call: the new values are staged and their
-// diagonals checked on the device; then either (fast path) the hierarchy's new values are computed into work buffers and
-// their pattern drift counted, or (rebuild: asked for, drift, or a construction the fast path does not cover) a whole new
-// hierarchy is built beside the old one.  Only then are the matrix, the row scaling and the hierarchy overwritten.
-static int refactor_impl (nkp_solver *s, const double *h_val, const void *d_val, int flags, const char *who)
-{
-   if (!s || (!h_val && !d_val)) return fail (NKP_EINVAL, "%s: NULL argument", who);
-   if (s->borrowed) return fail (NKP_EINVAL, "%s: a clone shares its matrix; refactor the solver it was cloned from", who);
-   if (s->dist.on) return fail (NKP_EINVAL, "%s: not available for the row-distributed flavour; every rank calls nkp_refactor_dist instead", who);
-   if (flags & ~NKP_REFACTOR_REBUILD) return fail (NKP_EINVAL, "%s: unknown flags 0x%x", who, flags);
-   HIPCHK (hipSetDevice (s->device));
-   struct timespec ts0;
-   clock_gettime (CLOCK_MONOTONIC, &ts0);
-   const int64_t n = s->n, nnz = s->A.nnz;
-   hipStream_t st = s->stream;
-   HIPCHK (hipStreamSynchronize (st));
-   if (!s->rf) s->rf = new RefactorWork;
-   RefactorWork &W = *s->rf;
-   const bool staged = W.aval != nullptr;
-   if (rf_stage (W, nnz, (int) s->ml.lev.size ()) != 0) return fail (NKP_ENOMEM, "%s: no device memory for the staged values", who);
-   if (!staged) s->device_bytes += ((size_t) nnz + 2) * sizeof (double) + (4 + 2 * 64) * sizeof (int);
-   if (nnz) HIPCHK (hipMemcpyAsync (W.aval, h_val ? (const void *) h_val : d_val, (size_t) nnz * sizeof (double), h_val ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, st));
-   if (s->opt.precond != NKP_PRECOND_NONE) {
-      rf_launch_diag_check (s->A, W.aval, W.dcnt, st);
-      int c[3] = { 0, 0, 0 };
-      HIPCHK (hipMemcpyAsync (c, W.dcnt, sizeof c, hipMemcpyDeviceToHost, st));
-      HIPCHK (hipStreamSynchronize (st));
-      if (c[1]) return fail (NKP_ESINGULAR, "%s: row %d has no (or a zero) diagonal entry (%d such rows); the solver is unchanged", who, c[2] - 1, c[1]);
-   }
-   const bool multilevel = s->opt.precond == NKP_PRECOND_MULTILEVEL;
-   bool rebuild = multilevel && (flags & NKP_REFACTOR_REBUILD);
-   if (multilevel && !rebuild) {
-      // the fast path covers the default construction of the whole matrix (filtered inter-tracer couplings: rebuild)
-      if (s->tune.ml_drop_intertracer && s->tracer_cnt > 1) rebuild = true;
-      if (!rebuild && !W.maps) {
-         const int mrc = rf_build_maps (W, s->ml, s->A, st);
-         if (mrc == 0) s->device_bytes += W.bytes;
-         else {
-            rf_free_maps (W);
-            if (mrc < 0) return fail (mrc == -2 ? NKP_ENOMEM : NKP_EDEVICE, "%s: the value maps of the hierarchy could not be built (%s)", who, mrc == -2 ? "out of device memory" : "HIP failure");
-            rebuild = true;
-         }
-      }
-      if (!rebuild) {
-         rf_values (W, s->ml, s->A, W.aval, st);
-         int drift = 0;
-         HIPCHK (hipMemcpyAsync (&drift, W.dcnt, sizeof drift, hipMemcpyDeviceToHost, st));
-         HIPCHK (hipStreamSynchronize (st));
-         HIPCHK (hipGetLastError ());
-         if (drift) {
-            msg (s, 1, "%s: %d couplings of the hierarchy appear or vanish with the new values: rebuilding it\n", who, drift);
-            rebuild = true;
-         }
-      }
-      if (!rebuild) {
-         // the coarsest inverse of the new values, before the commit point: a singular operator, or one whose inverse needs
-         // other storage than the clones point at, is refused with the solver unchanged
-         char err[256] = "";
-         const int irc = rf_prepare_inverse (W, s->ml, st, err, sizeof err);
-         if (irc) return fail (irc == -4 ? NKP_ESINGULAR : irc == -2 ? NKP_ENOMEM : NKP_EDEVICE, "%s", err);
-         const int live = s->shared->clones.load () - (int) s->batch_members.size ();
-         if (live > 0 && !rf_inverse_same_storage (W, s->ml)) {
-            rf_drop_inverse (W);
-            return fail (NKP_EINVAL, "%s: the coarsest inverse of the new values needs other storage, which %d live clone(s) would not see; destroy them first", who, live);
-         }
-      }
-   }
-   MlHierarchy H2;
-   if (rebuild) {
-      const int live = s->shared->clones.load () - (int) s->batch_members.size ();
-      if (live > 0) return fail (NKP_EINVAL, "%s: the hierarchy has to be rebuilt, which %d live clone(s) would not see; destroy them first", who, live);
-      std::vector<int32_t> rp ((size_t) n + 1), ci ((size_t) nnz);
-      std::vector<double> v ((size_t) nnz);
-      HIPCHK (hipMemcpy (rp.data (), s->A.rowptr, rp.size () * sizeof (int32_t), hipMemcpyDeviceToHost));
-      if (nnz) {
-         HIPCHK (hipMemcpy (ci.data (), s->A.colind, ci.size () * sizeof (int32_t), hipMemcpyDeviceToHost));
-         HIPCHK (hipMemcpy (v.data (), W.aval, v.size () * sizeof (double), hipMemcpyDeviceToHost));
-      }
-      char err[256] = "";
-      // the staged values on the device stand in for A's (as A does in nkp_create), so the device passes need no upload
-      CsrDev staged_A = s->A;
-      staged_A.val = W.aval;
-      const int mrc = rebuild_hierarchy (s, H2, n, rp.data (), ci.data (), v.data (), s->tune.ml_drop_intertracer && s->tracer_cnt > 1, &staged_A, err, sizeof err);
-      if (mrc != 0) return fail (mrc, "%s: %s (the solver is unchanged)", who, err);
-   }
-
-   // ---- commit point: from here on the solver's own buffers are written
-   if (nnz) HIPCHK (hipMemcpyAsync (s->A.val, W.aval, (size_t) nnz * sizeof (double), hipMemcpyDeviceToDevice, st));
-   char err[256] = "";
-   int rc = refactor_commit (s, multilevel && rebuild, H2, err, sizeof err);
-   if (rc) {
-      s->shared->broken = true;
-      s->shared->why = std::string (who) + " failed after writing part of the new values (" + err + "); this solver and its clones cannot solve until a refactor succeeds";
-      return fail (rc == -4 ? NKP_ESINGULAR : rc == -2 ? NKP_ENOMEM : NKP_EDEVICE, "%s: %s", who, err);
-   }
-   s->shared->broken = false;
-   s->refactor_count++;
-   s->refactor_rebuilt = rebuild ? 1 : 0;
-   struct timespec ts1;
-   clock_gettime (CLOCK_MONOTONIC, &ts1);
-   s->refactor_seconds = (double) (ts1.tv_sec - ts0.tv_sec) + 1e-9 * (double) (ts1.tv_nsec - ts0.tv_nsec);
-   msg (s, 1, "%s: %s, %.3f s\n", who, rebuild ? "hierarchy rebuilt" : "coarse cells kept", s->refactor_seconds);
-   return NKP_OK;
-}
-
-extern "C" int nkp_refactor (nkp_solver *s, const double *val, int flags) { return refactor_impl (s, val, nullptr, flags, "nkp_refactor"); }
-
-extern "C" int nkp_refactor_device (nkp_solver *s, const void *d_val, int flags) { return refactor_impl (s, nullptr, d_val, flags, "nkp_refactor_device"); }
-
-// ---------------------------------------------------------------- new values on a row-distributed solver (refactor_dist.hip)
-// Collective.  Every rank stages its own rows' values and checks them; the overlap rows of restricted additive Schwarz get their
-// values from their owners through one alltoallv of device doubles; then each rank runs the single-GPU value passes (or a
-// rebuild) on its hierarchy's source matrix.  Three agreements through allgather_i64_host keep the ranks together:
-//   (a) arguments, staged values, own diagonals, device maps      a failure anywhere: every rank unchanged
-//   (b) new values of the hierarchy, drift, coarsest inverse, or a rebuilt hierarchy beside the old one: the same
-//   (c) the commit                                                a failure anywhere: every rank's solver unusable
-// A rank whose own step failed returns its code and message, every other rank NKP_ECOMM naming it.  The callbacks are reached
-// in the same order on every rank (allgather, [alltoallv], allgather, allgather) whatever path each rank takes locally.
-static int dist_agree (nkp_solver *s, int local_rc, const char *who, const char *where)
-{
-   const nkp_comm_ops &c = s->dist.ops;
-   std::vector<int64_t> all ((size_t) c.nranks + 1, 0);
-   const std::string mine = local_rc ? g_last_error : std::string ();
-   const bool comm_ok = c.allgather_i64_host (c.ctx, local_rc ? 1 : 0, all.data ()) == 0;
-   if (local_rc) { g_last_error = mine; return local_rc; }
-   if (!comm_ok) return fail (NKP_ECOMM, "%s: allgather failed (%s)", who, where);
-   for (int p = 0; p < c.nranks; p++)
-      if (all[(size_t) p]) return fail (NKP_ECOMM, "%s: rank %d failed (%s); see its message", who, p, where);
-   return NKP_OK;
-}
-
-static int refactor_dist_impl (nkp_solver *s, const double *h_val, const void *d_val, int flags, const char *who)
-{
-   if (!s || (!h_val && !d_val)) return fail (NKP_EINVAL, "%s: NULL argument", who);
-   if (!s->dist.on) return refactor_impl (s, h_val, d_val, flags, who);      // nkp_create_dist made a plain solver
-   // a rank that rebuilds its hierarchy drops its batch members (refactor_commit) and has to allocate them again, which can
-   // fail on that rank alone: the next batched solve agrees on its width anew on every rank
-   s->dist.agreed_K = 0;
-   struct timespec ts0;
-   clock_gettime (CLOCK_MONOTONIC, &ts0);
-   const int64_t nnz = s->A.nnz;
-   hipStream_t st = s->stream;
-   const bool multilevel = s->opt.precond == NKP_PRECOND_MULTILEVEL;
-   DistRefactorPlan *Q = s->dplan;
-   if (!s->rf) s->rf = new RefactorWork;
-   RefactorWork &W = *s->rf;
-
-   // ---- (a) this rank's arguments, its staged values and their diagonals, the device copies of the plan
-   int rc = [&] () -> int {
-      if (flags & ~NKP_REFACTOR_REBUILD) return fail (NKP_EINVAL, "%s: unknown flags 0x%x", who, flags);
-      if (multilevel && !Q) return fail (NKP_EINVAL, "%s: the solver kept no plan of its hierarchy's matrix", who);
-      HIPCHK (hipSetDevice (s->device));
-      HIPCHK (hipStreamSynchronize (st));
-      const bool staged = W.aval != nullptr;
-      if (rf_stage (W, nnz, (int) s->ml.lev.size ()) != 0) return fail (NKP_ENOMEM, "%s: no device memory for the staged values", who);
-      if (!staged) s->device_bytes += ((size_t) nnz + 2) * sizeof (double) + (4 + 2 * 64) * sizeof (int);
-      if (nnz) HIPCHK (hipMemcpyAsync (W.aval, h_val ? (const void *) h_val : d_val, (size_t) nnz * sizeof (double), h_val ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, st));
-      if (s->opt.precond != NKP_PRECOND_NONE) {
-         // own rows only: the halo columns (>= m_loc) are never a diagonal; an overlap row's diagonal is checked by its owner
-         rf_launch_diag_check (s->A, W.aval, W.dcnt, st);
-         int c[3] = { 0, 0, 0 };
-         HIPCHK (hipMemcpyAsync (c, W.dcnt, sizeof c, hipMemcpyDeviceToHost, st));
-         HIPCHK (hipStreamSynchronize (st));
-         if (c[1]) return fail (NKP_ESINGULAR, "%s: row %lld (global) has no (or a zero) diagonal entry (%d such rows on rank %d); no rank's solver is changed", who,
-                                (long long) (s->dist.fst + c[2] - 1), c[1], s->dist.ops.rank);
-      }
-      if (multilevel && !Q->uploaded) {
-         const int urc = rf_dist_upload (*Q, st);
-         if (urc) return fail (urc == -2 ? NKP_ENOMEM : NKP_EDEVICE, "%s: the value maps of the hierarchy's matrix could not be uploaded", who);
-         s->device_bytes += Q->bytes;
-      }
-      return NKP_OK;
-   } ();
-   if ((rc = dist_agree (s, rc, who, "arguments and own diagonals"))) return rc;
-
-   // ---- (b) the overlap values from their owners, then the hierarchy's new values beside the current ones
-   bool rebuild = multilevel && (flags & NKP_REFACTOR_REBUILD);
-   MlHierarchy H2;
-   bool built = false;
-   int64_t halo_values = 0;
-   if (multilevel) {
-      if (Q->exchange) {
-         rf_dist_launch_pack (*Q, W.aval, st);
-         if (s->dist.ops.alltoallv (s->dist.ops.ctx, Q->sendbuf, Q->ship_counts.data (), Q->recvbuf, Q->recv_counts.data (), (void *) st))
-            rc = fail (NKP_ECOMM, "%s: the exchange of the overlap values failed", who);
-         halo_values = Q->n_recv;
-      }
-      if (!rc) rc = [&] () -> int {
-         rf_dist_launch_assemble (*Q, W.aval, st);
-         // nkp_create's inter-tracer filter (developer switch) applies to the diagonal block only; its hierarchy is always rebuilt
-         const bool filtered = s->tune.ml_drop_intertracer && s->tracer_cnt > 1 && !s->dist.ras;
-         if (filtered) rebuild = true;
-         if (!rebuild && !W.maps) {
-            const int mrc = rf_build_maps (W, s->ml, Q->src, st);
-            if (mrc == 0) s->device_bytes += W.bytes;
-            else {
-               rf_free_maps (W);
-               if (mrc < 0) return fail (mrc == -2 ? NKP_ENOMEM : NKP_EDEVICE, "%s: the value maps of the hierarchy could not be built (%s)", who, mrc == -2 ? "out of device memory" : "HIP failure");
-               rebuild = true;
-            }
-         }
-         if (!rebuild) {
-            rf_values (W, s->ml, Q->src, Q->sval, st);
-            int drift = 0;
-            HIPCHK (hipMemcpyAsync (&drift, W.dcnt, sizeof drift, hipMemcpyDeviceToHost, st));
-            HIPCHK (hipStreamSynchronize (st));
-            HIPCHK (hipGetLastError ());
-            if (drift) {
-               msg (s, 1, "%s: %d couplings of this rank's hierarchy appear or vanish with the new values: rebuilding it\n", who, drift);
-               rebuild = true;
-            }
-         }
-         if (!rebuild) {
-            char err[256] = "";
-            const int irc = rf_prepare_inverse (W, s->ml, st, err, sizeof err);
-            if (irc) return fail (irc == -4 ? NKP_ESINGULAR : irc == -2 ? NKP_ENOMEM : NKP_EDEVICE, "%s", err);
-            return NKP_OK;
-         }
-         // rebuild: the hierarchy's matrix read back from the device, as nkp_create_dist passed it to ml_setup
-         std::vector<int32_t> rp ((size_t) Q->n_src + 1), ci ((size_t) Q->nnz_src);
-         std::vector<double> v ((size_t) Q->nnz_src);
-         HIPCHK (hipStreamSynchronize (st));
-         HIPCHK (hipMemcpy (rp.data (), Q->src.rowptr, rp.size () * sizeof (int32_t), hipMemcpyDeviceToHost));
-         if (Q->nnz_src) {
-            HIPCHK (hipMemcpy (ci.data (), Q->src.colind, ci.size () * sizeof (int32_t), hipMemcpyDeviceToHost));
-            HIPCHK (hipMemcpy (v.data (), Q->sval, v.size () * sizeof (double), hipMemcpyDeviceToHost));
-         }
-         char err[256] = "";
-         const int mrc = rebuild_hierarchy (s, H2, Q->n_src, rp.data (), ci.data (), v.data (), filtered, nullptr, err, sizeof err);
-         if (mrc != 0) return fail (mrc, "%s: %s (no rank's solver is changed)", who, err);
-         built = true;
-         return NKP_OK;
-      } ();
-   }
-   if ((rc = dist_agree (s, rc, who, "new values of the hierarchy"))) {
-      if (built) {
-         (void) hipStreamSynchronize (st);
-         ml_free (H2);
-      }
-      rf_drop_inverse (W);
-      return rc;
-   }
-
-   // ---- commit point: from here on the solver's own buffers are written
-   char err[256] = "";
-   int lrc = 0;
-   if (nnz && hipMemcpyAsync (s->A.val, W.aval, (size_t) nnz * sizeof (double), hipMemcpyDeviceToDevice, st) != hipSuccess) {
-      lrc = -3;
-      snprintf (err, sizeof err, "copy of the new values failed");
-      if (built) ml_free (H2);
-   } else
-      lrc = refactor_commit (s, multilevel && rebuild, H2, err, sizeof err);
-   rc = lrc ? fail (lrc == -4 ? NKP_ESINGULAR : lrc == -2 ? NKP_ENOMEM : NKP_EDEVICE, "%s: %s", who, err) : NKP_OK;
-   // ---- (c) all ranks committed, or none of them solves
-   if ((rc = dist_agree (s, rc, who, "commit"))) {
-      s->shared->broken = true;
-      s->shared->why = lrc ? std::string (who) + " failed after writing part of the new values (" + err + "); this solver cannot solve until nkp_refactor_dist succeeds on every rank"
-                           : g_last_error + "; the new values are written on this rank, so it cannot solve until nkp_refactor_dist succeeds on every rank";
-      return rc;
-   }
-   s->shared->broken = false;
-   s->refactor_count++;
-   s->refactor_rebuilt = rebuild ? 1 : 0;
-   s->refactor_halo_values = halo_values;
-   struct timespec ts1;
-   clock_gettime (CLOCK_MONOTONIC, &ts1);
-   s->refactor_seconds = (double) (ts1.tv_sec - ts0.tv_sec) + 1e-9 * (double) (ts1.tv_nsec - ts0.tv_nsec);
-   msg (s, 1, "%s: %s, %lld overlap values received, %.3f s\n", who, rebuild ? "hierarchy rebuilt" : "coarse cells kept", (long long) halo_values, s->refactor_seconds);
-   return NKP_OK;
-}
-
-extern "C" int nkp_refactor_dist (nkp_solver *s, const double *val_loc, int flags) { return refactor_dist_impl (s, val_loc, nullptr, flags, "nkp_refactor_dist"); }
-
-extern "C" int nkp_refactor_dist_device (nkp_solver *s, const void *d_val_loc, int flags) { return refactor_dist_impl (s, nullptr, d_val_loc, flags, "nkp_refactor_dist_device"); }
 
 // ---------------------------------------------------------------- exposed pieces (parity / roofline)
 extern "C" int nkp_spmv_device (nkp_solver *s, const void *d_x, void *d_y)

@@ -1,0 +1,142 @@
+// The solver object and the few helpers that solver.hip (C ABI, create, clone, the Krylov drivers) and refactor_api.hip (new
+// matrix values on an existing solver) share.  Private to the library: nothing here is part of the C ABI.
+#pragma once
+#include "../../include/nkp.h"
+#include "nkp_dev.h"
+#include "multilevel.h"
+#include "refactor.h"
+#include "dist_plan.h"
+
+#include <atomic>
+#include <memory>
+#include <string>
+#include <vector>
+
+#define HIPCHK(call)                                                                             \
+   do {                                                                                          \
+      hipError_t e_ = (call);                                                                    \
+      if (e_ != hipSuccess) return fail (NKP_EDEVICE, "%s failed: %s (%s:%d)", #call, hipGetErrorString (e_), __FILE__, __LINE__); \
+   } while (0)
+
+struct nkp_solver {
+   nkp_options opt;
+   nkp_tuning tune;             // resolved once in nkp_create; the matrix, column-block and hierarchy objects point at it
+   int device = 0;
+   bool stagnated = false;      // last solve stopped by the attainable-accuracy guard
+   bool borrowed = false;       // nkp_clone: matrix, factors and hierarchy belong to the solver this one was cloned from
+   hipStream_t stream = nullptr;
+   bool own_stream = false;
+   CsrDev A;
+   ColBlocksDev B;
+   MlHierarchy ml;
+   // row-distributed flavour: halo exchange before every SpMV, allreduce after every local reduction
+   struct {
+      bool on = false;
+      nkp_comm_ops ops;
+      int64_t n_global = 0, fst = 0, n_halo = 0, nsend = 0;
+      std::vector<int> send_counts, recv_counts;
+      int *send_idx = nullptr;        // local rows other ranks need, grouped by destination rank
+      double *sendbuf = nullptr;      // packed values for them
+      double *xe = nullptr;           // [n + n_halo] extended SpMV input: own rows then halo rows
+      // overlap of the halo exchange with the SpMV of the interior rows (rows without off-rank columns): the row blocks
+      // are built per segment [head boundary rows | interior | tail boundary rows]; seg_rb[q] = first row block of segment q
+      int seg_rb[4] = { 0, 0, 0, 0 };
+      bool overlap = false;
+      hipStream_t comm_stream = nullptr;
+      hipEvent_t ev_packed = nullptr, ev_halo = nullptr;
+      // restricted additive Schwarz: the hierarchy of this rank also covers the neighbouring ranks' water columns its rows
+      // couple to laterally (one ring); a cycle runs on [own rows | those halo rows] and only the own part is kept
+      bool ras = false;
+      int64_t n_ext = 0, n_sel = 0;
+      int *sel_idx = nullptr;         // position in the halo of every overlap row (one ring)
+      double *rext = nullptr, *zext = nullptr;
+      // two or more rings (tuning dist_ras_rings): rows of ring 2 and beyond are not in the SpMV halo, so the overlap residual has
+      // an exchange of its own -- own rows sent (by destination), their packed values, per-rank counts; the rows arrive at
+      // rext + n in the hierarchy's order.  bras_send / bras_recv: the same K wide (batch_prepare)
+      int ras_rings = 0;              // the depth the ranks agreed on, 0 without overlap
+      bool ras_sep = false;
+      int64_t ras_nsend = 0;
+      int *ras_send_idx = nullptr;
+      double *ras_sendbuf = nullptr, *bras_send = nullptr, *bras_recv = nullptr;
+      std::vector<int> ras_send_counts, ras_recv_counts, ras_send_counts_k, ras_recv_counts_k;
+      // K right-hand sides in lockstep: the K-interleaved operator input [own rows | halo rows] x K, the
+      // K-wide send rows, the plan's counts times K, and the group's Gram-Schmidt messages
+      // gmsg = dots [K x (m + 2)] | second pass [K x (m + 2)] | norms [K] | 1 / norms [K], ghpin its pinned host mirror
+      double *bxe = nullptr, *bsend = nullptr, *gmsg = nullptr, *ghpin = nullptr;
+      int bK = 0;                     // width these buffers exist for
+      int agreed_K = 0;               // widest interleave every rank is known to have buffers for
+      std::vector<int> send_counts_k, recv_counts_k;
+   } dist;
+   int64_t n = 0, ld = 0;
+   int m = 0;
+   // work vectors
+   bool vf32 = false;              // Krylov basis stored as float (stride ld floats inside the V allocation)
+   double *vcur = nullptr;         // f64 copy of the newest basis vector (input of the next preconditioner call)
+   double *V = nullptr, *Z = nullptr, *w = nullptr, *r = nullptr, *x = nullptr, *b = nullptr, *t1 = nullptr, *t2 = nullptr;
+   double *p1 = nullptr, *p2 = nullptr;   // scratch of the multi-step preconditioner (NKP_PRECOND_STEPS > 1)
+   int precond_steps = 1;        // configured cycles per application
+   int steps_now = 1;            // cycles per application of the running solve (the run-time guard may lower it for one solve)
+   bool equil = false;           // row-weighted FGMRES
+   double *rscale = nullptr, *rinv = nullptr;   // R and R^-1 (device), R_i = 1 / max_j |a_ij|
+   double *eqtmp = nullptr;      // R^-1 v_j, the input of the preconditioner in the row-weighted iteration
+   bool comm_failed = false;     // a collective callback returned non-zero: every verdict after that is NKP_ECOMM
+   double *partial = nullptr;       // reduction scratch
+   double *dscal = nullptr;         // device scalars: h[m+2] | h2[m+2] | misc[16] | ycoef[m+1]
+   double *hpin = nullptr;          // pinned host mirror
+   int *dint = nullptr;             // device ints
+   // K right-hand sides at once (nkp_solve_batch_device): K - 1 more sets of work vectors (clones sharing this solver's stream)
+   // and three K-interleaved vectors around the batched operator / cycle application
+   std::vector<nkp_solver *> batch_members;
+   double *bvin = nullptr, *bz = nullptr, *bw = nullptr;
+   int batch_K = 0;
+   int64_t batch_steps = 0;         // batched operator applications (lockstep Krylov steps) over the solver's life
+   int batch_width = 0;             // K of the last batched group
+   size_t device_bytes = 0;
+   double create_seconds = 0.0;     // wall time of nkp_create
+   // nkp_refactor: state shared by a solver and its clones (live clones, a refactor that failed after its commit point),
+   // the owner's work space, and the host arrays a rebuild of the hierarchy needs again
+   struct Shared {
+      std::atomic<int> clones { 0 };
+      std::atomic<int64_t> alltoallv_calls { 0 }, allreduce_calls { 0 };      // device collectives of solves (a batch's members count here too)
+      bool broken = false;
+      std::string why;
+   };
+   std::shared_ptr<Shared> shared = std::make_shared<Shared> ();
+   RefactorWork *rf = nullptr;
+   std::vector<int> h_blk, h_col_i, h_col_j, h_col_t;
+   int tracer_cnt = 1;
+   int64_t refactor_count = 0;
+   int refactor_rebuilt = 0;
+   double refactor_seconds = 0.0;
+   // nkp_refactor_dist: where the values of the hierarchy's source come from (kept by nkp_create_dist, multilevel only)
+   DistRefactorPlan *dplan = nullptr;
+   int64_t refactor_halo_values = 0;
+   double *h_dev () { return dscal; }
+   double *h2_dev () { return dscal + (m + 2); }
+   double *misc_dev () { return dscal + 2 * (m + 2); }     // [0]=nrm2 [1]=inv [2]=dot out ...
+   double *y_dev () { return dscal + 2 * (m + 2) + 16; }
+};
+
+template <class T>
+static int dev_alloc (nkp_solver *s, T **p, size_t count)
+{
+   void *q = nullptr;
+   size_t bytes = (count ? count : 1) * sizeof (T);
+   hipError_t e = hipMalloc (&q, bytes);
+   if (e != hipSuccess) return fail (NKP_ENOMEM, "hipMalloc of %zu bytes failed: %s", bytes, hipGetErrorString (e));
+   *p = (T *) q;
+   s->device_bytes += bytes;
+   return NKP_OK;
+}
+
+
+// ---- defined in solver.hip -------------------------------------------------------------------------------------------------
+NKP_PRIVATE void solver_free (nkp_solver *s);
+NKP_PRIVATE void msg (const nkp_solver *s, int lvl, const char *fmt, ...);
+// Row-distributed solvers: every rank learns whether any rank's step failed, and all leave together.  A rank whose own step
+// failed returns its code and message, every other rank NKP_ECOMM naming it; a failed allgather is NKP_ECOMM everywhere.
+NKP_PRIVATE int dist_agree (nkp_solver *s, int local_rc, const char *who, const char *where);
+// developer switch ml_drop_intertracer: the matrix without the couplings between its tracer_cnt tracers, i.e. exactly what a
+// tracer-per-rank partition builds its rank-local hierarchies from
+NKP_PRIVATE void drop_intertracer (int64_t n, int tracer_cnt, const int32_t *rowptr, const int32_t *colind, const double *val,
+                                   std::vector<int32_t> &f_rowptr, std::vector<int32_t> &f_colind, std::vector<double> &f_val);
