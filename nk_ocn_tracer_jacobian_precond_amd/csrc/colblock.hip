@@ -1000,15 +1000,21 @@ void colblock_apply_ldsres_kernel (const int *__restrict__ grp_nb, const int *__
 // the other with a single chunk of look-ahead, and a chunk is 32-48 load instructions of 128 bytes -- the 63 loads a
 // wave may have in flight are 8 KB.  A latency-bound chain per wave with nothing to overlap it.
 // Here the factors of 4 consecutive steps of a column sit side by side ([diag][k / 4][lane][4], f32), so one instruction
-// moves 512 bytes and a chunk of 16 steps is 2-3 instructions per diagonal; and the schedule is static: every forward chunk
-// is requested before the right-hand side is even staged, the backward chunks follow as the registers of consumed forward
-// chunks come free (a compile-time budget of LDSP_BUDGET registers decides what is in flight when), so by the time the
+// moves 512 bytes and a chunk of 16 steps is 2-3 instructions per diagonal; and the schedule is static: the forward chunks
+// are requested around the right-hand side's burst (the batch kernels: all before it), the backward chunks follow as the
+// registers of consumed forward chunks come free (a compile-time budget of LDSP_BUDGET registers decides what is in flight when), so by the time the
 // forward sweep is done the backward factors have landed.  Same operations in the same order => same bits.
 #define LDSP_BUDGET 200
 
-template <int NCH, int FR, int BR>
+// RR: the registers of one double per column and 64 rows (the right-hand side on its way into LDS, the accumulate target on
+// its way out), which the single-vector kernel holds in one burst beside the factor chunks; the factor schedule itself does
+// not depend on it.  f_staged = forward chunks (of the f_upfront) requested before the right-hand side is written to LDS, the
+// others follow the writes that free its registers; z_after = backward steps done when the accumulate target is requested:
+// the first point at which it fits beside the backward chunks still in flight (+ 16: the request is made with nothing else
+// of the wave waiting, and its addresses want registers too -- without them the P = 1 kernels spill).
+template <int NCH, int FR, int BR, int RR = 0>
 struct LdspSchedule {
-   int f_upfront = 0, b_upfront = 0;
+   int f_upfront = 0, b_upfront = 0, f_staged = 0, z_after = NCH;
    int f_after[NCH] = {}, b_after_f[NCH] = {}, b_after_b[NCH] = {};     // chunks issued in total once fwd step c / bwd step j is done
    constexpr LdspSchedule ()
    {
@@ -1017,6 +1023,7 @@ struct LdspSchedule {
       while (bi < NCH && (fi - fc) * FR + (bi - bc) * BR + BR <= LDSP_BUDGET) bi++;
       f_upfront = fi;
       b_upfront = bi;
+      while (f_staged < f_upfront && (RR + (f_staged + 1) * FR <= LDSP_BUDGET || f_staged == 0)) f_staged++;
       for (int c = 0; c < NCH; c++) {
          fc++;
          while (fi < NCH && ((fi - fc) * FR + (bi - bc) * BR + FR <= LDSP_BUDGET || fi == fc)) fi++;
@@ -1024,10 +1031,12 @@ struct LdspSchedule {
          f_after[c] = fi;
          b_after_f[c] = bi;
       }
+      if (bi * BR + RR + 16 <= LDSP_BUDGET) z_after = 0;
       for (int j = 0; j < NCH; j++) {
          bc++;
-         while (bi < NCH && ((bi - bc) * BR + BR <= LDSP_BUDGET || bi == bc)) bi++;
+         while (bi < NCH && ((bi - bc) * BR + BR + (z_after <= j ? RR : 0) <= LDSP_BUDGET || bi == bc)) bi++;
          b_after_b[j] = bi;
+         if (z_after == NCH && (bi - bc) * BR + RR + 16 <= LDSP_BUDGET) z_after = j + 1;
       }
    }
 };
@@ -1111,11 +1120,100 @@ __device__ __forceinline__ void ldsp_step_bwd (PackChunk<P> &c, double *col, int
    }
 }
 
+// one double per column of the group and 64 rows, as it travels between global memory and the LDS image: the right-hand side on
+// the way in, the accumulate target on the way out (NCH = 5: rows 64-79 too, in v[32 ...])
+template <int NCH>
+struct PackRows { double v[NCH > 4 ? 64 : 32]; };
+
+// Requests the rows of all 32 columns from x in ONE burst: no load of it is waited for before the last is issued.  A lane behind
+// the end of its column reads the column's first row instead (an absent column of the last group: row R0), an address that is
+// always valid, so these loads are unconditional like the factor loads -- a `lane < len` around each compiles to a branch and a
+// full wait per column.  Whoever consumes the value discards it for those lanes.
+template <int NCH>
+__device__ __forceinline__ void ldsp_request_rows (PackRows<NCH> &t, const double *x, int R0, int s, int len, int lane)
+{
+#pragma unroll
+   for (int c = 0; c < 32; c++) {
+      const int sc = __builtin_amdgcn_readlane (s, c), lc = __builtin_amdgcn_readlane (len, c);
+      t.v[c] = x[(int64_t) R0 + sc + (lane < lc ? lane : 0)];
+      if (NCH > 4) t.v[32 + c] = x[(int64_t) R0 + sc + (lane + NKP_WAVE < lc ? lane + NKP_WAVE : 0)];
+   }
+}
+
+// No access to memory moves across this point of the program, neither in the compiler's passes nor in its instruction scheduler;
+// no instruction and no wait of its own.  p: the array whose loads are to stay where they are -- the compiler knows that an
+// empty statement cannot reach a __restrict__ array it has not been handed, and moves such loads across it all the same.
+__device__ __forceinline__ void ldsp_fence (const void *p)
+{
+   asm volatile ("" : : "v" (p) : "memory");
+   __builtin_amdgcn_sched_barrier (0);
+}
+
+// The solution leaves the LDS image: z = (ACC ? target : 0.0) + solution, the operands in this order.  All LDS reads first, then
+// the stores, one behind the other without a wait: with the read inside the `lane < len` of its store every column would pay an
+// LDS round trip of its own.  t is read only where ACC says that it has been requested.
+template <int NCH, bool ACC>
+__device__ __forceinline__ void ldsp_write_back (const PackRows<NCH> &t, const double *lds, double *z, int R0, int s, int len, int lane)
+{
+   constexpr int STRIDE = NCH * 16 + 1;
+   // h = 1: rows 64-79 of the columns (NCH = 5), the lane clamped into the column's slot
+#pragma unroll
+   for (int h = 0; h < (NCH > 4 ? 2 : 1); h++) {
+      const int row = h ? (lane + NKP_WAVE < STRIDE - 1 ? lane + NKP_WAVE : STRIDE - 2) : lane;
+      double x[32];
+#pragma unroll
+      for (int c = 0; c < 32; c++) x[c] = (ACC ? t.v[32 * h + c] : 0.0) + lds[c * STRIDE + row];
+      ldsp_fence (z);
+#pragma unroll
+      for (int c = 0; c < 32; c++) {
+         const int sc = __builtin_amdgcn_readlane (s, c), lc = __builtin_amdgcn_readlane (len, c);
+         if (lane + h * NKP_WAVE < lc) z[(int64_t) R0 + sc + lane + h * NKP_WAVE] = x[c];
+      }
+   }
+}
+
+// The end of a wave's work: (ACC) the accumulate target of all 32 columns is requested by all 64 lanes, into registers that
+// backward chunks have left; the backward steps from S.z_after on run over that round trip; the solution goes back out.
+template <int P, int NCH, bool ACC, class SCHED>
+__device__ __forceinline__ void ldsp_finish (PackChunk<P> (&Bq)[NCH], double (&w)[P], const float4 *f4, int mlq, int nch, double *lds, double *z, int R0,
+                                             int s, int len, int lane)
+{
+   constexpr SCHED S;
+   constexpr int gw = 32, CH = 16, STRIDE = NCH * CH + 1;
+   double *col = lds + (lane & (gw - 1)) * STRIDE;
+   PackRows<NCH> Z;
+   if (ACC) {
+      ldsp_fence (z);
+      ldsp_request_rows<NCH> (Z, z, R0, s, len, lane);
+      ldsp_fence (z);
+   }
+#pragma unroll
+   for (int j = 0; j < NCH; j++) {
+      if (j >= S.z_after) {
+         if (lane < gw && j < nch) ldsp_step_bwd<P> (Bq[j], col, (nch - 1 - j) * CH, w);
+#pragma unroll
+         for (int t = 0; t < NCH; t++)
+            if (t >= (j ? S.b_after_b[j - 1] : S.b_after_f[NCH - 1]) && t < S.b_after_b[j])
+               ldsp_load_bwd<P> (Bq[t], f4, mlq, (nch - 1 - t > 0 ? nch - 1 - t : 0) * CH, gw);
+      }
+   }
+   __syncthreads ();
+   ldsp_write_back<NCH, ACC> (Z, lds, z, R0, s, len, lane);
+}
+
 // LDS image: column l of the group at [l * LDSP_STRIDE, ...), LDSP_STRIDE = NCH * 16 + 1 doubles.  Odd stride: the 32 lanes of
 // a substitution step hit 32 different bank pairs; fixed stride: every LDS address of the sweeps is "lane base + constant",
 // no address arithmetic and no predicate (SQ counters of the first version: 21 VALU instructions per step, most of them
 // the padded index of the linear image, and 41 % of a wave's life spent issuing).  Rows beyond a column's length are zero
 // (their factors are zero too), so the sweeps need no length test.
+// A wave's dependent trips to memory, in the order of its requests (= the order of arrival):
+//   1. the group's descriptors (scalar), 2. col_slot, with the first forward chunk requested beside it, 3. the right-hand side of
+//   all 32 columns in one burst, the other forward chunks behind it -- the burst is waited for with counts that leave those in
+//   flight, and the chunks that did not fit beside its registers follow the LDS writes, 4. the accumulate target of all 32
+//   columns in one burst from inside the backward sweep (S.z_after: as soon as it fits beside the backward chunks still in
+//   flight), so that it has landed when the sweep ends, 5. the stores, none of them waited for.
+// Before, the staging was four batches of 8 columns, each drained with vmcnt(0) (the first behind the whole factor burst), and
+// the write-back four batches of target loads, each drained, with a drain behind every store as well.
 template <int P, int NCH>
 __global__ __launch_bounds__ (NKP_WAVE, 2)
 void colblock_apply_ldspack_kernel (const int *__restrict__ grp_nb, const int *__restrict__ grp_maxlen, const long long *__restrict__ grp_base, int g_first,
@@ -1124,7 +1222,7 @@ void colblock_apply_ldspack_kernel (const int *__restrict__ grp_nb, const int *_
 {
    extern __shared__ double lds[];
    constexpr int gw = 32, CH = 16, STRIDE = NCH * CH + 1;
-   constexpr LdspSchedule<NCH, P * CH, (P + 1) * CH> S;
+   constexpr LdspSchedule<NCH, P * CH, (P + 1) * CH, 2 * (NCH > 4 ? 64 : 32)> S;
    const int g = blockIdx.x + g_first;
    const int lane = threadIdx.x;
    const int ml = grp_maxlen[g];                            // a multiple of 16, at most NCH * 16
@@ -1140,76 +1238,66 @@ void colblock_apply_ldspack_kernel (const int *__restrict__ grp_nb, const int *_
 #define LDSP_FWD_K0(t) (((t) < nch ? (t) : nch - 1) * CH)
 #define LDSP_BWD_K0(t) ((nch - 1 - (t) > 0 ? nch - 1 - (t) : 0) * CH)
    PackChunk<P> F[NCH], Bq[NCH];
+   PackRows<NCH> T;
+   // the fences keep the requests in this order: left alone, the compiler moves the factor loads to their first use (behind
+   // the staging, inside the sweep) or ahead of the burst, and in-order return then delivers the burst behind all of them
+   ldsp_load_fwd<P> (F[0], f4, mlq, LDSP_FWD_K0 (0), gw);
+   ldsp_fence (f4);
+   ldsp_request_rows<NCH> (T, rhs, R0, s, len, lane);
+   ldsp_fence (f4);
 #pragma unroll
-   for (int t = 0; t < NCH; t++)
-      if (t < S.f_upfront) ldsp_load_fwd<P> (F[t], f4, mlq, LDSP_FWD_K0 (t), gw);
+   for (int t = 1; t < NCH; t++)
+      if (t < S.f_staged) ldsp_load_fwd<P> (F[t], f4, mlq, LDSP_FWD_K0 (t), gw);
+   ldsp_fence (f4);
+   // staging: the 64 lanes hold up to 64 consecutive rows of each column (coalesced) and write them to its slot, zeros behind its end
+#pragma unroll
+   for (int c = 0; c < gw; c++) {
+      const int lc = __builtin_amdgcn_readlane (len, c);
+      lds[c * STRIDE + lane] = (lane < lc) ? T.v[c] : 0.0;
+      if (NCH > 4 && lane < STRIDE - 1 - NKP_WAVE) lds[c * STRIDE + lane + NKP_WAVE] = (lane + NKP_WAVE < lc) ? T.v[32 + c] : 0.0;
+   }
+   ldsp_fence (f4);
+#pragma unroll
+   for (int t = 1; t < NCH; t++)
+      if (t >= S.f_staged && t < S.f_upfront) ldsp_load_fwd<P> (F[t], f4, mlq, LDSP_FWD_K0 (t), gw);
 #pragma unroll
    for (int t = 0; t < NCH; t++)
       if (t < S.b_upfront) ldsp_load_bwd<P> (Bq[t], f4, mlq, LDSP_BWD_K0 (t), gw);
-   // staging, one column per step: 64 lanes read up to 64 consecutive rows of column c (coalesced) and write them to its slot,
-   // zeros behind its end; 8 columns' loads are in flight together
-#pragma unroll
-   for (int c0 = 0; c0 < gw; c0 += 8) {
-      double t[8], t2[8];
-#pragma unroll
-      for (int u = 0; u < 8; u++) {
-         const int sc = __builtin_amdgcn_readlane (s, c0 + u), lc = __builtin_amdgcn_readlane (len, c0 + u);
-         t[u] = (lane < lc) ? rhs[(int64_t) R0 + sc + lane] : 0.0;
-         if (NCH > 4) t2[u] = (lane + NKP_WAVE < lc) ? rhs[(int64_t) R0 + sc + lane + NKP_WAVE] : 0.0;
-      }
-#pragma unroll
-      for (int u = 0; u < 8; u++) {
-         lds[(c0 + u) * STRIDE + lane] = t[u];
-         if (NCH > 4 && lane < STRIDE - 1 - NKP_WAVE) lds[(c0 + u) * STRIDE + lane + NKP_WAVE] = t2[u];
-      }
-   }
    __syncthreads ();
-   if (lane < gw) {
-      double *col = lds + lane * STRIDE;
-      double w[P];
+   // The sweeps: lanes 0-31 run the steps, all 64 request the chunks (the upper half its mirror's, from the same addresses) --
+   // a chunk requested under `lane < gw` and consumed under the next is a value the compiler keeps a second, undefined copy of
+   // for the other lanes, and the register allocation that follows spills
+   double *col = lds + cl * STRIDE;
+   double w[P];
 #pragma unroll
-      for (int q = 0; q < P; q++) w[q] = 0.0;
+   for (int q = 0; q < P; q++) w[q] = 0.0;
 #pragma unroll
-      for (int c = 0; c < NCH; c++) {
-         if (c < nch) ldsp_step_fwd<P> (F[c], col, c * CH, w);
+   for (int c = 0; c < NCH; c++) {
+      if (lane < gw && c < nch) ldsp_step_fwd<P> (F[c], col, c * CH, w);
 #pragma unroll
-         for (int t = 0; t < NCH; t++)
-            if (t >= (c ? S.f_after[c - 1] : S.f_upfront) && t < S.f_after[c]) ldsp_load_fwd<P> (F[t], f4, mlq, LDSP_FWD_K0 (t), gw);
+      for (int t = 0; t < NCH; t++)
+         if (t >= (c ? S.f_after[c - 1] : S.f_upfront) && t < S.f_after[c]) ldsp_load_fwd<P> (F[t], f4, mlq, LDSP_FWD_K0 (t), gw);
 #pragma unroll
-         for (int t = 0; t < NCH; t++)
-            if (t >= (c ? S.b_after_f[c - 1] : S.b_upfront) && t < S.b_after_f[c]) ldsp_load_bwd<P> (Bq[t], f4, mlq, LDSP_BWD_K0 (t), gw);
-      }
+      for (int t = 0; t < NCH; t++)
+         if (t >= (c ? S.b_after_f[c - 1] : S.b_upfront) && t < S.b_after_f[c]) ldsp_load_bwd<P> (Bq[t], f4, mlq, LDSP_BWD_K0 (t), gw);
+   }
 #pragma unroll
-      for (int q = 0; q < P; q++) w[q] = 0.0;
+   for (int q = 0; q < P; q++) w[q] = 0.0;
 #pragma unroll
-      for (int j = 0; j < NCH; j++) {
-         if (j < nch) ldsp_step_bwd<P> (Bq[j], col, (nch - 1 - j) * CH, w);
+   for (int j = 0; j < NCH; j++) {
+      if (j < S.z_after) {
+         if (lane < gw && j < nch) ldsp_step_bwd<P> (Bq[j], col, (nch - 1 - j) * CH, w);
 #pragma unroll
          for (int t = 0; t < NCH; t++)
             if (t >= (j ? S.b_after_b[j - 1] : S.b_after_f[NCH - 1]) && t < S.b_after_b[j]) ldsp_load_bwd<P> (Bq[t], f4, mlq, LDSP_BWD_K0 (t), gw);
       }
    }
+   // two copies of the rest, not one with `if (accumulate)` around the request: where the two paths meet again the compiler
+   // waits for a chunk with the count that is right when nothing was requested behind it, and that drains the target
+   if (accumulate) ldsp_finish<P, NCH, true, decltype (S)> (Bq, w, f4, mlq, nch, lds, z, R0, s, len, lane);
+   else ldsp_finish<P, NCH, false, decltype (S)> (Bq, w, f4, mlq, nch, lds, z, R0, s, len, lane);
 #undef LDSP_FWD_K0
 #undef LDSP_BWD_K0
-   __syncthreads ();
-   // back out, one column per step; the accumulate target of 8 columns is requested together
-#pragma unroll
-   for (int c0 = 0; c0 < gw; c0 += 8) {
-      double t[8], t2[8];
-      int sc[8], lc[8];
-#pragma unroll
-      for (int u = 0; u < 8; u++) {
-         sc[u] = __builtin_amdgcn_readlane (s, c0 + u);
-         lc[u] = __builtin_amdgcn_readlane (len, c0 + u);
-         t[u] = (accumulate && lane < lc[u]) ? z[(int64_t) R0 + sc[u] + lane] : 0.0;
-         if (NCH > 4) t2[u] = (accumulate && lane + NKP_WAVE < lc[u]) ? z[(int64_t) R0 + sc[u] + lane + NKP_WAVE] : 0.0;
-      }
-#pragma unroll
-      for (int u = 0; u < 8; u++) {
-         if (lane < lc[u]) z[(int64_t) R0 + sc[u] + lane] = t[u] + lds[(c0 + u) * STRIDE + lane];
-         if (NCH > 4 && lane + NKP_WAVE < lc[u]) z[(int64_t) R0 + sc[u] + lane + NKP_WAVE] = t2[u] + lds[(c0 + u) * STRIDE + lane + NKP_WAVE];
-      }
-   }
 }
 
 // The same kernel on TWO right-hand sides of a K-interleaved batch (batch.hip): lanes 0-31 run the columns on system k0, lanes
