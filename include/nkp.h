@@ -114,7 +114,8 @@ typedef struct nkp_tuning {
    int spmv_wgs;             /* NKP_SPMV_WGS (256): workgroups per CU at most */
    /* ---- Krylov / distributed flavour / setup */
    int rhs_batch;            /* NKP_RHS_BATCH (1): several right-hand sides of one call share the sweeps over the matrix and the
-                                hierarchy (nkp_solve_batch_device; same bits per column); 0 = one at a time, 1 or 4 = groups of up to
+                                hierarchy (nkp_solve_batch_device; same bits per column, also under equil and precond_steps >= 2;
+                                its comment lists what still goes one at a time); 0 = one at a time, 1 or 4 = groups of up to
                                 four, 2 = pairs, 8 = groups of up to eight (measured at 1 degree: no better per solve than four -- with
                                 four vectors interleaved the vectors, not the matrix, are most of every kernel's bytes) */
    int precond_steps;        /* NKP_PRECOND_STEPS (0 = leave nkp_options.precond_steps) */
@@ -226,15 +227,26 @@ int nkp_solve (nkp_solver *s, double *b_in_x_out, int nrhs, int64_t ldb,
  * (d_X may alias d_B).  Systems are solved in groups of up to four; each keeps its own FGMRES recurrence and stopping test, the
  * operator and preconditioner applications of a Krylov step are one pass for the group.  Column c of the result has the bits
  * nkp_solve_device gives for that right-hand side alone, iters[c] / relres[c] / berr[c] likewise; the return code is the worst of
- * the columns'.  Needs K - 1 more sets of work vectors (kept for later calls).  Falls back to one at a time where the batched path
- * does not apply (BiCGStab, row equilibration, chained cycles, an f32 basis) or with nkp_tuning.rhs_batch = 0.
+ * the columns'.  Needs K - 1 more sets of work vectors (kept for later calls).
+ * Row equilibration (nkp_options.equil) and chained preconditioner cycles (precond_steps >= 2) are batched with the rest, alone or
+ * together: the two row scalings sit in the kernels that read the basis vectors and write the operator products, and every stage
+ * of a chained step -- cycle, residual v - A z, cycle, z += correction, operator -- is one pass for the group.  The run-time
+ * guard that drops a solve to one cycle per step is per system, as in a solve done alone; a group may hold both kinds.
+ * Falls back to one at a time, with the same answers, where the batched path does not apply:
+ *    - a solver made by nkp_clone,
+ *    - BiCGStab,
+ *    - an f32 Krylov basis (basis_f32),
+ *    - row equilibration on a row-distributed solver,
+ * or with nkp_tuning.rhs_batch = 0.  With verbose >= 1 such a call prints one "(rank)"-prefixed line that names the reason.
  * nkp_solve with nrhs >= 2 takes the same path.
  *
  * On a solver made by nkp_create_dist with more than one rank the call is collective for nrhs >= 2 exactly as nkp_solve is
  * for one system: every rank calls with the same nrhs and passes its own rows of every vector (ldb >= m_loc).  A group of K
  * systems then runs in lockstep on every rank with the collectives of ONE system per Krylov step: one alltoallv of K-wide
  * rows for the overlap rows of the preconditioner, one for the halo of the SpMV, and one allreduce per Gram-Schmidt pass
- * (plus one for the norms) whose message holds the K systems' dot products.  The interleave width is agreed between the ranks
+ * (plus one for the norms) whose message holds the K systems' dot products.  With precond_steps = s chained cycles a step has s
+ * preconditioner applications and s operator applications (s - 1 residuals and the product), each with its one exchange: 2 s
+ * alltoallv per step with an overlap, s without (dist_ras = 0); the allreduces do not change.  The interleave width is agreed between the ranks
  * (allgather_i64_host): all of them take the narrowest one any rank has device memory for; a rank with another failure returns
  * its code, the others NKP_ECOMM naming it (nkp_solve agrees likewise on having staged its host vectors on the device).  Bits: column c has the bits of nkp_solve_device on right-hand side c alone
  * (solution, iters, relres, berr) whenever the transport's allreduce gives an element the same bits whatever the length of the
@@ -276,7 +288,9 @@ int nkp_time_kernel (nkp_solver *s, int which, int arg, int reps, double *avg_ms
  * counters, cumulative over the solver's life, per rank: "dist_alltoallv_calls", "dist_allreduce_calls" (every call of the two
  * device collectives made by solves, single or batched; 0 on a single-GPU solver), "batch_steps" (batched operator
  * applications = lockstep Krylov steps of a group of right-hand sides), "batch_width" (K of the last batched group, 0 if
- * none ran).  An unknown key returns -1. */
+ * none ran); "batch_member_bytes" (device bytes of the K - 1 further sets of work vectors a batched call has made and keeps:
+ * Krylov bases, level vectors, with chained cycles the residual between two cycles; "device_bytes" counts the solver's own set
+ * and the K-interleaved buffers, the sum of the two is what the solver holds).  An unknown key returns -1. */
 int64_t nkp_get_int (nkp_solver *s, const char *key);
 
 /* New matrix values on the sparsity pattern the solver was created with (the analogue of SuperLU's

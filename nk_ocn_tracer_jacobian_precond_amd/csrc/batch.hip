@@ -32,6 +32,19 @@ void interleave_kernel (BatchPtrs src, double *__restrict__ X, int64_t n)
    }
 }
 
+// row-weighted iteration: X[i * K + k] = src_k[i] * scale[i], the product rounded like launch_vmul rounds it
+template <int K>
+__global__ __launch_bounds__ (BT_THREADS)
+void interleave_scaled_kernel (BatchPtrs src, const double *__restrict__ scale, double *__restrict__ X, int64_t n)
+{
+   const int64_t stride = (int64_t) gridDim.x * BT_THREADS;
+   for (int64_t i = (int64_t) blockIdx.x * BT_THREADS + threadIdx.x; i < n; i += stride) {
+      const double sc = scale[i];
+#pragma unroll
+      for (int k = 0; k < K; k++) X[i * K + k] = src.p[k] ? __dmul_rn (src.p[k][i], sc) : 0.0;
+   }
+}
+
 template <int K>
 __global__ __launch_bounds__ (BT_THREADS)
 void deinterleave_kernel (const double *__restrict__ X, BatchOutPtrs dst, int64_t n)
@@ -44,10 +57,16 @@ void deinterleave_kernel (const double *__restrict__ X, BatchOutPtrs dst, int64_
    }
 }
 
-void launch_interleave (int K, const double *const *src, double *X, int64_t n, hipStream_t st)
+void launch_interleave (int K, const double *const *src, double *X, int64_t n, hipStream_t st, const double *scale)
 {
    BatchPtrs P;
    for (int k = 0; k < NKP_BATCH_MAX; k++) P.p[k] = k < K ? src[k] : nullptr;
+   if (scale) {
+      if (K == 2) hipLaunchKernelGGL (interleave_scaled_kernel<2>, dim3 (bt_grid (n)), dim3 (BT_THREADS), 0, st, P, scale, X, n);
+      else if (K == 4) hipLaunchKernelGGL (interleave_scaled_kernel<4>, dim3 (bt_grid (n)), dim3 (BT_THREADS), 0, st, P, scale, X, n);
+      else hipLaunchKernelGGL (interleave_scaled_kernel<8>, dim3 (bt_grid (n)), dim3 (BT_THREADS), 0, st, P, scale, X, n);
+      return;
+   }
    if (K == 2) hipLaunchKernelGGL (interleave_kernel<2>, dim3 (bt_grid (n)), dim3 (BT_THREADS), 0, st, P, X, n);
    else if (K == 4) hipLaunchKernelGGL (interleave_kernel<4>, dim3 (bt_grid (n)), dim3 (BT_THREADS), 0, st, P, X, n);
    else hipLaunchKernelGGL (interleave_kernel<8>, dim3 (bt_grid (n)), dim3 (BT_THREADS), 0, st, P, X, n);
@@ -66,11 +85,12 @@ void launch_deinterleave (int K, const double *X, double *const *dst, int64_t n,
 // csr_spmv_stream_kernel (spmv.hip) with the (value, column) stream of a row block read ONCE into registers and K / 2 passes
 // over it: a pass gathers the 16-byte pair (x[c][2g], x[c][2g + 1]), parks both products in LDS and sums every row's segment
 // in stored order.  MODE 0: y = A x   1: y = b - A x
-template <int MODE, class VT, int K>
+// SCALED (MODE 0, row-weighted iteration): every finished sum times scale[row], one rounded multiplication like launch_vmul's
+template <int MODE, class VT, int K, bool SCALED = false>
 __global__ __launch_bounds__ (BT_THREADS)
 void csr_spmv_batch_kernel (const int *__restrict__ rowblk_all, int rb0, int nrowblk, int per_xcd, const int *__restrict__ rowptr,
                             const int *__restrict__ colind, const VT *__restrict__ val, const double *__restrict__ x,
-                            double *__restrict__ y, const double *__restrict__ b)
+                            double *__restrict__ y, const double *__restrict__ b, const double *__restrict__ scale = nullptr)
 {
    __shared__ double2 prod[NKP_SPMV_LDS_NNZ];
    __shared__ double2 wsum[BT_WAVES];
@@ -102,6 +122,7 @@ void csr_spmv_batch_kernel (const int *__restrict__ rowblk_all, int rb0, int nro
             double2 s = make_double2 (0.0, 0.0);
             for (int w = 0; w < BT_WAVES; w++) { s.x += wsum[w].x; s.y += wsum[w].y; }
             if (MODE == 1) { const double2 bv = *reinterpret_cast<const double2 *> (b + (int64_t) r0 * K + 2 * g); s.x = bv.x - s.x; s.y = bv.y - s.y; }
+            if (SCALED) { const double sc = scale[r0]; s.x = __dmul_rn (s.x, sc); s.y = __dmul_rn (s.y, sc); }
             *reinterpret_cast<double2 *> (y + (int64_t) r0 * K + 2 * g) = s;
          }
          __syncthreads ();
@@ -141,6 +162,7 @@ void csr_spmv_batch_kernel (const int *__restrict__ rowblk_all, int rb0, int nro
 #pragma unroll 4
          for (int k = s0; k < s1; k++) { acc.x += prod[k].x; acc.y += prod[k].y; }
          if (MODE == 1) { const double2 bv = *reinterpret_cast<const double2 *> (b + (int64_t) r * K + 2 * g); acc.x = bv.x - acc.x; acc.y = bv.y - acc.y; }
+         if (SCALED) { const double sc = scale[r]; acc.x = __dmul_rn (acc.x, sc); acc.y = __dmul_rn (acc.y, sc); }
          *reinterpret_cast<double2 *> (y + (int64_t) r * K + 2 * g) = acc;
       }
       if (g + 1 < K / 2) __syncthreads ();
@@ -152,12 +174,16 @@ void csr_spmv_batch_kernel (const int *__restrict__ rowblk_all, int rb0, int nro
 // segment, gathers the K-wide rows of x itself (GU entries in flight) and accumulates its K sums in registers -- same
 // products, same stored order, one pass for any K.
 // SPLIT: the K results of a row go to K separate vectors (split.p[k][r]; NULL = dropped) instead of the interleaved y -- the
-// operator product at the end of an Arnoldi step writes every system's w directly.
-template <int MODE, class VT, int K, bool SPLIT = false>
+// operator product at the end of an Arnoldi step writes every system's w directly.  With MODE 1 the right-hand side is split
+// too (bsplit.p[k][r]; NULL = zero): the residual between two chained cycles, p1_k = v_k - A z_k, from and to per-system vectors.
+// SCALED (row-weighted iteration): MODE 0 multiplies every finished sum by scale[row]; MODE 1 + SPLIT multiplies the right-hand
+// side it reads by scale[row].  Either is ONE rounded multiplication of a finished value, which is what launch_vmul does.
+template <int MODE, class VT, int K, bool SPLIT = false, bool SCALED = false>
 __global__ __launch_bounds__ (BT_THREADS)
 void csr_spmv_batch_rows_kernel (const int *__restrict__ rowblk_all, int rb0, int nrowblk, int per_xcd, const int *__restrict__ rowptr,
                                  const int *__restrict__ colind, const VT *__restrict__ val, const double *__restrict__ x,
-                                 double *__restrict__ y, const double *__restrict__ b, BatchOutPtrs split = BatchOutPtrs ())
+                                 double *__restrict__ y, const double *__restrict__ b, BatchOutPtrs split = BatchOutPtrs (),
+                                 BatchPtrs bsplit = BatchPtrs (), const double *__restrict__ scale = nullptr)
 {
    __shared__ VT sv[NKP_SPMV_LDS_NNZ];
    __shared__ int sc[NKP_SPMV_LDS_NNZ];
@@ -186,7 +212,15 @@ void csr_spmv_batch_rows_kernel (const int *__restrict__ rowblk_all, int rb0, in
          if (tid == 0) {
             double2 s = make_double2 (0.0, 0.0);
             for (int w = 0; w < BT_WAVES; w++) { s.x += wsum[w].x; s.y += wsum[w].y; }
-            if (MODE == 1) { const double2 bv = *reinterpret_cast<const double2 *> (b + (int64_t) r0 * K + 2 * g); s.x = bv.x - s.x; s.y = bv.y - s.y; }
+            if (MODE == 1) {
+               double2 bv;
+               if (SPLIT) {
+                  bv.x = bsplit.p[2 * g] ? bsplit.p[2 * g][r0] : 0.0;
+                  bv.y = bsplit.p[2 * g + 1] ? bsplit.p[2 * g + 1][r0] : 0.0;
+                  if (SCALED) { const double sc = scale[r0]; bv.x = __dmul_rn (bv.x, sc); bv.y = __dmul_rn (bv.y, sc); }
+               } else bv = *reinterpret_cast<const double2 *> (b + (int64_t) r0 * K + 2 * g);
+               s.x = bv.x - s.x; s.y = bv.y - s.y;
+            } else if (SCALED) { const double sc = scale[r0]; s.x = __dmul_rn (s.x, sc); s.y = __dmul_rn (s.y, sc); }
             if (SPLIT) { if (split.p[2 * g]) split.p[2 * g][r0] = s.x; if (split.p[2 * g + 1]) split.p[2 * g + 1][r0] = s.y; }
             else *reinterpret_cast<double2 *> (y + (int64_t) r0 * K + 2 * g) = s;
          }
@@ -214,7 +248,16 @@ void csr_spmv_batch_rows_kernel (const int *__restrict__ rowblk_all, int rb0, in
    }
    double2 bv[K / 2];
 #pragma unroll
-   for (int g = 0; g < K / 2; g++) bv[g] = (MODE == 1 && r < r1) ? *reinterpret_cast<const double2 *> (b + (int64_t) r * K + 2 * g) : make_double2 (0.0, 0.0);
+   for (int g = 0; g < K / 2; g++) {
+      bv[g] = make_double2 (0.0, 0.0);
+      if (MODE == 1 && r < r1) {
+         if (SPLIT) {
+            if (bsplit.p[2 * g]) bv[g].x = bsplit.p[2 * g][r];
+            if (bsplit.p[2 * g + 1]) bv[g].y = bsplit.p[2 * g + 1][r];
+            if (SCALED) { const double sc = scale[r]; bv[g].x = __dmul_rn (bv[g].x, sc); bv[g].y = __dmul_rn (bv[g].y, sc); }
+         } else bv[g] = *reinterpret_cast<const double2 *> (b + (int64_t) r * K + 2 * g);
+      }
+   }
    __syncthreads ();
    if (r >= r1) return;
    double2 acc[K / 2];
@@ -241,17 +284,34 @@ void csr_spmv_batch_rows_kernel (const int *__restrict__ rowblk_all, int rb0, in
 #pragma unroll
    for (int g = 0; g < K / 2; g++) {
       if (MODE == 1) { acc[g].x = bv[g].x - acc[g].x; acc[g].y = bv[g].y - acc[g].y; }
+      else if (SCALED) { const double sc = scale[r]; acc[g].x = __dmul_rn (acc[g].x, sc); acc[g].y = __dmul_rn (acc[g].y, sc); }
       if (SPLIT) { if (split.p[2 * g]) split.p[2 * g][r] = acc[g].x; if (split.p[2 * g + 1]) split.p[2 * g + 1][r] = acc[g].y; }
       else *reinterpret_cast<double2 *> (y + (int64_t) r * K + 2 * g) = acc[g];
    }
 }
 
-void launch_csr_spmv_batch (int K, const CsrDev &A, int rb0, int rb1, const double *x, double *y, const double *b, int mode, hipStream_t st)
+void launch_csr_spmv_batch (int K, const CsrDev &A, int rb0, int rb1, const double *x, double *y, const double *b, int mode, hipStream_t st, const double *scale)
 {
    const int cnt = rb1 - rb0;
    if (cnt <= 0) return;
    const int per_xcd = (cnt + 7) / 8;
    const nkp_tuning &T = A.tune ? *A.tune : nkp_builtin_tuning ();
+   if (scale && mode == 0) {
+      // y = R (A x): the same kernels with the scaling in their epilogue
+#define BS_ARGS A.rowblk, rb0, cnt, per_xcd, A.rowptr, A.colind
+#define BS_ROWS(VT_, K_, VAL_) hipLaunchKernelGGL ((csr_spmv_batch_rows_kernel<0, VT_, K_, false, true>), dim3 (per_xcd * 8), dim3 (BT_THREADS), 0, st, \
+                                                   BS_ARGS, VAL_, x, y, b, BatchOutPtrs (), BatchPtrs (), scale)
+#define BS_PROD(VT_, K_, VAL_) hipLaunchKernelGGL ((csr_spmv_batch_kernel<0, VT_, K_, true>), dim3 (per_xcd * 8), dim3 (BT_THREADS), 0, st, BS_ARGS, VAL_, x, y, b, scale)
+#define BSCALED_K(VT_, VAL_) do { if (K == 8) BS_ROWS (VT_, 8, VAL_);                                                                          \
+                                  else if (T.batch_spmv_rows) { if (K == 2) BS_ROWS (VT_, 2, VAL_); else BS_ROWS (VT_, 4, VAL_); } \
+                                  else { if (K == 2) BS_PROD (VT_, 2, VAL_); else BS_PROD (VT_, 4, VAL_); } } while (0)
+      if (A.valf) BSCALED_K (float, A.valf); else BSCALED_K (double, A.val);
+#undef BSCALED_K
+#undef BS_PROD
+#undef BS_ROWS
+#undef BS_ARGS
+      return;
+   }
 #define BSPMV(KERNEL_, MODE_, VT_, K_, VAL_) hipLaunchKernelGGL ((KERNEL_<MODE_, VT_, K_>), dim3 (per_xcd * 8), dim3 (BT_THREADS), 0, st, \
                                                                  A.rowblk, rb0, cnt, per_xcd, A.rowptr, A.colind, VAL_, x, y, b)
 #define BSPMV_K(MODE_, VT_, VAL_) do { if (K == 8) BSPMV (csr_spmv_batch_rows_kernel, MODE_, VT_, 8, VAL_);      /* (the products-in-LDS variant stops at four) */ \
@@ -265,13 +325,21 @@ void launch_csr_spmv_batch (int K, const CsrDev &A, int rb0, int rb1, const doub
 
 // y_k = A x_k for the K interleaved columns of x, every result in its own vector (dst[k] NULL: not wanted); row blocks
 // [rb0, rb1) only (the row-distributed flavour multiplies its interior rows while the halo of x travels)
-void launch_csr_spmv_batch_split_range (int K, const CsrDev &A, int rb0, int rb1, const double *x, double *const *dst, hipStream_t st)
+void launch_csr_spmv_batch_split_range (int K, const CsrDev &A, int rb0, int rb1, const double *x, double *const *dst, hipStream_t st, const double *scale)
 {
    const int cnt = rb1 - rb0;
    if (cnt <= 0) return;
    const int per_xcd = (cnt + 7) / 8;
    BatchOutPtrs P;
    for (int k = 0; k < NKP_BATCH_MAX; k++) P.p[k] = k < K ? dst[k] : nullptr;
+   if (scale) {
+#define BSPLIT_S(VT_, K_, VAL_) hipLaunchKernelGGL ((csr_spmv_batch_rows_kernel<0, VT_, K_, true, true>), dim3 (per_xcd * 8), dim3 (BT_THREADS), 0, st, \
+                                                    A.rowblk, rb0, cnt, per_xcd, A.rowptr, A.colind, VAL_, x, (double *) nullptr, (const double *) nullptr, P, BatchPtrs (), scale)
+      if (A.valf) { if (K == 2) BSPLIT_S (float, 2, A.valf); else if (K == 4) BSPLIT_S (float, 4, A.valf); else BSPLIT_S (float, 8, A.valf); }
+      else { if (K == 2) BSPLIT_S (double, 2, A.val); else if (K == 4) BSPLIT_S (double, 4, A.val); else BSPLIT_S (double, 8, A.val); }
+#undef BSPLIT_S
+      return;
+   }
 #define BSPLIT(VT_, K_, VAL_) hipLaunchKernelGGL ((csr_spmv_batch_rows_kernel<0, VT_, K_, true>), dim3 (per_xcd * 8), dim3 (BT_THREADS), 0, st, \
                                                   A.rowblk, rb0, cnt, per_xcd, A.rowptr, A.colind, VAL_, x, (double *) nullptr, (const double *) nullptr, P)
    if (A.valf) { if (K == 2) BSPLIT (float, 2, A.valf); else if (K == 4) BSPLIT (float, 4, A.valf); else BSPLIT (float, 8, A.valf); }
@@ -279,9 +347,28 @@ void launch_csr_spmv_batch_split_range (int K, const CsrDev &A, int rb0, int rb1
 #undef BSPLIT
 }
 
-void launch_csr_spmv_batch_split (int K, const CsrDev &A, const double *x, double *const *dst, hipStream_t st)
+void launch_csr_spmv_batch_split (int K, const CsrDev &A, const double *x, double *const *dst, hipStream_t st, const double *scale)
 {
-   launch_csr_spmv_batch_split_range (K, A, 0, A.nrowblk, x, dst, st);
+   launch_csr_spmv_batch_split_range (K, A, 0, A.nrowblk, x, dst, st, scale);
+}
+
+// dst_k = b_k - A x_k (b_k, times bscale when given, and dst_k per system; NULL: system takes no part), row blocks [rb0, rb1)
+void launch_csr_residual_batch_split_range (int K, const CsrDev &A, int rb0, int rb1, const double *x, const double *const *b, const double *bscale,
+                                            double *const *dst, hipStream_t st)
+{
+   const int cnt = rb1 - rb0;
+   if (cnt <= 0) return;
+   const int per_xcd = (cnt + 7) / 8;
+   BatchOutPtrs P;
+   BatchPtrs Q;
+   for (int k = 0; k < NKP_BATCH_MAX; k++) { P.p[k] = k < K ? dst[k] : nullptr; Q.p[k] = k < K ? b[k] : nullptr; }
+#define BRESID(VT_, K_, S_, VAL_) hipLaunchKernelGGL ((csr_spmv_batch_rows_kernel<1, VT_, K_, true, S_>), dim3 (per_xcd * 8), dim3 (BT_THREADS), 0, st, \
+                                                      A.rowblk, rb0, cnt, per_xcd, A.rowptr, A.colind, VAL_, x, (double *) nullptr, (const double *) nullptr, P, Q, bscale)
+#define BRESID_K(VT_, S_, VAL_) do { if (K == 2) BRESID (VT_, 2, S_, VAL_); else if (K == 4) BRESID (VT_, 4, S_, VAL_); else BRESID (VT_, 8, S_, VAL_); } while (0)
+   if (A.valf) { if (bscale) BRESID_K (float, true, A.valf); else BRESID_K (float, false, A.valf); }
+   else { if (bscale) BRESID_K (double, true, A.val); else BRESID_K (double, false, A.val); }
+#undef BRESID_K
+#undef BRESID
 }
 
 // ---------------------------------------------------------------- grid transfer / permutation / coarsest solve, K columns
@@ -332,6 +419,38 @@ void gather_interleave_kernel (const int *__restrict__ perm, BatchPtrs src, doub
       const int64_t pi = perm[i];
 #pragma unroll
       for (int k = 0; k < K; k++) out[i * K + k] = src.p[k] ? src.p[k][pi] : 0.0;
+   }
+}
+
+// the entry in the row-weighted iteration: out[i * K + k] = src_k[perm[i]] * scale[perm[i]] (launch_vmul's product, then the gather)
+template <int K>
+__global__ __launch_bounds__ (BT_THREADS)
+void gather_interleave_scaled_kernel (const int *__restrict__ perm, BatchPtrs src, const double *__restrict__ scale, double *__restrict__ out, int64_t n)
+{
+   const int64_t stride = (int64_t) gridDim.x * BT_THREADS;
+   for (int64_t i = (int64_t) blockIdx.x * BT_THREADS + threadIdx.x; i < n; i += stride) {
+      const int64_t pi = perm[i];
+      const double sc = scale[pi];
+#pragma unroll
+      for (int k = 0; k < K; k++) out[i * K + k] = src.p[k] ? __dmul_rn (src.p[k][pi], sc) : 0.0;
+   }
+}
+
+// z_k += p_k between two chained cycles, on the interleaved z that feeds the operator and on the systems' own vectors at once:
+// z[i * K + k] = dst_k[i] = z[i * K + k] + p[i * K + k] for the systems that take part (dst_k != NULL); the others keep their z
+template <int K>
+__global__ __launch_bounds__ (BT_THREADS)
+void add_split_kernel (const double *__restrict__ p, double *__restrict__ z, BatchOutPtrs dst, int64_t n)
+{
+   const int64_t stride = (int64_t) gridDim.x * BT_THREADS;
+   for (int64_t i = (int64_t) blockIdx.x * BT_THREADS + threadIdx.x; i < n; i += stride) {
+#pragma unroll
+      for (int k = 0; k < K; k++)
+         if (dst.p[k]) {
+            const double v = z[i * K + k] + p[i * K + k];
+            z[i * K + k] = v;
+            dst.p[k][i] = v;
+         }
    }
 }
 
@@ -473,11 +592,19 @@ void launch_scatter_batch (int K, const int *perm, const double *in, double *out
 {
    if (n > 0) BT_K (gather_batch_kernel, dim3 (bt_grid (n * K)), perm, in, out, n, 1);
 }
-void launch_gather_interleave (int K, const int *perm, const double *const *src, double *out, int64_t n, hipStream_t st)
+void launch_gather_interleave (int K, const int *perm, const double *const *src, double *out, int64_t n, hipStream_t st, const double *scale)
 {
    BatchPtrs P;
    for (int k = 0; k < NKP_BATCH_MAX; k++) P.p[k] = k < K ? src[k] : nullptr;
-   if (n > 0) BT_K (gather_interleave_kernel, dim3 (bt_grid (n)), perm, P, out, n);
+   if (n <= 0) return;
+   if (scale) BT_K (gather_interleave_scaled_kernel, dim3 (bt_grid (n)), perm, P, scale, out, n);
+   else BT_K (gather_interleave_kernel, dim3 (bt_grid (n)), perm, P, out, n);
+}
+void launch_add_split (int K, const double *p, double *z, double *const *dst, int64_t n, hipStream_t st)
+{
+   BatchOutPtrs P;
+   for (int k = 0; k < NKP_BATCH_MAX; k++) P.p[k] = k < K ? dst[k] : nullptr;
+   if (n > 0) BT_K (add_split_kernel, dim3 (bt_grid (n)), p, z, P, n);
 }
 void launch_scatter_split (int K, const int *perm, const double *in, double *z, double *const *dst, int64_t n, hipStream_t st)
 {

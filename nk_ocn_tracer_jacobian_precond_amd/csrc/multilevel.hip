@@ -1729,11 +1729,13 @@ void ml_apply_batch (MlHierarchy &H, int K, const double *r, double *z, hipStrea
 }
 
 // the same from / to per-system vectors: src[k] = residual of system k (NULL: zeros), z = the K corrections interleaved,
-// dst[k] (may be NULL) = a plain copy of column k
-void ml_apply_batch_split (MlHierarchy &H, int K, const double *const *src, double *z, double *const *dst, hipStream_t st)
+// dst[k] (may be NULL) = a plain copy of column k; src_scale (row-weighted iteration): the residuals are src[k] times it, row by row.
+// A Krylov step with chained cycles comes here several times: a cycle starts from its right-hand side V.bb alone (x is
+// filled, the buffer selectors reset), so nothing of the previous application is read.
+void ml_apply_batch_split (MlHierarchy &H, int K, const double *const *src, double *z, double *const *dst, hipStream_t st, const double *src_scale)
 {
    MlLevel &V = H.lev[0];
-   launch_gather_interleave (K, H.perm0, src, V.bb, V.n, st);
+   launch_gather_interleave (K, H.perm0, src, V.bb, V.n, st, src_scale);
    ml_cycle_batch (H, K, 0, st);
    launch_scatter_split (K, H.perm0, V.bxnow (), z, dst, V.n, st);
 }

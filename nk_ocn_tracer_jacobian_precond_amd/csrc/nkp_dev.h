@@ -190,18 +190,26 @@ int dense_inverse_blocked_device (int n, const int *h_rowptr, const int *h_col, 
                                   size_t *bytes, hipStream_t st);
 
 // ---------------------------------------------------------------- K interleaved right-hand sides (batch.hip; X[i * K + k], K = 2 or 4)
-void launch_interleave (int K, const double *const *src /* K pointers, NULL = zeros */, double *X, int64_t n, hipStream_t st);
+// scale (may be NULL), here and below: the row scaling of the row-weighted iteration folded into the kernel, one rounded
+// multiplication per value (what launch_vmul does): on the way in src_k[i] * scale[i], on the way out (A x)_i * scale[i]
+void launch_interleave (int K, const double *const *src /* K pointers, NULL = zeros */, double *X, int64_t n, hipStream_t st, const double *scale = nullptr);
 void launch_deinterleave (int K, const double *X, double *const *dst /* K pointers, NULL = skip */, int64_t n, hipStream_t st);
 // row blocks [rb0, rb1) of A: y = A x (mode 0) or y = b - A x (mode 1) on K columns
-void launch_csr_spmv_batch (int K, const CsrDev &A, int rb0, int rb1, const double *x, double *y, const double *b, int mode, hipStream_t st);
+void launch_csr_spmv_batch (int K, const CsrDev &A, int rb0, int rb1, const double *x, double *y, const double *b, int mode, hipStream_t st,
+                            const double *scale = nullptr /* mode 0 only */);
 void launch_restrict_sum_batch (int K, const int *rptr, const int *ridx, const double *fine, double *coarse, int64_t nc, hipStream_t st);
 void launch_prolong_add_batch (int K, const int *cmap, const double *coarse, double *fine, int64_t nf, double omega, hipStream_t st);
 void launch_gather_batch (int K, const int *perm, const double *in, double *out, int64_t n, hipStream_t st);
 void launch_scatter_batch (int K, const int *perm, const double *in, double *out, int64_t n, hipStream_t st);
-void launch_gather_interleave (int K, const int *perm, const double *const *src, double *out, int64_t n, hipStream_t st);
+void launch_gather_interleave (int K, const int *perm, const double *const *src, double *out, int64_t n, hipStream_t st, const double *scale = nullptr);
 void launch_scatter_split (int K, const int *perm, const double *in, double *z, double *const *dst, int64_t n, hipStream_t st);
-void launch_csr_spmv_batch_split (int K, const CsrDev &A, const double *x, double *const *dst, hipStream_t st);
-void launch_csr_spmv_batch_split_range (int K, const CsrDev &A, int rb0, int rb1, const double *x, double *const *dst, hipStream_t st);
+void launch_csr_spmv_batch_split (int K, const CsrDev &A, const double *x, double *const *dst, hipStream_t st, const double *scale = nullptr);
+void launch_csr_spmv_batch_split_range (int K, const CsrDev &A, int rb0, int rb1, const double *x, double *const *dst, hipStream_t st, const double *scale = nullptr);
+// chained cycles: dst_k = b_k - A x_k from and to per-system vectors (b_k times bscale when given; dst_k NULL: system k takes no
+// part), and z_k += p_k on the interleaved z and the systems' own vectors at once (dst_k NULL: column k of z stays as it is)
+void launch_csr_residual_batch_split_range (int K, const CsrDev &A, int rb0, int rb1, const double *x, const double *const *b, const double *bscale,
+                                            double *const *dst, hipStream_t st);
+void launch_add_split (int K, const double *p, double *z, double *const *dst, int64_t n, hipStream_t st);
 // row-distributed flavour: K-wide message rows out[i * K + k] = src_k[idx[i]]; the entry / exit of a batched cycle on the
 // extended rows [own | overlap] (overlap rows read from the K-interleaved halo at sel[.], only own rows written back)
 void launch_pack_rows_split (int K, const int *idx, const double *const *src, double *out, int64_t nrows, hipStream_t st);

@@ -327,13 +327,15 @@ void drop_intertracer (int64_t n, int tracer_cnt, const int32_t *rowptr, const i
 }
 
 // The work vectors of one system in flight (a solver's own, a clone's, a batch member's), for s->m, s->ld, s->precond_steps and
-// s->equil as they stand.  A failure leaves what was allocated to solver_free.
-static int alloc_work_vectors (nkp_solver *s)
+// s->equil as they stand.  A batch member never applies the preconditioner on its own: of the scratch of the chained cycles it
+// needs p1 only (the residual between two cycles; the second cycle's correction stays interleaved), and no eqtmp (the
+// batched kernels scale on the way in).  A failure leaves what was allocated to solver_free.
+static int alloc_work_vectors (nkp_solver *s, bool member = false)
 {
    const size_t ld = (size_t) s->ld, m = (size_t) s->m, nscal = 3 * (m + 2) + 16 + 8;
    const struct { double **p; size_t count; } vec[] = {
       { &s->V, ld * (m + 1) }, { &s->vcur, ld }, { &s->Z, ld * m }, { &s->w, ld }, { &s->r, ld }, { &s->x, ld }, { &s->b, ld }, { &s->t1, ld }, { &s->t2, ld },
-      { &s->p1, s->precond_steps > 1 ? ld : 0 }, { &s->p2, s->precond_steps > 1 ? ld : 0 }, { &s->eqtmp, s->equil ? ld : 0 },
+      { &s->p1, s->precond_steps > 1 ? ld : 0 }, { &s->p2, s->precond_steps > 1 && !member ? ld : 0 }, { &s->eqtmp, s->equil && !member ? ld : 0 },
       { &s->partial, ((m + 1 + NKP_DOT_CHUNK) / NKP_DOT_CHUNK + 1) * NKP_RED_BLOCKS * (NKP_DOT_CHUNK + 1) }, { &s->dscal, nscal } };
    int rc = NKP_OK;
    for (const auto &v : vec)
@@ -728,6 +730,11 @@ extern "C" int64_t nkp_get_int (nkp_solver *s, const char *key)
    if (!strcmp (key, "dist_allreduce_calls")) return s->shared->allreduce_calls.load ();
    if (!strcmp (key, "batch_steps")) return s->batch_steps;
    if (!strcmp (key, "batch_width")) return s->batch_width;
+   if (!strcmp (key, "batch_member_bytes")) {      // the further sets of work vectors a batched group keeps (not part of device_bytes)
+      size_t sum = 0;
+      for (const nkp_solver *c : s->batch_members) sum += c->device_bytes;
+      return (int64_t) sum;
+   }
    return -1;
 }
 
@@ -1143,7 +1150,7 @@ static int clone_impl (nkp_solver *src, nkp_solver **out, bool member)
    int rc = NKP_OK;
    TRYHIP (hipStreamCreateWithFlags (&s->stream, hipStreamNonBlocking));
    s->own_stream = true;
-   TRY (alloc_work_vectors (s));
+   TRY (alloc_work_vectors (s, member));
    for (MlLevel &L : s->ml.lev) {
       TRY (dev_alloc (s, &L.x, (size_t) L.n));
       TRY (dev_alloc (s, &L.x2, (size_t) L.n));
@@ -1168,14 +1175,26 @@ extern "C" int nkp_clone (nkp_solver *src, nkp_solver **out) { return clone_impl
 // systems: every system keeps its own FGMRES recurrence (own basis, own Hessenberg matrix, own restart decisions -- the state
 // machine above), but the K applications of the cycle and of A in a step are one application to K interleaved vectors
 // (batch.hip).  Per system the operations and their order are those of a solve done alone, so are the bits.
+//
+// Row equilibration and chained preconditioner cycles are fixed linear changes around those same applications and are batched
+// with them (batch_step_apply).  What is NOT covered takes its right-hand sides one at a time, with the same answers:
+//   a clone                    its work vectors are one system's, and it may run next to its siblings
+//   BiCGStab                   the lockstep driver is FGMRES's state machine
+//   an f32 Krylov basis        the batched kernels read an f64 basis
+//   row equilibration on a row-distributed solver      the K-wide overlap exchange carries unscaled rows
 static const char *batch_unsupported (const nkp_solver *s)
 {
    if (s->borrowed) return "a clone";
    if (s->opt.krylov != NKP_KRYLOV_FGMRES) return "BiCGStab";
-   if (s->equil) return "row equilibration";
-   if (s->precond_steps > 1) return "chained preconditioner cycles";
+   if (s->equil && s->dist.on) return "row equilibration on a row-distributed solver";
    if (s->vf32) return "an f32 Krylov basis";
    return nullptr;
+}
+
+// the one line a batched call that falls back leaves at -D1
+static void note_fallback (const nkp_solver *s, const char *who, const char *why, int nrhs)
+{
+   msg (s, 1, "%s: %d right-hand sides one at a time: the batched path does not cover %s\n", who, nrhs, why);
 }
 
 // Everything K systems in flight need.  Transactional per buffer set: after a failed allocation the set is gone and its
@@ -1243,63 +1262,128 @@ static int batch_prepare (nkp_solver *s, int K)
    return NKP_OK;
 }
 
-// The group's operator application in the row-distributed flavour: ONE exchange of K-wide rows for the overlap rows of the
-// preconditioner and ONE for the halo of the SpMV, whatever K is.  The interleaved operator input is bxe = [own | halo] x K, so
-// the column indices of A (halo slots at >= n) address it unchanged; its halo part also receives the overlap residuals
-// (it is rewritten by the second exchange before A reads it).
-static void batch_apply_dist (nkp_solver *s, int K, const double *const *src, double *const *dz, double *const *dw)
+// The group's Krylov step applies the cycle and the operator to K vectors, one or several times each (chained cycles), so the
+// two are separate routines: "precondition K vectors" and "apply A to K vectors".  Both work from / to per-system vectors
+// (src[k] / dst[k], NULL = system k takes no part: zeros in, nothing out) around ONE K-interleaved vector.
+//
+// Row-distributed flavour: each routine has the exchange of ONE system, K rows wide -- the overlap rows of the preconditioner,
+// the halo of the SpMV.  The interleaved operator input is bxe = [own | halo] x K, so the column indices of A (halo slots
+// at >= n) address it unchanged; its halo part also receives the overlap residuals (it is rewritten by the operator's
+// exchange before A reads it).
+
+// zi[i * K + k] = dz[k][i] = (M src_k)[i] on the own rows (dz NULL: the interleaved result alone); src_scale: src_k times it
+static void batch_precond (nkp_solver *s, int K, const double *const *src, const double *src_scale, double *zi, double *const *dz)
 {
    const int64_t n = s->n;
    hipStream_t st = s->stream;
    auto &D = s->dist;
-   D.send_counts_k.resize (D.send_counts.size ());
-   D.recv_counts_k.resize (D.recv_counts.size ());
-   for (size_t p = 0; p < D.send_counts.size (); p++) D.send_counts_k[p] = D.send_counts[p] * K;
-   for (size_t p = 0; p < D.recv_counts.size (); p++) D.recv_counts_k[p] = D.recv_counts[p] * K;
-   double *halo = D.bxe + n * K;
-   if (s->opt.precond == NKP_PRECOND_MULTILEVEL && D.ras_sep) {
-      // several rings: the overlap rows alone, K wide, into a block of their own in the hierarchy's order
-      D.ras_send_counts_k.resize (D.ras_send_counts.size ());
-      D.ras_recv_counts_k.resize (D.ras_recv_counts.size ());
-      for (size_t p = 0; p < D.ras_send_counts.size (); p++) D.ras_send_counts_k[p] = D.ras_send_counts[p] * K;
-      for (size_t p = 0; p < D.ras_recv_counts.size (); p++) D.ras_recv_counts_k[p] = D.ras_recv_counts[p] * K;
-      if (D.ras_nsend) launch_pack_rows_split (K, D.ras_send_idx, src, D.bras_send, D.ras_nsend, st);
-      alltoallv_dev (s, D.bras_send, D.ras_send_counts_k.data (), D.bras_recv, D.ras_recv_counts_k.data (), st);
-      ml_apply_batch_split_ext (s->ml, K, src, D.bras_recv, nullptr, n, D.bxe, dz, st);
-   } else if (s->opt.precond == NKP_PRECOND_MULTILEVEL && D.ras) {
-      if (D.nsend) launch_pack_rows_split (K, D.send_idx, src, D.bsend, D.nsend, st);
-      alltoallv_dev (s, D.bsend, D.send_counts_k.data (), halo, D.recv_counts_k.data (), st);
-      ml_apply_batch_split_ext (s->ml, K, src, halo, D.sel_idx, n, D.bxe, dz, st);
-   } else if (s->opt.precond == NKP_PRECOND_MULTILEVEL) ml_apply_batch_split (s->ml, K, src, D.bxe, dz, st);
-   else {
-      launch_interleave (K, src, s->bvin, n, st);
-      if (s->opt.precond == NKP_PRECOND_COLUMN_JACOBI) {
-         if (launch_colblock_apply_lanes_batch (K, s->B, 0, s->B.ngrp, s->bvin, D.bxe, 0, st) != 0)
-            launch_colblock_apply_wave_batch (K, s->B, 0, s->B.nblk, s->bvin, D.bxe, 0, s->B.fac_tf ? 1 : 0, st);
-      } else
-         launch_copy (s->bvin, D.bxe, n * K, st);
-      launch_deinterleave (K, D.bxe, dz, n, st);
-   }
-   // w_k = A z_k: the rows other ranks need, K wide, then as spmv_op does it for one vector
-   if (D.nsend) launch_gather_batch (K, D.send_idx, D.bxe, D.bsend, D.nsend, st);
-   auto rows = [&] (int rb0, int rb1) {
-      if (s->tune.batch_spmv_rows) launch_csr_spmv_batch_split_range (K, s->A, rb0, rb1, D.bxe, dw, st);
-      else launch_csr_spmv_batch (K, s->A, rb0, rb1, D.bxe, s->bw, nullptr, 0, st);
-   };
-   if (D.overlap) {
-      (void) hipEventRecord (D.ev_packed, st);
-      (void) hipStreamWaitEvent (D.comm_stream, D.ev_packed, 0);
-      alltoallv_dev (s, D.bsend, D.send_counts_k.data (), halo, D.recv_counts_k.data (), D.comm_stream);
-      (void) hipEventRecord (D.ev_halo, D.comm_stream);
-      rows (D.seg_rb[1], D.seg_rb[2]);
-      (void) hipStreamWaitEvent (st, D.ev_halo, 0);
-      rows (D.seg_rb[0], D.seg_rb[1]);
-      rows (D.seg_rb[2], D.seg_rb[3]);
+   double *const none[NKP_BATCH_MAX] = {};
+   if (s->opt.precond == NKP_PRECOND_MULTILEVEL && D.on && D.ras) {
+      double *halo = D.bxe + n * K;
+      if (D.ras_sep) {
+         // several rings: the overlap rows alone, K wide, into a block of their own in the hierarchy's order
+         D.ras_send_counts_k.resize (D.ras_send_counts.size ());
+         D.ras_recv_counts_k.resize (D.ras_recv_counts.size ());
+         for (size_t p = 0; p < D.ras_send_counts.size (); p++) D.ras_send_counts_k[p] = D.ras_send_counts[p] * K;
+         for (size_t p = 0; p < D.ras_recv_counts.size (); p++) D.ras_recv_counts_k[p] = D.ras_recv_counts[p] * K;
+         if (D.ras_nsend) launch_pack_rows_split (K, D.ras_send_idx, src, D.bras_send, D.ras_nsend, st);
+         alltoallv_dev (s, D.bras_send, D.ras_send_counts_k.data (), D.bras_recv, D.ras_recv_counts_k.data (), st);
+         ml_apply_batch_split_ext (s->ml, K, src, D.bras_recv, nullptr, n, zi, dz ? dz : none, st);
+      } else {
+         if (D.nsend) launch_pack_rows_split (K, D.send_idx, src, D.bsend, D.nsend, st);
+         alltoallv_dev (s, D.bsend, D.send_counts_k.data (), halo, D.recv_counts_k.data (), st);
+         ml_apply_batch_split_ext (s->ml, K, src, halo, D.sel_idx, n, zi, dz ? dz : none, st);
+      }
+   } else if (s->opt.precond == NKP_PRECOND_MULTILEVEL) {
+      // permutation into the hierarchy's row order and the (de-)interleave in one kernel each
+      ml_apply_batch_split (s->ml, K, src, zi, dz ? dz : none, st, src_scale);
    } else {
-      alltoallv_dev (s, D.bsend, D.send_counts_k.data (), halo, D.recv_counts_k.data (), st);
-      rows (0, s->A.nrowblk);
+      launch_interleave (K, src, s->bvin, n, st, src_scale);
+      if (s->opt.precond == NKP_PRECOND_COLUMN_JACOBI) {
+         if (launch_colblock_apply_lanes_batch (K, s->B, 0, s->B.ngrp, s->bvin, zi, 0, st) != 0)
+            launch_colblock_apply_wave_batch (K, s->B, 0, s->B.nblk, s->bvin, zi, 0, s->B.fac_tf ? 1 : 0, st);
+      } else
+         launch_copy (s->bvin, zi, n * K, st);
+      if (dz) launch_deinterleave (K, zi, dz, n, st);
    }
-   if (!s->tune.batch_spmv_rows) launch_deinterleave (K, s->bw, dw, n, st);
+}
+
+// dst_k = A x_k (b NULL; times out_scale when given) or dst_k = b_k - A x_k (b_k times b_scale when given) for the K columns
+// of xi -- s->bz, or the own rows of s->dist.bxe, whose halo rows arrive here as spmv_op fetches them for one vector
+static void batch_operator (nkp_solver *s, int K, const double *xi, const double *const *b, const double *b_scale, const double *out_scale, double *const *dst)
+{
+   const int64_t n = s->n;
+   hipStream_t st = s->stream;
+   auto &D = s->dist;
+   const bool split = s->tune.batch_spmv_rows != 0;
+   // the products-in-LDS layout works on interleaved vectors: right-hand side in through bvin, result out through bw
+   if (!split && b) launch_interleave (K, b, s->bvin, n, st, b_scale);
+   auto rows = [&] (int rb0, int rb1) {
+      if (split && b) launch_csr_residual_batch_split_range (K, s->A, rb0, rb1, xi, b, b_scale, dst, st);
+      else if (split) launch_csr_spmv_batch_split_range (K, s->A, rb0, rb1, xi, dst, st, out_scale);
+      else launch_csr_spmv_batch (K, s->A, rb0, rb1, xi, s->bw, b ? s->bvin : nullptr, b ? 1 : 0, st, out_scale);
+   };
+   if (!D.on) rows (0, s->A.nrowblk);
+   else {
+      double *halo = D.bxe + n * K;
+      if (D.nsend) launch_gather_batch (K, D.send_idx, xi, D.bsend, D.nsend, st);
+      if (D.overlap) {
+         (void) hipEventRecord (D.ev_packed, st);
+         (void) hipStreamWaitEvent (D.comm_stream, D.ev_packed, 0);
+         alltoallv_dev (s, D.bsend, D.send_counts_k.data (), halo, D.recv_counts_k.data (), D.comm_stream);
+         (void) hipEventRecord (D.ev_halo, D.comm_stream);
+         rows (D.seg_rb[1], D.seg_rb[2]);
+         (void) hipStreamWaitEvent (st, D.ev_halo, 0);
+         rows (D.seg_rb[0], D.seg_rb[1]);
+         rows (D.seg_rb[2], D.seg_rb[3]);
+      } else {
+         alltoallv_dev (s, D.bsend, D.send_counts_k.data (), halo, D.recv_counts_k.data (), st);
+         rows (0, s->A.nrowblk);
+      }
+   }
+   if (!split) launch_deinterleave (K, s->bw, dst, n, st);
+}
+
+// One Krylov step's applications for the running systems of a group, arnoldi_apply / apply_precond operation by operation:
+//   z_k = M v_k;  for c = 1 .. steps - 1:  p1_k = v_k - A z_k,  z_k += M p1_k;  w_k = A z_k
+// and in the row-weighted iteration v_k R^-1 on the way in and R on the way out, folded into the kernels that read v and write w.
+// Each stage is one pass for the group (one exchange in the row-distributed flavour).
+static void batch_step_apply (nkp_solver *s, int K, nkp_solver *const *mem, const bool *running, int j)
+{
+   const int64_t ld = s->ld, n = s->n;
+   hipStream_t st = s->stream;
+   const double *src[NKP_BATCH_MAX] = {};
+   double *dz[NKP_BATCH_MAX] = {}, *dw[NKP_BATCH_MAX] = {};
+   int steps = 1;
+   for (int k = 0; k < K; k++)
+      if (mem[k] && running[k]) {
+         src[k] = mem[k]->V + (int64_t) j * ld; dz[k] = mem[k]->Z + (int64_t) j * ld; dw[k] = mem[k]->w;
+         if (mem[k]->p1 && mem[k]->steps_now > steps) steps = mem[k]->steps_now;
+      }
+   const double *rinv = s->equil ? s->rinv : nullptr, *rscale = s->equil ? s->rscale : nullptr;
+   double *zi = s->dist.on ? s->dist.bxe : s->bz;
+   if (s->dist.on) {
+      auto &D = s->dist;
+      D.send_counts_k.resize (D.send_counts.size ());
+      D.recv_counts_k.resize (D.recv_counts.size ());
+      for (size_t p = 0; p < D.send_counts.size (); p++) D.send_counts_k[p] = D.send_counts[p] * K;
+      for (size_t p = 0; p < D.recv_counts.size (); p++) D.recv_counts_k[p] = D.recv_counts[p] * K;
+   }
+   batch_precond (s, K, src, rinv, zi, dz);
+   for (int c = 1; c < steps; c++) {
+      // The run-time guard of fg_restart is per system: one whose steps_now it has lowered takes no part in the further
+      // cycles (NULL pointers, like a system that is not running) and keeps the z of its single solve.  On a row-distributed
+      // solver steps_now follows from allreduced residual norms, so every rank builds the same mask and `steps` is the same
+      // everywhere: the ranks' sequences of exchanges stay together.
+      const double *rin[NKP_BATCH_MAX] = {}, *p1c[NKP_BATCH_MAX] = {};
+      double *p1[NKP_BATCH_MAX] = {}, *zc[NKP_BATCH_MAX] = {};
+      for (int k = 0; k < K; k++)
+         if (src[k] && mem[k]->p1 && mem[k]->steps_now > c) { rin[k] = src[k]; p1[k] = mem[k]->p1; p1c[k] = mem[k]->p1; zc[k] = dz[k]; }
+      batch_operator (s, K, zi, rin, rinv, nullptr, p1);
+      batch_precond (s, K, p1c, nullptr, s->bw, nullptr);
+      launch_add_split (K, s->bw, zi, zc, n, st);
+   }
+   batch_operator (s, K, zi, nullptr, nullptr, rscale, dw);
 }
 
 // Gram-Schmidt of the running systems (run[0 .. R-1], at column j) with the allreduces of ONE system: row r of each message
@@ -1329,34 +1413,6 @@ static void orthogonalise_group (nkp_solver *s, int R, nkp_solver *const *run, i
    launch_scale_to_group (R, G, inv, n, st);
 }
 
-// z_k = M^-1 v_k, w_k = A z_k for the running systems; v, z, w per system, the application batched
-static void batch_apply (nkp_solver *s, int K, nkp_solver *const *mem, const bool *running, int j)
-{
-   const int64_t ld = s->ld, n = s->n;
-   hipStream_t st = s->stream;
-   const double *src[NKP_BATCH_MAX] = {};
-   double *dz[NKP_BATCH_MAX] = {}, *dw[NKP_BATCH_MAX] = {};
-   for (int k = 0; k < K; k++)
-      if (mem[k] && running[k]) { src[k] = mem[k]->V + (int64_t) j * ld; dz[k] = mem[k]->Z + (int64_t) j * ld; dw[k] = mem[k]->w; }
-   if (s->opt.precond == NKP_PRECOND_MULTILEVEL) {
-      // permutation into the hierarchy's row order and the (de-)interleave in one kernel each
-      ml_apply_batch_split (s->ml, K, src, s->bz, dz, st);
-   } else {
-      launch_interleave (K, src, s->bvin, n, st);
-      if (s->opt.precond == NKP_PRECOND_COLUMN_JACOBI) {
-         if (launch_colblock_apply_lanes_batch (K, s->B, 0, s->B.ngrp, s->bvin, s->bz, 0, st) != 0)
-            launch_colblock_apply_wave_batch (K, s->B, 0, s->B.nblk, s->bvin, s->bz, 0, s->B.fac_tf ? 1 : 0, st);
-      } else
-         launch_copy (s->bvin, s->bz, n * K, st);
-      launch_deinterleave (K, s->bz, dz, n, st);
-   }
-   if (s->tune.batch_spmv_rows) launch_csr_spmv_batch_split (K, s->A, s->bz, dw, st);
-   else {
-      launch_csr_spmv_batch (K, s->A, 0, s->A.nrowblk, s->bz, s->bw, nullptr, 0, st);
-      launch_deinterleave (K, s->bw, dw, n, st);
-   }
-}
-
 // mem[k]->b / ->x hold right-hand side and initial guess of system k (k < nact); on return ->x holds the solutions
 static int fgmres_batch (nkp_solver *s, int K, int nact, nkp_solver *const *mem, FgmresState *F)
 {
@@ -1376,15 +1432,12 @@ static int fgmres_batch (nkp_solver *s, int K, int nact, nkp_solver *const *mem,
       // the running systems advance together: all of them are at column j of their cycle
       for (int j = 0; nrun; j++) {
          s->batch_steps++;
+         batch_step_apply (s, K, mem, running, j);
          if (s->dist.on) {
-            const int64_t ld = s->ld;
-            const double *src[NKP_BATCH_MAX] = {};
-            double *dz[NKP_BATCH_MAX] = {}, *dw[NKP_BATCH_MAX] = {};
             nkp_solver *run[NKP_BATCH_MAX] = {};
             int R = 0;
             for (int k = 0; k < nact; k++)
-               if (running[k]) { src[k] = mem[k]->V + (int64_t) j * ld; dz[k] = mem[k]->Z + (int64_t) j * ld; dw[k] = mem[k]->w; run[R++] = mem[k]; }
-            batch_apply_dist (s, K, src, dz, dw);
+               if (running[k]) run[R++] = mem[k];
             orthogonalise_group (s, R, run, j);
             HIPCHK (hipMemcpyAsync (s->dist.ghpin, s->dist.gmsg, (size_t) R * (size_t) (j + 2) * sizeof (double), hipMemcpyDeviceToHost, s->stream));
             HIPCHK (hipStreamSynchronize (s->stream));
@@ -1395,7 +1448,6 @@ static int fgmres_batch (nkp_solver *s, int K, int nact, nkp_solver *const *mem,
                if (running[k] && fg_post_step (mem[k], F[k])) { running[k] = false; nrun--; }
             continue;
          }
-         batch_apply (s, K, mem, running, j);
          for (int k = 0; k < nact; k++) {
             if (!running[k]) continue;
             arnoldi_orthogonalise (mem[k], j);
@@ -1441,6 +1493,7 @@ extern "C" int nkp_solve_batch_device (nkp_solver *s, int nrhs, const void *d_B,
    const char *why = batch_unsupported (s);
    if (why || nrhs < 2 || !s->tune.rhs_batch) {
       // one at a time (the reference's loop); `why` names what the batched path does not cover
+      if (why && nrhs >= 2 && s->tune.rhs_batch) note_fallback (s, "nkp_solve_batch", why, nrhs);
       for (int c = 0; c < nrhs; c++) {
          const int status = nkp_solve_device (s, B + (size_t) c * (size_t) ldb, X + (size_t) c * (size_t) ldb, 0, berr ? berr + c : nullptr, iters ? iters + c : nullptr, relres ? relres + c : nullptr);
          if (status < 0) return status;
@@ -1557,6 +1610,7 @@ extern "C" int nkp_solve (nkp_solver *s, double *b_in_x_out, int nrhs, int64_t l
       (void) hipFree (dB);
       return status;
    }
+   if (nrhs >= 2 && s->tune.rhs_batch) note_fallback (s, "nkp_solve", batch_unsupported (s), nrhs);
    for (int c = 0; c < nrhs; c++) {          // nrhs = 0 is the reference's factor-only call: nothing to do
       double *col = b_in_x_out + (size_t) c * (size_t) ldb;
       HIPCHK (hipMemcpyAsync (s->b, col, bytes, hipMemcpyHostToDevice, s->stream));

@@ -1,0 +1,209 @@
+"""Batched right-hand sides under row equilibration (nkp_options.equil) and chained preconditioner cycles (precond_steps >= 2),
+single GPU: the batched path takes both instead of falling back to one solve at a time, and every column still has the BITS of its
+own solve with the same options -- same iteration count, same residual, same solution.  That a call really went through the
+batched driver is read from the counters batch_steps / batch_width (a fallback leaves batch_steps where it was).
+
+The run-time guard of the chained cycles (a restart cycle without progress => one cycle per step for the rest of THAT solve) is per
+system, so a group can hold systems with different step counts: test_guard_fires_for_some_columns_of_a_group pins such a group."""
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from nk_ocn_tracer_jacobian_precond_amd import nc3, solver, synth
+
+pytestmark = pytest.mark.gpu
+
+BIN = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "nk_ocn_tracer_jacobian_precond_amd", "bin")
+
+
+def _case(name):
+    cnt = 1
+    if name == "long_columns":
+        p = synth.generate(imt=24, jmt=20, km=70, adv="centred", hmix="const", seed=5)
+    elif name == "tracers2":
+        cnt = 2
+        p = synth.generate(imt=40, jmt=46, km=20, adv="upwind3", hmix="isop", coupled_tracer_cnt=2, seed=3)
+    else:
+        p = synth.generate(imt=24, jmt=20, km=12, adv="upwind3", hmix="isop", seed=0)
+    blk = solver.column_blocks(p.col_start(), p.tracer_state_len, cnt)
+    ci, cj = solver.column_coords(p.ind_i, p.ind_j, p.col_start(), cnt)
+    return p, blk, ci, cj, cnt
+
+
+def _rhs(n, count=5):
+    B = np.random.default_rng(11).standard_normal((count, n))
+    B[2] *= 1e-3                                            # systems of a group leave it at different steps
+    return B
+
+
+def _make(name, precond=solver.PRECOND_MULTILEVEL, **opts):
+    p, blk, ci, cj, cnt = _case(name)
+    kw = dict(col_i=ci, col_j=cj) if precond == solver.PRECOND_MULTILEVEL else {}
+    restart = opts.pop("restart", 200 if precond == solver.PRECOND_MULTILEVEL else 60)
+    return p, solver.NkpSolver(p.rowptr, p.colind, p.nzval, blk, coupled_tracer_cnt=cnt, precond=precond, rtol=opts.pop("rtol", 1e-10), restart=restart, max_iters=4000,
+                               **kw, **opts)
+
+
+def _assert_column_bits(tag, X, infos, single, cols):
+    for q, c in enumerate(cols):
+        x1, i1 = single[c]
+        assert infos[q]["iters"] == i1["iters"] and infos[q]["relres"] == i1["relres"] and infos[q]["berr"] == i1["berr"], (tag, c, infos[q], i1)
+        assert np.array_equal(X[q], x1), (tag, c, np.abs(X[q] - x1).max())
+
+
+def _check(name, precond=solver.PRECOND_MULTILEVEL, chained=False, nrhs_list=(2, 3, 4, 5), width=4, count=5, **opts):
+    p, s = _make(name, precond, **opts)
+    with s:
+        assert s.get_int("equil") == (1 if opts.get("equil", 0) > 0 else 0) and s.get_int("precond_steps") == opts.get("precond_steps", 1)
+        B = _rhs(p.flat_len, count)
+        single = [s.solve(B[c], raise_on_fail=False) for c in range(count)]
+        assert all(i["iters"] > 0 for _, i in single)
+        for nrhs in nrhs_list:
+            before = s.get_int("batch_steps")
+            X, infos = s.solve_many(B[:nrhs], raise_on_fail=False)
+            steps = s.get_int("batch_steps") - before
+            _assert_column_bits((name, opts, nrhs), X, infos, single, range(nrhs))
+            assert steps > 0, (name, opts, nrhs, "the call fell back to one solve at a time")
+            last = [g for g in range(0, nrhs, width) if nrhs - g > 1][-1]          # first column of the last group of two or more
+            assert s.get_int("batch_width") == (2 if min(nrhs - last, width) <= 2 else 4 if min(nrhs - last, width) <= 4 else 8)
+            if nrhs >= width:
+                assert s.get_int("batch_width") == width
+            if chained:
+                # lockstep steps of the full groups of the call: the longest solve of each group at least, never the sum of all
+                its = [single[c][1]["iters"] for c in range(nrhs)]
+                groups = [its[g:g + width] for g in range(0, nrhs, width)]
+                batched = [g for g in groups if len(g) > 1]
+                assert sum(max(g) for g in batched) <= steps < sum(sum(g) for g in batched), (name, opts, nrhs, steps, its)
+
+
+@pytest.mark.parametrize("name,precond,f32", [("small", solver.PRECOND_MULTILEVEL, "1"), ("small", solver.PRECOND_COLUMN_JACOBI, "1"),
+                                              ("small", solver.PRECOND_NONE, "1"), ("long_columns", solver.PRECOND_MULTILEVEL, "1"),
+                                              ("tracers2", solver.PRECOND_MULTILEVEL, "0")])
+def test_equilibrated_batched_solves_have_the_bits_of_single_solves(name, precond, f32, monkeypatch):
+    monkeypatch.setenv("NKP_ML_F32", f32)
+    _check(name, precond, equil=1)
+
+
+@pytest.mark.parametrize("name,steps", [("small", 2), ("long_columns", 2), ("tracers2", 2), ("small", 3)])
+def test_chained_cycles_batched_solves_have_the_bits_of_single_solves(name, steps):
+    _check(name, chained=True, precond_steps=steps)
+
+
+@pytest.mark.parametrize("name", ["small", "long_columns"])
+def test_equilibration_and_chained_cycles_combine(name):
+    _check(name, chained=True, equil=1, precond_steps=2)
+
+
+@pytest.mark.parametrize("precond", [solver.PRECOND_COLUMN_JACOBI, solver.PRECOND_MULTILEVEL])
+def test_products_in_lds_layout_takes_both_options(precond):
+    """nkp_tuning.batch_spmv_rows = 0 is the other layout of the batched SpMV; it has the scaling in its epilogue and the residual
+    between two cycles as well."""
+    _check("small", precond, chained=True, nrhs_list=(3, 4), equil=1, precond_steps=2, tuning=dict(batch_spmv_rows=0))
+
+
+def test_eight_right_hand_sides_with_chained_cycles():
+    _check("small", chained=True, nrhs_list=(9,), width=8, count=9, precond_steps=2, tuning=dict(rhs_batch=8))
+
+
+def test_members_hold_what_the_options_need_and_no_more():
+    """A group member under chained cycles has one more vector than without (the residual between two cycles; the correction of the
+    second cycle stays interleaved), and none for row equilibration (the scalings are applied inside the batched kernels).
+    "batch_member_bytes" counts the three members of a group of four."""
+    got = {}
+    for key, opts in (("plain", {}), ("chained", dict(precond_steps=2)), ("equil", dict(equil=1))):
+        p, s = _make("small", **opts)
+        with s:
+            assert s.get_int("batch_member_bytes") == 0
+            s.solve_many(_rhs(p.flat_len, 4), raise_on_fail=False)
+            assert s.get_int("batch_width") == 4
+            got[key] = s.get_int("batch_member_bytes")
+    n = p.flat_len
+    assert got["plain"] > 3 * 8 * n * 400                     # three sets of V and Z at restart = 200
+    assert 3 * 8 * n <= got["chained"] - got["plain"] < 2 * 3 * 8 * n, got
+    assert got["equil"] == got["plain"], got
+
+
+def test_fallback_names_its_reason_at_verbose_1(capfd):
+    """What the batched path still does not cover goes one at a time and says so in one "(rank)"-prefixed line."""
+    p, s = _make("small", basis_f32=1, verbose=1)
+    with s:
+        capfd.readouterr()
+        B = _rhs(p.flat_len)[:2]
+        before = s.get_int("batch_steps")
+        X, infos = s.solve_many(B, raise_on_fail=False)
+        out = capfd.readouterr().out
+        assert s.get_int("batch_steps") == before
+        lines = [ln for ln in out.splitlines() if "one at a time" in ln]
+        assert len(lines) == 1 and lines[0].startswith("(0) ") and "an f32 Krylov basis" in lines[0], out
+        for c in range(2):
+            x1, i1 = s.solve(B[c], raise_on_fail=False)
+            assert np.array_equal(X[c], x1) and infos[c]["iters"] == i1["iters"]
+
+
+GUARD_LINE = "continuing with one"
+GUARD_RESTART = 3
+GUARD_RTOL = 3.5e-13
+GUARD_SCALES = (1.0, 1e-3, 1.0, 1e3)
+
+
+def test_guard_fires_for_some_columns_of_a_group(capfd):
+    """long_columns, two cycles per step, a short restart: the run-time guard ("no progress over a restart cycle ...; continuing
+    with one") fires in the single solves of a proper subset of the right-hand sides.  In the batched group those systems go on
+    with one cycle while the others keep two; all of them keep the bits of their single solves.
+
+    The guard needs a restart cycle that gains nothing, which these well-conditioned shapes show only where rounding ends the
+    descent: at rtol = 1e-10 .. 5e-13 it fires for no right-hand side (restart 2 .. 6), at 2.7e-13 for all.  With FGMRES(3) and
+    rtol = 3.5e-13 columns 0 and 3 meet it on their way (118 and 116 iterations) and columns 1 and 2 do not (112, 109); all four
+    converge."""
+    p, s = _make("long_columns", precond_steps=2, restart=GUARD_RESTART, rtol=GUARD_RTOL, verbose=1)
+    with s:
+        B = np.random.default_rng(11).standard_normal((4, p.flat_len)) * np.array(GUARD_SCALES)[:, None]
+        single, fired = [], []
+        capfd.readouterr()
+        for c in range(4):
+            single.append(s.solve(B[c], raise_on_fail=False))
+            fired.append(GUARD_LINE in capfd.readouterr().out)
+        print("guard fired in the single solves of columns", [c for c in range(4) if fired[c]], "iterations", [i["iters"] for _, i in single])
+        assert 0 < sum(fired) < 4, fired
+        before = s.get_int("batch_steps")
+        X, infos = s.solve_many(B, raise_on_fail=False)
+        out = capfd.readouterr().out
+        assert s.get_int("batch_steps") > before and s.get_int("batch_width") == 4
+        assert out.count(GUARD_LINE) == sum(fired), out
+        _assert_column_bits("guard", X, infos, single, range(4))
+
+
+def test_cli_rhs_block_under_equilibration(tmp_path, golden_by_name):
+    """bin/solve_ABglobal with NKP_EQUIL=1: two right-hand-side groups of the coupled pair, NKP_RHS_BLOCK=2 against one at a time --
+    the same bytes in the tracer file, and no fallback line at -D1."""
+    g = golden_by_name("pair_8x8x5")
+    src = nc3.NcFile(g.tracer_path)
+    dims = {"nlon": g.imt, "nlat": g.jmt, "z_t": g.km}
+    fill = {"_FillValue": np.float64(synth.FILL_DOUBLE)}
+    ocean = np.zeros((g.km, g.jmt, g.imt), bool)
+    ocean[g.ind_k, g.ind_j, g.ind_i] = True
+    rng = np.random.default_rng(7)
+    variables = []
+    for v in g.varnames:
+        variables.append((v, ["z_t", "nlat", "nlon"], src.get(v), fill))
+    for v in g.varnames:                                    # a second group of the pair with a right-hand side of its own
+        f = src.get(v).copy()
+        f[ocean] = 1e-2 * rng.standard_normal(int(ocean.sum()))
+        variables.append((v + "_B", ["z_t", "nlat", "nlon"], f, fill))
+    names = ",".join(list(g.varnames) + [v + "_B" for v in g.varnames])
+    out = {}
+    for tag, extra in (("block", {"NKP_RHS_BLOCK": "2"}), ("plain", {})):
+        path = str(tmp_path / f"B_{tag}.nc")
+        nc3.write(path, dims, variables)
+        env = dict(os.environ, NKP_EQUIL="1", NKP_ACCEPT_BERR="1", **extra)
+        if not extra:
+            env.pop("NKP_RHS_BLOCK", None)
+        r = subprocess.run([os.path.join(BIN, "solve_ABglobal"), "-D1", "-v", names, g.matrix_path, path], capture_output=True, text=True, env=env, timeout=240)
+        assert r.returncode == 0, r.stderr + r.stdout
+        out[tag] = (open(path, "rb").read(), r.stdout)
+    assert "calling nkp_solve for 2 right-hand sides, 2 per call" in out["block"][1], out["block"][1]
+    assert "one at a time" not in out["block"][1], out["block"][1]
+    assert "nkp_solve_batch: right-hand side 1:" in out["block"][1], out["block"][1]          # the batched driver's own verdict line
+    assert out["block"][0] == out["plain"][0]
