@@ -61,24 +61,17 @@ void launch_interleave (int K, const double *const *src, double *X, int64_t n, h
 {
    BatchPtrs P;
    for (int k = 0; k < NKP_BATCH_MAX; k++) P.p[k] = k < K ? src[k] : nullptr;
-   if (scale) {
-      if (K == 2) hipLaunchKernelGGL (interleave_scaled_kernel<2>, dim3 (bt_grid (n)), dim3 (BT_THREADS), 0, st, P, scale, X, n);
-      else if (K == 4) hipLaunchKernelGGL (interleave_scaled_kernel<4>, dim3 (bt_grid (n)), dim3 (BT_THREADS), 0, st, P, scale, X, n);
-      else hipLaunchKernelGGL (interleave_scaled_kernel<8>, dim3 (bt_grid (n)), dim3 (BT_THREADS), 0, st, P, scale, X, n);
-      return;
-   }
-   if (K == 2) hipLaunchKernelGGL (interleave_kernel<2>, dim3 (bt_grid (n)), dim3 (BT_THREADS), 0, st, P, X, n);
-   else if (K == 4) hipLaunchKernelGGL (interleave_kernel<4>, dim3 (bt_grid (n)), dim3 (BT_THREADS), 0, st, P, X, n);
-   else hipLaunchKernelGGL (interleave_kernel<8>, dim3 (bt_grid (n)), dim3 (BT_THREADS), 0, st, P, X, n);
+   with_k (K, [&] (auto k) {
+      if (scale) hipLaunchKernelGGL (interleave_scaled_kernel<decltype (k)::value>, dim3 (bt_grid (n)), dim3 (BT_THREADS), 0, st, P, scale, X, n);
+      else hipLaunchKernelGGL (interleave_kernel<decltype (k)::value>, dim3 (bt_grid (n)), dim3 (BT_THREADS), 0, st, P, X, n);
+   });
 }
 
 void launch_deinterleave (int K, const double *X, double *const *dst, int64_t n, hipStream_t st)
 {
    BatchOutPtrs P;
    for (int k = 0; k < NKP_BATCH_MAX; k++) P.p[k] = k < K ? dst[k] : nullptr;
-   if (K == 2) hipLaunchKernelGGL (deinterleave_kernel<2>, dim3 (bt_grid (n)), dim3 (BT_THREADS), 0, st, X, P, n);
-   else if (K == 4) hipLaunchKernelGGL (deinterleave_kernel<4>, dim3 (bt_grid (n)), dim3 (BT_THREADS), 0, st, X, P, n);
-   else hipLaunchKernelGGL (deinterleave_kernel<8>, dim3 (bt_grid (n)), dim3 (BT_THREADS), 0, st, X, P, n);
+   with_k (K, [&] (auto k) { hipLaunchKernelGGL (deinterleave_kernel<decltype (k)::value>, dim3 (bt_grid (n)), dim3 (BT_THREADS), 0, st, X, P, n); });
 }
 
 // ---------------------------------------------------------------- CSR SpMV, K columns
@@ -290,61 +283,56 @@ void csr_spmv_batch_rows_kernel (const int *__restrict__ rowblk_all, int rb0, in
    }
 }
 
+// csr_spmv_batch_rows_kernel<MODE, storage of A, K, SPLIT, SCALED> on the row blocks [rb0, rb0 + cnt) of A
+template <int MODE, bool SPLIT, bool SCALED>
+static void launch_batch_rows (int K, const CsrDev &A, int rb0, int cnt, const double *x, double *y, const double *b, const BatchOutPtrs &split,
+                               const BatchPtrs &bsplit, const double *scale, hipStream_t st)
+{
+   const int per_xcd = (cnt + 7) / 8;
+   with_storage (A.valf, A.val, [&] (auto val) {
+      with_k (K, [&] (auto k) {
+         hipLaunchKernelGGL ((csr_spmv_batch_rows_kernel<MODE, elem_t<decltype (val)>, decltype (k)::value, SPLIT, SCALED>), dim3 (per_xcd * 8), dim3 (BT_THREADS), 0, st,
+                             A.rowblk, rb0, cnt, per_xcd, A.rowptr, A.colind, val, x, y, b, split, bsplit, scale);
+      });
+   });
+}
+
 void launch_csr_spmv_batch (int K, const CsrDev &A, int rb0, int rb1, const double *x, double *y, const double *b, int mode, hipStream_t st, const double *scale)
 {
    const int cnt = rb1 - rb0;
    if (cnt <= 0) return;
-   const int per_xcd = (cnt + 7) / 8;
    const nkp_tuning &T = A.tune ? *A.tune : nkp_builtin_tuning ();
-   if (scale && mode == 0) {
-      // y = R (A x): the same kernels with the scaling in their epilogue
-#define BS_ARGS A.rowblk, rb0, cnt, per_xcd, A.rowptr, A.colind
-#define BS_ROWS(VT_, K_, VAL_) hipLaunchKernelGGL ((csr_spmv_batch_rows_kernel<0, VT_, K_, false, true>), dim3 (per_xcd * 8), dim3 (BT_THREADS), 0, st, \
-                                                   BS_ARGS, VAL_, x, y, b, BatchOutPtrs (), BatchPtrs (), scale)
-#define BS_PROD(VT_, K_, VAL_) hipLaunchKernelGGL ((csr_spmv_batch_kernel<0, VT_, K_, true>), dim3 (per_xcd * 8), dim3 (BT_THREADS), 0, st, BS_ARGS, VAL_, x, y, b, scale)
-#define BSCALED_K(VT_, VAL_) do { if (K == 8) BS_ROWS (VT_, 8, VAL_);                                                                          \
-                                  else if (T.batch_spmv_rows) { if (K == 2) BS_ROWS (VT_, 2, VAL_); else BS_ROWS (VT_, 4, VAL_); } \
-                                  else { if (K == 2) BS_PROD (VT_, 2, VAL_); else BS_PROD (VT_, 4, VAL_); } } while (0)
-      if (A.valf) BSCALED_K (float, A.valf); else BSCALED_K (double, A.val);
-#undef BSCALED_K
-#undef BS_PROD
-#undef BS_ROWS
-#undef BS_ARGS
+   const bool scaled = scale && mode == 0;          // y = R (A x): the same kernels with the scaling in their epilogue
+   if (K == 8 || T.batch_spmv_rows) {               // (the products-in-LDS variant stops at four)
+      if (scaled) launch_batch_rows<0, false, true> (K, A, rb0, cnt, x, y, b, BatchOutPtrs (), BatchPtrs (), scale, st);
+      else if (mode == 0) launch_batch_rows<0, false, false> (K, A, rb0, cnt, x, y, b, BatchOutPtrs (), BatchPtrs (), nullptr, st);
+      else launch_batch_rows<1, false, false> (K, A, rb0, cnt, x, y, b, BatchOutPtrs (), BatchPtrs (), nullptr, st);
       return;
    }
-#define BSPMV(KERNEL_, MODE_, VT_, K_, VAL_) hipLaunchKernelGGL ((KERNEL_<MODE_, VT_, K_>), dim3 (per_xcd * 8), dim3 (BT_THREADS), 0, st, \
-                                                                 A.rowblk, rb0, cnt, per_xcd, A.rowptr, A.colind, VAL_, x, y, b)
-#define BSPMV_K(MODE_, VT_, VAL_) do { if (K == 8) BSPMV (csr_spmv_batch_rows_kernel, MODE_, VT_, 8, VAL_);      /* (the products-in-LDS variant stops at four) */ \
-                                       else if (T.batch_spmv_rows) { if (K == 2) BSPMV (csr_spmv_batch_rows_kernel, MODE_, VT_, 2, VAL_); else BSPMV (csr_spmv_batch_rows_kernel, MODE_, VT_, 4, VAL_); } \
-                                       else { if (K == 2) BSPMV (csr_spmv_batch_kernel, MODE_, VT_, 2, VAL_); else BSPMV (csr_spmv_batch_kernel, MODE_, VT_, 4, VAL_); } } while (0)
-   if (A.valf) { if (mode == 0) BSPMV_K (0, float, A.valf); else BSPMV_K (1, float, A.valf); }
-   else { if (mode == 0) BSPMV_K (0, double, A.val); else BSPMV_K (1, double, A.val); }
-#undef BSPMV_K
-#undef BSPMV
+   const int per_xcd = (cnt + 7) / 8;
+   with_storage (A.valf, A.val, [&] (auto val) {
+      using VT = elem_t<decltype (val)>;
+      with_int<2, 4> (K, [&] (auto k) {
+         constexpr int KK = decltype (k)::value;
+         const auto products = [&] (auto kernel, const double *sc) {
+            hipLaunchKernelGGL (kernel, dim3 (per_xcd * 8), dim3 (BT_THREADS), 0, st, A.rowblk, rb0, cnt, per_xcd, A.rowptr, A.colind, val, x, y, b, sc);
+         };
+         if (scaled) products (csr_spmv_batch_kernel<0, VT, KK, true>, scale);
+         else if (mode == 0) products (csr_spmv_batch_kernel<0, VT, KK, false>, nullptr);
+         else products (csr_spmv_batch_kernel<1, VT, KK, false>, nullptr);
+      });
+   });
 }
 
 // y_k = A x_k for the K interleaved columns of x, every result in its own vector (dst[k] NULL: not wanted); row blocks
 // [rb0, rb1) only (the row-distributed flavour multiplies its interior rows while the halo of x travels)
 void launch_csr_spmv_batch_split_range (int K, const CsrDev &A, int rb0, int rb1, const double *x, double *const *dst, hipStream_t st, const double *scale)
 {
-   const int cnt = rb1 - rb0;
-   if (cnt <= 0) return;
-   const int per_xcd = (cnt + 7) / 8;
+   if (rb1 <= rb0) return;
    BatchOutPtrs P;
    for (int k = 0; k < NKP_BATCH_MAX; k++) P.p[k] = k < K ? dst[k] : nullptr;
-   if (scale) {
-#define BSPLIT_S(VT_, K_, VAL_) hipLaunchKernelGGL ((csr_spmv_batch_rows_kernel<0, VT_, K_, true, true>), dim3 (per_xcd * 8), dim3 (BT_THREADS), 0, st, \
-                                                    A.rowblk, rb0, cnt, per_xcd, A.rowptr, A.colind, VAL_, x, (double *) nullptr, (const double *) nullptr, P, BatchPtrs (), scale)
-      if (A.valf) { if (K == 2) BSPLIT_S (float, 2, A.valf); else if (K == 4) BSPLIT_S (float, 4, A.valf); else BSPLIT_S (float, 8, A.valf); }
-      else { if (K == 2) BSPLIT_S (double, 2, A.val); else if (K == 4) BSPLIT_S (double, 4, A.val); else BSPLIT_S (double, 8, A.val); }
-#undef BSPLIT_S
-      return;
-   }
-#define BSPLIT(VT_, K_, VAL_) hipLaunchKernelGGL ((csr_spmv_batch_rows_kernel<0, VT_, K_, true>), dim3 (per_xcd * 8), dim3 (BT_THREADS), 0, st, \
-                                                  A.rowblk, rb0, cnt, per_xcd, A.rowptr, A.colind, VAL_, x, (double *) nullptr, (const double *) nullptr, P)
-   if (A.valf) { if (K == 2) BSPLIT (float, 2, A.valf); else if (K == 4) BSPLIT (float, 4, A.valf); else BSPLIT (float, 8, A.valf); }
-   else { if (K == 2) BSPLIT (double, 2, A.val); else if (K == 4) BSPLIT (double, 4, A.val); else BSPLIT (double, 8, A.val); }
-#undef BSPLIT
+   if (scale) launch_batch_rows<0, true, true> (K, A, rb0, rb1 - rb0, x, nullptr, nullptr, P, BatchPtrs (), scale, st);
+   else launch_batch_rows<0, true, false> (K, A, rb0, rb1 - rb0, x, nullptr, nullptr, P, BatchPtrs (), nullptr, st);
 }
 
 void launch_csr_spmv_batch_split (int K, const CsrDev &A, const double *x, double *const *dst, hipStream_t st, const double *scale)
@@ -356,19 +344,12 @@ void launch_csr_spmv_batch_split (int K, const CsrDev &A, const double *x, doubl
 void launch_csr_residual_batch_split_range (int K, const CsrDev &A, int rb0, int rb1, const double *x, const double *const *b, const double *bscale,
                                             double *const *dst, hipStream_t st)
 {
-   const int cnt = rb1 - rb0;
-   if (cnt <= 0) return;
-   const int per_xcd = (cnt + 7) / 8;
+   if (rb1 <= rb0) return;
    BatchOutPtrs P;
    BatchPtrs Q;
    for (int k = 0; k < NKP_BATCH_MAX; k++) { P.p[k] = k < K ? dst[k] : nullptr; Q.p[k] = k < K ? b[k] : nullptr; }
-#define BRESID(VT_, K_, S_, VAL_) hipLaunchKernelGGL ((csr_spmv_batch_rows_kernel<1, VT_, K_, true, S_>), dim3 (per_xcd * 8), dim3 (BT_THREADS), 0, st, \
-                                                      A.rowblk, rb0, cnt, per_xcd, A.rowptr, A.colind, VAL_, x, (double *) nullptr, (const double *) nullptr, P, Q, bscale)
-#define BRESID_K(VT_, S_, VAL_) do { if (K == 2) BRESID (VT_, 2, S_, VAL_); else if (K == 4) BRESID (VT_, 4, S_, VAL_); else BRESID (VT_, 8, S_, VAL_); } while (0)
-   if (A.valf) { if (bscale) BRESID_K (float, true, A.valf); else BRESID_K (float, false, A.valf); }
-   else { if (bscale) BRESID_K (double, true, A.val); else BRESID_K (double, false, A.val); }
-#undef BRESID_K
-#undef BRESID
+   if (bscale) launch_batch_rows<1, true, true> (K, A, rb0, rb1 - rb0, x, nullptr, nullptr, P, Q, bscale, st);
+   else launch_batch_rows<1, true, false> (K, A, rb0, rb1 - rb0, x, nullptr, nullptr, P, Q, bscale, st);
 }
 
 // ---------------------------------------------------------------- grid transfer / permutation / coarsest solve, K columns
@@ -572,74 +553,70 @@ void dense_matvec_batch_kernel (const double *__restrict__ M, const double *__re
    }
 }
 
-#define BT_K(KERNEL, GRID, ...) do { if (K == 2) hipLaunchKernelGGL ((KERNEL<2>), GRID, dim3 (BT_THREADS), 0, st, __VA_ARGS__); \
-                                     else if (K == 4) hipLaunchKernelGGL ((KERNEL<4>), GRID, dim3 (BT_THREADS), 0, st, __VA_ARGS__); \
-                                     else hipLaunchKernelGGL ((KERNEL<8>), GRID, dim3 (BT_THREADS), 0, st, __VA_ARGS__); } while (0)
-
 void launch_restrict_sum_batch (int K, const int *rptr, const int *ridx, const double *fine, double *coarse, int64_t nc, hipStream_t st)
 {
-   if (nc > 0) BT_K (restrict_sum_batch_kernel, dim3 (bt_grid (nc * K)), rptr, ridx, fine, coarse, nc);
+   if (nc > 0) with_k (K, [&] (auto k) { hipLaunchKernelGGL (restrict_sum_batch_kernel<decltype (k)::value>, dim3 (bt_grid (nc * K)), dim3 (BT_THREADS), 0, st, rptr, ridx, fine, coarse, nc); });
 }
 void launch_prolong_add_batch (int K, const int *cmap, const double *coarse, double *fine, int64_t nf, double omega, hipStream_t st)
 {
-   if (nf > 0) BT_K (prolong_add_batch_kernel, dim3 (bt_grid (nf * K)), cmap, coarse, fine, nf, omega);
+   if (nf > 0) with_k (K, [&] (auto k) { hipLaunchKernelGGL (prolong_add_batch_kernel<decltype (k)::value>, dim3 (bt_grid (nf * K)), dim3 (BT_THREADS), 0, st, cmap, coarse, fine, nf, omega); });
 }
 void launch_gather_batch (int K, const int *perm, const double *in, double *out, int64_t n, hipStream_t st)
 {
-   if (n > 0) BT_K (gather_batch_kernel, dim3 (bt_grid (n * K)), perm, in, out, n, 0);
+   if (n > 0) with_k (K, [&] (auto k) { hipLaunchKernelGGL (gather_batch_kernel<decltype (k)::value>, dim3 (bt_grid (n * K)), dim3 (BT_THREADS), 0, st, perm, in, out, n, 0); });
 }
 void launch_scatter_batch (int K, const int *perm, const double *in, double *out, int64_t n, hipStream_t st)
 {
-   if (n > 0) BT_K (gather_batch_kernel, dim3 (bt_grid (n * K)), perm, in, out, n, 1);
+   if (n > 0) with_k (K, [&] (auto k) { hipLaunchKernelGGL (gather_batch_kernel<decltype (k)::value>, dim3 (bt_grid (n * K)), dim3 (BT_THREADS), 0, st, perm, in, out, n, 1); });
 }
 void launch_gather_interleave (int K, const int *perm, const double *const *src, double *out, int64_t n, hipStream_t st, const double *scale)
 {
    BatchPtrs P;
    for (int k = 0; k < NKP_BATCH_MAX; k++) P.p[k] = k < K ? src[k] : nullptr;
    if (n <= 0) return;
-   if (scale) BT_K (gather_interleave_scaled_kernel, dim3 (bt_grid (n)), perm, P, scale, out, n);
-   else BT_K (gather_interleave_kernel, dim3 (bt_grid (n)), perm, P, out, n);
+   if (scale) with_k (K, [&] (auto k) { hipLaunchKernelGGL (gather_interleave_scaled_kernel<decltype (k)::value>, dim3 (bt_grid (n)), dim3 (BT_THREADS), 0, st, perm, P, scale, out, n); });
+   else with_k (K, [&] (auto k) { hipLaunchKernelGGL (gather_interleave_kernel<decltype (k)::value>, dim3 (bt_grid (n)), dim3 (BT_THREADS), 0, st, perm, P, out, n); });
 }
 void launch_add_split (int K, const double *p, double *z, double *const *dst, int64_t n, hipStream_t st)
 {
    BatchOutPtrs P;
    for (int k = 0; k < NKP_BATCH_MAX; k++) P.p[k] = k < K ? dst[k] : nullptr;
-   if (n > 0) BT_K (add_split_kernel, dim3 (bt_grid (n)), p, z, P, n);
+   if (n > 0) with_k (K, [&] (auto k) { hipLaunchKernelGGL (add_split_kernel<decltype (k)::value>, dim3 (bt_grid (n)), dim3 (BT_THREADS), 0, st, p, z, P, n); });
 }
 void launch_scatter_split (int K, const int *perm, const double *in, double *z, double *const *dst, int64_t n, hipStream_t st)
 {
    BatchOutPtrs P;
    for (int k = 0; k < NKP_BATCH_MAX; k++) P.p[k] = k < K ? dst[k] : nullptr;
-   if (n > 0) BT_K (scatter_split_kernel, dim3 (bt_grid (n)), perm, in, z, P, n);
+   if (n > 0) with_k (K, [&] (auto k) { hipLaunchKernelGGL (scatter_split_kernel<decltype (k)::value>, dim3 (bt_grid (n)), dim3 (BT_THREADS), 0, st, perm, in, z, P, n); });
 }
 void launch_pack_rows_split (int K, const int *idx, const double *const *src, double *out, int64_t nrows, hipStream_t st)
 {
    BatchPtrs P;
    for (int k = 0; k < NKP_BATCH_MAX; k++) P.p[k] = k < K ? src[k] : nullptr;
-   if (nrows > 0) BT_K (pack_rows_split_kernel, dim3 (bt_grid (nrows)), idx, P, out, nrows);
+   if (nrows > 0) with_k (K, [&] (auto k) { hipLaunchKernelGGL (pack_rows_split_kernel<decltype (k)::value>, dim3 (bt_grid (nrows)), dim3 (BT_THREADS), 0, st, idx, P, out, nrows); });
 }
 void launch_gather_interleave_ext (int K, const int *perm, const double *const *src, const double *halo, const int *sel, int64_t n_own, double *out, int64_t n,
                                    hipStream_t st)
 {
    BatchPtrs P;
    for (int k = 0; k < NKP_BATCH_MAX; k++) P.p[k] = k < K ? src[k] : nullptr;
-   if (n > 0) BT_K (gather_interleave_ext_kernel, dim3 (bt_grid (n)), perm, P, halo, sel, n_own, out, n);
+   if (n > 0) with_k (K, [&] (auto k) { hipLaunchKernelGGL (gather_interleave_ext_kernel<decltype (k)::value>, dim3 (bt_grid (n)), dim3 (BT_THREADS), 0, st, perm, P, halo, sel, n_own, out, n); });
 }
 void launch_gather_interleave_ext_block (int K, const int *perm, const double *const *src, const double *recv, int64_t n_own, double *out, int64_t n, hipStream_t st)
 {
    BatchPtrs P;
    for (int k = 0; k < NKP_BATCH_MAX; k++) P.p[k] = k < K ? src[k] : nullptr;
-   if (n > 0) BT_K (gather_interleave_ext_block_kernel, dim3 (bt_grid (n)), perm, P, recv, n_own, out, n);
+   if (n > 0) with_k (K, [&] (auto k) { hipLaunchKernelGGL (gather_interleave_ext_block_kernel<decltype (k)::value>, dim3 (bt_grid (n)), dim3 (BT_THREADS), 0, st, perm, P, recv, n_own, out, n); });
 }
 void launch_scatter_split_own (int K, const int *perm, const double *in, double *z, double *const *dst, int64_t n_own, int64_t n, hipStream_t st)
 {
    BatchOutPtrs P;
    for (int k = 0; k < NKP_BATCH_MAX; k++) P.p[k] = k < K ? dst[k] : nullptr;
-   if (n > 0) BT_K (scatter_split_own_kernel, dim3 (bt_grid (n)), perm, in, z, P, n_own, n);
+   if (n > 0) with_k (K, [&] (auto k) { hipLaunchKernelGGL (scatter_split_own_kernel<decltype (k)::value>, dim3 (bt_grid (n)), dim3 (BT_THREADS), 0, st, perm, in, z, P, n_own, n); });
 }
 void launch_dense_matvec_batch (int K, const double *Minv, const double *x, double *y, int n, hipStream_t st)
 {
-   if (n > 0) BT_K (dense_matvec_batch_kernel, dim3 ((n + BT_WAVES - 1) / BT_WAVES), Minv, x, y, n);
+   if (n > 0) with_k (K, [&] (auto k) { hipLaunchKernelGGL (dense_matvec_batch_kernel<decltype (k)::value>, dim3 ((n + BT_WAVES - 1) / BT_WAVES), dim3 (BT_THREADS), 0, st, Minv, x, y, n); });
 }
 
 // ---------------------------------------------------------------- water columns, one per wave, K columns of right-hand sides
@@ -885,36 +862,33 @@ static inline dim3 bt_wave_grid (int nblk) { return dim3 ((nblk + BT_WAVES - 1) 
 void launch_colblock_apply_wave_batch (int K, const ColBlocksDev &B, int b0, int b1, const double *r, double *z, int accumulate, int r32, hipStream_t st)
 {
    if (b1 <= b0) return;
-   const int rpl = B.max_len <= NKP_WAVE ? 1 : 2;
-#define CW_GO(PP, RR, R32_, K_) hipLaunchKernelGGL ((colblock_apply_wave_batch_kernel<PP, RR, R32_, K_>), bt_wave_grid (b1 - b0), dim3 (BT_THREADS), 0, st, \
-                                                     B.blk_start, b0, b1, B.n, B.fac, r, z, accumulate)
-#define CW_K(PP, RR, R32_) do { if (K == 2) CW_GO (PP, RR, R32_, 2); else if (K == 4) CW_GO (PP, RR, R32_, 4); else CW_GO (PP, RR, R32_, 8); } while (0)
-#define CW_R(PP, RR) do { if (r32) CW_K (PP, RR, true); else CW_K (PP, RR, false); } while (0)
-   if (B.P == 1) { if (rpl == 1) CW_R (1, 1); else CW_R (1, 2); }
-   else if (B.P == 2) { if (rpl == 1) CW_R (2, 1); else CW_R (2, 2); }
-   else { if (rpl == 1) CW_R (4, 1); else CW_R (4, 2); }
-#undef CW_R
-#undef CW_K
-#undef CW_GO
+   with_band_rows (B, [&] (auto p, auto rpl) {
+      with_bool (r32, [&] (auto r32_) {
+         with_k (K, [&] (auto k) {
+            hipLaunchKernelGGL ((colblock_apply_wave_batch_kernel<decltype (p)::value, decltype (rpl)::value, decltype (r32_)::value, decltype (k)::value>),
+                                bt_wave_grid (b1 - b0), dim3 (BT_THREADS), 0, st, B.blk_start, b0, b1, B.n, B.fac, r, z, accumulate);
+         });
+      });
+   });
 }
 
 void launch_gs_wave_batch (int K, const CsrDev &L, const ColBlocksDev &B, int b0, int b1, const double *xa, const double *xb, int split, const double *b, double *xout,
                            int r32, hipStream_t st)
 {
    if (b1 <= b0) return;
-   const int rpl = B.max_len <= NKP_WAVE ? 1 : 2;
-#define GW_GO(PP, RR, VT_, R32_, K_, VAL_) do { const size_t lds_ = (size_t) BT_WAVES * BGS_CAP * (sizeof (int) + sizeof (VT_));                                   \
-                                                static bool opted_ = false;                                                                                             \
-                                                if (lds_ > 48 * 1024 && !opted_) { (void) hipFuncSetAttribute ((const void *) gs_wave_batch_kernel<PP, RR, VT_, R32_, K_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds_); opted_ = true; } \
-                                                hipLaunchKernelGGL ((gs_wave_batch_kernel<PP, RR, VT_, R32_, K_>), bt_wave_grid (b1 - b0), dim3 (BT_THREADS), lds_, st, \
-                                                                    L.rowptr, L.colind, VAL_, B.blk_start, b0, b1, B.n, B.fac, xa, xb, split, b, xout, reinterpret_cast<const int4 *> (B.wave_desc)); } while (0)
-#define GW_K(PP, RR, VT_, R32_, VAL_) do { if (K == 2) GW_GO (PP, RR, VT_, R32_, 2, VAL_); else if (K == 4) GW_GO (PP, RR, VT_, R32_, 4, VAL_); else GW_GO (PP, RR, VT_, R32_, 8, VAL_); } while (0)
-#define GW_PR(PP, RR) do { if (L.valf) { if (r32) GW_K (PP, RR, float, true, L.valf); else GW_K (PP, RR, float, false, L.valf); } \
-                           else { if (r32) GW_K (PP, RR, double, true, L.val); else GW_K (PP, RR, double, false, L.val); } } while (0)
-   if (B.P == 1) { if (rpl == 1) GW_PR (1, 1); else GW_PR (1, 2); }
-   else if (B.P == 2) { if (rpl == 1) GW_PR (2, 1); else GW_PR (2, 2); }
-   else { if (rpl == 1) GW_PR (4, 1); else GW_PR (4, 2); }
-#undef GW_PR
-#undef GW_K
-#undef GW_GO
+   with_band_rows (B, [&] (auto p, auto rpl) {
+      with_storage (L.valf, L.val, [&] (auto val) {
+         with_bool (r32, [&] (auto r32_) {
+            with_k (K, [&] (auto k) {
+               const auto kernel = gs_wave_batch_kernel<decltype (p)::value, decltype (rpl)::value, elem_t<decltype (val)>, decltype (r32_)::value, decltype (k)::value>;
+               const size_t lds = (size_t) BT_WAVES * BGS_CAP * (sizeof (int) + sizeof (*val));
+               // more than 48 KB of dynamic LDS needs an opt-in: once per instantiation (this lambda's body is one), before its first launch
+               static bool opted = false;
+               if (lds > 48 * 1024 && !opted) { (void) hipFuncSetAttribute ((const void *) kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds); opted = true; }
+               hipLaunchKernelGGL (kernel, bt_wave_grid (b1 - b0), dim3 (BT_THREADS), lds, st,
+                                   L.rowptr, L.colind, val, B.blk_start, b0, b1, B.n, B.fac, xa, xb, split, b, xout, reinterpret_cast<const int4 *> (B.wave_desc));
+            });
+         });
+      });
+   });
 }

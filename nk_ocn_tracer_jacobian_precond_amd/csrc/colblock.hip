@@ -398,48 +398,42 @@ void launch_colblock_measure (const CsrDev &A, const ColBlocksDev &B, int *d_out
                        A.rowptr, A.colind, A.val, B.blk_start, B.nblk, d_out3);
 }
 
-#define CB_DISPATCH(KERNEL, ...) CB_DISPATCH_N (KERNEL, B.nblk, __VA_ARGS__)
-#define CB_DISPATCH_N(KERNEL, NB, ...)                                                             \
-   do {                                                                                           \
-      const int rpl = B.max_len <= NKP_WAVE ? 1 : 2;                                              \
-      if (B.P == 1 && rpl == 1) hipLaunchKernelGGL ((KERNEL<1, 1>), cb_grid (NB), dim3 (CB_THREADS), 0, st, __VA_ARGS__); \
-      else if (B.P == 1) hipLaunchKernelGGL ((KERNEL<1, 2>), cb_grid (NB), dim3 (CB_THREADS), 0, st, __VA_ARGS__);        \
-      else if (B.P == 2 && rpl == 1) hipLaunchKernelGGL ((KERNEL<2, 1>), cb_grid (NB), dim3 (CB_THREADS), 0, st, __VA_ARGS__); \
-      else if (B.P == 2) hipLaunchKernelGGL ((KERNEL<2, 2>), cb_grid (NB), dim3 (CB_THREADS), 0, st, __VA_ARGS__);        \
-      else if (rpl == 1) hipLaunchKernelGGL ((KERNEL<4, 1>), cb_grid (NB), dim3 (CB_THREADS), 0, st, __VA_ARGS__);        \
-      else hipLaunchKernelGGL ((KERNEL<4, 2>), cb_grid (NB), dim3 (CB_THREADS), 0, st, __VA_ARGS__);                      \
-   } while (0)
-
 void launch_colblock_factor (const CsrDev &A, ColBlocksDev &B, int *d_status, hipStream_t st)
 {
    if (B.nblk == 0) return;
    int *d_dropped = d_status + 1;
-   CB_DISPATCH (colblock_factor_kernel, A.rowptr, A.colind, A.val, B.blk_start, B.nblk, B.n, B.fac, d_status, d_dropped);
+   with_band_rows (B, [&] (auto p, auto rpl) {
+      hipLaunchKernelGGL ((colblock_factor_kernel<decltype (p)::value, decltype (rpl)::value>), cb_grid (B.nblk), dim3 (CB_THREADS), 0, st,
+                          A.rowptr, A.colind, A.val, B.blk_start, B.nblk, B.n, B.fac, d_status, d_dropped);
+   });
+}
+
+// blocks [b0, b1) only; accumulate: z_blk += M_blk^-1 r_blk, else z_blk = M_blk^-1 r_blk; r32: the factors rounded to f32 on
+// load (multilevel cycle with f32 storage)
+static void colblock_apply_blocks (const ColBlocksDev &B, int b0, int b1, const double *r, double *z, int accumulate, bool r32, hipStream_t st)
+{
+   if (b1 <= b0) return;
+   with_band_rows (B, [&] (auto p, auto rpl) {
+      with_bool (r32, [&] (auto r32_) {
+         hipLaunchKernelGGL ((colblock_apply_kernel<decltype (p)::value, decltype (rpl)::value, decltype (r32_)::value>), cb_grid (b1 - b0), dim3 (CB_THREADS), 0, st,
+                             B.blk_start, b0, b1, B.n, B.fac, r, z, accumulate);
+      });
+   });
 }
 
 void launch_colblock_apply (const ColBlocksDev &B, const double *r, double *z, hipStream_t st)
 {
-   if (B.nblk == 0) return;
-   CB_DISPATCH (colblock_apply_kernel, B.blk_start, 0, B.nblk, B.n, B.fac, r, z, 0);
+   colblock_apply_blocks (B, 0, B.nblk, r, z, 0, false, st);
 }
 
 void launch_colblock_apply_range (const ColBlocksDev &B, int b0, int b1, const double *r, double *z, int accumulate, hipStream_t st)
 {
-   if (b1 <= b0) return;
-   CB_DISPATCH_N (colblock_apply_kernel, b1 - b0, B.blk_start, b0, b1, B.n, B.fac, r, z, accumulate);
+   colblock_apply_blocks (B, b0, b1, r, z, accumulate, false, st);
 }
 
-// same with the factors rounded to f32 on load (multilevel cycle with f32 storage)
 void launch_colblock_apply_range_r32 (const ColBlocksDev &B, int b0, int b1, const double *r, double *z, int accumulate, hipStream_t st)
 {
-   if (b1 <= b0) return;
-   const int rpl = B.max_len <= NKP_WAVE ? 1 : 2;
-   const dim3 grid = cb_grid (b1 - b0);
-#define R32_GO(PP, RR) hipLaunchKernelGGL ((colblock_apply_kernel<PP, RR, true>), grid, dim3 (CB_THREADS), 0, st, B.blk_start, b0, b1, B.n, B.fac, r, z, accumulate)
-   if (B.P == 1) { if (rpl == 1) R32_GO (1, 1); else R32_GO (1, 2); }
-   else if (B.P == 2) { if (rpl == 1) R32_GO (2, 1); else R32_GO (2, 2); }
-   else { if (rpl == 1) R32_GO (4, 1); else R32_GO (4, 2); }
-#undef R32_GO
+   colblock_apply_blocks (B, b0, b1, r, z, accumulate, true, st);
 }
 
 __global__ __launch_bounds__ (CB_THREADS)
@@ -464,20 +458,19 @@ void launch_gs_wave (const CsrDev &L, const ColBlocksDev &B, int b0, int b1, con
                      int r32, hipStream_t st)
 {
    if (b1 <= b0) return;
-   const int rpl = B.max_len <= NKP_WAVE ? 1 : 2;
-   const dim3 grid = cb_grid (b1 - b0);
-#define GSW_GO(PP, RR, VT_, R32_, VAL_) do { const size_t lds_ = (size_t) CB_WAVES * GSW_CAP * (sizeof (int) + sizeof (VT_));                              \
-                                             static bool opted_ = false;                                                                                        \
-                                             if (lds_ > 48 * 1024 && !opted_) { (void) hipFuncSetAttribute ((const void *) gs_wave_kernel<PP, RR, VT_, R32_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds_); opted_ = true; } \
-                                             hipLaunchKernelGGL ((gs_wave_kernel<PP, RR, VT_, R32_>), grid, dim3 (CB_THREADS), lds_, st, L.rowptr, L.colind, VAL_, \
-                                                                 B.blk_start, b0, b1, B.n, B.fac, xa, xb, split, b, xout, reinterpret_cast<const int4 *> (B.wave_desc)); } while (0)
-#define GSW_PR(PP, RR) do { if (L.valf) { if (r32) GSW_GO (PP, RR, float, true, L.valf); else GSW_GO (PP, RR, float, false, L.valf); } \
-                            else { if (r32) GSW_GO (PP, RR, double, true, L.val); else GSW_GO (PP, RR, double, false, L.val); } } while (0)
-   if (B.P == 1) { if (rpl == 1) GSW_PR (1, 1); else GSW_PR (1, 2); }
-   else if (B.P == 2) { if (rpl == 1) GSW_PR (2, 1); else GSW_PR (2, 2); }
-   else { if (rpl == 1) GSW_PR (4, 1); else GSW_PR (4, 2); }
-#undef GSW_PR
-#undef GSW_GO
+   with_band_rows (B, [&] (auto p, auto rpl) {
+      with_storage (L.valf, L.val, [&] (auto val) {
+         with_bool (r32, [&] (auto r32_) {
+            const auto kernel = gs_wave_kernel<decltype (p)::value, decltype (rpl)::value, elem_t<decltype (val)>, decltype (r32_)::value>;
+            const size_t lds = (size_t) CB_WAVES * GSW_CAP * (sizeof (int) + sizeof (*val));
+            // more than 48 KB of dynamic LDS needs an opt-in: once per instantiation (this lambda's body is one), before its first launch
+            static bool opted = false;
+            if (lds > 48 * 1024 && !opted) { (void) hipFuncSetAttribute ((const void *) kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds); opted = true; }
+            hipLaunchKernelGGL (kernel, cb_grid (b1 - b0), dim3 (CB_THREADS), lds, st, L.rowptr, L.colind, val,
+                                B.blk_start, b0, b1, B.n, B.fac, xa, xb, split, b, xout, reinterpret_cast<const int4 *> (B.wave_desc));
+         });
+      });
+   });
 }
 
 // ================================================================ lane-per-column apply
@@ -522,8 +515,15 @@ void colblock_transpose_kernel (const int *__restrict__ blk_start, const int *__
       }
 }
 
-template <int P, int MAXL, class FT>
-__global__ __launch_bounds__ (NKP_WAVE)
+// WPE is the least number of waves per SIMD the register allocation has to leave room for; 1 asks for nothing.  Only the
+// 80-level instantiations (65-80 rows per column) are launched with 3, as <*, 80, *, 3>: left alone the compiler spends all
+// 256 VGPRs on hoisted factor reads and ONE wave per SIMD remains -- 0.25 degree x 80: 1120 us per colour of the fine level
+// (1 TB/s); capped it spills 56 registers of a kernel in which 8 lanes compute and runs three waves per SIMD: 619 us, whole
+// cycle 32.8 -> 24.9 ms, same bits.  The cap HURTS the 64-level kernel (3 degree: 16.1 -> 25.5 us) and the streamed kernel
+// (26 -> 94 us), so no other instantiation gets it.  The attribute takes the template parameter, so the text exists once and
+// <*, *, *, 1> compiles to what the kernel without the attribute does.
+template <int P, int MAXL, class FT, int WPE = 1>
+__global__ __launch_bounds__ (NKP_WAVE) __attribute__ ((amdgpu_waves_per_eu (WPE)))
 void colblock_apply_lanes_kernel (const int *__restrict__ blk_start, const int *__restrict__ grp_b0, const int *__restrict__ grp_nb,
                                   const int *__restrict__ grp_maxlen, const long long *__restrict__ grp_base, int g_first,
                                   const FT *__restrict__ fac_t, const double *__restrict__ rhs, double *__restrict__ z, int accumulate,
@@ -640,132 +640,6 @@ void colblock_apply_lanes_kernel (const int *__restrict__ blk_start, const int *
    } else
       for (int i = lane; i < nrows; i += NKP_WAVE) z[(int64_t) R0 + i] = lds[LDS_PAD (i)];
 }
-
-// The same kernel text once more for 80-level grids (65-80 rows per column), capped at three waves per SIMD: left alone
-// the compiler spends all 256 VGPRs on hoisted factor reads and ONE wave per SIMD remains -- 0.25 degree x 80: 1120 us per
-// colour of the fine level (1 TB/s); capped it spills 56 registers of a kernel in which 8 lanes compute and runs three
-// waves per SIMD: 619 us, whole cycle 32.8 -> 24.9 ms, same bits.  The cap HURTS the 64-level kernel (3 degree: 16.1 -> 25.5
-// us) and the streamed kernel (26 -> 94 us), so it is confined to this instantiation.  (A shared __device__ body would
-// be tidier than a second copy of the text, but inlining it changed the register allocation of the other kernels.)
-template <int P, int MAXL, class FT>
-__global__ __launch_bounds__ (NKP_WAVE) __attribute__ ((amdgpu_waves_per_eu (3)))
-void colblock_apply_lanes_kernel_w3 (const int *__restrict__ blk_start, const int *__restrict__ grp_b0, const int *__restrict__ grp_nb,
-                                  const int *__restrict__ grp_maxlen, const long long *__restrict__ grp_base, int g_first,
-                                  const FT *__restrict__ fac_t, const double *__restrict__ rhs, double *__restrict__ z, int accumulate,
-                                  int gw, int rhs_slots, const int *__restrict__ grp_row0, const int *__restrict__ col_slot, int ngrp)
-{
-   extern __shared__ double lds[];            // [rhs_slots] staged right-hand side | [(2P+1)*ml*gw] the group's factors
-   const int g = blockIdx.x + g_first;
-   const int lane = threadIdx.x;
-   // every index this wave needs depends on g alone: one round trip, not a chain through blk_start
-   const int nb = grp_nb[g], ml = grp_maxlen[g];
-   const int R0 = grp_row0[g], nrows = grp_row0[ngrp + g];
-   int s_pre = 0, len_pre = 0;
-   if (lane < gw) { s_pre = col_slot[g * gw + lane]; len_pre = col_slot[(ngrp + g) * gw + lane]; }
-   FT *fl = reinterpret_cast<FT *> (lds + rhs_slots);
-   // the accumulate target is requested together with the right-hand side
-   double tz[8];
-#pragma unroll
-   for (int u = 0; u < 8; u++) {
-      const int i = lane + u * NKP_WAVE;
-      tz[u] = (accumulate && i < nrows) ? z[(int64_t) R0 + i] : 0.0;
-   }
-   // bulk, fully coalesced staging: every load is independent, so the whole group is in flight at once
-   {
-      // 16-byte units of the group's factor block (ml*gw is a multiple of 64, so this is exact for f32 too)
-      const double2 *src = reinterpret_cast<const double2 *> (fac_t + grp_base[g]);
-      double2 *dst = reinterpret_cast<double2 *> (fl);
-      const int cnt2 = (int) (((size_t) (2 * P + 1) * ml * gw * sizeof (FT)) >> 4);
-      // the right-hand side and a batch of 20 factor loads per lane are all in flight before the first LDS
-      // store waits on them (a group of 8 columns x 64 levels x 5 diagonals is exactly one batch)
-      double tr[8];
-#pragma unroll
-      for (int u = 0; u < 8; u++) {
-         const int i = lane + u * NKP_WAVE;
-         tr[u] = (i < nrows) ? rhs[(int64_t) R0 + i] : 0.0;
-      }
-      constexpr int BATCH = sizeof (FT) == 4 ? 10 : 20;      // 16-byte loads per lane: one batch covers 8 x 64 x 5 factors
-      for (int i0 = lane; i0 < cnt2; i0 += BATCH * NKP_WAVE) {
-         double2 t[BATCH];
-#pragma unroll
-         for (int u = 0; u < BATCH; u++) {
-            const int i = i0 + u * NKP_WAVE;
-            t[u] = (i < cnt2) ? src[i] : make_double2 (0.0, 0.0);
-         }
-#pragma unroll
-         for (int u = 0; u < BATCH; u++) {
-            const int i = i0 + u * NKP_WAVE;
-            if (i < cnt2) dst[i] = t[u];
-         }
-      }
-#pragma unroll
-      for (int u = 0; u < 8; u++) {
-         const int i = lane + u * NKP_WAVE;
-         if (i < nrows) lds[LDS_PAD (i)] = tr[u];
-      }
-   }
-   for (int i = lane + 8 * NKP_WAVE; i < nrows; i += NKP_WAVE) lds[LDS_PAD (i)] = rhs[(int64_t) R0 + i];
-   __syncthreads ();
-
-   if (lane < nb) {
-      const int s = s_pre;
-      const int len = len_pre;
-      const FT *ft = fl + lane;
-      const int dstride = ml * gw;
-      // the whole column lives in registers: no LDS write sits between two LDS reads, so the compiler
-      // can keep the (read-only) factor reads in flight ahead of the dependent arithmetic
-      double v[MAXL];
-#pragma unroll
-      for (int k = 0; k < MAXL; k++) v[k] = (k < len) ? lds[LDS_PAD (s + k)] : 0.0;
-      // forward: y_k = ((r_k - l(k,k-P) y_{k-P}) ... - l(k,k-1) y_{k-1})   (far diagonal first, like the column sweep)
-      // steps k >= len need no predicate: their factors are zero-padded, so they compute 0 - 0*x = 0;
-      // the only branch left is wave-uniform (k < ml), which keeps the LDS reads hoistable
-      // ml is a multiple of 8 (layout builder), so the only branch is one wave-uniform test per 8 steps and
-      // the 8*P factor reads of a chunk are issued together, ahead of the dependent arithmetic
-#pragma unroll
-      for (int k0 = 0; k0 < MAXL; k0 += 8) {
-         if (k0 < ml) {
-#pragma unroll
-            for (int k = k0; k < k0 + 8; k++) {
-               double y = v[k];
-#pragma unroll
-               for (int q = P; q >= 1; q--)
-                  if (k - q >= 0) y -= (double) ft[(P - q) * dstride + k * gw] * v[k - q];
-               v[k] = y;
-            }
-         }
-      }
-      // backward: x_k = (((y_k - u(k,k+P) x_{k+P}) ... - u(k,k+1) x_{k+1}) * (1/u_kk)
-#pragma unroll
-      for (int k0 = MAXL - 8; k0 >= 0; k0 -= 8) {
-         if (k0 < ml) {
-#pragma unroll
-            for (int k = k0 + 7; k >= k0; k--) {
-               double x = v[k];
-#pragma unroll
-               for (int q = P; q >= 1; q--)
-                  if (k + q < MAXL) x -= (double) ft[(P + q) * dstride + k * gw] * v[k + q];
-               x *= (double) ft[P * dstride + k * gw];
-               v[k] = x;
-            }
-         }
-      }
-#pragma unroll
-      for (int k = 0; k < MAXL; k++)
-         if (k < len) lds[LDS_PAD (s + k)] = v[k];
-   }
-   __syncthreads ();
-   if (accumulate) {
-#pragma unroll
-      for (int u = 0; u < 8; u++) {
-         const int i = lane + u * NKP_WAVE;
-         if (i < nrows) z[(int64_t) R0 + i] = tz[u] + lds[LDS_PAD (i)];
-      }
-      for (int i = lane + 8 * NKP_WAVE; i < nrows; i += NKP_WAVE) z[(int64_t) R0 + i] += lds[LDS_PAD (i)];
-   } else
-      for (int i = lane; i < nrows; i += NKP_WAVE) z[(int64_t) R0 + i] = lds[LDS_PAD (i)];
-}
-
 
 // ================================================================ lane-per-column apply, 64 columns per wave, factors streamed
 // The 8-columns-per-wave kernel above keeps 56 of 64 lanes idle during the substitution and stages the factors through
@@ -1201,6 +1075,11 @@ __device__ __forceinline__ void ldsp_finish (PackChunk<P> (&Bq)[NCH], double (&w
    ldsp_write_back<NCH, ACC> (Z, lds, z, R0, s, len, lane);
 }
 
+// first step of the chunk a packed kernel (ldspack, ldspack2, ldspack4) keeps in F[t] and in Bq[t], from the kernel's nch and CH;
+// undefined again behind the last of them
+#define LDSP_FWD_K0(t) (((t) < nch ? (t) : nch - 1) * CH)
+#define LDSP_BWD_K0(t) ((nch - 1 - (t) > 0 ? nch - 1 - (t) : 0) * CH)
+
 // LDS image: column l of the group at [l * LDSP_STRIDE, ...), LDSP_STRIDE = NCH * 16 + 1 doubles.  Odd stride: the 32 lanes of
 // a substitution step hit 32 different bank pairs; fixed stride: every LDS address of the sweeps is "lane base + constant",
 // no address arithmetic and no predicate (SQ counters of the first version: 21 VALU instructions per step, most of them
@@ -1235,8 +1114,6 @@ void colblock_apply_ldspack_kernel (const int *__restrict__ grp_nb, const int *_
    // The factor loads are unconditional so that the kernel is one straight line the static schedule can be written into: a
    // group with fewer than NCH chunks requests its last chunk again (an L2 hit) and skips the steps.
    // F[c] = forward chunk min (c, nch - 1);  Bq[j] = backward chunk max (nch - 1 - j, 0)
-#define LDSP_FWD_K0(t) (((t) < nch ? (t) : nch - 1) * CH)
-#define LDSP_BWD_K0(t) ((nch - 1 - (t) > 0 ? nch - 1 - (t) : 0) * CH)
    PackChunk<P> F[NCH], Bq[NCH];
    PackRows<NCH> T;
    // the fences keep the requests in this order: left alone, the compiler moves the factor loads to their first use (behind
@@ -1296,8 +1173,6 @@ void colblock_apply_ldspack_kernel (const int *__restrict__ grp_nb, const int *_
    // waits for a chunk with the count that is right when nothing was requested behind it, and that drains the target
    if (accumulate) ldsp_finish<P, NCH, true, decltype (S)> (Bq, w, f4, mlq, nch, lds, z, R0, s, len, lane);
    else ldsp_finish<P, NCH, false, decltype (S)> (Bq, w, f4, mlq, nch, lds, z, R0, s, len, lane);
-#undef LDSP_FWD_K0
-#undef LDSP_BWD_K0
 }
 
 // The same kernel on TWO right-hand sides of a K-interleaved batch (batch.hip): lanes 0-31 run the columns on system k0, lanes
@@ -1321,8 +1196,6 @@ void colblock_apply_ldspack2_kernel (const int *__restrict__ grp_maxlen, const l
    const int cl = lane & (gw - 1);
    const int s = col_slot[g * gw + cl], len = col_slot[(ngrp + g) * gw + cl];
    const float4 *f4 = reinterpret_cast<const float4 *> (fac_t + grp_base[g]) + cl;
-#define LDSP_FWD_K0(t) (((t) < nch ? (t) : nch - 1) * CH)
-#define LDSP_BWD_K0(t) ((nch - 1 - (t) > 0 ? nch - 1 - (t) : 0) * CH)
    PackChunk<P> F[NCH], Bq[NCH];
 #pragma unroll
    for (int t = 0; t < NCH; t++)
@@ -1375,8 +1248,6 @@ void colblock_apply_ldspack2_kernel (const int *__restrict__ grp_maxlen, const l
             if (t >= (j ? S.b_after_b[j - 1] : S.b_after_f[NCH - 1]) && t < S.b_after_b[j]) ldsp_load_bwd<P> (Bq[t], f4, mlq, LDSP_BWD_K0 (t), gw);
       }
    }
-#undef LDSP_FWD_K0
-#undef LDSP_BWD_K0
    __syncthreads ();
 #pragma unroll
    for (int c0 = 0; c0 < gw; c0 += 8) {
@@ -1585,8 +1456,8 @@ int colblock_build_lane_layout (ColBlocksDev &B, const int *h_blk_start, const i
       LDS_OPT_IN (1, 64); LDS_OPT_IN (2, 64); LDS_OPT_IN (4, 64); LDS_OPT_IN (1, 128); LDS_OPT_IN (2, 128); LDS_OPT_IN (4, 128);
 #undef LDS_OPT_IN
 #define LDS_OPT_IN(PP, ML)                                                                                                              \
-      (void) hipFuncSetAttribute ((const void *) colblock_apply_lanes_kernel_w3<PP, ML, double>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes); \
-      (void) hipFuncSetAttribute ((const void *) colblock_apply_lanes_kernel_w3<PP, ML, float>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes)
+      (void) hipFuncSetAttribute ((const void *) colblock_apply_lanes_kernel<PP, ML, double, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes); \
+      (void) hipFuncSetAttribute ((const void *) colblock_apply_lanes_kernel<PP, ML, float, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes)
       LDS_OPT_IN (1, 80); LDS_OPT_IN (2, 80); LDS_OPT_IN (4, 80);
 #undef LDS_OPT_IN
 #define LDS_OPT_IN(PP, ML)                                                                                                              \
@@ -1908,127 +1779,77 @@ int launch_gs_fused (const CsrDev &L, const ColBlocksDev &B, int g0, int g1, con
    static bool opted = false;
    if (!opted) {
       opted = true;
-#define GS_OPT_IN(PP)                                                                                                                    \
-      (void) hipFuncSetAttribute ((const void *) gs_fused_kernel<PP, float, float>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);   \
-      (void) hipFuncSetAttribute ((const void *) gs_fused_kernel<PP, double, double>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024)
-      GS_OPT_IN (1); GS_OPT_IN (2); GS_OPT_IN (4);
-#undef GS_OPT_IN
+      for (int P : { 1, 2, 4 })      // all six instantiations
+         with_band (P, [] (auto p) {
+            (void) hipFuncSetAttribute ((const void *) gs_fused_kernel<decltype (p)::value, float, float>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
+            (void) hipFuncSetAttribute ((const void *) gs_fused_kernel<decltype (p)::value, double, double>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
+         });
    }
-#define GS_LAUNCH(PP)                                                                                                                                       \
-   do {                                                                                                                                                     \
-      if (B.fac_tf && L.valf)                                                                                                                               \
-         hipLaunchKernelGGL ((gs_fused_kernel<PP, float, float>), dim3 (g1 - g0), dim3 (GS_THREADS), (size_t) B.gs_lds_bytes, st, L.rowptr, L.colind, L.valf, \
-                             B.grp_nb, B.grp_maxlen, B.grp_base, g0, B.fac_tf, B.gw, B.rhs_slots, B.grp_row0, B.col_slot, B.ngrp, B.gs_rb_ptr, B.gs_rb,         \
-                             xa, xb, split, b, xout);                                                                                                        \
-      else if (B.fac_t && !L.valf)                                                                                                                          \
-         hipLaunchKernelGGL ((gs_fused_kernel<PP, double, double>), dim3 (g1 - g0), dim3 (GS_THREADS), (size_t) B.gs_lds_bytes, st, L.rowptr, L.colind, L.val, \
-                             B.grp_nb, B.grp_maxlen, B.grp_base, g0, B.fac_t, B.gw, B.rhs_slots, B.grp_row0, B.col_slot, B.ngrp, B.gs_rb_ptr, B.gs_rb,           \
-                             xa, xb, split, b, xout);                                                                                                        \
-      else return 1;                                                                                                                                        \
-   } while (0)
-   if (B.P == 1) GS_LAUNCH (1);
-   else if (B.P == 2) GS_LAUNCH (2);
-   else GS_LAUNCH (4);
-#undef GS_LAUNCH
-   return 0;
+   return with_band (B.P, [&] (auto p) {
+      // f32 factors go with an f32 level operator, f64 with f64
+      const auto launch = [&] (auto kernel, auto fac, auto val) {
+         hipLaunchKernelGGL (kernel, dim3 (g1 - g0), dim3 (GS_THREADS), (size_t) B.gs_lds_bytes, st, L.rowptr, L.colind, val,
+                             B.grp_nb, B.grp_maxlen, B.grp_base, g0, fac, B.gw, B.rhs_slots, B.grp_row0, B.col_slot, B.ngrp, B.gs_rb_ptr, B.gs_rb,
+                             xa, xb, split, b, xout);
+         return 0;
+      };
+      if (B.fac_tf && L.valf) return launch (gs_fused_kernel<decltype (p)::value, float, float>, B.fac_tf, L.valf);
+      if (B.fac_t && !L.valf) return launch (gs_fused_kernel<decltype (p)::value, double, double>, B.fac_t, L.val);
+      return 1;
+   });
 }
 
 void launch_colblock_apply_lanes (const ColBlocksDev &B, int g0, int g1, const double *r, double *z, int accumulate, hipStream_t st)
 {
    if (g1 <= g0) return;
    const size_t lds = (size_t) B.lds_doubles * sizeof (double);
-   {
-      // pipelined persistent variant: f32 factors, <= 64 levels, 8 columns per wave, band <= 2.  OFF unless
-      // NKP_COLPIPE_MIN=<groups> is set: it needs 256 VGPRs (one wave per SIMD), and with nothing to interleave the
-      // recurrence's own dependency stalls cost more than the hidden load latency saves -- 1 degree V-cycle 3.10 ms
-      // against 2.70 ms for the one-group-per-wave kernel (bit-identical results)
-      const int pipe_min = B.tune ? B.tune->col_pipe_min : 0;
-      if (B.fac_tf && B.max_len <= 64 && B.gw == 8 && B.P <= 2 && pipe_min > 0 && g1 - g0 >= pipe_min && lds <= 48 * 1024) {
-         int waves = 256 * 8;                         // two waves per SIMD fit the ~230 registers
-         if (waves > (g1 - g0 + 1) / 2) waves = (g1 - g0 + 1) / 2;
-         if (B.P == 1) hipLaunchKernelGGL ((colblock_apply_lanes_pipe_kernel<1>), dim3 (waves), dim3 (NKP_WAVE), lds, st, B.grp_nb, B.grp_maxlen, B.grp_base, g0, g1,
-                                           B.fac_tf, r, z, accumulate, B.rhs_slots, B.grp_row0, B.col_slot, B.ngrp);
-         else hipLaunchKernelGGL ((colblock_apply_lanes_pipe_kernel<2>), dim3 (waves), dim3 (NKP_WAVE), lds, st, B.grp_nb, B.grp_maxlen, B.grp_base, g0, g1,
-                                  B.fac_tf, r, z, accumulate, B.rhs_slots, B.grp_row0, B.col_slot, B.ngrp);
-         return;
-      }
-   }
-   if (B.ldsres == 2) {
-#define LDSP_LAUNCH(PP) do { if (B.max_len <= 64) hipLaunchKernelGGL ((colblock_apply_ldspack_kernel<PP, 4>), dim3 (g1 - g0), dim3 (NKP_WAVE), lds, st, B.grp_nb, B.grp_maxlen, \
-                                                                        B.grp_base, g0, B.fac_tf, r, z, accumulate, B.grp_row0, B.col_slot, B.ngrp);                                \
-                             else hipLaunchKernelGGL ((colblock_apply_ldspack_kernel<PP, 5>), dim3 (g1 - g0), dim3 (NKP_WAVE), lds, st, B.grp_nb, B.grp_maxlen,                      \
-                                                      B.grp_base, g0, B.fac_tf, r, z, accumulate, B.grp_row0, B.col_slot, B.ngrp); } while (0)
-      if (B.P == 1) LDSP_LAUNCH (1);
-      else if (B.P == 2) LDSP_LAUNCH (2);
-      else LDSP_LAUNCH (4);
-#undef LDSP_LAUNCH
+   // pipelined persistent variant: f32 factors, <= 64 levels, 8 columns per wave, band <= 2.  OFF unless
+   // NKP_COLPIPE_MIN=<groups> is set: it needs 256 VGPRs (one wave per SIMD), and with nothing to interleave the
+   // recurrence's own dependency stalls cost more than the hidden load latency saves -- 1 degree V-cycle 3.10 ms
+   // against 2.70 ms for the one-group-per-wave kernel (bit-identical results)
+   const int pipe_min = B.tune ? B.tune->col_pipe_min : 0;
+   if (B.fac_tf && B.max_len <= 64 && B.gw == 8 && B.P <= 2 && pipe_min > 0 && g1 - g0 >= pipe_min && lds <= 48 * 1024) {
+      int waves = 256 * 8;                         // two waves per SIMD fit the ~230 registers
+      if (waves > (g1 - g0 + 1) / 2) waves = (g1 - g0 + 1) / 2;
+      with_int<1, 2> (B.P, [&] (auto p) {
+         hipLaunchKernelGGL ((colblock_apply_lanes_pipe_kernel<decltype (p)::value>), dim3 (waves), dim3 (NKP_WAVE), lds, st, B.grp_nb, B.grp_maxlen, B.grp_base, g0, g1,
+                             B.fac_tf, r, z, accumulate, B.rhs_slots, B.grp_row0, B.col_slot, B.ngrp);
+      });
       return;
    }
-   if (B.ldsres) {
-#define LDSRES_LAUNCH2(PP, EE)                                                                                                                                    \
-      do {                                                                                                                                                       \
-         if (B.fac_tf) hipLaunchKernelGGL ((colblock_apply_ldsres_kernel<PP, float, NKP_LDSRES_CH, EE>), dim3 (g1 - g0), dim3 (NKP_WAVE), lds, st, B.grp_nb, B.grp_maxlen, \
-                                           B.grp_base, g0, B.fac_tf, r, z, accumulate, B.grp_row0, B.col_slot, B.ngrp);                                           \
-         else hipLaunchKernelGGL ((colblock_apply_ldsres_kernel<PP, double, NKP_LDSRES_CH, EE>), dim3 (g1 - g0), dim3 (NKP_WAVE), lds, st, B.grp_nb, B.grp_maxlen,         \
-                                  B.grp_base, g0, B.fac_t, r, z, accumulate, B.grp_row0, B.col_slot, B.ngrp);                                                    \
-      } while (0)
-      // col_ldsres_early = 1: first factor chunks and the accumulate target requested before the right-hand side is staged
-      // (247 instead of 172 VGPRs).  Measured twice on one box: 26.9 / 26.6 us per colour of the 1 degree fine level with it,
-      // 26.8 / 27.0 without -- no difference, so it stays off
-      const int early = B.tune ? B.tune->col_ldsres_early : 0;
-#define LDSRES_LAUNCH(PP) do { if (early) LDSRES_LAUNCH2 (PP, true); else LDSRES_LAUNCH2 (PP, false); } while (0)
-      if (B.P == 1) LDSRES_LAUNCH (1);
-      else if (B.P == 2) LDSRES_LAUNCH (2);
-      else LDSRES_LAUNCH (4);
-#undef LDSRES_LAUNCH
-#undef LDSRES_LAUNCH2
-      return;
-   }
-   if (B.stream) {
-#define STREAM_LAUNCH3(PP, ML, GG)                                                                                                                              \
-      do {                                                                                                                                                     \
-         if (B.fac_tf) hipLaunchKernelGGL ((colblock_apply_stream_kernel<PP, ML, float, GG>), dim3 (g1 - g0), dim3 (NKP_WAVE), lds, st, B.grp_nb, B.grp_maxlen,  \
-                                           B.grp_base, g0, B.fac_tf, r, z, accumulate, B.grp_row0, B.col_slot, B.ngrp);                                         \
-         else hipLaunchKernelGGL ((colblock_apply_stream_kernel<PP, ML, double, GG>), dim3 (g1 - g0), dim3 (NKP_WAVE), lds, st, B.grp_nb, B.grp_maxlen,          \
-                                  B.grp_base, g0, B.fac_t, r, z, accumulate, B.grp_row0, B.col_slot, B.ngrp);                                                  \
-      } while (0)
-#define STREAM_LAUNCH2(PP, ML) do { if (B.gw == 32) STREAM_LAUNCH3 (PP, ML, 32); else STREAM_LAUNCH3 (PP, ML, 64); } while (0)
-#define STREAM_LAUNCH(PP) do { if (B.max_len <= 64) STREAM_LAUNCH2 (PP, 64); else STREAM_LAUNCH2 (PP, 96); } while (0)
-      if (B.P == 1) STREAM_LAUNCH (1);
-      else if (B.P == 2) STREAM_LAUNCH (2);
-      else STREAM_LAUNCH (4);
-#undef STREAM_LAUNCH
-#undef STREAM_LAUNCH2
-#undef STREAM_LAUNCH3
-      return;
-   }
+   // col_ldsres_early = 1: first factor chunks and the accumulate target requested before the right-hand side is staged
+   // (247 instead of 172 VGPRs).  Measured twice on one box: 26.9 / 26.6 us per colour of the 1 degree fine level with it,
+   // 26.8 / 27.0 without -- no difference, so it stays off
+   const int early = B.tune ? B.tune->col_ldsres_early : 0;
    const int use_w3 = B.tune ? B.tune->col_w3 : 1;
-#define LANES_LAUNCH_W3(PP, ML)                                                                                                                                 \
-   do {                                                                                                                                                        \
-      if (B.fac_tf) hipLaunchKernelGGL ((colblock_apply_lanes_kernel_w3<PP, ML, float>), dim3 (g1 - g0), dim3 (NKP_WAVE), lds, st, B.blk_start, B.grp_b0, B.grp_nb, \
-                                        B.grp_maxlen, B.grp_base, g0, B.fac_tf, r, z, accumulate, B.gw, B.rhs_slots, B.grp_row0, B.col_slot, B.ngrp);             \
-      else hipLaunchKernelGGL ((colblock_apply_lanes_kernel_w3<PP, ML, double>), dim3 (g1 - g0), dim3 (NKP_WAVE), lds, st, B.blk_start, B.grp_b0, B.grp_nb,          \
-                               B.grp_maxlen, B.grp_base, g0, B.fac_t, r, z, accumulate, B.gw, B.rhs_slots, B.grp_row0, B.col_slot, B.ngrp);                       \
-   } while (0)
-#define LANES_LAUNCH(PP)                                                                                                   \
-   do {                                                                                                                    \
-      if (B.max_len <= 64) LANES_LAUNCH2 (PP, 64);                                                                         \
-      else if (B.max_len <= 80 && use_w3) LANES_LAUNCH_W3 (PP, 80);                                                        \
-      else LANES_LAUNCH2 (PP, 128);                                                                                        \
-   } while (0)
-#define LANES_LAUNCH2(PP, ML)                                                                                                                                   \
-   do {                                                                                                                                                        \
-      if (B.fac_tf) hipLaunchKernelGGL ((colblock_apply_lanes_kernel<PP, ML, float>), dim3 (g1 - g0), dim3 (NKP_WAVE), lds, st, B.blk_start, B.grp_b0, B.grp_nb, \
-                                        B.grp_maxlen, B.grp_base, g0, B.fac_tf, r, z, accumulate, B.gw, B.rhs_slots, B.grp_row0, B.col_slot, B.ngrp);             \
-      else hipLaunchKernelGGL ((colblock_apply_lanes_kernel<PP, ML, double>), dim3 (g1 - g0), dim3 (NKP_WAVE), lds, st, B.blk_start, B.grp_b0, B.grp_nb,          \
-                               B.grp_maxlen, B.grp_base, g0, B.fac_t, r, z, accumulate, B.gw, B.rhs_slots, B.grp_row0, B.col_slot, B.ngrp);                       \
-   } while (0)
-   if (B.P == 1) LANES_LAUNCH (1);
-   else if (B.P == 2) LANES_LAUNCH (2);
-   else LANES_LAUNCH (4);
-#undef LANES_LAUNCH
-#undef LANES_LAUNCH2
-#undef LANES_LAUNCH_W3
+   // the kernels that keep the factors out of LDS take one argument list
+   const auto streamed = [&] (auto kernel, auto fac) {
+      hipLaunchKernelGGL (kernel, dim3 (g1 - g0), dim3 (NKP_WAVE), lds, st, B.grp_nb, B.grp_maxlen, B.grp_base, g0, fac, r, z, accumulate, B.grp_row0, B.col_slot, B.ngrp);
+   };
+   with_band (B.P, [&] (auto p) {
+      constexpr int P = decltype (p)::value;
+      if (B.ldsres == 2)
+         with_int<4, 5> (B.max_len <= 64 ? 4 : 5, [&] (auto nch) { streamed (colblock_apply_ldspack_kernel<P, decltype (nch)::value>, (const float *) B.fac_tf); });
+      else
+         with_storage (B.fac_tf, B.fac_t, [&] (auto fac) {
+            using FT = elem_t<decltype (fac)>;
+            if (B.ldsres)
+               with_bool (early, [&] (auto e) { streamed (colblock_apply_ldsres_kernel<P, FT, NKP_LDSRES_CH, decltype (e)::value>, fac); });
+            else if (B.stream)
+               with_int<64, 96> (B.max_len <= 64 ? 64 : 96, [&] (auto ml) {
+                  with_int<32, 64> (B.gw, [&] (auto gw) { streamed (colblock_apply_stream_kernel<P, decltype (ml)::value, FT, decltype (gw)::value>, fac); });
+               });
+            else {
+               const auto lanes = [&] (auto ml, auto wpe) {
+                  hipLaunchKernelGGL ((colblock_apply_lanes_kernel<P, decltype (ml)::value, FT, decltype (wpe)::value>), dim3 (g1 - g0), dim3 (NKP_WAVE), lds, st,
+                                      B.blk_start, B.grp_b0, B.grp_nb, B.grp_maxlen, B.grp_base, g0, fac, r, z, accumulate, B.gw, B.rhs_slots, B.grp_row0, B.col_slot, B.ngrp);
+               };
+               if (B.max_len <= 64) lanes (int_tag<64> (), int_tag<1> ());
+               else if (B.max_len <= 80 && use_w3) lanes (int_tag<80> (), int_tag<3> ());
+               else lanes (int_tag<128> (), int_tag<1> ());
+            }
+         });
+   });
 }
 
 // FOUR right-hand sides in one launch: a wave takes 16 of a group's 32 columns (block 2 g + h = half h of group g) for all four
@@ -2055,8 +1876,6 @@ void colblock_apply_ldspack4_kernel (const int *__restrict__ grp_maxlen, const l
    const int cl = half * hw + (lane & (hw - 1));             // this lane's column within the group
    const int s = col_slot[g * gw + cl], len = col_slot[(ngrp + g) * gw + cl];
    const float4 *f4 = reinterpret_cast<const float4 *> (fac_t + grp_base[g]) + cl;
-#define LDSP_FWD_K0(t) (((t) < nch ? (t) : nch - 1) * CH)
-#define LDSP_BWD_K0(t) ((nch - 1 - (t) > 0 ? nch - 1 - (t) : 0) * CH)
    PackChunk<P> F[NCH], Bq[NCH];
 #pragma unroll
    for (int t = 0; t < NCH; t++)
@@ -2162,29 +1981,20 @@ int launch_colblock_apply_lanes_batch (int K, const ColBlocksDev &B, int g0, int
    if (g1 <= g0) return 0;
    const int nch = B.max_len <= 64 ? 4 : 5;
    const size_t lds = (size_t) 64 * (size_t) (nch * NKP_LDSRES_CH + 1) * sizeof (double);
-   if (K % 4 == 0) {
-      // one launch per four systems, two waves (16 columns each) per group
-      for (int k0 = 0; k0 < K; k0 += 4) {
-#define LDSP4_LAUNCH(PP) do { if (nch == 4) hipLaunchKernelGGL ((colblock_apply_ldspack4_kernel<PP, 4>), dim3 (2 * (g1 - g0)), dim3 (NKP_WAVE), lds, st, B.grp_maxlen, B.grp_base, g0, \
-                                                                 B.fac_tf, r, z, accumulate, B.grp_row0, B.col_slot, B.ngrp, K, k0);                                         \
-                              else hipLaunchKernelGGL ((colblock_apply_ldspack4_kernel<PP, 5>), dim3 (2 * (g1 - g0)), dim3 (NKP_WAVE), lds, st, B.grp_maxlen, B.grp_base, g0,  \
-                                                       B.fac_tf, r, z, accumulate, B.grp_row0, B.col_slot, B.ngrp, K, k0); } while (0)
-         if (B.P == 1) LDSP4_LAUNCH (1);
-         else if (B.P == 2) LDSP4_LAUNCH (2);
-         else LDSP4_LAUNCH (4);
-#undef LDSP4_LAUNCH
-      }
-      return 0;
-   }
-   for (int k0 = 0; k0 < K; k0 += 2) {
-#define LDSP2_LAUNCH(PP) do { if (nch == 4) hipLaunchKernelGGL ((colblock_apply_ldspack2_kernel<PP, 4>), dim3 (g1 - g0), dim3 (NKP_WAVE), lds, st, B.grp_maxlen, B.grp_base, g0, \
-                                                                 B.fac_tf, r, z, accumulate, B.grp_row0, B.col_slot, B.ngrp, K, k0);                                         \
-                              else hipLaunchKernelGGL ((colblock_apply_ldspack2_kernel<PP, 5>), dim3 (g1 - g0), dim3 (NKP_WAVE), lds, st, B.grp_maxlen, B.grp_base, g0,       \
-                                                       B.fac_tf, r, z, accumulate, B.grp_row0, B.col_slot, B.ngrp, K, k0); } while (0)
-      if (B.P == 1) LDSP2_LAUNCH (1);
-      else if (B.P == 2) LDSP2_LAUNCH (2);
-      else LDSP2_LAUNCH (4);
-#undef LDSP2_LAUNCH
-   }
+   with_band (B.P, [&] (auto p) {
+      constexpr int P = decltype (p)::value;
+      with_int<4, 5> (nch, [&] (auto nch_) {
+         constexpr int NCH = decltype (nch_)::value;
+         // four systems per launch, two waves (16 columns each) per group; K / 2 launches of the two-system kernel otherwise
+         if (K % 4 == 0)
+            for (int k0 = 0; k0 < K; k0 += 4)
+               hipLaunchKernelGGL ((colblock_apply_ldspack4_kernel<P, NCH>), dim3 (2 * (g1 - g0)), dim3 (NKP_WAVE), lds, st, B.grp_maxlen, B.grp_base, g0,
+                                   B.fac_tf, r, z, accumulate, B.grp_row0, B.col_slot, B.ngrp, K, k0);
+         else
+            for (int k0 = 0; k0 < K; k0 += 2)
+               hipLaunchKernelGGL ((colblock_apply_ldspack2_kernel<P, NCH>), dim3 (g1 - g0), dim3 (NKP_WAVE), lds, st, B.grp_maxlen, B.grp_base, g0,
+                                   B.fac_tf, r, z, accumulate, B.grp_row0, B.col_slot, B.ngrp, K, k0);
+      });
+   });
    return 0;
 }

@@ -5,6 +5,7 @@
 
 #include "../../include/nkp.h"
 
+#include <type_traits>
 #include <vector>
 
 // the tuning a launcher uses when its object carries none: the plain defaults (no environment)
@@ -91,6 +92,37 @@ struct ColBlocksDev {
    int *wave_desc = nullptr;   // levels run by gs_wave_kernel: per column {first row, rows, first entry, entries} -- one load instead of two dependent ones
    const nkp_tuning *tune = nullptr;   // kernel selection knobs of the owning solver (NULL: built-in defaults)
 };
+
+// ---------------------------------------------------------------- kernel selection (host side)
+// A launcher turns each run-time value that picks a kernel instantiation into a compile-time tag and names the kernel, with its
+// argument list, once inside a generic lambda:
+//    with_band (B.P, [&] (auto p) { constexpr int P = decltype (p)::value; hipLaunchKernelGGL ((kernel<P>), ...); });
+// The lambda's body is compiled for every value of the list, so nested selectors instantiate the product of their lists
+// (`if constexpr` on a tag leaves out a combination that has no kernel).  The lambda's result, if any, is passed on.
+
+template <int V> using int_tag = std::integral_constant<int, V>;
+// f (int_tag<V>) for the first V of the list that v equals; any other v takes the last one
+template <int V0, int... Vs, class F>
+inline auto with_int (int v, F &&f)
+{
+   if constexpr (sizeof... (Vs) == 0) return f (int_tag<V0> ());
+   else {
+      if (v == V0) return f (int_tag<V0> ());
+      return with_int<Vs...> (v, f);
+   }
+}
+template <class F> inline auto with_band (int P, F &&f) { return with_int<1, 2, 4> (P, f); }   // half bandwidth stored
+template <class F> inline auto with_k (int K, F &&f) { return with_int<2, 4, 8> (K, f); }       // interleaved right-hand sides
+template <class F> inline auto with_bool (bool b, F &&f) { return b ? f (std::true_type ()) : f (std::false_type ()); }
+// f (vf) when the f32 copy exists, f (vd) otherwise; inside, elem_t<decltype (v)> is the storage type of the pointer f was given
+template <class F> inline auto with_storage (const float *vf, const double *vd, F &&f) { return vf ? f (vf) : f (vd); }
+template <class PTR> using elem_t = std::remove_cv_t<std::remove_pointer_t<PTR>>;
+// wave-per-column kernels: f (band tag, rows-per-lane tag) -- a lane holds one row of a column, two where a column can exceed the wave
+template <class F>
+inline auto with_band_rows (const ColBlocksDev &B, F &&f)
+{
+   return with_band (B.P, [&] (auto p) { return with_int<1, 2> (B.max_len <= NKP_WAVE ? 1 : 2, [&] (auto rpl) { return f (p, rpl); }); });
+}
 
 #define GS_THREADS 256
 #define GS_NNZ 2048

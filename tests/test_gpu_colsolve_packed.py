@@ -96,3 +96,34 @@ def test_packed_column_solve_is_bit_identical(grid, km, monkeypatch):
                     z[variant] = s.precond_apply(r)
             assert np.isfinite(z["packed"]).all() and np.linalg.norm(z["packed"]) > 0
             assert np.array_equal(z["lanes"], z["packed"]), (grid, km, adv, precond, np.abs(z["lanes"] - z["packed"]).max())
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("f32", ["0", "1"], ids=["f64", "f32"])
+@pytest.mark.parametrize("km", [70, 80])
+@pytest.mark.parametrize("grid", [g for g in GRIDS if g[:2] == (8, 8)], ids=lambda g: "%dx%d_seed%d" % g)
+def test_capped_lanes_kernel_is_bit_identical(grid, km, f32, monkeypatch):
+    """The 8-columns-per-wave kernel on columns of 65-80 levels: its instantiation capped at three waves per SIMD,
+    colblock_apply_lanes_kernel<P, 80, FT, 3> (NKP_COL_W3=1, the default), against the uncapped <P, 128, FT, 1> that
+    NKP_COL_W3=0 selects.  Same text, other register allocation => precond_apply of the multilevel cycle is np.array_equal,
+    band half-width 1 and 2, f64 and f32 factor storage.  (Columns of at most 64 levels take <P, 64, FT, 1> under either
+    setting: seed 7 at km = 70.)"""
+    imt, jmt, seed = grid
+    monkeypatch.setenv("NKP_COLSTREAM_MIN", "1")
+    monkeypatch.setenv("NKP_COLWAVE_MAX", "0")              # no wave-per-column kernel on the small levels
+    monkeypatch.setenv("NKP_ML_F32", f32)
+    for name, value in {**SMALL_LEVELS, **LANES}.items():
+        monkeypatch.setenv(name, value)
+    for adv, hmix, band in BANDS:
+        p = synth.generate(imt=imt, jmt=jmt, km=km, adv=adv, hmix=hmix, seed=seed)
+        blk = solver.column_blocks(p.col_start(), p.tracer_state_len, 1)
+        ci, cj = solver.column_coords(p.ind_i, p.ind_j, p.col_start(), 1)
+        r = np.random.default_rng(41).standard_normal(p.flat_len)
+        z = {}
+        for w3 in ("1", "0"):
+            monkeypatch.setenv("NKP_COL_W3", w3)
+            with solver.NkpSolver(p.rowptr, p.colind, p.nzval, blk, precond=solver.PRECOND_MULTILEVEL, restart=4, col_i=ci, col_j=cj) as s:
+                assert s.get_int("levels") >= 2, s.get_int("levels")      # level 0 runs sweeps, i.e. the column kernel
+                z[w3] = s.precond_apply(r)
+        assert np.isfinite(z["1"]).all() and np.linalg.norm(z["1"]) > 0
+        assert np.array_equal(z["1"], z["0"]), (grid, km, adv, f32, np.abs(z["1"] - z["0"]).max())
