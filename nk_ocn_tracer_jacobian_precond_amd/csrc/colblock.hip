@@ -164,17 +164,17 @@ void colblock_apply_kernel (const int *__restrict__ blk_start, int b_first, int 
    const int r0 = blk_start[b];
    const int len = blk_start[b + 1] - r0;
 
-   double y[RPL], invd[RPL], L[RPL][P], U[RPL][P];
+   double y[RPL][1], invd[RPL], L[RPL][P], U[RPL][P];
 #pragma unroll
    for (int s = 0; s < RPL; s++) {
       const int li = s * NKP_WAVE + lane;
-      y[s] = 0.0;
+      y[s][0] = 0.0;
       invd[s] = 0.0;
 #pragma unroll
       for (int q = 0; q < P; q++) { L[s][q] = 0.0; U[s][q] = 0.0; }
       if (li < len) {
          const int64_t r = r0 + li;
-         y[s] = rhs[r];
+         y[s][0] = rhs[r];
          invd[s] = fac[(int64_t) P * n + r];
          if (R32) invd[s] = (double) (float) invd[s];
 #pragma unroll
@@ -186,45 +186,13 @@ void colblock_apply_kernel (const int *__restrict__ blk_start, int b_first, int 
       }
    }
 
-   // forward: y <- L^-1 y   (unit lower band)
-   for (int k = 0; k < len - 1; k++) {
-      const int ks = k >> 6, kl = k & (NKP_WAVE - 1);
-      double yk = 0.0;
-#pragma unroll
-      for (int s = 0; s < RPL; s++)
-         if (ks == s) yk = readlane_f64 (y[s], kl);
-#pragma unroll
-      for (int s = 0; s < RPL; s++) {
-         const int rel = s * NKP_WAVE + lane - k;               // my level minus k
-#pragma unroll
-         for (int q = 1; q <= P; q++)
-            if (rel == q) y[s] -= L[s][q - 1] * yk;
-      }
-   }
-   // backward: y <- U^-1 y
-   for (int k = len - 1; k >= 0; k--) {
-      const int ks = k >> 6, kl = k & (NKP_WAVE - 1);
-      double xk = 0.0;
-#pragma unroll
-      for (int s = 0; s < RPL; s++)
-         if (ks == s) {
-            if (lane == kl) y[s] *= invd[s];
-            xk = readlane_f64 (y[s], kl);
-         }
-#pragma unroll
-      for (int s = 0; s < RPL; s++) {
-         const int rel = k - (s * NKP_WAVE + lane);             // k minus my level
-#pragma unroll
-         for (int q = 1; q <= P; q++)
-            if (rel == q) y[s] -= U[s][q - 1] * xk;
-      }
-   }
+   wave_band_sweeps<P, RPL, 1> (len, lane, y, invd, L, U);
 #pragma unroll
    for (int s = 0; s < RPL; s++) {
       const int li = s * NKP_WAVE + lane;
       if (li < len) {
-         if (accumulate) z[(int64_t) r0 + li] += y[s];
-         else z[(int64_t) r0 + li] = y[s];
+         if (accumulate) z[(int64_t) r0 + li] += y[s][0];
+         else z[(int64_t) r0 + li] = y[s][0];
       }
    }
 }
@@ -257,22 +225,20 @@ void gs_wave_kernel (const int *__restrict__ rowptr, const int *__restrict__ col
    int *sc = reinterpret_cast<int *> (gsw_lds) + wv * GSW_CAP;
    VT *sv = reinterpret_cast<VT *> (gsw_lds + (size_t) CB_WAVES * GSW_CAP * sizeof (int)) + wv * GSW_CAP;
    const int blk = wave_block_id () + b_first;
-   const bool act = blk < b_end;                    // (no early return: the whole workgroup meets at the barrier below)
+   if (blk >= b_end) return;                        // a wave stages and reads its own LDS region only: no workgroup barrier below
    const int lane = threadIdx.x & (NKP_WAVE - 1);
    // {first row, rows, first entry, entries} of the column in one 16-byte load (desc: built at setup), else through blk_start and rowptr
-   int4 d4 = make_int4 (0, 0, 0, 0);
-   if (act) {
-      if (desc) d4 = desc[blk];
-      else {
-         d4.x = blk_start[blk];
-         d4.y = blk_start[blk + 1] - d4.x;
-         d4.z = d4.y > 0 ? rowptr[d4.x] : 0;
-         d4.w = d4.y > 0 ? rowptr[d4.x + d4.y] - d4.z : 0;
-      }
+   int4 d4;
+   if (desc) d4 = desc[blk];
+   else {
+      d4.x = blk_start[blk];
+      d4.y = blk_start[blk + 1] - d4.x;
+      d4.z = d4.y > 0 ? rowptr[d4.x] : 0;
+      d4.w = d4.y > 0 ? rowptr[d4.x + d4.y] - d4.z : 0;
    }
    const int r0 = d4.x, len = d4.y;
 
-   double y[RPL], xold[RPL], invd[RPL], L[RPL][P], U[RPL][P];
+   double y[RPL][1], xold[RPL], invd[RPL], L[RPL][P], U[RPL][P];
    int e0[RPL], rl[RPL];
    const int e_begin = d4.z, e_total = d4.w;
    const bool staged = e_total <= GSW_CAP;
@@ -296,14 +262,14 @@ void gs_wave_kernel (const int *__restrict__ rowptr, const int *__restrict__ col
 #pragma unroll
    for (int s = 0; s < RPL; s++) {
       const int li = s * NKP_WAVE + lane;
-      y[s] = 0.0; xold[s] = 0.0; invd[s] = 0.0; e0[s] = 0; rl[s] = 0;
+      y[s][0] = 0.0; xold[s] = 0.0; invd[s] = 0.0; e0[s] = 0; rl[s] = 0;
 #pragma unroll
       for (int q = 0; q < P; q++) { L[s][q] = 0.0; U[s][q] = 0.0; }
       if (li < len) {
          const int64_t r = r0 + li;
          e0[s] = rowptr[r];
          rl[s] = rowptr[r + 1] - e0[s];
-         y[s] = b[r];
+         y[s][0] = b[r];
          xold[s] = (r < split) ? xa[r] : xb[r];
          invd[s] = fac[(int64_t) P * n + r];
          if (R32) invd[s] = (double) (float) invd[s];
@@ -315,7 +281,10 @@ void gs_wave_kernel (const int *__restrict__ rowptr, const int *__restrict__ col
          }
       }
    }
-   __syncthreads ();
+   // the staged entries are written and read by this wave alone, and a wave's LDS operations complete in order: all that is
+   // needed is that the compiler keeps the writes above in front of the reads below
+   __builtin_amdgcn_fence (__ATOMIC_ACQ_REL, "wavefront");
+   __builtin_amdgcn_wave_barrier ();
    // residual of this lane's row(s): entries in stored order, GSW_UNROLL of them requested together (from LDS, or one round trip for the (column, value) pairs of a column too long to stage; then one for the gathered x)
 #pragma unroll
    for (int s = 0; s < RPL; s++) {
@@ -346,45 +315,25 @@ void gs_wave_kernel (const int *__restrict__ rowptr, const int *__restrict__ col
          for (int u = 0; u < GSW_UNROLL; u++)
             if (k0 + u < rl[s]) acc += (double) vv[u] * xv[u];
       }
-      if (s * NKP_WAVE + lane < len) y[s] -= acc;
+      if (s * NKP_WAVE + lane < len) y[s][0] -= acc;
    }
-   // forward: y <- L^-1 y   (unit lower band)
-   for (int k = 0; k < len - 1; k++) {
-      const int ks = k >> 6, kl = k & (NKP_WAVE - 1);
-      double yk = 0.0;
+#if defined(NKP_ABLATION) && defined(NKP_ABLATE_GSW_SWEEPS)
+   // TIMING-ONLY (wrong results by design; `make ablation ABLATE=-DNKP_ABLATE_GSW_SWEEPS`): the launch without its two sweeps;
+   // the factor loads stay alive.  What this takes off a launch is the most any rewrite of the sweeps can gain
 #pragma unroll
-      for (int s = 0; s < RPL; s++)
-         if (ks == s) yk = readlane_f64 (y[s], kl);
+   for (int s = 0; s < RPL; s++) {
+      double f = invd[s];
 #pragma unroll
-      for (int s = 0; s < RPL; s++) {
-         const int rel = s * NKP_WAVE + lane - k;
-#pragma unroll
-         for (int q = 1; q <= P; q++)
-            if (rel == q) y[s] -= L[s][q - 1] * yk;
-      }
+      for (int q = 0; q < P; q++) f += L[s][q] + U[s][q];
+      if (f == 123.456) y[s][0] = f;
    }
-   // backward: y <- U^-1 y
-   for (int k = len - 1; k >= 0; k--) {
-      const int ks = k >> 6, kl = k & (NKP_WAVE - 1);
-      double xk = 0.0;
-#pragma unroll
-      for (int s = 0; s < RPL; s++)
-         if (ks == s) {
-            if (lane == kl) y[s] *= invd[s];
-            xk = readlane_f64 (y[s], kl);
-         }
-#pragma unroll
-      for (int s = 0; s < RPL; s++) {
-         const int rel = k - (s * NKP_WAVE + lane);
-#pragma unroll
-         for (int q = 1; q <= P; q++)
-            if (rel == q) y[s] -= U[s][q - 1] * xk;
-      }
-   }
+#else
+   wave_band_sweeps<P, RPL, 1> (len, lane, y, invd, L, U);
+#endif
 #pragma unroll
    for (int s = 0; s < RPL; s++) {
       const int li = s * NKP_WAVE + lane;
-      if (li < len) xout[(int64_t) r0 + li] = xold[s] + y[s];
+      if (li < len) xout[(int64_t) r0 + li] = xold[s] + y[s][0];
    }
 }
 

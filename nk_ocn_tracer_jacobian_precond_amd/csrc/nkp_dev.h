@@ -6,6 +6,7 @@
 #include "../../include/nkp.h"
 
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 // the tuning a launcher uses when its object carries none: the plain defaults (no environment)
@@ -122,6 +123,109 @@ template <class F>
 inline auto with_band_rows (const ColBlocksDev &B, F &&f)
 {
    return with_band (B.P, [&] (auto p) { return with_int<1, 2> (B.max_len <= NKP_WAVE ? 1 : 2, [&] (auto rpl) { return f (p, rpl); }); });
+}
+
+// ---------------------------------------------------------------- band substitution, one water column per wave (device side)
+// f (int_tag<0>), ..., f (int_tag<N - 1>) in this order: the index is a constant inside every call
+template <int... Is, class F>
+__device__ __forceinline__ void static_for_seq (std::integer_sequence<int, Is...>, F &&f) { (f (int_tag<Is> ()), ...); }
+template <int N, class F>
+__device__ __forceinline__ void static_for (F &&f) { static_for_seq (std::make_integer_sequence<int, N> (), f); }
+
+template <int LANE>
+__device__ __forceinline__ double readlane_const_f64 (double v)
+{
+   int lo = __double2loint (v), hi = __double2hiint (v);
+   lo = __builtin_amdgcn_readlane (lo, LANE);
+   hi = __builtin_amdgcn_readlane (hi, LANE);
+   return __hiloint2double (hi, lo);
+}
+
+// y <- (LU)^-1 y for the column a wave holds: lane l owns row s * 64 + l in y[s][.] (RPL = 2: columns of 65-128 rows), K
+// right-hand sides side by side, L[s][q - 1] = l(r, r - q), U[s][q - 1] = u(r, r + q), invd = 1 / u(r, r), all zero behind
+// the column's end.  Both sweeps are written out step by step, so the lane a step broadcasts and the lanes it updates are
+// constants: no lane compare or register select sits between two broadcasts, only
+//    forward:   v_readlane (y_k) -> multiply by l(k+1, k) -> subtract -> v_readlane (y_{k+1})
+//    backward:  v_readlane (x_k) -> multiply by u(k-1, k) -> subtract -> multiply by invd -> v_readlane (x_{k-1})
+// computed on all lanes, of which the next step reads the one that is complete; the masked write into y and the updates of
+// the rows further off (q >= 2) are issued behind that and are off the chain.  Each step is guarded by the wave-uniform
+// k < len - 1 (forward) or k < len (backward), so no step runs beyond the column's end.  Per row the operations and their
+// order are those of the lane-per-column kernels: row r takes - l(r, r-q) y_{r-q} for q = P first down to q = 1, then
+// - u(r, r+q) x_{r+q} for q = P first down to q = 1, then * invd; a product and a difference each rounded (no FMA).
+template <int P, int RPL, int K>
+__device__ __forceinline__ void wave_band_sweeps (int len, int lane, double (&y)[RPL][K], const double (&invd)[RPL], const double (&L)[RPL][P],
+                                                  const double (&U)[RPL][P])
+{
+   constexpr int ROWS = RPL * NKP_WAVE;
+   len = __builtin_amdgcn_readfirstlane (len);
+   double bc[K];                                   // the step's broadcast: y_k, then x_k
+#pragma unroll
+   for (int j = 0; j < K; j++) bc[j] = readlane_const_f64<0> (y[0][j]);
+   static_for<ROWS - 1> ([&] (auto kc) __attribute__ ((always_inline)) {
+      constexpr int k = decltype (kc)::value;
+      if (__builtin_expect (k < len - 1, 1)) {
+         constexpr int s1 = (k + 1) / NKP_WAVE, l1 = (k + 1) % NKP_WAVE;
+         double t[K], nb[K];
+#pragma unroll
+         for (int j = 0; j < K; j++) {
+            t[j] = y[s1][j] - L[s1][0] * bc[j];             // row k + 1 is complete in lane l1
+            nb[j] = readlane_const_f64<l1> (t[j]);
+         }
+#pragma unroll
+         for (int j = 0; j < K; j++) y[s1][j] = lane == l1 ? t[j] : y[s1][j];
+#pragma unroll
+         for (int q = 2; q <= P; q++)
+            if (k + q < ROWS) {
+               const int s = (k + q) / NKP_WAVE, l = (k + q) % NKP_WAVE;
+#pragma unroll
+               for (int j = 0; j < K; j++) {
+                  const double u = y[s][j] - L[s][q - 1] * bc[j];
+                  y[s][j] = lane == l ? u : y[s][j];
+               }
+            }
+#pragma unroll
+         for (int j = 0; j < K; j++) bc[j] = nb[j];
+      }
+   });
+   // (the backward guards test a copy of len the compiler cannot see through: left to itself it keeps every forward guard's
+   // outcome in a register pair for the backward sweep and spills them)
+   asm volatile ("" : "+s" (len));
+   // c: lane k holds row k with its subtractions done when step k begins; the sweep enters at row len - 1
+   double c[K];
+#pragma unroll
+   for (int j = 0; j < K; j++) {
+      c[j] = y[0][j];
+      if (RPL == 2 && len > NKP_WAVE) c[j] = y[RPL - 1][j];
+   }
+   static_for<ROWS> ([&] (auto ic) __attribute__ ((always_inline)) {
+      constexpr int k = ROWS - 1 - decltype (ic)::value;
+      if (__builtin_expect (k < len, 1)) {
+         constexpr int s0 = k / NKP_WAVE, l0 = k % NKP_WAVE;
+         double v[K];
+#pragma unroll
+         for (int j = 0; j < K; j++) {
+            v[j] = c[j] * invd[s0];                           // x_k in lane l0
+            bc[j] = readlane_const_f64<l0> (v[j]);
+         }
+         if (k > 0) {
+            constexpr int s1 = (k > 0 ? k - 1 : 0) / NKP_WAVE;
+#pragma unroll
+            for (int j = 0; j < K; j++) c[j] = y[s1][j] - U[s1][0] * bc[j];
+         }
+#pragma unroll
+         for (int j = 0; j < K; j++) y[s0][j] = lane == l0 ? v[j] : y[s0][j];
+#pragma unroll
+         for (int q = 2; q <= P; q++)
+            if (k - q >= 0) {
+               const int s = (k - q) / NKP_WAVE, l = (k - q) % NKP_WAVE;
+#pragma unroll
+               for (int j = 0; j < K; j++) {
+                  const double u = y[s][j] - U[s][q - 1] * bc[j];
+                  y[s][j] = lane == l ? u : y[s][j];
+               }
+            }
+      }
+   });
 }
 
 #define GS_THREADS 256
