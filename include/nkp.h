@@ -425,6 +425,37 @@ int nkp_permuted_rows (int64_t n, const int32_t *rowptr, const int32_t *colind, 
  * clones are alive. */
 int nkp_clone (nkp_solver *src, nkp_solver **out);
 
+/* Solves with A^T (SuperLU's options.Trans, the mode pdgssvx reads next to Fact and Equil: src/solve_ABglobal.c:327-335) --
+ * adjoint tracer problems, sensitivities, the backward pass through a solve.  *out is a solver for A^T on the same device and
+ * the same stream as s, built from the matrix s holds ON THE DEVICE (the caller passes no arrays): the CSR is transposed by
+ * kernels (rows of A^T sorted by column, stored zeros kept), and the transposed solver is made with the options and tuning s
+ * resolved at its creation -- preconditioner, Krylov method, restart, tolerances, equil, precond_steps, the block offsets,
+ * col_i / col_j / col_t, coupled_tracer_cnt.  It is bit for bit what nkp_create builds from the host transpose of the same
+ * CSR: matrix, every array of the hierarchy, solves and batched solves.  Every entry point keeps its documented meaning on
+ * the handle (nkp_solve*, nkp_spmv*: y = A^T x, nkp_precond_apply, nkp_get_int, nkp_ml_level_array, nkp_time_kernel).
+ *   Ownership: the handle belongs to s.  A second nkp_transpose (s, ...) returns the same handle.  nkp_destroy (s) destroys
+ *   the transposed solver too: it must not be used or destroyed afterwards.  nkp_destroy on the transposed handle itself frees
+ *   it and detaches it; a later nkp_transpose builds a new one.  nkp_set_stream (s, ...) moves both solvers.
+ *   nkp_refactor / nkp_refactor_device on s keep it in step: after the refactor of s has succeeded the new values are gathered
+ *   on the device (valT = val[src], one kernel) and the same sequence runs on the transposed solver with the same flags.  When
+ *   the refactor of s fails before its commit point neither solver changes.  When the transposed solver's own refactor fails
+ *   it is freed and detached, the call still returns the code of s (one "(rank)" line at verbose >= 1), and the next
+ *   nkp_transpose rebuilds from the new matrix and reports its own error.  The transposed solver is not a clone: it does not
+ *   block NKP_REFACTOR_REBUILD.  No solve may be in flight on either solver during nkp_transpose or a refactor.
+ *   Memory: a second solver (matrix, hierarchy, work vectors) plus the int32 value map, plus nnz doubles from the first
+ *   refactor on.  nkp_get_int on s: "trans_device_bytes" (all of that, 0 when there is none; "device_bytes" of s does not
+ *   change), "trans_us" (wall time of the last nkp_transpose that built one), "trans_kernel_us" (of which: the device
+ *   transpose); on either handle: "is_transpose".
+ * Returns 0; NKP_EINVAL with *out = NULL and nothing allocated when s or out is NULL (before any HIP call), s is a clone, s is
+ * itself a transposed handle, or s is row-distributed (the transpose of a row block needs an exchange between the ranks);
+ * NKP_ESINGULAR when a refactor of s failed after its commit point (s cannot solve either until a refactor succeeds; the message
+ * is that failure's); NKP_ENOMEM / NKP_EDEVICE, with s solving exactly as before.  On the transposed handle nkp_refactor*
+ * (refactor the solver it was transposed from), nkp_clone and nkp_set_stream return NKP_EINVAL.
+ * Cost: one nkp_create plus the device transpose, whose sorting step reads a row of A^T once per entry of that row -- any row
+ * length is accepted, but the work is quadratic in it (a column of A with 10^5 entries means 10^10 reads; ocean Jacobians have
+ * 5 - 40 per row, a sink that couples a cell to every level a few hundred). */
+int nkp_transpose (nkp_solver *s, nkp_solver **out);
+
 /* hipSetDevice for host programs that do not link HIP themselves (call before nkp_comm_rccl_init). */
 int nkp_set_device (int device);
 

@@ -216,6 +216,19 @@ int main (int argc, char *argv[])
    }
    if (parse_cmd_line (argc, argv))
       exit (EXIT_FAILURE);
+   // NKP_TRANS=1: solve A^T x = b (SuperLU's options.Trans) on the handle nkp_transpose makes from the matrix on the device
+   int trans = 0;
+   {
+      const char *e = getenv ("NKP_TRANS");
+      int v;
+      if (e && !parse_to_int ((char *) e, &v) && v != 0) trans = 1;
+   }
+#ifdef NKP_DIST
+   if (trans) {
+      fprintf (stderr, "(%d) NKP_TRANS=1: nkp_transpose is not available for the row-distributed flavour (the transpose of a row block needs an exchange between the ranks); use solve_ABglobal\n", iam);
+      exit (EXIT_FAILURE);
+   }
+#endif
    int world = 1, local_rank = 0, use_comm = 0;
    (void) local_rank;
 #ifdef NKP_DIST
@@ -498,6 +511,18 @@ int main (int argc, char *argv[])
       fprintf (stderr, "(%d) %s failed: %s\n", iam, prog_solver, nkp_last_error ());
       exit (EXIT_FAILURE);
    }
+   nkp_solver *owner = NULL;   // NKP_TRANS: the solver of A, which owns the transposed one the loop below solves with
+   if (trans) {
+      nkp_solver *at = NULL;
+      if (nkp_transpose (solver, &at)) {
+         fprintf (stderr, "(%d) nkp_transpose failed: %s\n", iam, nkp_last_error ());
+         exit (EXIT_FAILURE);
+      }
+      if (dbg_lvl)
+         printf ("(%d) NKP_TRANS: solving A^T x = b, trans_us = %lld\n", iam, (long long) nkp_get_int (solver, "trans_us"));
+      owner = solver;
+      solver = at;
+   }
    free_sparse_matrix ();      // the device holds its own copy
    free (blk_start);
    free (col_i);
@@ -710,7 +735,7 @@ int main (int argc, char *argv[])
 
    }
 
-   nkp_destroy (solver);
+   nkp_destroy (owner ? owner : solver);      // the owner frees its transposed solver
 #ifdef NKP_DIST
    if (use_comm) { if (file_transport) nkp_comm_file_free (&ops); else nkp_comm_rccl_free (&ops); }
 #endif

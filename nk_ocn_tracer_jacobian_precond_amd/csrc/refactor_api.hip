@@ -275,10 +275,41 @@ static int refactor_impl (nkp_solver *s, const double *h_val, const void *d_val,
    return NKP_OK;
 }
 
-extern "C" int nkp_refactor (nkp_solver *s, const double *val, int flags) { return refactor_impl (s, val, nullptr, flags, "nkp_refactor", false); }
+// The entry points.  A solver that owns a transposed one (nkp_transpose) keeps it in step: once its own refactor has succeeded
+// the new values are gathered through the value map on the device and the same sequence, with the same flags, runs on the
+// transposed solver.  A transposed solver that cannot follow is freed -- the next nkp_transpose rebuilds it from the new matrix
+// and reports its own error -- and the call still returns the owner's code.
+static int refactor_entry (nkp_solver *s, const double *h_val, const void *d_val, int flags, const char *who, bool collective)
+{
+   if (!s || (!h_val && !d_val)) return refactor_impl (s, h_val, d_val, flags, who, collective);      // refused before s is looked at
+   if (s->trans_of) return fail (NKP_EINVAL, "%s: a transposed solver follows its source; refactor the solver it was transposed from", who);
+   const int rc = refactor_impl (s, h_val, d_val, flags, who, collective);
+   if (!s->trans) return rc;
+   if (rc != NKP_OK) {
+      if (s->shared->broken) {      // failed after the commit point: nobody knows which matrix the owner holds
+         const std::string keep = last_error_message ();
+         msg (s, 1, "%s: the transposed solver is freed with the failed refactor\n", who);
+         trans_release (s);
+         restore_error_message (keep);
+      }
+      return rc;
+   }
+   const double *d_valT = nullptr;
+   int trc = trans_gather_values (s, &d_valT);
+   if (!trc) trc = refactor_impl (s->trans, nullptr, d_valT, flags, who, false);
+   if (trc) {
+      msg (s, 1, "%s: the transposed solver could not follow (%d: %s); it is freed, the next nkp_transpose builds a new one\n", who, trc, last_error_message ().c_str ());
+      (void) hipStreamSynchronize (s->stream);
+      trans_release (s);
+      (void) hipGetLastError ();
+   }
+   return rc;      // the code of s
+}
 
-extern "C" int nkp_refactor_device (nkp_solver *s, const void *d_val, int flags) { return refactor_impl (s, nullptr, d_val, flags, "nkp_refactor_device", false); }
+extern "C" int nkp_refactor (nkp_solver *s, const double *val, int flags) { return refactor_entry (s, val, nullptr, flags, "nkp_refactor", false); }
 
-extern "C" int nkp_refactor_dist (nkp_solver *s, const double *val_loc, int flags) { return refactor_impl (s, val_loc, nullptr, flags, "nkp_refactor_dist", true); }
+extern "C" int nkp_refactor_device (nkp_solver *s, const void *d_val, int flags) { return refactor_entry (s, nullptr, d_val, flags, "nkp_refactor_device", false); }
 
-extern "C" int nkp_refactor_dist_device (nkp_solver *s, const void *d_val_loc, int flags) { return refactor_impl (s, nullptr, d_val_loc, flags, "nkp_refactor_dist_device", true); }
+extern "C" int nkp_refactor_dist (nkp_solver *s, const double *val_loc, int flags) { return refactor_entry (s, val_loc, nullptr, flags, "nkp_refactor_dist", true); }
+
+extern "C" int nkp_refactor_dist_device (nkp_solver *s, const void *d_val_loc, int flags) { return refactor_entry (s, nullptr, d_val_loc, flags, "nkp_refactor_dist_device", true); }

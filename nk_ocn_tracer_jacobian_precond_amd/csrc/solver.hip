@@ -175,6 +175,8 @@ void solver_free (nkp_solver *s)
       delete s;
       return;
    }
+   if (s->trans_of) trans_detach (s);
+   if (s->trans) trans_release (s);      // before the stream it shares goes
    for (nkp_solver *c : s->batch_members) solver_free (c);
    s->batch_members.clear ();
    for (double *p : { s->bvin, s->bz, s->bw })
@@ -537,8 +539,8 @@ static int create_impl (nkp_solver **out, const nkp_options *opt_in, int64_t n, 
    TRY (alloc_work_vectors (s));
 
    const double t_work = since0 ();
-   if (opt.precond == NKP_PRECOND_MULTILEVEL && !pm) {
-      // what a rebuild of the hierarchy (nkp_refactor) passes to ml_setup again
+   if (opt.precond != NKP_PRECOND_NONE && !pm) {
+      // what a rebuild of the hierarchy (nkp_refactor) passes to ml_setup again, and nkp_transpose to nkp_create
       s->h_blk.assign (blk_start, blk_start + nblk + 1);
       s->tracer_cnt = coupled_tracer_cnt;
       if (blk_default.empty ()) {
@@ -682,12 +684,14 @@ extern "C" int nkp_create64 (nkp_solver **out, const nkp_options *opt, int64_t n
 extern "C" int nkp_set_stream (nkp_solver *s, void *hip_stream)
 {
    if (!s) return fail (NKP_EINVAL, "nkp_set_stream: NULL solver");
+   if (s->trans_of) return fail (NKP_EINVAL, "nkp_set_stream: a transposed solver runs on the stream of the solver it was transposed from; set that one's stream");
    if (s->own_stream && s->stream) { (void) hipStreamSynchronize (s->stream); (void) hipStreamDestroy (s->stream); }
    // NULL is a stream too: the device's default stream (what torch.cuda.current_stream() is unless the
    // caller switched streams), so work enqueued here stays ordered with the caller's own kernels
    s->stream = (hipStream_t) hip_stream;
    s->own_stream = false;
    for (nkp_solver *c : s->batch_members) c->stream = s->stream;      // the members of a batch share the solver's stream
+   trans_set_stream (s);                                               // ... and so does the transposed solver
    return NKP_OK;
 }
 
@@ -726,6 +730,10 @@ extern "C" int64_t nkp_get_int (nkp_solver *s, const char *key)
    if (!strcmp (key, "refactor_rebuilt")) return s->refactor_rebuilt;
    if (!strcmp (key, "refactor_us")) return (int64_t) (s->refactor_seconds * 1.0e6);
    if (!strcmp (key, "refactor_halo_values")) return s->refactor_halo_values;
+   if (!strcmp (key, "is_transpose")) return s->trans_of ? 1 : 0;
+   if (!strcmp (key, "trans_device_bytes")) return trans_device_bytes (s);
+   if (!strcmp (key, "trans_us")) return (int64_t) (s->trans_seconds * 1.0e6);
+   if (!strcmp (key, "trans_kernel_us")) return (int64_t) (s->trans_kernel_seconds * 1.0e6);
    if (!strcmp (key, "dist_alltoallv_calls")) return s->shared->alltoallv_calls.load ();
    if (!strcmp (key, "dist_allreduce_calls")) return s->shared->allreduce_calls.load ();
    if (!strcmp (key, "batch_steps")) return s->batch_steps;
@@ -1124,6 +1132,7 @@ static int clone_impl (nkp_solver *src, nkp_solver **out, bool member)
    *out = nullptr;
    if (src->dist.on && !member) return fail (NKP_EINVAL, "nkp_clone: not available for the row-distributed flavour");
    if (src->borrowed) return fail (NKP_EINVAL, "nkp_clone: clone the original solver, not a clone");
+   if (src->trans_of && !member) return fail (NKP_EINVAL, "nkp_clone: not available on a transposed solver (its owner may free it at a refactor)");
    HIPCHK (hipSetDevice (src->device));
    nkp_solver *s = new (std::nothrow) nkp_solver (*src);
    if (!s) return fail (NKP_ENOMEM, "nkp_clone: out of host memory");
@@ -1137,6 +1146,10 @@ static int clone_impl (nkp_solver *src, nkp_solver **out, bool member)
    s->dist.bxe = s->dist.bsend = s->dist.gmsg = s->dist.ghpin = s->dist.bras_send = s->dist.bras_recv = nullptr;
    s->dist.bK = s->dist.agreed_K = 0;
    s->dplan = nullptr;
+   s->trans = s->trans_of = nullptr;
+   s->trans_src = nullptr;
+   s->trans_val = nullptr;
+   s->trans_map_bytes = 0;
    s->A.tune = &s->tune;
    s->B.tune = &s->tune;
    s->ml.tune = &s->tune;

@@ -111,6 +111,13 @@ struct nkp_solver {
    // nkp_refactor_dist: where the values of the hierarchy's source come from (kept by nkp_create_dist, multilevel only)
    DistRefactorPlan *dplan = nullptr;
    int64_t refactor_halo_values = 0;
+   // nkp_transpose: the solver of A^T this one owns (trans), or the solver this one was transposed from (trans_of); the owner
+   // keeps the value map valT[p] = val[trans_src[p]] and, from its first refactor on, the gathered values (both on the device)
+   nkp_solver *trans = nullptr, *trans_of = nullptr;
+   int *trans_src = nullptr;
+   double *trans_val = nullptr;
+   size_t trans_map_bytes = 0;
+   double trans_seconds = 0.0, trans_kernel_seconds = 0.0;
    double *h_dev () { return dscal; }
    double *h2_dev () { return dscal + (m + 2); }
    double *misc_dev () { return dscal + 2 * (m + 2); }     // [0]=nrm2 [1]=inv [2]=dot out ...
@@ -138,5 +145,16 @@ NKP_PRIVATE void msg (const nkp_solver *s, int lvl, const char *fmt, ...);
 NKP_PRIVATE int dist_agree (nkp_solver *s, int local_rc, const char *who, const char *where);
 // developer switch ml_drop_intertracer: the matrix without the couplings between its tracer_cnt tracers, i.e. exactly what a
 // tracer-per-rank partition builds its rank-local hierarchies from
+// ---- defined in transpose.hip ----------------------------------------------------------------------------------------------
+// the owner frees its transposed solver and the value map; a transposed solver that is destroyed leaves its owner
+NKP_PRIVATE void trans_release (nkp_solver *s);
+NKP_PRIVATE void trans_detach (nkp_solver *t);
+// the transposed solver and its batch members follow the owner's stream
+NKP_PRIVATE void trans_set_stream (nkp_solver *s);
+NKP_PRIVATE int64_t trans_device_bytes (const nkp_solver *s);
+// valT = A.val[trans_src] on the owner's stream, into a buffer the owner keeps
+NKP_PRIVATE int trans_gather_values (nkp_solver *s, const double **d_valT);
+
+// ---- defined in solver.hip -------------------------------------------------------------------------------------------------
 NKP_PRIVATE void drop_intertracer (int64_t n, int tracer_cnt, const int32_t *rowptr, const int32_t *colind, const double *val,
                                    std::vector<int32_t> &f_rowptr, std::vector<int32_t> &f_colind, std::vector<double> &f_val);

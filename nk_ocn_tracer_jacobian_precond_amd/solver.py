@@ -30,7 +30,7 @@ ABI_SYMBOLS = [
     "nkp_gather_root", "nkp_clone", "nkp_ml_plan_host", "nkp_comm_file_init", "nkp_comm_file_free",
     "nkp_create64", "nkp_cell_major_order", "nkp_permuted_rows", "nkp_dist_overlap_plan_host", "nkp_dist_plan_size",
     "nkp_dist_plan_copy", "nkp_dist_plan_free", "nkp_ml_level_array", "nkp_default_tuning", "nkp_solve_batch_device",
-    "nkp_refactor", "nkp_refactor_device", "nkp_refactor_dist", "nkp_refactor_dist_device",
+    "nkp_refactor", "nkp_refactor_device", "nkp_refactor_dist", "nkp_refactor_dist_device", "nkp_transpose",
 ]
 
 _ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p)
@@ -123,6 +123,7 @@ def load_library(path=None):
     lib.nkp_set_device.argtypes = [C.c_int]
     lib.nkp_gather_root.argtypes = [vp, f64p, f64p]
     lib.nkp_clone.argtypes = [vp, C.POINTER(vp)]
+    lib.nkp_transpose.argtypes = [vp, C.POINTER(vp)]
     lib.nkp_refactor.argtypes = [vp, f64p, C.c_int]
     lib.nkp_refactor_device.argtypes = [vp, vp, C.c_int]
     lib.nkp_refactor_dist.argtypes = [vp, f64p, C.c_int]
@@ -399,8 +400,29 @@ class NkpSolver:
         c._lib, c._h, c.n, c.nnz, c.options, c._parent = self._lib, h, self.n, self.nnz, self.options, self
         return c
 
+    def transposed(self):
+        """nkp_transpose: the solver for A^T, built on the device from the matrix this solver holds.  It belongs to this
+        solver (a second call returns the same object), follows its refactors, and is invalid once this solver is closed;
+        closing it detaches it, and the next call builds a new one."""
+        h = C.c_void_p()
+        self._check(self._lib.nkp_transpose(self._h, C.byref(h)))
+        t = getattr(self, "_trans", None)
+        if t is not None and t._h.value == h.value:
+            return t
+        t = object.__new__(NkpSolver)
+        t._lib, t._h, t.n, t.nnz, t.options, t._parent, t._trans_of = self._lib, h, self.n, self.nnz, self.options, self, self
+        self._trans = t
+        return t
+
     def close(self):
         if getattr(self, "_h", None) and self._h.value:
+            t = getattr(self, "_trans", None)
+            if t is not None:                                  # the library frees the transposed solver with this one
+                t._h = C.c_void_p()
+                self._trans = None
+            owner = getattr(self, "_trans_of", None)
+            if owner is not None and getattr(owner, "_trans", None) is self:
+                owner._trans = None
             self._lib.nkp_destroy(self._h)
             self._h = C.c_void_p()
 
