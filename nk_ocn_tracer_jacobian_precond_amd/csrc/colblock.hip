@@ -205,7 +205,7 @@ void colblock_apply_kernel (const int *__restrict__ blk_start, int b_first, int 
 // bandwidth, and the loads of 8 entries are in flight together), then the wave runs the band substitution on the
 // residual it holds in registers, and x_new = x_old + z goes out.  r never touches memory and half of the launches go.
 // x comes from TWO buffers like gs_fused_kernel's (rows < split from xa, the others from xb; new values to xout): columns
-// of one colour are coupled, so the sweep must not see its own updates (multilevel.hip ping-pongs the buffers).
+// of one colour are coupled, so the sweep must not see its own updates (mlcycle.hip ping-pongs the buffers).
 // Same products, same per-row summation order, same substitution as the two-kernel path => identical bits.
 #define GSW_UNROLL 24
 #define GSW_CAP 1536          // entries of one water column staged per wave (LDS: 4 waves x 1536 x 8 bytes = 48 KB with f32 values)
@@ -1592,7 +1592,7 @@ void colblock_apply_lanes_pipe_kernel (const int *__restrict__ grp_nb, const int
 // their launch-latency floor).
 // x comes from TWO buffers: rows < split (colour 0) from xa, the rest from xb, and the new values of this colour go to
 // xout -- the columns of one colour are coupled to each other (upwind3's +-2 neighbours, stub columns), so updating x in
-// place would make the result depend on which workgroup ran first.  The caller ping-pongs the buffers (multilevel.hip).
+// place would make the result depend on which workgroup ran first.  The caller ping-pongs the buffers (mlcycle.hip).
 // Same products, same per-row summation order, same substitution order as the two-kernel path => identical bits.
 template <int P, class FT, class VT>
 __global__ __launch_bounds__ (GS_THREADS)

@@ -3,8 +3,9 @@
 // A level of a few thousand rows costs the cycle ~200 us whatever its size -- 16 launches at their latency floor -- while
 // a dense inverse applied as ONE matrix-vector product costs its bytes: n^2 x 4 at f32, 35 us for the 7177 rows of the 1
 // degree hierarchy's fifth level.  So the hierarchy now stops at <= 8000 rows instead of <= 3000 (nkp_tuning.ml_coarsest_rows),
-// which needs an inverse of that size inside the setup budget: 2 n^3 = 7.4e11 flops.  The unblocked elimination of
-// multilevel.hip (four launches and two sweeps over both matrices per pivot) moves 32 n^3 bytes -- 3.1 s at n = 7177.
+// which needs an inverse of that size inside the setup budget: 2 n^3 = 7.4e11 flops.  The unblocked elimination at the
+// end of this file (four launches and two sweeps over both matrices per pivot) moves 32 n^3 bytes -- 3.1 s at n = 7177; it
+// stays as the pivoted fallback.
 //
 // Here: in-place block Gauss-Jordan, 64 x 64 blocks, no pivoting across blocks (the operator is the Galerkin product of an
 // M-matrix: elimination without pivoting is stable; a pivot below 1e-14 of the largest diagonal entry raises a flag and the
@@ -334,4 +335,108 @@ void launch_dense_matvec_f32_batch (int K, const float *Minv, int ld, const doub
    if (K == 2) hipLaunchKernelGGL ((dense_matvec_f32_batch_kernel<2>), grid, dim3 (256), 0, st, Minv, ld, x, y, n);
    else if (K == 4) hipLaunchKernelGGL ((dense_matvec_f32_batch_kernel<4>), grid, dim3 (256), 0, st, Minv, ld, x, y, n);
    else hipLaunchKernelGGL ((dense_matvec_f32_batch_kernel<8>), grid, dim3 (256), 0, st, Minv, ld, x, y, n);
+}
+
+// ---------------------------------------------------------------- the pivoted routine (unblocked)
+// Gauss-Jordan with partial pivoting, one elimination step = four small launches; the same operations as the host routine
+// of ml_plan.cpp (swap, scale the pivot row by the reciprocal, subtract f x pivot row from every other row), every element updated
+// by one multiply and one subtract, so the result has the same bits -- and a 1450-row inverse takes 40 ms instead of the
+// second it cost on the host (a third of the whole 1 degree setup).
+namespace {
+
+__global__ void gj_pivot_kernel (const double *__restrict__ a, int n, int k, int *__restrict__ piv, double *__restrict__ pivval)
+{
+   __shared__ double smax[256];
+   __shared__ int sidx[256];
+   double mx = -1.0;
+   int p = k;
+   for (int i = k + (int) threadIdx.x; i < n; i += 256) {
+      const double v = fabs (a[(size_t) i * n + k]);
+      if (v > mx) { mx = v; p = i; }               // ascending i per thread: the first maximum wins
+   }
+   smax[threadIdx.x] = mx;
+   sidx[threadIdx.x] = p;
+   __syncthreads ();
+   for (int off = 128; off > 0; off >>= 1) {
+      if ((int) threadIdx.x < off) {
+         const double o = smax[threadIdx.x + off];
+         const int oi = sidx[threadIdx.x + off];
+         if (o > smax[threadIdx.x] || (o == smax[threadIdx.x] && oi < sidx[threadIdx.x])) { smax[threadIdx.x] = o; sidx[threadIdx.x] = oi; }
+      }
+      __syncthreads ();
+   }
+   if (threadIdx.x == 0) {
+      piv[0] = sidx[0];
+      if (!(smax[0] > 0.0)) piv[1] = 1;            // singular
+      pivval[0] = a[(size_t) sidx[0] * n + k];
+   }
+}
+
+__global__ void gj_swap_scale_kernel (double *__restrict__ a, double *__restrict__ inv, int n, int k, const int *__restrict__ piv, const double *__restrict__ pivval)
+{
+   const int c = blockIdx.x * 256 + threadIdx.x;
+   if (c >= n) return;
+   const int p = piv[0];
+   const double r = 1.0 / pivval[0];
+   double *m[2] = { a, inv };
+   for (int w = 0; w < 2; w++) {
+      const double vk = m[w][(size_t) k * n + c], vp = m[w][(size_t) p * n + c];
+      m[w][(size_t) k * n + c] = vp * r;
+      if (p != k) m[w][(size_t) p * n + c] = vk;
+   }
+}
+
+__global__ void gj_column_kernel (const double *__restrict__ a, int n, int k, double *__restrict__ fcol)
+{
+   const int i = blockIdx.x * 256 + threadIdx.x;
+   if (i < n) fcol[i] = a[(size_t) i * n + k];
+}
+
+__global__ void gj_update_kernel (double *__restrict__ a, double *__restrict__ inv, int n, int k, const double *__restrict__ fcol)
+{
+   const int i = blockIdx.y;
+   const int c = blockIdx.x * 256 + threadIdx.x;
+   if (c >= n || i == k) return;
+   const double f = fcol[i];
+   if (f == 0.0) return;
+   a[(size_t) i * n + c] -= f * a[(size_t) k * n + c];
+   inv[(size_t) i * n + c] -= f * inv[(size_t) k * n + c];
+}
+
+}  // namespace
+
+// a (device, row-major n x n) is destroyed, *inv_out receives a device buffer with the inverse; false if singular / no memory
+bool dense_inverse_device (int n, const std::vector<double> &host_a, double **inv_out, size_t *bytes, hipStream_t st)
+{
+   double *a = nullptr, *inv = nullptr, *fcol = nullptr, *pivval = nullptr;
+   int *piv = nullptr;
+   const size_t nn = (size_t) n * n;
+   bool ok = hipMalloc ((void **) &a, nn * sizeof (double)) == hipSuccess && hipMalloc ((void **) &inv, nn * sizeof (double)) == hipSuccess &&
+             hipMalloc ((void **) &fcol, (size_t) n * sizeof (double)) == hipSuccess && hipMalloc ((void **) &pivval, sizeof (double)) == hipSuccess &&
+             hipMalloc ((void **) &piv, 2 * sizeof (int)) == hipSuccess;
+   if (ok) {
+      std::vector<double> eye (nn, 0.0);
+      for (int i = 0; i < n; i++) eye[(size_t) i * n + i] = 1.0;
+      ok = hipMemcpy (a, host_a.data (), nn * sizeof (double), hipMemcpyHostToDevice) == hipSuccess &&
+           hipMemcpy (inv, eye.data (), nn * sizeof (double), hipMemcpyHostToDevice) == hipSuccess && hipMemset (piv, 0, 2 * sizeof (int)) == hipSuccess;
+   }
+   if (ok) {
+      const int cb = (n + 255) / 256;
+      for (int k = 0; k < n; k++) {
+         hipLaunchKernelGGL (gj_pivot_kernel, dim3 (1), dim3 (256), 0, st, a, n, k, piv, pivval);
+         hipLaunchKernelGGL (gj_swap_scale_kernel, dim3 (cb), dim3 (256), 0, st, a, inv, n, k, piv, pivval);
+         hipLaunchKernelGGL (gj_column_kernel, dim3 (cb), dim3 (256), 0, st, a, n, k, fcol);
+         hipLaunchKernelGGL (gj_update_kernel, dim3 (cb, n), dim3 (256), 0, st, a, inv, n, k, fcol);
+      }
+      int flags[2] = { 0, 0 };
+      ok = hipMemcpyAsync (flags, piv, sizeof flags, hipMemcpyDeviceToHost, st) == hipSuccess && hipStreamSynchronize (st) == hipSuccess && flags[1] == 0;
+   }
+   if (a) (void) hipFree (a);
+   if (fcol) (void) hipFree (fcol);
+   if (pivval) (void) hipFree (pivval);
+   if (piv) (void) hipFree (piv);
+   if (!ok) { if (inv) (void) hipFree (inv); return false; }
+   *inv_out = inv;
+   *bytes += nn * sizeof (double);
+   return true;
 }

@@ -137,7 +137,7 @@ struct Planner {
       rings = 1;
       nkp_tuning tune;
       bool range_error = false;
-      if (dist_resolve_tuning (&o, &tune, &range_error) == NKP_OK) {      // a struct of the wrong size is reported by the create call itself
+      if (resolve_tuning (&o, &tune, &range_error) == NKP_OK) {      // a struct of the wrong size is reported by the create call itself
          if (!tune.dist_ras) want_ras = 0;
          rings = tune.dist_ras_rings > 0 ? tune.dist_ras_rings : 1;
       }

@@ -2,23 +2,12 @@
 // part of the C ABI, so everything is hidden from the dynamic symbol table.
 #pragma once
 #include "../../include/nkp.h"
+#include "tuning.h"
 
 #include <stdint.h>
 
 #include <string>
 #include <vector>
-
-#define NKP_PRIVATE __attribute__ ((visibility ("hidden")))
-
-// ---- what the plan needs from solver.hip (defined there, once) -------------------------------------------------------------
-// the error reporter behind nkp_last_error: formats the calling thread's message and returns `code`
-NKP_PRIVATE int fail (int code, const char *fmt, ...) __attribute__ ((format (printf, 2, 3)));
-// a step that reports on behalf of all ranks keeps a rank's own message across the collective
-NKP_PRIVATE std::string last_error_message ();
-NKP_PRIVATE void restore_error_message (const std::string &text);
-// solver.hip's resolve_tuning: the caller's knobs, or the defaults + environment; *range_error tells a value out of range (out
-// is filled) from a struct of the wrong size (out is not)
-NKP_PRIVATE int dist_resolve_tuning (const nkp_options *opt, nkp_tuning *out, bool *range_error);
 
 // ---- the plan ---------------------------------------------------------------------------------------------------------------
 struct DistPlan {

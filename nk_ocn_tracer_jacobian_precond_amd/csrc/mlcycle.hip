@@ -1,0 +1,282 @@
+// Multilevel water-column preconditioner: the V(nu, nu) cycle on the hierarchy ml_setup built (multilevel.hip), for one
+// right-hand side and for K interleaved ones, and the measurement helpers of bench.py and the probes.  Launchers only: the
+// kernels are colblock.hip, spmv.hip, blas1.hip, batch.hip, dense.hip and mltail.hip.
+#include "nkp_dev.h"
+#include "multilevel.h"
+
+// ================================================================ cycle
+// one Gauss-Seidel half sweep over colour c.  Fused path: one launch, x ping-pongs between the level's two buffers (the
+// new values of colour c go where the other colour's current values are if the level is incoherent, else to the other
+// buffer).  Two-kernel path: residual SpMV of the colour's rows, then the column solves accumulate into x in place.
+// column solves of colour c: levels with few columns run one column per WAVE (colblock_apply_kernel: one round trip for the
+// column's right-hand side and factors, the substitution by lane broadcasts) -- with thousands of idle wave slots its
+// ~5 us beat the 12-16 us latency floor of the lane-per-column kernels, which only win when the chip is full
+static void column_solves (const MlHierarchy &H, MlLevel &V, int c, const double *rhs, double *x, int accumulate, hipStream_t st)
+{
+   if (V.wave_columns) {
+      if (H.f32) launch_colblock_apply_range_r32 (V.B, V.color_blk[c], V.color_blk[c + 1], rhs, x, accumulate, st);
+      else launch_colblock_apply_range (V.B, V.color_blk[c], V.color_blk[c + 1], rhs, x, accumulate, st);
+   } else
+      launch_colblock_apply_lanes (V.B, V.color_grp[c], V.color_grp[c + 1], rhs, x, accumulate, st);
+}
+
+static void gs_half (const MlHierarchy &H, MlLevel &V, int c, bool fused, hipStream_t st)
+{
+   if (fused) {
+      const int out = (V.cur[0] != V.cur[1]) ? V.cur[1 - c] : 1 - V.cur[c];
+      const int rows0 = (int) V.rows0;
+      // (the launchers cannot refuse: ml_setup clears gs_ok / wave_fused for a level whose storage they do not serve)
+      if (V.wave_fused) launch_gs_wave (V.L, V.B, V.color_blk[c], V.color_blk[c + 1], V.xbuf (V.cur[0]), V.xbuf (V.cur[1]), rows0, V.b, V.xbuf (out), H.f32, st);
+      else (void) launch_gs_fused (V.L, V.B, V.color_grp[c], V.color_grp[c + 1], V.xbuf (V.cur[0]), V.xbuf (V.cur[1]), rows0, V.b, V.xbuf (out), st);
+      V.cur[c] = out;
+      return;
+   }
+   launch_csr_residual_range (V.L, V.color_rb[c], V.color_rb[c + 1], V.x, V.b, V.r, st);
+   column_solves (H, V, c, V.r, V.x, 1, st);
+}
+
+static void gs_sweep (const MlHierarchy &H, MlLevel &V, bool reverse, bool fused, hipStream_t st)
+{
+   for (int step = 0; step < 2; step++) gs_half (H, V, reverse ? 1 - step : step, fused, st);
+}
+
+static void ml_cycle (MlHierarchy &H, int l, hipStream_t st)
+{
+   MlLevel &V = H.lev[l];
+   V.cur[0] = V.cur[1] = 0;
+   if (l == H.tail_from && H.coarse_inv && H.gamma_to <= H.gamma_from && ml_tail_launch (H, l, st) == 0) return;
+   if (l == (int) H.lev.size () - 1) {
+      if (H.coarse_inv) {
+         if (H.coarse_invf) launch_dense_matvec_f32 (H.coarse_invf, H.coarse_ldf, V.b, V.x, (int) V.n, st);
+         else launch_dense_matvec (H.coarse_inv, V.b, V.x, (int) V.n, st);
+         return;
+      }
+      // no dense inverse: many sweeps of the column smoother from x = 0 (what is left here is diagonally dominant)
+      const int sweeps = H.tune->ml_coarsest_sweeps > 0 ? H.tune->ml_coarsest_sweeps : 30;
+      launch_fill (V.x, 0.0, V.n, st);
+      column_solves (H, V, 0, V.b, V.x, 0, st);
+      gs_half (H, V, 1, false, st);
+      for (int s = 1; s < sweeps; s++) gs_sweep (H, V, s & 1, false, st);
+      return;
+   }
+   // ml_fused_max_cols: the fused half sweep only on levels with at most that many columns (the launch-bound end)
+   const int fused_max = H.tune->ml_fused_max_cols;
+   const bool fused = V.wave_fused || (H.fused && V.B.gs_ok && (fused_max <= 0 || V.color_grp[2] * V.B.gw <= fused_max));
+   // pre-smoothing from x = 0: the first half-sweep needs no SpMV (r = b on colour 0)
+   launch_fill (V.x, 0.0, V.n, st);
+   if (fused) {
+      // colour 0's first values go to the second buffer: the level starts incoherent, and the odd number of fused half
+      // sweeps that follows (colour 1, then nu - 1 full sweeps) ends coherent
+      if (V.wave_fused) column_solves (H, V, 0, V.b, V.x2, 0, st);
+      else launch_colblock_apply_lanes (V.B, V.color_grp[0], V.color_grp[1], V.b, V.x2, 0, st);
+      V.cur[0] = 1;
+      gs_half (H, V, 1, true, st);
+   } else {
+      column_solves (H, V, 0, V.b, V.x, 0, st);
+      gs_half (H, V, 1, false, st);
+   }
+   const int nu = (l >= H.coarse_from) ? H.nu_coarse : H.nu;
+   for (int s = 1; s < nu; s++) gs_sweep (H, V, false, fused, st);
+   // coarse-grid correction; levels in [gamma_from, gamma_to) repeat it on the updated residual, which by the
+   // Galerkin property is the second coarse iteration of a W-cycle (NKP_ML_GAMMA_FROM / NKP_ML_GAMMA_TO, default off)
+   MlLevel &C = H.lev[l + 1];
+   const int gamma = (l >= H.gamma_from && l < H.gamma_to) ? 2 : 1;
+   for (int g = 0; g < gamma; g++) {
+      launch_csr_spmv (V.L, V.xnow (), V.r, V.b, 1, st);
+      launch_restrict_sum (V.rptr, V.ridx, V.r, C.b, V.nc, st);
+      ml_cycle (H, l + 1, st);
+      launch_prolong_add (V.cmap, C.xnow (), V.xnow (), V.n, H.omega, st);
+   }
+   for (int s = 0; s < nu; s++) gs_sweep (H, V, true, fused, st);
+}
+
+void ml_apply (MlHierarchy &H, const double *r, double *z, hipStream_t st)
+{
+   MlLevel &V = H.lev[0];
+   launch_gather (H.perm0, r, V.b, V.n, st);
+   ml_cycle (H, 0, st);
+   launch_scatter (H.perm0, V.xnow (), z, V.n, st);
+}
+
+// ================================================================ the cycle on K interleaved right-hand sides
+int ml_batch_prepare (MlHierarchy &H, int K)
+{
+   if (K != 2 && K != 4 && K != 8) return -1;
+   if (H.batch_K >= K) return 0;
+   // all or nothing: the narrower vectors go first, and a failure leaves none behind (batch_K = 0 says so to the retry)
+   auto drop = [&H] () {
+      for (MlLevel &V : H.lev)
+         for (double **p : { &V.bx, &V.bx2, &V.bb, &V.br })
+            if (*p) {
+               (void) hipFree (*p);
+               *p = nullptr;
+               H.device_bytes -= (size_t) (V.n ? V.n : 1) * (size_t) H.batch_K * sizeof (double);
+            }
+      H.batch_K = 0;
+   };
+   drop ();
+   for (MlLevel &V : H.lev) {
+      for (double **p : { &V.bx, &V.bx2, &V.bb, &V.br }) {
+         const size_t bytes = (size_t) (V.n ? V.n : 1) * (size_t) K * sizeof (double);
+         void *q = nullptr;
+         if (hipMalloc (&q, bytes) != hipSuccess || hipMemset (q, 0, bytes) != hipSuccess) {
+            if (q) (void) hipFree (q);
+            // the vectors made so far were sized for K
+            H.batch_K = K;
+            drop ();
+            (void) hipGetLastError ();      // the out-of-memory error is answered here, not by the next call that looks
+            return -2;
+         }
+         *p = (double *) q;
+         H.device_bytes += bytes;
+      }
+   }
+   H.batch_K = K;
+   return 0;
+}
+
+static void column_solves_batch (const MlHierarchy &H, MlLevel &V, int K, int c, const double *rhs, double *x, int accumulate, hipStream_t st)
+{
+   // the packed lane layout has a two-system kernel; every other level takes the wave-per-column kernel (which reads the
+   // f64 factors and rounds them like the f32 layouts store them: same values)
+   if (V.wave_columns || launch_colblock_apply_lanes_batch (K, V.B, V.color_grp[c], V.color_grp[c + 1], rhs, x, accumulate, st) != 0)
+      launch_colblock_apply_wave_batch (K, V.B, V.color_blk[c], V.color_blk[c + 1], rhs, x, accumulate, H.f32, st);
+}
+
+static void gs_half_batch (const MlHierarchy &H, MlLevel &V, int K, int c, hipStream_t st)
+{
+   if (V.wave_fused) {
+      const int out = (V.bcur[0] != V.bcur[1]) ? V.bcur[1 - c] : 1 - V.bcur[c];
+      launch_gs_wave_batch (K, V.L, V.B, V.color_blk[c], V.color_blk[c + 1], V.bxbuf (V.bcur[0]), V.bxbuf (V.bcur[1]), (int) V.rows0, V.bb, V.bxbuf (out), H.f32, st);
+      V.bcur[c] = out;
+      return;
+   }
+   launch_csr_spmv_batch (K, V.L, V.color_rb[c], V.color_rb[c + 1], V.bx, V.br, V.bb, 1, st);
+   column_solves_batch (H, V, K, c, V.br, V.bx, 1, st);
+}
+
+static void ml_cycle_batch (MlHierarchy &H, int K, int l, hipStream_t st)
+{
+   MlLevel &V = H.lev[l];
+   const int64_t nk = V.n * K;
+   V.bcur[0] = V.bcur[1] = 0;
+   if (l == (int) H.lev.size () - 1) {
+      if (H.coarse_inv) {
+         if (H.coarse_invf) launch_dense_matvec_f32_batch (K, H.coarse_invf, H.coarse_ldf, V.bb, V.bx, (int) V.n, st);
+         else launch_dense_matvec_batch (K, H.coarse_inv, V.bb, V.bx, (int) V.n, st);
+         return;
+      }
+      const int sweeps = H.tune->ml_coarsest_sweeps > 0 ? H.tune->ml_coarsest_sweeps : 30;
+      launch_fill (V.bx, 0.0, nk, st);
+      column_solves_batch (H, V, K, 0, V.bb, V.bx, 0, st);
+      launch_csr_spmv_batch (K, V.L, V.color_rb[1], V.color_rb[2], V.bx, V.br, V.bb, 1, st);
+      column_solves_batch (H, V, K, 1, V.br, V.bx, 1, st);
+      for (int s = 1; s < sweeps; s++)
+         for (int step = 0; step < 2; step++) {
+            const int c = (s & 1) ? 1 - step : step;
+            launch_csr_spmv_batch (K, V.L, V.color_rb[c], V.color_rb[c + 1], V.bx, V.br, V.bb, 1, st);
+            column_solves_batch (H, V, K, c, V.br, V.bx, 1, st);
+         }
+      return;
+   }
+   launch_fill (V.bx, 0.0, nk, st);
+   if (V.wave_fused) {
+      column_solves_batch (H, V, K, 0, V.bb, V.bx2, 0, st);
+      V.bcur[0] = 1;
+      gs_half_batch (H, V, K, 1, st);
+   } else {
+      column_solves_batch (H, V, K, 0, V.bb, V.bx, 0, st);
+      gs_half_batch (H, V, K, 1, st);
+   }
+   const int nu = (l >= H.coarse_from) ? H.nu_coarse : H.nu;
+   for (int s = 1; s < nu; s++) { gs_half_batch (H, V, K, 0, st); gs_half_batch (H, V, K, 1, st); }
+   MlLevel &C = H.lev[l + 1];
+   const int gamma = (l >= H.gamma_from && l < H.gamma_to) ? 2 : 1;
+   for (int g = 0; g < gamma; g++) {
+      launch_csr_spmv_batch (K, V.L, 0, V.L.nrowblk, V.bxnow (), V.br, V.bb, 1, st);
+      launch_restrict_sum_batch (K, V.rptr, V.ridx, V.br, C.bb, V.nc, st);
+      ml_cycle_batch (H, K, l + 1, st);
+      launch_prolong_add_batch (K, V.cmap, C.bxnow (), V.bxnow (), V.n, H.omega, st);
+   }
+   for (int s = 0; s < nu; s++) { gs_half_batch (H, V, K, 1, st); gs_half_batch (H, V, K, 0, st); }
+}
+
+void ml_apply_batch (MlHierarchy &H, int K, const double *r, double *z, hipStream_t st)
+{
+   MlLevel &V = H.lev[0];
+   launch_gather_batch (K, H.perm0, r, V.bb, V.n, st);
+   ml_cycle_batch (H, K, 0, st);
+   launch_scatter_batch (K, H.perm0, V.bxnow (), z, V.n, st);
+}
+
+// the same from / to per-system vectors: src[k] = residual of system k (NULL: zeros), z = the K corrections interleaved,
+// dst[k] (may be NULL) = a plain copy of column k; src_scale (row-weighted iteration): the residuals are src[k] times it, row by row.
+// A Krylov step with chained cycles comes here several times: a cycle starts from its right-hand side V.bb alone (x is
+// filled, the buffer selectors reset), so nothing of the previous application is read.
+void ml_apply_batch_split (MlHierarchy &H, int K, const double *const *src, double *z, double *const *dst, hipStream_t st, const double *src_scale)
+{
+   MlLevel &V = H.lev[0];
+   launch_gather_interleave (K, H.perm0, src, V.bb, V.n, st, src_scale);
+   ml_cycle_batch (H, K, 0, st);
+   launch_scatter_split (K, H.perm0, V.bxnow (), z, dst, V.n, st);
+}
+
+// the same on the extended rows of a rank of the row-distributed flavour: level 0 has n_own own rows followed by the overlap
+// rows, whose residuals are the K-interleaved halo rows halo[sel[.] * K + k] (sel NULL: halo is the K-interleaved block of the
+// overlap rows in their own order); z and dst receive the own rows only
+void ml_apply_batch_split_ext (MlHierarchy &H, int K, const double *const *src, const double *halo, const int *sel, int64_t n_own, double *z,
+                               double *const *dst, hipStream_t st)
+{
+   MlLevel &V = H.lev[0];
+   if (sel) launch_gather_interleave_ext (K, H.perm0, src, halo, sel, n_own, V.bb, V.n, st);
+   else launch_gather_interleave_ext_block (K, H.perm0, src, halo, n_own, V.bb, V.n, st);
+   ml_cycle_batch (H, K, 0, st);
+   launch_scatter_split_own (K, H.perm0, V.bxnow (), z, dst, n_own, V.n, st);
+}
+
+// ================================================================ measurement helpers (bench.py, probes)
+// one half sweep of level 0, colour 0: the residual rows (which = 0) or the column solves (which = 1)
+void ml_time_piece (MlHierarchy &H, int which, hipStream_t st)
+{
+   MlLevel &V = H.lev[0];
+   if (H.lev.size () < 2) return;
+   if (which == 0) launch_csr_residual_range (V.L, V.color_rb[0], V.color_rb[1], V.x, V.b, V.r, st);
+   else launch_colblock_apply_lanes (V.B, V.color_grp[0], V.color_grp[1], V.r, V.x, 1, st);
+}
+
+// compulsory HBM bytes (every array element counted once per kernel that must touch it):
+//  which 0: residual rows of level 0, colour 0: its entries (value + column), row pointers, b in, r out, x once
+//  which 1: column solves of level 0, colour 0: factors, r in, x in and out
+//  which 2: one whole V(nu, nu) cycle
+int64_t ml_bytes (const MlHierarchy &H, int which)
+{
+   if (H.lev.size () < 2) return 0;
+   auto level_piece = [&] (const MlLevel &V, int colour, int what) -> int64_t {
+      const int64_t rows = colour == 0 ? V.rows0 : V.n - V.rows0;
+      const int64_t vb = V.L.valf ? 4 : 8, fb = V.B.fac_tf ? 4 : 8;
+      if (what == 0) {
+         // entries of the colour's rows: the colour-major CSR keeps them contiguous; split nnz by rows as an estimate is not
+         // needed -- the host knows the exact count only at setup, so use the level's average row length
+         const double per_row = V.n ? (double) V.L.nnz / (double) V.n : 0.0;
+         return (int64_t) (per_row * (double) rows * (double) (vb + 4)) + rows * (4 + 8 + 8) + V.n * 8;
+      }
+      return rows * ((2 * V.B.P + 1) * fb + 8 + 8 + 8);
+   };
+   if (which == 0 || which == 1) return level_piece (H.lev[0], 0, which);
+   int64_t total = 0;
+   for (size_t l = 0; l + 1 < H.lev.size (); l++) {
+      const MlLevel &V = H.lev[l];
+      const int nu = ((int) l >= H.coarse_from) ? H.nu_coarse : H.nu;
+      for (int c = 0; c < 2; c++) {
+         total += (int64_t) (2 * nu) * level_piece (V, c, 1);                       // column solves: nu pre + nu post sweeps
+         total += (int64_t) (2 * nu - (c == 0 ? 1 : 0)) * level_piece (V, c, 0);    // residual rows (the first half sweep needs none)
+      }
+      total += V.L.nnz * ((V.L.valf ? 4 : 8) + 4) + V.n * (4 + 8 + 8 + 8);         // full residual before the restriction
+      total += V.n * (8 + 4) + V.nc * (8 + 4);                                      // restriction
+      total += V.n * (8 + 8 + 4) + V.nc * 8;                                        // prolongation
+   }
+   const int64_t ncoarse = H.lev.back ().n;
+   total += ncoarse * ncoarse * 8 + 2 * ncoarse * 8;                                // dense coarsest solve
+   total += H.lev[0].n * (8 + 8 + 4) * 2;                                           // gather in, scatter out
+   return total;
+}

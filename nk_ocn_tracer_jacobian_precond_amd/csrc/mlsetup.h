@@ -1,5 +1,5 @@
 // Device-side construction of the multilevel hierarchy (see mlsetup.hip): the row- and entry-level passes of the setup
-// as HIP kernels.  Column-level decisions (a few 10^4 .. 10^5 items per level) stay on the host, in multilevel.hip.
+// as HIP kernels.  Column-level decisions (a few 10^4 .. 10^5 items per level) stay on the host, in ml_plan.cpp.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -54,10 +54,10 @@ int scan_exclusive (const int *d_in, int *d_out, int64_t n, hipStream_t st, int6
 // col_of[r] = column block of row r
 int rows_to_cols (const int *d_blk_start, int ncol, int *d_col_of, hipStream_t st);
 
-// low-order twin of A (multilevel.hip: build_low_order), natural order
+// low-order twin of A (ml_plan.cpp: build_low_order), natural order
 int twin (int64_t n, const int *d_rowptr, const int *d_colind, const double *d_val, const int *d_col_of, DevCsr &L, hipStream_t st);
 
-// ---- connectivity-aware coarse cells of one coarsening step (multilevel.hip: split_aggregate)
+// ---- connectivity-aware coarse cells of one coarsening step (ml_plan.cpp: split_aggregate)
 struct AggregateIn {
    int64_t n = 0;
    int ncol = 0;

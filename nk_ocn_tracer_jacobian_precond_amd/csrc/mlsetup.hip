@@ -1,12 +1,12 @@
 // Device-side construction of the multilevel hierarchy (round 3).
 //
 // What it replaces: the host threads that built the low-order twin, the connectivity-aware coarse cells, the Galerkin
-// products and the colour-major operators of every level (multilevel.hip, rounds 1-2) -- the stand-in of SuperLU's
+// products and the colour-major operators of every level (now ml_plan.cpp, rounds 1-2) -- the stand-in of SuperLU's
 // symbolic + numeric factorisation (reference src/solve_ABglobal.c:349-360, src/SuperLU_brief_tree.txt:5-14), which at
 // 1 degree cost five solves' worth of host time.  Here every row- and entry-level pass is a kernel; only column-level
 // bookkeeping (10^4-10^5 items) goes through the host.
 //
-// Contract: the hierarchy is ENTRY FOR ENTRY the one the host routines of multilevel.hip build (which still serve the
+// Contract: the hierarchy is ENTRY FOR ENTRY the one the host routines of ml_plan.cpp build (which still serve the
 // small levels and the no-GPU plan tests): same set numbering (a set's id is the rank of its lowest row), same tie rules,
 // same summation order in every floating-point sum.  tests/test_gpu_setup.py compares the two.
 //
@@ -537,7 +537,7 @@ int row_blocks (const int *d_rowptr, int64_t r0, int64_t r1, int **d_out, int *n
 }
 
 // ================================================================ connectivity-aware coarse cells
-// multilevel.hip: split_aggregate, pass for pass.  depth (r) = ktop[col] + (r - blk_start[col]).
+// ml_plan.cpp: split_aggregate, pass for pass.  depth (r) = ktop[col] + (r - blk_start[col]).
 struct AggDev {
    int64_t n;
    int ncol;

@@ -1,4 +1,4 @@
-// Multilevel water-column preconditioner: data structures (see multilevel.hip).
+// Multilevel water-column preconditioner: data structures, setup (multilevel.hip) and cycle (mlcycle.hip).
 #pragma once
 #include "nkp_dev.h"
 

@@ -4,13 +4,11 @@
 #include <stdint.h>
 
 #include "../../include/nkp.h"
+#include "tuning.h"
 
 #include <type_traits>
 #include <utility>
 #include <vector>
-
-// the tuning a launcher uses when its object carries none: the plain defaults (no environment)
-const nkp_tuning &nkp_builtin_tuning ();
 
 #define NKP_LDSRES_CH 16         // substitution steps per factor chunk of colblock_apply_ldsres_kernel (group lengths are padded to it)
 #define NKP_WAVE 64
@@ -324,6 +322,9 @@ void launch_dense_matvec_f32 (const float *Minv, int ld, const double *x, double
 void launch_dense_matvec_f32_batch (int K, const float *Minv, int ld, const double *x, double *y, int n, hipStream_t st);
 int dense_inverse_blocked_device (int n, const int *h_rowptr, const int *h_col, const double *h_val, double **inv_out, float **invf_out, int *ldf_out,
                                   size_t *bytes, hipStream_t st);
+// the pivoted routine: unblocked Gauss-Jordan with partial pivoting on the dense matrix host_a (row-major n x n); *inv_out
+// receives a device buffer with the inverse; false if singular / no memory
+bool dense_inverse_device (int n, const std::vector<double> &host_a, double **inv_out, size_t *bytes, hipStream_t st);
 
 // ---------------------------------------------------------------- K interleaved right-hand sides (batch.hip; X[i * K + k], K = 2 or 4)
 // scale (may be NULL), here and below: the row scaling of the row-weighted iteration folded into the kernel, one rounded

@@ -2,7 +2,7 @@
 //
 // Everything the setup decided from the pattern and the coarse cells stays: allocations, colour-major orders, row blocks,
 // lane layouts, transfer maps.  What changes is a stream over entries per level:
-//   twin      L0 = A + D - diag(rowsum D), D_ij = max(0, -a_ij, -a_ji) between water columns (multilevel.hip:
+//   twin      L0 = A + D - diag(rowsum D), D_ij = max(0, -a_ij, -a_ji) between water columns (ml_plan.cpp:
 //             build_low_order), one thread per row of A in A's stored order, each value written straight into its
 //             colour-major slot of level 0 (tslot, built once);
 //   Galerkin  every entry of level l + 1 is the sum of its fine entries of level l, in the order the setup summed them:
@@ -16,6 +16,7 @@
 #include "refactor.h"
 
 #include "mlsetup.h"
+#include "ml_plan.h"
 
 #include <stdio.h>
 #include <string.h>
@@ -235,7 +236,7 @@ int rf_build_maps (RefactorWork &W, const MlHierarchy &H, const CsrDev &A, hipSt
    if (hipStreamSynchronize (st) != hipSuccess) return -3;
    rf_free_maps (W);
    const nkp_tuning &T = H.tune ? *H.tune : nkp_builtin_tuning ();
-   const int nt = T.setup_threads > 0 ? T.setup_threads : (int) std::min (32u, std::max (1u, std::thread::hardware_concurrency ()));
+   const int nt = mlp::setup_thread_count (T);
    // host copies of the pattern: A (natural order), every level (colour-major), the transfer maps
    std::vector<int> arp, aci, perm0, blk0;
    std::vector<std::vector<int>> rp (nlev), ci (nlev), cmap (nlev), rptr (nlev), ridx (nlev);

@@ -1,5 +1,5 @@
 """Independent scipy restatement of the multilevel water-column preconditioner, for cross-checking the HIP
-implementation (csrc/multilevel.hip) on small grids.  TEST INFRASTRUCTURE: slow, sequential, never shipped.
+implementation (csrc/ml_plan.cpp) on small grids.  TEST INFRASTRUCTURE: slow, sequential, never shipped.
 
 Same rules, written from the description in DESIGN.md section 2, not from the C++:
   * low-order twin: L = A + D - diag(rowsum D), D_ij = max(0, -a_ij, -a_ji) for i, j in different water columns

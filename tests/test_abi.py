@@ -97,14 +97,15 @@ def test_no_ablation_kernels_in_the_shipped_library():
 
 
 def test_kernels_and_cycle_do_not_read_the_environment():
-    """Tuning knobs reach the kernels through nkp_tuning, resolved once per nkp_create (csrc/solver.hip: nkp_default_tuning);
-    no launcher, cycle or setup routine calls getenv."""
+    """Tuning knobs reach the kernels through nkp_tuning, resolved once per nkp_create (csrc/tuning.cpp: nkp_default_tuning);
+    no launcher, cycle, planner or setup routine calls getenv."""
     csrc = os.path.join(ROOT, "nk_ocn_tracer_jacobian_precond_amd", "csrc")
-    for name in ("spmv.hip", "colblock.hip", "multilevel.hip", "mlsetup.hip", "mltail.hip", "blas1.hip", "dist_plan.cpp", "refactor_api.hip"):
+    for name in ("spmv.hip", "colblock.hip", "multilevel.hip", "mlsetup.hip", "mltail.hip", "blas1.hip", "dist_plan.cpp", "refactor_api.hip",
+                 "solver.hip", "ml_plan.cpp", "mlcycle.hip", "dense.hip", "refactor.hip", "batch.hip"):
         assert "getenv" not in open(os.path.join(csrc, name)).read(), name
-    text = open(os.path.join(csrc, "solver.hip")).read()
-    body = text[text.index('extern "C" int nkp_default_tuning'):text.index("static int resolve_tuning")]
-    assert text.count("getenv") == body.count("getenv")
+    text = open(os.path.join(csrc, "tuning.cpp")).read()
+    body = text[text.index('extern "C" int nkp_default_tuning'):text.index("int resolve_tuning")]
+    assert text.count("getenv") == body.count("getenv") > 0
 
 
 def test_tuning_struct_round_trip():

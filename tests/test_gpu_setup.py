@@ -1,7 +1,12 @@
 """The hierarchy the setup KERNELS build (csrc/mlsetup.hip: low-order twin, connectivity-aware coarse cells, Galerkin
-products, colour-major operators, transfer maps) against the one the host routines of csrc/multilevel.hip build -- the
-routines tests/test_ml_plan.py pins to the scipy restatement without a GPU.  Entry for entry, bit for bit; then the same
-right-hand side through both preconditioners.  NKP_ML_DEVICE_MIN is the smallest level (rows) the kernels take."""
+products, colour-major operators, transfer maps) against the one the host planner of csrc/ml_plan.cpp builds (uploaded and
+factored by csrc/multilevel.hip) -- the planner tests/test_ml_plan.py pins to the scipy restatement without a GPU.  Entry
+for entry, bit for bit; then the same right-hand side through both preconditioners.  NKP_ML_DEVICE_MIN is the smallest
+level (rows) the kernels take.  The host-built hierarchy itself is pinned to recorded hashes."""
+import hashlib
+import json
+import os
+
 import numpy as np
 import pytest
 
@@ -68,3 +73,33 @@ def test_device_built_hierarchy_solves(monkeypatch):
     assert out[0][3] == 0 and out[1][3] >= 2
     assert out[0][1] == out[1][1] and out[1][2] <= 1e-10
     assert np.array_equal(out[0][0], out[1][0])
+
+
+HOST_LEVEL_CASES = {"24x20x10-1": ((24, 20, 10), False, 1), "36x30x12-k33-2": ((36, 30, 12), True, 2)}
+
+
+def host_levels_sha256(grid, k33, cnt):
+    """sha256 of every array of the host-built hierarchy (NKP_ML_DEVICE_MIN = 2^40, NKP_ML_COARSEST_ROWS = 300 in the
+    environment) and of one preconditioner application"""
+    sha = lambda a: hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
+    p, blk, ci, cj = _problem(grid, 1.0, k33, cnt)
+    with solver.NkpSolver(p.rowptr, p.colind, p.nzval, blk, coupled_tracer_cnt=cnt, col_i=ci, col_j=cj, precond=solver.PRECOND_MULTILEVEL) as s:
+        assert s.get_int("ml_levels_on_device") == 0
+        levels = [{a: sha(s.ml_level_array(l, a)) for a in ARRAYS} for l in range(s.get_int("levels"))]
+        z = s.precond_apply(np.random.default_rng(5).standard_normal(p.flat_len))
+    return {"levels": levels, "precond_apply": sha(z)}
+
+
+@pytest.mark.parametrize("case", list(HOST_LEVEL_CASES))
+def test_host_built_hierarchy_equals_recorded(case, monkeypatch):
+    """the levels the host planner builds, and what multilevel.hip makes of them on the device, are the recorded ones"""
+    monkeypatch.setenv("NKP_ML_DEVICE_MIN", str(1 << 40))
+    monkeypatch.setenv("NKP_ML_COARSEST_ROWS", "300")
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ml_host_levels_sha256.json")) as f:
+        want = json.load(f)[case]
+    got = host_levels_sha256(*HOST_LEVEL_CASES[case])
+    assert len(got["levels"]) == len(want["levels"]) >= 3
+    for l, (a, b) in enumerate(zip(got["levels"], want["levels"])):
+        for name in ARRAYS:
+            assert a[name] == b[name], f"level {l}: {name} differs from the record"
+    assert got["precond_apply"] == want["precond_apply"]

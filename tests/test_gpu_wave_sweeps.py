@@ -40,7 +40,7 @@ SETTINGS = [("reference", dict(NKP_COLWAVE_MAX="0", NKP_ML_WAVE_FUSED="0")),
 
 
 def fine_level_colours(p):
-    """columns per colour of the fine level (multilevel.hip: (i + j) & 1 of the column's horizontal cell)"""
+    """columns per colour of the fine level (ml_plan.cpp: (i + j) & 1 of the column's horizontal cell)"""
     ci, cj = solver.column_coords(p.ind_i, p.ind_j, p.col_start(), 1)
     odd = int(((np.asarray(ci) + np.asarray(cj)) & 1).sum())
     return len(ci) - odd, odd

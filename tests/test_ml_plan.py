@@ -1,6 +1,13 @@
-"""Host-side aggregation of the multilevel preconditioner (nkp_ml_plan_host, csrc/multilevel.hip) against the
-independent scipy restatement tests/ml_reference.py: identical coarse cells and coarse columns on every level.
-No GPU needed: the plan is host code."""
+"""Host-side aggregation of the multilevel preconditioner (nkp_ml_plan_host, csrc/ml_plan.cpp) against the
+independent scipy restatement tests/ml_reference.py: identical coarse cells and coarse columns on every level; against
+recorded hashes on hierarchies of several levels, with and without grid positions; and once more from a stand-alone
+program built with the address and undefined-behaviour sanitizers.  No GPU needed: the plan is host code, compiled by
+the host compiler."""
+import hashlib
+import json
+import os
+import subprocess
+
 import numpy as np
 import pytest
 
@@ -37,3 +44,104 @@ def test_split_aggregation_matches_restatement(grid, refine, k33):
         nxt[cmaps[l]] = ref_of_fine
         to_ref = nxt
         assert _same_partition(colofs[l], levels[l].coarse_colid[to_ref]), f"coarse columns differ on level {l + 1}"
+
+
+# ---------------------------------------------------------------- recorded plans (tests/golden/ml_plan_sha256.json)
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PLAN_GRIDS = [((12, 10, 6), 1.0, False), ((24, 20, 10), 1.0, False), ((40, 46, 20), 12.0, True)]
+PLAN_CASES = [(g, r, k, geo) for g, r, k in PLAN_GRIDS for geo in (True, False)]
+PLAN_ROWS = {"12x10x6-geo": [383, 150], "12x10x6-graph": [383, 117],
+             "24x20x10-geo": [2813, 889, 275, 100], "24x20x10-graph": [2813, 767, 233, 82],
+             "40x46x20-geo": [21952, 6198, 1830, 529, 103], "40x46x20-graph": [21952, 5848, 1629, 510, 191]}
+
+
+def _case_name(grid, geo):
+    return "x".join(map(str, grid)) + ("-geo" if geo else "-graph")
+
+
+def _plan_input(grid, refine, k33):
+    p = synth.generate(imt=grid[0], jmt=grid[1], km=grid[2], adv="upwind3", hmix="isop", seed=2, u_scale=3.0 * refine,
+                       ah=4.0e6 * refine ** 2, isop_k33=k33)
+    blk = solver.column_blocks(p.col_start(), p.tracer_state_len, 1)
+    ci, cj = solver.column_coords(p.ind_i, p.ind_j, p.col_start(), 1)
+    return p, blk, ci, cj
+
+
+def _sha(a, dtype):
+    return hashlib.sha256(np.ascontiguousarray(a, dtype).tobytes()).hexdigest()
+
+
+def plan_sha256(grid, refine, k33, geo):
+    """rows per level and the sha256 of rows (int64), every cmap and every col_of (int32) of the plan at coarsest_rows = 200"""
+    p, blk, ci, cj = _plan_input(grid, refine, k33)
+    rows, cmaps, colofs = solver.ml_plan_host(p.rowptr, p.colind, p.nzval, blk, ci if geo else None, cj if geo else None, coarsest_rows=200)
+    return {"rows": [int(r) for r in rows], "sha256": {"rows": _sha(rows, np.int64), "cmap": [_sha(c, np.int32) for c in cmaps],
+                                                       "col_of": [_sha(c, np.int32) for c in colofs]}}
+
+
+@pytest.fixture(scope="module")
+def recorded_plans():
+    with open(os.path.join(ROOT, "tests", "golden", "ml_plan_sha256.json")) as f:
+        return json.load(f)
+
+
+@pytest.mark.parametrize("grid,refine,k33,geo", PLAN_CASES)
+def test_plan_equals_recorded(grid, refine, k33, geo, recorded_plans):
+    name = _case_name(grid, geo)
+    got = plan_sha256(grid, refine, k33, geo)
+    assert got["rows"] == PLAN_ROWS[name]
+    assert got == recorded_plans[name]
+
+
+# ---------------------------------------------------------------- the planner alone, under the sanitizers
+SANITIZE = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]
+# the sanitizer runtimes are linked into the program itself, so that it starts the same in whatever environment it inherits
+STATIC_RUNTIME = ["-static-libasan", "-static-libubsan"]
+
+
+@pytest.fixture(scope="module")
+def sanitized_planner(tmp_path_factory):
+    """tuning.cpp + ml_plan.cpp + dist_plan.cpp + tests/ml_plan_main.cpp as one program: the host units link without the HIP
+    runtime and without solver.o.  All six inputs have fewer than 200000 rows, below which for_row_chunks stays on the calling
+    thread: the run covers the planner's index arithmetic, not its row-parallel loops on more than one thread."""
+    d = tmp_path_factory.mktemp("ml_plan_asan")
+    probe = d / "probe.cpp"
+    probe.write_text("int main () { return 0; }\n")
+    if subprocess.run(["g++", "-fsanitize=address", *STATIC_RUNTIME, str(probe), "-o", str(d / "probe")], capture_output=True).returncode != 0:
+        pytest.skip("this compiler cannot link -fsanitize=address")
+    csrc = os.path.join(ROOT, "nk_ocn_tracer_jacobian_precond_amd", "csrc")
+    exe = str(d / "ml_plan_main")
+    cxx = ["g++", "-std=c++17", "-Wall", "-ffp-contract=off", "-pthread", *SANITIZE]
+    units = [os.path.join(ROOT, "tests", "ml_plan_main.cpp"), *(os.path.join(csrc, f) for f in ("tuning.cpp", "ml_plan.cpp", "dist_plan.cpp"))]
+    objs = [str(d / (os.path.basename(u) + ".o")) for u in units]
+    jobs = [subprocess.Popen([*cxx, "-c", u, "-o", o], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True) for u, o in zip(units, objs)]
+    for j in jobs:                                   # the four units compile side by side; any warning fails the build
+        out = j.communicate()[0]
+        assert j.returncode == 0 and not out.strip(), out
+    r = subprocess.run([*cxx, *STATIC_RUNTIME, *objs, "-o", exe], capture_output=True, text=True)
+    assert r.returncode == 0 and not r.stderr.strip(), r.stderr
+    return exe
+
+
+@pytest.mark.parametrize("grid,refine,k33,geo", PLAN_CASES)
+def test_plan_under_sanitizers(grid, refine, k33, geo, sanitized_planner, recorded_plans, tmp_path):
+    p, blk, ci, cj = _plan_input(grid, refine, k33)
+    path = str(tmp_path / "matrix.bin")
+    with open(path, "wb") as f:
+        np.array([p.rowptr.size - 1, p.colind.size, blk.size - 1, int(geo)], np.int64).tofile(f)
+        for a, dt in ((p.rowptr, np.int32), (p.colind, np.int32), (p.nzval, np.float64), (blk, np.int32), (ci, np.int32), (cj, np.int32)):
+            np.ascontiguousarray(a, dt).tofile(f)
+    env = {k: v for k, v in os.environ.items() if not k.startswith("NKP_")}        # defaults, whatever the caller tunes
+    r = subprocess.run([sanitized_planner, path, "200"], capture_output=True, text=True, env=env, timeout=300)
+    out = r.stdout + r.stderr
+    assert r.returncode == 0 and "runtime error" not in out and "AddressSanitizer" not in out, out
+    got = {"rows": [], "sha256": {"rows": None, "cmap": [], "col_of": []}}
+    for line in r.stdout.splitlines():
+        key, *vals = line.split()
+        if key == "levels":
+            got["rows"] = [int(v) for v in vals]
+        elif key == "rows":
+            got["sha256"]["rows"] = vals[0]
+        elif key in ("cmap", "col_of"):
+            got["sha256"][key].append(vals[0])
+    assert got == recorded_plans[_case_name(grid, geo)]
