@@ -107,7 +107,7 @@ typedef struct nkp_tuning {
    int col_ldsres_early;     /* NKP_LDSRES_EARLY (0) */
    int col_ldsres_packed;    /* NKP_COL_PACKED (1): LDS-resident column kernel with factors packed four steps to a 16-byte load */
    /* ---- CSR SpMV launch shape */
-   int spmv_variant;         /* NKP_SPMV_VARIANT (4) */
+   int spmv_variant;         /* NKP_SPMV_VARIANT (4): 0 .. 4 load flavours of the stream kernel (4 pipelined from spmv_pipe_min row blocks on), 9 rows kernel; the environment's values outside 0 .. 9 count as 4 */
    int spmv_compress;        /* NKP_SPMV_COMPRESS (0): 2-byte column codes */
    int spmv_pipe_min;        /* NKP_SPMV_PIPE_MIN (1024): fewest row blocks for the pipelined kernel */
    int spmv_run;             /* NKP_SPMV_RUN (1): row blocks one workgroup walks */

@@ -105,7 +105,7 @@ extern "C" int nkp_default_tuning (nkp_tuning *t)
 #undef ENV_INT
 #undef ENV_POS
 #undef ENV_FLAG
-   if (t->spmv_variant < 0 || t->spmv_variant > 8) t->spmv_variant = 4;
+   if (t->spmv_variant < 0 || t->spmv_variant > 9) t->spmv_variant = 4;      // 0-4 stream flavours (5-8: ablation library), 9 rows kernel
    return NKP_OK;
 }
 

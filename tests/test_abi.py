@@ -111,3 +111,13 @@ def test_kernels_and_cycle_do_not_read_the_environment():
 def test_tuning_struct_round_trip():
     t = solver.default_tuning(ml_pocket=6)
     assert t.struct_size == C.sizeof(solver.NkpTuning) and t.ml_pocket == 6 and t.ml_omega == 1.1 and t.spmv_variant == 4
+
+
+def test_spmv_variant_from_the_environment(monkeypatch):
+    """NKP_SPMV_VARIANT steers the executables and the distributed workers: the rows kernel (9) can be chosen with it, and a
+    value that names no kernel falls back to the default."""
+    for text, want in (("9", 9), ("0", 0), ("3", 3), ("10", 4), ("-1", 4)):
+        monkeypatch.setenv("NKP_SPMV_VARIANT", text)
+        assert solver.default_tuning().spmv_variant == want, text
+    monkeypatch.delenv("NKP_SPMV_VARIANT")
+    assert solver.default_tuning().spmv_variant == 4

@@ -25,6 +25,21 @@ def test_distributed_solve(tmp_path, world):
     assert res[0]["iters"] <= plain[0]["iters"], (res[0]["iters"], plain[0]["iters"])     # the overlap is there to save iterations
 
 
+def test_spmv_kernels_on_row_block_sub_ranges(tmp_path):
+    """The distributed operator product runs the SpMV kernels on sub-ranges of the row blocks (interior rows while the halo
+    travels, then the boundary segments: rb0 != 0).  At this size every range is below spmv_pipe_min and takes the stream kernel;
+    NKP_SPMV_PIPE_MIN=1 sends them through the pipelined kernel and NKP_SPMV_VARIANT=9 through the rows kernel.  All three sum
+    every row in stored order and two ranks reduce deterministically, so the whole solve repeats itself."""
+    base = launch(2, "gpu-solve", str(tmp_path / "stream"), extra=("--grid", "40x46x20"))
+    assert all(r["spmv_bit_exact"] and r["status"] == 0 and r["interior_rowblocks"] > 0 for r in base), base
+    for tag, env in (("pipe", {"NKP_SPMV_PIPE_MIN": "1"}), ("rows", {"NKP_SPMV_VARIANT": "9"})):
+        res = launch(2, "gpu-solve", str(tmp_path / tag), extra=("--grid", "40x46x20"), env_extra=env)
+        assert all(r["spmv_bit_exact"] for r in res), (tag, res)
+        assert all(r["status"] == 0 and not r["comm_errors"] for r in res), (tag, res)
+        for r, r0 in zip(res, base):
+            assert r["iters"] == r0["iters"] and r["relres"] == r0["relres"], (tag, r, r0)
+
+
 def test_one_allreduce_per_arnoldi_step(tmp_path):
     """nkp_tuning.dist_one_reduce (opt-in): the norm of the orthogonalised vector comes out of the reduced multi-dot message
     (w.w - sum h^2) instead of a second allreduce.  It converges to the same tolerance; the iterations it costs (the identity
