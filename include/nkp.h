@@ -501,7 +501,9 @@ int nkp_dist_plan_host (int64_t m_loc, int64_t nnz_loc, const int32_t *rowptr_lo
  * "valf" (float, the f32 storage of a level operator) / "val" (double, where the f64 values are kept), "cmap" (int32: row ->
  * row of the next level), "rptr" / "ridx" (int32: row of the next level -> its rows here), "blk_start" (int32), "fac"
  * (double, band factors of the column blocks), "perm0" (int32, level 0: row -> original row), "coarse_inv" (double, last
- * level).  All in the level's colour-major row order. */
+ * level, empty when that level is relaxed instead), "color_blk" (int32, 3 entries, every level with column blocks -- a last
+ * level that is relaxed included: column blocks [color_blk[c], color_blk[c + 1]) have colour c, so the rows of colour 0 are
+ * [0, blk_start[color_blk[1]]); a host array, copied without a device call).  All in the level's colour-major row order. */
 int64_t nkp_ml_level_array (nkp_solver *s, int level, const char *what, void *dst, int64_t capacity_bytes);
 
 /* Host-only planning step of the multilevel preconditioner inside nkp_create, exposed so the aggregation logic can

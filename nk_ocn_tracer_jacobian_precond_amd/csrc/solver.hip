@@ -514,6 +514,7 @@ extern "C" int64_t nkp_ml_level_array (nkp_solver *s, int level, const char *wha
    const void *src = nullptr;
    int64_t count = 0;
    size_t elem = 4;
+   bool host = false;
    if (!strcmp (what, "rowptr")) { src = V.L.rowptr; count = V.n + 1; }
    else if (!strcmp (what, "colind")) { src = V.L.colind; count = V.L.nnz; }
    else if (!strcmp (what, "valf")) { src = V.L.valf; count = V.L.valf ? V.L.nnz : 0; }
@@ -525,9 +526,14 @@ extern "C" int64_t nkp_ml_level_array (nkp_solver *s, int level, const char *wha
    else if (!strcmp (what, "fac")) { src = V.B.fac; count = V.B.fac ? (int64_t) (2 * V.B.P + 1) * V.n : 0; elem = 8; }
    else if (!strcmp (what, "perm0")) { src = level == 0 ? s->ml.perm0 : nullptr; count = src ? V.n : 0; }
    else if (!strcmp (what, "coarse_inv")) { src = last ? s->ml.coarse_inv : nullptr; count = src ? V.n * V.n : 0; elem = 8; }
+   else if (!strcmp (what, "color_blk")) { src = V.B.blk_start ? V.color_blk : nullptr; count = src ? 3 : 0; host = true; }
    else return fail (NKP_EINVAL, "nkp_ml_level_array: unknown array '%s'", what);
    if (!dst) return count;
    if (count * (int64_t) elem > capacity_bytes) return fail (NKP_EINVAL, "nkp_ml_level_array: buffer too small");
+   if (host) {                                  // kept on the host: no device call
+      if (count) memcpy (dst, src, (size_t) count * elem);
+      return count;
+   }
    HIPCHK (hipSetDevice (s->device));
    HIPCHK (hipStreamSynchronize (s->stream));
    if (count) HIPCHK (hipMemcpy (dst, src, (size_t) count * elem, hipMemcpyDeviceToHost));

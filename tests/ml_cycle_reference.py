@@ -1,0 +1,221 @@
+"""The multilevel cycle restated in numpy / scipy (f64) on levels that are GIVEN: read back from a solver
+(nkp_ml_level_array) or taken from ml_reference.build.  TEST INFRASTRUCTURE: slow, sequential, never shipped.
+
+Only the cycle is restated here, from the comments of include/nkp.h (nkp_tuning: "cycle"; nkp_ml_level_array), not the
+aggregation: so it runs on every hierarchy the planner can build.
+
+  outer step      b0 = r[perm0], x = cyc(0, b0), z[perm0] = x
+  half sweep      of colour c: x[R_c] += B_c^-1 (b - L x)[R_c]; R_c the rows of colour c, B_c the entries of L inside each
+                  column (block diagonal, one block per column).  No proper 2-colouring is assumed.
+  sweep           forward: colour 0 then colour 1; reversed: colour 1 then colour 0
+  level l < last  nu_l = nu_coarse if nu_coarse >= 1 and l >= coarse_from else nu.  From x = 0: nu_l forward sweeps; the
+                  coarse correction rc = P^T (b - L x), x += omega * P cyc(l + 1, rc), twice if gamma_from <= l < gamma_to;
+                  nu_l reversed sweeps
+  last level      x = coarse_inv @ b where the level has a dense inverse; else from x = 0 `coarsest_sweeps` sweeps (30 if the
+                  knob is <= 0), sweep s forward for even s and reversed for odd s
+
+Two further modes exist only to size tolerances: blocks="inverse" solves the column blocks with explicit dense inverses
+instead of LU (the same mathematics in another rounding), factors="f32" rounds the LU factors of every block and the coarsest
+inverse to f32 and widens them again (what f32 storage of the factors does to a solve).  With f32 storage the device factors
+the blocks of the f64 operator BEFORE it rounds operator and factors to f32, each on its own: a level that carries that f64
+operator (with_exact_blocks) factors its blocks likewise in the factors="f32" mode."""
+import numpy as np
+import scipy.linalg as sla
+import scipy.sparse as sp
+
+MAX_BAND = 4          # beyond it the device's band factors drop entries: an exact block solve is no reference then
+
+# The cycle options of tests/test_gpu_cycle_options.py, by the names of nkp_options / nkp_tuning.  "hierarchy": deep = 5 levels
+# with a dense last level, iterated = 3 levels with a last level that is relaxed, two = ml_levels = 2.
+DEFAULT_KNOBS = dict(ml_smooth=3, ml_smooth_coarse=0, ml_coarse_from=2, ml_gamma_from=0, ml_gamma_to=0, ml_omega=1.1,
+                     ml_coarsest_sweeps=30)
+COMBINED = dict(ml_smooth=2, ml_smooth_coarse=1, ml_coarse_from=1, ml_gamma_from=1, ml_gamma_to=3, ml_omega=1.0)
+OPTION_CASES = [
+    ("default", "deep", {}),
+    ("nu1", "deep", dict(ml_smooth=1)),
+    ("nu2", "deep", dict(ml_smooth=2)),
+    ("nu2_coarse1_from1", "deep", dict(ml_smooth=2, ml_smooth_coarse=1, ml_coarse_from=1)),
+    ("coarse1_from2", "deep", dict(ml_smooth_coarse=1)),
+    ("gamma_0_1", "deep", dict(ml_gamma_from=0, ml_gamma_to=1)),
+    ("gamma_1_3", "deep", dict(ml_gamma_from=1, ml_gamma_to=3)),
+    ("gamma_0_9", "deep", dict(ml_gamma_from=0, ml_gamma_to=9)),
+    ("omega_1.0", "deep", dict(ml_omega=1.0)),
+    ("omega_1.35", "deep", dict(ml_omega=1.35)),
+    ("sweeps5", "iterated", dict(ml_coarsest_sweeps=5)),
+    ("sweeps30", "iterated", dict(ml_coarsest_sweeps=30)),
+    ("levels2", "two", {}),
+    ("combined", "deep", COMBINED),
+]
+
+
+def cycle_kwargs(**knobs):
+    """cycle()'s arguments from knobs named as in nkp_options / nkp_tuning."""
+    k = dict(DEFAULT_KNOBS, **knobs)
+    return dict(nu=k["ml_smooth"], nu_coarse=k["ml_smooth_coarse"], coarse_from=k["ml_coarse_from"], gamma_from=k["ml_gamma_from"],
+                gamma_to=k["ml_gamma_to"], omega=k["ml_omega"], coarsest_sweeps=k["ml_coarsest_sweeps"])
+
+
+class CycleLevel:
+    """L: operator (csr, f64); col_of: column of every row (None on a level that only has an inverse); rows: [R_0, R_1];
+    P: piecewise-constant prolongation (None on the last level); coarse_inv: dense inverse (last level) or None."""
+
+    def __init__(self, L, col_of=None, rows=None, P=None, coarse_inv=None, perm0=None):
+        self.L = sp.csr_matrix(L, dtype=np.float64)
+        self.L.sort_indices()
+        self.n = self.L.shape[0]
+        self.col_of, self.rows, self.P, self.coarse_inv, self.perm0 = col_of, rows, P, coarse_inv, perm0
+        self._solvers = {}
+        self.Bd_unrounded = None
+        if col_of is not None:
+            self.band, self.Bd = self._block_diagonal(self.L)
+
+    def _block_diagonal(self, L):
+        C = L.tocoo()
+        same = self.col_of[C.row] == self.col_of[C.col]
+        band = int(np.abs(C.row[same] - C.col[same]).max()) if same.any() else 0
+        return band, sp.csr_matrix((C.data[same], (C.row[same], C.col[same])), shape=L.shape)
+
+    def blocks(self, c, Bd):
+        """(rows, dense block) of every column of colour c; a column's rows need not be contiguous."""
+        R = self.rows[c]
+        out = []
+        if R.size:
+            cols = self.col_of[R]
+            o = np.argsort(cols, kind="stable")
+            cut = np.flatnonzero(np.diff(cols[o])) + 1
+            for idx in np.split(R[o], cut):
+                out.append((idx, Bd[idx][:, idx].toarray()))
+        return out
+
+    def solver(self, c, blocks, factors):
+        """res -> B_c^-1 res on the rows of colour c (res indexed by level row)."""
+        key = (c, blocks, factors)
+        if key not in self._solvers:
+            parts = []
+            Bd = self.Bd_unrounded if (factors == "f32" and self.Bd_unrounded is not None) else self.Bd
+            for idx, B in self.blocks(c, Bd):
+                if blocks == "inverse":
+                    parts.append((idx, np.linalg.inv(B)))
+                else:
+                    lu, piv = sla.lu_factor(B, check_finite=False)
+                    if factors == "f32":
+                        lu = lu.astype(np.float32).astype(np.float64)
+                    parts.append((idx, (lu, piv)))
+            self._solvers[key] = parts
+        return self._solvers[key]
+
+
+def _half(lv, x, b, c, blocks, factors):
+    R = lv.rows[c]
+    if not R.size:
+        return
+    res = b - lv.L @ x                                  # only the rows of colour c are used: they do not change below
+    for idx, f in lv.solver(c, blocks, factors):
+        x[idx] += f @ res[idx] if blocks == "inverse" else sla.lu_solve(f, res[idx], check_finite=False)
+
+
+def _sweep(lv, x, b, reverse, blocks, factors):
+    for c in ((1, 0) if reverse else (0, 1)):
+        _half(lv, x, b, c, blocks, factors)
+
+
+def cycle(levels, r, nu=3, nu_coarse=0, coarse_from=2, gamma_from=0, gamma_to=0, omega=1.1, coarsest_sweeps=30, blocks="lu",
+          factors="f64"):
+    assert blocks in ("lu", "inverse") and factors in ("f64", "f32")
+    last = len(levels) - 1
+
+    def cyc(l, b):
+        lv = levels[l]
+        x = np.zeros(lv.n)
+        if l == last:
+            if lv.coarse_inv is not None:
+                inv = lv.coarse_inv
+                if factors == "f32":
+                    inv = inv.astype(np.float32).astype(np.float64)
+                return inv @ b
+            for s in range(coarsest_sweeps if coarsest_sweeps > 0 else 30):
+                _sweep(lv, x, b, s % 2 == 1, blocks, factors)
+            return x
+        nu_l = nu_coarse if (nu_coarse >= 1 and l >= coarse_from) else nu
+        for _ in range(nu_l):
+            _sweep(lv, x, b, False, blocks, factors)
+        for _ in range(2 if gamma_from <= l < gamma_to else 1):
+            rc = lv.P.T @ (b - lv.L @ x)
+            x += omega * (lv.P @ cyc(l + 1, rc))
+        for _ in range(nu_l):
+            _sweep(lv, x, b, True, blocks, factors)
+        return x
+
+    r = np.asarray(r, np.float64)
+    perm0 = levels[0].perm0
+    if perm0 is None:
+        return cyc(0, r.copy())
+    z = np.empty_like(r)
+    z[perm0] = cyc(0, r[perm0])
+    return z
+
+
+def relative_difference(a, b):
+    return float(np.linalg.norm(a - b) / np.linalg.norm(b))
+
+
+def with_exact_blocks(levels_f32, levels_f64):
+    """Levels read from a solver with f32 storage, given the f64 operators their factors were made from (the levels of the same
+    hierarchy read from a solver with f64 storage).  Checks that the f32 values are those f64 values rounded."""
+    assert len(levels_f32) == len(levels_f64)
+    for l, (a, b) in enumerate(zip(levels_f32, levels_f64)):
+        assert np.array_equal(a.L.indptr, b.L.indptr) and np.array_equal(a.L.indices, b.L.indices), l
+        assert np.array_equal(a.L.data, b.L.data.astype(np.float32).astype(np.float64)) or np.array_equal(a.L.data, b.L.data), l
+        if a.col_of is not None:
+            a.Bd_unrounded = a._block_diagonal(b.L)[1]
+            a._solvers = {}
+    return levels_f32
+
+
+def levels_from_mlr(mlr_levels, dense_last=True):
+    """The levels of ml_reference.build (natural row order, colours by grid position)."""
+    out = []
+    for l, lv in enumerate(mlr_levels):
+        is_last = l == len(mlr_levels) - 1
+        out.append(CycleLevel(lv.A, col_of=np.asarray(lv.colid), rows=[np.asarray(rows) for rows, _, _ in lv.colours],
+                              P=None if is_last else lv.P, coarse_inv=lv.dense_inv if (is_last and dense_last) else None))
+    return out
+
+
+def levels_from_solver(s):
+    """Every level as it sits on the device.  The operator is the one the kernels multiply with: the f32 values widened to f64
+    where the level stores them, else the f64 values; the last level multiplies by the device's own inverse if it has one."""
+    nlev = s.get_int("levels")
+    out = []
+    for l in range(nlev):
+        rowptr, colind = s.ml_level_array(l, "rowptr"), s.ml_level_array(l, "colind")
+        valf = s.ml_level_array(l, "valf")
+        val = valf.astype(np.float64) if valf.size else s.ml_level_array(l, "val")
+        n = rowptr.size - 1
+        assert val.size == colind.size == rowptr[-1], (l, val.size, colind.size, rowptr[-1])
+        L = sp.csr_matrix((val, colind, rowptr), shape=(n, n))
+        blk = s.ml_level_array(l, "blk_start").astype(np.int64)
+        col_of = rows = None
+        if blk.size:
+            cb = s.ml_level_array(l, "color_blk")
+            assert cb.size == 3 and cb[0] == 0 and cb[0] <= cb[1] <= cb[2] == blk.size - 1, (l, cb, blk.size)
+            assert blk[0] == 0 and blk[-1] == n and (np.diff(blk) > 0).all(), l
+            col_of = np.repeat(np.arange(blk.size - 1), np.diff(blk))
+            rows0 = int(blk[cb[1]])
+            rows = [np.arange(0, rows0), np.arange(rows0, n)]
+        cmap = s.ml_level_array(l, "cmap")
+        P = None
+        if l < nlev - 1:
+            assert cmap.size == n
+            nc = s.ml_level_array(l + 1, "rowptr").size - 1
+            P = sp.csr_matrix((np.ones(n), (np.arange(n), cmap)), shape=(n, nc))
+        inv = s.ml_level_array(l, "coarse_inv") if l == nlev - 1 else np.empty(0)
+        lv = CycleLevel(L, col_of=col_of, rows=rows, P=P, coarse_inv=inv.reshape(n, n) if inv.size else None,
+                        perm0=s.ml_level_array(0, "perm0").astype(np.int64) if l == 0 else None)
+        lv.blk_start = blk
+        if col_of is not None:
+            assert lv.band <= MAX_BAND, (l, lv.band)
+        else:
+            assert lv.coarse_inv is not None, l
+        out.append(lv)
+    return out
