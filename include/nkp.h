@@ -447,7 +447,8 @@ int nkp_clone (nkp_solver *src, nkp_solver **out);
  *   change), "trans_us" (wall time of the last nkp_transpose that built one), "trans_kernel_us" (of which: the device
  *   transpose); on either handle: "is_transpose".
  * Returns 0; NKP_EINVAL with *out = NULL and nothing allocated when s or out is NULL (before any HIP call), s is a clone, s is
- * itself a transposed handle, or s is row-distributed (the transpose of a row block needs an exchange between the ranks);
+ * itself a transposed handle, or s is row-distributed (the transpose of a row block needs an exchange between the ranks:
+ * every rank calls nkp_transpose_dist instead);
  * NKP_ESINGULAR when a refactor of s failed after its commit point (s cannot solve either until a refactor succeeds; the message
  * is that failure's); NKP_ENOMEM / NKP_EDEVICE, with s solving exactly as before.  On the transposed handle nkp_refactor*
  * (refactor the solver it was transposed from), nkp_clone and nkp_set_stream return NKP_EINVAL.
@@ -455,6 +456,58 @@ int nkp_clone (nkp_solver *src, nkp_solver **out);
  * length is accepted, but the work is quadratic in it (a column of A with 10^5 entries means 10^10 reads; ocean Jacobians have
  * 5 - 40 per row, a sink that couples a cell to every level a few hundred). */
 int nkp_transpose (nkp_solver *s, nkp_solver **out);
+
+/* nkp_transpose for row-distributed solvers.  COLLECTIVE: every rank calls it.  *out is a row-distributed solver for A^T with
+ * the row partition of s, on the same device, stream and nkp_comm_ops, built from the row block s holds ON THE DEVICE (the
+ * caller passes no arrays).  On every rank it is bit for bit what nkp_create_dist builds from rows [fst_row, fst_row + m_loc)
+ * of the host transpose of the global matrix (rows sorted by column, stored zeros kept) with the options and tuning s resolved
+ * at its creation, the same local block offsets, col_i / col_j / col_t, coupled_tracer_cnt and comm: the SpMV matrix, the halo
+ * plan, every array of every level of the hierarchy -- including the restricted-additive-Schwarz overlap A^T's own pattern asks
+ * for, which is generally not A's -- solves and batched solves.  Every entry point keeps its documented meaning on the handle
+ * (nkp_solve*, nkp_spmv*: y = A^T x on local slices, nkp_precond_apply, nkp_get_int, nkp_ml_level_array, nkp_gather_root).
+ *   How: the rank's m_loc x (m_loc + n_halo) matrix is transposed by the kernels of nkp_transpose; the rows of the result
+ *   beyond m_loc are the entries other ranks own, already grouped by destination and sorted by source row.  Their owners know
+ *   which of their rows each peer holds as halo (the send rows of the SpMV plan), so only the entry count of each such row, the
+ *   global source rows and the values travel; a row of A^T is then the concatenation of the ranks' pieces in rank order, and
+ *   kernels place every own and received entry without a sort.  The assembled block goes to the host once and through
+ *   nkp_create_dist.
+ *   Ownership, as for nkp_transpose: the handle belongs to s; nkp_destroy (s) frees it; nkp_destroy on the handle detaches it;
+ *   nkp_set_stream (s, ...) moves both.  The ranks must hold or not hold a handle together: the first thing every call does is
+ *   one allgather_i64_host of "I hold a transposed handle".  All hold one: the call returns it, with no further collective.
+ *   None does: it is built.  They differ (a rank destroyed its handle alone): every rank returns NKP_EINVAL naming such a rank
+ *   and nothing changes; destroy the handle on the other ranks too, then call again.  (A refactor of s in that state is an
+ *   error of the caller: the ranks that still hold a handle would wait for the others.)
+ *   The callbacks of nkp_comm_ops are reached in the same order on every rank whatever happens locally:
+ *     allgather_i64_host   who holds a handle
+ *     allgather_i64_host   agreement: local transpose (a broken s -- a refactor that failed after its commit point -- is
+ *                          NKP_ESINGULAR here)
+ *     alltoallv_i32_host   entry counts of the halo rows, to their owners
+ *     allgather_i64_host   agreement: entry counts, receive buffers
+ *     alltoallv_i32_host   global source rows of the shipped entries
+ *     alltoallv            their values (device doubles, on the solver's stream)
+ *     allgather_i64_host   agreement: exchange and placement
+ *     nkp_create_dist's own sequence, which succeeds or fails on all ranks together.
+ *   After a failed agreement every rank returns: the rank whose step failed its own code and message, the others NKP_ECOMM
+ *   naming it.  Either way s solves exactly as before, *out = NULL, and nothing is left allocated.
+ *   nkp_refactor_dist / nkp_refactor_dist_device on s keep it in step: after the refactor of s has succeeded on all ranks, the
+ *   values of A^T's row block are reassembled on the device (a gather of the values to ship, ONE alltoallv of device doubles on
+ *   the solver's stream, a gather into the block's order) and nkp_refactor_dist_device's sequence runs on the transposed solver
+ *   with the same flags.  Callbacks after those of the refactor of s: allgather_i64_host (value buffers, allocated at the first
+ *   refactor), alltoallv, allgather_i64_host (values), then the sequence of nkp_refactor_dist on the transposed solver.  If any
+ *   of this fails on any rank, the agreements tell every rank, and every rank frees and detaches its transposed solver, returns
+ *   the code of s and prints one "(rank)" line at verbose >= 1; the next nkp_transpose_dist rebuilds from the new matrix.  A
+ *   refactor of s refused before its commit point touches neither solver.
+ *   Memory: a second distributed solver, one int32 per entry of A^T's row block (where its value comes from) and per shipped
+ *   entry, and, from the first refactor on, doubles for the assembled block, the shipped and the received values.  nkp_get_int
+ *   on s: "trans_device_bytes", "trans_us", "trans_kernel_us" (device transpose and placement) as for nkp_transpose,
+ *   "trans_sent_entries" / "trans_recv_entries" (entries this rank shipped / received in the last build); on either handle:
+ *   "is_transpose".
+ * Refused at once on the calling rank, before any collective (NKP_EINVAL): s or out NULL, s a clone, s itself a transposed
+ * handle.  On the transposed handle nkp_refactor_dist*, nkp_refactor*, nkp_clone, nkp_set_stream, nkp_transpose and
+ * nkp_transpose_dist return NKP_EINVAL without a collective.  On a plain solver (nkp_create, or nkp_create_dist for one rank
+ * without force_dist) the call is nkp_transpose.  The ranking step of the device transpose is quadratic in the length of a row
+ * of the LOCAL transpose, as in nkp_transpose. */
+int nkp_transpose_dist (nkp_solver *s, nkp_solver **out);
 
 /* hipSetDevice for host programs that do not link HIP themselves (call before nkp_comm_rccl_init). */
 int nkp_set_device (int device);

@@ -225,8 +225,15 @@ int main (int argc, char *argv[])
    }
 #ifdef NKP_DIST
    if (trans) {
-      fprintf (stderr, "(%d) NKP_TRANS=1: nkp_transpose is not available for the row-distributed flavour (the transpose of a row block needs an exchange between the ranks); use solve_ABglobal\n", iam);
+      fprintf (stderr, "(%d) NKP_TRANS=1: nkp_transpose is not available for the row-distributed flavour (the transpose of a row block needs an exchange between the ranks); set NKP_TRANS_DIST=1 (nkp_transpose_dist), or use solve_ABglobal\n", iam);
       exit (EXIT_FAILURE);
+   }
+   // NKP_TRANS_DIST=1: the same on the row-distributed solver, through nkp_transpose_dist (solve_ABglobal ignores it)
+   int trans_dist = 0;
+   {
+      const char *e = getenv ("NKP_TRANS_DIST");
+      int v;
+      if (e && !parse_to_int ((char *) e, &v) && v != 0) trans_dist = 1;
    }
 #endif
    int world = 1, local_rank = 0, use_comm = 0;
@@ -523,6 +530,19 @@ int main (int argc, char *argv[])
       owner = solver;
       solver = at;
    }
+#ifdef NKP_DIST
+   if (trans_dist) {
+      nkp_solver *at = NULL;
+      if (nkp_transpose_dist (solver, &at)) {
+         fprintf (stderr, "(%d) nkp_transpose_dist failed: %s\n", iam, nkp_last_error ());
+         exit (EXIT_FAILURE);
+      }
+      if (dbg_lvl)
+         printf ("(%d) NKP_TRANS_DIST: solving A^T x = b, trans_us = %lld\n", iam, (long long) nkp_get_int (solver, "trans_us"));
+      owner = solver;
+      solver = at;
+   }
+#endif
    free_sparse_matrix ();      // the device holds its own copy
    free (blk_start);
    free (col_i);

@@ -278,7 +278,9 @@ static int refactor_impl (nkp_solver *s, const double *h_val, const void *d_val,
 // The entry points.  A solver that owns a transposed one (nkp_transpose) keeps it in step: once its own refactor has succeeded
 // the new values are gathered through the value map on the device and the same sequence, with the same flags, runs on the
 // transposed solver.  A transposed solver that cannot follow is freed -- the next nkp_transpose rebuilds it from the new matrix
-// and reports its own error -- and the call still returns the owner's code.
+// and reports its own error -- and the call still returns the owner's code.  On a row-distributed solver (nkp_transpose_dist) the
+// gather is a gather, one alltoallv and an assembly (trans_dist_follow), every step is agreed between the ranks, and the sequence
+// on the transposed solver is the collective one: all ranks keep their transposed solvers, or all free them.
 static int refactor_entry (nkp_solver *s, const double *h_val, const void *d_val, int flags, const char *who, bool collective)
 {
    if (!s || (!h_val && !d_val)) return refactor_impl (s, h_val, d_val, flags, who, collective);      // refused before s is looked at
@@ -295,10 +297,17 @@ static int refactor_entry (nkp_solver *s, const double *h_val, const void *d_val
       return rc;
    }
    const double *d_valT = nullptr;
-   int trc = trans_gather_values (s, &d_valT);
-   if (!trc) trc = refactor_impl (s->trans, nullptr, d_valT, flags, who, false);
+   int trc;
+   if (s->dist.on) {
+      // nkp_transpose_dist: collective, and every step agreed, so that all ranks keep or free their transposed solvers together
+      trc = trans_dist_follow (s, flags, who, [] (nkp_solver *t, const void *d_val, int fl, const char *w) { return refactor_impl (t, nullptr, d_val, fl, w, true); });
+   } else {
+      trc = trans_gather_values (s, &d_valT);
+      if (!trc) trc = refactor_impl (s->trans, nullptr, d_valT, flags, who, false);
+   }
    if (trc) {
-      msg (s, 1, "%s: the transposed solver could not follow (%d: %s); it is freed, the next nkp_transpose builds a new one\n", who, trc, last_error_message ().c_str ());
+      msg (s, 1, "%s: the transposed solver could not follow (%d: %s); it is freed, the next %s builds a new one\n", who, trc, last_error_message ().c_str (),
+           s->dist.on ? "nkp_transpose_dist" : "nkp_transpose");
       (void) hipStreamSynchronize (s->stream);
       trans_release (s);
       (void) hipGetLastError ();

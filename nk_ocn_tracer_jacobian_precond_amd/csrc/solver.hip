@@ -617,6 +617,8 @@ extern "C" int64_t nkp_get_int (nkp_solver *s, const char *key)
    if (!strcmp (key, "trans_device_bytes")) return trans_device_bytes (s);
    if (!strcmp (key, "trans_us")) return (int64_t) (s->trans_seconds * 1.0e6);
    if (!strcmp (key, "trans_kernel_us")) return (int64_t) (s->trans_kernel_seconds * 1.0e6);
+   if (!strcmp (key, "trans_sent_entries")) return s->trans_sent;
+   if (!strcmp (key, "trans_recv_entries")) return s->trans_received;
    if (!strcmp (key, "dist_alltoallv_calls")) return s->shared->alltoallv_calls.load ();
    if (!strcmp (key, "dist_allreduce_calls")) return s->shared->allreduce_calls.load ();
    if (!strcmp (key, "batch_steps")) return s->batch_steps;
@@ -1033,6 +1035,8 @@ static int clone_impl (nkp_solver *src, nkp_solver **out, bool member)
    s->trans_src = nullptr;
    s->trans_val = nullptr;
    s->trans_map_bytes = 0;
+   s->trans_ship = nullptr;
+   s->trans_send = s->trans_recv = nullptr;
    s->A.tune = &s->tune;
    s->B.tune = &s->tune;
    s->ml.tune = &s->tune;
@@ -1735,6 +1739,16 @@ extern "C" int nkp_create_dist (nkp_solver **out, const nkp_options *opt, int64_
          s->dist.overlap = true;
    }
    s->dist.on = true;
+   // nkp_transpose_dist builds A^T's row block from these and passes the caller's own block data to nkp_create_dist again
+   s->dist.starts = starts;
+   s->dist.h_halo_rows.assign (D.halo_rows.begin (), D.halo_rows.begin () + D.n_halo);
+   s->dist.h_send_rows.assign (D.send_rows.begin (), D.send_rows.begin () + D.nsend);
+   s->dist.own_has_blk = blk_start_loc != nullptr;
+   if (blk_start_loc) s->dist.own_blk.assign (blk_start_loc, blk_start_loc + nblk_loc + 1);
+   if (o.col_i) s->dist.own_ci.assign (o.col_i, o.col_i + nblk_loc);
+   if (o.col_j) s->dist.own_cj.assign (o.col_j, o.col_j + nblk_loc);
+   if (o.col_t) s->dist.own_ct.assign (o.col_t, o.col_t + nblk_loc);
+   s->dist.own_tracer_cnt = coupled_tracer_cnt;
    if (s->opt.precond == NKP_PRECOND_MULTILEVEL) {
       // nkp_refactor_dist: the hierarchy's source matrix and where its values come from (host memory only until the first call)
       DistRefactorPlan *Q = new DistRefactorPlan;

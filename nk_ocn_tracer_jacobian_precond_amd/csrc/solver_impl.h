@@ -66,6 +66,13 @@ struct nkp_solver {
       int bK = 0;                     // width these buffers exist for
       int agreed_K = 0;               // widest interleave every rank is known to have buffers for
       std::vector<int> send_counts_k, recv_counts_k;
+      // nkp_transpose_dist: what nkp_create_dist was given and planned, in host memory -- the first rows of all ranks, the global
+      // rows of the halo, the own rows the peers hold as halo (send_idx), the caller's OWN block offsets and grid positions
+      // (with overlap h_blk / h_col_* hold the extended [own | overlap] arrays)
+      std::vector<int64_t> starts;
+      std::vector<int32_t> h_halo_rows, h_send_rows, own_blk, own_ci, own_cj, own_ct;
+      bool own_has_blk = false;
+      int own_tracer_cnt = 1;
    } dist;
    int64_t n = 0, ld = 0;
    int m = 0;
@@ -118,6 +125,13 @@ struct nkp_solver {
    double *trans_val = nullptr;
    size_t trans_map_bytes = 0;
    double trans_seconds = 0.0, trans_kernel_seconds = 0.0;
+   // nkp_transpose_dist: trans_src[p] is then the origin of A^T's row block entry p -- a position in val, or -1 - position in the
+   // received values; trans_ship = the positions in val of the entries shipped (grouped by destination), the entry counts per
+   // rank, and, from the first refactor on, the send / receive buffers of the value exchange
+   int *trans_ship = nullptr;
+   double *trans_send = nullptr, *trans_recv = nullptr;
+   std::vector<int> trans_send_counts, trans_recv_counts;
+   int64_t trans_nnz = 0, trans_sent = 0, trans_received = 0;
    double *h_dev () { return dscal; }
    double *h2_dev () { return dscal + (m + 2); }
    double *misc_dev () { return dscal + 2 * (m + 2); }     // [0]=nrm2 [1]=inv [2]=dot out ...
@@ -154,6 +168,10 @@ NKP_PRIVATE void trans_set_stream (nkp_solver *s);
 NKP_PRIVATE int64_t trans_device_bytes (const nkp_solver *s);
 // valT = A.val[trans_src] on the owner's stream, into a buffer the owner keeps
 NKP_PRIVATE int trans_gather_values (nkp_solver *s, const double **d_valT);
+// ---- defined in transpose_dist.hip -----------------------------------------------------------------------------------------
+// collective: the values of A^T's row block from the owner's new values (gather, one alltoallv, placement), then the refactor
+// `refactor` (nkp_refactor_dist_device's sequence) on the transposed solver; non-zero on every rank when it could not follow
+NKP_PRIVATE int trans_dist_follow (nkp_solver *s, int flags, const char *who, int (*refactor) (nkp_solver *t, const void *d_val, int flags, const char *who));
 
 // ---- defined in solver.hip -------------------------------------------------------------------------------------------------
 NKP_PRIVATE void drop_intertracer (int64_t n, int tracer_cnt, const int32_t *rowptr, const int32_t *colind, const double *val,

@@ -11,7 +11,7 @@
 //   resolved, so the result is bit for bit what nkp_create builds from the host transpose.  The map src (valT[p] = val[src[p]])
 //   stays on the device: a refactor of the source gathers the new values through it and refactors the transposed solver too.
 #include "solver_impl.h"
-#include "mlsetup.h"
+#include "transpose.h"
 
 #include <stdio.h>
 #include <time.h>
@@ -85,11 +85,12 @@ static double seconds_since (const struct timespec &t0)
    return (double) (t.tv_sec - t0.tv_sec) + 1e-9 * (double) (t.tv_nsec - t0.tv_nsec);
 }
 
-// A^T of the device CSR A: rowptrT[n + 1], colindT / valT / src[nnz], every row sorted by column.  0, or a hipError_t
+// A^T of the device CSR A of A.n rows and ncols columns (nkp_transpose_dist: the rectangle [own | halo]): rowptrT[ncols + 1],
+// colindT / valT / src[nnz], every row sorted by column.  0, or a hipError_t
 #define TRCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return (int) e_; } while (0)
-static int transpose_device (const CsrDev &A, mls::DBuf<int> &rowptrT, mls::DBuf<int> &colindT, mls::DBuf<double> &valT, mls::DBuf<int> &src, hipStream_t st)
+int transpose_device (const CsrDev &A, int64_t ncols, mls::DBuf<int> &rowptrT, mls::DBuf<int> &colindT, mls::DBuf<double> &valT, mls::DBuf<int> &src, hipStream_t st)
 {
-   const int64_t n = A.n, nnz = A.nnz;
+   const int64_t n = ncols, nnz = A.nnz;
    mls::DBuf<int> cursor, row_tmp, src_tmp;
    TRCHK (rowptrT.alloc ((size_t) n + 1));
    TRCHK (colindT.alloc ((size_t) nnz));
@@ -106,7 +107,7 @@ static int transpose_device (const CsrDev &A, mls::DBuf<int> &rowptrT, mls::DBuf
    if (rc) return rc;
    if (total != nnz) return 1000;
    if (nnz > 0) {
-      hipLaunchKernelGGL (tr_fill_kernel, tr_grid (nnz), dim3 (TR_T), 0, st, A.rowptr, A.colind, (int) n, nnz, rowptrT.p, cursor.p, row_tmp.p, src_tmp.p);
+      hipLaunchKernelGGL (tr_fill_kernel, tr_grid (nnz), dim3 (TR_T), 0, st, A.rowptr, A.colind, (int) A.n, nnz, rowptrT.p, cursor.p, row_tmp.p, src_tmp.p);
       hipLaunchKernelGGL (tr_rank_kernel, tr_grid (nnz), dim3 (TR_T), 0, st, rowptrT.p, (int) n, nnz, row_tmp.p, src_tmp.p, A.val, colindT.p, src.p, valT.p);
    }
    TRCHK (hipStreamSynchronize (st));      // the work buffers are freed on return
@@ -119,8 +120,11 @@ static void trans_free_maps (nkp_solver *s)
 {
    if (s->trans_src) (void) hipFree (s->trans_src);
    if (s->trans_val) (void) hipFree (s->trans_val);
-   s->trans_src = nullptr;
-   s->trans_val = nullptr;
+   if (s->trans_ship) (void) hipFree (s->trans_ship);
+   if (s->trans_send) (void) hipFree (s->trans_send);
+   if (s->trans_recv) (void) hipFree (s->trans_recv);
+   s->trans_src = s->trans_ship = nullptr;
+   s->trans_val = s->trans_send = s->trans_recv = nullptr;
    s->trans_map_bytes = 0;
 }
 
@@ -187,7 +191,7 @@ extern "C" int nkp_transpose (nkp_solver *s, nkp_solver **out)
    if (!s || !out) return fail (NKP_EINVAL, "nkp_transpose: NULL argument");
    if (s->borrowed) return fail (NKP_EINVAL, "nkp_transpose: a clone shares its matrix; transpose the solver it was cloned from");
    if (s->trans_of) return fail (NKP_EINVAL, "nkp_transpose: this solver is itself a transposed handle; the solver it was transposed from holds A");
-   if (s->dist.on) return fail (NKP_EINVAL, "nkp_transpose: not available for the row-distributed flavour (the transpose of a row block needs an exchange between the ranks)");
+   if (s->dist.on) return fail (NKP_EINVAL, "nkp_transpose: not available for the row-distributed flavour (the transpose of a row block needs an exchange between the ranks: every rank calls nkp_transpose_dist instead)");
    if (s->trans) { *out = s->trans; return NKP_OK; }
    if (s->shared->broken) return fail (NKP_ESINGULAR, "nkp_transpose: %s", s->shared->why.c_str ());
    HIPCHK (hipSetDevice (s->device));
@@ -202,7 +206,7 @@ extern "C" int nkp_transpose (nkp_solver *s, nkp_solver **out)
    {
       mls::DBuf<int> rowptrT, colindT;
       mls::DBuf<double> valT;
-      const int trc = transpose_device (s->A, rowptrT, colindT, valT, src, s->stream);
+      const int trc = transpose_device (s->A, s->n, rowptrT, colindT, valT, src, s->stream);
       if (trc) {
          (void) hipStreamSynchronize (s->stream);
          (void) hipGetLastError ();      // an out-of-memory error is sticky until read

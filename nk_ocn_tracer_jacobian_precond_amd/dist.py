@@ -419,3 +419,20 @@ class NkpDistSolver(_solver.NkpSolver):
     def refactor_dist_device(self, d_val_loc, rebuild=False):
         """nkp_refactor_dist_device (collective): d_val_loc = integer device address of this rank's nnz_loc float64 values."""
         self._check_dist(self._lib.nkp_refactor_dist_device(self._h, C.c_void_p(d_val_loc), _solver.REFACTOR_REBUILD if rebuild else 0))
+
+    def transposed_dist(self):
+        """nkp_transpose_dist (collective: every rank calls it): the row-distributed solver for A^T with this solver's row
+        partition, built on the device from the row block this solver holds.  It belongs to this solver (a second call returns
+        the same object), follows refactor_dist / refactor_dist_device, and is invalid once this solver is closed; closing it
+        detaches it -- on every rank, or the next call is refused.  The inherited transposed() (nkp_transpose) is refused by
+        the library on a distributed solver."""
+        h = C.c_void_p()
+        self._check_dist(self._lib.nkp_transpose_dist(self._h, C.byref(h)))
+        t = getattr(self, "_trans", None)
+        if t is not None and t._h.value == h.value:
+            return t
+        t = object.__new__(NkpDistSolver)
+        t._lib, t._h, t.n, t.options, t._parent, t._trans_of, t._comm = self._lib, h, self.n, self.options, self, self, self._comm
+        t.nnz = int(self._lib.nkp_get_int(h, b"nnz"))
+        self._trans = t
+        return t

@@ -30,7 +30,7 @@ ABI_SYMBOLS = [
     "nkp_gather_root", "nkp_clone", "nkp_ml_plan_host", "nkp_comm_file_init", "nkp_comm_file_free",
     "nkp_create64", "nkp_cell_major_order", "nkp_permuted_rows", "nkp_dist_overlap_plan_host", "nkp_dist_plan_size",
     "nkp_dist_plan_copy", "nkp_dist_plan_free", "nkp_ml_level_array", "nkp_default_tuning", "nkp_solve_batch_device",
-    "nkp_refactor", "nkp_refactor_device", "nkp_refactor_dist", "nkp_refactor_dist_device", "nkp_transpose",
+    "nkp_refactor", "nkp_refactor_device", "nkp_refactor_dist", "nkp_refactor_dist_device", "nkp_transpose", "nkp_transpose_dist",
 ]
 
 _ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p)
@@ -124,6 +124,7 @@ def load_library(path=None):
     lib.nkp_gather_root.argtypes = [vp, f64p, f64p]
     lib.nkp_clone.argtypes = [vp, C.POINTER(vp)]
     lib.nkp_transpose.argtypes = [vp, C.POINTER(vp)]
+    lib.nkp_transpose_dist.argtypes = [vp, C.POINTER(vp)]
     lib.nkp_refactor.argtypes = [vp, f64p, C.c_int]
     lib.nkp_refactor_device.argtypes = [vp, vp, C.c_int]
     lib.nkp_refactor_dist.argtypes = [vp, f64p, C.c_int]
