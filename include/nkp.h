@@ -278,6 +278,8 @@ int nkp_multi_dot (nkp_solver *s, const double *V, int64_t ld, int k, const doub
 int nkp_time_kernel (nkp_solver *s, int which, int arg, int reps, double *avg_ms);
 
 /* Introspection: key = "n", "nnz", "nblk", "band", "levels", "spmv_bytes", "device_bytes", "precond_steps", "equil";
+ * column-Jacobi preconditioner, the lane layout of its column blocks: "col_stream" (1 = factors streamed), "col_ldsres" (0, 1 =
+ * column resident in LDS, 2 = packed), "col_gw" (columns per group), "col_max_len" (longest column), "col_lds_bytes" (dynamic LDS);
  * "create_us" (wall time of nkp_create), "ml_setup_us" (of which: the hierarchy), "ml_levels_on_device" (levels whose operator
  * the setup kernels built; the smaller ones are built on the host);
  * compulsory HBM bytes of the pieces nkp_time_kernel times: "smoother_spmv_bytes", "column_solve_bytes", "cycle_bytes";
@@ -556,7 +558,11 @@ int nkp_dist_plan_host (int64_t m_loc, int64_t nnz_loc, const int32_t *rowptr_lo
  * (double, band factors of the column blocks), "perm0" (int32, level 0: row -> original row), "coarse_inv" (double, last
  * level, empty when that level is relaxed instead), "color_blk" (int32, 3 entries, every level with column blocks -- a last
  * level that is relaxed included: column blocks [color_blk[c], color_blk[c + 1]) have colour c, so the rows of colour 0 are
- * [0, blk_start[color_blk[1]]); a host array, copied without a device call).  All in the level's colour-major row order. */
+ * [0, blk_start[color_blk[1]]); a host array, copied without a device call), "col_kernel" (int32, 11 entries, every level with
+ * column blocks, a host array like "color_blk": which column-solve kernels serve the level -- wave_columns, wave_fused, stream,
+ * ldsres (0 / 1 = LDS-resident / 2 = packed), gw (columns per group), P (half bandwidth stored), dropped (1 if entries beyond
+ * the band were dropped), max_len (longest column), gs_ok (the fused half sweep can serve the level), ngrp, lds_doubles (dynamic
+ * LDS of the lane kernels, in doubles)).  All in the level's colour-major row order. */
 int64_t nkp_ml_level_array (nkp_solver *s, int level, const char *what, void *dst, int64_t capacity_bytes);
 
 /* Host-only planning step of the multilevel preconditioner inside nkp_create, exposed so the aggregation logic can

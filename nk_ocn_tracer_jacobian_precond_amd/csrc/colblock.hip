@@ -1390,7 +1390,9 @@ int colblock_build_lane_layout (ColBlocksDev &B, const int *h_blk_start, const i
       *device_bytes -= gcols.size () * sizeof (int);
    }
    if (gs_ok) {
-      const int gs_bytes = (GS_NNZ + lds_need) * (int) sizeof (double);
+      // gs_fused_kernel stages the group's factors behind the right-hand side under EVERY layout; the streamed and the
+      // LDS-resident lane kernels read them from memory, so lds_need has no room for them there
+      const int gs_bytes = (GS_NNZ + B.rhs_slots + (f32 ? (fac_need + 1) / 2 : fac_need)) * (int) sizeof (double);
       if (gs_bytes > 64 * 1024) gs_ok = false;          // not worth running one workgroup per CU
       B.gs_lds_bytes = gs_bytes;
    }

@@ -515,6 +515,7 @@ extern "C" int64_t nkp_ml_level_array (nkp_solver *s, int level, const char *wha
    int64_t count = 0;
    size_t elem = 4;
    bool host = false;
+   int col_kernel[11];
    if (!strcmp (what, "rowptr")) { src = V.L.rowptr; count = V.n + 1; }
    else if (!strcmp (what, "colind")) { src = V.L.colind; count = V.L.nnz; }
    else if (!strcmp (what, "valf")) { src = V.L.valf; count = V.L.valf ? V.L.nnz : 0; }
@@ -527,6 +528,12 @@ extern "C" int64_t nkp_ml_level_array (nkp_solver *s, int level, const char *wha
    else if (!strcmp (what, "perm0")) { src = level == 0 ? s->ml.perm0 : nullptr; count = src ? V.n : 0; }
    else if (!strcmp (what, "coarse_inv")) { src = last ? s->ml.coarse_inv : nullptr; count = src ? V.n * V.n : 0; elem = 8; }
    else if (!strcmp (what, "color_blk")) { src = V.B.blk_start ? V.color_blk : nullptr; count = src ? 3 : 0; host = true; }
+   else if (!strcmp (what, "col_kernel")) {      // which column-solve kernels the level was given (read-only, host values)
+      const ColBlocksDev &B = V.B;
+      const int v[11] = { V.wave_columns ? 1 : 0, V.wave_fused ? 1 : 0, B.stream ? 1 : 0, B.ldsres, B.gw, B.P, B.dropped, B.max_len, B.gs_ok, B.ngrp, B.lds_doubles };
+      memcpy (col_kernel, v, sizeof v);
+      src = B.blk_start ? col_kernel : nullptr; count = src ? 11 : 0; host = true;
+   }
    else return fail (NKP_EINVAL, "nkp_ml_level_array: unknown array '%s'", what);
    if (!dst) return count;
    if (count * (int64_t) elem > capacity_bytes) return fail (NKP_EINVAL, "nkp_ml_level_array: buffer too small");
@@ -586,6 +593,11 @@ extern "C" int64_t nkp_get_int (nkp_solver *s, const char *key)
    if (!strcmp (key, "nblk")) return s->B.nblk;
    if (!strcmp (key, "band")) return s->B.P;
    if (!strcmp (key, "band_dropped")) return s->B.dropped;
+   if (!strcmp (key, "col_stream")) return s->B.stream ? 1 : 0;
+   if (!strcmp (key, "col_ldsres")) return s->B.ldsres;
+   if (!strcmp (key, "col_gw")) return s->B.gw;
+   if (!strcmp (key, "col_max_len")) return s->B.max_len;
+   if (!strcmp (key, "col_lds_bytes")) return (int64_t) s->B.lds_doubles * (int64_t) sizeof (double);
    if (!strcmp (key, "levels")) return s->opt.precond == NKP_PRECOND_MULTILEVEL ? (int64_t) s->ml.lev.size () : 1;
    if (!strcmp (key, "ml_rows")) { int64_t t = 0; for (auto &v : s->ml.lev) t += v.n; return t; }
    if (!strcmp (key, "ml_nnz")) { int64_t t = 0; for (auto &v : s->ml.lev) t += v.L.nnz; return t; }

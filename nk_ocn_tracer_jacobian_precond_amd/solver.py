@@ -375,7 +375,8 @@ class NkpSolver:
     def get_int(self, key):
         return int(self._lib.nkp_get_int(self._h, key.encode()))
 
-    _ML_ARRAY_TYPES = {"valf": np.float32, "val": np.float64, "fac": np.float64, "coarse_inv": np.float64, "color_blk": np.int32}
+    _ML_ARRAY_TYPES = {"valf": np.float32, "val": np.float64, "fac": np.float64, "coarse_inv": np.float64, "color_blk": np.int32,
+                       "col_kernel": np.int32}
 
     def ml_level_array(self, level, what):
         """One array of the multilevel hierarchy as it sits on the device (nkp_ml_level_array); empty if the level has none."""

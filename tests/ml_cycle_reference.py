@@ -23,7 +23,7 @@ import numpy as np
 import scipy.linalg as sla
 import scipy.sparse as sp
 
-MAX_BAND = 4          # beyond it the device's band factors drop entries: an exact block solve is no reference then
+MAX_BAND = 4          # beyond it the device's band factors drop entries: the block solve is then the band-capped one (band_cap)
 
 # The cycle options of tests/test_gpu_cycle_options.py, by the names of nkp_options / nkp_tuning.  "hierarchy": deep = 5 levels
 # with a dense last level, iterated = 3 levels with a last level that is relaxed, two = ml_levels = 2.
@@ -57,22 +57,30 @@ def cycle_kwargs(**knobs):
 
 class CycleLevel:
     """L: operator (csr, f64); col_of: column of every row (None on a level that only has an inverse); rows: [R_0, R_1];
-    P: piecewise-constant prolongation (None on the last level); coarse_inv: dense inverse (last level) or None."""
+    P: piecewise-constant prolongation (None on the last level); coarse_inv: dense inverse (last level) or None.
+    band_cap: the half sweep's block solve is built from the in-column entries with |row - col| <= band_cap only (what the
+    device's band factors keep on a level that reports dropped entries; the rows of a column must then be contiguous, as they
+    are in a level's own colour-major order); the residual b - L x still uses all of L.  None: the whole block."""
 
-    def __init__(self, L, col_of=None, rows=None, P=None, coarse_inv=None, perm0=None):
+    def __init__(self, L, col_of=None, rows=None, P=None, coarse_inv=None, perm0=None, band_cap=None):
         self.L = sp.csr_matrix(L, dtype=np.float64)
         self.L.sort_indices()
         self.n = self.L.shape[0]
         self.col_of, self.rows, self.P, self.coarse_inv, self.perm0 = col_of, rows, P, coarse_inv, perm0
         self._solvers = {}
         self.Bd_unrounded = None
+        self.band_cap = band_cap
         if col_of is not None:
+            if band_cap is not None:
+                assert (np.diff(col_of) >= 0).all()           # contiguous columns: |row - col| is the distance inside the column
             self.band, self.Bd = self._block_diagonal(self.L)
 
     def _block_diagonal(self, L):
         C = L.tocoo()
         same = self.col_of[C.row] == self.col_of[C.col]
         band = int(np.abs(C.row[same] - C.col[same]).max()) if same.any() else 0
+        if self.band_cap is not None:
+            same &= np.abs(C.row - C.col) <= self.band_cap
         return band, sp.csr_matrix((C.data[same], (C.row[same], C.col[same])), shape=L.shape)
 
     def blocks(self, c, Bd):
@@ -159,6 +167,30 @@ def relative_difference(a, b):
     return float(np.linalg.norm(a - b) / np.linalg.norm(b))
 
 
+class Reference:
+    """(tests/test_gpu_cycle_options.py, tests/test_gpu_colsolve_families.py)  The restated cycle on the levels of one hierarchy in one storage mode, for a set of option cases: z_ref per case and the
+    yardstick of the tolerance (d per case with f64 storage, e over the cases with f32 storage).  Computed once per module."""
+
+    def __init__(self, levels, r, f32, cases):
+        self.levels, self.f32 = levels, f32
+        self.rows = [lv.n for lv in levels]
+        self.z, self.yard = {}, {}
+        for name, knobs in cases.items():
+            kw = cycle_kwargs(**knobs)
+            self.z[name] = cycle(levels, r, **kw)
+            other = cycle(levels, r, factors="f32", **kw) if f32 else cycle(levels, r, blocks="inverse", **kw)
+            self.yard[name] = relative_difference(other, self.z[name])
+        self.e = max(self.yard.values())
+
+    def bound(self, name):
+        return min(2e-5, 16 * self.e) if self.f32 else max(1e-12, 4096 * self.yard[name])
+
+    def check(self, label, name, z):
+        err, bound = relative_difference(z, self.z[name]), self.bound(name)
+        print("MEASURED %-34s %s  %.1e  bound %.1e  ratio %.2g" % (label, "f32" if self.f32 else "f64", err, bound, err / bound))
+        assert err <= bound, (label, name, self.f32, err, bound, self.yard[name], self.e)
+
+
 def with_exact_blocks(levels_f32, levels_f64):
     """Levels read from a solver with f32 storage, given the f64 operators their factors were made from (the levels of the same
     hierarchy read from a solver with f64 storage).  Checks that the f32 values are those f64 values rounded."""
@@ -182,9 +214,10 @@ def levels_from_mlr(mlr_levels, dense_last=True):
     return out
 
 
-def levels_from_solver(s):
+def levels_from_solver(s, band_cap=MAX_BAND):
     """Every level as it sits on the device.  The operator is the one the kernels multiply with: the f32 values widened to f64
-    where the level stores them, else the f64 values; the last level multiplies by the device's own inverse if it has one."""
+    where the level stores them, else the f64 values; the last level multiplies by the device's own inverse if it has one.
+    A level whose "col_kernel" reports dropped entries solves its blocks capped at band_cap; lv.band stays the measured one."""
     nlev = s.get_int("levels")
     out = []
     for l in range(nlev):
@@ -210,10 +243,16 @@ def levels_from_solver(s):
             nc = s.ml_level_array(l + 1, "rowptr").size - 1
             P = sp.csr_matrix((np.ones(n), (np.arange(n), cmap)), shape=(n, nc))
         inv = s.ml_level_array(l, "coarse_inv") if l == nlev - 1 else np.empty(0)
+        ck = s.ml_level_array(l, "col_kernel")
+        assert ck.size == (11 if blk.size else 0), (l, ck)
+        dropped = bool(blk.size and ck[6])
         lv = CycleLevel(L, col_of=col_of, rows=rows, P=P, coarse_inv=inv.reshape(n, n) if inv.size else None,
-                        perm0=s.ml_level_array(0, "perm0").astype(np.int64) if l == 0 else None)
+                        perm0=s.ml_level_array(0, "perm0").astype(np.int64) if l == 0 else None, band_cap=band_cap if dropped else None)
         lv.blk_start = blk
-        if col_of is not None:
+        lv.dropped = dropped
+        if col_of is not None and dropped:
+            assert lv.band > band_cap, (l, lv.band)
+        elif col_of is not None:
             assert lv.band <= MAX_BAND, (l, lv.band)
         else:
             assert lv.coarse_inv is not None, l

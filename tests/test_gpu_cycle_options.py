@@ -171,28 +171,7 @@ def split_knobs(knobs):
     return ({k: v for k, v in knobs.items() if k in OPTION_FIELDS}, {k: v for k, v in knobs.items() if k not in OPTION_FIELDS})
 
 
-class Reference:
-    """The restated cycle on the levels of one hierarchy in one storage mode, for a set of option cases: z_ref per case and the
-    yardstick of the tolerance (d per case with f64 storage, e over the cases with f32 storage).  Computed once per module."""
-
-    def __init__(self, levels, r, f32, cases):
-        self.levels, self.f32 = levels, f32
-        self.rows = [lv.n for lv in levels]
-        self.z, self.yard = {}, {}
-        for name, knobs in cases.items():
-            kw = mcr.cycle_kwargs(**knobs)
-            self.z[name] = mcr.cycle(levels, r, **kw)
-            other = mcr.cycle(levels, r, factors="f32", **kw) if f32 else mcr.cycle(levels, r, blocks="inverse", **kw)
-            self.yard[name] = mcr.relative_difference(other, self.z[name])
-        self.e = max(self.yard.values())
-
-    def bound(self, name):
-        return min(2e-5, 16 * self.e) if self.f32 else max(1e-12, 4096 * self.yard[name])
-
-    def check(self, label, name, z):
-        err, bound = mcr.relative_difference(z, self.z[name]), self.bound(name)
-        print("MEASURED %-34s %s  %.1e  bound %.1e  ratio %.2g" % (label, "f32" if self.f32 else "f64", err, bound, err / bound))
-        assert err <= bound, (label, name, self.f32, err, bound, self.yard[name], self.e)
+Reference = mcr.Reference          # z_ref per case and the yardsticks d / e of the tolerances above
 
 
 @pytest.fixture(scope="module")
