@@ -274,7 +274,9 @@ int nkp_multi_dot (nkp_solver *s, const double *V, int64_t ld, int k, const doub
 /* Average duration (ms) of `reps` back-to-back launches of one kernel on the solver's stream,
  * measured with HIP events on that stream.  which: 0 = CSR SpMV, 1 = preconditioner apply,
  * 2 = one full Krylov iteration body at restart position `arg` (0 <= arg < restart); multilevel only: 3 = the
- * smoother's residual rows of one colour of the fine level, 4 = the water-column solves of that colour. */
+ * smoother's residual rows of one colour of the fine level, 4 = the water-column solves of that colour; 5 = the gradient kernel of
+ * nkp_value_gradient alone with K = arg in {1, 2, 4, 8} pairs of vectors, on scratch vectors of the solver (single-GPU solvers
+ * only, NKP_EINVAL elsewhere and for another arg; its compulsory bytes: 12 nnz + 4 (n + 1) + 16 K n). */
 int nkp_time_kernel (nkp_solver *s, int which, int arg, int reps, double *avg_ms);
 
 /* Introspection: key = "n", "nnz", "nblk", "band", "levels", "spmv_bytes", "device_bytes", "precond_steps", "equil";
@@ -288,7 +290,8 @@ int nkp_time_kernel (nkp_solver *s, int which, int arg, int reps, double *avg_ms
  * "dist_ras_rings" (the depth the ranks agreed on, 0 without overlap), "dist_halo_rows" (rows received before every SpMV),
  * "dist_ras_recv_rows" (rows received per preconditioner application: the SpMV halo with one ring, the overlap rows with more);
  * counters, cumulative over the solver's life, per rank: "dist_alltoallv_calls", "dist_allreduce_calls" (every call of the two
- * device collectives made by solves, single or batched; 0 on a single-GPU solver), "batch_steps" (batched operator
+ * device collectives made by solves, single or batched, and the one alltoallv of every nkp_value_gradient*; 0 on a single-GPU
+ * solver), "value_gradient_calls" (successful nkp_value_gradient* calls), "value_gradient_us" (wall time of the last one), "batch_steps" (batched operator
  * applications = lockstep Krylov steps of a group of right-hand sides), "batch_width" (K of the last batched group, 0 if
  * none ran); "batch_member_bytes" (device bytes of the K - 1 further sets of work vectors a batched call has made and keeps:
  * Krylov bases, level vectors, with chained cycles the residual between two cycles; "device_bytes" counts the solver's own set
@@ -510,6 +513,44 @@ int nkp_transpose (nkp_solver *s, nkp_solver **out);
  * without force_dist) the call is nkp_transpose.  The ranking step of the device transpose is quadratic in the length of a row
  * of the LOCAL transpose, as in nkp_transpose. */
 int nkp_transpose_dist (nkp_solver *s, nkp_solver **out);
+
+/* The sensitivity of a solve to the stored matrix values -- the last step of the backward pass that options.Trans (nkp_transpose
+ * above; SuperLU's Trans next to Fact and Equil, src/solve_ABglobal.c:327-335) opens: from x = A^-1 b and the adjoint solution
+ * lambda = A^-T (dL/dx) the sensitivity to the right-hand side is lambda itself, and to the matrix it is
+ * dL/da_ij = - lambda_i x_j on the sparsity pattern.  For every stored entry e of the solver's CSR matrix, with row i and column
+ * j = colind[e], and nrhs pairs of vectors,
+ *      s = lambda_0[i] * x_0[j];   s = s + lambda_c[i] * x_c[j]   for c = 1 .. nrhs - 1, ascending;
+ *      gval[e] = alpha * s   (accumulate == 0)        gval[e] = gval[e] + alpha * s   (accumulate != 0)
+ * in f64, every product and every sum rounded on its own (no fused multiply-add), so the result can be restated bit for bit on
+ * the host.  alpha = -1 gives the gradient with respect to the values, in the CSR order of nkp_create / nkp_create64 -- the order
+ * in which nkp_refactor* take new values.
+ *   Buffers, all the caller's: lambda and x hold nrhs vectors of n doubles, column-major, vector c at offset c * ld, ld >= n, as in
+ *   nkp_solve_batch_device; gval holds nnz doubles and is read only when accumulate != 0.  nkp_value_gradient takes host buffers,
+ *   nkp_value_gradient_device buffers on the solver's device.  1 <= nrhs <= 8; with more pairs call again with accumulate = 1:
+ *   the sum then chains per CALL, gval = (gval + alpha * s_first) + alpha * s_second, which in general is not the bit pattern of
+ *   one longer sum.  The work runs on the solver's stream and has finished when the call returns.
+ *   Only the pattern is read: the call is allowed on a clone, on a solver whose refactor failed after its commit point, and on
+ *   a transposed handle, where it gives the gradient with respect to the values of A^T in A^T's own CSR order (rows sorted by
+ *   column).  Work space -- K-interleaved copies of lambda and x for nrhs >= 2, the device staging of the host flavour -- is
+ *   allocated at first use, kept, and counted in "device_bytes"; a failed allocation leaves the solver exactly as it was.
+ *   nkp_get_int: "value_gradient_calls", "value_gradient_us" (wall time of the last call).
+ * Row-distributed solvers (nkp_create_dist with more than one rank, or force_dist): the same two entry points, COLLECTIVE, with
+ * the same nrhs on every rank.  Each rank passes its own rows of every vector (ld >= m_loc) and receives nnz_loc values in the
+ * order of the rowptr_loc / colind_glob it created the solver with.  lambda is needed on the own rows only; the halo rows of x
+ * come from their owners, all nrhs vectors in ONE alltoallv of nrhs-wide rows (for nrhs >= 2 the K-wide buffers of the batched
+ * solve, K = 2, 4 or 8; counted in "dist_alltoallv_calls").  The callbacks of nkp_comm_ops are reached in the same order on
+ * every rank whatever happens locally:
+ *      allgather_i64_host   agreement: arguments (nrhs, ld), work space, staging of the host vectors
+ *      alltoallv            the halo rows of x (device doubles, on the solver's stream; made like the SpMV's, also when this
+ *                           rank sends and receives nothing)
+ *      allgather_i64_host   agreement: exchange and kernel
+ *   After a failed agreement every rank returns: the rank whose step failed its own code and message, the others NKP_ECOMM
+ *   naming it; gval is then undefined, the solvers solve as before.
+ * Returns 0; NKP_EINVAL for a NULL solver or buffer (refused on the calling rank before the solver is looked at and before any
+ * collective; the message names the argument), nrhs outside 1 .. 8 or ld < n (found before any HIP call; on a row-distributed
+ * solver told to the other ranks through the first agreement); NKP_ENOMEM / NKP_EDEVICE; NKP_ECOMM. */
+int nkp_value_gradient_device (nkp_solver *s, int nrhs, const void *d_lambda, const void *d_x, int64_t ld, double alpha, int accumulate, void *d_gval);
+int nkp_value_gradient (nkp_solver *s, int nrhs, const double *lambda, const double *x, int64_t ld, double alpha, int accumulate, double *gval);
 
 /* hipSetDevice for host programs that do not link HIP themselves (call before nkp_comm_rccl_init). */
 int nkp_set_device (int device);

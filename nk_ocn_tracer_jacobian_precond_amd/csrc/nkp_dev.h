@@ -54,6 +54,10 @@ void launch_csr_abs_spmv (const CsrDev &A, const double *x, const double *b, dou
 // host helper: greedy row-block partition (host arrays)
 void build_rowblocks_host (int64_t n, const int *rowptr, int **rowblk_out, int *nrowblk_out);
 
+// nkp_value_gradient (valgrad.hip): g[e] (+)= alpha * sum_{c < nk} lam_c[row of e] * x_c[colind[e]] on the pattern of A, the sum taken
+// in ascending c, every product and sum rounded.  K in {1, 2, 4, 8}: interleave width of lam and x (1 = plain vectors), nk <= K
+void launch_value_gradient (int K, int nk, const CsrDev &A, const double *lam, const double *x, double alpha, int accumulate, double *g, hipStream_t st);
+
 // ---------------------------------------------------------------- water-column blocks
 // Banded LU (no pivoting) of every diagonal block, half-bandwidth P in {1,2,4}; SoA by
 // diagonal: fac[(d+P)*n + row] holds, for d<0 the L multiplier l(row,row+d), for d=0 the

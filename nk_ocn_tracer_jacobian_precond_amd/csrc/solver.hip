@@ -46,6 +46,7 @@ void solver_free (nkp_solver *s)
          for (void *p : lv)
             if (p) (void) hipFree (p);
       }
+      valgrad_release (s);
       if (s->hpin) (void) hipHostFree (s->hpin);
       if (s->own_stream && s->stream) (void) hipStreamDestroy (s->stream);
       s->shared->clones--;
@@ -54,6 +55,7 @@ void solver_free (nkp_solver *s)
    }
    if (s->trans_of) trans_detach (s);
    if (s->trans) trans_release (s);      // before the stream it shares goes
+   valgrad_release (s);
    for (nkp_solver *c : s->batch_members) solver_free (c);
    s->batch_members.clear ();
    for (double *p : { s->bvin, s->bz, s->bw })
@@ -633,6 +635,8 @@ extern "C" int64_t nkp_get_int (nkp_solver *s, const char *key)
    if (!strcmp (key, "trans_recv_entries")) return s->trans_received;
    if (!strcmp (key, "dist_alltoallv_calls")) return s->shared->alltoallv_calls.load ();
    if (!strcmp (key, "dist_allreduce_calls")) return s->shared->allreduce_calls.load ();
+   if (!strcmp (key, "value_gradient_calls")) return s->vg.calls;
+   if (!strcmp (key, "value_gradient_us")) return (int64_t) (s->vg.seconds * 1.0e6);
    if (!strcmp (key, "batch_steps")) return s->batch_steps;
    if (!strcmp (key, "batch_width")) return s->batch_width;
    if (!strcmp (key, "batch_member_bytes")) {      // the further sets of work vectors a batched group keeps (not part of device_bytes)
@@ -1049,6 +1053,7 @@ static int clone_impl (nkp_solver *src, nkp_solver **out, bool member)
    s->trans_map_bytes = 0;
    s->trans_ship = nullptr;
    s->trans_send = s->trans_recv = nullptr;
+   s->vg = decltype (s->vg) ();      // nkp_value_gradient's work space and counters are per handle
    s->A.tune = &s->tune;
    s->B.tune = &s->tune;
    s->ml.tune = &s->tune;
@@ -1109,6 +1114,48 @@ static void note_fallback (const nkp_solver *s, const char *who, const char *why
    msg (s, 1, "%s: %d right-hand sides one at a time: the batched path does not cover %s\n", who, nrhs, why);
 }
 
+// a set of device buffers of `count` doubles per unit of width each, all or nothing (see batch_prepare)
+static int buffer_set (nkp_solver *s, std::initializer_list<std::pair<double **, size_t>> set, int *width, int K_new)
+{
+   auto drop = [s, &set] (int K_old) {
+      for (auto &e : set)
+         if (*e.first) {
+            const size_t count = e.second * (size_t) K_old;
+            (void) hipFree (*e.first);
+            *e.first = nullptr;
+            s->device_bytes -= (count ? count : 1) * sizeof (double);      // what dev_alloc added
+         }
+   };
+   drop (*width);
+   *width = 0;
+   int rc = NKP_OK;
+   for (auto &e : set) {
+      const size_t count = e.second * (size_t) K_new;
+      if ((rc = dev_alloc (s, e.first, count)) != NKP_OK) break;
+      if (hipMemset (*e.first, 0, (count ? count : 1) * sizeof (double)) != hipSuccess) { rc = fail (NKP_EDEVICE, "nkp_solve_batch: hipMemset failed"); break; }
+   }
+   if (rc == NKP_OK) { *width = K_new; return NKP_OK; }
+   drop (K_new);
+   (void) hipGetLastError ();
+   return rc;
+}
+
+// the row-distributed part of batch_prepare (solver_impl.h): the buffers of the K-wide exchanges, for s->dist.bK < K
+int batch_prepare_exchange (nkp_solver *s, int K)
+{
+   // the host mirror of the Hessenberg columns is small: made once for the widest group
+   if (!s->dist.ghpin && hipHostMalloc ((void **) &s->dist.ghpin, (size_t) NKP_BATCH_MAX * (size_t) (s->m + 2) * sizeof (double), hipHostMallocDefault) != hipSuccess) {
+      s->dist.ghpin = nullptr;
+      (void) hipGetLastError ();
+      return fail (NKP_ENOMEM, "nkp_solve_batch: pinned host memory for the Gram-Schmidt messages");
+   }
+   const size_t gcount = 2 * (size_t) (s->m + 2) + 2;
+   return s->dist.ras_sep
+             ? buffer_set (s, { { &s->dist.bxe, (size_t) (s->n + s->dist.n_halo) }, { &s->dist.bsend, (size_t) s->dist.nsend }, { &s->dist.gmsg, gcount },
+                                { &s->dist.bras_send, (size_t) s->dist.ras_nsend }, { &s->dist.bras_recv, (size_t) s->dist.n_sel } }, &s->dist.bK, K)
+             : buffer_set (s, { { &s->dist.bxe, (size_t) (s->n + s->dist.n_halo) }, { &s->dist.bsend, (size_t) s->dist.nsend }, { &s->dist.gmsg, gcount } }, &s->dist.bK, K);
+}
+
 // Everything K systems in flight need.  Transactional per buffer set: after a failed allocation the set is gone and its
 // recorded width is 0 (never a width whose buffers are missing or short), and the sticky out-of-memory error is cleared, so
 // the narrower retry of the caller starts clean.
@@ -1123,46 +1170,12 @@ static int batch_prepare (nkp_solver *s, int K)
       c->own_stream = false;
       s->batch_members.push_back (c);
    }
-   // a set of device buffers of `count` doubles each, all or nothing
-   auto buffer_set = [s] (std::initializer_list<std::pair<double **, size_t>> set, int *width, int K_new) -> int {
-      auto drop = [s, &set] (int K_old) {
-         for (auto &e : set)
-            if (*e.first) {
-               const size_t count = e.second * (size_t) K_old;
-               (void) hipFree (*e.first);
-               *e.first = nullptr;
-               s->device_bytes -= (count ? count : 1) * sizeof (double);      // what dev_alloc added
-            }
-      };
-      drop (*width);
-      *width = 0;
-      int rc = NKP_OK;
-      for (auto &e : set) {
-         const size_t count = e.second * (size_t) K_new;
-         if ((rc = dev_alloc (s, e.first, count)) != NKP_OK) break;
-         if (hipMemset (*e.first, 0, (count ? count : 1) * sizeof (double)) != hipSuccess) { rc = fail (NKP_EDEVICE, "nkp_solve_batch: hipMemset failed"); break; }
-      }
-      if (rc == NKP_OK) { *width = K_new; return NKP_OK; }
-      drop (K_new);
-      (void) hipGetLastError ();
-      return rc;
-   };
    if (s->batch_K < K) {
-      const int rc = buffer_set ({ { &s->bvin, (size_t) s->ld }, { &s->bz, (size_t) s->ld }, { &s->bw, (size_t) s->ld } }, &s->batch_K, K);
+      const int rc = buffer_set (s, { { &s->bvin, (size_t) s->ld }, { &s->bz, (size_t) s->ld }, { &s->bw, (size_t) s->ld } }, &s->batch_K, K);
       if (rc) return rc;
    }
    if (s->dist.on && s->dist.bK < K) {
-      // the host mirror of the Hessenberg columns is small: made once for the widest group
-      if (!s->dist.ghpin && hipHostMalloc ((void **) &s->dist.ghpin, (size_t) NKP_BATCH_MAX * (size_t) (s->m + 2) * sizeof (double), hipHostMallocDefault) != hipSuccess) {
-         s->dist.ghpin = nullptr;
-         (void) hipGetLastError ();
-         return fail (NKP_ENOMEM, "nkp_solve_batch: pinned host memory for the Gram-Schmidt messages");
-      }
-      const size_t gcount = 2 * (size_t) (s->m + 2) + 2;
-      const int rc = s->dist.ras_sep
-                        ? buffer_set ({ { &s->dist.bxe, (size_t) (s->n + s->dist.n_halo) }, { &s->dist.bsend, (size_t) s->dist.nsend }, { &s->dist.gmsg, gcount },
-                                        { &s->dist.bras_send, (size_t) s->dist.ras_nsend }, { &s->dist.bras_recv, (size_t) s->dist.n_sel } }, &s->dist.bK, K)
-                        : buffer_set ({ { &s->dist.bxe, (size_t) (s->n + s->dist.n_halo) }, { &s->dist.bsend, (size_t) s->dist.nsend }, { &s->dist.gmsg, gcount } }, &s->dist.bK, K);
+      const int rc = batch_prepare_exchange (s, K);
       if (rc) return rc;
    }
    if (s->opt.precond == NKP_PRECOND_MULTILEVEL) {
@@ -1601,6 +1614,10 @@ extern "C" int nkp_time_kernel (nkp_solver *s, int which, int arg, int reps, dou
 {
    if (!s || !avg_ms || reps < 1) return fail (NKP_EINVAL, "nkp_time_kernel: bad argument");
    HIPCHK (hipSetDevice (s->device));
+   if (which == 5) {      // the gradient kernel of nkp_value_gradient at interleave width arg, on scratch operands of its own
+      const int prc = valgrad_time_prepare (s, arg);
+      if (prc) return prc;
+   }
    hipEvent_t e0, e1;
    HIPCHK (hipEventCreate (&e0));
    HIPCHK (hipEventCreate (&e1));
@@ -1625,6 +1642,7 @@ extern "C" int nkp_time_kernel (nkp_solver *s, int which, int arg, int reps, dou
          if (which == 0) spmv_op (s, s->t1, s->t2, nullptr, 0);
          else if (which == 1) apply_precond_once (s, s->t1, s->t2);
          else if (which == 2) arnoldi_step_device (s, arg);
+         else if (which == 5) valgrad_time_launch (s, arg);
          else if (s->opt.precond == NKP_PRECOND_MULTILEVEL) ml_time_piece (s->ml, which - 3, s->stream);   // 3: smoother residual rows, 4: column solves (level 0, colour 0)
       }
       HIPCHK (hipEventRecord (e1, s->stream));

@@ -132,6 +132,14 @@ struct nkp_solver {
    double *trans_send = nullptr, *trans_recv = nullptr;
    std::vector<int> trans_send_counts, trans_recv_counts;
    int64_t trans_nnz = 0, trans_sent = 0, trans_received = 0;
+   // nkp_value_gradient: the K-interleaved copies of lambda and x, the device staging of the host flavour (lambda and x side by
+   // side, the gradient), each with its capacity in doubles -- made at first use, kept, counted in device_bytes
+   struct {
+      double *lam = nullptr, *x = nullptr, *stage = nullptr, *g = nullptr;
+      size_t lam_cap = 0, x_cap = 0, stage_cap = 0, g_cap = 0;
+      int64_t calls = 0;
+      double seconds = 0.0;        // wall time of the last call
+   } vg;
    double *h_dev () { return dscal; }
    double *h2_dev () { return dscal + (m + 2); }
    double *misc_dev () { return dscal + 2 * (m + 2); }     // [0]=nrm2 [1]=inv [2]=dot out ...
@@ -159,6 +167,14 @@ NKP_PRIVATE void msg (const nkp_solver *s, int lvl, const char *fmt, ...);
 NKP_PRIVATE int dist_agree (nkp_solver *s, int local_rc, const char *who, const char *where);
 // developer switch ml_drop_intertracer: the matrix without the couplings between its tracer_cnt tracers, i.e. exactly what a
 // tracer-per-rank partition builds its rank-local hierarchies from
+// the K-wide exchange buffers of a row-distributed solver (bxe, bsend, gmsg, with several rings bras_send / bras_recv), all or
+// nothing: the part of the batched solve's preparation that nkp_value_gradient shares
+NKP_PRIVATE int batch_prepare_exchange (nkp_solver *s, int K);
+// ---- defined in valgrad_api.hip --------------------------------------------------------------------------------------------
+NKP_PRIVATE void valgrad_release (nkp_solver *s);
+// nkp_time_kernel, which = 5: scratch operands for the gradient kernel at interleave width K (1, 2, 4, 8), then one launch
+NKP_PRIVATE int valgrad_time_prepare (nkp_solver *s, int K);
+NKP_PRIVATE void valgrad_time_launch (nkp_solver *s, int K);
 // ---- defined in transpose.hip ----------------------------------------------------------------------------------------------
 // the owner frees its transposed solver and the value map; a transposed solver that is destroyed leaves its owner
 NKP_PRIVATE void trans_release (nkp_solver *s);

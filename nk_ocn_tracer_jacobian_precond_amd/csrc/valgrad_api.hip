@@ -1,0 +1,208 @@
+// nkp_value_gradient / nkp_value_gradient_device (include/nkp.h): the sensitivity of a solve to the stored matrix values,
+// g[e] (+)= alpha * sum_c lambda_c[row of e] * x_c[colind[e]], on single-GPU and row-distributed solvers.  The kernel is
+// valgrad.hip; this unit checks the arguments, keeps the work space, fetches the halo rows of x on a row-distributed solver
+// and keeps the ranks together.  Only the pattern of the solver's matrix is read.
+#include "solver_impl.h"
+
+#include <time.h>
+
+#include <initializer_list>
+
+namespace {
+
+struct Want {
+   double **p;
+   size_t *cap;        // doubles *p holds
+   size_t need;        // doubles this call needs
+};
+
+// Grow the buffers of `set` that are too small, all of them or none: the new ones are allocated first and take the place of
+// the old ones only when every allocation succeeded.  After a failure the solver holds exactly what it held before and HIP's
+// last error is cleared.
+int reserve (nkp_solver *s, std::initializer_list<Want> set, const char *who)
+{
+   double *fresh[8] = {};
+   int rc = NKP_OK;
+   size_t i = 0;
+   for (const Want &w : set) {
+      if (w.need > *w.cap) {
+         void *q = nullptr;
+         if (hipMalloc (&q, w.need * sizeof (double)) != hipSuccess) {
+            rc = fail (NKP_ENOMEM, "%s: hipMalloc of %zu bytes of work space failed", who, w.need * sizeof (double));
+            break;
+         }
+         fresh[i] = (double *) q;
+      }
+      i++;
+   }
+   if (rc) {
+      for (double *q : fresh)
+         if (q) (void) hipFree (q);
+      (void) hipGetLastError ();
+      return rc;
+   }
+   i = 0;
+   for (const Want &w : set) {
+      if (fresh[i]) {
+         if (*w.p) {
+            (void) hipFree (*w.p);
+            s->device_bytes -= *w.cap * sizeof (double);
+         }
+         *w.p = fresh[i];
+         *w.cap = w.need;
+         s->device_bytes += w.need * sizeof (double);
+      }
+      i++;
+   }
+   return NKP_OK;
+}
+
+inline int width_of (int nrhs) { return nrhs <= 1 ? 1 : nrhs <= 2 ? 2 : nrhs <= 4 ? 4 : 8; }
+
+// Host flavour: h_* given, d_* NULL; device flavour the other way round.  The entry points have refused NULL arguments on the
+// calling rank, before the solver is looked at and before any collective.
+int value_gradient (nkp_solver *s, int nrhs, const double *h_lam, const double *h_x, const double *d_lam, const double *d_x, int64_t ld, double alpha,
+                    int accumulate, double *h_g, double *d_g, const char *who)
+{
+   const bool host = h_g != nullptr;
+   const bool dist = s->dist.on;
+   auto &D = s->dist;
+   auto &W = s->vg;
+   const int64_t n = s->n, nnz = s->A.nnz;
+   hipStream_t st = s->stream;
+   struct timespec ts0;
+   clock_gettime (CLOCK_MONOTONIC, &ts0);
+
+   // ---- (a) this rank's arguments (no HIP call), its work space, the host vectors staged on the device
+   int rc = NKP_OK;
+   if (nrhs < 1 || nrhs > NKP_BATCH_MAX) rc = fail (NKP_EINVAL, "%s: nrhs = %d, must be 1 .. %d (more right-hand sides: call again with accumulate = 1)", who, nrhs, NKP_BATCH_MAX);
+   else if (ld < n) rc = fail (NKP_EINVAL, "%s: ld = %lld < n = %lld", who, (long long) ld, (long long) n);
+   if (rc && !dist) return rc;
+   const int K = width_of (nrhs);
+   if (!rc && hipSetDevice (s->device) != hipSuccess) rc = fail (NKP_EDEVICE, "%s: hipSetDevice (%d) failed", who, s->device);
+   if (!rc) {
+      const size_t il = K >= 2 ? (size_t) n * (size_t) K : 0;      // K = 1 reads the vectors in place
+      rc = reserve (s, { { &W.lam, &W.lam_cap, il }, { &W.x, &W.x_cap, dist ? 0 : il },      // row-distributed: x interleaved is dist.bxe
+                         { &W.stage, &W.stage_cap, host ? 2 * (size_t) nrhs * (size_t) n : 0 }, { &W.g, &W.g_cap, host ? (size_t) nnz : 0 } }, who);
+   }
+   if (!rc && dist && K >= 2 && D.bK < K) rc = batch_prepare_exchange (s, K);
+   const double *L = d_lam, *X = d_x;
+   double *G = d_g;
+   int64_t ldv = ld;
+   if (!rc && host) {
+      const size_t bytes = (size_t) n * sizeof (double);
+      hipError_t e = hipSuccess;
+      for (int c = 0; c < nrhs && e == hipSuccess && bytes; c++) {
+         e = hipMemcpyAsync (W.stage + (size_t) c * (size_t) n, h_lam + (size_t) c * (size_t) ld, bytes, hipMemcpyHostToDevice, st);
+         if (e == hipSuccess) e = hipMemcpyAsync (W.stage + (size_t) (nrhs + c) * (size_t) n, h_x + (size_t) c * (size_t) ld, bytes, hipMemcpyHostToDevice, st);
+      }
+      if (e == hipSuccess && accumulate && nnz) e = hipMemcpyAsync (W.g, h_g, (size_t) nnz * sizeof (double), hipMemcpyHostToDevice, st);
+      if (e != hipSuccess) rc = fail (NKP_EDEVICE, "%s: upload of the host vectors failed: %s", who, hipGetErrorString (e));
+      L = W.stage;
+      X = W.stage + (size_t) nrhs * (size_t) n;
+      G = W.g;
+      ldv = n;
+   }
+   if (dist && (rc = dist_agree (s, rc, who, "arguments and work space"))) {
+      // a rank whose K-wide exchange buffers are gone is not a rank "known to have buffers": the next batched solve agrees anew
+      D.agreed_K = 0;
+      return rc;
+   }
+   if (rc) return rc;
+
+   // ---- (b) the halo rows of x, all K vectors in one exchange; then the kernel
+   const double *lp[NKP_BATCH_MAX] = {}, *xp[NKP_BATCH_MAX] = {};
+   for (int c = 0; c < nrhs; c++) { lp[c] = L + (size_t) c * (size_t) ldv; xp[c] = X + (size_t) c * (size_t) ldv; }
+   const double *lam_in = L, *x_in = X;
+   if (K >= 2) {
+      launch_interleave (K, lp, W.lam, n, st);
+      lam_in = W.lam;
+   }
+   if (!dist) {
+      if (K >= 2) { launch_interleave (K, xp, W.x, n, st); x_in = W.x; }
+   } else {
+      int comm_rc;
+      s->shared->alltoallv_calls++;
+      if (K == 1) {
+         // as spmv_op fetches them: own rows copied, the rows the peers need packed, the halo behind the own rows
+         launch_copy (X, D.xe, n, st);
+         if (D.nsend) launch_gather (D.send_idx, X, D.sendbuf, D.nsend, st);
+         comm_rc = D.ops.alltoallv (D.ops.ctx, D.sendbuf, D.send_counts.data (), D.xe + n, D.recv_counts.data (), (void *) st);
+         x_in = D.xe;
+      } else {
+         // K-wide rows, the plan's counts times K (the buffers and counts of the batched solve)
+         D.send_counts_k.resize (D.send_counts.size ());
+         D.recv_counts_k.resize (D.recv_counts.size ());
+         for (size_t p = 0; p < D.send_counts.size (); p++) D.send_counts_k[p] = D.send_counts[p] * K;
+         for (size_t p = 0; p < D.recv_counts.size (); p++) D.recv_counts_k[p] = D.recv_counts[p] * K;
+         launch_interleave (K, xp, D.bxe, n, st);
+         if (D.nsend) launch_pack_rows_split (K, D.send_idx, xp, D.bsend, D.nsend, st);
+         comm_rc = D.ops.alltoallv (D.ops.ctx, D.bsend, D.send_counts_k.data (), D.bxe + (size_t) n * (size_t) K, D.recv_counts_k.data (), (void *) st);
+         x_in = D.bxe;
+      }
+      if (comm_rc) rc = fail (NKP_ECOMM, "%s: the exchange of the halo rows of x failed", who);
+   }
+   if (!rc) {
+      launch_value_gradient (K, nrhs, s->A, lam_in, x_in, alpha, accumulate, G, st);
+      hipError_t e = hipSuccess;
+      if (host && nnz) e = hipMemcpyAsync (h_g, W.g, (size_t) nnz * sizeof (double), hipMemcpyDeviceToHost, st);
+      if (e == hipSuccess) e = hipStreamSynchronize (st);
+      if (e == hipSuccess) e = hipGetLastError ();
+      if (e != hipSuccess) rc = fail (NKP_EDEVICE, "%s: the gradient kernel or its copies failed: %s", who, hipGetErrorString (e));
+   } else
+      (void) hipStreamSynchronize (st);
+   if (dist) rc = dist_agree (s, rc, who, "exchange and kernel");
+   if (rc) return rc;
+   struct timespec ts1;
+   clock_gettime (CLOCK_MONOTONIC, &ts1);
+   W.seconds = (double) (ts1.tv_sec - ts0.tv_sec) + 1e-9 * (double) (ts1.tv_nsec - ts0.tv_nsec);
+   W.calls++;
+   return NKP_OK;
+}
+
+}   // namespace
+
+void valgrad_release (nkp_solver *s)
+{
+   for (double **p : { &s->vg.lam, &s->vg.x, &s->vg.stage, &s->vg.g })
+      if (*p) { (void) hipFree (*p); *p = nullptr; }
+   s->vg.lam_cap = s->vg.x_cap = s->vg.stage_cap = s->vg.g_cap = 0;
+}
+
+int valgrad_time_prepare (nkp_solver *s, int K)
+{
+   if (s->dist.on) return fail (NKP_EINVAL, "nkp_time_kernel: the gradient kernel (which = 5) is timed on single-GPU solvers only");
+   if (K != 1 && K != 2 && K != 4 && K != 8) return fail (NKP_EINVAL, "nkp_time_kernel: which = 5 takes arg = K in {1, 2, 4, 8}");
+   const size_t il = K >= 2 ? (size_t) s->n * (size_t) K : 0;
+   const int rc = reserve (s, { { &s->vg.lam, &s->vg.lam_cap, il }, { &s->vg.x, &s->vg.x_cap, il }, { &s->vg.g, &s->vg.g_cap, (size_t) s->A.nnz } }, "nkp_time_kernel");
+   if (rc) return rc;
+   if (il) {
+      launch_fill (s->vg.lam, 1.0, (int64_t) il, s->stream);
+      launch_fill (s->vg.x, 1.0, (int64_t) il, s->stream);
+   }
+   return NKP_OK;
+}
+
+// K = 1 reads the solver's work vector t1 (filled by nkp_time_kernel) as lambda and as x
+void valgrad_time_launch (nkp_solver *s, int K)
+{
+   launch_value_gradient (K, K, s->A, K >= 2 ? s->vg.lam : s->t1, K >= 2 ? s->vg.x : s->t1, -1.0, 0, s->vg.g, s->stream);
+}
+
+extern "C" int nkp_value_gradient_device (nkp_solver *s, int nrhs, const void *d_lambda, const void *d_x, int64_t ld, double alpha, int accumulate, void *d_gval)
+{
+   if (!s) return fail (NKP_EINVAL, "nkp_value_gradient_device: NULL solver (argument s)");
+   if (!d_lambda) return fail (NKP_EINVAL, "nkp_value_gradient_device: NULL argument d_lambda");
+   if (!d_x) return fail (NKP_EINVAL, "nkp_value_gradient_device: NULL argument d_x");
+   if (!d_gval) return fail (NKP_EINVAL, "nkp_value_gradient_device: NULL argument d_gval");
+   return value_gradient (s, nrhs, nullptr, nullptr, (const double *) d_lambda, (const double *) d_x, ld, alpha, accumulate, nullptr, (double *) d_gval, "nkp_value_gradient_device");
+}
+
+extern "C" int nkp_value_gradient (nkp_solver *s, int nrhs, const double *lambda, const double *x, int64_t ld, double alpha, int accumulate, double *gval)
+{
+   if (!s) return fail (NKP_EINVAL, "nkp_value_gradient: NULL solver (argument s)");
+   if (!lambda) return fail (NKP_EINVAL, "nkp_value_gradient: NULL argument lambda");
+   if (!x) return fail (NKP_EINVAL, "nkp_value_gradient: NULL argument x");
+   if (!gval) return fail (NKP_EINVAL, "nkp_value_gradient: NULL argument gval");
+   return value_gradient (s, nrhs, lambda, x, nullptr, nullptr, ld, alpha, accumulate, gval, nullptr, "nkp_value_gradient");
+}

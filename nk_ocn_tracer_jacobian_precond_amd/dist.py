@@ -393,6 +393,9 @@ class NkpDistSolver(_solver.NkpSolver):
             comm = self._comm
             raise _solver.NkpError(rc, self._lib.nkp_last_error().decode() + (" | comm: " + "; ".join(comm.errors) if comm.errors else ""))
 
+    def _check_collective(self, rc):           # value_gradient / value_gradient_device: collective here, local slices in and out
+        self._check_dist(rc)
+
     def solve_many(self, B, raise_on_fail=True):
         """nkp_solve with nrhs = B.shape[0] right-hand sides, collective: every rank calls it with the same number of rows,
         each passing its own m_loc entries of every vector (ldb = m_loc).  Groups of 2 / 4 (8 with rhs_batch = 8) systems run in

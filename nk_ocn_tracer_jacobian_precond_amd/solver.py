@@ -31,6 +31,7 @@ ABI_SYMBOLS = [
     "nkp_create64", "nkp_cell_major_order", "nkp_permuted_rows", "nkp_dist_overlap_plan_host", "nkp_dist_plan_size",
     "nkp_dist_plan_copy", "nkp_dist_plan_free", "nkp_ml_level_array", "nkp_default_tuning", "nkp_solve_batch_device",
     "nkp_refactor", "nkp_refactor_device", "nkp_refactor_dist", "nkp_refactor_dist_device", "nkp_transpose", "nkp_transpose_dist",
+    "nkp_value_gradient", "nkp_value_gradient_device",
 ]
 
 _ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p)
@@ -125,6 +126,8 @@ def load_library(path=None):
     lib.nkp_clone.argtypes = [vp, C.POINTER(vp)]
     lib.nkp_transpose.argtypes = [vp, C.POINTER(vp)]
     lib.nkp_transpose_dist.argtypes = [vp, C.POINTER(vp)]
+    lib.nkp_value_gradient.argtypes = [vp, C.c_int, f64p, f64p, C.c_int64, C.c_double, C.c_int, f64p]
+    lib.nkp_value_gradient_device.argtypes = [vp, C.c_int, vp, vp, C.c_int64, C.c_double, C.c_int, vp]
     lib.nkp_refactor.argtypes = [vp, f64p, C.c_int]
     lib.nkp_refactor_device.argtypes = [vp, vp, C.c_int]
     lib.nkp_refactor_dist.argtypes = [vp, f64p, C.c_int]
@@ -343,6 +346,28 @@ class NkpSolver:
     def refactor_device(self, d_val, rebuild=False):
         """nkp_refactor_device: d_val = integer device address (e.g. torch tensor .data_ptr()) of nnz float64 on the solver's device."""
         self._check(self._lib.nkp_refactor_device(self._h, C.c_void_p(d_val), REFACTOR_REBUILD if rebuild else 0))
+
+    def value_gradient(self, lam, x, alpha=-1.0):
+        """nkp_value_gradient: g[e] = alpha * sum_c lam[c, row of e] * x[c, colind[e]] for every stored entry e, in the CSR order
+        the solver was created with -- with lam = A^-T (dL/dx) and alpha = -1 the gradient of L with respect to the matrix
+        values.  lam, x: shape (n,) or (K, n), K <= 8.  Returns nnz float64.  Collective on a row-distributed solver (local rows)."""
+        lam = np.ascontiguousarray(np.atleast_2d(np.asarray(lam, np.float64)))
+        x = np.ascontiguousarray(np.atleast_2d(np.asarray(x, np.float64)))
+        if lam.ndim != 2 or lam.shape != x.shape or lam.shape[1] != self.n:
+            raise ValueError(f"lam and x must both have shape ({self.n},) or (K, {self.n})")
+        g = np.empty(max(self.nnz, 1), np.float64)
+        self._check_collective(self._lib.nkp_value_gradient(self._h, lam.shape[0], _p(lam, C.c_double), _p(x, C.c_double), self.n, float(alpha), 0,
+                                                            _p(g, C.c_double)))
+        return g[:self.nnz]
+
+    def value_gradient_device(self, d_lam, d_x, nrhs, ld, d_g, alpha=-1.0, accumulate=False):
+        """nkp_value_gradient_device: d_lam / d_x = integer device addresses of nrhs vectors of n float64 each (vector c at
+        + 8 * c * ld), d_g of nnz float64, written (accumulate=False) or added to.  Runs on the solver's stream."""
+        self._check_collective(self._lib.nkp_value_gradient_device(self._h, int(nrhs), C.c_void_p(d_lam), C.c_void_p(d_x), int(ld), float(alpha),
+                                                                   int(bool(accumulate)), C.c_void_p(d_g)))
+
+    def _check_collective(self, rc):
+        self._check(rc)
 
     def spmv(self, x):
         x = np.ascontiguousarray(x, np.float64)
