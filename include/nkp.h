@@ -142,6 +142,10 @@ typedef struct nkp_tuning {
                                 With two or more rings the overlap residual travels in an exchange of its own (still one per preconditioner
                                 application) instead of riding on the SpMV halo.  No effect without dist_ras, grid positions or a lateral
                                 cut (a tracer partition has no overlap) */
+   int ml_diag;              /* NKP_ML_DIAG (32): level operators also stored as per-column diagonals, which the residual rows of the
+                                two-kernel half sweeps and the residual before the restriction then read instead of CSR (no per-entry
+                                column index; same bits).  N > 0 = a level gets them if no water column needs more than N diagonals
+                                and the padding stays within 1.5 x its entries, else it stays on CSR; 0 = off */
 } nkp_tuning;
 
 /* defaults, then the NKP_* environment overrides listed above */
@@ -603,7 +607,10 @@ int nkp_dist_plan_host (int64_t m_loc, int64_t nnz_loc, const int32_t *rowptr_lo
  * column blocks, a host array like "color_blk": which column-solve kernels serve the level -- wave_columns, wave_fused, stream,
  * ldsres (0 / 1 = LDS-resident / 2 = packed), gw (columns per group), P (half bandwidth stored), dropped (1 if entries beyond
  * the band were dropped), max_len (longest column), gs_ok (the fused half sweep can serve the level), ngrp, lds_doubles (dynamic
- * LDS of the lane kernels, in doubles)).  All in the level's colour-major row order. */
+ * LDS of the lane kernels, in doubles)), "dg_ptr" (int32, columns + 1) / "dg_key" (int32) / "dg_voff" (int64, columns) / "dg_val"
+ * (float): the per-column diagonals of tuning ml_diag, empty when the level runs on CSR -- column c of blk_start, of len rows, has
+ * the keys dg_key[dg_ptr[c] .. dg_ptr[c + 1]), ascending, and its row kl has the entry dg_val[dg_voff[c] + s * len + kl] in column
+ * key_s + kl, 0 where it has none.  All in the level's colour-major row order. */
 int64_t nkp_ml_level_array (nkp_solver *s, int level, const char *what, void *dst, int64_t capacity_bytes);
 
 /* Host-only planning step of the multilevel preconditioner inside nkp_create, exposed so the aggregation logic can

@@ -31,7 +31,8 @@ static void gs_half (const MlHierarchy &H, MlLevel &V, int c, bool fused, hipStr
       V.cur[c] = out;
       return;
    }
-   launch_csr_residual_range (V.L, V.color_rb[c], V.color_rb[c + 1], V.x, V.b, V.r, st);
+   if (V.L.dg_val) launch_diag_residual (V.L, V.color_tile[c], V.color_tile[c + 1], V.x, V.b, V.r, st);
+   else launch_csr_residual_range (V.L, V.color_rb[c], V.color_rb[c + 1], V.x, V.b, V.r, st);
    column_solves (H, V, c, V.r, V.x, 1, st);
 }
 
@@ -59,9 +60,7 @@ static void ml_cycle (MlHierarchy &H, int l, hipStream_t st)
       for (int s = 1; s < sweeps; s++) gs_sweep (H, V, s & 1, false, st);
       return;
    }
-   // ml_fused_max_cols: the fused half sweep only on levels with at most that many columns (the launch-bound end)
-   const int fused_max = H.tune->ml_fused_max_cols;
-   const bool fused = V.wave_fused || (H.fused && V.B.gs_ok && (fused_max <= 0 || V.color_grp[2] * V.B.gw <= fused_max));
+   const bool fused = ml_level_fused (H, V);
    // pre-smoothing from x = 0: the first half-sweep needs no SpMV (r = b on colour 0)
    launch_fill (V.x, 0.0, V.n, st);
    if (fused) {
@@ -82,7 +81,8 @@ static void ml_cycle (MlHierarchy &H, int l, hipStream_t st)
    MlLevel &C = H.lev[l + 1];
    const int gamma = (l >= H.gamma_from && l < H.gamma_to) ? 2 : 1;
    for (int g = 0; g < gamma; g++) {
-      launch_csr_spmv (V.L, V.xnow (), V.r, V.b, 1, st);
+      if (V.L.dg_val) launch_diag_residual (V.L, V.color_tile[0], V.color_tile[2], V.xnow (), V.b, V.r, st);
+      else launch_csr_spmv (V.L, V.xnow (), V.r, V.b, 1, st);
       launch_restrict_sum (V.rptr, V.ridx, V.r, C.b, V.nc, st);
       ml_cycle (H, l + 1, st);
       launch_prolong_add (V.cmap, C.xnow (), V.xnow (), V.n, H.omega, st);
@@ -240,12 +240,16 @@ void ml_time_piece (MlHierarchy &H, int which, hipStream_t st)
 {
    MlLevel &V = H.lev[0];
    if (H.lev.size () < 2) return;
-   if (which == 0) launch_csr_residual_range (V.L, V.color_rb[0], V.color_rb[1], V.x, V.b, V.r, st);
+   if (which == 0) {
+      if (V.L.dg_val) launch_diag_residual (V.L, V.color_tile[0], V.color_tile[1], V.x, V.b, V.r, st);
+      else launch_csr_residual_range (V.L, V.color_rb[0], V.color_rb[1], V.x, V.b, V.r, st);
+   }
    else launch_colblock_apply_lanes (V.B, V.color_grp[0], V.color_grp[1], V.r, V.x, 1, st);
 }
 
 // compulsory HBM bytes (every array element counted once per kernel that must touch it):
-//  which 0: residual rows of level 0, colour 0: its entries (value + column), row pointers, b in, r out, x once
+//  which 0: residual rows of level 0, colour 0: its entries (value + column), row pointers, b in, r out, x once; with the
+//           per-column diagonals its padded slots (value only), keys and tiles instead of entries and row pointers
 //  which 1: column solves of level 0, colour 0: factors, r in, x in and out
 //  which 2: one whole V(nu, nu) cycle
 int64_t ml_bytes (const MlHierarchy &H, int which)
@@ -254,6 +258,11 @@ int64_t ml_bytes (const MlHierarchy &H, int which)
    auto level_piece = [&] (const MlLevel &V, int colour, int what) -> int64_t {
       const int64_t rows = colour == 0 ? V.rows0 : V.n - V.rows0;
       const int64_t vb = V.L.valf ? 4 : 8, fb = V.B.fac_tf ? 4 : 8;
+      if (what == 0 && V.L.dg_val) {
+         // the colour's share of the slots, keys and tiles by its share of the rows (as below)
+         const double share = V.n ? (double) rows / (double) V.n : 0.0;
+         return (int64_t) (share * ((double) V.L.dg_nval * 4.0 + (double) V.L.dg_ntile * (double) sizeof (DgTile))) + rows * (8 + 8) + V.n * 8;
+      }
       if (what == 0) {
          // entries of the colour's rows: the colour-major CSR keeps them contiguous; split nnz by rows as an estimate is not
          // needed -- the host knows the exact count only at setup, so use the level's average row length
@@ -271,7 +280,8 @@ int64_t ml_bytes (const MlHierarchy &H, int which)
          total += (int64_t) (2 * nu) * level_piece (V, c, 1);                       // column solves: nu pre + nu post sweeps
          total += (int64_t) (2 * nu - (c == 0 ? 1 : 0)) * level_piece (V, c, 0);    // residual rows (the first half sweep needs none)
       }
-      total += V.L.nnz * ((V.L.valf ? 4 : 8) + 4) + V.n * (4 + 8 + 8 + 8);         // full residual before the restriction
+      if (V.L.dg_val) total += V.L.dg_nval * 4 + (int64_t) V.L.dg_ntile * (int64_t) sizeof (DgTile) + V.n * (8 + 8 + 8);
+      else total += V.L.nnz * ((V.L.valf ? 4 : 8) + 4) + V.n * (4 + 8 + 8 + 8);    // full residual before the restriction
       total += V.n * (8 + 4) + V.nc * (8 + 4);                                      // restriction
       total += V.n * (8 + 8 + 4) + V.nc * 8;                                        // prolongation
    }

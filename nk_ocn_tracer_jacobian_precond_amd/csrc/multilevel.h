@@ -11,6 +11,7 @@ struct MlLevel {
    int color_rb[3] = { 0, 0, 0 };    // SpMV row blocks of colour c: [color_rb[c], color_rb[c+1])
    int color_blk[3] = { 0, 0, 0 };   // column blocks of colour c
    int color_grp[3] = { 0, 0, 0 };   // lane-per-column groups of colour c
+   int color_tile[3] = { 0, 0, 0 };  // tiles of colour c in L's per-column diagonals (all 0: the level runs on CSR)
    int64_t rows0 = 0;           // rows of colour 0 (they come first)
    int wave_columns = 0;        // few columns: solve them one per wave (colblock_apply_kernel) instead of one per lane
    int wave_fused = 0;          // ... and run every half sweep as one launch (gs_wave_kernel: residual rows + band solve per wave)
@@ -55,6 +56,14 @@ struct MlHierarchy {
    int batch_K = 0;             // the level vectors of ml_apply_batch exist for this many right-hand sides
    int default_build = 0;       // built by the default construction (the one the setup kernels cover): nkp_refactor may keep the cells
 };
+
+// the level's half sweeps are one launch each (gs_wave_kernel or gs_fused_kernel) instead of residual rows + column solves
+inline bool ml_level_fused (const MlHierarchy &H, const MlLevel &V)
+{
+   // ml_fused_max_cols: the fused half sweep only on levels with at most that many columns (the launch-bound end)
+   const int fused_max = H.tune->ml_fused_max_cols;
+   return V.wave_fused || (H.fused && V.B.gs_ok && (fused_max <= 0 || V.color_grp[2] * V.B.gw <= fused_max));
+}
 
 // returns 0, or a negative nkp error code with a message in err
 int ml_setup (MlHierarchy &H, int64_t n, const int *rowptr, const int *colind, const double *val,

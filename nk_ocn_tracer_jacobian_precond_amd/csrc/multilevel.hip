@@ -103,6 +103,13 @@ int finish_level_columns (MlHierarchy &H, MlLevel &V, int l, const std::vector<i
       if (V.B.gs_ok && !((V.B.fac_tf && V.L.valf) || (V.B.fac_t && !V.L.valf))) V.B.gs_ok = 0;
       T.lay += secs_since (t_lay0);
    }
+   // per-column diagonals for the residual rows of the two-kernel half sweeps and the full residual (ml_diag = most keys a
+   // column may need; 0 = off).  A level that does not qualify stays on CSR.
+   if (H.tune->ml_diag > 0 && V.L.valf && !ml_level_fused (H, V)) {
+      auto t_dg0 = setup_clk::now ();
+      (void) diag_build (V.L, pblk.data (), V.B.blk_start, ncol, ncol0, V.B.max_len, H.tune->ml_diag, V.color_tile, &H.device_bytes, st);
+      T.lay += secs_since (t_dg0);
+   }
    // f32 storage mode: the f64 copy of the level operator was only needed to factor the column blocks
    if (V.L.valf && V.L.val) {
       (void) hipStreamSynchronize (st);
@@ -560,7 +567,7 @@ int ml_coarse_inverse (const MlHierarchy &H, int n, const int *prow, const int *
 void ml_free (MlHierarchy &H)
 {
    for (MlLevel &V : H.lev) {
-      void *ptrs[] = { V.L.rowptr, V.L.colind, V.L.val, V.L.valf, V.B.fac_tf, V.L.rowblk, V.L.codes, V.L.dict, V.L.dict_ptr, V.B.blk_start, V.B.fac, V.B.grp_b0, V.B.grp_nb, V.B.grp_maxlen, V.B.grp_base, V.B.grp_row0, V.B.col_slot, V.B.fac_t, V.B.gs_rb_ptr, V.B.gs_rb, V.B.wave_desc, V.cmap, V.rptr, V.ridx, V.x, V.x2, V.b, V.r, V.bx, V.bx2, V.bb, V.br };
+      void *ptrs[] = { V.L.rowptr, V.L.colind, V.L.val, V.L.valf, V.B.fac_tf, V.L.rowblk, V.L.codes, V.L.dict, V.L.dict_ptr, V.L.dg_ptr, V.L.dg_key, V.L.dg_voff, V.L.dg_val, V.L.dg_tile, V.B.blk_start, V.B.fac, V.B.grp_b0, V.B.grp_nb, V.B.grp_maxlen, V.B.grp_base, V.B.grp_row0, V.B.col_slot, V.B.fac_t, V.B.gs_rb_ptr, V.B.gs_rb, V.B.wave_desc, V.cmap, V.rptr, V.ridx, V.x, V.x2, V.b, V.r, V.bx, V.bx2, V.bb, V.br };
       for (void *p : ptrs)
          if (p) (void) hipFree (p);
    }

@@ -17,6 +17,14 @@
 #define NKP_SPMV_MAX_ROWS 256    // ... and rows (= threads of the SpMV workgroup) at most
 
 // ---------------------------------------------------------------- CSR matrix on the device
+// per-column diagonals (below): what one wave of the diagonal kernels needs of its tile, in one aligned 32-byte load
+struct alignas (32) DgTile {
+   int row0, rows;                    // first row of the tile, its rows (<= 64)
+   int kl0, len;                      // position of row0 inside its column, rows of the column
+   int k0, nk;                        // the column's keys: dg_key[k0 .. k0 + nk)
+   long long voff;                    // the column's value block: dg_val[voff + s * len + kl]
+};
+
 struct CsrDev {
    int64_t n = 0, nnz = 0;
    int *rowptr = nullptr;      // [n+1]
@@ -34,6 +42,18 @@ struct CsrDev {
    unsigned short *codes = nullptr;   // [nnz]
    int *dict = nullptr;
    int *dict_ptr = nullptr;           // [nrowblk+1]
+   // optional per-column diagonals of a level operator (diagop.hip; all NULL = the level runs on CSR).  Rows of a water
+   // column are contiguous and depth-ordered, so with kl = the position of a row inside its column, colind - kl takes few
+   // distinct values ("keys") over a column: one per (neighbour column, depth offset).  Column c keeps its keys ascending in
+   // dg_key[dg_ptr[c] .. dg_ptr[c+1]) and one dense diagonal per key: dg_val[dg_voff[c] + s * len + kl] is the entry of row
+   // kl in column key_s + kl, exactly 0.0f where the row has none.  Ascending keys = ascending columns within every row.
+   int *dg_ptr = nullptr;             // [ncol+1]
+   int *dg_key = nullptr;             // [dg_nkey = dg_ptr[ncol]] (+ 8 zeros: the residual kernel reads keys eight at a time)
+   long long *dg_voff = nullptr;      // [ncol]
+   float *dg_val = nullptr;           // [dg_nval]
+   DgTile *dg_tile = nullptr;         // [dg_ntile] one per (column, 64 rows of it), in row order
+   int dg_ntile = 0, dg_ncol = 0, dg_nkey = 0;
+   int64_t dg_nval = 0;
    const nkp_tuning *tune = nullptr;  // launch shape knobs of the owning solver (NULL: built-in defaults)
 };
 
@@ -51,6 +71,17 @@ void launch_csr_residual_range (const CsrDev &A, int rb0, int rb1, const double 
 void launch_csr_spmv_range (const CsrDev &A, int rb0, int rb1, const double *x, double *y, const double *b, int mode, hipStream_t st);
 // y = |A| |x| + |b|   (denominator of the componentwise backward error)
 void launch_csr_abs_spmv (const CsrDev &A, const double *x, const double *b, double *y, hipStream_t st);
+// ---- per-column diagonals (diagop.hip)
+// Build the layout of L from its CSR arrays (f32 values) if every column gets by with at most cap keys, no column is longer
+// than 256 rows and the padded slots stay within 1.5 nnz; h_blk_start / d_blk_start: row offsets of the ncol columns, the first
+// ncol0 of them colour 0.  Returns 1 (built: color_tile[c] .. color_tile[c+1] are colour c's tiles) or 0 (L stays on CSR: not
+// eligible, or out of device memory, which is answered here).
+int diag_build (CsrDev &L, const int *h_blk_start, const int *d_blk_start, int ncol, int ncol0, int max_len, int cap, int color_tile[3],
+                size_t *device_bytes, hipStream_t st);
+// dg_val from L.valf (new values on the same pattern)
+void launch_diag_fill (const CsrDev &L, hipStream_t st);
+// rows of the tiles [tile0, tile1): y_rows = b_rows - (L x)_rows, every row summed in stored order like the CSR kernels
+void launch_diag_residual (const CsrDev &L, int tile0, int tile1, const double *x, const double *b, double *y, hipStream_t st);
 // host helper: greedy row-block partition (host arrays)
 void build_rowblocks_host (int64_t n, const int *rowptr, int **rowblk_out, int *nrowblk_out);
 

@@ -379,6 +379,7 @@ int rf_commit (RefactorWork &W, MlHierarchy &H, hipStream_t st, char *err, size_
       const double *nv = W.lev[l].nv;
       if (V.L.val && V.L.nnz) (void) hipMemcpyAsync (V.L.val, nv, (size_t) V.L.nnz * sizeof (double), hipMemcpyDeviceToDevice, st);
       if (V.L.valf && V.L.nnz) mls::to_float (nv, V.L.valf, V.L.nnz, st);
+      launch_diag_fill (V.L, st);         // the per-column diagonals, where the level has them, hold the same values
       if (V.B.fac) {
          CsrDev t = V.L;                  // the f64 values the setup factored (the level keeps only the f32 copy in f32 storage mode)
          t.val = const_cast<double *> (nv);

@@ -59,7 +59,7 @@ class NkpTuning(C.Structure):
         ("spmv_variant", C.c_int), ("spmv_compress", C.c_int), ("spmv_pipe_min", C.c_int), ("spmv_run", C.c_int), ("spmv_wgs", C.c_int),
         ("rhs_batch", C.c_int), ("precond_steps", C.c_int), ("equil", C.c_int), ("dist_overlap", C.c_int), ("dist_ras", C.c_int), ("force_dist", C.c_int),
         ("setup_threads", C.c_int), ("plan_times", C.c_int), ("ml_drop_intertracer", C.c_int), ("dist_one_reduce", C.c_int), ("ml_huge_from", C.c_int), ("col_ldsres_min", C.c_int), ("col_sort_groups", C.c_int), ("batch_spmv_rows", C.c_int),
-        ("dist_ras_rings", C.c_int),
+        ("dist_ras_rings", C.c_int), ("ml_diag", C.c_int),
     ]
 
 
@@ -401,7 +401,7 @@ class NkpSolver:
         return int(self._lib.nkp_get_int(self._h, key.encode()))
 
     _ML_ARRAY_TYPES = {"valf": np.float32, "val": np.float64, "fac": np.float64, "coarse_inv": np.float64, "color_blk": np.int32,
-                       "col_kernel": np.int32}
+                       "col_kernel": np.int32, "dg_ptr": np.int32, "dg_key": np.int32, "dg_voff": np.int64, "dg_val": np.float32}
 
     def ml_level_array(self, level, what):
         """One array of the multilevel hierarchy as it sits on the device (nkp_ml_level_array); empty if the level has none."""
