@@ -17,7 +17,7 @@
 #define DG_THREADS 256
 #define DG_WAVES (DG_THREADS / NKP_WAVE)
 #define DG_RPL 4                 // rows per lane of the key kernel: columns of up to 256 rows
-#define DG_UNROLL 8              // slots whose loads are in flight together
+#define DG_UNROLL 8              // slots whose loads are in flight together (and the zeros behind dg_key)
 
 // ---------------------------------------------------------------- setup: the keys of every column
 // One wave per column, lane l walks rows l, l + 64, ..: every round takes the smallest key any row still has to offer (rows
@@ -97,8 +97,28 @@ void diag_fill_kernel (int ntile, const DgTile *__restrict__ tile, const int *__
 // One wave per tile, lane l < rows owns row row0 + l (the lanes behind the tile's end repeat its last row and store nothing,
 // so every load stays inside the arrays).  The tile and the keys are wave-uniform: scalar loads.  Per slot one contiguous
 // f32 load of the diagonal and one contiguous load of x at key + kl, clamped into [0, n) -- out of range only where the
-// value is a padded zero; DG_UNROLL slots are requested before the first is consumed (the slots behind the column's last repeat
-// its values, replaced by zero, and take whatever key follows in dg_key, one load for the DG_UNROLL of them).  f64 product and sum, each rounded, in slot order.
+// value is a padded zero.  f64 product and sum, each rounded, in slot order.
+//
+// dg_slots: M slots from slot s on, all 2 M loads requested before the first is consumed.  The kernel takes a column's nk
+// slots DG_UNROLL at a time and the nk % DG_UNROLL behind them in one step of exactly that length: the launch is bound by
+// the vector loads it issues, not by their bytes, and a last step filled up to DG_UNROLL with repeated loads cost 9.5 % more
+// of them on the 1 degree levels (keys per column 13 .. 17, mean 14.8: two steps, 16 slots).
+template <int M>
+__device__ __forceinline__ void dg_slots (const int *__restrict__ key, const float *__restrict__ val, const double *__restrict__ x, int s, int len, int kl,
+                                          int n, double &acc)
+{
+   float v[M];
+   double xv[M];
+#pragma unroll
+   for (int u = 0; u < M; u++) {
+      const int j = min (max (key[s + u] + kl, 0), n - 1);
+      v[u] = (val + (size_t) (s + u) * len)[kl];
+      xv[u] = x[j];
+   }
+#pragma unroll
+   for (int u = 0; u < M; u++) acc += (double) v[u] * xv[u];
+}
+
 __global__ __launch_bounds__ (DG_THREADS)
 void diag_residual_kernel (const DgTile *__restrict__ tile, int ntile, const int *__restrict__ dg_key, const float *__restrict__ dg_val,
                            const double *__restrict__ x, const double *__restrict__ b, double *__restrict__ y, int n)
@@ -112,23 +132,19 @@ void diag_residual_kernel (const DgTile *__restrict__ tile, int ntile, const int
    const double bv = b[T.row0 + lr];
    const int *__restrict__ key = dg_key + T.k0;
    const float *__restrict__ val = dg_val + T.voff;
-   const int last = T.nk - 1;
    double acc = 0.0;
-   for (int s = 0; s < T.nk; s += DG_UNROLL) {
-      float v[DG_UNROLL];
-      double xv[DG_UNROLL];
-#pragma unroll
-      for (int u = 0; u < DG_UNROLL; u++) {
-         const int ss = min (s + u, last);
-         const int j = min (max (key[s + u] + kl, 0), n - 1);     // (dg_key is padded: behind the last column's keys it is still ours)
-         v[u] = (val + (size_t) ss * T.len)[kl];
-         xv[u] = x[j];
-      }
-#pragma unroll
-      for (int u = 0; u < DG_UNROLL; u++) {
-         const float vu = s + u <= last ? v[u] : 0.0f;
-         acc += (double) vu * xv[u];
-      }
+   int s = 0;
+   for (; s + DG_UNROLL <= T.nk; s += DG_UNROLL) dg_slots<DG_UNROLL> (key, val, x, s, T.len, kl, n, acc);
+   static_assert (DG_UNROLL == 8, "one case per length of the last step");
+   switch (T.nk - s) {
+      case 1: dg_slots<1> (key, val, x, s, T.len, kl, n, acc); break;
+      case 2: dg_slots<2> (key, val, x, s, T.len, kl, n, acc); break;
+      case 3: dg_slots<3> (key, val, x, s, T.len, kl, n, acc); break;
+      case 4: dg_slots<4> (key, val, x, s, T.len, kl, n, acc); break;
+      case 5: dg_slots<5> (key, val, x, s, T.len, kl, n, acc); break;
+      case 6: dg_slots<6> (key, val, x, s, T.len, kl, n, acc); break;
+      case 7: dg_slots<7> (key, val, x, s, T.len, kl, n, acc); break;
+      default: break;
    }
    if (lane < T.rows) y[T.row0 + lane] = bv - acc;
 }

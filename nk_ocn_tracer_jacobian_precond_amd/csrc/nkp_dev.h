@@ -48,7 +48,7 @@ struct CsrDev {
    // dg_key[dg_ptr[c] .. dg_ptr[c+1]) and one dense diagonal per key: dg_val[dg_voff[c] + s * len + kl] is the entry of row
    // kl in column key_s + kl, exactly 0.0f where the row has none.  Ascending keys = ascending columns within every row.
    int *dg_ptr = nullptr;             // [ncol+1]
-   int *dg_key = nullptr;             // [dg_nkey = dg_ptr[ncol]] (+ 8 zeros: the residual kernel reads keys eight at a time)
+   int *dg_key = nullptr;             // [dg_nkey = dg_ptr[ncol]] (+ 8 zeros behind them, which no kernel reads)
    long long *dg_voff = nullptr;      // [ncol]
    float *dg_val = nullptr;           // [dg_nval]
    DgTile *dg_tile = nullptr;         // [dg_ntile] one per (column, 64 rows of it), in row order

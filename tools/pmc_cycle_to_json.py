@@ -26,9 +26,9 @@ cal_f = sum(fetch[scale]) / len(fetch[scale])
 rec = {"workload": "320x384x60 upwind3+isop (K33), fine level, one colour", "n": info["n"], "nnz": info["nnz"],
        "calibration": {"kernel": "scale_to_kernel", "FETCH_SIZE_KB": cal_f, "algorithmic_read_KB": info["n"] * 8 / 1024.0,
                        "fetch_factor": info["n"] * 8 / 1024.0 / cal_f}, "kernels": []}
-for prefix, key, ms in (("void csr_spmv_pipe_kernel<1, float", "smoother_spmv_bytes", "smoother_ms"),
-                        ("void colblock_apply_ldspack_kernel<2", "column_solve_bytes", "column_ms")):
-    names = [k for k in fetch if k.startswith(prefix)]
+for prefix, key, ms in (("diag_residual_kernel", "smoother_spmv_bytes", "smoother_ms"),
+                        ("colblock_apply_ldspack_kernel<2", "column_solve_bytes", "column_ms")):
+    names = [k for k in fetch if k.replace("void ", "", 1).startswith(prefix)]
     if not names:
         raise SystemExit(f"kernel {prefix} not found in {list(fetch)[:10]}")
     k = names[0]
