@@ -287,7 +287,9 @@ int nkp_time_kernel (nkp_solver *s, int which, int arg, int reps, double *avg_ms
  * column-Jacobi preconditioner, the lane layout of its column blocks: "col_stream" (1 = factors streamed), "col_ldsres" (0, 1 =
  * column resident in LDS, 2 = packed), "col_gw" (columns per group), "col_max_len" (longest column), "col_lds_bytes" (dynamic LDS);
  * "create_us" (wall time of nkp_create), "ml_setup_us" (of which: the hierarchy), "ml_levels_on_device" (levels whose operator
- * the setup kernels built; the smaller ones are built on the host);
+ * the setup kernels built; the smaller ones are built on the host), "ml_inverse_pivoted" (1 = the last level's dense inverse came
+ * from the pivoted routine, because the blocked elimination met a pivot it does not trust; 0 = blocked elimination or the host routine;
+ * read it on the solver that owns the hierarchy: a clone keeps the value of the moment it was cloned, also across a refactor of its owner);
  * compulsory HBM bytes of the pieces nkp_time_kernel times: "smoother_spmv_bytes", "column_solve_bytes", "cycle_bytes";
  * distributed flavour: "dist_overlap" (halo exchange hidden behind the interior rows), "dist_interior_rowblocks",
  * "dist_ras" (hierarchy overlaps the neighbouring ranks), "dist_ras_rows" (rows of other ranks in this rank's hierarchy, all rings),

@@ -53,6 +53,7 @@ struct MlHierarchy {
    size_t device_bytes = 0;
    double setup_seconds = 0.0;  // wall time of ml_setup
    int levels_on_device = 0;    // levels whose operator was built by the kernels of mlsetup.hip
+   int inverse_pivoted = 0;     // coarse_inv came from the pivoted routine (ml_coarse_inverse returned 1); 0: blocked elimination or the host routine
    int batch_K = 0;             // the level vectors of ml_apply_batch exist for this many right-hand sides
    int default_build = 0;       // built by the default construction (the one the setup kernels cover): nkp_refactor may keep the cells
 };

@@ -226,6 +226,7 @@ int finalize_host_level (MlHierarchy &H, int l, int nlev, Nat &N, Nat *Cn, const
          const int brc = ml_coarse_inverse (H, (int) nl, prow.data (), pcol.data (), pval.data (), &H.coarse_inv, &H.coarse_invf, &H.coarse_ldf, &H.device_bytes, st);
          if (brc == -2) ML_FAIL (-2, "multilevel setup: device allocation failed (dense inverse of %lld rows)", (long long) nl);
          if (brc == -4) ML_FAIL (-4, "multilevel setup: coarsest operator is singular (or the device is out of memory)");
+         H.inverse_pivoted = brc == 1;
          if (verbose) printf ("(%d) multilevel: dense inverse of %lld rows: %s, %.3f s\n", rank, (long long) nl, brc == 0 ? "blocked elimination" : "a pivot too small for it, pivoted routine instead", secs_since (t_inv0));
       }
    }

@@ -29,6 +29,7 @@ struct RefactorWork {
    float *invf_new = nullptr;
    int ldf_new = 0;
    size_t inv_bytes = 0;
+   int inv_pivoted = 0;          // ml_coarse_inverse's return value for inv_new: 1 = the pivoted routine made it
 };
 
 // free the maps (keeps aval / dcnt); returns the bytes released

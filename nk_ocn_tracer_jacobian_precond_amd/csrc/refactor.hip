@@ -395,6 +395,7 @@ int rf_commit (RefactorWork &W, MlHierarchy &H, hipStream_t st, char *err, size_
    if (H.coarse_inv && W.inv_new) {
       const MlLevel &V = H.lev[nlev - 1];
       const size_t nn = (size_t) V.n * (size_t) V.n;
+      H.inverse_pivoted = W.inv_pivoted;
       if (rf_inverse_same_storage (W, H)) {
          // same storage: into the buffers the cycle (and every clone) already points at
          bool ok = hipMemcpyAsync (H.coarse_inv, W.inv_new, nn * sizeof (double), hipMemcpyDeviceToDevice, st) == hipSuccess;
@@ -445,6 +446,7 @@ int rf_prepare_inverse (RefactorWork &W, const MlHierarchy &H, hipStream_t st, c
    const int irc = ml_coarse_inverse (H, (int) V.n, W.last_rowptr.data (), W.last_colind.data (), hv.data (), &W.inv_new, &W.invf_new, &W.ldf_new, &W.inv_bytes, st);
    if (irc == -4) RF_FAIL (-4, "nkp_refactor: the coarsest operator of the new values is singular (or the device is out of memory); the solver is unchanged");
    if (irc < 0) { (void) hipGetLastError (); RF_FAIL (-2, "nkp_refactor: device allocation failed (dense inverse of %lld rows)", (long long) V.n); }
+   W.inv_pivoted = irc == 1;
    return 0;
 }
 

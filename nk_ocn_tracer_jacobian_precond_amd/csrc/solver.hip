@@ -625,6 +625,7 @@ extern "C" int64_t nkp_get_int (nkp_solver *s, const char *key)
    if (!strcmp (key, "column_solve_bytes")) return s->opt.precond == NKP_PRECOND_MULTILEVEL ? ml_bytes (s->ml, 1) : 0;
    if (!strcmp (key, "cycle_bytes")) return s->opt.precond == NKP_PRECOND_MULTILEVEL ? ml_bytes (s->ml, 2) : 0;
    if (!strcmp (key, "ml_levels_on_device")) return s->ml.levels_on_device;
+   if (!strcmp (key, "ml_inverse_pivoted")) return s->ml.inverse_pivoted;
    if (!strcmp (key, "ml_setup_us")) return (int64_t) (s->ml.setup_seconds * 1.0e6);
    if (!strcmp (key, "create_us")) return (int64_t) (s->create_seconds * 1.0e6);
    if (!strcmp (key, "refactor_count")) return s->refactor_count;

@@ -823,15 +823,9 @@ def test_device_dense_inverse_matches_host(medium, monkeypatch):
 def test_blocked_dense_inverse_sizes(n):
     """Block-size edges of the blocked elimination: a one-level 'hierarchy' whose only level is solved by its dense inverse
     (tridiagonal-plus-random diagonally dominant operators of 1 .. 1000 rows, single-row water columns)."""
-    rng = np.random.default_rng(n)
-    import scipy.sparse as sp
-    A = sp.random(n, n, density=min(1.0, 6.0 / n), random_state=int(n), format="csr")
-    A = -abs(A) - abs(A.T)
-    A = (A - sp.diags(np.asarray(A.sum(axis=1)).ravel() - 1.0 - rng.random(n))).tocsr()
-    A = (-A).tocsr()                                  # the sign of an ocean Jacobian: negative diagonal (the twin keeps such a matrix as it is)
-    A.sort_indices()
+    import dense_cases
+    A, b = dense_cases.benign_with_rhs(n)
     blk = np.arange(n + 1, dtype=np.int32)
-    b = rng.standard_normal(n)
     with solver.NkpSolver(A.indptr.astype(np.int32), A.indices.astype(np.int32), A.data, blk, col_i=np.arange(n, dtype=np.int32), col_j=np.zeros(n, np.int32),
                           restart=10, tuning=dict(ml_f32=0)) as s:
         assert s.get_int("levels") == 1
