@@ -280,7 +280,12 @@ int nkp_multi_dot (nkp_solver *s, const double *V, int64_t ld, int k, const doub
  * 2 = one full Krylov iteration body at restart position `arg` (0 <= arg < restart); multilevel only: 3 = the
  * smoother's residual rows of one colour of the fine level, 4 = the water-column solves of that colour; 5 = the gradient kernel of
  * nkp_value_gradient alone with K = arg in {1, 2, 4, 8} pairs of vectors, on scratch vectors of the solver (single-GPU solvers
- * only, NKP_EINVAL elsewhere and for another arg; its compulsory bytes: 12 nnz + 4 (n + 1) + 16 K n). */
+ * only, NKP_EINVAL elsewhere and for another arg; its compulsory bytes: 12 nnz + 4 (n + 1) + 16 K n); 6 = the product kernel of
+ * nkp_values_product alone with K = arg in {1, 2, 4, 8} vectors, values and vectors scratch of the solver, alpha = -1 without
+ * accumulation (single-GPU solvers only, NKP_EINVAL elsewhere and for another arg; its compulsory bytes: 12 nnz + 4 (n + 1) +
+ * 16 K n, plus 8 K n when accumulating -- at K = 1 exactly the SpMV's); 7 = for comparison with 6, same arg: the composition
+ * that kernel replaces, made of the SpMV kernels on the solver's own values -- the (batched) operator product into a temporary, its
+ * de-interleave, one update pass over the K vectors (24 K n more bytes). */
 int nkp_time_kernel (nkp_solver *s, int which, int arg, int reps, double *avg_ms);
 
 /* Introspection: key = "n", "nnz", "nblk", "band", "levels", "spmv_bytes", "device_bytes", "precond_steps", "equil";
@@ -297,7 +302,9 @@ int nkp_time_kernel (nkp_solver *s, int which, int arg, int reps, double *avg_ms
  * "dist_ras_recv_rows" (rows received per preconditioner application: the SpMV halo with one ring, the overlap rows with more);
  * counters, cumulative over the solver's life, per rank: "dist_alltoallv_calls", "dist_allreduce_calls" (every call of the two
  * device collectives made by solves, single or batched, and the one alltoallv of every nkp_value_gradient*; 0 on a single-GPU
- * solver), "value_gradient_calls" (successful nkp_value_gradient* calls), "value_gradient_us" (wall time of the last one), "batch_steps" (batched operator
+ * solver), "value_gradient_calls" (successful nkp_value_gradient* calls), "value_gradient_us" (wall time of the last one),
+ * "values_product_calls" (successful products: nkp_values_product* calls and the one inside every nkp_solve_tangent_device with
+ * d_dval), "values_product_us" (wall time of the last one), "tangent_calls" (nkp_solve_tangent_device calls that ran their solve), "batch_steps" (batched operator
  * applications = lockstep Krylov steps of a group of right-hand sides), "batch_width" (K of the last batched group, 0 if
  * none ran); "batch_member_bytes" (device bytes of the K - 1 further sets of work vectors a batched call has made and keeps:
  * Krylov bases, level vectors, with chained cycles the residual between two cycles; "device_bytes" counts the solver's own set
@@ -557,6 +564,55 @@ int nkp_transpose_dist (nkp_solver *s, nkp_solver **out);
  * solver told to the other ranks through the first agreement); NKP_ENOMEM / NKP_EDEVICE; NKP_ECOMM. */
 int nkp_value_gradient_device (nkp_solver *s, int nrhs, const void *d_lambda, const void *d_x, int64_t ld, double alpha, int accumulate, void *d_gval);
 int nkp_value_gradient (nkp_solver *s, int nrhs, const double *lambda, const double *x, int64_t ld, double alpha, int accumulate, double *gval);
+
+/* The product of caller-supplied values on the solver's sparsity pattern with nrhs vectors -- the forward-mode partner of
+ * nkp_value_gradient: with dA the perturbation of the stored values, the tangent of X = A^-1 B is dX = A^-1 (dB - dA X), and
+ * dA X is this product.  It also gives A_new x and b - A_new x for the next Jacobian on the same stencil before a refactor.
+ * For every row i and vector c, with t_c[i] = the sum over the stored entries e of row i of val[e] * x_c[colind[e]],
+ *      y_c[i] = alpha * t_c[i]   (accumulate == 0; y is not read and may hold anything)      y_c[i] = y_c[i] + alpha * t_c[i]   (accumulate != 0)
+ * alpha * t is one rounded product, the sum one rounded sum (no fused multiply-add).  t_c[i] has the bits nkp_spmv_device gives
+ * for x_c on a solver created from the same pattern with val as its values: +0.0, then every stored entry of the row in stored
+ * order, each product and each sum rounded on its own; a row of more than 2048 entries is summed in the SpMV's tree for such
+ * rows.  The bits are the same for every nrhs.  A row without entries gets alpha * (+0.0).
+ *   Buffers, all the caller's: val holds nnz doubles in the CSR order of nkp_create / nkp_create64 (the order of nkp_refactor* and
+ *   nkp_value_gradient*); x and y hold nrhs vectors, column-major, vector c at offset c * ldx and c * ldy, ldx, ldy >= n; rows
+ *   n .. ld - 1 are neither read nor written.  1 <= nrhs <= 8.  nkp_values_product takes host buffers, nkp_values_product_device
+ *   buffers on the solver's device.  y == x is refused (NKP_EINVAL); any other overlap of y with val or x is the caller's error
+ *   and gives undefined values.  The work runs on the solver's stream and has finished when the call returns.
+ *   Only the pattern is read: the call is allowed on a clone, on a solver whose refactor failed after its commit point, and on a
+ *   transposed handle, where val is in A^T's own CSR order and t is the product with A^T's pattern; a refactor does not change
+ *   the result.  Work space -- the K-interleaved copy of x for nrhs >= 2 (8 K n bytes, K = 2, 4 or 8), the device staging of the
+ *   host flavour (8 (nnz + 2 nrhs n) bytes) -- is allocated at first use, all or nothing, kept, and counted in "device_bytes"; a
+ *   failed allocation leaves the solver exactly as it was.  nkp_get_int: "values_product_calls", "values_product_us".
+ * Row-distributed solvers: the same entry points, COLLECTIVE, with the same nrhs on every rank.  Each rank passes nnz_loc values
+ * in the order of the rowptr_loc / colind_glob it created the solver with and its own rows of every vector (ldx, ldy >= m_loc).
+ * The halo rows of x come from their owners, all nrhs vectors in ONE alltoallv (K = 1: the SpMV's buffers; K >= 2: the K-wide
+ * buffers of the batched solve; counted in "dist_alltoallv_calls").  The callbacks are reached in the same order on every rank
+ * whatever happens locally, the sequence of nkp_value_gradient*:
+ *      allgather_i64_host   agreement: arguments, work space, staging of the host arrays
+ *      alltoallv            the halo rows of x (always made, also by a rank that sends and receives nothing)
+ *      allgather_i64_host   agreement: exchange and kernel
+ *   After a failed agreement every rank returns: the rank whose step failed its own code and message, the others NKP_ECOMM
+ *   naming it; y is then undefined, the solvers solve as before.
+ * Returns 0; NKP_EINVAL for a NULL solver or buffer (refused on the calling rank before the solver is looked at and before any
+ * collective; the message names the argument), nrhs outside 1 .. 8, ldx or ldy < n, y == x (found before any HIP call; on a
+ * row-distributed solver told to the other ranks through the first agreement); NKP_ENOMEM / NKP_EDEVICE; NKP_ECOMM. */
+int nkp_values_product_device (nkp_solver *s, int nrhs, const void *d_val, const void *d_x, int64_t ldx, double alpha, int accumulate, void *d_y, int64_t ldy);
+int nkp_values_product (nkp_solver *s, int nrhs, const double *val, const double *x, int64_t ldx, double alpha, int accumulate, double *y, int64_t ldy);
+
+/* The tangent (forward mode) of a solve: dX = A^-1 (dB - dA X) for nrhs right-hand sides, device buffers.  R_c = dB_c - dA X_c is
+ * formed in work space of the solver (8 nrhs ld bytes, at first use, kept, counted in "device_bytes") and has the bits of
+ * nkp_values_product_device (s, nrhs, d_dval, d_x, ldx, -1.0, 1, R, ld) on a copy of dB; then nkp_solve_batch_device (s, nrhs, R,
+ * d_dx, ld, berr, iters, relres) runs, so dX, iters, relres, berr and the return code are that call's: the tangent solve converges
+ * or fails like any solve.  d_db == NULL means dB = 0; d_dval == NULL means no dA term (d_x may then be NULL, no product is made);
+ * both NULL is NKP_EINVAL.  d_x: the nrhs solutions X (vector c at c * ldx), d_db and d_dx: vector c at c * ld; d_dx may be d_db.
+ * Row-distributed solvers: collective; the sequence above (its first agreement always, the exchange and the second agreement
+ * only with d_dval), then the batched solve's own collectives.  Every rank must pass d_dval NULL or non-NULL alike: the first
+ * agreement carries it, and a mismatch is NKP_EINVAL on every rank, naming a rank, before any exchange.
+ * nkp_get_int: "tangent_calls".  Errors as for nkp_values_product_device (NULL s, d_dx, or d_x with d_dval: refused before the
+ * handle is read). */
+int nkp_solve_tangent_device (nkp_solver *s, int nrhs, const void *d_dval, const void *d_x, int64_t ldx, const void *d_db, void *d_dx, int64_t ld,
+                              double *berr, int *iters, double *relres);
 
 /* hipSetDevice for host programs that do not link HIP themselves (call before nkp_comm_rccl_init). */
 int nkp_set_device (int device);

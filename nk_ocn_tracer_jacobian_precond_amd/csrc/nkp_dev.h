@@ -88,6 +88,10 @@ void build_rowblocks_host (int64_t n, const int *rowptr, int **rowblk_out, int *
 // nkp_value_gradient (valgrad.hip): g[e] (+)= alpha * sum_{c < nk} lam_c[row of e] * x_c[colind[e]] on the pattern of A, the sum taken
 // in ascending c, every product and sum rounded.  K in {1, 2, 4, 8}: interleave width of lam and x (1 = plain vectors), nk <= K
 void launch_value_gradient (int K, int nk, const CsrDev &A, const double *lam, const double *x, double alpha, int accumulate, double *g, hipStream_t st);
+// nkp_values_product (valprod.hip): y_c[i] (+)= alpha * sum_e val[e] * x_c[colind[e]] over the stored entries of row i in stored order, c < nk,
+// with the bits of the SpMV kernels on a matrix that stores val.  K in {1, 2, 4, 8}: interleave width of x (1 = a plain vector), nk <= K;
+// y is column-major, vector c at c * ldy.  Every row is written, also of a matrix without entries
+void launch_values_product (int K, int nk, const CsrDev &A, const double *val, const double *x, double alpha, int accumulate, double *y, int64_t ldy, hipStream_t st);
 
 // ---------------------------------------------------------------- water-column blocks
 // Banded LU (no pivoting) of every diagonal block, half-bandwidth P in {1,2,4}; SoA by

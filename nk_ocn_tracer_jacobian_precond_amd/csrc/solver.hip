@@ -47,6 +47,7 @@ void solver_free (nkp_solver *s)
             if (p) (void) hipFree (p);
       }
       valgrad_release (s);
+      valprod_release (s);
       if (s->hpin) (void) hipHostFree (s->hpin);
       if (s->own_stream && s->stream) (void) hipStreamDestroy (s->stream);
       s->shared->clones--;
@@ -56,6 +57,7 @@ void solver_free (nkp_solver *s)
    if (s->trans_of) trans_detach (s);
    if (s->trans) trans_release (s);      // before the stream it shares goes
    valgrad_release (s);
+   valprod_release (s);
    for (nkp_solver *c : s->batch_members) solver_free (c);
    s->batch_members.clear ();
    for (double *p : { s->bvin, s->bz, s->bw })
@@ -642,6 +644,9 @@ extern "C" int64_t nkp_get_int (nkp_solver *s, const char *key)
    if (!strcmp (key, "dist_allreduce_calls")) return s->shared->allreduce_calls.load ();
    if (!strcmp (key, "value_gradient_calls")) return s->vg.calls;
    if (!strcmp (key, "value_gradient_us")) return (int64_t) (s->vg.seconds * 1.0e6);
+   if (!strcmp (key, "values_product_calls")) return s->vp.calls;
+   if (!strcmp (key, "values_product_us")) return (int64_t) (s->vp.seconds * 1.0e6);
+   if (!strcmp (key, "tangent_calls")) return s->vp.tangent_calls;
    if (!strcmp (key, "batch_steps")) return s->batch_steps;
    if (!strcmp (key, "batch_width")) return s->batch_width;
    if (!strcmp (key, "batch_member_bytes")) {      // the further sets of work vectors a batched group keeps (not part of device_bytes)
@@ -1059,6 +1064,7 @@ static int clone_impl (nkp_solver *src, nkp_solver **out, bool member)
    s->trans_ship = nullptr;
    s->trans_send = s->trans_recv = nullptr;
    s->vg = decltype (s->vg) ();      // nkp_value_gradient's work space and counters are per handle
+   s->vp = decltype (s->vp) ();      // and nkp_values_product's
    s->A.tune = &s->tune;
    s->B.tune = &s->tune;
    s->ml.tune = &s->tune;
@@ -1623,6 +1629,10 @@ extern "C" int nkp_time_kernel (nkp_solver *s, int which, int arg, int reps, dou
       const int prc = valgrad_time_prepare (s, arg);
       if (prc) return prc;
    }
+   if (which == 6 || which == 7) {      // the product kernel of nkp_values_product at interleave width arg, likewise; 7: what it replaces
+      const int prc = valprod_time_prepare (s, arg, which);
+      if (prc) return prc;
+   }
    hipEvent_t e0, e1;
    HIPCHK (hipEventCreate (&e0));
    HIPCHK (hipEventCreate (&e1));
@@ -1648,6 +1658,8 @@ extern "C" int nkp_time_kernel (nkp_solver *s, int which, int arg, int reps, dou
          else if (which == 1) apply_precond_once (s, s->t1, s->t2);
          else if (which == 2) arnoldi_step_device (s, arg);
          else if (which == 5) valgrad_time_launch (s, arg);
+         else if (which == 6) valprod_time_launch (s, arg);
+         else if (which == 7) valprod_time_composition (s, arg);
          else if (s->opt.precond == NKP_PRECOND_MULTILEVEL) ml_time_piece (s->ml, which - 3, s->stream);   // 3: smoother residual rows, 4: column solves (level 0, colour 0)
       }
       HIPCHK (hipEventRecord (e1, s->stream));

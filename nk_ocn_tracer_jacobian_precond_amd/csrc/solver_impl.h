@@ -8,6 +8,7 @@
 #include "dist_plan.h"
 
 #include <atomic>
+#include <initializer_list>
 #include <memory>
 #include <string>
 #include <vector>
@@ -140,6 +141,14 @@ struct nkp_solver {
       int64_t calls = 0;
       double seconds = 0.0;        // wall time of the last call
    } vg;
+   // nkp_values_product / nkp_solve_tangent_device: the K-interleaved copy of x (single-GPU, nrhs >= 2), the device staging of the
+   // host flavour (val | x | y), the right-hand sides R = dB - dA X of a tangent solve -- like vg made at first use and kept
+   struct {
+      double *x = nullptr, *stage = nullptr, *r = nullptr;
+      size_t x_cap = 0, stage_cap = 0, r_cap = 0;
+      int64_t calls = 0, tangent_calls = 0;
+      double seconds = 0.0;        // wall time of the last product
+   } vp;
    double *h_dev () { return dscal; }
    double *h2_dev () { return dscal + (m + 2); }
    double *misc_dev () { return dscal + 2 * (m + 2); }     // [0]=nrm2 [1]=inv [2]=dot out ...
@@ -159,6 +168,57 @@ static int dev_alloc (nkp_solver *s, T **p, size_t count)
 }
 
 
+// ---- work space made at first use (nkp_value_gradient, nkp_values_product) -----------------------------------------------------
+struct Want {
+   double **p;
+   size_t *cap;        // doubles *p holds
+   size_t need;        // doubles this call needs
+};
+
+// Grow the buffers of `set` that are too small, all of them or none: the new ones are allocated first and take the place of
+// the old ones only when every allocation succeeded.  After a failure the solver holds exactly what it held before and HIP's
+// last error is cleared.
+inline int reserve (nkp_solver *s, std::initializer_list<Want> set, const char *who)
+{
+   double *fresh[8] = {};
+   int rc = NKP_OK;
+   size_t i = 0;
+   for (const Want &w : set) {
+      if (w.need > *w.cap) {
+         void *q = nullptr;
+         if (hipMalloc (&q, w.need * sizeof (double)) != hipSuccess) {
+            rc = fail (NKP_ENOMEM, "%s: hipMalloc of %zu bytes of work space failed", who, w.need * sizeof (double));
+            break;
+         }
+         fresh[i] = (double *) q;
+      }
+      i++;
+   }
+   if (rc) {
+      for (double *q : fresh)
+         if (q) (void) hipFree (q);
+      (void) hipGetLastError ();
+      return rc;
+   }
+   i = 0;
+   for (const Want &w : set) {
+      if (fresh[i]) {
+         if (*w.p) {
+            (void) hipFree (*w.p);
+            s->device_bytes -= *w.cap * sizeof (double);
+         }
+         *w.p = fresh[i];
+         *w.cap = w.need;
+         s->device_bytes += w.need * sizeof (double);
+      }
+      i++;
+   }
+   return NKP_OK;
+}
+
+// the interleave width that serves nrhs vectors
+inline int width_of (int nrhs) { return nrhs <= 1 ? 1 : nrhs <= 2 ? 2 : nrhs <= 4 ? 4 : 8; }
+
 // ---- defined in solver.hip -------------------------------------------------------------------------------------------------
 NKP_PRIVATE void solver_free (nkp_solver *s);
 NKP_PRIVATE void msg (const nkp_solver *s, int lvl, const char *fmt, ...);
@@ -175,6 +235,18 @@ NKP_PRIVATE void valgrad_release (nkp_solver *s);
 // nkp_time_kernel, which = 5: scratch operands for the gradient kernel at interleave width K (1, 2, 4, 8), then one launch
 NKP_PRIVATE int valgrad_time_prepare (nkp_solver *s, int K);
 NKP_PRIVATE void valgrad_time_launch (nkp_solver *s, int K);
+// The operand x of a K-wide kernel on the pattern (xp = the vectors, own rows; pointers beyond them NULL): single-GPU the vectors
+// themselves (K = 1) or their K-interleaved copy in `il` (n * K doubles); row-distributed [own | halo] rows in dist.xe (K = 1) or
+// dist.bxe (K >= 2, batch_prepare_exchange done), the halo rows of all vectors fetched in ONE alltoallv, which is always made and
+// counted.  *x_in = what the kernel reads.  NKP_ECOMM when the exchange failed (the stream is then still to be synchronised).
+NKP_PRIVATE int fetch_x_operand (nkp_solver *s, int K, const double *const *xp, double *il, const double **x_in, const char *who);
+// ---- defined in valprod_api.hip --------------------------------------------------------------------------------------------
+NKP_PRIVATE void valprod_release (nkp_solver *s);
+// nkp_time_kernel, which = 6: scratch operands for the product kernel at interleave width K (1, 2, 4, 8), then one launch;
+// which = 7: the composition of SpMV kernels it replaces (product into a temporary, de-interleave, update pass)
+NKP_PRIVATE int valprod_time_prepare (nkp_solver *s, int K, int which);
+NKP_PRIVATE void valprod_time_launch (nkp_solver *s, int K);
+NKP_PRIVATE void valprod_time_composition (nkp_solver *s, int K);
 // ---- defined in transpose.hip ----------------------------------------------------------------------------------------------
 // the owner frees its transposed solver and the value map; a transposed solver that is destroyed leaves its owner
 NKP_PRIVATE void trans_release (nkp_solver *s);

@@ -6,58 +6,7 @@
 
 #include <time.h>
 
-#include <initializer_list>
-
 namespace {
-
-struct Want {
-   double **p;
-   size_t *cap;        // doubles *p holds
-   size_t need;        // doubles this call needs
-};
-
-// Grow the buffers of `set` that are too small, all of them or none: the new ones are allocated first and take the place of
-// the old ones only when every allocation succeeded.  After a failure the solver holds exactly what it held before and HIP's
-// last error is cleared.
-int reserve (nkp_solver *s, std::initializer_list<Want> set, const char *who)
-{
-   double *fresh[8] = {};
-   int rc = NKP_OK;
-   size_t i = 0;
-   for (const Want &w : set) {
-      if (w.need > *w.cap) {
-         void *q = nullptr;
-         if (hipMalloc (&q, w.need * sizeof (double)) != hipSuccess) {
-            rc = fail (NKP_ENOMEM, "%s: hipMalloc of %zu bytes of work space failed", who, w.need * sizeof (double));
-            break;
-         }
-         fresh[i] = (double *) q;
-      }
-      i++;
-   }
-   if (rc) {
-      for (double *q : fresh)
-         if (q) (void) hipFree (q);
-      (void) hipGetLastError ();
-      return rc;
-   }
-   i = 0;
-   for (const Want &w : set) {
-      if (fresh[i]) {
-         if (*w.p) {
-            (void) hipFree (*w.p);
-            s->device_bytes -= *w.cap * sizeof (double);
-         }
-         *w.p = fresh[i];
-         *w.cap = w.need;
-         s->device_bytes += w.need * sizeof (double);
-      }
-      i++;
-   }
-   return NKP_OK;
-}
-
-inline int width_of (int nrhs) { return nrhs <= 1 ? 1 : nrhs <= 2 ? 2 : nrhs <= 4 ? 4 : 8; }
 
 // Host flavour: h_* given, d_* NULL; device flavour the other way round.  The entry points have refused NULL arguments on the
 // calling rank, before the solver is looked at and before any collective.
@@ -118,30 +67,7 @@ int value_gradient (nkp_solver *s, int nrhs, const double *h_lam, const double *
       launch_interleave (K, lp, W.lam, n, st);
       lam_in = W.lam;
    }
-   if (!dist) {
-      if (K >= 2) { launch_interleave (K, xp, W.x, n, st); x_in = W.x; }
-   } else {
-      int comm_rc;
-      s->shared->alltoallv_calls++;
-      if (K == 1) {
-         // as spmv_op fetches them: own rows copied, the rows the peers need packed, the halo behind the own rows
-         launch_copy (X, D.xe, n, st);
-         if (D.nsend) launch_gather (D.send_idx, X, D.sendbuf, D.nsend, st);
-         comm_rc = D.ops.alltoallv (D.ops.ctx, D.sendbuf, D.send_counts.data (), D.xe + n, D.recv_counts.data (), (void *) st);
-         x_in = D.xe;
-      } else {
-         // K-wide rows, the plan's counts times K (the buffers and counts of the batched solve)
-         D.send_counts_k.resize (D.send_counts.size ());
-         D.recv_counts_k.resize (D.recv_counts.size ());
-         for (size_t p = 0; p < D.send_counts.size (); p++) D.send_counts_k[p] = D.send_counts[p] * K;
-         for (size_t p = 0; p < D.recv_counts.size (); p++) D.recv_counts_k[p] = D.recv_counts[p] * K;
-         launch_interleave (K, xp, D.bxe, n, st);
-         if (D.nsend) launch_pack_rows_split (K, D.send_idx, xp, D.bsend, D.nsend, st);
-         comm_rc = D.ops.alltoallv (D.ops.ctx, D.bsend, D.send_counts_k.data (), D.bxe + (size_t) n * (size_t) K, D.recv_counts_k.data (), (void *) st);
-         x_in = D.bxe;
-      }
-      if (comm_rc) rc = fail (NKP_ECOMM, "%s: the exchange of the halo rows of x failed", who);
-   }
+   rc = fetch_x_operand (s, K, xp, W.x, &x_in, who);
    if (!rc) {
       launch_value_gradient (K, nrhs, s->A, lam_in, x_in, alpha, accumulate, G, st);
       hipError_t e = hipSuccess;
@@ -161,6 +87,39 @@ int value_gradient (nkp_solver *s, int nrhs, const double *h_lam, const double *
 }
 
 }   // namespace
+
+int fetch_x_operand (nkp_solver *s, int K, const double *const *xp, double *il, const double **x_in, const char *who)
+{
+   auto &D = s->dist;
+   const int64_t n = s->n;
+   hipStream_t st = s->stream;
+   if (!D.on) {
+      *x_in = xp[0];
+      if (K >= 2) { launch_interleave (K, xp, il, n, st); *x_in = il; }
+      return NKP_OK;
+   }
+   int comm_rc;
+   s->shared->alltoallv_calls++;
+   if (K == 1) {
+      // as spmv_op fetches them: own rows copied, the rows the peers need packed, the halo behind the own rows
+      launch_copy (xp[0], D.xe, n, st);
+      if (D.nsend) launch_gather (D.send_idx, xp[0], D.sendbuf, D.nsend, st);
+      comm_rc = D.ops.alltoallv (D.ops.ctx, D.sendbuf, D.send_counts.data (), D.xe + n, D.recv_counts.data (), (void *) st);
+      *x_in = D.xe;
+   } else {
+      // K-wide rows, the plan's counts times K (the buffers and counts of the batched solve)
+      D.send_counts_k.resize (D.send_counts.size ());
+      D.recv_counts_k.resize (D.recv_counts.size ());
+      for (size_t p = 0; p < D.send_counts.size (); p++) D.send_counts_k[p] = D.send_counts[p] * K;
+      for (size_t p = 0; p < D.recv_counts.size (); p++) D.recv_counts_k[p] = D.recv_counts[p] * K;
+      launch_interleave (K, xp, D.bxe, n, st);
+      if (D.nsend) launch_pack_rows_split (K, D.send_idx, xp, D.bsend, D.nsend, st);
+      comm_rc = D.ops.alltoallv (D.ops.ctx, D.bsend, D.send_counts_k.data (), D.bxe + (size_t) n * (size_t) K, D.recv_counts_k.data (), (void *) st);
+      *x_in = D.bxe;
+   }
+   if (comm_rc) return fail (NKP_ECOMM, "%s: the exchange of the halo rows of x failed", who);
+   return NKP_OK;
+}
 
 void valgrad_release (nkp_solver *s)
 {

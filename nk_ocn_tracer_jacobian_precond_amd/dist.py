@@ -393,7 +393,7 @@ class NkpDistSolver(_solver.NkpSolver):
             comm = self._comm
             raise _solver.NkpError(rc, self._lib.nkp_last_error().decode() + (" | comm: " + "; ".join(comm.errors) if comm.errors else ""))
 
-    def _check_collective(self, rc):           # value_gradient / value_gradient_device: collective here, local slices in and out
+    def _check_collective(self, rc):           # value_gradient*, values_product*: collective here, local slices in and out
         self._check_dist(rc)
 
     def solve_many(self, B, raise_on_fail=True):

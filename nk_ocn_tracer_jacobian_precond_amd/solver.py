@@ -32,6 +32,7 @@ ABI_SYMBOLS = [
     "nkp_dist_plan_copy", "nkp_dist_plan_free", "nkp_ml_level_array", "nkp_default_tuning", "nkp_solve_batch_device",
     "nkp_refactor", "nkp_refactor_device", "nkp_refactor_dist", "nkp_refactor_dist_device", "nkp_transpose", "nkp_transpose_dist",
     "nkp_value_gradient", "nkp_value_gradient_device",
+    "nkp_values_product", "nkp_values_product_device", "nkp_solve_tangent_device",
 ]
 
 _ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p)
@@ -128,6 +129,9 @@ def load_library(path=None):
     lib.nkp_transpose_dist.argtypes = [vp, C.POINTER(vp)]
     lib.nkp_value_gradient.argtypes = [vp, C.c_int, f64p, f64p, C.c_int64, C.c_double, C.c_int, f64p]
     lib.nkp_value_gradient_device.argtypes = [vp, C.c_int, vp, vp, C.c_int64, C.c_double, C.c_int, vp]
+    lib.nkp_values_product.argtypes = [vp, C.c_int, f64p, f64p, C.c_int64, C.c_double, C.c_int, f64p, C.c_int64]
+    lib.nkp_values_product_device.argtypes = [vp, C.c_int, vp, vp, C.c_int64, C.c_double, C.c_int, vp, C.c_int64]
+    lib.nkp_solve_tangent_device.argtypes = [vp, C.c_int, vp, vp, C.c_int64, vp, vp, C.c_int64, f64p, C.POINTER(C.c_int), f64p]
     lib.nkp_refactor.argtypes = [vp, f64p, C.c_int]
     lib.nkp_refactor_device.argtypes = [vp, vp, C.c_int]
     lib.nkp_refactor_dist.argtypes = [vp, f64p, C.c_int]
@@ -366,6 +370,65 @@ class NkpSolver:
         self._check_collective(self._lib.nkp_value_gradient_device(self._h, int(nrhs), C.c_void_p(d_lam), C.c_void_p(d_x), int(ld), float(alpha),
                                                                    int(bool(accumulate)), C.c_void_p(d_g)))
 
+    def values_product(self, val, X, alpha=1.0, Y=None):
+        """nkp_values_product: Y = alpha * (the solver's pattern with the values val) X, or Y += ... when Y is given.  val: nnz
+        values in the CSR order the solver was created with; X (and Y): shape (n,) or (K, n), K <= 8.  Returns Y (a new array
+        of X's shape).  Only the pattern is read.  Collective on a row-distributed solver (local values and rows)."""
+        val = np.ascontiguousarray(val, np.float64).reshape(-1)
+        x = np.ascontiguousarray(np.atleast_2d(np.asarray(X, np.float64)))
+        if val.size != self.nnz or x.ndim != 2 or x.shape[1] != self.n:
+            raise ValueError(f"val must hold {self.nnz} values and X have shape ({self.n},) or (K, {self.n})")
+        if Y is None:
+            y, acc = np.empty_like(x), 0
+        else:
+            y, acc = np.array(np.atleast_2d(np.asarray(Y, np.float64)), order="C", copy=True), 1
+            if y.shape != x.shape:
+                raise ValueError("Y must have the shape of X")
+        v = val if val.size else np.zeros(1)
+        self._check_collective(self._lib.nkp_values_product(self._h, x.shape[0], _p(v, C.c_double), _p(x, C.c_double), self.n, float(alpha), acc,
+                                                            _p(y, C.c_double), self.n))
+        return y.reshape(np.shape(X))
+
+    def values_product_device(self, d_val, d_x, nrhs, ldx, d_y, ldy, alpha=1.0, accumulate=False):
+        """nkp_values_product_device: d_val = integer device address of nnz float64, d_x / d_y of nrhs vectors of n float64 each
+        (vector c at + 8 * c * ldx / ldy); d_y is written (accumulate=False) or added to.  Runs on the solver's stream."""
+        self._check_collective(self._lib.nkp_values_product_device(self._h, int(nrhs), C.c_void_p(d_val), C.c_void_p(d_x), int(ldx), float(alpha),
+                                                                   int(bool(accumulate)), C.c_void_p(d_y), int(ldy)))
+
+    def solve_tangent_device(self, d_dval, d_x, ldx, d_db, d_dx, nrhs, ld, raise_on_fail=True):
+        """nkp_solve_tangent_device: dX = A^-1 (dB - dA X) on device buffers; d_dval (nnz values) or d_db may be None / 0 (no
+        dA term / dB = 0), d_x may be None without d_dval.  Returns one info dict per right-hand side, like solve_batch_device."""
+        berr, relres, iters = (C.c_double * nrhs)(), (C.c_double * nrhs)(), (C.c_int * nrhs)()
+        rc = self._lib.nkp_solve_tangent_device(self._h, int(nrhs), C.c_void_p(d_dval or None), C.c_void_p(d_x or None), int(ldx), C.c_void_p(d_db or None),
+                                                C.c_void_p(d_dx), int(ld), berr, iters, relres)
+        self._check(rc, (0,) if raise_on_fail else (0, 1, 2, 3))
+        return [dict(status=rc, iters=iters[c], relres=relres[c], berr=berr[c]) for c in range(nrhs)]
+
+    def solve_tangent(self, X, dval=None, dB=None, raise_on_fail=True):
+        """The tangent of X = A^-1 B from host arrays: dX = A^-1 (dB - dA X), dA = dval on the solver's pattern.  X, dB: shape (n,)
+        or (K, n), K <= 8; dval: nnz values.  The arrays are staged on the device through the HIP runtime the library links.
+        Returns (dX, infos)."""
+        if dval is None and dB is None:
+            raise ValueError("solve_tangent needs dval or dB")
+        x = np.ascontiguousarray(np.atleast_2d(np.asarray(X, np.float64)))
+        K, n = x.shape
+        if n != self.n:
+            raise ValueError(f"X must have shape ({self.n},) or (K, {self.n})")
+        bufs = []
+        try:
+            d_x = _device_array(bufs, x) if dval is not None else None
+            d_v = _device_array(bufs, np.ascontiguousarray(dval, np.float64).reshape(-1), self.nnz) if dval is not None else None
+            d_b = _device_array(bufs, np.ascontiguousarray(np.atleast_2d(np.asarray(dB, np.float64))), K * n) if dB is not None else None
+            out = np.empty((K, n))
+            d_o = _device_array(bufs, out)
+            infos = self.solve_tangent_device(d_v, d_x, n, d_b, d_o, K, n, raise_on_fail)
+            if out.nbytes:
+                _hip_check(_hip().hipMemcpy(C.c_void_p(out.ctypes.data), C.c_void_p(d_o), C.c_size_t(out.nbytes), 2))
+        finally:
+            for q in bufs:
+                _hip().hipFree(C.c_void_p(q))
+        return out.reshape(np.shape(X)), infos
+
     def _check_collective(self, rc):
         self._check(rc)
 
@@ -464,6 +527,34 @@ class NkpSolver:
 
     def __exit__(self, *a):
         self.close()
+
+
+_HIP = None
+
+
+def _hip():
+    """the HIP runtime the library links (no second runtime in the process)"""
+    global _HIP
+    if _HIP is None:
+        _HIP = C.CDLL("libamdhip64.so")
+    return _HIP
+
+
+def _hip_check(code):
+    if code != 0:
+        raise RuntimeError(f"HIP runtime call failed with code {code}")
+
+
+def _device_array(keep, a, size=None):
+    """a float64 host array copied to a device buffer; its address is appended to `keep` for the caller to free"""
+    if size is not None and a.size != size:
+        raise ValueError(f"array has {a.size} entries, expected {size}")
+    p = C.c_void_p()
+    _hip_check(_hip().hipMalloc(C.byref(p), C.c_size_t(max(a.nbytes, 8))))
+    keep.append(p.value)
+    if a.nbytes:
+        _hip_check(_hip().hipMemcpy(p, C.c_void_p(a.ctypes.data), C.c_size_t(a.nbytes), 1))
+    return p.value
 
 
 def device_count():

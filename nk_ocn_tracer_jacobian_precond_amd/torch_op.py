@@ -4,8 +4,12 @@ The backward pass through a solve is a solve with A^T: with G = dL/dX,
 
     Lambda = A^-T G,      dL/dB = Lambda,      dL/dval[e] = - sum_c Lambda[c, row of e] * X[c, colind[e]]
 
-(nkp_transpose for the first, nkp_value_gradient for the last; include/nkp.h).  torch is imported when NkpTorchSolver is
-constructed, not when this module is: the package stays importable without it.
+(nkp_transpose for the first, nkp_value_gradient for the last; include/nkp.h).  The forward mode (torch.autograd.forward_ad dual
+tensors) is the tangent solve nkp_solve_tangent_device: with the tangents dB and dval,
+
+    dX = A^-1 (dB - dA X),      dA = dval on the pattern of A
+
+torch is imported when NkpTorchSolver is constructed, not when this module is: the package stays importable without it.
 """
 from __future__ import annotations
 
@@ -27,7 +31,9 @@ class NkpTorchSolver:
     extra synchronisation is needed.  Use the wrapper under the stream it was constructed under.
 
     The backward pass calls transposed() once -- the handle is kept by the solver and follows set_values -- and runs one
-    batched solve there.  A forward or backward solve that does not converge raises NkpError: no partial gradient is returned.
+    batched solve there.  Forward mode runs one product with dval on the pattern (only when val carries a tangent) and one batched
+    solve on the solver itself.  A forward, backward or tangent solve that does not converge raises NkpError: no partial
+    gradient or tangent is returned.  Double backward is not supported.
     """
 
     def __init__(self, solver):
@@ -69,7 +75,24 @@ def _make_function(torch):
             s.solve_batch_device(B.data_ptr(), X.data_ptr(), B.shape[0], s.n)      # raises NkpError unless every column converged
             ctx.owner = owner
             ctx.save_for_backward(X)
+            ctx.save_for_forward(X)
+            # an input without a tangent reaches jvp as None, not as zeros: a dual on B alone makes no product with the values
+            # (backward has one output and runs only with a gradient for it, so it never sees None)
+            ctx.set_materialize_grads(False)
             return X
+
+        @staticmethod
+        def jvp(ctx, dB, dval, _):
+            if dB is None and dval is None:
+                return None
+            s = ctx.owner.solver
+            (X,) = ctx.saved_tensors
+            dB = None if dB is None else dB.contiguous()
+            dval = None if dval is None else dval.contiguous()
+            dX = torch.empty_like(X)
+            s.solve_tangent_device(None if dval is None else dval.data_ptr(), X.data_ptr(), s.n, None if dB is None else dB.data_ptr(), dX.data_ptr(),
+                                   X.shape[0], s.n)                 # raises NkpError unless every column converged
+            return dX
 
         @staticmethod
         @torch.autograd.function.once_differentiable
