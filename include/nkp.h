@@ -668,7 +668,10 @@ int nkp_dist_plan_host (int64_t m_loc, int64_t nnz_loc, const int32_t *rowptr_lo
  * LDS of the lane kernels, in doubles)), "dg_ptr" (int32, columns + 1) / "dg_key" (int32) / "dg_voff" (int64, columns) / "dg_val"
  * (float): the per-column diagonals of tuning ml_diag, empty when the level runs on CSR -- column c of blk_start, of len rows, has
  * the keys dg_key[dg_ptr[c] .. dg_ptr[c + 1]), ascending, and its row kl has the entry dg_val[dg_voff[c] + s * len + kl] in column
- * key_s + kl, 0 where it has none.  All in the level's colour-major row order. */
+ * key_s + kl, 0 where it has none; "dg_gptr" (int32, columns + 1) / "dg_grp" (int32 pairs): the groups of consecutive keys the
+ * residual kernel loads x for once -- column c has the groups dg_gptr[c] .. dg_gptr[c + 1], in slot order, group g with the first
+ * key dg_grp[2 g] and dg_grp[2 g + 1] = s0 | m << 16, its first slot in the column and its keys (m <= 5 and m <= 64 - rows + 1,
+ * rows = ceil (len / ceil (len / 64)), the column's tallest tile).  All in the level's colour-major row order. */
 int64_t nkp_ml_level_array (nkp_solver *s, int level, const char *what, void *dst, int64_t capacity_bytes);
 
 /* Host-only planning step of the multilevel preconditioner inside nkp_create, exposed so the aggregation logic can

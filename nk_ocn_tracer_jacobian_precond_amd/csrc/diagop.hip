@@ -17,7 +17,8 @@
 #define DG_THREADS 256
 #define DG_WAVES (DG_THREADS / NKP_WAVE)
 #define DG_RPL 4                 // rows per lane of the key kernel: columns of up to 256 rows
-#define DG_UNROLL 8              // slots whose loads are in flight together (and the zeros behind dg_key)
+#define DG_UNROLL 8              // the zeros behind dg_key
+#define DG_GROUPS 3              // groups whose loads are in flight together
 
 // ---------------------------------------------------------------- setup: the keys of every column
 // One wave per column, lane l walks rows l, l + 64, ..: every round takes the smallest key any row still has to offer (rows
@@ -95,32 +96,70 @@ void diag_fill_kernel (int ntile, const DgTile *__restrict__ tile, const int *__
 
 // ---------------------------------------------------------------- y_rows = b_rows - (L x)_rows
 // One wave per tile, lane l < rows owns row row0 + l (the lanes behind the tile's end repeat its last row and store nothing,
-// so every load stays inside the arrays).  The tile and the keys are wave-uniform: scalar loads.  Per slot one contiguous
-// f32 load of the diagonal and one contiguous load of x at key + kl, clamped into [0, n) -- out of range only where the
-// value is a padded zero.  f64 product and sum, each rounded, in slot order.
+// so every load stays inside the arrays).  The tile and the groups are wave-uniform: scalar loads.  Per slot one contiguous
+// f32 load of the diagonal; f64 product and sum, each rounded, in slot order.
 //
-// dg_slots: M slots from slot s on, all 2 M loads requested before the first is consumed.  The kernel takes a column's nk
-// slots DG_UNROLL at a time and the nk % DG_UNROLL behind them in one step of exactly that length: the launch is bound by
-// the vector loads it issues, not by their bytes, and a last step filled up to DG_UNROLL with repeated loads cost 9.5 % more
-// of them on the 1 degree levels (keys per column 13 .. 17, mean 14.8: two steps, 16 slots).
-template <int M>
-__device__ __forceinline__ void dg_slots (const int *__restrict__ key, const float *__restrict__ val, const double *__restrict__ x, int s, int len, int kl,
-                                          int n, double &acc)
+// Groups: the keys of a neighbour column's rows at depth -1, 0, +1 are consecutive, and for the key behind one a lane would
+// load the x its upper neighbour lane loaded for the key before.  So x is loaded once per group of consecutive keys (DgGroup,
+// nkp_dev.h), by all 64 lanes with their true lane number: lane i holds x[key0 + kl0 + i], clamped into [0, n) -- out of
+// range only where every value that meets it is a padded zero --, and row l takes the x of the group's d-th key from lane
+// l + d <= 63 (the groups are cut to fit).  dg_lane_up moves the window one lane down per key: no LDS, no further load.  The
+// launch is bound by the vector loads it issues, not by their bytes (a last step filled up with repeated loads cost 9.5 %
+// more of them and 5 % of the launch): the 1 degree levels have 14.8 keys in 5.3 groups per column, 29.5 loads per lane
+// with one x load per key and 20 with one per group.
+//
+// dg_step: G groups, their G + (keys of the groups) loads requested before the first is consumed.  Both halves are straight
+// lines with wave-uniform exits: the loads (dg_vals) and the sums (dg_sums) of a group of m keys are the first m stages of
+// the text for DG_RUN_MAX keys.  The kernel takes a column's groups DG_GROUPS at a time and the rest in one step of exactly
+// that length.
+__device__ __forceinline__ double dg_lane_up (double w)
 {
-   float v[M];
-   double xv[M];
+   // v_mov_b32_dpp wave_shl:1 -- lane i takes lane i + 1's, lane 63 keeps its own (bound_ctrl off); __shfl_down (w, 1), two
+   // ds_bpermute_b32, measured no faster
+   int lo = __double2loint (w), hi = __double2hiint (w);
+   lo = __builtin_amdgcn_update_dpp (lo, lo, 0x130, 0xf, 0xf, false);
+   hi = __builtin_amdgcn_update_dpp (hi, hi, 0x130, 0xf, 0xf, false);
+   return __hiloint2double (hi, lo);
+}
+
+template <int U>
+__device__ __forceinline__ void dg_vals (const float *__restrict__ p, int len, int m, float (&v)[DG_RUN_MAX])
+{
+   v[U] = p[(size_t) U * len];
+   if constexpr (U + 1 < DG_RUN_MAX)
+      if (m > U + 1) dg_vals<U + 1> (p, len, m, v);
+}
+
+template <int U>
+__device__ __forceinline__ void dg_sums (const float (&v)[DG_RUN_MAX], int m, double w, double &acc)
+{
+   acc += (double) v[U] * w;
+   if constexpr (U + 1 < DG_RUN_MAX)
+      if (m > U + 1) dg_sums<U + 1> (v, m, dg_lane_up (w), acc);
+}
+
+template <int G>
+__device__ __forceinline__ void dg_step (const DgGroup *__restrict__ grp, const float *__restrict__ val, const double *__restrict__ x, int len, int kl,
+                                         int base, int n, double &acc)
+{
+   float v[G][DG_RUN_MAX];
+   double w[G];
+   int m[G];
+   DgGroup R[G];
 #pragma unroll
-   for (int u = 0; u < M; u++) {
-      const int j = min (max (key[s + u] + kl, 0), n - 1);
-      v[u] = (val + (size_t) (s + u) * len)[kl];
-      xv[u] = x[j];
+   for (int g = 0; g < G; g++) R[g] = grp[g];
+#pragma unroll
+   for (int g = 0; g < G; g++) {
+      m[g] = R[g].slots >> 16;
+      w[g] = x[min (max (R[g].key0 + base, 0), n - 1)];
+      dg_vals<0> (val + (size_t) (R[g].slots & 0xffff) * len + kl, len, m[g], v[g]);
    }
 #pragma unroll
-   for (int u = 0; u < M; u++) acc += (double) v[u] * xv[u];
+   for (int g = 0; g < G; g++) dg_sums<0> (v[g], m[g], w[g], acc);
 }
 
 __global__ __launch_bounds__ (DG_THREADS)
-void diag_residual_kernel (const DgTile *__restrict__ tile, int ntile, const int *__restrict__ dg_key, const float *__restrict__ dg_val,
+void diag_residual_kernel (const DgTile *__restrict__ tile, int ntile, const DgGroup *__restrict__ dg_grp, const float *__restrict__ dg_val,
                            const double *__restrict__ x, const double *__restrict__ b, double *__restrict__ y, int n)
 {
    const int t = __builtin_amdgcn_readfirstlane (blockIdx.x * DG_WAVES + (threadIdx.x >> 6));
@@ -129,21 +168,17 @@ void diag_residual_kernel (const DgTile *__restrict__ tile, int ntile, const int
    const int lane = threadIdx.x & (NKP_WAVE - 1);
    const int lr = min (lane, T.rows - 1);
    const int kl = T.kl0 + lr;
+   const int base = T.kl0 + lane;
    const double bv = b[T.row0 + lr];
-   const int *__restrict__ key = dg_key + T.k0;
+   const DgGroup *__restrict__ grp = dg_grp + T.g0;
    const float *__restrict__ val = dg_val + T.voff;
    double acc = 0.0;
-   int s = 0;
-   for (; s + DG_UNROLL <= T.nk; s += DG_UNROLL) dg_slots<DG_UNROLL> (key, val, x, s, T.len, kl, n, acc);
-   static_assert (DG_UNROLL == 8, "one case per length of the last step");
-   switch (T.nk - s) {
-      case 1: dg_slots<1> (key, val, x, s, T.len, kl, n, acc); break;
-      case 2: dg_slots<2> (key, val, x, s, T.len, kl, n, acc); break;
-      case 3: dg_slots<3> (key, val, x, s, T.len, kl, n, acc); break;
-      case 4: dg_slots<4> (key, val, x, s, T.len, kl, n, acc); break;
-      case 5: dg_slots<5> (key, val, x, s, T.len, kl, n, acc); break;
-      case 6: dg_slots<6> (key, val, x, s, T.len, kl, n, acc); break;
-      case 7: dg_slots<7> (key, val, x, s, T.len, kl, n, acc); break;
+   int g = 0;
+   for (; g + DG_GROUPS <= T.ng; g += DG_GROUPS) dg_step<DG_GROUPS> (grp + g, val, x, T.len, kl, base, n, acc);
+   static_assert (DG_GROUPS == 3, "one case per length of the last step");
+   switch (T.ng - g) {
+      case 1: dg_step<1> (grp + g, val, x, T.len, kl, base, n, acc); break;
+      case 2: dg_step<2> (grp + g, val, x, T.len, kl, base, n, acc); break;
       default: break;
    }
    if (lane < T.rows) y[T.row0 + lane] = bv - acc;
@@ -152,12 +187,31 @@ void diag_residual_kernel (const DgTile *__restrict__ tile, int ntile, const int
 // ---------------------------------------------------------------- host side
 static void diag_drop (CsrDev &L, size_t *device_bytes, size_t held)
 {
-   for (void **p : { (void **) &L.dg_ptr, (void **) &L.dg_key, (void **) &L.dg_voff, (void **) &L.dg_val, (void **) &L.dg_tile })
+   for (void **p : { (void **) &L.dg_ptr, (void **) &L.dg_key, (void **) &L.dg_voff, (void **) &L.dg_val, (void **) &L.dg_tile, (void **) &L.dg_gptr, (void **) &L.dg_grp })
       if (*p) { (void) hipFree (*p); *p = nullptr; }
-   L.dg_ntile = L.dg_ncol = L.dg_nkey = 0;
+   L.dg_ntile = L.dg_ncol = L.dg_nkey = L.dg_ngrp = 0;
    L.dg_nval = 0;
    *device_bytes -= held;
    (void) hipGetLastError ();      // an out-of-memory error is answered here: the level stays on CSR
+}
+
+// tiles of a column of len rows: ceil (len / 64) of equal heights (the first len % tiles one row taller)
+static inline int dg_col_tiles (int len) { return (len + NKP_WAVE - 1) / NKP_WAVE; }
+
+// The groups of a column with the ascending keys key[0 .. nk), whose tallest tile has rows rows: maximal runs of consecutive
+// keys, cut to at most DG_RUN_MAX and at most 64 - rows + 1 keys.
+static void dg_groups (const int *key, int nk, int rows, std::vector<DgGroup> &out)
+{
+   const int fit = NKP_WAVE - rows + 1, lim = fit < DG_RUN_MAX ? fit : DG_RUN_MAX;
+   for (int s = 0; s < nk;) {
+      int m = 1;
+      while (s + m < nk && m < lim && key[s + m] == key[s + m - 1] + 1) m++;
+      DgGroup R;
+      R.key0 = key[s];
+      R.slots = s | m << 16;
+      out.push_back (R);
+      s += m;
+   }
 }
 
 int diag_build (CsrDev &L, const int *h_blk_start, const int *d_blk_start, int ncol, int ncol0, int max_len, int cap, int color_tile[3],
@@ -178,27 +232,16 @@ int diag_build (CsrDev &L, const int *h_blk_start, const int *d_blk_start, int n
    }
    std::vector<int> ptr ((size_t) ncol + 1, 0);
    std::vector<long long> voff ((size_t) ncol);
-   std::vector<DgTile> tiles;
-   tiles.reserve ((size_t) ncol);
-   long long nval = 0;
+   long long nval = 0, ntile = 0;
    for (int c = 0; c < ncol; c++) {
-      if (cnt[c] > cap) { color_tile[1] = 0; return 0; }
+      if (cnt[c] > cap) return 0;
       const int len = h_blk_start[c + 1] - h_blk_start[c];
-      if (c == ncol0) color_tile[1] = (int) tiles.size ();
       ptr[c + 1] = ptr[c] + cnt[c];
       voff[c] = nval;
       nval += (long long) cnt[c] * len;
-      for (int kl0 = 0; kl0 < len; kl0 += NKP_WAVE) {
-         DgTile T;
-         T.row0 = h_blk_start[c] + kl0;
-         T.rows = len - kl0 < NKP_WAVE ? len - kl0 : NKP_WAVE;
-         T.kl0 = kl0; T.len = len; T.k0 = ptr[c]; T.nk = cnt[c]; T.voff = voff[c];
-         tiles.push_back (T);
-      }
+      ntile += dg_col_tiles (len);
    }
-   if (ncol0 >= ncol) color_tile[1] = (int) tiles.size ();
-   color_tile[2] = (int) tiles.size ();
-   if (2 * nval > 3 * (long long) L.nnz || tiles.empty ()) { color_tile[0] = color_tile[1] = color_tile[2] = 0; return 0; }
+   if (2 * nval > 3 * (long long) L.nnz || ntile == 0 || ntile > INT_MAX) return 0;
    size_t held = 0;
    auto put = [&] (void **dst, const void *src, size_t bytes) {
       void *q = nullptr;
@@ -208,30 +251,55 @@ int diag_build (CsrDev &L, const int *h_blk_start, const int *d_blk_start, int n
       *device_bytes += bytes ? bytes : 1;
       return !src || !bytes || hipMemcpyAsync (q, src, bytes, hipMemcpyHostToDevice, st) == hipSuccess;
    };
-   const bool ok = put ((void **) &L.dg_ptr, ptr.data (), ptr.size () * sizeof (int)) && put ((void **) &L.dg_key, nullptr, ((size_t) ptr[ncol] + DG_UNROLL) * sizeof (int)) &&
-                   put ((void **) &L.dg_voff, voff.data (), voff.size () * sizeof (long long)) && put ((void **) &L.dg_val, nullptr, (size_t) nval * sizeof (float)) &&
-                   put ((void **) &L.dg_tile, tiles.data (), tiles.size () * sizeof (DgTile));
-   if (!ok) {
+   auto give_up = [&] () {
       (void) hipStreamSynchronize (st);
       diag_drop (L, device_bytes, held);
       color_tile[0] = color_tile[1] = color_tile[2] = 0;
       return 0;
-   }
-   L.dg_ntile = (int) tiles.size ();
-   L.dg_ncol = ncol;
-   L.dg_nkey = ptr[ncol];
-   L.dg_nval = nval;
+   };
+   if (!(put ((void **) &L.dg_ptr, ptr.data (), ptr.size () * sizeof (int)) && put ((void **) &L.dg_key, nullptr, ((size_t) ptr[ncol] + DG_UNROLL) * sizeof (int)) &&
+         put ((void **) &L.dg_voff, voff.data (), voff.size () * sizeof (long long)) && put ((void **) &L.dg_val, nullptr, (size_t) nval * sizeof (float))))
+      return give_up ();
    (void) hipMemsetAsync (L.dg_key + ptr[ncol], 0, DG_UNROLL * sizeof (int), st);
    const int64_t slots = (int64_t) ncol * cap;
    hipLaunchKernelGGL (diag_compact_kernel, dim3 ((unsigned) ((slots + DG_THREADS - 1) / DG_THREADS)), dim3 (DG_THREADS), 0, st, ncol, cap, (const int *) tmpkey.p,
                        (const int *) L.dg_ptr, L.dg_key);
+   // the groups and the tiles want the keys on the host
+   std::vector<int> key ((size_t) ptr[ncol]);
+   if (hipMemcpyAsync (key.data (), L.dg_key, key.size () * sizeof (int), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize (st) != hipSuccess)
+      return give_up ();
+   std::vector<int> gptr ((size_t) ncol + 1, 0);
+   std::vector<DgGroup> grp;
+   std::vector<DgTile> tiles;
+   grp.reserve (key.size ());
+   tiles.reserve ((size_t) ntile);
+   for (int c = 0; c < ncol; c++) {
+      const int len = h_blk_start[c + 1] - h_blk_start[c], nt = dg_col_tiles (len);
+      if (c == ncol0) color_tile[1] = (int) tiles.size ();
+      if (nt) dg_groups (key.data () + ptr[c], cnt[c], (len + nt - 1) / nt, grp);
+      gptr[c + 1] = (int) grp.size ();
+      for (int t = 0, kl0 = 0; t < nt; t++) {
+         DgTile T;
+         T.rows = len / nt + (t < len % nt ? 1 : 0);
+         T.row0 = h_blk_start[c] + kl0;
+         T.kl0 = kl0; T.len = len; T.k0 = ptr[c]; T.nk = cnt[c]; T.g0 = gptr[c]; T.ng = gptr[c + 1] - gptr[c]; T.voff = voff[c];
+         tiles.push_back (T);
+         kl0 += T.rows;
+      }
+   }
+   if (ncol0 >= ncol) color_tile[1] = (int) tiles.size ();
+   color_tile[2] = (int) tiles.size ();
+   if (!(put ((void **) &L.dg_gptr, gptr.data (), gptr.size () * sizeof (int)) && put ((void **) &L.dg_grp, grp.data (), grp.size () * sizeof (DgGroup)) &&
+         put ((void **) &L.dg_tile, tiles.data (), tiles.size () * sizeof (DgTile))))
+      return give_up ();
+   L.dg_ntile = (int) tiles.size ();
+   L.dg_ncol = ncol;
+   L.dg_nkey = ptr[ncol];
+   L.dg_ngrp = (int) grp.size ();
+   L.dg_nval = nval;
    launch_diag_fill (L, st);
    // the host arrays and the scratch buffers go when this returns
-   if (hipStreamSynchronize (st) != hipSuccess) {
-      diag_drop (L, device_bytes, held);
-      color_tile[0] = color_tile[1] = color_tile[2] = 0;
-      return 0;
-   }
+   if (hipStreamSynchronize (st) != hipSuccess) return give_up ();
    return 1;
 }
 
@@ -247,5 +315,5 @@ void launch_diag_residual (const CsrDev &L, int tile0, int tile1, const double *
    const int cnt = tile1 - tile0;
    if (cnt <= 0) return;
    hipLaunchKernelGGL (diag_residual_kernel, dim3 ((cnt + DG_WAVES - 1) / DG_WAVES), dim3 (DG_THREADS), 0, st, (const DgTile *) L.dg_tile + tile0, cnt,
-                       (const int *) L.dg_key, (const float *) L.dg_val, x, b, y, (int) L.n);
+                       (const DgGroup *) L.dg_grp, (const float *) L.dg_val, x, b, y, (int) L.n);
 }

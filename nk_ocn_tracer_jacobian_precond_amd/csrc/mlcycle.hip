@@ -249,7 +249,7 @@ void ml_time_piece (MlHierarchy &H, int which, hipStream_t st)
 
 // compulsory HBM bytes (every array element counted once per kernel that must touch it):
 //  which 0: residual rows of level 0, colour 0: its entries (value + column), row pointers, b in, r out, x once; with the
-//           per-column diagonals its padded slots (value only), keys and tiles instead of entries and row pointers
+//           per-column diagonals its padded slots (value only), groups of keys and tiles instead of entries and row pointers
 //  which 1: column solves of level 0, colour 0: factors, r in, x in and out
 //  which 2: one whole V(nu, nu) cycle
 int64_t ml_bytes (const MlHierarchy &H, int which)
@@ -259,9 +259,9 @@ int64_t ml_bytes (const MlHierarchy &H, int which)
       const int64_t rows = colour == 0 ? V.rows0 : V.n - V.rows0;
       const int64_t vb = V.L.valf ? 4 : 8, fb = V.B.fac_tf ? 4 : 8;
       if (what == 0 && V.L.dg_val) {
-         // the colour's share of the slots, keys and tiles by its share of the rows (as below)
+         // the colour's share of the slots, groups and tiles by its share of the rows (as below)
          const double share = V.n ? (double) rows / (double) V.n : 0.0;
-         return (int64_t) (share * ((double) V.L.dg_nval * 4.0 + (double) V.L.dg_ntile * (double) sizeof (DgTile))) + rows * (8 + 8) + V.n * 8;
+         return (int64_t) (share * ((double) V.L.dg_nval * 4.0 + (double) V.L.dg_ntile * (double) sizeof (DgTile) + (double) V.L.dg_ngrp * (double) sizeof (DgGroup))) + rows * (8 + 8) + V.n * 8;
       }
       if (what == 0) {
          // entries of the colour's rows: the colour-major CSR keeps them contiguous; split nnz by rows as an estimate is not
@@ -280,7 +280,7 @@ int64_t ml_bytes (const MlHierarchy &H, int which)
          total += (int64_t) (2 * nu) * level_piece (V, c, 1);                       // column solves: nu pre + nu post sweeps
          total += (int64_t) (2 * nu - (c == 0 ? 1 : 0)) * level_piece (V, c, 0);    // residual rows (the first half sweep needs none)
       }
-      if (V.L.dg_val) total += V.L.dg_nval * 4 + (int64_t) V.L.dg_ntile * (int64_t) sizeof (DgTile) + V.n * (8 + 8 + 8);
+      if (V.L.dg_val) total += V.L.dg_nval * 4 + (int64_t) V.L.dg_ntile * (int64_t) sizeof (DgTile) + (int64_t) V.L.dg_ngrp * (int64_t) sizeof (DgGroup) + V.n * (8 + 8 + 8);
       else total += V.L.nnz * ((V.L.valf ? 4 : 8) + 4) + V.n * (4 + 8 + 8 + 8);    // full residual before the restriction
       total += V.n * (8 + 4) + V.nc * (8 + 4);                                      // restriction
       total += V.n * (8 + 8 + 4) + V.nc * 8;                                        // prolongation

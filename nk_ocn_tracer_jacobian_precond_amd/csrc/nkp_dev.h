@@ -17,13 +17,20 @@
 #define NKP_SPMV_MAX_ROWS 256    // ... and rows (= threads of the SpMV workgroup) at most
 
 // ---------------------------------------------------------------- CSR matrix on the device
-// per-column diagonals (below): what one wave of the diagonal kernels needs of its tile, in one aligned 32-byte load
-struct alignas (32) DgTile {
+// per-column diagonals (below): what one wave of the diagonal kernels needs of its tile, in aligned scalar loads (48 bytes)
+struct alignas (16) DgTile {
    int row0, rows;                    // first row of the tile, its rows (<= 64)
    int kl0, len;                      // position of row0 inside its column, rows of the column
    int k0, nk;                        // the column's keys: dg_key[k0 .. k0 + nk)
+   int g0, ng;                        // the column's groups of consecutive keys: dg_grp[g0 .. g0 + ng)
    long long voff;                    // the column's value block: dg_val[voff + s * len + kl]
 };
+// a run of m consecutive keys key0, key0 + 1, .. of a column, slots s0 .. s0 + m - 1 of it: one 64-lane window of x serves them
+struct DgGroup {
+   int key0;
+   int slots;                         // s0 | m << 16
+};
+#define DG_RUN_MAX 5             // keys of a group at most
 
 struct CsrDev {
    int64_t n = 0, nnz = 0;
@@ -51,8 +58,13 @@ struct CsrDev {
    int *dg_key = nullptr;             // [dg_nkey = dg_ptr[ncol]] (+ 8 zeros behind them, which no kernel reads)
    long long *dg_voff = nullptr;      // [ncol]
    float *dg_val = nullptr;           // [dg_nval]
-   DgTile *dg_tile = nullptr;         // [dg_ntile] one per (column, 64 rows of it), in row order
-   int dg_ntile = 0, dg_ncol = 0, dg_nkey = 0;
+   DgTile *dg_tile = nullptr;         // [dg_ntile] ceil (len / 64) per column, of equal heights (67 rows: 34 + 33), in row order
+   // groups (pattern only, built once): column c cuts its keys into maximal runs of consecutive keys of at most DG_RUN_MAX and
+   // at most 64 - rows + 1 keys (rows: of the column's tallest tile), so that row l of a tile finds x for the group's d-th key
+   // in lane l + d <= 63 of one contiguous load of x.  A tile of 64 rows has groups of one key.
+   int *dg_gptr = nullptr;            // [ncol+1]
+   DgGroup *dg_grp = nullptr;         // [dg_ngrp = dg_gptr[ncol]]
+   int dg_ntile = 0, dg_ncol = 0, dg_nkey = 0, dg_ngrp = 0;
    int64_t dg_nval = 0;
    const nkp_tuning *tune = nullptr;  // launch shape knobs of the owning solver (NULL: built-in defaults)
 };

@@ -528,6 +528,8 @@ extern "C" int64_t nkp_ml_level_array (nkp_solver *s, int level, const char *wha
    else if (!strcmp (what, "dg_key")) { src = V.L.dg_key; count = src ? (int64_t) V.L.dg_nkey : 0; }
    else if (!strcmp (what, "dg_voff")) { src = V.L.dg_voff; count = src ? V.L.dg_ncol : 0; elem = 8; }
    else if (!strcmp (what, "dg_val")) { src = V.L.dg_val; count = src ? V.L.dg_nval : 0; }
+   else if (!strcmp (what, "dg_gptr")) { src = V.L.dg_gptr; count = src ? V.L.dg_ncol + 1 : 0; }
+   else if (!strcmp (what, "dg_grp")) { src = V.L.dg_grp; count = src ? 2 * (int64_t) V.L.dg_ngrp : 0; }
    else if (!strcmp (what, "cmap")) { src = V.cmap; count = V.cmap ? V.n : 0; }
    else if (!strcmp (what, "rptr")) { src = V.rptr; count = V.rptr ? V.nc + 1 : 0; }
    else if (!strcmp (what, "ridx")) { src = V.ridx; count = V.ridx ? V.n : 0; }

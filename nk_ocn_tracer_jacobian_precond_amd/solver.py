@@ -464,7 +464,8 @@ class NkpSolver:
         return int(self._lib.nkp_get_int(self._h, key.encode()))
 
     _ML_ARRAY_TYPES = {"valf": np.float32, "val": np.float64, "fac": np.float64, "coarse_inv": np.float64, "color_blk": np.int32,
-                       "col_kernel": np.int32, "dg_ptr": np.int32, "dg_key": np.int32, "dg_voff": np.int64, "dg_val": np.float32}
+                       "col_kernel": np.int32, "dg_ptr": np.int32, "dg_key": np.int32, "dg_voff": np.int64, "dg_val": np.float32,
+                       "dg_gptr": np.int32, "dg_grp": np.int32}
 
     def ml_level_array(self, level, what):
         """One array of the multilevel hierarchy as it sits on the device (nkp_ml_level_array); empty if the level has none."""
