@@ -146,6 +146,16 @@ typedef struct nkp_tuning {
                                 two-kernel half sweeps and the residual before the restriction then read instead of CSR (no per-entry
                                 column index; same bits).  N > 0 = a level gets them if no water column needs more than N diagonals
                                 and the padding stays within 1.5 x its entries, else it stays on CSR; 0 = off */
+   int spmv_diag;            /* NKP_SPMV_DIAG (32): the solver's own matrix A also stored as per-column diagonals (f64 values), which
+                                y = A x and y = b - A x of nkp_spmv, the Krylov drivers and the chained cycles then read instead of
+                                CSR.  Same meaning as ml_diag: N > 0 = A gets them if no water column of the caller's blk_start
+                                needs more than N diagonals and the padding stays within 1.5 x its entries; 0 = off.  CSR is kept
+                                -- silently -- when no blk_start was given, on a row-distributed solver (NKP_FORCE_DIST included:
+                                the halo columns live behind n) and on a transposed handle, and by everything else that reads A
+                                (|A||x| + |b|, the K-vector products, nkp_values_product, nkp_value_gradient, the setup).  Every
+                                row is summed from +0.0 in stored order, so the bits are those of the CSR kernels for finite x; the
+                                one difference: a padded slot holds +0.0, and +0.0 times a non-finite x is NaN where CSR would not
+                                touch that x (the level operators under ml_diag behave the same) */
 } nkp_tuning;
 
 /* defaults, then the NKP_* environment overrides listed above */
@@ -285,10 +295,14 @@ int nkp_multi_dot (nkp_solver *s, const double *V, int64_t ld, int k, const doub
  * accumulation (single-GPU solvers only, NKP_EINVAL elsewhere and for another arg; its compulsory bytes: 12 nnz + 4 (n + 1) +
  * 16 K n, plus 8 K n when accumulating -- at K = 1 exactly the SpMV's); 7 = for comparison with 6, same arg: the composition
  * that kernel replaces, made of the SpMV kernels on the solver's own values -- the (batched) operator product into a temporary, its
- * de-interleave, one update pass over the K vectors (24 K n more bytes). */
+ * de-interleave, one update pass over the K vectors (24 K n more bytes); 8 = the product y = A x on A's per-column diagonals
+ * (tuning spmv_diag; NKP_EINVAL when A has none -- 0 stays the CSR kernel on the same matrix either way). */
 int nkp_time_kernel (nkp_solver *s, int which, int arg, int reps, double *avg_ms);
 
-/* Introspection: key = "n", "nnz", "nblk", "band", "levels", "spmv_bytes", "device_bytes", "precond_steps", "equil";
+/* Introspection: key = "n", "nnz", "nblk", "band", "levels", "spmv_bytes" (compulsory bytes of the CSR product: 12 nnz +
+ * 4 (n + 1) + 16 n), "device_bytes", "precond_steps", "equil"; "spmv_diag" (1 = the products with A run on its per-column
+ * diagonals, tuning spmv_diag), "spmv_diag_bytes" (compulsory bytes of one such product: 8 per stored slot, padding included,
+ * the tile and group descriptors, 16 n; 0 without diagonals);
  * column-Jacobi preconditioner, the lane layout of its column blocks: "col_stream" (1 = factors streamed), "col_ldsres" (0, 1 =
  * column resident in LDS, 2 = packed), "col_gw" (columns per group), "col_max_len" (longest column), "col_lds_bytes" (dynamic LDS);
  * "create_us" (wall time of nkp_create), "ml_setup_us" (of which: the hierarchy), "ml_levels_on_device" (levels whose operator
@@ -673,6 +687,12 @@ int nkp_dist_plan_host (int64_t m_loc, int64_t nnz_loc, const int32_t *rowptr_lo
  * key dg_grp[2 g] and dg_grp[2 g + 1] = s0 | m << 16, its first slot in the column and its keys (m <= 5 and m <= 64 - rows + 1,
  * rows = ceil (len / ceil (len / 64)), the column's tallest tile).  All in the level's colour-major row order. */
 int64_t nkp_ml_level_array (nkp_solver *s, int level, const char *what, void *dst, int64_t capacity_bytes);
+
+/* The same for the per-column diagonals of the solver's own matrix A (tuning spmv_diag), in the row order and with the water
+ * columns of nkp_create: what = "dg_ptr", "dg_key", "dg_voff", "dg_gptr", "dg_grp" as above, "dg_val" (double).  Every array is
+ * empty when A runs on CSR (spmv_diag = 0, not eligible, no blk_start, row-distributed, a transposed handle).  A clone reads its
+ * owner's. */
+int64_t nkp_matrix_array (nkp_solver *s, const char *what, void *dst, int64_t capacity_bytes);
 
 /* Host-only planning step of the multilevel preconditioner inside nkp_create, exposed so the aggregation logic can
  * be tested without a GPU: builds the low-order twin, the coarse cells of every level (geometric groups split by

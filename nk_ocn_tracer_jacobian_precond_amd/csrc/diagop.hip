@@ -1,12 +1,15 @@
-// Level operators as per-column diagonals (CsrDev::dg_*, nkp_dev.h): the residual rows of the Gauss-Seidel half sweeps and the
-// full residual before the restriction without a per-entry column index.
+// Operators as per-column diagonals (CsrDev::dg_*, nkp_dev.h): the residual rows of the Gauss-Seidel half sweeps and the full
+// residual before the restriction on the level operators (f32 values), and the solver's own products with A (f64 values,
+// tuning spmv_diag), without a per-entry column index.  One kernel text serves both value types and both y = L x and
+// y = b - L x.
 //
 // Rows of a water column are contiguous and depth-ordered on every level.  For a row at position kl of its column and an
 // entry in column j, key = j - kl is the same for every row of the column that couples to the same neighbour column at the
 // same depth offset, so a column needs a short sorted list of keys and one dense diagonal of values per key.  With one lane
 // per row the value loads and the x loads of a slot are both contiguous runs.  Ascending keys are ascending columns within
 // every row -- the stored order the CSR kernels sum in -- and a padded position adds 0.0f * x = +-0 to a sum that is never
-// -0, which leaves it as it is: same bits as csr_spmv_pipe_kernel / csr_spmv_stream_kernel for finite x.
+// -0, which leaves it as it is: same bits as csr_spmv_pipe_kernel / csr_spmv_stream_kernel for finite x (a padded zero times
+// a non-finite x is NaN, where CSR never touches that x).
 #include "nkp_dev.h"
 #include "mlsetup.h"
 
@@ -18,7 +21,7 @@
 #define DG_WAVES (DG_THREADS / NKP_WAVE)
 #define DG_RPL 4                 // rows per lane of the key kernel: columns of up to 256 rows
 #define DG_UNROLL 8              // the zeros behind dg_key
-#define DG_GROUPS 3              // groups whose loads are in flight together
+#define DG_GROUPS 3              // groups whose loads are in flight together (f64 values: 2 and 4 measured the same)
 
 // ---------------------------------------------------------------- setup: the keys of every column
 // One wave per column, lane l walks rows l, l + 64, ..: every round takes the smallest key any row still has to offer (rows
@@ -74,10 +77,11 @@ void diag_compact_kernel (int ncol, int cap, const int *__restrict__ tmpkey, con
 
 // ---------------------------------------------------------------- values (setup and refresh)
 // One wave per tile, one lane per row: the row's entries and the column's keys are both ascending, so one walk over the keys
-// places every value and writes 0.0f everywhere else -- each position of the value block is written once, by its own row.
+// places every value and writes +0.0 everywhere else -- each position of the value block is written once, by its own row.
+template <class VT>
 __global__ __launch_bounds__ (DG_THREADS)
 void diag_fill_kernel (int ntile, const DgTile *__restrict__ tile, const int *__restrict__ rowptr, const int *__restrict__ colind,
-                       const float *__restrict__ valf, const int *__restrict__ dg_key, float *__restrict__ dg_val)
+                       const VT *__restrict__ valf, const int *__restrict__ dg_key, VT *__restrict__ dg_val)
 {
    const int t = blockIdx.x * DG_WAVES + (threadIdx.x >> 6), lane = threadIdx.x & (NKP_WAVE - 1);
    if (t >= ntile) return;
@@ -86,18 +90,19 @@ void diag_fill_kernel (int ntile, const DgTile *__restrict__ tile, const int *__
    const int kl = T.kl0 + lane;
    int p = rowptr[T.row0 + lane];
    const int e1 = rowptr[T.row0 + lane + 1];
-   float *dst = dg_val + T.voff + kl;
+   VT *dst = dg_val + T.voff + kl;
    for (int s = 0; s < T.nk; s++) {
-      float v = 0.0f;
+      VT v = (VT) 0;
       if (p < e1 && colind[p] - kl == dg_key[T.k0 + s]) v = valf[p++];
       dst[(size_t) s * T.len] = v;
    }
 }
 
-// ---------------------------------------------------------------- y_rows = b_rows - (L x)_rows
+// ---------------------------------------------------------------- y_rows = b_rows - (L x)_rows (MODE 1), y_rows = (L x)_rows (MODE 0)
 // One wave per tile, lane l < rows owns row row0 + l (the lanes behind the tile's end repeat its last row and store nothing,
 // so every load stays inside the arrays).  The tile and the groups are wave-uniform: scalar loads.  Per slot one contiguous
-// f32 load of the diagonal; f64 product and sum, each rounded, in slot order.
+// load of the diagonal in its stored type VT (float: the level operators, double: A); f64 product and sum, each rounded, in
+// slot order, from acc = +0.0.
 //
 // Groups: the keys of a neighbour column's rows at depth -1, 0, +1 are consecutive, and for the key behind one a lane would
 // load the x its upper neighbour lane loaded for the key before.  So x is loaded once per group of consecutive keys (DgGroup,
@@ -111,7 +116,7 @@ void diag_fill_kernel (int ntile, const DgTile *__restrict__ tile, const int *__
 // dg_step: G groups, their G + (keys of the groups) loads requested before the first is consumed.  Both halves are straight
 // lines with wave-uniform exits: the loads (dg_vals) and the sums (dg_sums) of a group of m keys are the first m stages of
 // the text for DG_RUN_MAX keys.  The kernel takes a column's groups DG_GROUPS at a time and the rest in one step of exactly
-// that length.
+// that length.  The f64 instantiation holds twice the value registers per group (48 VGPRs against 32, both 8 waves per SIMD).
 __device__ __forceinline__ double dg_lane_up (double w)
 {
    // v_mov_b32_dpp wave_shl:1 -- lane i takes lane i + 1's, lane 63 keeps its own (bound_ctrl off); __shfl_down (w, 1), two
@@ -122,27 +127,27 @@ __device__ __forceinline__ double dg_lane_up (double w)
    return __hiloint2double (hi, lo);
 }
 
-template <int U>
-__device__ __forceinline__ void dg_vals (const float *__restrict__ p, int len, int m, float (&v)[DG_RUN_MAX])
+template <int U, class VT>
+__device__ __forceinline__ void dg_vals (const VT *__restrict__ p, int len, int m, VT (&v)[DG_RUN_MAX])
 {
    v[U] = p[(size_t) U * len];
    if constexpr (U + 1 < DG_RUN_MAX)
       if (m > U + 1) dg_vals<U + 1> (p, len, m, v);
 }
 
-template <int U>
-__device__ __forceinline__ void dg_sums (const float (&v)[DG_RUN_MAX], int m, double w, double &acc)
+template <int U, class VT>
+__device__ __forceinline__ void dg_sums (const VT (&v)[DG_RUN_MAX], int m, double w, double &acc)
 {
    acc += (double) v[U] * w;
    if constexpr (U + 1 < DG_RUN_MAX)
       if (m > U + 1) dg_sums<U + 1> (v, m, dg_lane_up (w), acc);
 }
 
-template <int G>
-__device__ __forceinline__ void dg_step (const DgGroup *__restrict__ grp, const float *__restrict__ val, const double *__restrict__ x, int len, int kl,
+template <int G, class VT>
+__device__ __forceinline__ void dg_step (const DgGroup *__restrict__ grp, const VT *__restrict__ val, const double *__restrict__ x, int len, int kl,
                                          int base, int n, double &acc)
 {
-   float v[G][DG_RUN_MAX];
+   VT v[G][DG_RUN_MAX];
    double w[G];
    int m[G];
    DgGroup R[G];
@@ -158,8 +163,9 @@ __device__ __forceinline__ void dg_step (const DgGroup *__restrict__ grp, const 
    for (int g = 0; g < G; g++) dg_sums<0> (v[g], m[g], w[g], acc);
 }
 
+template <class VT, int MODE>
 __global__ __launch_bounds__ (DG_THREADS)
-void diag_residual_kernel (const DgTile *__restrict__ tile, int ntile, const DgGroup *__restrict__ dg_grp, const float *__restrict__ dg_val,
+void diag_residual_kernel (const DgTile *__restrict__ tile, int ntile, const DgGroup *__restrict__ dg_grp, const VT *__restrict__ dg_val,
                            const double *__restrict__ x, const double *__restrict__ b, double *__restrict__ y, int n)
 {
    const int t = __builtin_amdgcn_readfirstlane (blockIdx.x * DG_WAVES + (threadIdx.x >> 6));
@@ -169,9 +175,10 @@ void diag_residual_kernel (const DgTile *__restrict__ tile, int ntile, const DgG
    const int lr = min (lane, T.rows - 1);
    const int kl = T.kl0 + lr;
    const int base = T.kl0 + lane;
-   const double bv = b[T.row0 + lr];
+   double bv = 0.0;
+   if constexpr (MODE == 1) bv = b[T.row0 + lr];
    const DgGroup *__restrict__ grp = dg_grp + T.g0;
-   const float *__restrict__ val = dg_val + T.voff;
+   const VT *__restrict__ val = dg_val + T.voff;
    double acc = 0.0;
    int g = 0;
    for (; g + DG_GROUPS <= T.ng; g += DG_GROUPS) dg_step<DG_GROUPS> (grp + g, val, x, T.len, kl, base, n, acc);
@@ -181,13 +188,13 @@ void diag_residual_kernel (const DgTile *__restrict__ tile, int ntile, const DgG
       case 2: dg_step<2> (grp + g, val, x, T.len, kl, base, n, acc); break;
       default: break;
    }
-   if (lane < T.rows) y[T.row0 + lane] = bv - acc;
+   if (lane < T.rows) y[T.row0 + lane] = MODE == 1 ? bv - acc : acc;
 }
 
 // ---------------------------------------------------------------- host side
 static void diag_drop (CsrDev &L, size_t *device_bytes, size_t held)
 {
-   for (void **p : { (void **) &L.dg_ptr, (void **) &L.dg_key, (void **) &L.dg_voff, (void **) &L.dg_val, (void **) &L.dg_tile, (void **) &L.dg_gptr, (void **) &L.dg_grp })
+   for (void **p : { (void **) &L.dg_ptr, (void **) &L.dg_key, (void **) &L.dg_voff, (void **) &L.dg_val, (void **) &L.dg_vald, (void **) &L.dg_tile, (void **) &L.dg_gptr, (void **) &L.dg_grp })
       if (*p) { (void) hipFree (*p); *p = nullptr; }
    L.dg_ntile = L.dg_ncol = L.dg_nkey = L.dg_ngrp = 0;
    L.dg_nval = 0;
@@ -218,7 +225,8 @@ int diag_build (CsrDev &L, const int *h_blk_start, const int *d_blk_start, int n
                 size_t *device_bytes, hipStream_t st)
 {
    color_tile[0] = color_tile[1] = color_tile[2] = 0;
-   if (cap <= 0 || !L.valf || ncol <= 0 || L.nnz <= 0 || max_len > DG_RPL * NKP_WAVE) return 0;
+   const bool f64 = !L.valf;         // no f32 copy: the diagonals hold L.val as it is (the solver's own A)
+   if (cap <= 0 || (f64 && !L.val) || ncol <= 0 || L.nnz <= 0 || max_len > DG_RPL * NKP_WAVE) return 0;
    if (cap > 4096) cap = 4096;
    if ((int64_t) ncol * cap > INT_MAX) return 0;
    mls::DBuf<int> tmpkey, dcnt;
@@ -258,7 +266,7 @@ int diag_build (CsrDev &L, const int *h_blk_start, const int *d_blk_start, int n
       return 0;
    };
    if (!(put ((void **) &L.dg_ptr, ptr.data (), ptr.size () * sizeof (int)) && put ((void **) &L.dg_key, nullptr, ((size_t) ptr[ncol] + DG_UNROLL) * sizeof (int)) &&
-         put ((void **) &L.dg_voff, voff.data (), voff.size () * sizeof (long long)) && put ((void **) &L.dg_val, nullptr, (size_t) nval * sizeof (float))))
+         put ((void **) &L.dg_voff, voff.data (), voff.size () * sizeof (long long)) && (f64 ? put ((void **) &L.dg_vald, nullptr, (size_t) nval * sizeof (double)) : put ((void **) &L.dg_val, nullptr, (size_t) nval * sizeof (float)))))
       return give_up ();
    (void) hipMemsetAsync (L.dg_key + ptr[ncol], 0, DG_UNROLL * sizeof (int), st);
    const int64_t slots = (int64_t) ncol * cap;
@@ -305,15 +313,30 @@ int diag_build (CsrDev &L, const int *h_blk_start, const int *d_blk_start, int n
 
 void launch_diag_fill (const CsrDev &L, hipStream_t st)
 {
-   if (!L.dg_val || L.dg_ntile <= 0) return;
-   hipLaunchKernelGGL (diag_fill_kernel, dim3 ((L.dg_ntile + DG_WAVES - 1) / DG_WAVES), dim3 (DG_THREADS), 0, st, L.dg_ntile, (const DgTile *) L.dg_tile,
-                       (const int *) L.rowptr, (const int *) L.colind, (const float *) L.valf, (const int *) L.dg_key, L.dg_val);
+   if (!(L.dg_val || L.dg_vald) || L.dg_ntile <= 0) return;
+   const dim3 grid ((L.dg_ntile + DG_WAVES - 1) / DG_WAVES);
+   if (L.dg_vald)
+      hipLaunchKernelGGL (diag_fill_kernel<double>, grid, dim3 (DG_THREADS), 0, st, L.dg_ntile, (const DgTile *) L.dg_tile, (const int *) L.rowptr,
+                          (const int *) L.colind, (const double *) L.val, (const int *) L.dg_key, L.dg_vald);
+   else
+      hipLaunchKernelGGL (diag_fill_kernel<float>, grid, dim3 (DG_THREADS), 0, st, L.dg_ntile, (const DgTile *) L.dg_tile, (const int *) L.rowptr,
+                          (const int *) L.colind, (const float *) L.valf, (const int *) L.dg_key, L.dg_val);
 }
 
 void launch_diag_residual (const CsrDev &L, int tile0, int tile1, const double *x, const double *b, double *y, hipStream_t st)
 {
    const int cnt = tile1 - tile0;
    if (cnt <= 0) return;
-   hipLaunchKernelGGL (diag_residual_kernel, dim3 ((cnt + DG_WAVES - 1) / DG_WAVES), dim3 (DG_THREADS), 0, st, (const DgTile *) L.dg_tile + tile0, cnt,
+   hipLaunchKernelGGL ((diag_residual_kernel<float, 1>), dim3 ((cnt + DG_WAVES - 1) / DG_WAVES), dim3 (DG_THREADS), 0, st, (const DgTile *) L.dg_tile + tile0, cnt,
                        (const DgGroup *) L.dg_grp, (const float *) L.dg_val, x, b, y, (int) L.n);
+}
+
+void launch_diag_spmv (const CsrDev &A, const double *x, double *y, const double *b, int mode, hipStream_t st)
+{
+   if (A.dg_ntile <= 0 || !A.dg_vald) return;
+   const dim3 grid ((A.dg_ntile + DG_WAVES - 1) / DG_WAVES);
+   with_bool (mode == 1, [&] (auto residual) {
+      hipLaunchKernelGGL ((diag_residual_kernel<double, decltype (residual)::value ? 1 : 0>), grid, dim3 (DG_THREADS), 0, st, (const DgTile *) A.dg_tile, A.dg_ntile,
+                          (const DgGroup *) A.dg_grp, (const double *) A.dg_vald, x, b, y, (int) A.n);
+   });
 }

@@ -49,7 +49,8 @@ struct CsrDev {
    unsigned short *codes = nullptr;   // [nnz]
    int *dict = nullptr;
    int *dict_ptr = nullptr;           // [nrowblk+1]
-   // optional per-column diagonals of a level operator (diagop.hip; all NULL = the level runs on CSR).  Rows of a water
+   // optional per-column diagonals of a level operator (tuning ml_diag) or of the solver's own A (tuning spmv_diag, f64 values
+   // in dg_vald) (diagop.hip; all NULL = the operator runs on CSR).  Rows of a water
    // column are contiguous and depth-ordered, so with kl = the position of a row inside its column, colind - kl takes few
    // distinct values ("keys") over a column: one per (neighbour column, depth offset).  Column c keeps its keys ascending in
    // dg_key[dg_ptr[c] .. dg_ptr[c+1]) and one dense diagonal per key: dg_val[dg_voff[c] + s * len + kl] is the entry of row
@@ -57,7 +58,8 @@ struct CsrDev {
    int *dg_ptr = nullptr;             // [ncol+1]
    int *dg_key = nullptr;             // [dg_nkey = dg_ptr[ncol]] (+ 8 zeros behind them, which no kernel reads)
    long long *dg_voff = nullptr;      // [ncol]
-   float *dg_val = nullptr;           // [dg_nval]
+   float *dg_val = nullptr;           // [dg_nval] (a level operator: the values of valf)
+   double *dg_vald = nullptr;         // [dg_nval] (a matrix without valf, the solver's own A: the values of val); one of the two at most
    DgTile *dg_tile = nullptr;         // [dg_ntile] ceil (len / 64) per column, of equal heights (67 rows: 34 + 33), in row order
    // groups (pattern only, built once): column c cuts its keys into maximal runs of consecutive keys of at most DG_RUN_MAX and
    // at most 64 - rows + 1 keys (rows: of the column's tallest tile), so that row l of a tile finds x for the group's d-th key
@@ -84,16 +86,19 @@ void launch_csr_spmv_range (const CsrDev &A, int rb0, int rb1, const double *x, 
 // y = |A| |x| + |b|   (denominator of the componentwise backward error)
 void launch_csr_abs_spmv (const CsrDev &A, const double *x, const double *b, double *y, hipStream_t st);
 // ---- per-column diagonals (diagop.hip)
-// Build the layout of L from its CSR arrays (f32 values) if every column gets by with at most cap keys, no column is longer
-// than 256 rows and the padded slots stay within 1.5 nnz; h_blk_start / d_blk_start: row offsets of the ncol columns, the first
-// ncol0 of them colour 0.  Returns 1 (built: color_tile[c] .. color_tile[c+1] are colour c's tiles) or 0 (L stays on CSR: not
-// eligible, or out of device memory, which is answered here).
+// Build the layout of L from its CSR arrays (the f32 values valf into dg_val; without valf the f64 values val into dg_vald) if
+// every column gets by with at most cap keys, no column is longer than 256 rows and the padded slots stay within 1.5 nnz;
+// h_blk_start / d_blk_start: row offsets of the ncol columns, the first ncol0 of them colour 0.  Returns 1 (built:
+// color_tile[c] .. color_tile[c+1] are colour c's tiles) or 0 (L stays on CSR: not eligible, or out of device memory, which is
+// answered here).
 int diag_build (CsrDev &L, const int *h_blk_start, const int *d_blk_start, int ncol, int ncol0, int max_len, int cap, int color_tile[3],
                 size_t *device_bytes, hipStream_t st);
-// dg_val from L.valf (new values on the same pattern)
+// dg_val from L.valf, dg_vald from L.val (new values on the same pattern)
 void launch_diag_fill (const CsrDev &L, hipStream_t st);
 // rows of the tiles [tile0, tile1): y_rows = b_rows - (L x)_rows, every row summed in stored order like the CSR kernels
 void launch_diag_residual (const CsrDev &L, int tile0, int tile1, const double *x, const double *b, double *y, hipStream_t st);
+// all rows of a matrix with f64 diagonals (dg_vald): y = A x (mode 0) or y = b - A x (mode 1), the bits of launch_csr_spmv
+void launch_diag_spmv (const CsrDev &A, const double *x, double *y, const double *b, int mode, hipStream_t st);
 // host helper: greedy row-block partition (host arrays)
 void build_rowblocks_host (int64_t n, const int *rowptr, int **rowblk_out, int *nrowblk_out);
 

@@ -153,6 +153,7 @@ static int refactor_commit (nkp_solver *s, bool rebuilt, MlHierarchy &H2, char *
       if (rebuilt) ml_free (H2);
       return -3;
    }
+   launch_diag_fill (s->A, st);            // A's own per-column diagonals (tuning spmv_diag) hold the same values
    if (s->equil) rf_launch_row_scale (s->A, W.aval, s->rscale, s->rinv, st);
    int rc = 0;
    if (multilevel && rebuilt) {

@@ -12,6 +12,7 @@
 // is solver_impl.h.
 #include "solver_impl.h"
 
+#include <limits.h>
 #include <math.h>
 #include <stdarg.h>
 #include <stdio.h>
@@ -62,7 +63,7 @@ void solver_free (nkp_solver *s)
    s->batch_members.clear ();
    for (double *p : { s->bvin, s->bz, s->bw })
       if (p) (void) hipFree (p);
-   void *ptrs[] = { s->A.rowptr, s->A.colind, s->A.val, s->A.rowblk, s->A.codes, s->A.dict, s->A.dict_ptr, s->B.blk_start, s->B.fac, s->B.grp_b0, s->B.grp_nb, s->B.grp_maxlen, s->B.grp_base, s->B.grp_row0, s->B.col_slot, s->B.fac_t, s->B.gs_rb_ptr, s->B.gs_rb, s->V, s->vcur, s->Z, s->w, s->r,
+   void *ptrs[] = { s->A.rowptr, s->A.colind, s->A.val, s->A.rowblk, s->A.codes, s->A.dict, s->A.dict_ptr, s->A.dg_ptr, s->A.dg_key, s->A.dg_voff, s->A.dg_vald, s->A.dg_tile, s->A.dg_gptr, s->A.dg_grp, s->B.blk_start, s->B.fac, s->B.grp_b0, s->B.grp_nb, s->B.grp_maxlen, s->B.grp_base, s->B.grp_row0, s->B.col_slot, s->B.fac_t, s->B.gs_rb_ptr, s->B.gs_rb, s->V, s->vcur, s->Z, s->w, s->r,
                     s->x, s->b, s->t1, s->t2, s->p1, s->p2, s->partial, s->dscal, s->dint, s->rscale, s->rinv, s->eqtmp };
    for (void *p : ptrs)
       if (p) (void) hipFree (p);
@@ -170,7 +171,32 @@ static void spmv_op (nkp_solver *s, const double *x, double *y, const double *b,
       alltoallv_dev (s, s->dist.sendbuf, s->dist.send_counts.data (), s->dist.xe + s->n, s->dist.recv_counts.data (), s->stream);
    }
    if (mode == 2) launch_csr_abs_spmv (s->A, xin, b, y, s->stream);
+   else if (s->A.dg_vald) launch_diag_spmv (s->A, xin, y, b, mode, s->stream);      // tuning spmv_diag: same bits, no column indices
    else launch_csr_spmv (s->A, xin, y, b, mode, s->stream);
+}
+
+// A's per-column diagonals (tuning spmv_diag) from the caller's water columns.  Any reason not to have them -- columns that do
+// not tile the rows, too many keys, too much padding, no device memory -- leaves A on CSR and is no error.
+static void build_matrix_diagonals (nkp_solver *s, const int32_t *blk_start, int64_t nblk)
+{
+   const int64_t n = s->n;
+   if (s->tune.spmv_diag <= 0 || !blk_start || nblk <= 0 || nblk >= INT_MAX || n <= 0 || blk_start[0] != 0 || blk_start[nblk] != n) return;
+   int max_len = 0;
+   for (int64_t c = 0; c < nblk; c++) {
+      const int len = blk_start[c + 1] - blk_start[c];
+      if (len <= 0) return;
+      max_len = std::max (max_len, len);
+   }
+   void *d_blk = nullptr;
+   const size_t bytes = ((size_t) nblk + 1) * sizeof (int);
+   if (hipMalloc (&d_blk, bytes) != hipSuccess || hipMemcpy (d_blk, blk_start, bytes, hipMemcpyHostToDevice) != hipSuccess) {
+      if (d_blk) (void) hipFree (d_blk);
+      (void) hipGetLastError ();
+      return;
+   }
+   int color_tile[3];
+   (void) diag_build (s->A, blk_start, (const int *) d_blk, (int) nblk, (int) nblk, max_len, s->tune.spmv_diag, color_tile, &s->device_bytes, s->stream);
+   (void) hipFree (d_blk);
 }
 
 static inline void allreduce_dev (nkp_solver *s, double *dev, int count, int op)
@@ -399,6 +425,8 @@ static int create_impl (nkp_solver **out, const nkp_options *opt_in, int64_t n, 
       free (rb);
       if (rc != NKP_OK) { solver_free (s); return rc; }
    }
+   // the caller's own water columns only; a row-distributed rank keeps CSR (its halo columns live behind n)
+   if (!spmv_mat && blk_default.empty ()) build_matrix_diagonals (s, blk_start, nblk);
 
    if (s->equil) {
       // R_i = 1 / max_j |a_ij| (the row half of dgsequ); rows without entries keep 1
@@ -557,6 +585,30 @@ extern "C" int64_t nkp_ml_level_array (nkp_solver *s, int level, const char *wha
    return count;
 }
 
+// the per-column diagonals of the solver's own matrix (tuning spmv_diag), same contract as nkp_ml_level_array
+extern "C" int64_t nkp_matrix_array (nkp_solver *s, const char *what, void *dst, int64_t capacity_bytes)
+{
+   if (!s || !what) return fail (NKP_EINVAL, "nkp_matrix_array: bad argument");
+   const CsrDev &A = s->A;
+   const bool have = A.dg_vald != nullptr;
+   const void *src = nullptr;
+   int64_t count = 0;
+   size_t elem = 4;
+   if (!strcmp (what, "dg_ptr")) { src = A.dg_ptr; count = have ? A.dg_ncol + 1 : 0; }
+   else if (!strcmp (what, "dg_key")) { src = A.dg_key; count = have ? (int64_t) A.dg_nkey : 0; }
+   else if (!strcmp (what, "dg_voff")) { src = A.dg_voff; count = have ? A.dg_ncol : 0; elem = 8; }
+   else if (!strcmp (what, "dg_val")) { src = A.dg_vald; count = have ? A.dg_nval : 0; elem = 8; }
+   else if (!strcmp (what, "dg_gptr")) { src = A.dg_gptr; count = have ? A.dg_ncol + 1 : 0; }
+   else if (!strcmp (what, "dg_grp")) { src = A.dg_grp; count = have ? 2 * (int64_t) A.dg_ngrp : 0; }
+   else return fail (NKP_EINVAL, "nkp_matrix_array: unknown array '%s'", what);
+   if (!dst) return count;
+   if (count * (int64_t) elem > capacity_bytes) return fail (NKP_EINVAL, "nkp_matrix_array: buffer too small");
+   HIPCHK (hipSetDevice (s->device));
+   HIPCHK (hipStreamSynchronize (s->stream));
+   if (count) HIPCHK (hipMemcpy (dst, src, (size_t) count * elem, hipMemcpyDeviceToHost));
+   return count;
+}
+
 extern "C" int nkp_create (nkp_solver **out, const nkp_options *opt, int64_t n, int64_t nnz,
                            const int32_t *rowptr, const int32_t *colind, const double *val,
                            const int32_t *blk_start, int64_t nblk, int coupled_tracer_cnt)
@@ -613,6 +665,10 @@ extern "C" int64_t nkp_get_int (nkp_solver *s, const char *key)
    if (!strcmp (key, "ml_nnz")) { int64_t t = 0; for (auto &v : s->ml.lev) t += v.L.nnz; return t; }
    if (!strcmp (key, "rowblocks")) return s->A.nrowblk;
    if (!strcmp (key, "spmv_bytes")) return 12 * s->A.nnz + 4 * (s->n + 1) + 16 * s->n;
+   if (!strcmp (key, "spmv_diag")) return s->A.dg_vald ? 1 : 0;
+   // compulsory bytes of one product on the diagonals, counted as ml_bytes counts a level's: values, tiles, groups, x and y
+   if (!strcmp (key, "spmv_diag_bytes"))
+      return s->A.dg_vald ? 8 * s->A.dg_nval + (int64_t) s->A.dg_ntile * (int64_t) sizeof (DgTile) + (int64_t) s->A.dg_ngrp * (int64_t) sizeof (DgGroup) + 16 * s->n : 0;
    if (!strcmp (key, "precond_bytes")) return s->opt.precond == NKP_PRECOND_NONE ? 16 * s->n : (int64_t) (2 * s->B.P + 1) * 8 * s->n + 16 * s->n;
    if (!strcmp (key, "device_bytes")) return (int64_t) s->device_bytes;
    if (!strcmp (key, "precond_steps")) return s->precond_steps;
@@ -1626,6 +1682,7 @@ extern "C" int nkp_multi_dot (nkp_solver *s, const double *V, int64_t ld, int k,
 extern "C" int nkp_time_kernel (nkp_solver *s, int which, int arg, int reps, double *avg_ms)
 {
    if (!s || !avg_ms || reps < 1) return fail (NKP_EINVAL, "nkp_time_kernel: bad argument");
+   if (which == 8 && !s->A.dg_vald) return fail (NKP_EINVAL, "nkp_time_kernel: the matrix has no per-column diagonals (tuning spmv_diag)");
    HIPCHK (hipSetDevice (s->device));
    if (which == 5) {      // the gradient kernel of nkp_value_gradient at interleave width arg, on scratch operands of its own
       const int prc = valgrad_time_prepare (s, arg);
@@ -1656,7 +1713,9 @@ extern "C" int nkp_time_kernel (nkp_solver *s, int which, int arg, int reps, dou
       const int cnt = pass == 0 ? (reps < 3 ? reps : 3) : reps;
       HIPCHK (hipEventRecord (e0, s->stream));
       for (int i = 0; i < cnt; i++) {
-         if (which == 0) spmv_op (s, s->t1, s->t2, nullptr, 0);
+         if (which == 0 && s->A.dg_vald) launch_csr_spmv (s->A, s->t1, s->t2, nullptr, 0, s->stream);      // 0 stays the CSR kernel
+         else if (which == 0) spmv_op (s, s->t1, s->t2, nullptr, 0);
+         else if (which == 8) launch_diag_spmv (s->A, s->t1, s->t2, nullptr, 0, s->stream);
          else if (which == 1) apply_precond_once (s, s->t1, s->t2);
          else if (which == 2) arnoldi_step_device (s, arg);
          else if (which == 5) valgrad_time_launch (s, arg);

@@ -223,7 +223,9 @@ extern "C" int nkp_transpose (nkp_solver *s, nkp_solver **out)
    // the options and tuning the source resolved at its creation; the block offsets and grid positions it kept
    nkp_options opt = s->opt;
    opt.device = s->device;
-   opt.tuning = &s->tune;
+   nkp_tuning tune = s->tune;
+   tune.spmv_diag = 0;                 // the transposed handle keeps its products on CSR
+   opt.tuning = &tune;
    opt.col_i = s->h_col_i.empty () ? nullptr : s->h_col_i.data ();
    opt.col_j = s->h_col_j.empty () ? nullptr : s->h_col_j.data ();
    opt.col_t = s->h_col_t.empty () ? nullptr : s->h_col_t.data ();

@@ -60,7 +60,7 @@ static void builtin_tuning (nkp_tuning *t)
    t->col_group = 8; t->col_pipe_min = 0; t->col_ldsres_early = 0; t->col_ldsres_packed = 1; t->col_sort_groups = 1;
    t->spmv_variant = 4; t->spmv_compress = 0; t->spmv_pipe_min = 1024; t->spmv_run = 1; t->spmv_wgs = 256;
    t->rhs_batch = 1; t->batch_spmv_rows = 1; t->precond_steps = 0; t->equil = -1; t->dist_overlap = 1; t->dist_ras = 1; t->dist_one_reduce = 0; t->force_dist = 0; t->setup_threads = 0; t->plan_times = 0;
-   t->ml_drop_intertracer = 0; t->ml_huge_from = -1; t->dist_ras_rings = 1; t->ml_diag = 32;
+   t->ml_drop_intertracer = 0; t->ml_huge_from = -1; t->dist_ras_rings = 1; t->ml_diag = 32; t->spmv_diag = 32;
 }
 
 const nkp_tuning &nkp_builtin_tuning ()
@@ -103,6 +103,7 @@ extern "C" int nkp_default_tuning (nkp_tuning *t)
    ENV_FLAG ("NKP_ML_DROP_INTERTRACER", ml_drop_intertracer);
    ENV_INT ("NKP_DIST_RAS_RINGS", dist_ras_rings);
    ENV_INT ("NKP_ML_DIAG", ml_diag);
+   ENV_INT ("NKP_SPMV_DIAG", spmv_diag);
 #undef ENV_INT
 #undef ENV_POS
 #undef ENV_FLAG

@@ -32,7 +32,7 @@ ABI_SYMBOLS = [
     "nkp_dist_plan_copy", "nkp_dist_plan_free", "nkp_ml_level_array", "nkp_default_tuning", "nkp_solve_batch_device",
     "nkp_refactor", "nkp_refactor_device", "nkp_refactor_dist", "nkp_refactor_dist_device", "nkp_transpose", "nkp_transpose_dist",
     "nkp_value_gradient", "nkp_value_gradient_device",
-    "nkp_values_product", "nkp_values_product_device", "nkp_solve_tangent_device",
+    "nkp_values_product", "nkp_values_product_device", "nkp_solve_tangent_device", "nkp_matrix_array",
 ]
 
 _ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p)
@@ -60,7 +60,7 @@ class NkpTuning(C.Structure):
         ("spmv_variant", C.c_int), ("spmv_compress", C.c_int), ("spmv_pipe_min", C.c_int), ("spmv_run", C.c_int), ("spmv_wgs", C.c_int),
         ("rhs_batch", C.c_int), ("precond_steps", C.c_int), ("equil", C.c_int), ("dist_overlap", C.c_int), ("dist_ras", C.c_int), ("force_dist", C.c_int),
         ("setup_threads", C.c_int), ("plan_times", C.c_int), ("ml_drop_intertracer", C.c_int), ("dist_one_reduce", C.c_int), ("ml_huge_from", C.c_int), ("col_ldsres_min", C.c_int), ("col_sort_groups", C.c_int), ("batch_spmv_rows", C.c_int),
-        ("dist_ras_rings", C.c_int), ("ml_diag", C.c_int),
+        ("dist_ras_rings", C.c_int), ("ml_diag", C.c_int), ("spmv_diag", C.c_int),
     ]
 
 
@@ -112,6 +112,8 @@ def load_library(path=None):
     lib.nkp_get_int.restype = C.c_int64
     lib.nkp_ml_level_array.argtypes = [vp, C.c_int, C.c_char_p, vp, C.c_int64]
     lib.nkp_ml_level_array.restype = C.c_int64
+    lib.nkp_matrix_array.argtypes = [vp, C.c_char_p, vp, C.c_int64]
+    lib.nkp_matrix_array.restype = C.c_int64
     lib.nkp_set_stream.argtypes = [vp, vp]
     lib.nkp_destroy.argtypes = [vp]
     lib.nkp_destroy.restype = None
@@ -475,6 +477,18 @@ class NkpSolver:
         out = np.empty(cnt, self._ML_ARRAY_TYPES.get(what, np.int32))
         if cnt:
             got = int(self._lib.nkp_ml_level_array(self._h, level, what.encode(), out.ctypes.data_as(C.c_void_p), out.nbytes))
+            if got != cnt:
+                raise NkpError(got, last_error())
+        return out
+
+    def matrix_array(self, what):
+        """One array of the per-column diagonals of the solver's own matrix (nkp_matrix_array, tuning spmv_diag); empty when A runs on CSR."""
+        cnt = int(self._lib.nkp_matrix_array(self._h, what.encode(), None, 0))
+        if cnt < 0:
+            raise NkpError(cnt, last_error())
+        out = np.empty(cnt, {"dg_voff": np.int64, "dg_val": np.float64}.get(what, np.int32))
+        if cnt:
+            got = int(self._lib.nkp_matrix_array(self._h, what.encode(), out.ctypes.data_as(C.c_void_p), out.nbytes))
             if got != cnt:
                 raise NkpError(got, last_error())
         return out
