@@ -7,7 +7,7 @@
 // k (K = 2 or 4: one or two 16-byte loads per gathered row), and every kernel below does for the K columns exactly what its
 // single-vector twin (spmv.hip, colblock.hip, blas1.hip) does for one -- same products, same summation and substitution
 // order -- so every column of a batched solve has the bits of the solve done alone (tests/test_gpu_batch.py).
-// The Krylov recurrences stay per system (their basis vectors are not shared: nothing to amortise); solver.hip drives K
+// The Krylov recurrences stay per system (their basis vectors are not shared: nothing to amortise); batch_solve.hip drives K
 // of them in lockstep around these kernels.
 #include "nkp_dev.h"
 

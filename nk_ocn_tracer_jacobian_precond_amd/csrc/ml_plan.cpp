@@ -20,7 +20,7 @@
 //     2-coloured and stored colour-major, so a Gauss-Seidel half-sweep is one row-range
 //     residual SpMV + one block-range column solve.
 //
-// One V(nu,nu) cycle (mlcycle.hip) approximates L^-1; FGMRES (solver.hip) iterates on the original A.
+// One V(nu,nu) cycle (mlcycle.hip) approximates L^-1; FGMRES (krylov.hip) iterates on the original A.
 #include "ml_plan.h"
 
 #include <math.h>

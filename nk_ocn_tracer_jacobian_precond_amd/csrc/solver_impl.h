@@ -1,11 +1,21 @@
-// The solver object and the few helpers that solver.hip (C ABI, create, clone, the Krylov drivers) and refactor_api.hip (new
-// matrix values on an existing solver) share.  Private to the library: nothing here is part of the C ABI.
+// The solver object, and what the host-side units that work on it share.  Each of these units has one concern:
+//   solver.hip          lifetime of the object, messages, stream, counters (nkp_destroy, nkp_set_stream, nkp_get_int)
+//   create.hip          nkp_create, nkp_create64, nkp_clone: validation, uploads, work vectors, hierarchy, column factors
+//   create_dist.hip     nkp_create_dist, nkp_gather_root (the host-side plan: dist_plan.cpp)
+//   krylov.hip          one right-hand side: operator and preconditioner of a solve, FGMRES, BiCGStab, nkp_solve
+//   krylov_host.cpp     the host arithmetic of FGMRES (krylov_host.h): no HIP, no solver object
+//   batch_solve.hip     K right-hand sides in lockstep (nkp_solve_batch_device); the kernels are batch.hip
+//   inspect.hip         entry points of tests and timing (arrays of the hierarchy and the matrix, single products, nkp_time_kernel)
+//   refactor_api.hip, transpose*.hip, valgrad_api.hip, valprod_api.hip      new values, A^T, gradient and product by values
+// What crosses units is declared once, below, under the unit that defines it.  Private to the library: nothing here is part of
+// the C ABI.
 #pragma once
 #include "../../include/nkp.h"
 #include "nkp_dev.h"
 #include "multilevel.h"
 #include "refactor.h"
 #include "dist_plan.h"
+#include "krylov_host.h"
 
 #include <atomic>
 #include <initializer_list>
@@ -219,17 +229,103 @@ inline int reserve (nkp_solver *s, std::initializer_list<Want> set, const char *
 // the interleave width that serves nrhs vectors
 inline int width_of (int nrhs) { return nrhs <= 1 ? 1 : nrhs <= 2 ? 2 : nrhs <= 4 ? 4 : 8; }
 
+// the two device collectives of a solve; a failure leaves stale data behind and is checked before any verdict is returned
+// (inline: they run on every Krylov step)
+inline void alltoallv_dev (nkp_solver *s, const double *send, const int *send_counts, double *recv, const int *recv_counts, hipStream_t st)
+{
+   s->shared->alltoallv_calls++;
+   if (s->dist.ops.alltoallv (s->dist.ops.ctx, send, send_counts, recv, recv_counts, (void *) st)) s->comm_failed = true;
+}
+
+inline void allreduce_dev (nkp_solver *s, double *dev, int count, int op)
+{
+   if (!s->dist.on) return;
+   s->shared->allreduce_calls++;
+   if (s->dist.ops.allreduce (s->dist.ops.ctx, dev, count, op, (void *) s->stream)) s->comm_failed = true;
+}
+
+// a refactor that failed after its commit point left no usable preconditioner behind: what every later solve returns
+inline int refactor_broken (const nkp_solver *s) { return fail (NKP_ESINGULAR, "%s", s->shared->why.c_str ()); }
+
+// severity of a solve's status: OK < OK_BERR < NOT_CONVERGED < BREAKDOWN
+inline int sev_of (int c) { return c == NKP_OK ? 0 : c == NKP_OK_BERR ? 1 : c == NKP_NOT_CONVERGED ? 2 : 3; }
+
+#define NKP_BERR_ROUNDING_LEVEL 1.0e-14     // 45 eps
+
 // ---- defined in solver.hip -------------------------------------------------------------------------------------------------
 NKP_PRIVATE void solver_free (nkp_solver *s);
 NKP_PRIVATE void msg (const nkp_solver *s, int lvl, const char *fmt, ...);
-// Row-distributed solvers: every rank learns whether any rank's step failed, and all leave together.  A rank whose own step
-// failed returns its code and message, every other rank NKP_ECOMM naming it; a failed allgather is NKP_ECOMM everywhere.
-NKP_PRIVATE int dist_agree (nkp_solver *s, int local_rc, const char *who, const char *where);
+// ---- defined in create.hip -------------------------------------------------------------------------------------------------
+// the SpMV matrix (device copy; columns may address halo slots >= n) and the matrix the preconditioner
+// is built from (host only) are the same arrays except in the distributed flavour
+struct SpmvMatrixHost {
+   int64_t nnz, ncols;
+   const int32_t *rowptr, *colind;
+   const double *val;
+};
+// the matrix the multilevel hierarchy is built from when it is not the solver's own n x n block (distributed flavour
+// with overlap: own rows followed by the overlap rows, columns renumbered accordingly)
+struct PrecondMatrixHost {
+   int64_t n, nblk;
+   const int32_t *rowptr, *colind;
+   const double *val;
+   const int32_t *blk_start, *col_i, *col_j, *col_t;
+};
+// nkp_create (spmv_mat and pm NULL) and the rank-local part of nkp_create_dist
+NKP_PRIVATE int create_impl (nkp_solver **out, const nkp_options *opt_in, int64_t n, int64_t nnz,
+                             const int32_t *rowptr, const int32_t *colind, const double *val,
+                             const int32_t *blk_start, int64_t nblk, int coupled_tracer_cnt, const SpmvMatrixHost *spmv_mat,
+                             const PrecondMatrixHost *pm = nullptr);
+// A second set of work vectors (Krylov basis, level vectors, scalars) and a second stream on the SAME device-resident
+// matrix, factors and hierarchy: several right-hand sides can then be solved concurrently from different host threads,
+// one clone per thread.  Single-GPU solvers only.
+//
+// member: the work vectors of one more system of a batched solve.  A member of a row-distributed solver shares its parent's
+// matrix, hierarchy, stream, plan and exchange buffers (all of its work is ordered on that one stream) and is only ever driven
+// from inside the parent's collective calls, so it adds no collective of its own.
+NKP_PRIVATE int clone_impl (nkp_solver *src, nkp_solver **out, bool member);
 // developer switch ml_drop_intertracer: the matrix without the couplings between its tracer_cnt tracers, i.e. exactly what a
 // tracer-per-rank partition builds its rank-local hierarchies from
+NKP_PRIVATE void drop_intertracer (int64_t n, int tracer_cnt, const int32_t *rowptr, const int32_t *colind, const double *val,
+                                   std::vector<int32_t> &f_rowptr, std::vector<int32_t> &f_colind, std::vector<double> &f_val);
+// ---- defined in krylov.hip -------------------------------------------------------------------------------------------------
+// z = M r: one application of the preconditioner (one cycle)
+NKP_PRIVATE void apply_precond_once (nkp_solver *s, const double *rin, double *zout);
+// z = M r, optionally followed by defect-correction steps against the true operator: z += M (r - A z)
+// (NKP_PRECOND_STEPS, default 1; still a fixed linear operator, so FGMRES and BiCGStab are both fine with it)
+NKP_PRIVATE void apply_precond (nkp_solver *s, const double *rin, double *zout);
+// y = A x (0), y = b - A x (1), y = |A||x| + |b| (2); in the distributed flavour the rows other
+// ranks own are fetched first (pack -> alltoallv -> extended input vector)
+NKP_PRIVATE void spmv_op (nkp_solver *s, const double *x, double *y, const double *b, int mode);
+// one Arnoldi step on the device in two halves: (1) z_j = M^-1 v_j, w = A z_j; (2) orthogonalise w against V[0..j],
+// v_{j+1} = w / ||w||, which leaves the Hessenberg column h[0..j+1] in s->h_dev().  The batched driver replaces (1) by
+// ONE application of the cycle and of A to K interleaved vectors and runs (2) per system.
+NKP_PRIVATE void arnoldi_apply (nkp_solver *s, int j);
+NKP_PRIVATE void arnoldi_orthogonalise (nkp_solver *s, int j);
+NKP_PRIVATE void arnoldi_step_device (nkp_solver *s, int j);
+// The FGMRES state machine (FgmresState and its host arithmetic: krylov_host.h) around the device work of one system.
+// ||b||, the trivial case b = 0; returns a negative code on failure
+NKP_PRIVATE int fg_begin (nkp_solver *s, FgmresState &F);
+// true residual, verdict, start vector of the next restart cycle.  After it either F.finished, or v_0 is in place (F.j = 0).
+NKP_PRIVATE int fg_restart (nkp_solver *s, FgmresState &F);
+// column j of the Hessenberg matrix is in s->hpin[0 .. j+1] (copied and synchronised by the caller): Givens rotations, the
+// residual estimate.  Returns true when this system's restart cycle ends here (estimate met, breakdown, column budget).
+NKP_PRIVATE bool fg_post_step (nkp_solver *s, FgmresState &F);
+// y = H^-1 g (upper triangular, size F.j), x += Z y; after a breakdown the true residual of what we have decides
+NKP_PRIVATE int fg_end_cycle (nkp_solver *s, FgmresState &F);
+// componentwise backward error of s->x for s->b, like SuperLU's berr
+NKP_PRIVATE int backward_error (nkp_solver *s, double *berr);
+// ---- defined in batch_solve.hip --------------------------------------------------------------------------------------------
+// what keeps a solver's right-hand sides out of the lockstep driver (NULL: nothing), and the one line a batched call that
+// falls back leaves at -D1
+NKP_PRIVATE const char *batch_unsupported (const nkp_solver *s);
+NKP_PRIVATE void note_fallback (const nkp_solver *s, const char *who, const char *why, int nrhs);
 // the K-wide exchange buffers of a row-distributed solver (bxe, bsend, gmsg, with several rings bras_send / bras_recv), all or
 // nothing: the part of the batched solve's preparation that nkp_value_gradient shares
 NKP_PRIVATE int batch_prepare_exchange (nkp_solver *s, int K);
+// Row-distributed solvers: every rank learns whether any rank's step failed, and all leave together.  A rank whose own step
+// failed returns its code and message, every other rank NKP_ECOMM naming it; a failed allgather is NKP_ECOMM everywhere.
+NKP_PRIVATE int dist_agree (nkp_solver *s, int local_rc, const char *who, const char *where);
 // ---- defined in valgrad_api.hip --------------------------------------------------------------------------------------------
 NKP_PRIVATE void valgrad_release (nkp_solver *s);
 // nkp_time_kernel, which = 5: scratch operands for the gradient kernel at interleave width K (1, 2, 4, 8), then one launch
@@ -260,7 +356,3 @@ NKP_PRIVATE int trans_gather_values (nkp_solver *s, const double **d_valT);
 // collective: the values of A^T's row block from the owner's new values (gather, one alltoallv, placement), then the refactor
 // `refactor` (nkp_refactor_dist_device's sequence) on the transposed solver; non-zero on every rank when it could not follow
 NKP_PRIVATE int trans_dist_follow (nkp_solver *s, int flags, const char *who, int (*refactor) (nkp_solver *t, const void *d_val, int flags, const char *who));
-
-// ---- defined in solver.hip -------------------------------------------------------------------------------------------------
-NKP_PRIVATE void drop_intertracer (int64_t n, int tracer_cnt, const int32_t *rowptr, const int32_t *colind, const double *val,
-                                   std::vector<int32_t> &f_rowptr, std::vector<int32_t> &f_colind, std::vector<double> &f_val);

@@ -637,7 +637,7 @@ static void residual (int64_t n, const int32_t *rowptr, const int32_t *colind, c
 }
 
 /* right-preconditioned flexible GMRES, one classical Gram-Schmidt pass (two with reorth), the inner iteration stops on the
- * recurrence's estimate and the true residual decides at every restart -- the driver of csrc/solver.hip.
+ * recurrence's estimate and the true residual decides at every restart -- the driver of csrc/krylov.hip.
  * returns 0 converged / 1 not converged / 2 breakdown */
 ORA_EXPORT int ora_ml_fgmres (ora_ml *M, int64_t n, const int32_t *rowptr, const int32_t *colind, const double *val, int restart, int max_iters, double rtol,
                               int reorth, const double *b, double *x, int *iters_out, double *relres_out)

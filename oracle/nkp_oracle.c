@@ -255,7 +255,7 @@ static double dotp (int64_t n, const double *x, const double *y)
 }
 
 /* right-preconditioned flexible GMRES with two classical Gram-Schmidt passes: the algorithm of
- * csrc/solver.hip, operation for operation (reductions differ in summation order only).
+ * csrc/krylov.hip, operation for operation (reductions differ in summation order only).
  * precond: 0 none, 1 column blocks.  returns 0 converged / 1 not converged / 2 breakdown */
 ORA_EXPORT int ora_fgmres (int64_t n, const int32_t *rowptr, const int32_t *colind, const double *val,
                            int64_t nblk, const int32_t *blk_start, int precond, int restart, int max_iters,

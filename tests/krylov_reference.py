@@ -1,8 +1,8 @@
-"""The Krylov drivers of csrc/solver.hip restated in numpy -- TEST INFRASTRUCTURE.
+"""The Krylov drivers of csrc/krylov.hip restated in numpy -- TEST INFRASTRUCTURE.
 
-fgmres () restates fg_begin, fg_restart, arnoldi_apply, arnoldi_orthogonalise, fg_post_step and fg_end_cycle
-(csrc/solver.hip:664-891) together with the column epilogues of csrc/blas1.hip:418-486; bicgstab () restates
-csrc/solver.hip:893-961.  Vectors are float64; every inner product and norm is accumulated in np.longdouble and rounded
+fgmres () restates fg_begin, fg_restart, arnoldi_apply, arnoldi_orthogonalise, fg_post_step and fg_end_cycle (csrc/krylov.hip,
+with their host arithmetic in csrc/krylov_host.cpp: fg_restart_verdict, fg_column_step, fg_back_substitute) together with the
+column epilogues of csrc/blas1.hip:418-486; bicgstab () restates bicgstab of csrc/krylov.hip.  Vectors are float64; every inner product and norm is accumulated in np.longdouble and rounded
 once (Arith).  The operator A and the preconditioner M are callables on float64 vectors, so the same text runs on the oracle's
 operators (tests/test_krylov_reference.py) and on the solver's own spmv / precond_apply (tests/test_gpu_krylov.py).
 
@@ -10,7 +10,10 @@ A solve cut at max_iters = k returns x_k, which GMRES fixes uniquely (the residu
 implementations agree on it to rounding, whatever their summation order.
 
 Every host decision of the drivers is logged with the relative distance of the two numbers compared (Result.log), so that a
-test can show that no decision of a case sits within rounding of its threshold.
+test can show that no decision of a case sits within rounding of its threshold.  fgmres (trace=[...]) also records what the
+host saw and made of it, in order: ("restart", beta), then if the solve goes on ("cycle", steps_now, stalled_cycles,
+inner_scale); per step ("step", h, its, est, ends) with the Hessenberg column as it came from the device (est None: breakdown);
+per cycle ("end", k, y, cs, sn, g, columns of the rotated H) -- the input and the expected decisions of tests/test_krylov_host.py.
 
 Arith is the seam for the variants of tests/test_krylov_reference.py: plain f64 accumulation in reversed order (what two
 correct implementations differ by) and three deliberately wrong ones (what the GPU tests must be able to see).
@@ -77,7 +80,7 @@ def _dist(a, b):
 
 
 def chained_precond(A, M, steps):
-    """apply_precond (solver.hip:133-143): z = M r, then z += M (r - A z) for every further cycle"""
+    """apply_precond (krylov.hip): z = M r, then z += M (r - A z) for every further cycle"""
     def apply(r):
         z = M(r)
         for _ in range(1, steps):
@@ -87,7 +90,7 @@ def chained_precond(A, M, steps):
 
 
 def row_equilibration(rowptr, val):
-    """create_impl (solver.hip:401-413): R_i = 1 / max_j |a_ij| and its inverse max_j |a_ij|; rows without entries keep 1"""
+    """upload_row_scales (create.hip): R_i = 1 / max_j |a_ij| and its inverse max_j |a_ij|; rows without entries keep 1"""
     rowptr = np.asarray(rowptr, np.int64)
     n = rowptr.size - 1
     mx = np.zeros(n)
@@ -100,8 +103,8 @@ def row_equilibration(rowptr, val):
 
 
 def fgmres(A, M, b, x0=None, *, restart, max_iters, rtol=1e-10, atol=0.0, reorth=0, basis_f32=0, rscale=None, rinv=None,
-           precond_steps=1, pythagoras=False, arith=None):
-    """Restarted right-preconditioned flexible GMRES as csrc/solver.hip runs it.  rscale (with rinv = its inverse as the library
+           precond_steps=1, pythagoras=False, arith=None, trace=None):
+    """Restarted right-preconditioned flexible GMRES as csrc/krylov.hip runs it.  rscale (with rinv = its inverse as the library
     stores it, default 1 / rscale) turns the iteration into the row-weighted one on R A M R^-1.  pythagoras is the epilogue
     of a row-distributed solver with one reduction per step (it replaces the plain norm; with reorth it is not used)."""
     ar = arith or Arith()
@@ -113,7 +116,11 @@ def fgmres(A, M, b, x0=None, *, restart, max_iters, rtol=1e-10, atol=0.0, reorth
         log.append(Decision(kind, its, lhs, rhs, bool(taken), _dist(lhs, rhs)))
         return taken
 
-    # ---- fg_begin (solver.hip:733-754)
+    def note(*event):
+        if trace is not None:
+            trace.append(event)
+
+    # ---- fg_begin (krylov.hip)
     bnorm = math.sqrt(ar.dot(b, b))
     if not bnorm > 0.0:
         return Result(np.zeros(n), 0, OK, 0.0, log, False, 1.0)
@@ -128,10 +135,11 @@ def fgmres(A, M, b, x0=None, *, restart, max_iters, rtol=1e-10, atol=0.0, reorth
     stalled_cycles, inner_scale, beta_prev, est_at_exit, ended_on_estimate = 0, 1.0, 0.0, 0.0, False
 
     while True:
-        # ---- fg_restart (solver.hip:757-805)
+        # ---- fg_restart (krylov.hip; the verdict: krylov_host.cpp, fg_restart_verdict)
         r = b - A(x)
         beta = math.sqrt(ar.dot(r, r))
         relres = beta / bnorm
+        note("restart", beta)
         if beta != beta:
             status = BREAKDOWN
             break
@@ -154,6 +162,7 @@ def fgmres(A, M, b, x0=None, *, restart, max_iters, rtol=1e-10, atol=0.0, reorth
             inner_scale = max(1e-3, min(inner_scale, 0.5 * est_at_exit / beta))
         beta_prev = beta
         ended_on_estimate = False
+        note("cycle", steps_now, stalled_cycles, inner_scale)
         beta_it, target_it = beta, target
         if rscale is not None:
             r = r * rscale
@@ -171,7 +180,7 @@ def fgmres(A, M, b, x0=None, *, restart, max_iters, rtol=1e-10, atol=0.0, reorth
         precond = chained_precond(A, M, steps_now)
 
         while True:
-            # ---- arnoldi_apply (solver.hip:667-682): M sees the f64 twin of the newest basis vector
+            # ---- arnoldi_apply (krylov.hip): M sees the f64 twin of the newest basis vector
             vj = vcur
             if rscale is not None:
                 z = precond(vj * rinv)
@@ -180,7 +189,7 @@ def fgmres(A, M, b, x0=None, *, restart, max_iters, rtol=1e-10, atol=0.0, reorth
                 z = precond(vj)
                 w = A(z)
             Z.append(z)
-            # ---- arnoldi_orthogonalise (solver.hip:684-705)
+            # ---- arnoldi_orthogonalise (krylov.hip)
             h = np.array([ar.dot(V[i], w) for i in range(j + 1)] + [ar.dot(w, w)])
             w = ar.update(w, V, h)
             nrm2 = ar.dot(w, w)
@@ -206,7 +215,7 @@ def fgmres(A, M, b, x0=None, *, restart, max_iters, rtol=1e-10, atol=0.0, reorth
             vcur, vf = ar.scale_to(w, 1.0 / t if t > 0.0 else 0.0, basis_f32)
             V.append(vf if basis_f32 else vcur)
 
-            # ---- fg_post_step (solver.hip:809-841)
+            # ---- fg_post_step (krylov.hip; krylov_host.cpp, fg_column_step)
             hc = H[j]
             hc[:j + 2] = h
             weak_norm = hc[j + 1] < 0.0
@@ -220,6 +229,7 @@ def fgmres(A, M, b, x0=None, *, restart, max_iters, rtol=1e-10, atol=0.0, reorth
             d = math.hypot(hjj, hj1)
             if not d > 0.0 or d != d:
                 status, breakdown_in_cycle = BREAKDOWN, True          # column j is unusable: keep k = j
+                note("step", h.copy(), its, None, True)
                 break
             cs[j], sn[j] = hjj / d, hj1 / d
             hc[j], hc[j + 1] = d, 0.0
@@ -231,17 +241,21 @@ def fgmres(A, M, b, x0=None, *, restart, max_iters, rtol=1e-10, atol=0.0, reorth
             if decide("estimate", its, est, target_it * inner_scale, est <= target_it * inner_scale) or hj1 == 0.0:
                 ended_on_estimate = True
                 est_at_exit = est * (beta / beta_it)
+                note("step", h.copy(), its, est, True)
                 break
-            if weak_norm or j >= m or its >= max_iters:
+            ends = weak_norm or j >= m or its >= max_iters
+            note("step", h.copy(), its, est, ends)
+            if ends:
                 break
 
-        # ---- fg_end_cycle (solver.hip:844-868)
+        # ---- fg_end_cycle (krylov.hip; krylov_host.cpp, fg_back_substitute)
         k = j
         for i in range(k - 1, -1, -1):
             tt = g[i]
             for c in range(i + 1, k):
                 tt -= H[c][i] * y[c]
             y[i] = tt / H[i][i]
+        note("end", k, y[:k].copy(), cs[:k].copy(), sn[:k].copy(), g[:k + 1].copy(), [H[c][:c + 1].copy() for c in range(k)])
         x = ar.update(x, Z[:k], y, sign=1.0)
         if breakdown_in_cycle:
             r = b - A(x)
@@ -253,7 +267,7 @@ def fgmres(A, M, b, x0=None, *, restart, max_iters, rtol=1e-10, atol=0.0, reorth
 
 
 def bicgstab(A, M, b, x0=None, *, max_iters, rtol=1e-10, atol=0.0, precond_steps=1, arith=None):
-    """Right-preconditioned BiCGStab (solver.hip:893-961), the 1.0001 slack on the final true residual included."""
+    """Right-preconditioned BiCGStab (krylov.hip, bicgstab), the 1.0001 slack on the final true residual included."""
     ar = arith or Arith()
     b = np.asarray(b, np.float64)
     n = b.size

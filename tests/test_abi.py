@@ -98,11 +98,18 @@ def test_no_ablation_kernels_in_the_shipped_library():
 
 def test_kernels_and_cycle_do_not_read_the_environment():
     """Tuning knobs reach the kernels through nkp_tuning, resolved once per nkp_create (csrc/tuning.cpp: nkp_default_tuning);
-    no launcher, cycle, planner or setup routine calls getenv."""
+    no launcher, cycle, planner, setup routine or driver calls getenv: every .hip and .cpp unit of csrc/ but tuning.cpp is read.
+    The one other reader of the environment is named here and held to that one variable: the file communicator's time-out
+    (comm_file.hip, NKP_COMM_TIMEOUT), which belongs to a communicator of tests and tools, not to a solver."""
     csrc = os.path.join(ROOT, "nk_ocn_tracer_jacobian_precond_amd", "csrc")
-    for name in ("spmv.hip", "colblock.hip", "multilevel.hip", "mlsetup.hip", "mltail.hip", "blas1.hip", "dist_plan.cpp", "refactor_api.hip",
-                 "solver.hip", "ml_plan.cpp", "mlcycle.hip", "dense.hip", "refactor.hip", "batch.hip"):
-        assert "getenv" not in open(os.path.join(csrc, name)).read(), name
+    units = sorted(f for f in os.listdir(csrc) if f.endswith((".hip", ".cpp")) and f != "tuning.cpp")
+    assert len(units) >= 30 and {"krylov.hip", "krylov_host.cpp", "batch_solve.hip", "create.hip", "diagop.hip", "valprod_api.hip"} <= set(units)
+    for name in units:
+        text = open(os.path.join(csrc, name)).read()
+        if name == "comm_file.hip":
+            assert text.count("getenv") == text.count('getenv ("NKP_COMM_TIMEOUT")') == 1, name
+        else:
+            assert "getenv" not in text, name
     text = open(os.path.join(csrc, "tuning.cpp")).read()
     body = text[text.index('extern "C" int nkp_default_tuning'):text.index("int resolve_tuning")]
     assert text.count("getenv") == body.count("getenv") > 0

@@ -1,5 +1,6 @@
-"""The Krylov drivers (csrc/solver.hip:650-960) and their vector kernels (csrc/blas1.hip:47-486) step by step against the
-drivers restated in tests/krylov_reference.py, on the shapes of tests/krylov_cases.py.
+"""The Krylov drivers (csrc/krylov.hip: fg_begin, fg_restart, fg_post_step, fg_end_cycle, fgmres, bicgstab) and their vector
+kernels (csrc/blas1.hip:47-486) step by step against the drivers restated in tests/krylov_reference.py, on the shapes of
+tests/krylov_cases.py.
 
 The restatement runs on the host with the solver's own spmv and precond_apply as operators (both pinned elsewhere), so the
 only thing that differs between the two sides is the driver and its vector kernels.  A solve cut at max_iters = k returns x_k,
