@@ -1,6 +1,6 @@
 // Multilevel water-column preconditioner: the V(nu, nu) cycle on the hierarchy ml_setup built (multilevel.hip), for one
 // right-hand side and for K interleaved ones, and the measurement helpers of bench.py and the probes.  Launchers only: the
-// kernels are colblock.hip, spmv.hip, blas1.hip, batch.hip, dense.hip and mltail.hip.
+// kernels are colblock.hip, col_lanes.hip, col_packed.hip, col_gs_fused.hip, spmv.hip, blas1.hip, batch.hip, dense.hip and mltail.hip.
 #include "nkp_dev.h"
 #include "multilevel.h"
 
@@ -137,9 +137,9 @@ int ml_batch_prepare (MlHierarchy &H, int K)
 
 static void column_solves_batch (const MlHierarchy &H, MlLevel &V, int K, int c, const double *rhs, double *x, int accumulate, hipStream_t st)
 {
-   // the packed lane layout has a two-system kernel; every other level takes the wave-per-column kernel (which reads the
-   // f64 factors and rounds them like the f32 layouts store them: same values)
-   if (V.wave_columns || launch_colblock_apply_lanes_batch (K, V.B, V.color_grp[c], V.color_grp[c + 1], rhs, x, accumulate, st) != 0)
+   // the packed lane layout has kernels of its own; every other level takes the wave-per-column kernel (which reads the
+   // f64 factors and rounds them like the f32 layouts store them: same values).  V.B.kern says which (col_plan.cpp)
+   if (launch_colblock_apply_lanes_batch (K, V.B, V.color_grp[c], V.color_grp[c + 1], rhs, x, accumulate, st) != 0)
       launch_colblock_apply_wave_batch (K, V.B, V.color_blk[c], V.color_blk[c + 1], rhs, x, accumulate, H.f32, st);
 }
 

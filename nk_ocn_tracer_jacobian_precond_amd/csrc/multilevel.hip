@@ -64,6 +64,7 @@ int finish_level_columns (MlHierarchy &H, MlLevel &V, int l, const std::vector<i
    V.B.n = nl;
    V.B.nblk = ncol;
    V.B.tune = H.tune;
+   V.B.ml_level = 1;
    if (!upload (&V.B.blk_start, pblk.data (), pblk.size (), &H.device_bytes)) ML_FAIL (-2, "multilevel setup: device allocation failed");
    int *dint = nullptr;
    size_t dummy = 0;
@@ -92,9 +93,9 @@ int finish_level_columns (MlHierarchy &H, MlLevel &V, int l, const std::vector<i
       const int ranges[3] = { 0, ncol0, ncol };
       const int lrc = colblock_build_lane_layout (V.B, pblk.data (), ranges, 2, V.color_grp, &H.device_bytes, st, H.f32, H.fused ? h_prow : nullptr);
       if (lrc != 0) ML_FAIL (-3, "multilevel setup: lane layout of level %d failed (HIP error %d)", l, lrc);
-      V.wave_columns = ncol <= H.tune->col_wave_max && V.B.dropped == 0;
-      // ... and their half sweeps are one launch each (residual of the column's rows + its band solve, gs_wave_kernel)
-      V.wave_fused = V.wave_columns && (H.tune->ml_wave_fused == 1 || (H.tune->ml_wave_fused > 1 && ncol <= H.tune->ml_wave_fused));
+      // few columns: one per wave, and their half sweeps one launch each (residual of the column's rows + its band solve, gs_wave_kernel)
+      V.wave_columns = V.B.kern.wave_columns;
+      V.wave_fused = V.B.kern.wave_fused;
       if (V.wave_fused) {
          if (!upload (&V.B.wave_desc, (const int *) nullptr, (size_t) 4 * (size_t) ncol, &H.device_bytes)) ML_FAIL (-2, "multilevel setup: device allocation failed");
          launch_build_wave_desc (V.L, V.B, st);
@@ -571,6 +572,7 @@ void ml_free (MlHierarchy &H)
       void *ptrs[] = { V.L.rowptr, V.L.colind, V.L.val, V.L.valf, V.B.fac_tf, V.L.rowblk, V.L.codes, V.L.dict, V.L.dict_ptr, V.L.dg_ptr, V.L.dg_key, V.L.dg_voff, V.L.dg_val, V.L.dg_tile, V.L.dg_gptr, V.L.dg_grp, V.B.blk_start, V.B.fac, V.B.grp_b0, V.B.grp_nb, V.B.grp_maxlen, V.B.grp_base, V.B.grp_row0, V.B.col_slot, V.B.fac_t, V.B.gs_rb_ptr, V.B.gs_rb, V.B.wave_desc, V.cmap, V.rptr, V.ridx, V.x, V.x2, V.b, V.r, V.bx, V.bx2, V.bb, V.br };
       for (void *p : ptrs)
          if (p) (void) hipFree (p);
+      delete V.B.grp_cols;
    }
    H.lev.clear ();
    if (H.perm0) (void) hipFree (H.perm0);

@@ -4,13 +4,13 @@
 #include <stdint.h>
 
 #include "../../include/nkp.h"
+#include "col_plan.h"
 #include "tuning.h"
 
 #include <type_traits>
 #include <utility>
 #include <vector>
 
-#define NKP_LDSRES_CH 16         // substitution steps per factor chunk of colblock_apply_ldsres_kernel (group lengths are padded to it)
 #define NKP_WAVE 64
 #define NKP_MAX_K 512           // most basis vectors a fused update kernel takes (LDS coefficients)
 #define NKP_SPMV_LDS_NNZ 2048    // CSR-stream row block: entries staged in LDS ...
@@ -146,6 +146,11 @@ struct ColBlocksDev {
    int *gs_rb = nullptr;       // row-block boundaries (rows), groups back to back
    int *wave_desc = nullptr;   // levels run by gs_wave_kernel: per column {first row, rows, first entry, entries} -- one load instead of two dependent ones
    const nkp_tuning *tune = nullptr;   // kernel selection knobs of the owning solver (NULL: built-in defaults)
+   int ml_level = 0;           // 1: a level of the multilevel cycle (set before the layout is built), which may run one column per wave
+   ColKernel kern;             // the kernel choice col_plan resolved when the layout was built: what the launchers branch on
+   // HOST: the columns of every group's lanes when the groups were formed from sorted columns (else NULL), for the repack of
+   // nkp_refactor.  Owned, shared with clones and freed like the device arrays above
+   std::vector<int> *grp_cols = nullptr;
 };
 
 // ---------------------------------------------------------------- kernel selection (host side)
@@ -282,18 +287,13 @@ __device__ __forceinline__ void wave_band_sweeps (int len, int lane, double (&y)
    });
 }
 
-#define GS_THREADS 256
-#define GS_NNZ 2048
-
 // Build the lane-per-column layout.  ranges: nranges+1 block offsets; a group never straddles a
 // range boundary (Gauss-Seidel colours).  grp_first[r] = first group of range r (nranges+1 out).
 // Returns 0 or a HIP error code cast to int.
 int colblock_build_lane_layout (ColBlocksDev &B, const int *h_blk_start, const int *ranges, int nranges,
                                 int *grp_first, size_t *device_bytes, hipStream_t st, int f32 = 0, const int *h_rowptr = nullptr);
-// new factors (B.fac) into the layout built above, which depends on the pattern only (nkp_refactor).  d_gcols: the
-// columns of every group when the groups were formed from sorted columns (colblock_group_columns gives them; an empty
-// list = groups of consecutive columns, pass NULL)
-int colblock_group_columns (const ColBlocksDev &B, std::vector<int> &gcols);
+// new factors (B.fac) into the layout built above, which depends on the pattern only (nkp_refactor).  d_gcols: a device
+// copy of *B.grp_cols when the groups were formed from sorted columns, else NULL
 int colblock_repack_lane_layout (const ColBlocksDev &B, const int *d_gcols, hipStream_t st);
 // one Gauss-Seidel half sweep over the groups [g0, g1) of one colour in ONE launch: r = b - L x on the groups' rows
 // (x rows < split from xa, the others from xb), column solves, xout_rows = x_rows + z.  Returns non-zero (and does
@@ -415,5 +415,5 @@ void launch_dense_matvec_batch (int K, const double *Minv, const double *x, doub
 void launch_colblock_apply_wave_batch (int K, const ColBlocksDev &B, int b0, int b1, const double *r, double *z, int accumulate, int r32, hipStream_t st);
 void launch_gs_wave_batch (int K, const CsrDev &L, const ColBlocksDev &B, int b0, int b1, const double *xa, const double *xb, int split, const double *b, double *xout,
                            int r32, hipStream_t st);
-// groups [g0, g1) with the packed lane layout (colblock.hip); non-zero = layout not served, use the wave kernel
+// groups [g0, g1) with the packed lane layout (col_packed.hip); non-zero = the level takes the wave kernel (B.kern.batch4 / batch_other)
 int launch_colblock_apply_lanes_batch (int K, const ColBlocksDev &B, int g0, int g1, const double *r, double *z, int accumulate, hipStream_t st);

@@ -342,11 +342,7 @@ int rf_build_maps (RefactorWork &W, const MlHierarchy &H, const CsrDev &A, hipSt
    for (int l = 0; l < nlev; l++) {
       const MlLevel &V = H.lev[l];
       if (!dalloc (W, &W.lev[l].nv, (size_t) V.L.nnz)) return -2;
-      if (V.B.fac) {
-         std::vector<int> gc;
-         if (colblock_group_columns (V.B, gc)) return -3;
-         if (!gc.empty () && !dupload (W, &W.lev[l].gcols, gc)) return -2;
-      }
+      if (V.B.fac && V.B.grp_cols && !V.B.grp_cols->empty () && !dupload (W, &W.lev[l].gcols, *V.B.grp_cols)) return -2;
    }
    W.last_rowptr.swap (rp[nlev - 1]);
    W.last_colind.swap (ci[nlev - 1]);
@@ -453,9 +449,7 @@ int rf_prepare_inverse (RefactorWork &W, const MlHierarchy &H, hipStream_t st, c
 int rf_column_factor (RefactorWork &W, const CsrDev &A, ColBlocksDev &B, hipStream_t st, char *err, size_t errlen)
 {
    if (!W.col_gcols_done) {
-      std::vector<int> gc;
-      if (colblock_group_columns (B, gc)) RF_FAIL (-3, "nkp_refactor: lane groups of the column blocks could not be read");
-      if (!gc.empty () && !dupload (W, &W.col_gcols, gc)) RF_FAIL (-2, "nkp_refactor: device allocation failed");
+      if (B.grp_cols && !B.grp_cols->empty () && !dupload (W, &W.col_gcols, *B.grp_cols)) RF_FAIL (-2, "nkp_refactor: device allocation failed");
       W.col_gcols_done = true;
    }
    (void) hipMemsetAsync (W.dcnt + 4, 0, 2 * sizeof (int), st);

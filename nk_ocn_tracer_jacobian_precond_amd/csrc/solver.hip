@@ -48,6 +48,7 @@ void solver_free (nkp_solver *s)
                     s->x, s->b, s->t1, s->t2, s->p1, s->p2, s->partial, s->dscal, s->dint, s->rscale, s->rinv, s->eqtmp };
    for (void *p : ptrs)
       if (p) (void) hipFree (p);
+   delete s->B.grp_cols;
    ml_free (s->ml);
    if (s->rf) { rf_free (*s->rf); delete s->rf; }
    if (s->dplan) { rf_dist_free (*s->dplan); delete s->dplan; }

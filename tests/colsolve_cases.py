@@ -1,5 +1,6 @@
-"""Matrices, kernel families and the kernel selection rule of the water-column band solves (csrc/colblock.hip, the column
-kernels of csrc/batch.hip and csrc/mltail.hip) -- TEST INFRASTRUCTURE.
+"""Matrices, kernel families and the kernel selection rule of the water-column band solves (csrc/colblock.hip and the lane
+families csrc/col_lanes.hip, col_packed.hip, col_gs_fused.hip; the column kernels of csrc/batch.hip and csrc/mltail.hip) -- TEST
+INFRASTRUCTURE.
 
 Matrices.  widen(p, dists, seed) adds in-column entries at k +- d for every d in dists to a synth.generate problem: magnitude
 0.02 |a_rr| U(0.5, 1), random sign, and the diagonal grows by the row sum of the added magnitudes with its own sign, so no
@@ -15,8 +16,10 @@ Shapes.  The two grids of tests/test_gpu_colsolve_packed.py: 12 x 10, seed 36 (3
 Families.  FAMILIES is one nkp_tuning dict per kernel.  Each sets col_stream_min = 1 and ml_coarsest_rows = 40, so that every
 level but the last (which is solved densely) runs the kernel under test.
 
-Selection rule.  expected_kernel restates colblock_build_lane_layout, finish_level_columns, launch_colblock_apply_lanes,
-launch_colblock_apply_lanes_batch and column_solves_batch: which layout a level gets and which instantiation serves it,
+Selection rule.  expected_kernel restates col_plan (csrc/col_plan.cpp), the one place where the library decides which layout a
+level gets and which instantiation serves it -- launch_colblock_apply_lanes, launch_colblock_apply_lanes_batch,
+column_solves_batch and finish_level_columns branch on its ColKernel.  tests/test_col_plan.py holds the two against each other
+on the CPU; the GPU tests read the outcome through nkp_ml_level_array (.., "col_kernel").
 
   wave         only on a level without dropped entries (V.wave_columns)
   stream       only with columns of at most 64 rows
@@ -25,10 +28,6 @@ launch_colblock_apply_lanes_batch and column_solves_batch: which layout a level 
   col_group    halved while (2 P + 2) * pad8 (max_len) * gw doubles exceed 56 KB
   lanes        <P, 64, ., 1> up to 64 rows, <P, 80, ., 3> up to 80 rows with col_w3, else <P, 128, ., 1>
   LDS          the dynamic LDS of the lane kernels; above 48 KB the setup opts in (hipFuncSetAttribute)
-
-One instantiation cannot be selected at all: launch_colblock_apply_lanes asks for colblock_apply_stream_kernel<P, 96, ...> when
-a streamed level has columns of more than 64 rows, but colblock_build_lane_layout sets B.stream only with at most 64 rows.  The
-kernel is compiled and opted in, never launched; it is not in INSTANTIATIONS and no case can reach it.
 
 CASES_CYCLE / CASES_BATCH / CASES_REFACTOR / CASES_JACOBI are the case lists of tests/test_gpu_colsolve_families.py as data;
 tests/test_colsolve_cases.py asserts from them and expected_kernel that every instantiation of INSTANTIATIONS is selected on
@@ -166,6 +165,7 @@ TUNING_DEFAULTS = dict(col_ldsres=2, col_stream=1, col_stream_min=-1, col_stream
                        ml_wave_fused=1, ml_tail_rows=0)
 LDSRES_CH = 16
 GS_NNZ = 2048
+GS_THREADS = 256
 COL_KERNEL_FIELDS = ("wave_columns", "wave_fused", "stream", "ldsres", "gw", "P", "dropped", "max_len", "gs_ok", "ngrp", "lds_doubles")
 
 
@@ -185,7 +185,7 @@ def expected_kernel(family, f32, P, dropped, max_len, ncols, colour_lens=None, m
     fused_setup = multilevel and T["ml_fused"] != 0
     tail = multilevel and T["ml_tail_rows"] > 0
     ft = "f32" if f32 else "f64"
-    # ---- colblock_build_lane_layout
+    # ---- col_plan: the layout
     gw = T["col_group"] if T["col_group"] in (8, 16, 32, 64) else 8
     on = T["col_stream"] != 0
     env_min = T["col_stream_min"] >= 0
@@ -240,12 +240,12 @@ def expected_kernel(family, f32, P, dropped, max_len, ncols, colour_lens=None, m
     elif lds is not None:
         gs_ok = int(gs_doubles * 8 <= 64 * 1024)
     out["gs_ok"] = gs_ok
-    # ---- finish_level_columns
+    # ---- col_plan: one column per wave (levels of the multilevel cycle)
     wave = multilevel and ncols <= T["col_wave_max"] and not dropped
     wf = T["ml_wave_fused"]
     wave_fused = wave and (wf == 1 or (wf > 1 and ncols <= wf))
     out.update(wave_columns=int(wave), wave_fused=int(wave_fused))
-    # ---- launch_colblock_apply_lanes
+    # ---- col_plan: the instantiation launch_colblock_apply_lanes takes
     rpl = 1 if max_len <= 64 else 2
     if ldsres == 2:
         lanes = ("ldspack", P, 4 if max_len <= 64 else 5)
@@ -278,7 +278,7 @@ def expected_kernel(family, f32, P, dropped, max_len, ncols, colour_lens=None, m
         kernels = {lanes}
     out["kernels"] = {k for k in kernels if k is not None}
 
-    # ---- column_solves_batch / launch_colblock_apply_lanes_batch (the batched cycle has neither fused sweep nor tail)
+    # ---- col_plan: batch4 / batch_other (the batched cycle has neither fused sweep nor tail)
     def batch(K):
         assert K in (2, 4, 8)
         if wave_fused:
@@ -288,6 +288,67 @@ def expected_kernel(family, f32, P, dropped, max_len, ncols, colour_lens=None, m
         return {("ldspack4" if K % 4 == 0 else "ldspack2", P, 4 if max_len <= 64 else 5)}
     out["batch"] = batch
     return out
+
+
+def check_row_blocks(rowptr, r0, r1, starts):
+    """The row blocks of the fused sweep (gs_fused_kernel) over the rows [r0, r1) of one group, given by their first rows:
+    consecutive and covering, at most GS_THREADS rows and GS_NNZ entries each, and each as long as both limits allow."""
+    rowptr = np.asarray(rowptr, np.int64)
+    bounds = list(starts) + [r1]
+    assert bounds[0] == r0 and all(a < b for a, b in zip(bounds[:-1], bounds[1:])), (r0, r1, bounds)
+    for a, b in zip(bounds[:-1], bounds[1:]):
+        assert b - a <= GS_THREADS and rowptr[b] - rowptr[a] <= GS_NNZ, (a, b)
+        assert b == r1 or b - a == GS_THREADS or rowptr[b + 1] - rowptr[a] > GS_NNZ, (a, b)      # greedy-maximal
+
+
+# Levels worked by hand: (family or tuning dict, f32, P, dropped, max_len, multilevel, field, value) on 67 columns; the field
+# ("batch", K) is batch (K).  tests/test_colsolve_cases.py asserts them of expected_kernel, tests/test_col_plan.py of col_plan.
+HAND_WORKED = [
+    # wave only without dropped entries
+    ("wave2", 1, 4, 0, 60, True, "kernels", {("wave", 4, 1, "f32")}),
+    ("wave_fused", 0, 2, 0, 128, True, "kernels", {("gs_wave", 2, 2, "f64"), ("wave", 2, 2, "f64")}),
+    ("wave2", 1, 4, 1, 60, True, "wave_columns", 0),
+    ("wave2", 1, 4, 1, 60, True, "kernels", {("ldspack", 4, 4)}),       # ... falls to the default layout: packed with f32
+    # stream only up to 64 rows
+    ("stream32", 0, 2, 0, 64, True, "kernels", {("stream", 2, 32, "f64")}),
+    ("stream64", 1, 1, 0, 64, True, "kernels", {("stream", 1, 64, "f32")}),
+    ("stream32", 0, 2, 0, 65, True, "kernels", {("lanes", 2, 80, "f64")}),
+    ("stream32", 0, 2, 0, 65, True, "gw", 8),
+    # packed only with f32 storage, at most 80 rows, no fused sweep and no tail
+    ("packed_sorted", 1, 2, 0, 80, True, "kernels", {("ldspack", 2, 5)}),
+    ("packed_sorted", 1, 2, 0, 81, True, "kernels", {("ldsres", 2, "f32", 0)}),
+    ("packed_sorted", 0, 2, 0, 80, True, "kernels", {("ldsres", 2, "f64", 0)}),
+    (dict(FAMILIES["packed_sorted"], ml_fused=1), 1, 2, 0, 80, True, "ldsres", 1),
+    (dict(FAMILIES["packed_sorted"], ml_tail_rows=16000), 1, 2, 0, 80, True, "ldsres", 1),
+    # the pipelined kernel
+    ("lanes_pipe", 1, 2, 0, 64, True, "kernels", {("lanes_pipe", 2)}),
+    ("lanes_pipe", 1, 4, 0, 64, True, "kernels", {("lanes", 4, 64, "f32")}),
+    ("lanes_pipe", 0, 2, 0, 64, True, "kernels", {("lanes", 2, 64, "f64")}),
+    ("lanes_pipe", 1, 2, 0, 65, True, "kernels", {("lanes", 2, 80, "f32")}),
+    # col_group halves against 56 KB: (2 P + 2) * pad8 (max_len) * gw * 8 bytes
+    ("lanes64", 0, 1, 0, 10, True, "gw", 64),
+    ("lanes64", 0, 1, 0, 60, True, "gw", 16),
+    ("lanes64", 0, 2, 0, 60, True, "gw", 16),
+    ("lanes64", 0, 4, 0, 60, True, "gw", 8),
+    ("lanes64", 0, 4, 0, 128, True, "gw", 8),
+    ("lanes32", 0, 1, 0, 56, True, "gw", 32),
+    ("lanes32", 0, 1, 0, 57, True, "gw", 16),                            # 4 * 56 * 32 * 8 = 57344 = 56 KB
+    # the lanes family's instantiations
+    ("lanes8", 0, 4, 0, 80, True, "kernels", {("lanes", 4, 80, "f64")}),
+    ("lanes8_now3", 0, 4, 0, 80, True, "kernels", {("lanes", 4, 128, "f64")}),
+    ("lanes8", 1, 1, 0, 81, True, "kernels", {("lanes", 1, 128, "f32")}),
+    # dynamic LDS: f64 factors of 9 diagonals x 128 rows x 8 columns alone are 72 KB
+    ("lanes8", 0, 4, 0, 128, True, "lds_over_48k", True),
+    ("lanes8", 1, 1, 0, 60, True, "lds_over_48k", False),
+    # column-Jacobi: never wave, fused or tail
+    ("wave2", 0, 4, 0, 60, False, "wave_columns", 0),
+    # the batched cycle
+    ("packed_sorted", 1, 4, 0, 80, True, ("batch", 2), {("ldspack2", 4, 5)}),
+    ("packed_sorted", 1, 4, 0, 64, True, ("batch", 8), {("ldspack4", 4, 4)}),
+    ("packed_sorted", 1, 4, 1, 81, True, ("batch", 4), {("wave_batch", 4, 2)}),
+    ("wave_fused", 1, 4, 1, 60, True, ("batch", 4), {("ldspack4", 4, 4)}),
+]
+HAND_WORKED_NCOLS = 67
 
 
 def batch_groups(width, rhs_batch=1):
@@ -303,7 +364,7 @@ def batch_groups(width, rhs_batch=1):
 
 
 def all_instantiations():
-    """Every instantiation a launcher can select (colblock_apply_stream_kernel<P, 96, ...> cannot: see the module docstring)."""
+    """Every instantiation a launcher can select."""
     Ps, fts = (1, 2, 4), ("f32", "f64")
     inst = set()
     for P in Ps:

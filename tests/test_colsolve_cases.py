@@ -89,45 +89,14 @@ def test_shapes():
 
 def test_selection_rule_on_hand_worked_levels():
     e = cc.expected_kernel
-    # wave only without dropped entries
-    assert e("wave2", 1, 4, 0, 60, 67)["kernels"] == {("wave", 4, 1, "f32")}
-    assert e("wave_fused", 0, 2, 0, 128, 67)["kernels"] == {("gs_wave", 2, 2, "f64"), ("wave", 2, 2, "f64")}
-    assert e("wave2", 1, 4, 1, 60, 67)["wave_columns"] == 0
-    assert e("wave2", 1, 4, 1, 60, 67)["kernels"] == {("ldspack", 4, 4)}       # ... falls to the default layout: packed with f32
-    # stream only up to 64 rows
-    assert e("stream32", 0, 2, 0, 64, 67)["kernels"] == {("stream", 2, 32, "f64")}
-    assert e("stream64", 1, 1, 0, 64, 67)["kernels"] == {("stream", 1, 64, "f32")}
-    assert e("stream32", 0, 2, 0, 65, 67)["kernels"] == {("lanes", 2, 80, "f64")} and e("stream32", 0, 2, 0, 65, 67)["gw"] == 8
-    # packed only with f32 storage, at most 80 rows, no fused sweep and no tail
-    assert e("packed_sorted", 1, 2, 0, 80, 67)["kernels"] == {("ldspack", 2, 5)}
-    assert e("packed_sorted", 1, 2, 0, 81, 67)["kernels"] == {("ldsres", 2, "f32", 0)}
-    assert e("packed_sorted", 0, 2, 0, 80, 67)["kernels"] == {("ldsres", 2, "f64", 0)}
-    assert e(dict(cc.FAMILIES["packed_sorted"], ml_fused=1), 1, 2, 0, 80, 67)["ldsres"] == 1
-    assert e(dict(cc.FAMILIES["packed_sorted"], ml_tail_rows=16000), 1, 2, 0, 80, 67)["ldsres"] == 1
-    # the pipelined kernel
-    assert e("lanes_pipe", 1, 2, 0, 64, 67)["kernels"] == {("lanes_pipe", 2)}
-    assert e("lanes_pipe", 1, 4, 0, 64, 67)["kernels"] == {("lanes", 4, 64, "f32")}
-    assert e("lanes_pipe", 0, 2, 0, 64, 67)["kernels"] == {("lanes", 2, 64, "f64")}
-    assert e("lanes_pipe", 1, 2, 0, 65, 67)["kernels"] == {("lanes", 2, 80, "f32")}
-    # col_group halves against 56 KB: (2 P + 2) * pad8 (max_len) * gw * 8 bytes
-    assert [e("lanes64", 0, P, 0, ml, 67)["gw"] for P, ml in ((1, 10), (1, 60), (2, 60), (4, 60), (4, 128))] == [64, 16, 16, 8, 8]
-    assert e("lanes32", 0, 1, 0, 56, 67)["gw"] == 32 and e("lanes32", 0, 1, 0, 57, 67)["gw"] == 16      # 4 * 56 * 32 * 8 = 57344 = 56 KB
-    # the lanes family's instantiations
-    assert e("lanes8", 0, 4, 0, 80, 67)["kernels"] == {("lanes", 4, 80, "f64")}
-    assert e("lanes8_now3", 0, 4, 0, 80, 67)["kernels"] == {("lanes", 4, 128, "f64")}
-    assert e("lanes8", 1, 1, 0, 81, 67)["kernels"] == {("lanes", 1, 128, "f32")}
-    # dynamic LDS: f64 factors of 9 diagonals x 128 rows x 8 columns alone are 72 KB
-    assert e("lanes8", 0, 4, 0, 128, 67)["lds_over_48k"] is True and e("lanes8", 1, 1, 0, 60, 67)["lds_over_48k"] is False
+    for family, f32, P, dropped, max_len, multilevel, field, want in cc.HAND_WORKED:
+        got = e(family, f32, P, dropped, max_len, cc.HAND_WORKED_NCOLS, multilevel=multilevel)
+        value = got["batch"](field[1]) if isinstance(field, tuple) else got[field]
+        assert value == want and type(value) is type(want), (family, f32, P, dropped, max_len, field, value, want)
+    assert len(cc.HAND_WORKED) == 34
     lens = [np.full(33, 128), np.full(34, 128)]
     got = e("lanes8", 0, 2, 0, 128, 67, lens)
     assert got["lds_doubles"] == 1024 + 32 + 2 + 5 * 128 * 8 and got["lds_over_48k"] and got["ngrp"] == 10
-    # column-Jacobi: never wave, fused or tail
-    assert e("wave2", 0, 4, 0, 60, 67, multilevel=False)["wave_columns"] == 0
-    # the batched cycle
-    assert e("packed_sorted", 1, 4, 0, 80, 67)["batch"](2) == {("ldspack2", 4, 5)}
-    assert e("packed_sorted", 1, 4, 0, 64, 67)["batch"](8) == {("ldspack4", 4, 4)}
-    assert e("packed_sorted", 1, 4, 1, 81, 67)["batch"](4) == {("wave_batch", 4, 2)}
-    assert e("wave_fused", 1, 4, 1, 60, 67)["batch"](4) == {("ldspack4", 4, 4)}
     assert cc.batch_groups(5) == [4] and cc.batch_groups(3) == [4] and cc.batch_groups(6, 8) == [8] and cc.batch_groups(2) == [2]
 
 

@@ -2,7 +2,8 @@
 
 The matrices, the kernel families (one nkp_tuning dict per kernel), the restated selection rule (expected_kernel) and the case
 lists are data in tests/colsolve_cases.py; tests/test_colsolve_cases.py checks their claims without a GPU, among them that the
-lists below reach every instantiation a launcher can select.  Which kernel ran is read back (nkp_ml_level_array "col_kernel",
+lists below reach every instantiation a launcher can select; tests/test_col_plan.py holds expected_kernel against the
+library's own rule (col_plan, csrc/col_plan.cpp) on the CPU.  Which kernel ran is read back (nkp_ml_level_array "col_kernel",
 nkp_get_int "col_*") and compared with expected_kernel on every level, so that a knob combination that silently selects the
 default kernel fails here, and every designed fallback (wave with dropped bands, packed at 81 rows or with f64 storage, stream
 at 65 rows, the pipelined kernel at P = 4, gs_fused without room in LDS) is asserted as one.
@@ -26,7 +27,7 @@ No tolerance was fitted to the device's output.
 Found by (b): gs_fused_kernel on the streamed and the LDS-resident layouts (32 columns per group) gave results unrelated to the
 other families.  The kernel stages the group's factors in LDS under every layout, but the setup sized its dynamic LDS from the
 lane kernel's need, which has no factor area on those two layouts: the factors went past the end of the allocation.  Fixed in
-colblock_build_lane_layout (gs_lds_bytes counts the factors, and gs_ok falls when they do not fit 64 KB).
+the layout rule, now col_plan of csrc/col_plan.cpp (gs_lds_bytes counts the factors, and gs_ok falls when they do not fit 64 KB).
 
 Measured on an MI355X: ||z - z_ref|| / ||z_ref|| of the lanes8 family, its bound and their ratio, and the measured in-column
 half bandwidth of every level with column blocks (level 0 first; 6 = entries beyond the band dropped, on every level of those
