@@ -3,7 +3,7 @@ implementation (csrc/ml_plan.cpp) on small grids.  TEST INFRASTRUCTURE: slow, se
 
 Same rules, written from the description in DESIGN.md section 2, not from the C++:
   * low-order twin: L = A + D - diag(rowsum D), D_ij = max(0, -a_ij, -a_ji) for i, j in different water columns
-  * aggregates: groups of 2 x 2 columns in (i, j) per tracer (4 x 4 from level `big_from` down), levels k kept; inside a
+  * aggregates: groups of 2 x 2 columns in (i, j) per tracer (4 x 4 from level `big_from` down, 8 x 8 from `huge_from`), levels k kept; inside a
     group the cells of one depth form one coarse cell per laterally CONNECTED set (`split_groups` below: connected
     sets, same-depth sets of <= `pocket` cells merged across groups, sets threaded through depth into coarse columns
     by largest overlap, leaf stubs absorbed into the cell they hang from); piecewise-constant P, Galerkin
@@ -36,15 +36,21 @@ class Level:
     pass
 
 
-def split_groups(L, I, J, ck, colid, pocket=4, theta=0.0, tau=0.01):
+def split_groups(L, I, J, ck, colid, pocket=4, theta=0.0, tau=0.01, tracer=None, info=None):
     """Coarse cells of one coarsening step.  I, J: group coordinates of every row; ck: depth of every row; colid: column
-    of every row (rows of a column are contiguous and ordered by depth).  Returns (coarse row of every fine row, and per
-    coarse row: I, J, depth, coarse column)."""
+    of every row (rows of a column are contiguous and ordered by depth); tracer: tracer of every row of a coupled system
+    (None = one tracer) -- columns of different tracers are never aggregated together: they share no group, and a coupling
+    between two tracers counts neither as a lateral connection nor towards a stub's anchor or how strongly it is felt.
+    Returns (coarse row of every fine row, and per coarse row: I, J, depth, coarse column).  A dict passed as `info` receives
+    "leaf_stubs" (columns absorbed as leaf stubs), "anchor_ties" (those of them whose strongest coupling is attained by
+    entries that end in different coarse cells, so that the tie rule decided where they went), "pockets_merged" (same-depth sets of 2 to `pocket` cells that were merged
+    across groups) and "tracer" (tracer of every coarse row)."""
     from scipy.sparse.csgraph import connected_components
     n = L.shape[0]
-    grp = J.astype(np.int64) * (int(I.max()) + 2) + I
+    tr = np.zeros(n, np.int64) if tracer is None else np.asarray(tracer, np.int64)
+    grp = (tr * (int(J.max()) + 2) + J) * (int(I.max()) + 2) + I
     C = L.tocoo()
-    inter = colid[C.row] != colid[C.col]
+    inter = (colid[C.row] != colid[C.col]) & (tr[C.row] == tr[C.col])
     ir, ic, iv = C.row[inter], C.col[inter], abs(C.data[inter])
     rowmax = np.zeros(n)
     np.maximum.at(rowmax, ir, iv)
@@ -80,8 +86,10 @@ def split_groups(L, I, J, ck, colid, pocket=4, theta=0.0, tau=0.01):
         _, c0 = connected_components(sp.csr_matrix((np.ones(r.size), (r, t)), shape=(n, n)), directed=False)
         small = np.bincount(c0)[c0] <= pocket
         keep = same | small[r]
+        npockets = np.unique(c0[r[small[r] & ~same]]).size       # a set of one cell has no edge, so these have 2 .. pocket cells
     else:
         keep = same
+        npockets = 0
     _, comp = connected_components(sp.csr_matrix((np.ones(keep.sum()), (r[keep], t[keep])), shape=(n, n)), directed=False)
     _, firsts, comp = np.unique(comp, return_index=True, return_inverse=True)
     comp = np.argsort(np.argsort(firsts))[comp]        # sets numbered by their lowest row
@@ -117,10 +125,23 @@ def split_groups(L, I, J, ck, colid, pocket=4, theta=0.0, tau=0.01):
     gI[ccol[comp[keepr]]] = I[keepr]; gJ[ccol[comp[keepr]]] = J[keepr]
     colraw = uk // 4096
     _, colid2 = np.unique(colraw, return_inverse=True)
+    if info is not None:
+        tr2 = np.zeros(uk.size, np.int64)
+        tr2[inv] = tr
+        best = np.zeros(ncol)
+        np.maximum.at(best, colid[ir], iv)
+        tied = leaf[colid[ir]] & (iv == best[colid[ir]])          # the strongest couplings of the absorbed stubs ...
+        ends = np.unique(colid[ir][tied] * np.int64(uk.size) + inv[ic[tied]])
+        attained = np.bincount(ends // uk.size, minlength=ncol)    # ... and in how many coarse cells they end
+        info.update(leaf_stubs=int(leaf.sum()), anchor_ties=int((leaf & (attained > 1)).sum()), pockets_merged=int(npockets), tracer=tr2)
     return inv, gI[colraw], gJ[colraw], uk % 4096, colid2
 
 
-def build(A, ci, cj, ck, colid, nu=3, coarsest_rows=8000, big_from=3, max_levels=12, split=True):
+def build(A, ci, cj, ck, colid, nu=3, coarsest_rows=8000, big_from=3, max_levels=12, split=True, pocket=4, theta=0.0, tau=0.01,
+          huge_from=-1, tracer=None):
+    """The hierarchy.  big_from / huge_from: first level coarsened in 4 x 4 / 8 x 8 groups (-1 = never); pocket, theta, tau: see
+    split_groups; tracer: tracer of every row of a coupled system.  Every level that was coarsened records the counts of its
+    step in lv.counts (leaf_stubs, anchor_ties, pockets_merged)."""
     levels = []
     L = low_order(A, colid)
     lvl = 0
@@ -141,10 +162,11 @@ def build(A, ci, cj, ck, colid, nu=3, coarsest_rows=8000, big_from=3, max_levels
         levels.append(lv)
         if len(levels) >= max_levels or lv.n <= coarsest_rows or ncol <= 4:
             break
-        sh = 2 if (big_from >= 0 and lvl >= big_from) else 1
+        sh = 3 if (huge_from >= 0 and lvl >= huge_from) else 2 if (big_from >= 0 and lvl >= big_from) else 1
         I, J = ci >> sh, cj >> sh
+        info = {}
         if split:
-            inv, ci2, cj2, ck2, colid2 = split_groups(lv.A, I, J, ck, colid)
+            inv, ci2, cj2, ck2, colid2 = split_groups(lv.A, I, J, ck, colid, pocket, theta, tau, tracer, info)
             ncoarse = int(inv.max()) + 1
         else:
             key = (J.astype(np.int64) * (int(I.max()) + 2) + I) * 4096 + ck
@@ -158,6 +180,9 @@ def build(A, ci, cj, ck, colid, nu=3, coarsest_rows=8000, big_from=3, max_levels
             break
         lv.P = sp.csr_matrix((np.ones(lv.n), (np.arange(lv.n), inv)), shape=(lv.n, ncoarse))
         lv.cmap, lv.coarse_colid = inv, colid2
+        lv.counts = {what: info.get(what, 0) for what in ("leaf_stubs", "anchor_ties", "pockets_merged")}
+        if tracer is not None and split:
+            tracer = info["tracer"]
         L = (lv.P.T @ lv.A @ lv.P).tocsr()
         L.eliminate_zeros()
         ci, cj, ck, colid = ci2, cj2, ck2, colid2
