@@ -143,9 +143,10 @@ typedef struct nkp_tuning {
                                 application) instead of riding on the SpMV halo.  No effect without dist_ras, grid positions or a lateral
                                 cut (a tracer partition has no overlap) */
    int ml_diag;              /* NKP_ML_DIAG (32): level operators also stored as per-column diagonals, which the residual rows of the
-                                two-kernel half sweeps and the residual before the restriction then read instead of CSR (no per-entry
-                                column index; same bits).  N > 0 = a level gets them if no water column needs more than N diagonals
-                                and the padding stays within 1.5 x its entries, else it stays on CSR; 0 = off */
+                                two-kernel half sweeps, the wave-fused half sweeps of a level whose columns have at most 64 rows and
+                                the residual before the restriction then read instead of CSR (no per-entry column index; same bits).
+                                N > 0 = a level gets them if no water column needs more than N diagonals and the padding stays
+                                within 1.5 x its entries, else it stays on CSR; 0 = off */
    int spmv_diag;            /* NKP_SPMV_DIAG (32): the solver's own matrix A also stored as per-column diagonals (f64 values), which
                                 y = A x and y = b - A x of nkp_spmv, the Krylov drivers and the chained cycles then read instead of
                                 CSR.  Same meaning as ml_diag: N > 0 = A gets them if no water column of the caller's blk_start
@@ -685,7 +686,9 @@ int nkp_dist_plan_host (int64_t m_loc, int64_t nnz_loc, const int32_t *rowptr_lo
  * key_s + kl, 0 where it has none; "dg_gptr" (int32, columns + 1) / "dg_grp" (int32 pairs): the groups of consecutive keys the
  * residual kernel loads x for once -- column c has the groups dg_gptr[c] .. dg_gptr[c + 1], in slot order, group g with the first
  * key dg_grp[2 g] and dg_grp[2 g + 1] = s0 | m << 16, its first slot in the column and its keys (m <= 5 and m <= 64 - rows + 1,
- * rows = ceil (len / ceil (len / 64)), the column's tallest tile).  All in the level's colour-major row order. */
+ * rows = ceil (len / ceil (len / 64)), the column's tallest tile); "wave_diag" (int32, 1 entry, a host value): 1 where the level's
+ * wave-fused half sweeps read these diagonals (gs_wave_diag_kernel), 0 where they read CSR or the level is not wave-fused.  All in
+ * the level's colour-major row order. */
 int64_t nkp_ml_level_array (nkp_solver *s, int level, const char *what, void *dst, int64_t capacity_bytes);
 
 /* The same for the per-column diagonals of the solver's own matrix A (tuning spmv_diag), in the row order and with the water

@@ -1,7 +1,8 @@
 // Operators as per-column diagonals (CsrDev::dg_*, nkp_dev.h): the residual rows of the Gauss-Seidel half sweeps and the full
-// residual before the restriction on the level operators (f32 values), and the solver's own products with A (f64 values,
-// tuning spmv_diag), without a per-entry column index.  One kernel text serves both value types and both y = L x and
-// y = b - L x.
+// residual before the restriction on the level operators (f32 values), the wave-fused half sweeps of the small levels
+// (gs_wave_diag_kernel: residual rows + band solve per wave), and the solver's own products with A (f64 values, tuning
+// spmv_diag), without a per-entry column index.  One residual text serves both value types, y = L x and y = b - L x, and x
+// from one buffer or from two.
 //
 // Rows of a water column are contiguous and depth-ordered on every level.  For a row at position kl of its column and an
 // entry in column j, key = j - kl is the same for every row of the column that couples to the same neighbour column at the
@@ -143,9 +144,11 @@ __device__ __forceinline__ void dg_sums (const VT (&v)[DG_RUN_MAX], int m, doubl
       if (m > U + 1) dg_sums<U + 1> (v, m, dg_lane_up (w), acc);
 }
 
-template <int G, class VT>
+// TWO: the window of x comes from two buffers, position idx < split from x and the others from xb, chosen per lane by the
+// clamped index (the half sweeps of gs_wave_diag_kernel below, which must not see their own colour's new values).
+template <int G, class VT, bool TWO>
 __device__ __forceinline__ void dg_step (const DgGroup *__restrict__ grp, const VT *__restrict__ val, const double *__restrict__ x, int len, int kl,
-                                         int base, int n, double &acc)
+                                         int base, int n, double &acc, const double *__restrict__ xb, int split)
 {
    VT v[G][DG_RUN_MAX];
    double w[G];
@@ -156,11 +159,34 @@ __device__ __forceinline__ void dg_step (const DgGroup *__restrict__ grp, const 
 #pragma unroll
    for (int g = 0; g < G; g++) {
       m[g] = R[g].slots >> 16;
-      w[g] = x[min (max (R[g].key0 + base, 0), n - 1)];
+      const int idx = min (max (R[g].key0 + base, 0), n - 1);
+      if constexpr (TWO) w[g] = idx < split ? x[idx] : xb[idx];
+      else w[g] = x[idx];
       dg_vals<0> (val + (size_t) (R[g].slots & 0xffff) * len + kl, len, m[g], v[g]);
    }
 #pragma unroll
    for (int g = 0; g < G; g++) dg_sums<0> (v[g], m[g], w[g], acc);
+}
+
+// (L x) of the row a lane owns in tile T (lr = its row inside the tile, clamped to the tile's last row): all groups of the column
+template <class VT, bool TWO>
+__device__ __forceinline__ double dg_row_sum (const DgTile &T, const DgGroup *__restrict__ dg_grp, const VT *__restrict__ dg_val, int lane, int lr,
+                                              const double *__restrict__ x, int n, const double *__restrict__ xb = nullptr, int split = 0)
+{
+   const int kl = T.kl0 + lr;
+   const int base = T.kl0 + lane;
+   const DgGroup *__restrict__ grp = dg_grp + T.g0;
+   const VT *__restrict__ val = dg_val + T.voff;
+   double acc = 0.0;
+   int g = 0;
+   for (; g + DG_GROUPS <= T.ng; g += DG_GROUPS) dg_step<DG_GROUPS, VT, TWO> (grp + g, val, x, T.len, kl, base, n, acc, xb, split);
+   static_assert (DG_GROUPS == 3, "one case per length of the last step");
+   switch (T.ng - g) {
+      case 1: dg_step<1, VT, TWO> (grp + g, val, x, T.len, kl, base, n, acc, xb, split); break;
+      case 2: dg_step<2, VT, TWO> (grp + g, val, x, T.len, kl, base, n, acc, xb, split); break;
+      default: break;
+   }
+   return acc;
 }
 
 template <class VT, int MODE>
@@ -173,22 +199,52 @@ void diag_residual_kernel (const DgTile *__restrict__ tile, int ntile, const DgG
    const DgTile T = tile[t];
    const int lane = threadIdx.x & (NKP_WAVE - 1);
    const int lr = min (lane, T.rows - 1);
-   const int kl = T.kl0 + lr;
-   const int base = T.kl0 + lane;
    double bv = 0.0;
    if constexpr (MODE == 1) bv = b[T.row0 + lr];
-   const DgGroup *__restrict__ grp = dg_grp + T.g0;
-   const VT *__restrict__ val = dg_val + T.voff;
-   double acc = 0.0;
-   int g = 0;
-   for (; g + DG_GROUPS <= T.ng; g += DG_GROUPS) dg_step<DG_GROUPS> (grp + g, val, x, T.len, kl, base, n, acc);
-   static_assert (DG_GROUPS == 3, "one case per length of the last step");
-   switch (T.ng - g) {
-      case 1: dg_step<1> (grp + g, val, x, T.len, kl, base, n, acc); break;
-      case 2: dg_step<2> (grp + g, val, x, T.len, kl, base, n, acc); break;
-      default: break;
-   }
+   const double acc = dg_row_sum<VT, false> (T, dg_grp, dg_val, lane, lr, x, n);
    if (lane < T.rows) y[T.row0 + lane] = MODE == 1 ? bv - acc : acc;
+}
+
+// ---------------------------------------------------------------- one Gauss-Seidel half sweep of a wave-fused level
+// gs_wave_kernel (colblock.hip) on the diagonals, for levels whose columns are one tile each (at most 64 rows): one wave per
+// column, lane = row.  xout_rows = x_rows + M^-1 (b - L x)_rows with x from two buffers (rows < split from xa, the others from
+// xb) like the CSR kernel, whose chain of dependent memory trips -- descriptor, (column, value) stretch into LDS, row pointers,
+// LDS reads, gathered x -- becomes two: the tile (scalar), then everything else at once.  The row's b, old x and 2P + 1
+// factors (f64 in fac, rounded to f32 on load when R32, as there) depend on the tile alone and are requested in front of the
+// first step's value and x loads; the lanes behind the column's end load its last row's and take zeros, which is what
+// wave_band_sweeps wants there.  Same products in the same order, a padded position adds +-0: the bits of gs_wave_kernel.
+template <int P, bool R32>
+__global__ __launch_bounds__ (DG_THREADS)
+void gs_wave_diag_kernel (const DgTile *__restrict__ tile, int ntile, const DgGroup *__restrict__ dg_grp, const float *__restrict__ dg_val, int64_t n,
+                          const double *__restrict__ fac, const double *__restrict__ xa, const double *__restrict__ xb, int split,
+                          const double *__restrict__ b, double *__restrict__ xout)
+{
+   const int t = __builtin_amdgcn_readfirstlane (blockIdx.x * DG_WAVES + (threadIdx.x >> 6));
+   if (t >= ntile) return;
+   const DgTile T = tile[t];
+   const int lane = threadIdx.x & (NKP_WAVE - 1);
+   const bool own = lane < T.rows;
+   const int lr = min (lane, T.rows - 1);
+   const int64_t r = T.row0 + lr;
+   const double bv = b[r];
+   const double xold = r < split ? xa[r] : xb[r];
+   double f[2 * P + 1];
+#pragma unroll
+   for (int d = 0; d <= 2 * P; d++) {
+      f[d] = fac[(int64_t) d * n + r];
+      if (R32) f[d] = (double) (float) f[d];
+   }
+   const double acc = dg_row_sum<float, true> (T, dg_grp, dg_val, lane, lr, xa, (int) n, xb, split);
+   double y[1][1], invd[1], L[1][P], U[1][P];
+   y[0][0] = own ? bv - acc : 0.0;
+   invd[0] = own ? f[P] : 0.0;
+#pragma unroll
+   for (int q = 1; q <= P; q++) {
+      L[0][q - 1] = own ? f[P - q] : 0.0;      // l(r, r-q)
+      U[0][q - 1] = own ? f[P + q] : 0.0;      // u(r, r+q)
+   }
+   wave_band_sweeps<P, 1, 1> (T.rows, lane, y, invd, L, U);
+   if (own) xout[T.row0 + lane] = xold + y[0][0];
 }
 
 // ---------------------------------------------------------------- host side
@@ -329,6 +385,21 @@ void launch_diag_residual (const CsrDev &L, int tile0, int tile1, const double *
    if (cnt <= 0) return;
    hipLaunchKernelGGL ((diag_residual_kernel<float, 1>), dim3 ((cnt + DG_WAVES - 1) / DG_WAVES), dim3 (DG_THREADS), 0, st, (const DgTile *) L.dg_tile + tile0, cnt,
                        (const DgGroup *) L.dg_grp, (const float *) L.dg_val, x, b, y, (int) L.n);
+}
+
+// tiles [tile0, tile1) of one colour of a level whose columns are one tile each (ml_setup sets MlLevel::wave_diag only there)
+void launch_gs_wave_diag (const CsrDev &L, const ColBlocksDev &B, int tile0, int tile1, const double *xa, const double *xb, int split, const double *b,
+                          double *xout, int r32, hipStream_t st)
+{
+   const int cnt = tile1 - tile0;
+   if (cnt <= 0) return;
+   with_band (B.P, [&] (auto p) {
+      with_bool (r32, [&] (auto r32_) {
+         hipLaunchKernelGGL ((gs_wave_diag_kernel<decltype (p)::value, decltype (r32_)::value>), dim3 ((cnt + DG_WAVES - 1) / DG_WAVES), dim3 (DG_THREADS), 0, st,
+                             (const DgTile *) L.dg_tile + tile0, cnt, (const DgGroup *) L.dg_grp, (const float *) L.dg_val, B.n, (const double *) B.fac, xa, xb,
+                             split, b, xout);
+      });
+   });
 }
 
 void launch_diag_spmv (const CsrDev &A, const double *x, double *y, const double *b, int mode, hipStream_t st)

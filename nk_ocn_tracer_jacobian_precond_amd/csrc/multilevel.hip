@@ -96,20 +96,23 @@ int finish_level_columns (MlHierarchy &H, MlLevel &V, int l, const std::vector<i
       // few columns: one per wave, and their half sweeps one launch each (residual of the column's rows + its band solve, gs_wave_kernel)
       V.wave_columns = V.B.kern.wave_columns;
       V.wave_fused = V.B.kern.wave_fused;
-      if (V.wave_fused) {
-         if (!upload (&V.B.wave_desc, (const int *) nullptr, (size_t) 4 * (size_t) ncol, &H.device_bytes)) ML_FAIL (-2, "multilevel setup: device allocation failed");
-         launch_build_wave_desc (V.L, V.B, st);
-      }
       // the block-per-group fused kernel serves matching storage only (f32 operator with f32 factors, or f64 with f64)
       if (V.B.gs_ok && !((V.B.fac_tf && V.L.valf) || (V.B.fac_t && !V.L.valf))) V.B.gs_ok = 0;
       T.lay += secs_since (t_lay0);
    }
-   // per-column diagonals for the residual rows of the two-kernel half sweeps and the full residual (ml_diag = most keys a
-   // column may need; 0 = off).  A level that does not qualify stays on CSR.
-   if (H.tune->ml_diag > 0 && V.L.valf && !ml_level_fused (H, V)) {
+   // per-column diagonals (ml_diag = most keys a column may need; 0 = off) for the residual rows of the two-kernel half sweeps,
+   // for the wave-fused half sweeps of a level whose columns are one tile each (gs_wave_diag_kernel) and for the full residual
+   // of both.  A level that does not qualify stays on CSR; a level that runs gs_fused_kernel is not asked.
+   if (H.tune->ml_diag > 0 && V.L.valf && (V.wave_fused ? V.B.max_len <= NKP_WAVE : !ml_level_fused (H, V))) {
       auto t_dg0 = setup_clk::now ();
       (void) diag_build (V.L, pblk.data (), V.B.blk_start, ncol, ncol0, V.B.max_len, H.tune->ml_diag, V.color_tile, &H.device_bytes, st);
       T.lay += secs_since (t_dg0);
+   }
+   V.wave_diag = V.wave_fused && V.L.dg_val;
+   if (V.wave_fused && !V.wave_diag) {
+      // the CSR kernel's descriptors
+      if (!upload (&V.B.wave_desc, (const int *) nullptr, (size_t) 4 * (size_t) ncol, &H.device_bytes)) ML_FAIL (-2, "multilevel setup: device allocation failed");
+      launch_build_wave_desc (V.L, V.B, st);
    }
    // f32 storage mode: the f64 copy of the level operator was only needed to factor the column blocks
    if (V.L.valf && V.L.val) {

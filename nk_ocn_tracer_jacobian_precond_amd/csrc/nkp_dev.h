@@ -317,6 +317,10 @@ void launch_colblock_apply_range_r32 (const ColBlocksDev &B, int b0, int b1, con
 void launch_build_wave_desc (const CsrDev &L, ColBlocksDev &B, hipStream_t st);   // fills B.wave_desc (allocated by the caller: 4 ints per column)
 void launch_gs_wave (const CsrDev &L, const ColBlocksDev &B, int b0, int b1, const double *xa, const double *xb, int split, const double *b, double *xout,
                      int r32, hipStream_t st);
+// the same half sweep on L's per-column diagonals (diagop.hip), tiles [tile0, tile1) of one colour, for a level whose columns
+// are one tile each (at most 64 rows): the bits of launch_gs_wave
+void launch_gs_wave_diag (const CsrDev &L, const ColBlocksDev &B, int tile0, int tile1, const double *xa, const double *xb, int split, const double *b,
+                          double *xout, int r32, hipStream_t st);
 
 // ---------------------------------------------------------------- BLAS-1 style kernels
 #define NKP_BATCH_MAX 8            // right-hand sides per sweep at most (interleave widths 2, 4, 8)
