@@ -157,6 +157,10 @@ typedef struct nkp_tuning {
                                 row is summed from +0.0 in stored order, so the bits are those of the CSR kernels for finite x; the
                                 one difference: a padded slot holds +0.0, and +0.0 times a non-finite x is NaN where CSR would not
                                 touch that x (the level operators under ml_diag behave the same) */
+   int ml_lane_fused;        /* NKP_ML_LANE_FUSED (50000): levels of the cycle on the packed lane-per-column layout with at most that many
+                                water columns, columns of at most 64 rows, half bandwidth <= 2 and their operator on diagonals (ml_diag)
+                                run every Gauss-Seidel half sweep as ONE launch (gs_lanes_diag_kernel: residual rows per wave, band
+                                solves per lane) instead of residual rows + column solves; same bits.  0 = off */
 } nkp_tuning;
 
 /* defaults, then the NKP_* environment overrides listed above */
@@ -687,8 +691,10 @@ int nkp_dist_plan_host (int64_t m_loc, int64_t nnz_loc, const int32_t *rowptr_lo
  * residual kernel loads x for once -- column c has the groups dg_gptr[c] .. dg_gptr[c + 1], in slot order, group g with the first
  * key dg_grp[2 g] and dg_grp[2 g + 1] = s0 | m << 16, its first slot in the column and its keys (m <= 5 and m <= 64 - rows + 1,
  * rows = ceil (len / ceil (len / 64)), the column's tallest tile); "wave_diag" (int32, 1 entry, a host value): 1 where the level's
- * wave-fused half sweeps read these diagonals (gs_wave_diag_kernel), 0 where they read CSR or the level is not wave-fused.  All in
- * the level's colour-major row order. */
+ * wave-fused half sweeps read these diagonals (gs_wave_diag_kernel), 0 where they read CSR or the level is not wave-fused;
+ * "lane_diag" (int32, 1 entry, a host value): 1 where the half sweeps of a lane-per-column level are one launch each on these
+ * diagonals (gs_lanes_diag_kernel, tuning ml_lane_fused), and then "grp_tile" (int32, ngrp * gw): per lane of every packed group
+ * the column it holds, counted in columns that have rows, -1 = none.  All in the level's colour-major row order. */
 int64_t nkp_ml_level_array (nkp_solver *s, int level, const char *what, void *dst, int64_t capacity_bytes);
 
 /* The same for the per-column diagonals of the solver's own matrix A (tuning spmv_diag), in the row order and with the water

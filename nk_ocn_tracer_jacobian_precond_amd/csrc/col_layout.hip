@@ -76,6 +76,8 @@ int colblock_build_lane_layout (ColBlocksDev &B, const int *h_blk_start, const i
    if ((rc = up (&B.grp_b0, pl.grp_b0, device_bytes)) || (rc = up (&B.grp_nb, pl.grp_nb, device_bytes)) || (rc = up (&B.grp_maxlen, pl.grp_maxlen, device_bytes)) ||
        (rc = up (&B.grp_base, pl.grp_base, device_bytes)) || (rc = up (&B.grp_row0, pl.grp_row0, device_bytes)) || (rc = up (&B.col_slot, pl.col_slot, device_bytes)))
       return rc;
+   if (pl.kern.lane_fused && (rc = up (&B.grp_tile, pl.grp_tile, device_bytes))) return rc;
+   B.grp_tile_cnt = pl.ntile;
    void *q = nullptr;
    const size_t fsz = f32 ? sizeof (float) : sizeof (double);
    hipError_t e = hipMalloc (&q, (size_t) (pl.fac_total ? pl.fac_total : 1) * fsz);

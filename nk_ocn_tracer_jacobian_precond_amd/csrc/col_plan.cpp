@@ -56,6 +56,7 @@ static void choose_family (const ColPlanInput &in, const nkp_tuning &T, ColPlan 
    const bool packed_batch = k.family == COL_LDSPACK && !k.wave_columns;
    k.batch4 = packed_batch ? COL_BATCH_LDSPACK4 : COL_BATCH_WAVE;
    k.batch_other = packed_batch ? COL_BATCH_LDSPACK2 : COL_BATCH_WAVE;
+   k.lane_fused = k.family == COL_LDSPACK && !k.wave_columns && in.max_len <= 64 && in.P <= 2 && in.ncol >= 0 && T.ml_lane_fused > 0 && in.ncol <= T.ml_lane_fused;
 }
 
 // ---------------------------------------------------------------- groups
@@ -80,7 +81,12 @@ static void form_groups (const ColPlanInput &in, ColPlan &pl, int &rows_need, in
    const int *bs = in.h_blk_start;
    const int gw = pl.gw, ndiag = 2 * in.P + 1;
    const auto len = [bs] (int col) { return bs[col + 1] - bs[col]; };
-   std::vector<int> nrow, clen, order;
+   std::vector<int> nrow, clen, order, tile_of;
+   if (pl.kern.lane_fused) {
+      // a column of at most 64 rows is one tile of the diagonals, a column without rows none: tiles follow the columns
+      tile_of.resize ((size_t) in.ranges[in.nranges]);
+      for (int col = 0; col < in.ranges[in.nranges]; col++) tile_of[(size_t) col] = len (col) > 0 ? pl.ntile++ : -1;
+   }
    rows_need = fac_need = 0;
    rb_ok = in.h_rowptr != nullptr;
    pl.grp_first.assign ((size_t) in.nranges + 1, 0);
@@ -104,6 +110,7 @@ static void form_groups (const ColPlanInput &in, ColPlan &pl, int &rows_need, in
          for (int c = 0; c < gw; c++) {
             const int col = c < cnt ? order[q0 + c] : -1;
             if (pl.sorted) pl.grp_cols.push_back (col);
+            if (pl.kern.lane_fused) pl.grp_tile.push_back (col >= 0 ? tile_of[(size_t) col] : -1);
             pl.col_slot.push_back (col >= 0 ? bs[col] - row0 : 0);
             clen.push_back (col >= 0 ? len (col) : 0);
          }

@@ -53,6 +53,10 @@ struct ColKernel {
    int batch4 = COL_BATCH_WAVE, batch_other = COL_BATCH_WAVE;   // K interleaved right-hand sides with K % 4 == 0 / any other K
    int wave_columns = 0;       // a level of the multilevel cycle with few columns: one column per WAVE (colblock_apply_kernel)
    int wave_fused = 0;         // ... and its half sweeps are one launch each (gs_wave_kernel)
+   // COL_LDSPACK level of the cycle, not one column per wave, columns of at most 64 rows, P <= 2 (the group's factors beside
+   // its columns twice in a CU's LDS), at most ml_lane_fused columns: its half sweeps may run as one launch each on the level
+   // operator's diagonals (gs_lanes_diag_kernel); the plan then carries grp_tile
+   int lane_fused = 0;
 };
 
 struct ColPlanInput {
@@ -79,6 +83,8 @@ struct ColPlan {
    std::vector<int> grp_row0;          // [ngrp] first row of the group (0 when sorted), then [ngrp] its rows (0 when sorted)
    std::vector<int> col_slot;          // [ngrp * gw] first row of the lane's column relative to grp_row0, then [ngrp * gw] its length (0: no column)
    std::vector<int> grp_cols;          // sorted only: [ngrp * gw] the lane's column, -1 = none
+   std::vector<int> grp_tile;          // kern.lane_fused only: [ngrp * gw] the lane's column counted in columns that have rows (= its tile in the level operator's diagonals), -1 = none
+   int ntile = 0;                      // ... and how many such columns there are
    std::vector<int> gs_rb_ptr, gs_rb;  // fused sweep: [ngrp + 1] first row block of the group; first rows of the blocks + the end (empty: a row exceeds GS_NNZ, or not wanted)
    long long fac_total = 0;            // elements of the factor array
    int rhs_slots = 0;                  // LDS doubles reserved for the staged right-hand side

@@ -1,5 +1,5 @@
 // What crosses the units of the lane-per-column band solves: col_layout.hip (layout), col_lanes.hip (lanes, pipelined, streamed
-// and LDS-resident kernels; launch_colblock_apply_lanes), col_packed.hip (packed kernels), col_gs_fused.hip.  Private to them.
+// and LDS-resident kernels; launch_colblock_apply_lanes), col_packed.hip (packed kernels), col_gs_fused.hip, col_gs_lanes.hip.  Private to them.
 #pragma once
 #include "nkp_dev.h"
 

@@ -42,6 +42,8 @@ extern "C" int64_t nkp_ml_level_array (nkp_solver *s, int level, const char *wha
       src = B.blk_start ? col_kernel : nullptr; count = src ? 11 : 0; host = true;
    }
    else if (!strcmp (what, "wave_diag")) { src = &V.wave_diag; count = 1; host = true; }      // 1: the half sweeps run gs_wave_diag_kernel
+   else if (!strcmp (what, "lane_diag")) { src = &V.lane_diag; count = 1; host = true; }      // 1: the half sweeps run gs_lanes_diag_kernel
+   else if (!strcmp (what, "grp_tile")) { src = V.B.grp_tile; count = src ? (int64_t) V.B.ngrp * V.B.gw : 0; }
    else return fail (NKP_EINVAL, "nkp_ml_level_array: unknown array '%s'", what);
    if (!dst) return count;
    if (count * (int64_t) elem > capacity_bytes) return fail (NKP_EINVAL, "nkp_ml_level_array: buffer too small");

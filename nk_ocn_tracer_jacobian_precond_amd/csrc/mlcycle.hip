@@ -1,13 +1,14 @@
 // Multilevel water-column preconditioner: the V(nu, nu) cycle on the hierarchy ml_setup built (multilevel.hip), for one
 // right-hand side and for K interleaved ones, and the measurement helpers of bench.py and the probes.  Launchers only: the
-// kernels are colblock.hip, col_lanes.hip, col_packed.hip, col_gs_fused.hip, spmv.hip, blas1.hip, batch.hip, dense.hip and mltail.hip.
+// kernels are colblock.hip, col_lanes.hip, col_packed.hip, col_gs_fused.hip, col_gs_lanes.hip, diagop.hip, spmv.hip, blas1.hip,
+// batch.hip, dense.hip and mltail.hip.
 #include "nkp_dev.h"
 #include "multilevel.h"
 
 // ================================================================ cycle
-// one Gauss-Seidel half sweep over colour c.  Fused path: one launch, x ping-pongs between the level's two buffers (the
-// new values of colour c go where the other colour's current values are if the level is incoherent, else to the other
-// buffer).  Two-kernel path: residual SpMV of the colour's rows, then the column solves accumulate into x in place.
+// one Gauss-Seidel half sweep over colour c.  Fused path (gs_wave_diag_kernel, gs_lanes_diag_kernel, gs_wave_kernel or
+// gs_fused_kernel): one launch, x ping-pongs between the level's two buffers (the new values of colour c go where the other
+// colour's current values are if the level is incoherent, else to the other buffer).  Two-kernel path: residual SpMV of the colour's rows, then the column solves accumulate into x in place.
 // column solves of colour c: levels with few columns run one column per WAVE (colblock_apply_kernel: one round trip for the
 // column's right-hand side and factors, the substitution by lane broadcasts) -- with thousands of idle wave slots its
 // ~5 us beat the 12-16 us latency floor of the lane-per-column kernels, which only win when the chip is full
@@ -27,6 +28,7 @@ static void gs_half (const MlHierarchy &H, MlLevel &V, int c, bool fused, hipStr
       const int rows0 = (int) V.rows0;
       // (the launchers cannot refuse: ml_setup clears gs_ok / wave_fused for a level whose storage they do not serve)
       if (V.wave_diag) launch_gs_wave_diag (V.L, V.B, V.color_tile[c], V.color_tile[c + 1], V.xbuf (V.cur[0]), V.xbuf (V.cur[1]), rows0, V.b, V.xbuf (out), H.f32, st);
+      else if (V.lane_diag) launch_gs_lanes_diag (V.L, V.B, V.color_grp[c], V.color_grp[c + 1], V.xbuf (V.cur[0]), V.xbuf (V.cur[1]), rows0, V.b, V.xbuf (out), st);
       else if (V.wave_fused) launch_gs_wave (V.L, V.B, V.color_blk[c], V.color_blk[c + 1], V.xbuf (V.cur[0]), V.xbuf (V.cur[1]), rows0, V.b, V.xbuf (out), H.f32, st);
       else (void) launch_gs_fused (V.L, V.B, V.color_grp[c], V.color_grp[c + 1], V.xbuf (V.cur[0]), V.xbuf (V.cur[1]), rows0, V.b, V.xbuf (out), st);
       V.cur[c] = out;
@@ -280,6 +282,11 @@ int64_t ml_bytes (const MlHierarchy &H, int which)
       for (int c = 0; c < 2; c++) {
          total += (int64_t) (2 * nu) * level_piece (V, c, 1);                       // column solves: nu pre + nu post sweeps
          total += (int64_t) (2 * nu - (c == 0 ? 1 : 0)) * level_piece (V, c, 0);    // residual rows (the first half sweep needs none)
+         // one launch per half sweep (gs_lanes_diag_kernel): r is neither written nor read; the tile map of the colour's groups is
+         if (V.lane_diag) {
+            const int64_t rows = c == 0 ? V.rows0 : V.n - V.rows0, slots = (int64_t) (V.color_grp[c + 1] - V.color_grp[c]) * V.B.gw;
+            total -= (int64_t) (2 * nu - (c == 0 ? 1 : 0)) * (rows * (8 + 8) - slots * 4);
+         }
       }
       if (V.L.dg_val) total += V.L.dg_nval * 4 + (int64_t) V.L.dg_ntile * (int64_t) sizeof (DgTile) + (int64_t) V.L.dg_ngrp * (int64_t) sizeof (DgGroup) + V.n * (8 + 8 + 8);
       else total += V.L.nnz * ((V.L.valf ? 4 : 8) + 4) + V.n * (4 + 8 + 8 + 8);    // full residual before the restriction

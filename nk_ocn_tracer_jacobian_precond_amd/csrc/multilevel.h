@@ -16,6 +16,7 @@ struct MlLevel {
    int wave_columns = 0;        // few columns: solve them one per wave (colblock_apply_kernel) instead of one per lane
    int wave_fused = 0;          // ... and run every half sweep as one launch (gs_wave_kernel: residual rows + band solve per wave)
    int wave_diag = 0;           // ... on L's per-column diagonals (gs_wave_diag_kernel: every column one tile, no B.wave_desc)
+   int lane_diag = 0;           // a lane-per-column level (packed layout) whose half sweeps are one launch each on L's diagonals (gs_lanes_diag_kernel)
    int64_t nc = 0;              // rows of the next coarser level
    int *cmap = nullptr;         // fine row -> coarse row                 (prolongation)
    int *rptr = nullptr, *ridx = nullptr;   // coarse row -> its fine rows (restriction)
@@ -59,12 +60,12 @@ struct MlHierarchy {
    int default_build = 0;       // built by the default construction (the one the setup kernels cover): nkp_refactor may keep the cells
 };
 
-// the level's half sweeps are one launch each (gs_wave_kernel or gs_fused_kernel) instead of residual rows + column solves
+// the level's half sweeps are one launch each (gs_wave_kernel, gs_lanes_diag_kernel or gs_fused_kernel) instead of residual rows + column solves
 inline bool ml_level_fused (const MlHierarchy &H, const MlLevel &V)
 {
    // ml_fused_max_cols: the fused half sweep only on levels with at most that many columns (the launch-bound end)
    const int fused_max = H.tune->ml_fused_max_cols;
-   return V.wave_fused || (H.fused && V.B.gs_ok && (fused_max <= 0 || V.color_grp[2] * V.B.gw <= fused_max));
+   return V.wave_fused || V.lane_diag || (H.fused && V.B.gs_ok && (fused_max <= 0 || V.color_grp[2] * V.B.gw <= fused_max));
 }
 
 // returns 0, or a negative nkp error code with a message in err

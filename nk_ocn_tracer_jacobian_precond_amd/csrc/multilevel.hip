@@ -102,13 +102,16 @@ int finish_level_columns (MlHierarchy &H, MlLevel &V, int l, const std::vector<i
    }
    // per-column diagonals (ml_diag = most keys a column may need; 0 = off) for the residual rows of the two-kernel half sweeps,
    // for the wave-fused half sweeps of a level whose columns are one tile each (gs_wave_diag_kernel) and for the full residual
-   // of both.  A level that does not qualify stays on CSR; a level that runs gs_fused_kernel is not asked.
-   if (H.tune->ml_diag > 0 && V.L.valf && (V.wave_fused ? V.B.max_len <= NKP_WAVE : !ml_level_fused (H, V))) {
+   // of both, and for the one-launch half sweeps of a packed lane-per-column level (gs_lanes_diag_kernel, kern.lane_fused).  A level
+   // that does not qualify stays on CSR (and on two kernels); a level that runs gs_fused_kernel is not asked.
+   if (H.tune->ml_diag > 0 && V.L.valf && (V.wave_fused ? V.B.max_len <= NKP_WAVE : V.B.kern.lane_fused || !ml_level_fused (H, V))) {
       auto t_dg0 = setup_clk::now ();
       (void) diag_build (V.L, pblk.data (), V.B.blk_start, ncol, ncol0, V.B.max_len, H.tune->ml_diag, V.color_tile, &H.device_bytes, st);
       T.lay += secs_since (t_dg0);
    }
    V.wave_diag = V.wave_fused && V.L.dg_val;
+   // the tile map counts one tile per column that has rows, which is what diag_build makes of columns of at most 64 rows
+   V.lane_diag = V.B.kern.lane_fused && V.L.dg_val && V.B.grp_tile && V.B.fac_tf && V.B.grp_tile_cnt == V.L.dg_ntile;
    if (V.wave_fused && !V.wave_diag) {
       // the CSR kernel's descriptors
       if (!upload (&V.B.wave_desc, (const int *) nullptr, (size_t) 4 * (size_t) ncol, &H.device_bytes)) ML_FAIL (-2, "multilevel setup: device allocation failed");
@@ -572,7 +575,7 @@ int ml_coarse_inverse (const MlHierarchy &H, int n, const int *prow, const int *
 void ml_free (MlHierarchy &H)
 {
    for (MlLevel &V : H.lev) {
-      void *ptrs[] = { V.L.rowptr, V.L.colind, V.L.val, V.L.valf, V.B.fac_tf, V.L.rowblk, V.L.codes, V.L.dict, V.L.dict_ptr, V.L.dg_ptr, V.L.dg_key, V.L.dg_voff, V.L.dg_val, V.L.dg_tile, V.L.dg_gptr, V.L.dg_grp, V.B.blk_start, V.B.fac, V.B.grp_b0, V.B.grp_nb, V.B.grp_maxlen, V.B.grp_base, V.B.grp_row0, V.B.col_slot, V.B.fac_t, V.B.gs_rb_ptr, V.B.gs_rb, V.B.wave_desc, V.cmap, V.rptr, V.ridx, V.x, V.x2, V.b, V.r, V.bx, V.bx2, V.bb, V.br };
+      void *ptrs[] = { V.L.rowptr, V.L.colind, V.L.val, V.L.valf, V.B.fac_tf, V.L.rowblk, V.L.codes, V.L.dict, V.L.dict_ptr, V.L.dg_ptr, V.L.dg_key, V.L.dg_voff, V.L.dg_val, V.L.dg_tile, V.L.dg_gptr, V.L.dg_grp, V.B.blk_start, V.B.fac, V.B.grp_b0, V.B.grp_nb, V.B.grp_maxlen, V.B.grp_base, V.B.grp_row0, V.B.col_slot, V.B.fac_t, V.B.gs_rb_ptr, V.B.gs_rb, V.B.wave_desc, V.B.grp_tile, V.cmap, V.rptr, V.ridx, V.x, V.x2, V.b, V.r, V.bx, V.bx2, V.bb, V.br };
       for (void *p : ptrs)
          if (p) (void) hipFree (p);
       delete V.B.grp_cols;

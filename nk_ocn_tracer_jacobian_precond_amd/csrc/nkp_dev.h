@@ -145,6 +145,8 @@ struct ColBlocksDev {
    int *gs_rb_ptr = nullptr;   // [ngrp+1] first row-block boundary of the group
    int *gs_rb = nullptr;       // row-block boundaries (rows), groups back to back
    int *wave_desc = nullptr;   // levels run by gs_wave_kernel: per column {first row, rows, first entry, entries} -- one load instead of two dependent ones
+   int *grp_tile = nullptr;    // kern.lane_fused: [ngrp*gw] the tile of the level operator's diagonals that is the lane's column, -1 = none (pattern only)
+   int grp_tile_cnt = 0;       // ... the tiles the map counts on: columns with rows, each one tile
    const nkp_tuning *tune = nullptr;   // kernel selection knobs of the owning solver (NULL: built-in defaults)
    int ml_level = 0;           // 1: a level of the multilevel cycle (set before the layout is built), which may run one column per wave
    ColKernel kern;             // the kernel choice col_plan resolved when the layout was built: what the launchers branch on
@@ -321,6 +323,11 @@ void launch_gs_wave (const CsrDev &L, const ColBlocksDev &B, int b0, int b1, con
 // are one tile each (at most 64 rows): the bits of launch_gs_wave
 void launch_gs_wave_diag (const CsrDev &L, const ColBlocksDev &B, int tile0, int tile1, const double *xa, const double *xb, int split, const double *b,
                           double *xout, int r32, hipStream_t st);
+// the same half sweep for a level on the packed lane-per-column layout (col_gs_lanes.hip), groups [g0, g1) of one colour: L on its
+// diagonals, B.grp_tile built, columns of at most 64 rows, P <= 2 (B.kern.lane_fused); the bits of launch_diag_residual +
+// launch_colblock_apply_lanes
+void launch_gs_lanes_diag (const CsrDev &L, const ColBlocksDev &B, int g0, int g1, const double *xa, const double *xb, int split, const double *b,
+                           double *xout, hipStream_t st);
 
 // ---------------------------------------------------------------- BLAS-1 style kernels
 #define NKP_BATCH_MAX 8            // right-hand sides per sweep at most (interleave widths 2, 4, 8)
