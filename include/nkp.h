@@ -20,8 +20,8 @@
  *                        src/SuperLU_brief_tree.txt:17
  *
  * Conventions (mirroring the reference): 0 = success, non-zero = failure; diagnostics go to
- * stderr prefixed "(rank)"; all indices 0-based; CSR with sorted, duplicate-free rows
- * (src/matrix.c:3826-3832).  Unlike SuperLU (which takes ownership of the arrays and frees
+ * stderr prefixed "(rank)"; all indices 0-based; CSR, as the reference writes it with sorted,
+ * duplicate-free rows (src/matrix.c:3826-3832; what else a row may hold: nkp_create).  Unlike SuperLU (which takes ownership of the arrays and frees
  * them in Destroy_*_Matrix_dist) nkp_create COPIES the caller's arrays to the device and
  * never frees or keeps host pointers.
  *
@@ -214,7 +214,20 @@ int nkp_device_count (void);
  *   blk_start[nblk+1]: row offsets of the water-column blocks (contiguous, ascending,
  *   blk_start[0]=0, blk_start[nblk]=n).  Rows of one block are the levels k=0..KMT-1 of one
  *   (tracer, column) (src/matrix.c:239-251, 778-784).  NULL => every row its own block
- *   (point Jacobi). */
+ *   (point Jacobi).
+ *
+ * What the CSR arrays may hold.  A IS THE SUM OF ITS STORED ENTRIES: every product, factor and derivative below is
+ * of that sum, whatever the order of a row and however often a column is repeated in it.
+ *   NKP_PRECOND_NONE, NKP_PRECOND_COLUMN_JACOBI   rows in any order; a column may be repeated in a row (the entries
+ *        add up, in the products and in the factored water-column blocks alike); stored zeros are entries like any
+ *        other.  NKP_PRECOND_NONE also takes rows without entries.  Only strictly ascending rows can run on the
+ *        per-column diagonals of nkp_tuning.spmv_diag; A with any other row stays on CSR, with the same products.
+ *   NKP_PRECOND_MULTILEVEL   strictly ascending rows only (sorted by column, no column repeated; what gen_A writes):
+ *        the setup looks entries up by bisection.  Anything else is refused with NKP_EINVAL "not sorted by column".
+ * Both preconditioners need a non-zero diagonal in every row, judged on the SUM of the row's diagonal entries in
+ * stored order: a diagonal stored as +1, -1 is refused with NKP_ESINGULAR like a missing one, by nkp_create and by
+ * nkp_refactor*.  Per-entry results (nkp_value_gradient, nkp_values_product, nkp_refactor's values) follow the stored
+ * order entry by entry; the parts of a repeated entry each get the gradient of the coupling they add up to. */
 int nkp_create (nkp_solver **out, const nkp_options *opt, int64_t n, int64_t nnz,
                 const int32_t *rowptr, const int32_t *colind, const double *val,
                 const int32_t *blk_start, int64_t nblk, int coupled_tracer_cnt);
@@ -700,7 +713,9 @@ int64_t nkp_ml_level_array (nkp_solver *s, int level, const char *what, void *ds
 /* The same for the per-column diagonals of the solver's own matrix A (tuning spmv_diag), in the row order and with the water
  * columns of nkp_create: what = "dg_ptr", "dg_key", "dg_voff", "dg_gptr", "dg_grp" as above, "dg_val" (double).  Every array is
  * empty when A runs on CSR (spmv_diag = 0, not eligible, no blk_start, row-distributed, a transposed handle).  A clone reads its
- * owner's. */
+ * owner's.  Also A's CSR arrays as the device holds them, "rowptr" (n + 1), "colind" (nnz), "val" (nnz, double) -- the caller's
+ * stored order; on a transposed handle the device transpose --, and "fac" (double, (2 P + 1) n), the band factors of
+ * NKP_PRECOND_COLUMN_JACOBI (empty under any other preconditioner). */
 int64_t nkp_matrix_array (nkp_solver *s, const char *what, void *dst, int64_t capacity_bytes);
 
 /* Host-only planning step of the multilevel preconditioner inside nkp_create, exposed so the aggregation logic can

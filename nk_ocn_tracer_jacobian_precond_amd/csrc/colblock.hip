@@ -48,16 +48,16 @@ void colblock_measure_kernel (const int *__restrict__ rowptr, const int *__restr
    const int r0 = blk_start[b], r1 = blk_start[b + 1];
    int bw = 0, nodiag = 0;
    for (int r = r0 + lane; r < r1; r += NKP_WAVE) {
-      bool have = false;
+      double diag = 0.0;                  // repeated entries add up (check_rows of create.hip sums them in this order)
       for (int e = rowptr[r]; e < rowptr[r + 1]; e++) {
          const int c = colind[e];
          if (c >= r0 && c < r1) {
             const int d = c > r ? c - r : r - c;
             bw = d > bw ? d : bw;
-            if (c == r && val[e] != 0.0) have = true;
+            if (c == r) diag += val[e];
          }
       }
-      nodiag += have ? 0 : 1;
+      nodiag += diag != 0.0 ? 0 : 1;
    }
    for (int off = NKP_WAVE / 2; off > 0; off >>= 1) {
       const int o = __shfl_down (bw, off);
@@ -99,9 +99,10 @@ void colblock_factor_kernel (const int *__restrict__ rowptr, const int *__restri
             const int d = c - r;
             const double v = val[e];
             if (d < -P || d > P) { drop = 1; continue; }
+            // repeated entries add up, in stored order; a single one is added to +0.0, which leaves its bits
 #pragma unroll
             for (int dd = -P; dd <= P; dd++)
-               if (d == dd) a[s][dd + P] = v;
+               if (d == dd) a[s][dd + P] += v;
          }
       }
    }

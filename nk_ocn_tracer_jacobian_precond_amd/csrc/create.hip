@@ -104,13 +104,15 @@ static int check_rows (const nkp_options &opt, int64_t n, const int32_t *rowptr,
          Bad b;
          if (rowptr[r + 1] < rowptr[r]) b.kind = 1;
          else {
-            bool have_diag = false;
+            // A is the sum of its stored entries: so is the diagonal, in stored order (colblock_measure_kernel and rf_diag_kernel
+            // sum it the same way).  The order test covers every entry, the diagonal included.
+            double diag = 0.0;
             for (int e = rowptr[r]; e < rowptr[r + 1] && !b.kind; e++) {
                if (colind[e] < 0 || colind[e] >= n) { b.kind = 2; b.col = colind[e]; }
-               else if (colind[e] == r && val[e] != 0.0) have_diag = true;
                else if (opt.precond == NKP_PRECOND_MULTILEVEL && e > rowptr[r] && colind[e] <= colind[e - 1]) b.kind = 4;
+               else if (colind[e] == r) diag += val[e];
             }
-            if (!b.kind && opt.precond != NKP_PRECOND_NONE && !have_diag) b.kind = 3;
+            if (!b.kind && opt.precond != NKP_PRECOND_NONE && !(diag != 0.0)) b.kind = 3;
          }
          if (b.kind) { b.row = r; bad[(size_t) t] = b; }
       }

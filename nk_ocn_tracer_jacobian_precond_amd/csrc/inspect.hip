@@ -72,6 +72,11 @@ extern "C" int64_t nkp_matrix_array (nkp_solver *s, const char *what, void *dst,
    else if (!strcmp (what, "dg_val")) { src = A.dg_vald; count = have ? A.dg_nval : 0; elem = 8; }
    else if (!strcmp (what, "dg_gptr")) { src = A.dg_gptr; count = have ? A.dg_ncol + 1 : 0; }
    else if (!strcmp (what, "dg_grp")) { src = A.dg_grp; count = have ? 2 * (int64_t) A.dg_ngrp : 0; }
+   // A as it sits on the device in CSR (a transposed handle: the device transpose), and the band factors of column Jacobi
+   else if (!strcmp (what, "rowptr")) { src = A.rowptr; count = src ? A.n + 1 : 0; }
+   else if (!strcmp (what, "colind")) { src = A.colind; count = src ? A.nnz : 0; }
+   else if (!strcmp (what, "val")) { src = A.val; count = src ? A.nnz : 0; elem = 8; }
+   else if (!strcmp (what, "fac")) { src = s->opt.precond == NKP_PRECOND_COLUMN_JACOBI ? s->B.fac : nullptr; count = src ? (int64_t) (2 * s->B.P + 1) * s->B.n : 0; elem = 8; }
    else return fail (NKP_EINVAL, "nkp_matrix_array: unknown array '%s'", what);
    if (!dst) return count;
    if (count * (int64_t) elem > capacity_bytes) return fail (NKP_EINVAL, "nkp_matrix_array: buffer too small");

@@ -67,10 +67,10 @@ void rf_diag_kernel (int64_t n, const int *__restrict__ rowptr, const int *__res
 {
    const int64_t i = (int64_t) blockIdx.x * RF_T + threadIdx.x;
    if (i >= n) return;
-   bool have = false;
+   double diag = 0.0;                     // the sum of the stored diagonal entries, as nkp_create judged it
    for (int e = rowptr[i]; e < rowptr[i + 1]; e++)
-      if (colind[e] == i && val[e] != 0.0) have = true;
-   if (!have) {
+      if (colind[e] == i) diag += val[e];
+   if (!(diag != 0.0)) {
       atomicAdd (cnt + 1, 1);
       atomicMin (cnt + 2, (int) i + 1);
    }

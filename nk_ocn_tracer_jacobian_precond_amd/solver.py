@@ -482,11 +482,12 @@ class NkpSolver:
         return out
 
     def matrix_array(self, what):
-        """One array of the per-column diagonals of the solver's own matrix (nkp_matrix_array, tuning spmv_diag); empty when A runs on CSR."""
+        """One array of the per-column diagonals of the solver's own matrix (nkp_matrix_array, tuning spmv_diag); empty when A runs on CSR.
+        Also "rowptr", "colind", "val" (A's CSR arrays on the device) and "fac" (the band factors of column Jacobi)."""
         cnt = int(self._lib.nkp_matrix_array(self._h, what.encode(), None, 0))
         if cnt < 0:
             raise NkpError(cnt, last_error())
-        out = np.empty(cnt, {"dg_voff": np.int64, "dg_val": np.float64}.get(what, np.int32))
+        out = np.empty(cnt, {"dg_voff": np.int64, "dg_val": np.float64, "val": np.float64, "fac": np.float64}.get(what, np.int32))
         if cnt:
             got = int(self._lib.nkp_matrix_array(self._h, what.encode(), out.ctypes.data_as(C.c_void_p), out.nbytes))
             if got != cnt:

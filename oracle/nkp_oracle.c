@@ -151,7 +151,7 @@ ORA_EXPORT int64_t ora_colblock_factor (int64_t n, const int32_t *rowptr, const 
             if (c < r0 || c >= r0 + len) continue;
             const int d = (int) (c - r);
             if (d < -P || d > P) { drop = 1; continue; }
-            a[(size_t) li * W + d + P] = val[e];
+            a[(size_t) li * W + d + P] += val[e];       /* repeated entries add up, as in colblock_factor_kernel */
          }
       }
       for (int k = 0; k < len; k++) {
