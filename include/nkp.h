@@ -161,6 +161,25 @@ typedef struct nkp_tuning {
                                 water columns, columns of at most 64 rows, half bandwidth <= 2 and their operator on diagonals (ml_diag)
                                 run every Gauss-Seidel half sweep as ONE launch (gs_lanes_diag_kernel: residual rows per wave, band
                                 solves per lane) instead of residual rows + column solves; same bits.  0 = off */
+   int dist_smooth_exchange; /* NKP_DIST_SMOOTH_EXCHANGE (0): 1 = on a row-distributed multilevel solver whose hierarchy has an overlap
+                                (dist_ras; see dist_ras_rings) every Gauss-Seidel half sweep on level 0 of the cycle is followed by an
+                                exchange that overwrites x on that colour's overlap rows, over all rings, with their owners' values: the
+                                own rows then see the global two-colour water-column Gauss-Seidel instead of one cut at the rank's
+                                edge ("fine-level exchange").  The exchange after the cycle's last half sweep
+                                is left out (nothing reads those rows), so one cycle makes 2 (nu_pre + nu_post) - 1 more alltoallv
+                                calls of device doubles -- 11 with V(3, 3) -- each of rows x 8 bytes per neighbour (x K for a batched
+                                group, which makes the exchanges of one system); they run in line on the solver's stream, after the
+                                overlap residual's exchange of the same application, in the same order on every rank whatever its
+                                lists hold, and are counted in "dist_alltoallv_calls".  Any value other than 0 or 1 is NKP_EINVAL,
+                                refused by every rank together like a dist_ras_rings out of range.  The ranks take the smallest value any of
+                                them asks for; the agreement rides on the message that settles the overlap depth, so nkp_create_dist
+                                has no collective more than without it.  No effect without dist_ras, grid positions or a lateral
+                                cut (a tracer partition has no overlap), or on one rank; and none unless level 0 of EVERY rank's
+                                hierarchy runs the same half sweeps (a rank whose [own | overlap] block is small enough to be one
+                                dense level, ml_coarsest_rows, has none: its sweep count rides on the last agreement of
+                                nkp_create_dist, and the ranks then leave the exchange out together).  nkp_get_int
+                                "dist_smooth_exchange" tells what is in force.  The hierarchy of a refactor that rebuilds must keep a
+                                smoothed level 0, else the refactor fails at its commit agreement */
 } nkp_tuning;
 
 /* defaults, then the NKP_* environment overrides listed above */
@@ -332,6 +351,9 @@ int nkp_time_kernel (nkp_solver *s, int which, int arg, int reps, double *avg_ms
  * "dist_ras" (hierarchy overlaps the neighbouring ranks), "dist_ras_rows" (rows of other ranks in this rank's hierarchy, all rings),
  * "dist_ras_rings" (the depth the ranks agreed on, 0 without overlap), "dist_halo_rows" (rows received before every SpMV),
  * "dist_ras_recv_rows" (rows received per preconditioner application: the SpMV halo with one ring, the overlap rows with more);
+ * "dist_smooth_exchange" (1 = the fine-level exchange of tuning dist_smooth_exchange is in force: a Krylov step then has, per cycle,
+ * the overlap residual's alltoallv, then 2 (nu_pre + nu_post) - 1 alltoallv calls of the half sweeps, then those of the SpMV and the
+ * allreduces as before), "dist_smooth_rows" (overlap rows refreshed per pair of half sweeps, = "dist_ras_rows" when in force, else 0);
  * counters, cumulative over the solver's life, per rank: "dist_alltoallv_calls", "dist_allreduce_calls" (every call of the two
  * device collectives made by solves, single or batched, and the one alltoallv of every nkp_value_gradient*; 0 on a single-GPU
  * solver), "value_gradient_calls" (successful nkp_value_gradient* calls), "value_gradient_us" (wall time of the last one),
@@ -666,7 +688,12 @@ int nkp_gather_root (nkp_solver *s, const double *x_loc, double *x_global);
  * an exchange of its own: "ras_send_rows" (own local rows sent, grouped by destination, ascending within each), "ras_need" /
  * "ras_give" (per-rank row counts; the rows from rank p arrive in hierarchy order).  What nkp_refactor_dist redoes the values
  * from: "origin" (per entry of "colind": the own local entry it comes from, or -1 - position in the received overlap values),
- * "ship" (own local entries shipped, grouped by destination), "ent_need" / "ent_give" (per-rank entry counts). */
+ * "ship" (own local entries shipped, grouped by destination), "ent_need" / "ent_give" (per-rank entry counts).
+ * "smooth_exchange" (size only) is 1 when the ranks agreed on the fine-level exchange (tuning dist_smooth_exchange) and there is an
+ * overlap; then, per colour c = (i + j) % 2 of the water columns: "smooth_send_rows0" / "1" (own local rows that other ranks hold
+ * as overlap rows, all rings, grouped by destination, ascending within each), "smooth_give0" / "1" and "smooth_need0" / "1"
+ * (per-rank row counts; the rows from rank p arrive in the hierarchy order of this rank's overlap rows of that colour), and
+ * "smooth_recv_rows0" / "1" (those overlap rows as rows of the hierarchy's matrix).  All of them are empty otherwise. */
 typedef struct nkp_dist_plan nkp_dist_plan;
 int nkp_dist_overlap_plan_host (nkp_dist_plan **out, const nkp_options *opt, int64_t n_global, int64_t fst_row, int64_t m_loc,
                                 int64_t nnz_loc, const int32_t *rowptr_loc, const int32_t *colind_glob, const double *val,

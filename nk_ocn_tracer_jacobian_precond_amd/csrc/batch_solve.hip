@@ -34,7 +34,7 @@ void note_fallback (const nkp_solver *s, const char *who, const char *why, int n
 }
 
 // a set of device buffers of `count` doubles per unit of width each, all or nothing (see batch_prepare)
-static int buffer_set (nkp_solver *s, std::initializer_list<std::pair<double **, size_t>> set, int *width, int K_new)
+static int buffer_set (nkp_solver *s, const std::vector<std::pair<double **, size_t>> &set, int *width, int K_new)
 {
    auto drop = [s, &set] (int K_old) {
       for (auto &e : set)
@@ -69,10 +69,16 @@ int batch_prepare_exchange (nkp_solver *s, int K)
       return fail (NKP_ENOMEM, "nkp_solve_batch: pinned host memory for the Gram-Schmidt messages");
    }
    const size_t gcount = 2 * (size_t) (s->m + 2) + 2;
-   return s->dist.ras_sep
-             ? buffer_set (s, { { &s->dist.bxe, (size_t) (s->n + s->dist.n_halo) }, { &s->dist.bsend, (size_t) s->dist.nsend }, { &s->dist.gmsg, gcount },
-                                { &s->dist.bras_send, (size_t) s->dist.ras_nsend }, { &s->dist.bras_recv, (size_t) s->dist.n_sel } }, &s->dist.bK, K)
-             : buffer_set (s, { { &s->dist.bxe, (size_t) (s->n + s->dist.n_halo) }, { &s->dist.bsend, (size_t) s->dist.nsend }, { &s->dist.gmsg, gcount } }, &s->dist.bK, K);
+   std::vector<std::pair<double **, size_t>> set = { { &s->dist.bxe, (size_t) (s->n + s->dist.n_halo) }, { &s->dist.bsend, (size_t) s->dist.nsend }, { &s->dist.gmsg, gcount } };
+   if (s->dist.ras_sep) {
+      set.push_back ({ &s->dist.bras_send, (size_t) s->dist.ras_nsend });
+      set.push_back ({ &s->dist.bras_recv, (size_t) s->dist.n_sel });
+   }
+   if (s->dist.smooth) {      // the fine-level exchange, K rows wide
+      set.push_back ({ &s->dist.bsmooth_send, (size_t) s->dist.smooth_nsend_max });
+      set.push_back ({ &s->dist.bsmooth_recv, (size_t) s->dist.smooth_nrecv_max });
+   }
+   return buffer_set (s, set, &s->dist.bK, K);
 }
 
 // Everything K systems in flight need.  Transactional per buffer set: after a failed allocation the set is gone and its
@@ -132,11 +138,11 @@ static void batch_precond (nkp_solver *s, int K, const double *const *src, const
          for (size_t p = 0; p < D.ras_recv_counts.size (); p++) D.ras_recv_counts_k[p] = D.ras_recv_counts[p] * K;
          if (D.ras_nsend) launch_pack_rows_split (K, D.ras_send_idx, src, D.bras_send, D.ras_nsend, st);
          alltoallv_dev (s, D.bras_send, D.ras_send_counts_k.data (), D.bras_recv, D.ras_recv_counts_k.data (), st);
-         ml_apply_batch_split_ext (s->ml, K, src, D.bras_recv, nullptr, n, zi, dz ? dz : none, st);
+         ml_apply_batch_split_ext (s->ml, K, src, D.bras_recv, nullptr, n, zi, dz ? dz : none, st, smooth_hook_of (s));
       } else {
          if (D.nsend) launch_pack_rows_split (K, D.send_idx, src, D.bsend, D.nsend, st);
          alltoallv_dev (s, D.bsend, D.send_counts_k.data (), halo, D.recv_counts_k.data (), st);
-         ml_apply_batch_split_ext (s->ml, K, src, halo, D.sel_idx, n, zi, dz ? dz : none, st);
+         ml_apply_batch_split_ext (s->ml, K, src, halo, D.sel_idx, n, zi, dz ? dz : none, st, smooth_hook_of (s));
       }
    } else if (s->opt.precond == NKP_PRECOND_MULTILEVEL) {
       // permutation into the hierarchy's row order and the (de-)interleave in one kernel each

@@ -96,12 +96,25 @@ extern "C" int nkp_create_dist (nkp_solver **out, const nkp_options *opt, int64_
       }
       s->dist.ras = ok;
    }
+   // fine-level exchange (tuning dist_smooth_exchange, agreed by dist_plan): lists, counts, buffers; the index lists follow the
+   // hierarchy.  A rank's cycle makes 4 nu - 1 exchanges, nu = its level-0 sweeps, so the exchange is only in force when level 0
+   // of every rank runs the same nu half sweeps: each rank's count rides on the agreement below (0: its level 0 runs none)
+   int64_t smooth_nu = 0;
+   if (ok && D.ras && D.smooth) {
+      ok = smooth_install (s, D);
+      if (ok && ml_level0_hookable (s->ml)) {
+         ok = smooth_build_lists (s) == 0;
+         smooth_nu = ml_level0_sweeps (s->ml);
+      }
+   }
    {
       // once more all ranks together: a rank without halo buffers must not leave its peers to a first SpMV that never completes
       std::vector<int64_t> all (P + 1, 0);
-      const bool comm_ok = comm->allgather_i64_host (comm->ctx, ok ? 0 : 1, all.data ()) == 0;
+      const bool comm_ok = comm->allgather_i64_host (comm->ctx, (ok ? 0 : 1) + 2 * smooth_nu, all.data ()) == 0;
       int bad_rank = -1;
-      for (int p = 0; p < P && comm_ok; p++) if (all[p] && bad_rank < 0) bad_rank = p;
+      for (int p = 0; p < P && comm_ok; p++) if ((all[p] & 1) && bad_rank < 0) bad_rank = p;
+      s->dist.smooth = comm_ok && smooth_nu > 0;
+      for (int p = 0; p < P && comm_ok; p++) s->dist.smooth = s->dist.smooth && (all[p] >> 1) == smooth_nu;
       if (!ok || !comm_ok || bad_rank >= 0) {
          solver_free (s);
          if (!ok) return fail (NKP_ENOMEM, "nkp_create_dist: halo buffers could not be allocated");
@@ -162,6 +175,8 @@ extern "C" int nkp_create_dist (nkp_solver **out, const nkp_options *opt, int64_
    msg (s, 1, "nkp_create_dist: rows [%lld, %lld) of %lld, %lld halo rows in, %lld rows out; overlap (restricted additive Schwarz): %s, %lld rows of other ranks in this rank's hierarchy (overlap depth %d)\n",
         (long long) fst_row, (long long) (fst_row + m_loc), (long long) n_global, (long long) D.n_halo, (long long) D.nsend, s->dist.ras ? "on" : "off", (long long) s->dist.n_sel,
         s->dist.ras ? s->dist.ras_rings : 0);
+   if (D.smooth) msg (s, 1, "nkp_create_dist: fine-level exchange %s: %lld + %lld rows out, %lld + %lld rows in per pair of level-0 half sweeps\n", s->dist.smooth ? "on" : "agreed but not in force (the ranks' level-0 sweeps differ)",
+                      (long long) D.smooth_send_rows[0].size (), (long long) D.smooth_send_rows[1].size (), (long long) D.smooth_recv_rows[0].size (), (long long) D.smooth_recv_rows[1].size ());
    *out = s;
    return NKP_OK;
 }

@@ -98,6 +98,8 @@ struct Planner {
    std::vector<int32_t> ov_sorted;                         // global rows of the rings before the current one, ascending
    std::vector<std::vector<int32_t>> shipped = std::vector<std::vector<int32_t>> ((size_t) P);   // owner: own local rows shipped to each rank over all rings
    int64_t n_sel_all = 0;                                  // rows received over all rings
+   int64_t smooth = 0;                                     // the fine-level exchange the ranks agreed on (0 / 1)
+   std::vector<int> ov_need;                               // overlap rows per owner (hierarchy order = ascending owners)
 
    int agree (int local_rc, const char *where) { return dist_agree_checks (comm, local_rc, "nkp_create_dist", where); }
    int exchange (const int32_t *sendp, const int *scnt, int32_t *recvp, const int *rcnt, const char *what) {
@@ -129,7 +131,8 @@ struct Planner {
    }
 
    // ---- step 2: the depth this rank asks for rides on the message that decides the overlap (0 = none); the ranks take the
-   // smallest.  -1 = a depth out of range: every rank refuses it together
+   // smallest.  -1 = a knob out of range: every rank refuses it together.  The fine-level exchange a rank asks for (tuning
+   // dist_smooth_exchange) is the lowest bit of the same message, and again the smallest holds
    int agree_on_depth ()
    {
       const bool geo = o.col_i && o.col_j && blk_start_loc && nblk_loc > 0;
@@ -140,14 +143,15 @@ struct Planner {
       if (resolve_tuning (&o, &tune, &range_error) == NKP_OK) {      // a struct of the wrong size is reported by the create call itself
          if (!tune.dist_ras) want_ras = 0;
          rings = tune.dist_ras_rings > 0 ? tune.dist_ras_rings : 1;
+         smooth = tune.dist_smooth_exchange == 1 ? want_ras : 0;
       }
       const std::string mine = range_error ? last_error_message () : std::string ();
       std::vector<int64_t> all (P + 1, 0);
-      if (comm->allgather_i64_host (comm->ctx, range_error ? -1 : want_ras * rings, all.data ())) return fail (NKP_ECOMM, "nkp_create_dist: allgather failed");
+      if (comm->allgather_i64_host (comm->ctx, range_error ? -1 : 2 * want_ras * rings + smooth, all.data ())) return fail (NKP_ECOMM, "nkp_create_dist: allgather failed");
       if (range_error) { restore_error_message (mine); return NKP_EINVAL; }
       for (int p = 0; p < P; p++)
          if (all[p] < 0) return fail (NKP_ECOMM, "nkp_create_dist: rank %d failed its checks (tuning); see its message", p);
-      for (int p = 0; p < P; p++) rings = std::min (rings, all[p]);
+      for (int p = 0; p < P; p++) { rings = std::min (rings, all[p] >> 1); smooth = std::min (smooth, all[p] & 1); }
       return NKP_OK;
    }
 
@@ -476,6 +480,39 @@ struct Planner {
          D.ras_need[p]++;
          flush_row (m_loc + k);
       }
+      ov_need = D.ras_need;
+   }
+
+   // ---- step 6: the fine-level exchange, per colour of the water columns.  Nothing new is asked of the peers: what this rank
+   // shipped (step 3) is what its peers hold as overlap rows, and the overlap columns carry their grid positions (step 4), so
+   // both sides split the same rows by the same colours.  An owner's rows reach a peer ascending, which is the hierarchy's
+   // order of that peer's overlap rows (ascending global rows, grouped by owner)
+   void smooth_lists ()
+   {
+      D.smooth = (D.ras && smooth) ? 1 : 0;
+      if (!D.smooth) return;                                          // (every list stays empty)
+      for (int c = 0; c < 2; c++) {
+         D.smooth_give[c].assign (P, 0);
+         D.smooth_need[c].assign (P, 0);
+      }
+      for (int p = 0; p < P; p++)
+         for (int32_t r : shipped[(size_t) p]) {                      // (sorted by record_shipping)
+            const int32_t col = col_of[(size_t) r];
+            const int c = (o.col_i[col] + o.col_j[col]) & 1;
+            D.smooth_send_rows[c].push_back (r);
+            D.smooth_give[c][p]++;
+         }
+      int p = 0;
+      int64_t left = ov_need.empty () ? 0 : ov_need[0];
+      for (size_t ec = (size_t) nblk_loc; ec + 1 < D.e_blk.size (); ec++) {
+         const int c = (D.e_ci[ec] + D.e_cj[ec]) & 1;
+         for (int32_t r = D.e_blk[ec]; r < D.e_blk[ec + 1]; r++) {
+            while (left == 0 && p + 1 < P) left = ov_need[(size_t) ++p];
+            left--;
+            D.smooth_recv_rows[c].push_back (r);
+            D.smooth_need[c][p]++;
+         }
+      }
    }
 
    // ---- step 5: what the owner ships over all rings, ascending rows per destination: the entries (for nkp_refactor_dist) and,
@@ -511,6 +548,7 @@ struct Planner {
       if (comm->allgather_i64_host (comm->ctx, D.n_sel, all.data ())) return fail (NKP_ECOMM, "nkp_create_dist: allgather failed");
       for (int p = 0; p < P; p++) D.ras = D.ras || all[p] > 0;
       D.rings = D.ras ? (int) rings : 0;
+      smooth_lists ();                                        // 6. the fine-level exchange, if the ranks agreed on it
       return NKP_OK;
    }
 };
@@ -583,6 +621,12 @@ static bool dist_plan_field (const nkp_dist_plan *p, const char *what, const voi
       { "ras_give", D.ras_give.data (), (int64_t) D.ras_give.size (), 4 },
       { "origin", D.e_org.data (), (int64_t) D.e_org.size (), 4 }, { "ship", D.ship_e.data (), (int64_t) D.ship_e.size (), 4 },
       { "ent_give", D.ent_give.data (), (int64_t) D.ent_give.size (), 4 }, { "ent_need", D.ent_need.data (), (int64_t) D.ent_need.size (), 4 },
+      { "smooth_send_rows0", D.smooth_send_rows[0].data (), (int64_t) D.smooth_send_rows[0].size (), 4 },
+      { "smooth_send_rows1", D.smooth_send_rows[1].data (), (int64_t) D.smooth_send_rows[1].size (), 4 },
+      { "smooth_recv_rows0", D.smooth_recv_rows[0].data (), (int64_t) D.smooth_recv_rows[0].size (), 4 },
+      { "smooth_recv_rows1", D.smooth_recv_rows[1].data (), (int64_t) D.smooth_recv_rows[1].size (), 4 },
+      { "smooth_give0", D.smooth_give[0].data (), (int64_t) D.smooth_give[0].size (), 4 }, { "smooth_give1", D.smooth_give[1].data (), (int64_t) D.smooth_give[1].size (), 4 },
+      { "smooth_need0", D.smooth_need[0].data (), (int64_t) D.smooth_need[0].size (), 4 }, { "smooth_need1", D.smooth_need[1].data (), (int64_t) D.smooth_need[1].size (), 4 },
    };
    for (const F &f : fields)
       if (!strcmp (what, f.name)) { *ptr = f.ptr; *count = f.count; *elem = f.elem; return true; }
@@ -596,6 +640,7 @@ extern "C" int64_t nkp_dist_plan_size (const nkp_dist_plan *p, const char *what)
    if (!strcmp (what, "n_sel")) return p->D.n_sel;
    if (!strcmp (what, "n_halo")) return p->D.n_halo;
    if (!strcmp (what, "ras_rings")) return p->D.rings;
+   if (!strcmp (what, "smooth_exchange")) return p->D.smooth;
    const void *ptr; int64_t count; size_t elem;
    return dist_plan_field (p, what, &ptr, &count, &elem) ? count : -1;
 }

@@ -26,6 +26,13 @@ struct DistPlan {
    int rings = 0;
    std::vector<int32_t> ras_send_rows;
    std::vector<int> ras_need, ras_give;
+   // fine-level exchange (tuning dist_smooth_exchange, the smallest value any rank asked for; 0 without overlap): per colour
+   // c = (i + j) % 2 of the water columns' grid positions, the own local rows other ranks hold as overlap rows (all rings; by
+   // destination, ascending), the rows per rank both ways, and this rank's overlap rows of that colour as rows of the hierarchy's
+   // matrix (>= m_loc) in its order, which is the order they arrive in
+   int smooth = 0;
+   std::vector<int32_t> smooth_send_rows[2], smooth_recv_rows[2];
+   std::vector<int> smooth_give[2], smooth_need[2];
 };
 
 // Everything nkp_create_dist decides before a byte goes to the device.  Collective over the ranks through the host callbacks

@@ -28,7 +28,7 @@ void apply_precond_once (nkp_solver *s, const double *rin, double *zout)
          launch_copy (rin, s->dist.rext, s->n, s->stream);
          if (s->dist.n_sel) launch_gather (s->dist.sel_idx, s->dist.xe + s->n, s->dist.rext + s->n, s->dist.n_sel, s->stream);
       }
-      ml_apply (s->ml, s->dist.rext, s->dist.zext, s->stream);
+      ml_apply (s->ml, s->dist.rext, s->dist.zext, s->stream, smooth_hook_of (s));      // (tuning dist_smooth_exchange: + 4 nu - 1 exchanges)
       launch_copy (s->dist.zext, zout, s->n, s->stream);
    } else if (s->opt.precond == NKP_PRECOND_MULTILEVEL) ml_apply (s->ml, rin, zout, s->stream);
    else launch_colblock_apply_lanes (s->B, 0, s->B.ngrp, rin, zout, 0, s->stream);

@@ -1,7 +1,8 @@
 // Multilevel water-column preconditioner: the V(nu, nu) cycle on the hierarchy ml_setup built (multilevel.hip), for one
 // right-hand side and for K interleaved ones, and the measurement helpers of bench.py and the probes.  Launchers only: the
 // kernels are colblock.hip, col_lanes.hip, col_packed.hip, col_gs_fused.hip, col_gs_lanes.hip, diagop.hip, spmv.hip, blas1.hip,
-// batch.hip, dense.hip and mltail.hip.
+// batch.hip, dense.hip and mltail.hip.  The owner of the hierarchy may hang a hook behind the half sweeps of level 0
+// (MlSmoothHook in multilevel.h); without one -- every single-GPU cycle -- it is one pointer test per half sweep.
 #include "nkp_dev.h"
 #include "multilevel.h"
 
@@ -21,7 +22,15 @@ static void column_solves (const MlHierarchy &H, MlLevel &V, int c, const double
       launch_colblock_apply_lanes (V.B, V.color_grp[c], V.color_grp[c + 1], rhs, x, accumulate, st);
 }
 
-static void gs_half (const MlHierarchy &H, MlLevel &V, int c, bool fused, hipStream_t st)
+// The per-level hook behind a half sweep (MlSmoothHook): x holds the new values of colour c.  Level 0 only, and only while the
+// running cycle has level-0 half sweeps to come; nothing without a hook (every single-GPU cycle).
+static inline void after_half_sweep (MlHierarchy &H, const MlLevel &V, int c, double *x, int K, hipStream_t st)
+{
+   if (!H.hook || &V != &H.lev[0] || H.hook_left <= 0) return;
+   if (--H.hook_left > 0) H.hook->refresh (H.hook->ctx, c, x, K, st);
+}
+
+static void gs_half (MlHierarchy &H, MlLevel &V, int c, bool fused, hipStream_t st)
 {
    if (fused) {
       const int out = (V.cur[0] != V.cur[1]) ? V.cur[1 - c] : 1 - V.cur[c];
@@ -32,14 +41,16 @@ static void gs_half (const MlHierarchy &H, MlLevel &V, int c, bool fused, hipStr
       else if (V.wave_fused) launch_gs_wave (V.L, V.B, V.color_blk[c], V.color_blk[c + 1], V.xbuf (V.cur[0]), V.xbuf (V.cur[1]), rows0, V.b, V.xbuf (out), H.f32, st);
       else (void) launch_gs_fused (V.L, V.B, V.color_grp[c], V.color_grp[c + 1], V.xbuf (V.cur[0]), V.xbuf (V.cur[1]), rows0, V.b, V.xbuf (out), st);
       V.cur[c] = out;
+      after_half_sweep (H, V, c, V.xbuf (out), 1, st);      // the buffer the next half sweep reads colour c from
       return;
    }
    if (V.L.dg_val) launch_diag_residual (V.L, V.color_tile[c], V.color_tile[c + 1], V.x, V.b, V.r, st);
    else launch_csr_residual_range (V.L, V.color_rb[c], V.color_rb[c + 1], V.x, V.b, V.r, st);
    column_solves (H, V, c, V.r, V.x, 1, st);
+   after_half_sweep (H, V, c, V.x, 1, st);
 }
 
-static void gs_sweep (const MlHierarchy &H, MlLevel &V, bool reverse, bool fused, hipStream_t st)
+static void gs_sweep (MlHierarchy &H, MlLevel &V, bool reverse, bool fused, hipStream_t st)
 {
    for (int step = 0; step < 2; step++) gs_half (H, V, reverse ? 1 - step : step, fused, st);
 }
@@ -48,6 +59,7 @@ static void ml_cycle (MlHierarchy &H, int l, hipStream_t st)
 {
    MlLevel &V = H.lev[l];
    V.cur[0] = V.cur[1] = 0;
+   if (l == 0) H.hook_left = 0;
    if (l == H.tail_from && H.coarse_inv && H.gamma_to <= H.gamma_from && ml_tail_launch (H, l, st) == 0) return;
    if (l == (int) H.lev.size () - 1) {
       if (H.coarse_inv) {
@@ -64,6 +76,8 @@ static void ml_cycle (MlHierarchy &H, int l, hipStream_t st)
       return;
    }
    const bool fused = ml_level_fused (H, V);
+   const int nu = (l >= H.coarse_from) ? H.nu_coarse : H.nu;
+   if (l == 0 && H.hook) H.hook_left = 4 * nu;      // 2 nu half sweeps before and 2 nu after the coarse correction
    // pre-smoothing from x = 0: the first half-sweep needs no SpMV (r = b on colour 0)
    launch_fill (V.x, 0.0, V.n, st);
    if (fused) {
@@ -72,12 +86,13 @@ static void ml_cycle (MlHierarchy &H, int l, hipStream_t st)
       if (V.wave_fused) column_solves (H, V, 0, V.b, V.x2, 0, st);
       else launch_colblock_apply_lanes (V.B, V.color_grp[0], V.color_grp[1], V.b, V.x2, 0, st);
       V.cur[0] = 1;
+      after_half_sweep (H, V, 0, V.x2, 1, st);
       gs_half (H, V, 1, true, st);
    } else {
       column_solves (H, V, 0, V.b, V.x, 0, st);
+      after_half_sweep (H, V, 0, V.x, 1, st);
       gs_half (H, V, 1, false, st);
    }
-   const int nu = (l >= H.coarse_from) ? H.nu_coarse : H.nu;
    for (int s = 1; s < nu; s++) gs_sweep (H, V, false, fused, st);
    // coarse-grid correction; levels in [gamma_from, gamma_to) repeat it on the updated residual, which by the
    // Galerkin property is the second coarse iteration of a W-cycle (NKP_ML_GAMMA_FROM / NKP_ML_GAMMA_TO, default off)
@@ -93,11 +108,13 @@ static void ml_cycle (MlHierarchy &H, int l, hipStream_t st)
    for (int s = 0; s < nu; s++) gs_sweep (H, V, true, fused, st);
 }
 
-void ml_apply (MlHierarchy &H, const double *r, double *z, hipStream_t st)
+void ml_apply (MlHierarchy &H, const double *r, double *z, hipStream_t st, const MlSmoothHook *hook)
 {
    MlLevel &V = H.lev[0];
    launch_gather (H.perm0, r, V.b, V.n, st);
+   H.hook = hook;
    ml_cycle (H, 0, st);
+   H.hook = nullptr;
    launch_scatter (H.perm0, V.xnow (), z, V.n, st);
 }
 
@@ -146,16 +163,18 @@ static void column_solves_batch (const MlHierarchy &H, MlLevel &V, int K, int c,
       launch_colblock_apply_wave_batch (K, V.B, V.color_blk[c], V.color_blk[c + 1], rhs, x, accumulate, H.f32, st);
 }
 
-static void gs_half_batch (const MlHierarchy &H, MlLevel &V, int K, int c, hipStream_t st)
+static void gs_half_batch (MlHierarchy &H, MlLevel &V, int K, int c, hipStream_t st)
 {
    if (V.wave_fused) {
       const int out = (V.bcur[0] != V.bcur[1]) ? V.bcur[1 - c] : 1 - V.bcur[c];
       launch_gs_wave_batch (K, V.L, V.B, V.color_blk[c], V.color_blk[c + 1], V.bxbuf (V.bcur[0]), V.bxbuf (V.bcur[1]), (int) V.rows0, V.bb, V.bxbuf (out), H.f32, st);
       V.bcur[c] = out;
+      after_half_sweep (H, V, c, V.bxbuf (out), K, st);
       return;
    }
    launch_csr_spmv_batch (K, V.L, V.color_rb[c], V.color_rb[c + 1], V.bx, V.br, V.bb, 1, st);
    column_solves_batch (H, V, K, c, V.br, V.bx, 1, st);
+   after_half_sweep (H, V, c, V.bx, K, st);
 }
 
 static void ml_cycle_batch (MlHierarchy &H, int K, int l, hipStream_t st)
@@ -163,6 +182,7 @@ static void ml_cycle_batch (MlHierarchy &H, int K, int l, hipStream_t st)
    MlLevel &V = H.lev[l];
    const int64_t nk = V.n * K;
    V.bcur[0] = V.bcur[1] = 0;
+   if (l == 0) H.hook_left = 0;
    if (l == (int) H.lev.size () - 1) {
       if (H.coarse_inv) {
          if (H.coarse_invf) launch_dense_matvec_f32_batch (K, H.coarse_invf, H.coarse_ldf, V.bb, V.bx, (int) V.n, st);
@@ -182,16 +202,19 @@ static void ml_cycle_batch (MlHierarchy &H, int K, int l, hipStream_t st)
          }
       return;
    }
+   const int nu = (l >= H.coarse_from) ? H.nu_coarse : H.nu;
+   if (l == 0 && H.hook) H.hook_left = 4 * nu;
    launch_fill (V.bx, 0.0, nk, st);
    if (V.wave_fused) {
       column_solves_batch (H, V, K, 0, V.bb, V.bx2, 0, st);
       V.bcur[0] = 1;
+      after_half_sweep (H, V, 0, V.bx2, K, st);
       gs_half_batch (H, V, K, 1, st);
    } else {
       column_solves_batch (H, V, K, 0, V.bb, V.bx, 0, st);
+      after_half_sweep (H, V, 0, V.bx, K, st);
       gs_half_batch (H, V, K, 1, st);
    }
-   const int nu = (l >= H.coarse_from) ? H.nu_coarse : H.nu;
    for (int s = 1; s < nu; s++) { gs_half_batch (H, V, K, 0, st); gs_half_batch (H, V, K, 1, st); }
    MlLevel &C = H.lev[l + 1];
    const int gamma = (l >= H.gamma_from && l < H.gamma_to) ? 2 : 1;
@@ -228,12 +251,14 @@ void ml_apply_batch_split (MlHierarchy &H, int K, const double *const *src, doub
 // rows, whose residuals are the K-interleaved halo rows halo[sel[.] * K + k] (sel NULL: halo is the K-interleaved block of the
 // overlap rows in their own order); z and dst receive the own rows only
 void ml_apply_batch_split_ext (MlHierarchy &H, int K, const double *const *src, const double *halo, const int *sel, int64_t n_own, double *z,
-                               double *const *dst, hipStream_t st)
+                               double *const *dst, hipStream_t st, const MlSmoothHook *hook)
 {
    MlLevel &V = H.lev[0];
    if (sel) launch_gather_interleave_ext (K, H.perm0, src, halo, sel, n_own, V.bb, V.n, st);
    else launch_gather_interleave_ext_block (K, H.perm0, src, halo, n_own, V.bb, V.n, st);
+   H.hook = hook;
    ml_cycle_batch (H, K, 0, st);
+   H.hook = nullptr;
    launch_scatter_split_own (K, H.perm0, V.bxnow (), z, dst, n_own, V.n, st);
 }
 

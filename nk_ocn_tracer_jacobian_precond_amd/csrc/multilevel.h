@@ -37,8 +37,19 @@ struct MlLevel {
    double *xnow () { return xbuf (cur[0]); }      // valid when coherent
 };
 
+// What the owner of a hierarchy may hang on one application of the cycle: `refresh` runs after every Gauss-Seidel half sweep of
+// level 0 except the cycle's last, with the colour just swept and the level-0 vector (K interleaved ones) that holds that colour's
+// new values -- the buffer the next half sweep reads the colour from.  A row-distributed solver overwrites the overlap rows of
+// that colour with their owners' values there (smooth_exchange.hip); the hierarchy itself knows nothing of ranks or transports.
+struct MlSmoothHook {
+   void (*refresh) (void *ctx, int colour, double *x, int K, hipStream_t st);
+   void *ctx;
+};
+
 struct MlHierarchy {
    std::vector<MlLevel> lev;
+   const MlSmoothHook *hook = nullptr;   // set by ml_apply / ml_apply_batch_split_ext for the one application they run
+   int hook_left = 0;           // level-0 half sweeps of the running cycle still to come
    int *perm0 = nullptr;        // level-0 row i holds original row perm0[i]
    double *coarse_inv = nullptr;   // dense inverse of the coarsest operator (row-major)
    float *coarse_invf = nullptr;   // f32 storage mode: the copy the cycle multiplies with (rows padded to coarse_ldf)
@@ -79,15 +90,19 @@ void ml_free (MlHierarchy &H);
 // routine), -2 (no memory), -4 (singular)
 int ml_coarse_inverse (const MlHierarchy &H, int n, const int *prow, const int *pcol, const double *pval, double **inv, float **invf,
                        int *ldf, size_t *bytes, hipStream_t st);
-// z = V-cycle(r) in the ORIGINAL row order
-void ml_apply (MlHierarchy &H, const double *r, double *z, hipStream_t st);
+// the level-0 sweeps before (and after) the coarse correction, and whether level 0 runs the half sweeps a hook follows (it is
+// neither the last level nor part of the single-launch tail)
+inline int ml_level0_sweeps (const MlHierarchy &H) { return 0 >= H.coarse_from ? H.nu_coarse : H.nu; }
+inline bool ml_level0_hookable (const MlHierarchy &H) { return H.lev.size () >= 2 && H.tail_from != 0 && ml_level0_sweeps (H) > 0; }
+// z = V-cycle(r) in the ORIGINAL row order; hook: see MlSmoothHook (NULL = none)
+void ml_apply (MlHierarchy &H, const double *r, double *z, hipStream_t st, const MlSmoothHook *hook = nullptr);
 // the same cycle on K interleaved right-hand sides (r, z: n * K doubles, element (row, k) at row * K + k; K = 2 or 4); every
 // column gets the bits ml_apply gives it alone.  ml_batch_prepare allocates the level vectors (0, or -2 = out of device memory).
 int ml_batch_prepare (MlHierarchy &H, int K);
 void ml_apply_batch (MlHierarchy &H, int K, const double *r, double *z, hipStream_t st);
 void ml_apply_batch_split (MlHierarchy &H, int K, const double *const *src, double *z, double *const *dst, hipStream_t st, const double *src_scale = nullptr);
 void ml_apply_batch_split_ext (MlHierarchy &H, int K, const double *const *src, const double *halo, const int *sel, int64_t n_own, double *z,
-                               double *const *dst, hipStream_t st);
+                               double *const *dst, hipStream_t st, const MlSmoothHook *hook = nullptr);
 // measurement helpers: launch one piece of a level-0 half sweep (0 residual rows, 1 column solves); compulsory HBM bytes of
 // that piece or of the whole cycle (2)
 void ml_time_piece (MlHierarchy &H, int which, hipStream_t st);

@@ -165,6 +165,12 @@ static int refactor_commit (nkp_solver *s, bool rebuilt, MlHierarchy &H2, char *
       s->ml = H2;
       s->device_bytes += s->ml.device_bytes;
       s->device_bytes -= rf_free_maps (W);
+      // the fine-level exchange addresses level-0 positions, and the new hierarchy has its own perm0; a new level 0 that runs
+      // other sweeps than the ranks agreed on would leave the peers waiting in an exchange
+      if (s->dist.smooth && (!ml_level0_hookable (s->ml) || smooth_build_lists (s) != 0)) {
+         rc = -3;
+         snprintf (err, errlen, "the index lists of the fine-level exchange could not be rebuilt for the new hierarchy");
+      }
    } else if (multilevel) {
       int replaced = 0;
       const size_t before = s->ml.device_bytes;

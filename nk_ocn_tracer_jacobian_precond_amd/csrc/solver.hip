@@ -58,6 +58,7 @@ void solver_free (nkp_solver *s)
    if (s->dist.sel_idx) (void) hipFree (s->dist.sel_idx);
    if (s->dist.ras_send_idx) (void) hipFree (s->dist.ras_send_idx);
    if (s->dist.ras_sendbuf) (void) hipFree (s->dist.ras_sendbuf);
+   smooth_release (s);
    if (s->dist.rext) (void) hipFree (s->dist.rext);
    if (s->dist.zext) (void) hipFree (s->dist.zext);
    for (double *p : { s->dist.bxe, s->dist.bsend, s->dist.gmsg, s->dist.bras_send, s->dist.bras_recv })
@@ -129,6 +130,8 @@ extern "C" int64_t nkp_get_int (nkp_solver *s, const char *key)
    if (!strcmp (key, "dist_ras_rows")) return s->dist.n_sel;
    if (!strcmp (key, "dist_ras_rings")) return s->dist.ras ? s->dist.ras_rings : 0;
    if (!strcmp (key, "dist_halo_rows")) return s->dist.n_halo;
+   if (!strcmp (key, "dist_smooth_exchange")) return s->dist.smooth ? 1 : 0;
+   if (!strcmp (key, "dist_smooth_rows")) return s->dist.smooth ? s->dist.n_sel : 0;
    // rows received per preconditioner application: the SpMV halo with one ring, the overlap rows alone with more
    if (!strcmp (key, "dist_ras_recv_rows")) return !s->dist.ras ? 0 : s->dist.ras_sep ? s->dist.n_sel : s->dist.n_halo;
    if (!strcmp (key, "dist_interior_rowblocks")) return s->dist.seg_rb[2] - s->dist.seg_rb[1];

@@ -5,6 +5,7 @@
 //   krylov.hip          one right-hand side: operator and preconditioner of a solve, FGMRES, BiCGStab, nkp_solve
 //   krylov_host.cpp     the host arithmetic of FGMRES (krylov_host.h): no HIP, no solver object
 //   batch_solve.hip     K right-hand sides in lockstep (nkp_solve_batch_device); the kernels are batch.hip
+//   smooth_exchange.hip the fine-level exchange of a row-distributed cycle (tuning dist_smooth_exchange): kernels, lists, the cycle's hook
 //   inspect.hip         entry points of tests and timing (arrays of the hierarchy and the matrix, single products, nkp_time_kernel)
 //   refactor_api.hip, transpose*.hip, valgrad_api.hip, valprod_api.hip      new values, A^T, gradient and product by values
 // What crosses units is declared once, below, under the unit that defines it.  Private to the library: nothing here is part of
@@ -70,6 +71,18 @@ struct nkp_solver {
       int *ras_send_idx = nullptr;
       double *ras_sendbuf = nullptr, *bras_send = nullptr, *bras_recv = nullptr;
       std::vector<int> ras_send_counts, ras_recv_counts, ras_send_counts_k, ras_recv_counts_k;
+      // fine-level exchange (tuning dist_smooth_exchange; smooth_exchange.hip): after a level-0 half sweep of colour c the overlap
+      // rows of that colour take their owners' x.  Per colour: the plan's rows in host memory (own local rows sent by destination;
+      // overlap rows as rows of the hierarchy's matrix, in arrival order), the same as level-0 positions on the device (rebuilt
+      // with the hierarchy: perm0 changes), the per-rank counts; one send and one receive buffer for the larger colour, and
+      // their K-wide twins (batch_prepare_exchange)
+      bool smooth = false;
+      MlSmoothHook smooth_hook = { nullptr, nullptr };
+      std::vector<int32_t> h_smooth_send[2], h_smooth_recv[2];
+      int *smooth_send_idx[2] = { nullptr, nullptr }, *smooth_recv_idx[2] = { nullptr, nullptr };
+      std::vector<int> smooth_send_counts[2], smooth_recv_counts[2], smooth_send_counts_k[2], smooth_recv_counts_k[2];
+      int64_t smooth_nsend_max = 0, smooth_nrecv_max = 0;
+      double *smooth_sendbuf = nullptr, *smooth_recvbuf = nullptr, *bsmooth_send = nullptr, *bsmooth_recv = nullptr;
       // K right-hand sides in lockstep: the K-interleaved operator input [own rows | halo rows] x K, the
       // K-wide send rows, the plan's counts times K, and the group's Gram-Schmidt messages
       // gmsg = dots [K x (m + 2)] | second pass [K x (m + 2)] | norms [K] | 1 / norms [K], ghpin its pinned host mirror
@@ -326,6 +339,18 @@ NKP_PRIVATE int batch_prepare_exchange (nkp_solver *s, int K);
 // Row-distributed solvers: every rank learns whether any rank's step failed, and all leave together.  A rank whose own step
 // failed returns its code and message, every other rank NKP_ECOMM naming it; a failed allgather is NKP_ECOMM everywhere.
 NKP_PRIVATE int dist_agree (nkp_solver *s, int local_rc, const char *who, const char *where);
+// ---- defined in smooth_exchange.hip ----------------------------------------------------------------------------------------
+// the fine-level exchange of a row-distributed solver (tuning dist_smooth_exchange).  smooth_install: the plan's lists, counts
+// and one-vector buffers into s->dist (nkp_create_dist; false = out of device memory).  smooth_build_lists: the device index
+// lists in level-0 positions from the hierarchy s->ml holds now -- after ml_setup and after every rebuild (0, -2 no memory, -3 HIP
+// failure or a hierarchy that is not the plan's).  smooth_hook_of: what the cycle applications of s take (NULL when not in force)
+NKP_PRIVATE bool smooth_install (nkp_solver *s, const DistPlan &D);
+NKP_PRIVATE int smooth_build_lists (nkp_solver *s);
+NKP_PRIVATE const MlSmoothHook *smooth_hook_of (nkp_solver *s);
+NKP_PRIVATE void smooth_release (nkp_solver *s);
+// one thread per row: out[i] = x[idx[i]] / x[idx[i]] = in[i], K interleaved vectors (K = 1, 2, 4, 8)
+NKP_PRIVATE void launch_smooth_pack (int K, const int *idx, const double *x, double *out, int64_t nrows, hipStream_t st);
+NKP_PRIVATE void launch_smooth_unpack (int K, const int *idx, const double *in, double *x, int64_t nrows, hipStream_t st);
 // ---- defined in valgrad_api.hip --------------------------------------------------------------------------------------------
 NKP_PRIVATE void valgrad_release (nkp_solver *s);
 // nkp_time_kernel, which = 5: scratch operands for the gradient kernel at interleave width K (1, 2, 4, 8), then one launch

@@ -132,9 +132,11 @@ def overlap_plan_host(loc, n_global, comm, coupled_tracer_cnt=1, tuning=None):
                                         int(bs.size - 1), int(coupled_tracer_cnt), C.cast(C.byref(comm.ops), C.c_void_p))
     if rc != 0:
         raise _solver.NkpError(rc, lib.nkp_last_error().decode() + (" | comm: " + "; ".join(comm.errors) if comm.errors else ""))
-    out = {k: int(lib.nkp_dist_plan_size(h, k.encode())) for k in ("ras", "ras_rings", "n_sel", "n_halo")}
+    out = {k: int(lib.nkp_dist_plan_size(h, k.encode())) for k in ("ras", "ras_rings", "n_sel", "n_halo", "smooth_exchange")}
     for name in ("colind_ext", "halo_rows", "send_rows", "need", "give", "rowptr", "colind", "val", "blk_start", "col_i", "col_j", "col_t", "sel_hpos",
-                 "ras_send_rows", "ras_need", "ras_give", "origin", "ship", "ent_give", "ent_need"):
+                 "ras_send_rows", "ras_need", "ras_give", "origin", "ship", "ent_give", "ent_need",
+                 "smooth_send_rows0", "smooth_send_rows1", "smooth_recv_rows0", "smooth_recv_rows1", "smooth_give0", "smooth_give1",
+                 "smooth_need0", "smooth_need1"):
         cnt = int(lib.nkp_dist_plan_size(h, name.encode()))
         arr = np.empty(max(cnt, 0), np.float64 if name == "val" else np.int32)
         if cnt > 0:

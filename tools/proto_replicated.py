@@ -5,7 +5,10 @@ of levels l < k lose every coupling between rows of different bands (what per-ra
 (what levels replicated on all ranks would do).  k = number of levels = today's per-rank hierarchies without overlap,
 k = 0 = the single-domain cycle.
 
-  python tools/proto_replicated.py [--grid 100x116x60] [--bands 2,4] [--refine 4]
+  python tools/proto_replicated.py [--grid 100x116x60] [--bands 2,4] [--refine 4] [--reverse]
+
+--reverse turns the split round (levels < k whole, levels >= k cut): how much a fine level that smooths across the cut buys
+while every coarser level stays cut (--grid 60x70x30 --refine 4: DESIGN.md section 7, "fine-level exchange").
 """
 import argparse, copy, os, sys, time
 import numpy as np
@@ -35,6 +38,7 @@ def main():
     ap.add_argument("--bands", default="2,4")
     ap.add_argument("--refine", type=float, default=4.0)
     ap.add_argument("--maxit", type=int, default=400)
+    ap.add_argument("--reverse", action="store_true", help="the opposite split: levels < k whole, levels >= k cut (k = 0: every level cut)")
     a = ap.parse_args()
     imt, jmt, km = (int(t) for t in a.grid.split("x"))
     p = synth.generate(imt=imt, jmt=jmt, km=km, adv="upwind3", hmix="isop", seed=0, u_scale=3.0 * a.refine, ah=4.0e6 * a.refine ** 2)
@@ -59,15 +63,19 @@ def main():
             first = P.indices[P.indptr[:-1]]                   # a fine row of every coarse cell
             bands_l.append(bands_l[-1][first])
         for k in range(len(levels), -1, -1):
-            mixed = [cut_level(lv, bands_l[l]) if l < k else lv for l, lv in enumerate(levels)]
-            if k == len(levels):
+            # --reverse: the fine levels whole and the coarse ones cut -- what a fine-level exchange (tuning dist_smooth_exchange,
+            # DESIGN.md section 7) can reach without replicating anything; no overlap on the cut levels here
+            is_cut = [(l >= k) if a.reverse else (l < k) for l in range(len(levels))]
+            mixed = [cut_level(lv, bands_l[l]) if is_cut[l] else lv for l, lv in enumerate(levels)]
+            if is_cut[-1]:
                 C = levels[-1].A.tocoo()
                 keep = bands_l[-1][C.row] == bands_l[-1][C.col]
                 D = sp.csr_matrix((C.data[keep], (C.row[keep], C.col[keep])), shape=C.shape).toarray()
                 mixed[-1] = copy.copy(levels[-1]); mixed[-1].dense_inv = np.linalg.inv(D)
             t0 = time.perf_counter()
             x, its, rr = fgmres(A, b, lambda r: mlr.cycle(mixed, 0, r.copy()), maxit=a.maxit)
-            print(f"bands {nb}: levels < {k} cut, levels >= {k} global: {its} iterations, relres {rr:.2e}, {time.perf_counter() - t0:.0f} s", flush=True)
+            what = f"levels < {k} global, levels >= {k} cut" if a.reverse else f"levels < {k} cut, levels >= {k} global"
+            print(f"bands {nb}: {what}: {its} iterations, relres {rr:.2e}, {time.perf_counter() - t0:.0f} s", flush=True)
 
 
 if __name__ == "__main__":
