@@ -54,7 +54,8 @@ enum nkp_krylov { NKP_KRYLOV_FGMRES = 0, NKP_KRYLOV_BICGSTAB = 1 };
 enum {
    NKP_OK = 0,
    NKP_NOT_CONVERGED = 1,    /* max_iters reached; x holds the best iterate, NOT written by the CLIs */
-   NKP_BREAKDOWN = 2,
+   NKP_BREAKDOWN = 2,        /* the iteration broke down, or the system was not solved at all: a right-hand side or an initial
+                                guess the solve refuses (see nkp_solve); x is NOT written by the CLIs */
    NKP_OK_BERR = 3,          /* ||b-Ax||/||b|| stopped above rtol at the attainable f64 accuracy, but the componentwise
                                 backward error is <= max (1e-14, rtol/100); x is written; callers decide (the CLIs accept it
                                 only with NKP_ACCEPT_BERR=1 in the environment) */
@@ -269,7 +270,29 @@ int nkp_create64 (nkp_solver **out, const nkp_options *opt, int64_t n, const int
  * backward error -- the accuracy measure the reference itself reports (berr, src/solve_ABglobal.c:396-398) -- is
  * <= max (1e-14, rtol / 100), else NKP_NOT_CONVERGED.
  * nrhs >= 2 right-hand sides share the sweeps and, on a row-distributed solver, the collectives of every Krylov step
- * (nkp_solve_batch_device below; there the call is collective: the same nrhs on every rank, ldb >= m_loc). */
+ * (nkp_solve_batch_device below; there the call is collective: the same nrhs on every rank, ldb >= m_loc).
+ *
+ * Vectors the solve refuses.  With ||b||^2 (the f64 sum of squares) and target = max (rtol ||b||, atol):
+ *    - inside the range -- ||b||^2 finite and target >= 2^-480 (3.2e-145) -- the solve iterates; there a power of two on b is
+ *      the same power of two on x, bit for bit, with the same iters, relres and berr.  (The floor is derived, not measured:
+ *      target^2 < 2^-960 is 62 binary orders above the smallest normal number, so a sum of squares at the target loses less
+ *      than 2^-62 of itself per term to underflow.)  ||b||^2 = 0 with atol >= 2^-480 is ||b|| < atol: x = 0, NKP_OK.
+ *    - outside it the entries of b are counted (a counting kernel and, row-distributed, one more allreduce; all ranks take this
+ *      path together since ||b||^2 is global).  No non-finite and no non-zero entry: b = 0, x = 0 with NKP_OK, relres 0.
+ *      Anything else is NOT solved: NKP_BREAKDOWN with iters 0, relres NaN, berr NaN and EVERY entry of x NaN -- on the
+ *      device and in the host array of nkp_solve, which copies x back for every status >= 0 -- and nkp_last_error says
+ *      that the right-hand side "holds a non-finite entry" or "is outside the range" of the solve.  It is a status, not an
+ *      error code: one bad column of several does not stop the others, and the call returns the worst status of its columns.
+ *      Rescale such a system (b 2^k has the solution x 2^k).
+ *    - a non-finite initial guess (nkp_solve_device with use_guess), or a residual norm that overflows on the way, is
+ *      NKP_BREAKDOWN with relres NaN; with the non-finite guess berr is NaN too.
+ * Every driver takes the decision from one host routine (rhs_verdict, csrc/krylov_host.cpp): FGMRES, BiCGStab, the batched
+ * members, and through them the transposed solver and nkp_solve_tangent.
+ * berr is NaN as soon as one entry of b - A x or of |A||x| + |b| is NaN (Inf / Inf included); otherwise the rule above.  On a
+ * row-distributed solver the maximum is taken across ranks by the allreduce of the transport, and what that makes of a NaN is
+ * up to the transport: there only the status and x are promised.
+ * Matrix values must be finite, at nkp_create and at nkp_refactor alike; they are NOT checked, and what a solve with a NaN
+ * or an Inf in A returns is not specified (a status and numbers, no fault). */
 int nkp_solve (nkp_solver *s, double *b_in_x_out, int nrhs, int64_t ldb,
                double *berr, int *iters, double *relres);
 

@@ -419,7 +419,8 @@ extern "C" int nkp_solve_batch_device (nkp_solver *s, int nrhs, const void *d_B,
          if (relres) relres[c0 + k] = F[k].relres;
          msg (s, 1, "nkp_solve_batch: right-hand side %d: %s after %d iterations, ||b-Ax||/||b|| = %.3e\n", c0 + k,
               status == NKP_OK ? "converged" : status == NKP_OK_BERR ? "at the attainable accuracy (backward error accepted)" : status == NKP_BREAKDOWN ? "breakdown" : "NOT converged", F[k].its, F[k].relres);
-         if (status != NKP_OK) fail (status, "nkp_solve_batch: right-hand side %d: %s after %d iterations (relres %.3e, rtol %.1e)", c0 + k,
+         if (q->rhs_class == RHS_NONFINITE || q->rhs_class == RHS_OUT_OF_RANGE) rhs_refused (q->rhs_class, ("nkp_solve_batch: right-hand side " + std::to_string (c0 + k)).c_str ());
+         else if (status != NKP_OK) fail (status, "nkp_solve_batch: right-hand side %d: %s after %d iterations (relres %.3e, rtol %.1e)", c0 + k,
                                      status == NKP_OK_BERR ? "stopped above rtol at the attainable accuracy" : status == NKP_BREAKDOWN ? "breakdown" : "not converged", F[k].its, F[k].relres, s->opt.rtol);
          if (sev_of (status) > sev_of (worst)) worst = status;
          HIPCHK (hipMemcpyAsync (X + (size_t) (c0 + k) * (size_t) ldb, q->x, bytes, hipMemcpyDeviceToDevice, s->stream));

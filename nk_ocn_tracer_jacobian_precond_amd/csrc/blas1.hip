@@ -372,6 +372,13 @@ void launch_dot (const double *x, const double *y, int64_t n, double *partial, d
    hipLaunchKernelGGL (sum_partials_kernel, dim3 (1), dim3 (NKP_WAVE), 0, st, partial, g, out);
 }
 
+// The larger of two quotients, NaN sticky: a NaN on either side wins (a plain q > m ? q : m drops it), so that a residual or a
+// denominator that is not a number gives a backward error that is not one either, through every stage of the reduction.
+__device__ __forceinline__ double max_or_nan (double q, double m)
+{
+   return (q > m || q != q) ? q : m;
+}
+
 __global__ __launch_bounds__ (B1_THREADS)
 void berr_kernel (const double *__restrict__ r, const double *__restrict__ den, int64_t n, double *__restrict__ partial)
 {
@@ -380,18 +387,16 @@ void berr_kernel (const double *__restrict__ r, const double *__restrict__ den, 
    const int64_t stride = (int64_t) gridDim.x * B1_THREADS;
    for (int64_t i = (int64_t) blockIdx.x * B1_THREADS + threadIdx.x; i < n; i += stride) {
       const double a = fabs (r[i]), d = den[i];
-      const double q = (d > 0.0) ? a / d : (a > 0.0 ? 1.0e300 : 0.0);
-      m = q > m ? q : m;
+      // a / d keeps a NaN of either and makes one of Inf / Inf; d == 0 (an empty row with b_i = 0) follows the old rule
+      const double q = (d > 0.0 || d != d) ? a / d : (a != a ? a : a > 0.0 ? 1.0e300 : 0.0);
+      m = max_or_nan (q, m);
    }
-   for (int off = NKP_WAVE / 2; off > 0; off >>= 1) {
-      const double o = __shfl_down (m, off);
-      m = o > m ? o : m;
-   }
+   for (int off = NKP_WAVE / 2; off > 0; off >>= 1) m = max_or_nan (__shfl_down (m, off), m);
    const int lane = threadIdx.x & (NKP_WAVE - 1), wv = threadIdx.x / NKP_WAVE;
    if (lane == 0) sh[wv] = m;
    __syncthreads ();
    if (threadIdx.x == 0) {
-      for (int w = 1; w < B1_THREADS / NKP_WAVE; w++) m = sh[w] > m ? sh[w] : m;
+      for (int w = 1; w < B1_THREADS / NKP_WAVE; w++) m = max_or_nan (sh[w], m);
       partial[blockIdx.x] = m;
    }
 }
@@ -400,11 +405,8 @@ __global__ __launch_bounds__ (NKP_WAVE)
 void max_partials_kernel (const double *__restrict__ partial, int nblk, double *__restrict__ out)
 {
    double m = 0.0;
-   for (int b = threadIdx.x; b < nblk; b += NKP_WAVE) m = partial[b] > m ? partial[b] : m;
-   for (int off = NKP_WAVE / 2; off > 0; off >>= 1) {
-      const double o = __shfl_down (m, off);
-      m = o > m ? o : m;
-   }
+   for (int b = threadIdx.x; b < nblk; b += NKP_WAVE) m = max_or_nan (partial[b], m);
+   for (int off = NKP_WAVE / 2; off > 0; off >>= 1) m = max_or_nan (__shfl_down (m, off), m);
    if (threadIdx.x == 0) out[0] = m;
 }
 
@@ -413,6 +415,34 @@ void launch_berr (const double *r, const double *den, int64_t n, double *partial
    const int g = red_grid (n);
    hipLaunchKernelGGL (berr_kernel, dim3 (g), dim3 (B1_THREADS), 0, st, r, den, n, partial);
    hipLaunchKernelGGL (max_partials_kernel, dim3 (1), dim3 (NKP_WAVE), 0, st, partial, g, out);
+}
+
+// out[0] = entries of x that are NaN or Inf, out[1] = entries that are not zero (those included), as doubles: exact below 2^53,
+// and a row-distributed solver adds them across ranks like any other sum.  Only for a right-hand side whose norm has left the
+// range in which it decides alone (krylov.hip, classify_rhs).  partial: 2 * NKP_RED_BLOCKS doubles.
+__global__ __launch_bounds__ (B1_THREADS)
+void count_entries_kernel (const double *__restrict__ x, int64_t n, double *__restrict__ partial)
+{
+   __shared__ double sh[B1_THREADS / NKP_WAVE];
+   double bad = 0.0, set = 0.0;
+   const int64_t stride = (int64_t) gridDim.x * B1_THREADS;
+   for (int64_t i = (int64_t) blockIdx.x * B1_THREADS + threadIdx.x; i < n; i += stride) {
+      const double v = x[i];
+      bad += (v - v == 0.0) ? 0.0 : 1.0;
+      set += (v == 0.0) ? 0.0 : 1.0;
+   }
+   const double sb = block_sum (bad, sh);
+   if (threadIdx.x == 0) partial[blockIdx.x] = sb;
+   const double ss = block_sum (set, sh);
+   if (threadIdx.x == 0) partial[NKP_RED_BLOCKS + blockIdx.x] = ss;
+}
+
+void launch_count_entries (const double *x, int64_t n, double *partial, double *out, hipStream_t st)
+{
+   const int g = red_grid (n);
+   hipLaunchKernelGGL (count_entries_kernel, dim3 (g), dim3 (B1_THREADS), 0, st, x, n, partial);
+   hipLaunchKernelGGL (sum_partials_kernel, dim3 (1), dim3 (NKP_WAVE), 0, st, partial, g, out);
+   hipLaunchKernelGGL (sum_partials_kernel, dim3 (1), dim3 (NKP_WAVE), 0, st, partial + NKP_RED_BLOCKS, g, out + 1);
 }
 
 // ---------------------------------------------------------------- Hessenberg column epilogue

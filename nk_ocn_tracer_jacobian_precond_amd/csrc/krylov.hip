@@ -134,6 +134,37 @@ void arnoldi_step_device (nkp_solver *s, int j)
 
 // ---------------------------------------------------------------- FGMRES as a state machine
 // The device work around the host arithmetic of krylov_host.cpp, which takes every decision (FgmresState: krylov_host.h).
+
+// what nkp_last_error says of a right-hand side that was not solved (solver_impl.h)
+int rhs_refused (int verdict, const char *what)
+{
+   if (verdict == RHS_NONFINITE) return fail (NKP_BREAKDOWN, "%s holds a non-finite entry (NaN or Inf): not solved, x is NaN", what);
+   return fail (NKP_BREAKDOWN, "%s is outside the range of the solve (||b||^2 finite in f64 and max (rtol ||b||, atol) >= 2^-480 = 3.2e-145): "
+                               "not solved, x is NaN; scale the system", what);
+}
+
+// The verdict on the right-hand side in s->b (rhs_verdict of krylov_host.cpp; nkp.h at nkp_solve), kept in s->rhs_class for
+// the message of the solve.  b = 0 leaves x = 0, a right-hand side that is not solved leaves x = NaN.  Only outside the range
+// in which ||b||^2 and the target decide alone are the entries of b counted; row-distributed, ||b||^2 is global, so all ranks
+// take that path together and the two counts are added across them.
+static int classify_rhs (nkp_solver *s, double bnorm2, double target, int *verdict)
+{
+   double nonfinite = 0.0, nonzero = 0.0;
+   if (rhs_needs_counts (bnorm2, target)) {
+      launch_count_entries (s->b, s->n, s->partial, s->misc_dev () + 4, s->stream);
+      allreduce_dev (s, s->misc_dev () + 4, 2, 0);
+      HIPCHK (hipMemcpyAsync (s->hpin, s->misc_dev () + 4, 2 * sizeof (double), hipMemcpyDeviceToHost, s->stream));
+      HIPCHK (hipStreamSynchronize (s->stream));
+      if (s->comm_failed) return fail (NKP_ECOMM, "nkp_solve: a collective of the distributed solve failed");
+      nonfinite = s->hpin[0];
+      nonzero = s->hpin[1];
+   }
+   s->rhs_class = *verdict = rhs_verdict (bnorm2, target, nonfinite, nonzero);
+   if (*verdict == RHS_ZERO) launch_fill (s->x, 0.0, s->n, s->stream);
+   else if (*verdict != RHS_ORDINARY) launch_fill (s->x, NAN, s->n, s->stream);
+   return NKP_OK;
+}
+
 int fg_begin (nkp_solver *s, FgmresState &F)
 {
    fg_init (F, s->m);
@@ -141,16 +172,16 @@ int fg_begin (nkp_solver *s, FgmresState &F)
    int rc = dot_host (s, s->b, s->b, &bnorm2);
    if (rc) return rc;
    F.bnorm = sqrt (bnorm2);
+   F.target = fmax (s->opt.rtol * F.bnorm, s->opt.atol);
    s->stagnated = false;
    s->steps_now = s->precond_steps;      // the run-time guard of fg_restart lowers it for this solve only
-   if (!(F.bnorm > 0.0)) {         // b == 0 -> x = 0
-      launch_fill (s->x, 0.0, s->n, s->stream);
+   int verdict = RHS_ORDINARY;
+   if ((rc = classify_rhs (s, bnorm2, F.target, &verdict))) return rc;
+   if (verdict != RHS_ORDINARY) {
       F.finished = true;
-      F.status = NKP_OK;
-      F.relres = 0.0;
-      return NKP_OK;
+      F.status = verdict == RHS_ZERO ? NKP_OK : NKP_BREAKDOWN;
+      F.relres = verdict == RHS_ZERO ? 0.0 : NAN;
    }
-   F.target = fmax (s->opt.rtol * F.bnorm, s->opt.atol);
    return NKP_OK;
 }
 
@@ -214,7 +245,7 @@ int fg_end_cycle (nkp_solver *s, FgmresState &F)
       double r2 = 0.0;
       spmv_op (s, s->x, s->r, s->b, 1);
       if ((rc = dot_host (s, s->r, s->r, &r2))) return rc;
-      F.relres = sqrt (r2) / F.bnorm;
+      F.relres = is_finite (r2) ? sqrt (r2) / F.bnorm : NAN;
       F.status = sqrt (r2) <= F.target ? NKP_OK : NKP_BREAKDOWN;
       F.finished = true;
    }
@@ -256,8 +287,14 @@ static int bicgstab (nkp_solver *s, int *iters_out, double *relres_out)
    double bnorm2, rho = 1.0, alpha = 1.0, omega = 1.0, tmp;
    if ((rc = dot_host (s, s->b, s->b, &bnorm2))) return rc;
    const double bnorm = sqrt (bnorm2);
-   if (!(bnorm > 0.0)) { launch_fill (s->x, 0.0, n, st); *iters_out = 0; *relres_out = 0.0; return NKP_OK; }
    const double target = fmax (s->opt.rtol * bnorm, s->opt.atol);
+   int verdict = RHS_ORDINARY;
+   if ((rc = classify_rhs (s, bnorm2, target, &verdict))) return rc;
+   if (verdict != RHS_ORDINARY) {
+      *iters_out = 0;
+      *relres_out = verdict == RHS_ZERO ? 0.0 : NAN;
+      return verdict == RHS_ZERO ? NKP_OK : NKP_BREAKDOWN;
+   }
    spmv_op (s, s->x, r, s->b, 1);
    launch_copy (r, r0, n, st);
    launch_fill (p, 0.0, n, st);
@@ -267,6 +304,7 @@ static int bicgstab (nkp_solver *s, int *iters_out, double *relres_out)
    if ((rc = dot_host (s, r, r, &rn2))) return rc;
    double relres = sqrt (rn2) / bnorm;
    while (its < s->opt.max_iters) {
+      if (!is_finite (rn2)) { status = NKP_BREAKDOWN; break; }      // a non-finite start vector, an overflow on the way
       if (sqrt (rn2) <= target) { status = NKP_OK; break; }
       double rho_new;
       if ((rc = dot_host (s, r0, r, &rho_new))) return rc;
@@ -306,7 +344,8 @@ static int bicgstab (nkp_solver *s, int *iters_out, double *relres_out)
    spmv_op (s, s->x, r, s->b, 1);
    if ((rc = dot_host (s, r, r, &rn2))) return rc;
    relres = sqrt (rn2) / bnorm;
-   if (sqrt (rn2) <= target * 1.0001) status = NKP_OK;
+   if (!is_finite (rn2)) { relres = NAN; status = NKP_BREAKDOWN; }
+   else if (sqrt (rn2) <= target * 1.0001) status = NKP_OK;
    else if (status == NKP_OK) status = NKP_NOT_CONVERGED;
    HIPCHK (hipGetLastError ());
    *iters_out = its;
@@ -351,7 +390,8 @@ static int solve_resident (nkp_solver *s, double *berr, int *iters, double *relr
    if (iters) *iters = it;
    if (relres) *relres = rr;
    msg (s, 1, "nkp_solve: %s after %d iterations, ||b-Ax||/||b|| = %.3e\n", status == NKP_OK ? "converged" : status == NKP_OK_BERR ? "at the attainable accuracy (backward error accepted)" : status == NKP_BREAKDOWN ? "breakdown" : "NOT converged", it, rr);
-   if (status == NKP_OK_BERR) fail (status, "nkp_solve: ||b-Ax||/||b|| = %.3e stopped above rtol %.1e at the attainable accuracy after %d iterations; componentwise backward error %.3e", rr, s->opt.rtol, it, be);
+   if (s->rhs_class == RHS_NONFINITE || s->rhs_class == RHS_OUT_OF_RANGE) rhs_refused (s->rhs_class, "nkp_solve: the right-hand side");
+   else if (status == NKP_OK_BERR) fail (status, "nkp_solve: ||b-Ax||/||b|| = %.3e stopped above rtol %.1e at the attainable accuracy after %d iterations; componentwise backward error %.3e", rr, s->opt.rtol, it, be);
    else if (status != NKP_OK) fail (status, "nkp_solve: %s after %d iterations (relres %.3e, rtol %.1e)", status == NKP_BREAKDOWN ? "breakdown" : s->stagnated ? "stagnated at the attainable accuracy, not converged" : "not converged", it, rr, s->opt.rtol);
    return status;
 }

@@ -3,6 +3,18 @@
 
 #include <math.h>
 
+bool rhs_needs_counts (double bnorm2, double target)
+{
+   return !is_finite (bnorm2) || !(target >= NKP_TARGET_FLOOR);
+}
+
+int rhs_verdict (double bnorm2, double target, double n_nonfinite, double n_nonzero)
+{
+   if (!rhs_needs_counts (bnorm2, target)) return bnorm2 > 0.0 ? RHS_ORDINARY : RHS_ZERO;
+   if (!(n_nonfinite == 0.0)) return RHS_NONFINITE;
+   return n_nonzero == 0.0 ? RHS_ZERO : RHS_OUT_OF_RANGE;
+}
+
 void fg_init (FgmresState &F, int m)
 {
    F = FgmresState ();
@@ -16,7 +28,8 @@ int fg_restart_verdict (FgmresState &F, double beta, int max_iters, int steps_no
    int todo = FG_GO;
    F.beta = beta;
    F.relres = beta / F.bnorm;
-   if (!(beta == beta)) { F.status = NKP_BREAKDOWN; F.finished = true; return FG_STOP; }
+   // a residual that is not a number (a non-finite start vector, an overflow on the way) measures nothing: neither does relres
+   if (!is_finite (beta)) { F.relres = NAN; F.status = NKP_BREAKDOWN; F.finished = true; return FG_STOP; }
    if (beta <= F.target) { F.status = NKP_OK; F.finished = true; return FG_STOP; }
    if (F.its >= max_iters) { F.status = NKP_NOT_CONVERGED; F.finished = true; return FG_STOP; }
    // a whole restart cycle without progress: the chained cycles are not helping on this right-hand side

@@ -26,6 +26,22 @@ struct FgmresState {
    bool breakdown_in_cycle = false;
 };
 
+// ---- the right-hand side, before anything iterates (nkp.h at nkp_solve: "Vectors the solve refuses")
+// Below this target a sum of squares at the target loses digits to underflow: target^2 < 2^-960 is 62 binary orders above the
+// smallest normal number, so every term of such a sum keeps all but 2^-62 of itself.  Derived, not measured.
+#define NKP_TARGET_FLOOR 0x1p-480
+enum { RHS_ORDINARY = 0,       // iterate
+       RHS_ZERO = 1,           // b = 0 (or, with atol > 0, every square of b underflowed: ||b|| < atol): x = 0, NKP_OK
+       RHS_NONFINITE = 2,      // b holds a NaN or an Inf: not solved
+       RHS_OUT_OF_RANGE = 3 }; // b is finite but ||b||^2 overflows or the target is below NKP_TARGET_FLOOR: not solved
+inline bool is_finite (double v) { return v - v == 0.0; }
+// Whether ||b||^2 and target = max (rtol ||b||, atol) leave the range in which they decide alone: only then are the entries of b
+// counted (launch_count_entries and one more allreduce, on this rare path alone; ordinary solves keep their launches).
+NKP_PRIVATE bool rhs_needs_counts (double bnorm2, double target);
+// The verdict, from ||b||^2, the target and the two counts (non-finite entries, entries != 0; both ignored unless
+// rhs_needs_counts).  Every driver takes it from here: fg_begin (so the batched members too) and bicgstab.
+NKP_PRIVATE int rhs_verdict (double bnorm2, double target, double n_nonfinite, double n_nonzero);
+
 // a fresh state for restart length m
 NKP_PRIVATE void fg_init (FgmresState &F, int m);
 

@@ -345,8 +345,10 @@ void launch_scale_to (const double *x, const double *alpha_dev, double *y, float
 void launch_axpy_multi (const double *Z, int64_t ld, int k, const double *c, double *x, int64_t n, hipStream_t st);
 // out[0] = sum x_i*y_i
 void launch_dot (const double *x, const double *y, int64_t n, double *partial, double *out, hipStream_t st);
-// out[0] = max_i |r_i| / den_i  (den_i == 0 -> ignored when r_i == 0)
+// out[0] = max_i |r_i| / den_i  (den_i == 0 -> ignored when r_i == 0); NaN when any r_i or den_i is NaN, or both are Inf
 void launch_berr (const double *r, const double *den, int64_t n, double *partial, double *out, hipStream_t st);
+// out[0] = number of NaN / Inf entries of x, out[1] = number of entries != 0 (partial: 2 * NKP_RED_BLOCKS doubles)
+void launch_count_entries (const double *x, int64_t n, double *partial, double *out, hipStream_t st);
 // small device-side scalar programs of the Krylov drivers
 // h[j] += h2[j] (j<k); h[k] = sqrt(nrm2); inv[0] = 1/h[k] (0 if h[k]==0)
 void launch_finish_column (double *h, const double *h2, int k, const double *nrm2, double *inv, hipStream_t st);

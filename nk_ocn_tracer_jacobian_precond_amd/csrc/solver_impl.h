@@ -35,6 +35,7 @@ struct nkp_solver {
    nkp_tuning tune;             // resolved once in nkp_create; the matrix, column-block and hierarchy objects point at it
    int device = 0;
    bool stagnated = false;      // last solve stopped by the attainable-accuracy guard
+   int rhs_class = 0;           // last solve's verdict on its right-hand side (RHS_* of krylov_host.h)
    bool borrowed = false;       // nkp_clone: matrix, factors and hierarchy belong to the solver this one was cloned from
    hipStream_t stream = nullptr;
    bool own_stream = false;
@@ -326,6 +327,9 @@ NKP_PRIVATE int fg_restart (nkp_solver *s, FgmresState &F);
 NKP_PRIVATE bool fg_post_step (nkp_solver *s, FgmresState &F);
 // y = H^-1 g (upper triangular, size F.j), x += Z y; after a breakdown the true residual of what we have decides
 NKP_PRIVATE int fg_end_cycle (nkp_solver *s, FgmresState &F);
+// nkp_last_error of a right-hand side that fg_begin / bicgstab did not solve (s->rhs_class RHS_NONFINITE or RHS_OUT_OF_RANGE);
+// `what` names it ("nkp_solve: the right-hand side").  Returns NKP_BREAKDOWN.
+NKP_PRIVATE int rhs_refused (int verdict, const char *what);
 // componentwise backward error of s->x for s->b, like SuperLU's berr
 NKP_PRIVATE int backward_error (nkp_solver *s, double *berr);
 // ---- defined in batch_solve.hip --------------------------------------------------------------------------------------------

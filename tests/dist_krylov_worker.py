@@ -6,11 +6,16 @@
                status and the residuals of both sides
   --mode two   latitude bands of n2001 on two ranks: every rank writes its slice of x_k; the test gathers them and compares
                with the single-process restatement on the global matrix
+  --mode refuse  two ranks on the library's file transport (directory <out>.comm): a right-hand side with a NaN in a row of rank 1,
+               and b 2^-600, are refused on BOTH ranks (the counts of classify_rhs are added across them), and a clean solve
+               afterwards has the bits of the one before
 """
 import argparse
+import ctypes as C
 import json
 import os
 import sys
+import types
 
 import numpy as np
 
@@ -41,6 +46,40 @@ def main():
         starts = nd.snap_partition(c.blk, world)
         loc = nd.local_slice(c.rowptr, c.colind, c.val, c.blk, starts, rank)
         return loc, int(loc["fst_row"]), int(loc["m_loc"])
+
+    if a.mode == "refuse":
+        from nk_ocn_tracer_jacobian_precond_amd import solver
+        lib = solver.load_library()
+        lib.nkp_comm_file_init.argtypes = [C.POINTER(solver.NkpCommOps), C.c_char_p, C.c_int, C.c_int]
+        lib.nkp_comm_file_free.argtypes = [C.POINTER(solver.NkpCommOps)]
+        lib.nkp_comm_file_free.restype = None
+        os.makedirs(a.out + ".comm", exist_ok=True)
+        dist.barrier()
+        ops = solver.NkpCommOps()
+        assert lib.nkp_comm_file_init(C.byref(ops), (a.out + ".comm").encode(), rank, world) == 0
+        fcomm = types.SimpleNamespace(ops=ops, errors=[])
+        run = kc.Run("n2001", kc.JACOBI, None, restart=8)
+        c = kc.case(run.case)
+        loc, f, m = local(c)
+        s = nd.NkpDistSolver(loc, c.n, fcomm, **run.options())
+        x0, info0 = s.solve(c.b[f:f + m], raise_on_fail=False)
+        res.update(m_loc=m, fst_row=f, clean=info0, refused={})
+        nan = c.b.copy()
+        nan[c.n - 5] = np.nan                                # a row of the last rank
+        for what, b in (("nan_on_rank_1", nan), ("down600", kc.bad_rhs(c.b, "down600"))):
+            x, info = s.solve(b[f:f + m], raise_on_fail=False)
+            res["refused"][what] = dict(status=info["status"], iters=info["iters"], relres_is_nan=bool(info["relres"] != info["relres"]),
+                                        rows_nan=int(np.isnan(x).sum()), holds_nan=bool(np.isnan(b[f:f + m]).any()))
+        x1, info1 = s.solve(c.b[f:f + m], raise_on_fail=False)
+        res["clean_again"] = bool(kc.same_bits(x1, x0) and info1 == info0)
+        s.close()
+        res["comm_errors"] = list(fcomm.errors)
+        lib.nkp_comm_file_free(C.byref(ops))
+        with open(f"{a.out}.{rank}", "w") as fh:
+            json.dump(res, fh)
+        dist.barrier()
+        dist.destroy_process_group()
+        return
 
     for run in (kc.dist_one_rank_runs() if a.mode == "one" else kc.dist_two_rank_runs()):
         c = kc.case(run.case)

@@ -147,6 +147,35 @@ def guess(c):
     return np.random.default_rng(5).standard_normal(c.n)
 
 
+# ---------------------------------------------------------------- vectors no solve accepts (include/nkp.h at nkp_solve)
+# name -> what it does to a right-hand side.  The positions sit in different 512-element blocks of the reductions where n allows.
+BAD_RHS = ["nan", "inf", "inf_pair", "up520", "down600"]
+
+
+def bad_rhs(b, kind):
+    """b with one NaN, one +Inf, a +Inf and a -Inf, or scaled by 2^520 (||b||^2 overflows) or 2^-600 (every square underflows)"""
+    b = np.array(b, np.float64)
+    n = b.size
+    if kind == "nan":
+        b[n // 3] = np.nan
+    elif kind == "inf":
+        b[n // 3] = np.inf
+    elif kind == "inf_pair":
+        b[n // 3], b[n - 1] = np.inf, -np.inf
+    elif kind == "up520":
+        b = np.ldexp(b, 520)
+    elif kind == "down600":
+        b = np.ldexp(b, -600)
+    else:
+        raise ValueError(kind)
+    return b
+
+
+def same_bits(x, y):
+    x, y = np.ascontiguousarray(x, np.float64), np.ascontiguousarray(y, np.float64)
+    return x.shape == y.shape and np.array_equal(x.view(np.uint64), y.view(np.uint64))
+
+
 # several levels on 2001 rows, and one smoothing sweep per half cycle: FGMRES then takes 9 iterations to 1e-10 (5 with two
 # chained cycles, BiCGStab 5), so that a cut at k = 5 is still a cut
 ML_TUNING = dict(ml_coarsest_rows=60)

@@ -11,6 +11,8 @@
 //    E                the end of the cycle: prints "end <k>", then "y", "cs", "sn" (k numbers each), "g" (k + 1 numbers: what y was
 //                     solved from, and the entry behind it) and "H" (the rotated upper triangle, column by column: c + 1 numbers
 //                     of column c)
+//    V bnorm2 target nonfinite nonzero    the verdict on a right-hand side (rhs_needs_counts, rhs_verdict), at any point of the
+//                     file: prints "verdict <needs counts> <RHS_* code>"
 // Doubles are printed as hexadecimal floats, so that nothing is lost on the way.  The driver does what krylov.hip does between
 // two calls and nothing else: it lowers steps_now when the verdict says so.
 #include "../nk_ocn_tracer_jacobian_precond_amd/csrc/krylov_host.h"
@@ -80,6 +82,9 @@ int main (int argc, char **argv)
          for (int c = 0; c < k; c++)
             for (int i = 0; i <= c; i++) printf (" %a", F.H[(size_t) c * (size_t) (m + 1) + (size_t) i]);
          printf ("\n");
+      } else if (cmd[0] == 'V') {
+         const double bnorm2 = read_double (f), target = read_double (f), nonfinite = read_double (f), nonzero = read_double (f);
+         printf ("verdict %d %d\n", rhs_needs_counts (bnorm2, target) ? 1 : 0, rhs_verdict (bnorm2, target, nonfinite, nonzero));
       } else
          usage_error ("unknown command");
    }

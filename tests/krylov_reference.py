@@ -6,6 +6,10 @@ column epilogues of csrc/blas1.hip:418-486; bicgstab () restates bicgstab of csr
 once (Arith).  The operator A and the preconditioner M are callables on float64 vectors, so the same text runs on the oracle's
 operators (tests/test_krylov_reference.py) and on the solver's own spmv / precond_apply (tests/test_gpu_krylov.py).
 
+Both drivers begin with the verdict on the right-hand side (rhs_verdict of csrc/krylov_host.cpp restated: NaN, Inf and norms
+outside the range of a solve are refused with x = NaN) and treat a non-finite residual norm as a breakdown; berr () restates the
+NaN-sticky backward-error reduction of csrc/blas1.hip.
+
 A solve cut at max_iters = k returns x_k, which GMRES fixes uniquely (the residual minimiser over the Krylov space): two correct
 implementations agree on it to rounding, whatever their summation order.
 
@@ -74,6 +78,55 @@ class ReversedF64(Arith):
         return w
 
 
+# ---- the verdict on the right-hand side (csrc/krylov_host.cpp: rhs_needs_counts, rhs_verdict; include/nkp.h at nkp_solve)
+TARGET_FLOOR = 2.0 ** -480
+RHS_ORDINARY, RHS_ZERO, RHS_NONFINITE, RHS_OUT_OF_RANGE = 0, 1, 2, 3
+
+
+def rhs_needs_counts(bnorm2, target):
+    return not math.isfinite(bnorm2) or not target >= TARGET_FLOOR
+
+
+def rhs_verdict(bnorm2, target, n_nonfinite, n_nonzero):
+    if not rhs_needs_counts(bnorm2, target):
+        return RHS_ORDINARY if bnorm2 > 0.0 else RHS_ZERO
+    if n_nonfinite != 0:
+        return RHS_NONFINITE
+    return RHS_ZERO if n_nonzero == 0 else RHS_OUT_OF_RANGE
+
+
+def classify_rhs(b, bnorm2, target):
+    """classify_rhs (krylov.hip) with count_entries_kernel (blas1.hip): the verdict, and None or the Result that ends the solve"""
+    b = np.asarray(b, np.float64)
+    v = rhs_verdict(bnorm2, target, int((~np.isfinite(b)).sum()), int((b != 0.0).sum()))
+    if v == RHS_ORDINARY:
+        return v, None
+    if v == RHS_ZERO:
+        return v, Result(np.zeros(b.size), 0, OK, 0.0, [], False, 1.0)
+    return v, Result(np.full(b.size, np.nan), 0, BREAKDOWN, math.nan, [], False, 1.0)
+
+
+def _fmax(a, b):
+    """fmax of C: a NaN operand is ignored"""
+    return b if a != a else a if b != b else max(a, b)
+
+
+def _sqrt(v):
+    """sqrt of a sum of squares as C takes it: NaN stays NaN (math.sqrt raises on nothing a sum of squares can be)"""
+    return math.sqrt(v) if v == v else math.nan
+
+
+def berr(r, den):
+    """berr_kernel / max_partials_kernel (blas1.hip): max_i |r_i| / den_i, a row with den_i = 0 counting 1e300 when r_i != 0 and
+    nothing when r_i = 0 -- and NaN as soon as any quotient is (a NaN in r or den, Inf / Inf)"""
+    a, d = np.abs(np.asarray(r, np.float64)), np.asarray(den, np.float64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        q = np.where((d > 0.0) | np.isnan(d), a / d, np.where(np.isnan(a), a, np.where(a > 0.0, 1.0e300, 0.0)))
+    if np.isnan(q).any():
+        return math.nan
+    return float(q.max()) if q.size else 0.0
+
+
 def _dist(a, b):
     m = max(abs(a), abs(b))
     return abs(a - b) / m if m > 0.0 else 0.0
@@ -121,10 +174,12 @@ def fgmres(A, M, b, x0=None, *, restart, max_iters, rtol=1e-10, atol=0.0, reorth
             trace.append(event)
 
     # ---- fg_begin (krylov.hip)
-    bnorm = math.sqrt(ar.dot(b, b))
-    if not bnorm > 0.0:
-        return Result(np.zeros(n), 0, OK, 0.0, log, False, 1.0)
-    target = max(rtol * bnorm, atol)
+    bnorm2 = ar.dot(b, b)
+    bnorm = _sqrt(bnorm2)
+    target = _fmax(rtol * bnorm, atol)
+    _, over = classify_rhs(b, bnorm2, target)
+    if over is not None:
+        return over
     steps_now = precond_steps
     x = np.zeros(n) if x0 is None else np.array(x0, np.float64)
     if rscale is not None and rinv is None:
@@ -137,11 +192,11 @@ def fgmres(A, M, b, x0=None, *, restart, max_iters, rtol=1e-10, atol=0.0, reorth
     while True:
         # ---- fg_restart (krylov.hip; the verdict: krylov_host.cpp, fg_restart_verdict)
         r = b - A(x)
-        beta = math.sqrt(ar.dot(r, r))
+        beta = _sqrt(ar.dot(r, r))
         relres = beta / bnorm
         note("restart", beta)
-        if beta != beta:
-            status = BREAKDOWN
+        if not math.isfinite(beta):
+            status, relres = BREAKDOWN, math.nan
             break
         if decide("converged", its, beta, target, beta <= target):
             status = OK
@@ -259,8 +314,8 @@ def fgmres(A, M, b, x0=None, *, restart, max_iters, rtol=1e-10, atol=0.0, reorth
         x = ar.update(x, Z[:k], y, sign=1.0)
         if breakdown_in_cycle:
             r = b - A(x)
-            rn = math.sqrt(ar.dot(r, r))
-            relres = rn / bnorm
+            rn = _sqrt(ar.dot(r, r))
+            relres = rn / bnorm if math.isfinite(rn) else math.nan
             status = OK if rn <= target else BREAKDOWN
             break
     return Result(x, its, status, relres, log, stagnated, inner_scale)
@@ -279,10 +334,12 @@ def bicgstab(A, M, b, x0=None, *, max_iters, rtol=1e-10, atol=0.0, precond_steps
 
     precond = chained_precond(A, M, precond_steps)
     rho = alpha = omega = 1.0
-    bnorm = math.sqrt(ar.dot(b, b))
-    if not bnorm > 0.0:
-        return Result(np.zeros(n), 0, OK, 0.0, log, False, 1.0)
-    target = max(rtol * bnorm, atol)
+    bnorm2 = ar.dot(b, b)
+    bnorm = _sqrt(bnorm2)
+    target = _fmax(rtol * bnorm, atol)
+    _, over = classify_rhs(b, bnorm2, target)
+    if over is not None:
+        return over
     x = np.zeros(n) if x0 is None else np.array(x0, np.float64)
     r = b - A(x)
     r0 = r.copy()
@@ -290,6 +347,9 @@ def bicgstab(A, M, b, x0=None, *, max_iters, rtol=1e-10, atol=0.0, precond_steps
     its, status = 0, NOT_CONVERGED
     rn2 = ar.dot(r, r)
     while its < max_iters:
+        if not math.isfinite(rn2):
+            status = BREAKDOWN
+            break
         if decide("converged", its, math.sqrt(rn2), target, math.sqrt(rn2) <= target):
             status = OK
             break
@@ -325,9 +385,11 @@ def bicgstab(A, M, b, x0=None, *, max_iters, rtol=1e-10, atol=0.0, precond_steps
             status = BREAKDOWN
             break
     r = b - A(x)
-    rn = math.sqrt(ar.dot(r, r))
+    rn = _sqrt(ar.dot(r, r))
     relres = rn / bnorm
-    if decide("final", its, rn, target * 1.0001, rn <= target * 1.0001):
+    if not math.isfinite(rn):
+        status, relres = BREAKDOWN, math.nan
+    elif decide("final", its, rn, target * 1.0001, rn <= target * 1.0001):
         status = OK
     elif status == OK:
         status = NOT_CONVERGED

@@ -207,3 +207,32 @@ def test_cli_rhs_block_under_equilibration(tmp_path, golden_by_name):
     assert "one at a time" not in out["block"][1], out["block"][1]
     assert "nkp_solve_batch: right-hand side 1:" in out["block"][1], out["block"][1]          # the batched driver's own verdict line
     assert out["block"][0] == out["plain"][0]
+
+
+@pytest.mark.parametrize("block", ["", "2"], ids=["plain", "block"])
+def test_cli_refuses_a_tracer_with_a_nan(tmp_path, golden_by_name, block):
+    """bin/solve_ABglobal with a NaN at one ocean point of a tracer variable (a Newton step that has blown up): the solve is
+    NKP_BREAKDOWN ("holds a non-finite entry", include/nkp.h at nkp_solve), the program exits non-zero and the tracer file keeps
+    its bytes -- it used to come back as zeros with exit status 0"""
+    g = golden_by_name("pair_8x8x5")
+    src = nc3.NcFile(g.tracer_path)
+    dims = {"nlon": g.imt, "nlat": g.jmt, "z_t": g.km}
+    fill = {"_FillValue": np.float64(synth.FILL_DOUBLE)}
+    variables = []
+    for q, v in enumerate(g.varnames):
+        f = src.get(v).copy()
+        if q == 1:
+            at = g.ind_k.size // 2
+            f[g.ind_k[at], g.ind_j[at], g.ind_i[at]] = np.nan
+        variables.append((v, ["z_t", "nlat", "nlon"], f, fill))
+    path = str(tmp_path / "B_nan.nc")
+    nc3.write(path, dims, variables)
+    before = open(path, "rb").read()
+    env = dict(os.environ, NKP_ACCEPT_BERR="1")
+    env.pop("NKP_RHS_BLOCK", None)
+    if block:
+        env["NKP_RHS_BLOCK"] = block
+    r = subprocess.run([os.path.join(BIN, "solve_ABglobal"), "-D1", "-v", ",".join(g.varnames), g.matrix_path, path], capture_output=True, text=True, env=env, timeout=240)
+    assert r.returncode != 0, r.stdout + r.stderr
+    assert "holds a non-finite entry" in r.stderr and "left untouched" in r.stderr, r.stderr
+    assert open(path, "rb").read() == before

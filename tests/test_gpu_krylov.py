@@ -19,6 +19,7 @@ Which test reaches which kernel of blas1.hip:
   vmul_kernel                                                      test_truncated with equil
   zero_kernel                                                      test_truncated (b = 0 in test_zero_rhs; bicgstab's p, v)
   berr_kernel, max_partials_kernel                                 every solve () (info["berr"]), checked in test_full_solves
+  count_entries_kernel, and NaN / Inf through the above            test_gpu_vector_range.py
   multi_dot_group, multi_dot_finish_group, update_w_group, sum_partials_group, scale_to_group, finish_column_group
                                                                     test_batched_bits (against the single solves)
 """

@@ -96,3 +96,18 @@ def test_two_ranks_against_the_global_restatement(tmp_path):
             assert p["iters"] == ref.iters == 9 and p["status"] == ref.status, (run, p)
             assert abs(p["relres"] - ref.relres) <= c.relres_bound(ref.x, ref.relres, tol), (run, p)
         assert dx <= tol, (run, dx, tol)
+
+
+def test_two_ranks_refuse_together(tmp_path):
+    """a NaN in a row that rank 1 owns, and b 2^-600 (include/nkp.h at nkp_solve): ||b||^2 is global, so both ranks count their
+    entries, add the counts and return NKP_BREAKDOWN with iters 0 and every own row NaN -- rank 0 too, whose rows hold no NaN.
+    A clean solve afterwards has the bits of the one before.  (berr is left out: what the max-allreduce makes of a NaN is the
+    transport's business.)  The file transport of the library carries the collectives."""
+    res = launch(2, "refuse", str(tmp_path / "r"), {"NKP_COMM_TIMEOUT": "60"})
+    assert [r["fst_row"] for r in res] == [0, res[0]["m_loc"]] and min(r["m_loc"] for r in res) > 5
+    assert res[0]["clean"]["status"] == kr.OK and res[0]["clean"]["iters"] > 0
+    assert [res[r]["refused"]["nan_on_rank_1"]["holds_nan"] for r in range(2)] == [False, True]
+    for r in res:
+        for what, got in r["refused"].items():
+            assert got["status"] == kr.BREAKDOWN and got["iters"] == 0 and got["relres_is_nan"] and got["rows_nan"] == r["m_loc"], (r["rank"], what, got)
+        assert r["clean_again"], r

@@ -44,6 +44,11 @@ def test_a_tangent_solve_that_does_not_converge_raises(result):
     assert result["not_converged_raises"], result
 
 
+def test_a_right_hand_side_with_a_nan_raises(result):
+    """NkpTorchSolver.solve of a B with one NaN row: NkpError (NKP_BREAKDOWN, "holds a non-finite entry"), no tensor"""
+    assert result["nan_row_raises"], result
+
+
 def test_forward_and_reverse_mode_agree_on_the_golden_fixtures(result):
     """<W, jvp (dB, dval)> against <B.grad, dB> + <val.grad, dval>, K = 2, the solver options of the existing value-gradient test.
 

@@ -233,3 +233,62 @@ def test_host_unit_under_sanitizers(name, sanitized_program, tmp_path):
         assert [e for e in trace if e[0] == "step"][-1][3] is None
     else:
         assert res.iters == [e for e in trace if e[0] == "step"][-1][2] if any(e[0] == "step" for e in trace) else res.iters == 0
+
+
+# ---------------------------------------------------------------- the verdict on the right-hand side
+FLOOR = 2.0 ** -480          # NKP_TARGET_FLOOR (krylov_host.h); 2^-960 for its square is 62 binary orders above the smallest normal
+ORDINARY, ZERO, NONFINITE, OUT_OF_RANGE = kr.RHS_ORDINARY, kr.RHS_ZERO, kr.RHS_NONFINITE, kr.RHS_OUT_OF_RANGE
+SUBNORMAL = 2.0 ** -1070
+# (||b||^2, target, non-finite entries, entries != 0) -> (the entries are counted, verdict).  The expectation is the contract of
+# include/nkp.h written out by hand, not a call of the restatement.
+VERDICTS = [
+    ((4.0, 2e-10, 0, 7), (0, ORDINARY)),
+    ((4.0, 2e-10, 3, 0), (0, ORDINARY)),                       # inside the range the counts are not looked at
+    ((0.0, 0.0, 0, 0), (1, ZERO)),                             # b = 0
+    ((0.0, 0.0, 0, 5), (1, OUT_OF_RANGE)),                     # every square underflowed: b 2^-600
+    ((0.0, 0.0, 2, 5), (1, NONFINITE)),
+    ((SUBNORMAL, 1e-10 * math.sqrt(SUBNORMAL), 0, 513), (1, OUT_OF_RANGE)),
+    ((SUBNORMAL, 1e-10 * math.sqrt(SUBNORMAL), 0, 0), (1, ZERO)),       # (not reachable: a count that contradicts the norm)
+    ((math.inf, math.inf, 0, 513), (1, OUT_OF_RANGE)),         # b 2^520: finite entries, ||b||^2 overflows
+    ((math.inf, math.inf, 1, 513), (1, NONFINITE)),            # +Inf in b
+    ((math.inf, math.inf, 513, 513), (1, NONFINITE)),
+    ((math.nan, 0.0, 1, 513), (1, NONFINITE)),                 # NaN in b; fmax (rtol NaN, atol = 0) = 0
+    ((math.nan, 1e-8, 2, 513), (1, NONFINITE)),                # ... and with atol > 0: the norm alone sends it to the counts
+    ((math.nan, math.nan, 1, 1), (1, NONFINITE)),
+    ((1.0, math.nextafter(FLOOR, 0.0), 0, 9), (1, OUT_OF_RANGE)),      # the target just below 2^-480
+    ((1.0, FLOOR, 0, 9), (0, ORDINARY)),                       # at it
+    ((1.0, math.nextafter(FLOOR, 1.0), 0, 9), (0, ORDINARY)),  # just above
+    ((2.0 ** -1000, 1e-8, 0, 9), (0, ORDINARY)),               # atol > 0 keeps a tiny b on the normal path
+    ((SUBNORMAL, 1e-8, 0, 9), (0, ORDINARY)),
+    ((0.0, 1e-8, 0, 9), (0, ZERO)),                            # ... and where its squares are all gone, ||b|| < atol: x = 0 meets it
+    ((0.0, 1e-8, 0, 0), (0, ZERO)),
+]
+
+
+def test_rhs_verdict_of_the_restatement():
+    for (bnorm2, target, nonfinite, nonzero), (counts, verdict) in VERDICTS:
+        assert kr.rhs_needs_counts(bnorm2, target) == bool(counts), (bnorm2, target)
+        assert kr.rhs_verdict(bnorm2, target, nonfinite, nonzero) == verdict, (bnorm2, target, nonfinite, nonzero)
+
+
+def test_rhs_verdict_under_sanitizers(sanitized_program, tmp_path):
+    lines = ["1 0 1 0x1p+0 0x0p+0"] + ["V " + " ".join(_hex(float(v)) for v in args) for args, _ in VERDICTS]
+    path = tmp_path / "verdicts.txt"
+    path.write_text("\n".join(lines) + "\n")
+    r = subprocess.run([sanitized_program, str(path)], capture_output=True, text=True, timeout=60)
+    out = r.stdout + r.stderr
+    assert r.returncode == 0 and "runtime error" not in out and "AddressSanitizer" not in out, out
+    got = [tuple(int(v) for v in ln.split()[1:]) for ln in r.stdout.splitlines()]
+    assert all(ln.startswith("verdict ") for ln in r.stdout.splitlines())
+    assert got == [want for _, want in VERDICTS], list(zip(VERDICTS, got))
+
+
+def test_a_non_finite_restart_is_a_breakdown_without_a_relres(sanitized_program, tmp_path):
+    """fg_restart_verdict with beta = Inf (a start vector with an Inf) and NaN: NKP_BREAKDOWN, relres NaN"""
+    for beta in ("inf", "nan"):
+        path = tmp_path / f"restart_{beta}.txt"
+        path.write_text(f"4 10 1 0x1p+0 0x1p-30\nR {beta}\n")
+        r = subprocess.run([sanitized_program, str(path)], capture_output=True, text=True, timeout=60)
+        assert r.returncode == 0 and not r.stderr.strip(), r.stdout + r.stderr
+        w = r.stdout.split()
+        assert w[0] == "restart" and int(w[1]) & 1 and int(w[2]) == 1 and int(w[3]) == kr.BREAKDOWN and "nan" in w[6].lower(), r.stdout

@@ -296,3 +296,66 @@ def test_pythagoras_epilogue_stays_within_the_class_noise(run):
     assert d <= kc.TOL[run.cls][1] / 100.0
     if run.k is None:
         assert a.status == kr.OK and min(x.dist for x in a.log) >= 1000.0 * kc.TOL[run.cls][1]
+
+
+# ---------------------------------------------------------------- vectors outside the range of a solve (include/nkp.h at nkp_solve)
+RANGE_RUNS = [kc.Run("n2001", kc.JACOBI, None, ro, f32, restart=8) for ro, f32 in kc.OPTION_PAIRS] + [kc.Run("n2001", kc.JACOBI, None, krylov="bicgstab", restart=2)]
+
+
+def _solve_scaled(run, b):
+    c = kc.case(run.case)
+    A, M = oracle_operators(c, run.precond)
+    with np.errstate(all="ignore"):
+        if run.krylov == "bicgstab":
+            return kr.bicgstab(A, M, b, max_iters=run.max_iters, rtol=run.rtol)
+        return kr.fgmres(A, M, b, restart=run.restart, max_iters=run.max_iters, rtol=run.rtol, reorth=run.reorth, basis_f32=run.f32)
+
+
+@pytest.mark.parametrize("run", RANGE_RUNS, ids=lambda r: r.id)
+def test_a_power_of_two_on_b_is_a_power_of_two_on_x(run):
+    """b 2^e with e = +-300 is inside the range: every product and sum of the solve scales exactly, so x has the bits of
+    2^e x, with the same iteration count and the same bits of relres.  No absolute constant enters a decision."""
+    c = kc.case(run.case)
+    plain = solved(run)
+    assert plain.status == kr.OK and plain.iters > 8
+    for e in (300, -300):
+        r = _solve_scaled(run, np.ldexp(c.b, e))
+        assert (r.status, r.iters) == (plain.status, plain.iters), (run, e, r.iters, plain.iters)
+        assert kc.same_bits(r.x, np.ldexp(plain.x, e)), (run, e)
+        assert kc.same_bits(np.array([r.relres]), np.array([plain.relres])), (run, e, r.relres, plain.relres)
+
+
+@pytest.mark.parametrize("what", kc.BAD_RHS + ["down520", "up600"])
+@pytest.mark.parametrize("run", RANGE_RUNS, ids=lambda r: r.id)
+def test_a_right_hand_side_outside_the_range_is_refused(run, what):
+    """NaN, Inf, ||b||^2 beyond f64, a target below 2^-480: NKP_BREAKDOWN before any iteration, relres NaN, x all NaN -- where the
+    drivers used to return x = 0 with NKP_OK (NaN, 2^520, 2^-600), relres NaN with NKP_OK (Inf), or NKP_OK two iterations
+    early on a subnormal ||r||^2 (2^-520)"""
+    c = kc.case(run.case)
+    b = np.ldexp(c.b, {"down520": -520, "up600": 600}[what]) if what in ("down520", "up600") else kc.bad_rhs(c.b, what)
+    r = _solve_scaled(run, b)
+    assert r.status == kr.BREAKDOWN and r.iters == 0 and r.relres != r.relres
+    assert r.x.shape == (c.n,) and np.isnan(r.x).all()
+
+
+@pytest.mark.parametrize("krylov", ["fgmres", "bicgstab"])
+@pytest.mark.parametrize("bad", [np.nan, np.inf])
+def test_a_non_finite_guess_is_a_breakdown(krylov, bad):
+    c = kc.case("n513")
+    A, M = oracle_operators(c, kc.JACOBI)
+    x0 = kc.guess(c)
+    x0[c.n // 2] = bad
+    with np.errstate(all="ignore"):
+        for max_iters in (0, 5):
+            r = kr.fgmres(A, M, c.b, x0, restart=4, max_iters=max_iters) if krylov == "fgmres" else kr.bicgstab(A, M, c.b, x0, max_iters=max_iters)
+            assert r.status == kr.BREAKDOWN and r.iters == 0 and r.relres != r.relres, (krylov, bad, max_iters, r.status, r.relres)
+
+
+def test_berr_rule():
+    """kr.berr, the rule test_gpu_vector_range.py holds berr_kernel to: the quotient rule of the library, NaN sticky"""
+    assert kr.berr([1.0, -3.0, 0.0], [2.0, 4.0, 0.0]) == 0.75
+    assert kr.berr([1.0, 1e-300], [2.0, 0.0]) == 1.0e300            # a residual where the denominator is zero
+    assert kr.berr([0.0, 0.0], [0.0, 0.0]) == 0.0
+    assert kr.berr([np.inf, 1.0], [1.0, 1.0]) == np.inf
+    for r, d in (([np.nan, 1.0], [1.0, 1.0]), ([1.0, 1.0], [1.0, np.nan]), ([1.0, np.inf], [1.0, np.inf]), ([np.nan, 1.0], [0.0, 1.0])):
+        assert kr.berr(r, d) != kr.berr(r, d), (r, d)

@@ -101,6 +101,18 @@ def main():
         res["not_converged_raises"] = exc.code == solver.NKP_NOT_CONVERGED
     s2.close()
 
+    # a right-hand side with a NaN is not solved (nkp.h at nkp_solve): NkpError, and no tensor comes back
+    s3 = solver.NkpSolver(p.rowptr, p.colind, p.nzval, blk, 1, col_i=ci, col_j=cj, rtol=1e-10, restart=60, max_iters=3000)
+    Bn = B.clone()
+    Bn[1, n // 2] = float("nan")
+    got = None
+    try:
+        got = NkpTorchSolver(s3).solve(Bn)
+        res["nan_row_raises"] = False
+    except solver.NkpError as exc:
+        res["nan_row_raises"] = exc.code == solver.NKP_BREAKDOWN and got is None and "holds a non-finite entry" in str(exc)
+    s3.close()
+
     # ---------------------------------------------------------------- the two modes agree (golden fixtures, K = 2)
     res["consistency"] = []
     for name in GOLDEN_CASES:
