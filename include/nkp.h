@@ -181,6 +181,16 @@ typedef struct nkp_tuning {
                                 nkp_create_dist, and the ranks then leave the exchange out together).  nkp_get_int
                                 "dist_smooth_exchange" tells what is in force.  The hierarchy of a refactor that rebuilds must keep a
                                 smoothed level 0, else the refactor fails at its commit agreement */
+   int step_glue;            /* NKP_STEP_GLUE (12): bit mask of what a Krylov step leaves out between its large kernels; every stored double
+                                keeps its bits, 0 = every launch of its own.  4 = the restriction of the single-vector cycle also zeroes
+                                the coarse level's x (every level but a dense last one) and requests a coarse row's fine values
+                                together.  8 = FGMRES, not row-distributed, no row equilibration, one cycle per iteration: the kernel that
+                                completes the Hessenberg column adds up ||w||^2 itself and stores the column to pinned host memory as
+                                well, and the host waits on an event behind that kernel instead of copying and synchronising the
+                                stream; with an f64 basis and the multilevel preconditioner one kernel then writes v = w / ||w|| to
+                                the basis and to level 0's right-hand side and zeroes level 0's x (instead of scale, gather, fill), and
+                                it and the first column solves of level 0 are enqueued before the wait and run while the host decides.
+                                Not for the last slot of a restart cycle.  Bits 1 and 2 are not used */
 } nkp_tuning;
 
 /* defaults, then the NKP_* environment overrides listed above */
@@ -347,7 +357,8 @@ int nkp_multi_dot (nkp_solver *s, const double *V, int64_t ld, int k, const doub
 
 /* Average duration (ms) of `reps` back-to-back launches of one kernel on the solver's stream,
  * measured with HIP events on that stream.  which: 0 = CSR SpMV, 1 = preconditioner apply,
- * 2 = one full Krylov iteration body at restart position `arg` (0 <= arg < restart); multilevel only: 3 = the
+ * 2 = one full FGMRES step at restart position `arg` (0 <= arg < restart) as a solve runs it, the hand-over of the Hessenberg
+ * column to the host included (tuning step_glue: the wait and what is enqueued ahead of the next step); multilevel only: 3 = the
  * smoother's residual rows of one colour of the fine level, 4 = the water-column solves of that colour; 5 = the gradient kernel of
  * nkp_value_gradient alone with K = arg in {1, 2, 4, 8} pairs of vectors, on scratch vectors of the solver (single-GPU solvers
  * only, NKP_EINVAL elsewhere and for another arg; its compulsory bytes: 12 nnz + 4 (n + 1) + 16 K n); 6 = the product kernel of

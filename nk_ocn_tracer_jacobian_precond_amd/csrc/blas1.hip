@@ -235,7 +235,7 @@ void launch_update_w (const void *V, int v_f32, int64_t ld, int k, const double 
    const int g = red_grid (n);
    if (v_f32) hipLaunchKernelGGL ((update_w_kernel<float, float2>), dim3 (g), dim3 (B1_THREADS), 0, st, (const float *) V, ld, k, h, w, n, partial, -1.0);
    else hipLaunchKernelGGL ((update_w_kernel<double, double2>), dim3 (g), dim3 (B1_THREADS), 0, st, (const double *) V, ld, k, h, w, n, partial, -1.0);
-   hipLaunchKernelGGL (sum_partials_kernel, dim3 (1), dim3 (NKP_WAVE), 0, st, partial, g, out_nrm2);
+   if (out_nrm2) hipLaunchKernelGGL (sum_partials_kernel, dim3 (1), dim3 (NKP_WAVE), 0, st, partial, g, out_nrm2);      // NULL: launch_finish_column_host adds them up
 }
 
 void launch_update_w_group (int R, const GsGroup &G, int64_t ld, int k, const double *msg, int64_t n, double *nrm2, hipStream_t st)
@@ -510,6 +510,36 @@ void launch_finish_column_pythagoras (double *h, int k, double *inv, hipStream_t
    hipLaunchKernelGGL (finish_column_pythagoras_kernel, dim3 (1), dim3 (NKP_WAVE), 0, st, h, k, inv);
 }
 
+// The same for the step that hands its column over early (tuning step_glue bit 8), one launch and one copy command fewer: ||w||^2 is summed here from
+// the partial sums of update_w_kernel, in the order of sum_partials_kernel (and still stored to nrm2_out), and the finished column
+// h[0 .. k] also goes to host_col: pinned host memory the device can address, which the host reads after an event behind this
+// kernel -- no copy command between this kernel and the next.
+__global__ __launch_bounds__ (NKP_WAVE)
+void finish_column_host_kernel (double *__restrict__ h, const double *__restrict__ h2, int k, const double *__restrict__ partial, int nblk,
+                                double *__restrict__ nrm2_out, double *__restrict__ inv, double *__restrict__ host_col)
+{
+   double s = 0.0;
+   for (int b = threadIdx.x; b < nblk; b += NKP_WAVE) s += partial[b];
+   s = wave_sum (s);
+   if (h2)
+      for (int j = threadIdx.x; j < k; j += NKP_WAVE) h[j] += h2[j];
+   if (threadIdx.x == 0) {
+      nrm2_out[0] = s;
+      const double t = sqrt (s);
+      h[k] = t;
+      inv[0] = (t > 0.0) ? 1.0 / t : 0.0;
+   }
+   __syncthreads ();
+   for (int j = threadIdx.x; j <= k; j += NKP_WAVE) host_col[j] = h[j];
+   __threadfence_system ();
+}
+
+// partial: the n-vector's block sums as launch_update_w_only left them
+void launch_finish_column_host (double *h, const double *h2, int k, const double *partial, int64_t n, double *nrm2_out, double *inv, double *host_col, hipStream_t st)
+{
+   hipLaunchKernelGGL (finish_column_host_kernel, dim3 (1), dim3 (NKP_WAVE), 0, st, h, h2, k, partial, red_grid (n), nrm2_out, inv, host_col);
+}
+
 void launch_finish_column (double *h, const double *h2, int k, const double *nrm2, double *inv, hipStream_t st)
 {
    hipLaunchKernelGGL (finish_column_kernel, dim3 (1), dim3 (NKP_WAVE), 0, st, h, h2, k, nrm2, inv);
@@ -528,9 +558,40 @@ void restrict_sum_kernel (const int *__restrict__ rptr, const int *__restrict__ 
    }
 }
 
-void launch_restrict_sum (const int *rptr, const int *ridx, const double *fine, double *coarse, int64_t nc, hipStream_t st)
+// Tuning step_glue bit 4: the same sums, and coarse_x = 0 (the fill the coarse level's cycle would start with) in the same pass.
+// A coarse row's indices are requested eight at a time, then their fine values, and only then added -- in q order, from +0.0,
+// as above: same bits, the loads no longer wait for each other.
+__global__ __launch_bounds__ (B1_THREADS)
+void restrict_sum_fill_kernel (const int *__restrict__ rptr, const int *__restrict__ ridx, const double *__restrict__ fine,
+                               double *__restrict__ coarse, double *__restrict__ coarse_x, int64_t nc)
+{
+   const int64_t stride = (int64_t) gridDim.x * B1_THREADS;
+   for (int64_t I = (int64_t) blockIdx.x * B1_THREADS + threadIdx.x; I < nc; I += stride) {
+      const int q1 = rptr[I + 1];
+      double acc = 0.0;
+      for (int q0 = rptr[I]; q0 < q1; q0 += 8) {
+         int id[8];
+         double v[8];
+#pragma unroll
+         for (int t = 0; t < 8; t++) id[t] = (q0 + t < q1) ? ridx[q0 + t] : -1;
+#pragma unroll
+         for (int t = 0; t < 8; t++) v[t] = (id[t] >= 0) ? fine[id[t]] : 0.0;
+#pragma unroll
+         for (int t = 0; t < 8; t++)
+            if (q0 + t < q1) acc += v[t];
+      }
+      coarse[I] = acc;
+      coarse_x[I] = 0.0;
+   }
+}
+
+void launch_restrict_sum (const int *rptr, const int *ridx, const double *fine, double *coarse, int64_t nc, hipStream_t st, double *coarse_x)
 {
    if (nc <= 0) return;
+   if (coarse_x) {
+      hipLaunchKernelGGL (restrict_sum_fill_kernel, dim3 (red_grid (nc) * 2), dim3 (B1_THREADS), 0, st, rptr, ridx, fine, coarse, coarse_x, nc);
+      return;
+   }
    hipLaunchKernelGGL (restrict_sum_kernel, dim3 (red_grid (nc) * 2), dim3 (B1_THREADS), 0, st, rptr, ridx, fine, coarse, nc);
 }
 
@@ -568,6 +629,29 @@ void launch_scatter (const int *perm, const double *in, double *out, int64_t n, 
 {
    if (n <= 0) return;
    hipLaunchKernelGGL (gather_kernel, dim3 (red_grid (n) * 2), dim3 (B1_THREADS), 0, st, perm, in, out, n, 1);
+}
+
+// Tuning step_glue bit 8: what scale_to_kernel (w -> v), gather_kernel (v -> level 0's b) and zero_kernel (level 0's x) do in
+// three launches.  v = w * inv is the product scale_to_kernel forms, formed once per element.
+__global__ __launch_bounds__ (B1_THREADS)
+void cycle_entry_kernel (const int *__restrict__ perm, const double *__restrict__ w, const double *__restrict__ inv,
+                         double *__restrict__ vnext, double *__restrict__ b0, double *__restrict__ x0, int64_t n)
+{
+   const double a = inv[0];
+   const int64_t stride = (int64_t) gridDim.x * B1_THREADS;
+   for (int64_t i = (int64_t) blockIdx.x * B1_THREADS + threadIdx.x; i < n; i += stride) {
+      const int p = perm[i];
+      const double v = w[p] * a;
+      vnext[p] = v;
+      b0[i] = v;
+      x0[i] = 0.0;
+   }
+}
+
+void launch_cycle_entry (const int *perm, const double *w, const double *inv, double *vnext, double *b0, double *x0, int64_t n, hipStream_t st)
+{
+   if (n <= 0) return;
+   hipLaunchKernelGGL (cycle_entry_kernel, dim3 (red_grid (n) * 2), dim3 (B1_THREADS), 0, st, perm, w, inv, vnext, b0, x0, n);
 }
 
 // one wave per output row; the coarsest level is at most a few thousand unknowns

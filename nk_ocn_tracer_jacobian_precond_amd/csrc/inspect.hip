@@ -159,6 +159,11 @@ extern "C" int nkp_time_kernel (nkp_solver *s, int which, int arg, int reps, dou
       const int prc = valprod_time_prepare (s, arg, which);
       if (prc) return prc;
    }
+   StepEvent step_ev;
+   if (which == 2) {
+      const int erc = step_ev.make (s);
+      if (erc) return erc;
+   }
    hipEvent_t e0, e1;
    HIPCHK (hipEventCreate (&e0));
    HIPCHK (hipEventCreate (&e1));
@@ -184,7 +189,10 @@ extern "C" int nkp_time_kernel (nkp_solver *s, int which, int arg, int reps, dou
          else if (which == 0) spmv_op (s, s->t1, s->t2, nullptr, 0);
          else if (which == 8) launch_diag_spmv (s->A, s->t1, s->t2, nullptr, 0, s->stream);
          else if (which == 1) apply_precond_once (s, s->t1, s->t2);
-         else if (which == 2) arnoldi_step_device (s, arg);
+         else if (which == 2) {      // the step as fgmres runs it, the hand-over of the Hessenberg column to the host included
+            const int src = arnoldi_hand_over (s, arg, step_ev.ev);
+            if (src) { s->ml.entered = 0; return src; }
+         }
          else if (which == 5) valgrad_time_launch (s, arg);
          else if (which == 6) valprod_time_launch (s, arg);
          else if (which == 7) valprod_time_composition (s, arg);
@@ -198,6 +206,7 @@ extern "C" int nkp_time_kernel (nkp_solver *s, int which, int arg, int reps, dou
    }
    (void) hipEventDestroy (e0);
    (void) hipEventDestroy (e1);
+   s->ml.entered = 0;      // which == 2: the cycle the last step entered ahead is dropped
    HIPCHK (hipGetLastError ());
    return NKP_OK;
 }

@@ -91,6 +91,12 @@ void arnoldi_apply (nkp_solver *s, int j)
    const int64_t ld = s->ld;
    double *zj = s->Z + (int64_t) j * ld;
    const double *vj = s->vf32 ? s->vcur : s->V + (int64_t) j * ld;
+   if (s->ml.entered) {
+      // v_j went into level 0 of the hierarchy with the kernel that stored it (arnoldi_hand_over): the rest of that cycle
+      ml_finish (s->ml, zj, s->stream);
+      spmv_op (s, zj, s->w, nullptr, 0);
+      return;
+   }
    if (s->equil) {
       // row-weighted iteration: the basis lives in the scaled space, operator R A M R^-1
       launch_vmul (vj, s->rinv, s->eqtmp, s->n, s->stream);
@@ -103,33 +109,86 @@ void arnoldi_apply (nkp_solver *s, int j)
    }
 }
 
-void arnoldi_orthogonalise (nkp_solver *s, int j)
+// orthogonalise w against V[0..j]: the Hessenberg column h[0..j+1] in s->h_dev () is final, 1 / h[j+1] in misc_dev ()[1].
+// host_col (tuning step_glue bit 8, never row-distributed): the kernel that completes the column adds up ||w||^2 itself and
+// stores the column to that pinned host buffer too
+static void arnoldi_column (nkp_solver *s, int j, double *host_col = nullptr)
 {
    const int64_t ld = s->ld;
    launch_multi_dot (s->V, s->vf32, ld, j + 1, s->w, s->n, s->partial, s->h_dev (), s->stream);
    allreduce_dev (s, s->h_dev (), j + 2, 0);                 // one allreduce per Gram-Schmidt pass
-   launch_update_w (s->V, s->vf32, ld, j + 1, s->h_dev (), s->w, s->n, s->partial, s->misc_dev (), s->stream);
+   launch_update_w (s->V, s->vf32, ld, j + 1, s->h_dev (), s->w, s->n, s->partial, host_col && !s->opt.reorth ? nullptr : s->misc_dev (), s->stream);
    if (s->opt.reorth) {
       launch_multi_dot (s->V, s->vf32, ld, j + 1, s->w, s->n, s->partial, s->h2_dev (), s->stream);
       allreduce_dev (s, s->h2_dev (), j + 2, 0);
-      launch_update_w (s->V, s->vf32, ld, j + 1, s->h2_dev (), s->w, s->n, s->partial, s->misc_dev (), s->stream);
+      launch_update_w (s->V, s->vf32, ld, j + 1, s->h2_dev (), s->w, s->n, s->partial, host_col ? nullptr : s->misc_dev (), s->stream);
       allreduce_dev (s, s->misc_dev (), 1, 0);
-      launch_finish_column (s->h_dev (), s->h2_dev (), j + 1, s->misc_dev (), s->misc_dev () + 1, s->stream);
+      if (host_col) launch_finish_column_host (s->h_dev (), s->h2_dev (), j + 1, s->partial, s->n, s->misc_dev (), s->misc_dev () + 1, host_col, s->stream);
+      else launch_finish_column (s->h_dev (), s->h2_dev (), j + 1, s->misc_dev (), s->misc_dev () + 1, s->stream);
    } else if (s->dist.on && s->tune.dist_one_reduce) {
       // ||w||^2 after the update from the message that is already reduced (w.w rode along with the dots): one allreduce per step
       launch_finish_column_pythagoras (s->h_dev (), j + 1, s->misc_dev () + 1, s->stream);
-   } else {
+   } else if (host_col) launch_finish_column_host (s->h_dev (), nullptr, j + 1, s->partial, s->n, s->misc_dev (), s->misc_dev () + 1, host_col, s->stream);
+   else {
       allreduce_dev (s, s->misc_dev (), 1, 0);
       launch_finish_column (s->h_dev (), nullptr, j + 1, s->misc_dev (), s->misc_dev () + 1, s->stream);
    }
+}
+
+// v_{j+1} = w / ||w||
+static void arnoldi_normalise (nkp_solver *s, int j)
+{
+   const int64_t ld = s->ld;
    if (s->vf32) launch_scale_to (s->w, s->misc_dev () + 1, s->vcur, (float *) s->V + (int64_t) (j + 1) * ld, s->n, s->stream);
    else launch_scale_to (s->w, s->misc_dev () + 1, s->V + (int64_t) (j + 1) * ld, nullptr, s->n, s->stream);
 }
 
-void arnoldi_step_device (nkp_solver *s, int j)
+void arnoldi_orthogonalise (nkp_solver *s, int j)
 {
+   arnoldi_column (s, j);
+   arnoldi_normalise (s, j);
+}
+
+// Tuning step_glue bit 8, second half: the preconditioner of step j + 1 is applied to v_{j+1} itself -- f64 basis, no row weights,
+// one plain cycle of this solver's own hierarchy -- so the kernel that stores v_{j+1} can be the one that enters the cycle (ml_enter).
+static bool step_enters_cycle (const nkp_solver *s)
+{
+   return s->opt.precond == NKP_PRECOND_MULTILEVEL && !s->dist.on && !s->vf32 && !s->equil && s->steps_now == 1 &&
+          !s->ml.lev.empty () && s->ml.lev[0].n == s->n;
+}
+
+// One Arnoldi step of FGMRES and its hand-over: on return column j of the Hessenberg matrix is in s->hpin[0 .. j+1].
+// Without step_glue bit 8: the step, the copy, hipStreamSynchronize.  With it (ev; not row-distributed, no row weights, one cycle
+// per iteration, and a slot j + 1 in the restart cycle): the kernel that completes the column also stores it to s->hpin, which is
+// pinned host memory, and the host waits on the event behind that kernel while the stream goes on with v_{j+1} -- where
+// step_enters_cycle, with one kernel that writes it to the basis and into level 0 of the hierarchy, and with the first half sweep
+// of the next cycle.  No copy command stands between the column and those launches.  If the host then ends the restart cycle, the launches enqueued ahead have written v_{j+1} and scratch of
+// the hierarchy only, and fg_end_cycle follows them in stream order.
+int arnoldi_hand_over (nkp_solver *s, int j, hipEvent_t ev)
+{
+   const bool early = ev && (s->tune.step_glue & 8) && j + 1 < s->m && !s->dist.on && !s->equil && s->steps_now == 1;
    arnoldi_apply (s, j);
-   arnoldi_orthogonalise (s, j);
+   arnoldi_column (s, j, early ? s->hpin : nullptr);
+   if (early) HIPCHK (hipEventRecord (ev, s->stream));
+   if (early && step_enters_cycle (s)) ml_enter (s->ml, s->w, s->misc_dev () + 1, s->V + (int64_t) (j + 1) * s->ld, s->stream);
+   else arnoldi_normalise (s, j);
+   if (early) HIPCHK (hipEventSynchronize (ev));
+   else {
+      HIPCHK (hipMemcpyAsync (s->hpin, s->h_dev (), (size_t) (j + 2) * sizeof (double), hipMemcpyDeviceToHost, s->stream));
+      HIPCHK (hipStreamSynchronize (s->stream));
+   }
+   return NKP_OK;
+}
+
+int StepEvent::make (const nkp_solver *s)
+{
+   if (!ev && (s->tune.step_glue & 8) && !s->dist.on) HIPCHK (hipEventCreateWithFlags (&ev, hipEventDisableTiming | hipEventReleaseToSystem));
+   return NKP_OK;
+}
+
+StepEvent::~StepEvent ()
+{
+   if (ev) (void) hipEventDestroy (ev);
 }
 
 // ---------------------------------------------------------------- FGMRES as a state machine
@@ -190,6 +249,7 @@ int fg_restart (nkp_solver *s, FgmresState &F)
    hipStream_t st = s->stream;
    const int64_t n = s->n;
    int rc;
+   s->ml.entered = 0;      // a cycle entered ahead of a step that never came (arnoldi_hand_over) is dropped
    // true residual (unscaled: the stopping test is ||b - A x||_2 <= rtol ||b||_2 whatever norm the iteration minimises)
    spmv_op (s, s->x, s->r, s->b, 1);
    double r2 = 0.0;
@@ -255,20 +315,21 @@ int fg_end_cycle (nkp_solver *s, FgmresState &F)
 static int fgmres (nkp_solver *s, int *iters_out, double *relres_out)
 {
    FgmresState F;
+   StepEvent ev;
    int rc = fg_begin (s, F);
    if (rc) return rc;
+   if ((rc = ev.make (s))) return rc;
    while (!F.finished) {
       if ((rc = fg_restart (s, F))) return rc;
       if (F.finished) break;
       for (;;) {
-         arnoldi_step_device (s, F.j);
-         HIPCHK (hipMemcpyAsync (s->hpin, s->h_dev (), (size_t) (F.j + 2) * sizeof (double), hipMemcpyDeviceToHost, s->stream));
-         HIPCHK (hipStreamSynchronize (s->stream));
+         if ((rc = arnoldi_hand_over (s, F.j, ev.ev))) { s->ml.entered = 0; return rc; }
          if (s->comm_failed) return fail (NKP_ECOMM, "nkp_solve: a collective of the distributed solve failed (Arnoldi step %d)", F.its + 1);
          if (fg_post_step (s, F)) break;
       }
       if ((rc = fg_end_cycle (s, F))) return rc;
    }
+   s->ml.entered = 0;
    HIPCHK (hipGetLastError ());
    *iters_out = F.its;
    *relres_out = F.relres;

@@ -55,10 +55,38 @@ static void gs_sweep (MlHierarchy &H, MlLevel &V, bool reverse, bool fused, hipS
    for (int step = 0; step < 2; step++) gs_half (H, V, reverse ? 1 - step : step, fused, st);
 }
 
-static void ml_cycle (MlHierarchy &H, int l, hipStream_t st)
+// the first half sweep of a smoothed level from x = 0: the column solves of colour 0 straight from b (r = b there)
+static void first_half_sweep (MlHierarchy &H, MlLevel &V, bool fused, hipStream_t st)
+{
+   if (fused) {
+      // colour 0's first values go to the second buffer: the level starts incoherent, and the odd number of fused half
+      // sweeps that follows (colour 1, then nu - 1 full sweeps) ends coherent
+      if (V.wave_fused) column_solves (H, V, 0, V.b, V.x2, 0, st);
+      else launch_colblock_apply_lanes (V.B, V.color_grp[0], V.color_grp[1], V.b, V.x2, 0, st);
+      V.cur[0] = 1;
+      after_half_sweep (H, V, 0, V.x2, 1, st);
+   } else {
+      column_solves (H, V, 0, V.b, V.x, 0, st);
+      after_half_sweep (H, V, 0, V.x, 1, st);
+   }
+}
+
+// level l starts its cycle with a fill of x that whoever wrote its b may do in the same pass (tuning step_glue bit 4): every level
+// but a dense last one and the head of a single-launch tail
+static inline bool ml_level_fills_x (const MlHierarchy &H, int l)
+{
+   if (l == H.tail_from) return false;
+   return !(l == (int) H.lev.size () - 1 && H.coarse_inv);
+}
+
+// started: what of level l's cycle is already done -- ML_FILLED: x = 0 (with b); ML_SOLVED: the first half sweep too (level 0,
+// smoothed, no hook: ml_enter)
+enum { ML_FRESH = 0, ML_FILLED = 1, ML_SOLVED = 2 };
+
+static void ml_cycle (MlHierarchy &H, int l, hipStream_t st, int started = ML_FRESH)
 {
    MlLevel &V = H.lev[l];
-   V.cur[0] = V.cur[1] = 0;
+   if (started != ML_SOLVED) V.cur[0] = V.cur[1] = 0;
    if (l == 0) H.hook_left = 0;
    if (l == H.tail_from && H.coarse_inv && H.gamma_to <= H.gamma_from && ml_tail_launch (H, l, st) == 0) return;
    if (l == (int) H.lev.size () - 1) {
@@ -69,7 +97,7 @@ static void ml_cycle (MlHierarchy &H, int l, hipStream_t st)
       }
       // no dense inverse: many sweeps of the column smoother from x = 0 (what is left here is diagonally dominant)
       const int sweeps = H.tune->ml_coarsest_sweeps > 0 ? H.tune->ml_coarsest_sweeps : 30;
-      launch_fill (V.x, 0.0, V.n, st);
+      if (started == ML_FRESH) launch_fill (V.x, 0.0, V.n, st);
       column_solves (H, V, 0, V.b, V.x, 0, st);
       gs_half (H, V, 1, false, st);
       for (int s = 1; s < sweeps; s++) gs_sweep (H, V, s & 1, false, st);
@@ -79,20 +107,9 @@ static void ml_cycle (MlHierarchy &H, int l, hipStream_t st)
    const int nu = (l >= H.coarse_from) ? H.nu_coarse : H.nu;
    if (l == 0 && H.hook) H.hook_left = 4 * nu;      // 2 nu half sweeps before and 2 nu after the coarse correction
    // pre-smoothing from x = 0: the first half-sweep needs no SpMV (r = b on colour 0)
-   launch_fill (V.x, 0.0, V.n, st);
-   if (fused) {
-      // colour 0's first values go to the second buffer: the level starts incoherent, and the odd number of fused half
-      // sweeps that follows (colour 1, then nu - 1 full sweeps) ends coherent
-      if (V.wave_fused) column_solves (H, V, 0, V.b, V.x2, 0, st);
-      else launch_colblock_apply_lanes (V.B, V.color_grp[0], V.color_grp[1], V.b, V.x2, 0, st);
-      V.cur[0] = 1;
-      after_half_sweep (H, V, 0, V.x2, 1, st);
-      gs_half (H, V, 1, true, st);
-   } else {
-      column_solves (H, V, 0, V.b, V.x, 0, st);
-      after_half_sweep (H, V, 0, V.x, 1, st);
-      gs_half (H, V, 1, false, st);
-   }
+   if (started == ML_FRESH) launch_fill (V.x, 0.0, V.n, st);
+   if (started != ML_SOLVED) first_half_sweep (H, V, fused, st);
+   gs_half (H, V, 1, fused, st);
    for (int s = 1; s < nu; s++) gs_sweep (H, V, false, fused, st);
    // coarse-grid correction; levels in [gamma_from, gamma_to) repeat it on the updated residual, which by the
    // Galerkin property is the second coarse iteration of a W-cycle (NKP_ML_GAMMA_FROM / NKP_ML_GAMMA_TO, default off)
@@ -101,8 +118,10 @@ static void ml_cycle (MlHierarchy &H, int l, hipStream_t st)
    for (int g = 0; g < gamma; g++) {
       if (V.L.dg_val) launch_diag_residual (V.L, V.color_tile[0], V.color_tile[2], V.xnow (), V.b, V.r, st);
       else launch_csr_spmv (V.L, V.xnow (), V.r, V.b, 1, st);
-      launch_restrict_sum (V.rptr, V.ridx, V.r, C.b, V.nc, st);
-      ml_cycle (H, l + 1, st);
+      // tuning step_glue bit 4: the restriction zeroes the coarse x where the coarse cycle would start with that fill
+      const bool fill = (H.tune->step_glue & 4) && ml_level_fills_x (H, l + 1);
+      launch_restrict_sum (V.rptr, V.ridx, V.r, C.b, V.nc, st, fill ? C.x : nullptr);
+      ml_cycle (H, l + 1, st, fill ? ML_FILLED : ML_FRESH);
       launch_prolong_add (V.cmap, C.xnow (), V.xnow (), V.n, H.omega, st);
    }
    for (int s = 0; s < nu; s++) gs_sweep (H, V, true, fused, st);
@@ -115,6 +134,32 @@ void ml_apply (MlHierarchy &H, const double *r, double *z, hipStream_t st, const
    H.hook = hook;
    ml_cycle (H, 0, st);
    H.hook = nullptr;
+   launch_scatter (H.perm0, V.xnow (), z, V.n, st);
+}
+
+// The same cycle entered from the Krylov step (tuning step_glue bit 8): r = w * inv[0] is never stored on its own -- one kernel
+// writes it to vnext (original row order) and to level 0's b, and zeroes level 0's x; the first half sweep of level 0 follows
+// where the cycle has one of its own (a smoothed level 0).  ml_finish runs the rest of the cycle and scatters z.  Between the
+// two calls nothing else may run on this hierarchy's vectors; single-GPU cycles only (no hook).
+void ml_enter (MlHierarchy &H, const double *w, const double *inv, double *vnext, hipStream_t st)
+{
+   MlLevel &V = H.lev[0];
+   launch_cycle_entry (H.perm0, w, inv, vnext, V.b, V.x, V.n, st);
+   H.entered = ML_FILLED;
+   if (H.lev.size () >= 2 && H.tail_from != 0) {
+      V.cur[0] = V.cur[1] = 0;
+      H.hook_left = 0;
+      first_half_sweep (H, V, ml_level_fused (H, V), st);
+      H.entered = ML_SOLVED;
+   }
+}
+
+void ml_finish (MlHierarchy &H, double *z, hipStream_t st)
+{
+   MlLevel &V = H.lev[0];
+   const int started = H.entered;
+   H.entered = ML_FRESH;
+   ml_cycle (H, 0, st, started);
    launch_scatter (H.perm0, V.xnow (), z, V.n, st);
 }
 

@@ -50,6 +50,7 @@ struct MlHierarchy {
    std::vector<MlLevel> lev;
    const MlSmoothHook *hook = nullptr;   // set by ml_apply / ml_apply_batch_split_ext for the one application they run
    int hook_left = 0;           // level-0 half sweeps of the running cycle still to come
+   int entered = 0;             // ml_enter has started a cycle that ml_finish completes: 1 = level 0's b and x are set, 2 = its first half sweep is launched
    int *perm0 = nullptr;        // level-0 row i holds original row perm0[i]
    double *coarse_inv = nullptr;   // dense inverse of the coarsest operator (row-major)
    float *coarse_invf = nullptr;   // f32 storage mode: the copy the cycle multiplies with (rows padded to coarse_ldf)
@@ -96,6 +97,10 @@ inline int ml_level0_sweeps (const MlHierarchy &H) { return 0 >= H.coarse_from ?
 inline bool ml_level0_hookable (const MlHierarchy &H) { return H.lev.size () >= 2 && H.tail_from != 0 && ml_level0_sweeps (H) > 0; }
 // z = V-cycle(r) in the ORIGINAL row order; hook: see MlSmoothHook (NULL = none)
 void ml_apply (MlHierarchy &H, const double *r, double *z, hipStream_t st, const MlSmoothHook *hook = nullptr);
+// the same cycle for r = w * inv[0] (a device scalar), entered in one kernel that also stores r to vnext, with the first half sweep
+// of level 0 behind it (tuning step_glue bit 8).  ml_finish (H, z, st) runs what is left.  No hook: single-GPU cycles.
+void ml_enter (MlHierarchy &H, const double *w, const double *inv, double *vnext, hipStream_t st);
+void ml_finish (MlHierarchy &H, double *z, hipStream_t st);
 // the same cycle on K interleaved right-hand sides (r, z: n * K doubles, element (row, k) at row * K + k; K = 2 or 4); every
 // column gets the bits ml_apply gives it alone.  ml_batch_prepare allocates the level vectors (0, or -2 = out of device memory).
 int ml_batch_prepare (MlHierarchy &H, int K);

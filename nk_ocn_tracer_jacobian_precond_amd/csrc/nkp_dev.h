@@ -352,6 +352,9 @@ void launch_count_entries (const double *x, int64_t n, double *partial, double *
 // small device-side scalar programs of the Krylov drivers
 // h[j] += h2[j] (j<k); h[k] = sqrt(nrm2); inv[0] = 1/h[k] (0 if h[k]==0)
 void launch_finish_column (double *h, const double *h2, int k, const double *nrm2, double *inv, hipStream_t st);
+// the same behind a launch_update_w with out_nrm2 = NULL (tuning step_glue bit 8): adds up that launch's partial sums of the n-vector
+// itself (to nrm2_out, same order) and stores h[0 .. k] to host_col too, pinned host memory
+void launch_finish_column_host (double *h, const double *h2, int k, const double *partial, int64_t n, double *nrm2_out, double *inv, double *host_col, hipStream_t st);
 void launch_finish_column_pythagoras (double *h, int k, double *inv, hipStream_t st);
 // The Gram-Schmidt kernels above for a group of R systems in one launch each (batched solve of the row-distributed flavour):
 // system r has its own basis, w and partial sums; its dots form row r of ONE message msg[r * (k + 1) + j] (j <= k) that a
@@ -378,7 +381,10 @@ void launch_fill (double *y, double v, int64_t n, hipStream_t st);
 
 // ---------------------------------------------------------------- grid transfer / permutation
 // coarse[I] = sum_{q in [rptr[I], rptr[I+1])} fine[ridx[q]]   (restriction = P^T, fixed order)
-void launch_restrict_sum (const int *rptr, const int *ridx, const double *fine, double *coarse, int64_t nc, hipStream_t st);
+// coarse_x (tuning step_glue bit 4): also zeroed, nc doubles
+void launch_restrict_sum (const int *rptr, const int *ridx, const double *fine, double *coarse, int64_t nc, hipStream_t st, double *coarse_x = nullptr);
+// vnext[perm[i]] = b0[i] = w[perm[i]] * inv[0], x0[i] = 0 (tuning step_glue bit 8)
+void launch_cycle_entry (const int *perm, const double *w, const double *inv, double *vnext, double *b0, double *x0, int64_t n, hipStream_t st);
 // fine[i] += coarse[cmap[i]]                                  (prolongation = P)
 void launch_prolong_add (const int *cmap, const double *coarse, double *fine, int64_t nf, double omega, hipStream_t st);
 // out[i] = in[perm[i]]

@@ -316,7 +316,15 @@ NKP_PRIVATE void spmv_op (nkp_solver *s, const double *x, double *y, const doubl
 // ONE application of the cycle and of A to K interleaved vectors and runs (2) per system.
 NKP_PRIVATE void arnoldi_apply (nkp_solver *s, int j);
 NKP_PRIVATE void arnoldi_orthogonalise (nkp_solver *s, int j);
-NKP_PRIVATE void arnoldi_step_device (nkp_solver *s, int j);
+// one step as fgmres runs it, up to the Hessenberg column in s->hpin (tuning step_glue bit 8: krylov.hip); ev: the event
+// of StepEvent, or NULL.  Whoever drives it clears s->ml.entered when no further step follows.
+NKP_PRIVATE int arnoldi_hand_over (nkp_solver *s, int j, hipEvent_t ev);
+// the event a run of such steps waits on (made only where tuning step_glue bit 8 can use it), destroyed with the object
+struct NKP_PRIVATE StepEvent {
+   hipEvent_t ev = nullptr;
+   int make (const nkp_solver *s);
+   ~StepEvent ();
+};
 // The FGMRES state machine (FgmresState and its host arithmetic: krylov_host.h) around the device work of one system.
 // ||b||, the trivial case b = 0; returns a negative code on failure
 NKP_PRIVATE int fg_begin (nkp_solver *s, FgmresState &F);

@@ -61,7 +61,7 @@ static void builtin_tuning (nkp_tuning *t)
    t->spmv_variant = 4; t->spmv_compress = 0; t->spmv_pipe_min = 1024; t->spmv_run = 1; t->spmv_wgs = 256;
    t->rhs_batch = 1; t->batch_spmv_rows = 1; t->precond_steps = 0; t->equil = -1; t->dist_overlap = 1; t->dist_ras = 1; t->dist_one_reduce = 0; t->force_dist = 0; t->setup_threads = 0; t->plan_times = 0;
    t->ml_drop_intertracer = 0; t->ml_huge_from = -1; t->dist_ras_rings = 1; t->ml_diag = 32; t->spmv_diag = 32;
-   t->ml_lane_fused = 50000; t->dist_smooth_exchange = 0;
+   t->ml_lane_fused = 50000; t->dist_smooth_exchange = 0; t->step_glue = 12;
 }
 
 const nkp_tuning &nkp_builtin_tuning ()
@@ -107,6 +107,7 @@ extern "C" int nkp_default_tuning (nkp_tuning *t)
    ENV_INT ("NKP_SPMV_DIAG", spmv_diag);
    ENV_INT ("NKP_ML_LANE_FUSED", ml_lane_fused);
    ENV_INT ("NKP_DIST_SMOOTH_EXCHANGE", dist_smooth_exchange);
+   ENV_INT ("NKP_STEP_GLUE", step_glue);
 #undef ENV_INT
 #undef ENV_POS
 #undef ENV_FLAG

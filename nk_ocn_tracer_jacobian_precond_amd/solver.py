@@ -62,6 +62,7 @@ class NkpTuning(C.Structure):
         ("setup_threads", C.c_int), ("plan_times", C.c_int), ("ml_drop_intertracer", C.c_int), ("dist_one_reduce", C.c_int), ("ml_huge_from", C.c_int), ("col_ldsres_min", C.c_int), ("col_sort_groups", C.c_int), ("batch_spmv_rows", C.c_int),
         ("dist_ras_rings", C.c_int), ("ml_diag", C.c_int), ("spmv_diag", C.c_int), ("ml_lane_fused", C.c_int),
         ("dist_smooth_exchange", C.c_int),
+        ("step_glue", C.c_int),
     ]
 
 
