@@ -69,15 +69,8 @@ int batch_prepare_exchange (nkp_solver *s, int K)
       return fail (NKP_ENOMEM, "nkp_solve_batch: pinned host memory for the Gram-Schmidt messages");
    }
    const size_t gcount = 2 * (size_t) (s->m + 2) + 2;
-   std::vector<std::pair<double **, size_t>> set = { { &s->dist.bxe, (size_t) (s->n + s->dist.n_halo) }, { &s->dist.bsend, (size_t) s->dist.nsend }, { &s->dist.gmsg, gcount } };
-   if (s->dist.ras_sep) {
-      set.push_back ({ &s->dist.bras_send, (size_t) s->dist.ras_nsend });
-      set.push_back ({ &s->dist.bras_recv, (size_t) s->dist.n_sel });
-   }
-   if (s->dist.smooth) {      // the fine-level exchange, K rows wide
-      set.push_back ({ &s->dist.bsmooth_send, (size_t) s->dist.smooth_nsend_max });
-      set.push_back ({ &s->dist.bsmooth_recv, (size_t) s->dist.smooth_nrecv_max });
-   }
+   std::vector<std::pair<double **, size_t>> set = { { &s->dist.bxe, (size_t) (s->n + s->dist.n_halo) }, { &s->dist.gmsg, gcount } };
+   s->dist.each_exchange ([&set] (RowExchange &X, bool in_force) { push_wide (X, in_force, set); });
    return buffer_set (s, set, &s->dist.bK, K);
 }
 
@@ -129,21 +122,12 @@ static void batch_precond (nkp_solver *s, int K, const double *const *src, const
    auto &D = s->dist;
    double *const none[NKP_BATCH_MAX] = {};
    if (s->opt.precond == NKP_PRECOND_MULTILEVEL && D.on && D.ras) {
-      double *halo = D.bxe + n * K;
-      if (D.ras_sep) {
-         // several rings: the overlap rows alone, K wide, into a block of their own in the hierarchy's order
-         D.ras_send_counts_k.resize (D.ras_send_counts.size ());
-         D.ras_recv_counts_k.resize (D.ras_recv_counts.size ());
-         for (size_t p = 0; p < D.ras_send_counts.size (); p++) D.ras_send_counts_k[p] = D.ras_send_counts[p] * K;
-         for (size_t p = 0; p < D.ras_recv_counts.size (); p++) D.ras_recv_counts_k[p] = D.ras_recv_counts[p] * K;
-         if (D.ras_nsend) launch_pack_rows_split (K, D.ras_send_idx, src, D.bras_send, D.ras_nsend, st);
-         alltoallv_dev (s, D.bras_send, D.ras_send_counts_k.data (), D.bras_recv, D.ras_recv_counts_k.data (), st);
-         ml_apply_batch_split_ext (s->ml, K, src, D.bras_recv, nullptr, n, zi, dz ? dz : none, st, smooth_hook_of (s));
-      } else {
-         if (D.nsend) launch_pack_rows_split (K, D.send_idx, src, D.bsend, D.nsend, st);
-         alltoallv_dev (s, D.bsend, D.send_counts_k.data (), halo, D.recv_counts_k.data (), st);
-         ml_apply_batch_split_ext (s->ml, K, src, halo, D.sel_idx, n, zi, dz ? dz : none, st, smooth_hook_of (s));
-      }
+      // several rings: the overlap rows alone, K wide, in the hierarchy's order; one ring: the SpMV's halo, picked from by sel_idx
+      RowExchange &X = D.ras_sep ? D.x_ras : D.x_halo;
+      double *ext = D.ras_sep ? X.recv_for (K) : halo_rows_of (s, K);
+      if (X.nsend) launch_pack_rows_split (K, X.send_idx, src, X.send_for (K), X.nsend, st);
+      exchange_rows (s, X, K, X.send_for (K), ext, st);
+      ml_apply_batch_split_ext (s->ml, K, src, ext, D.ras_sep ? nullptr : D.sel_idx, n, zi, dz ? dz : none, st, smooth_hook_of (s));
    } else if (s->opt.precond == NKP_PRECOND_MULTILEVEL) {
       // permutation into the hierarchy's row order and the (de-)interleave in one kernel each
       ml_apply_batch_split (s->ml, K, src, zi, dz ? dz : none, st, src_scale);
@@ -159,7 +143,7 @@ static void batch_precond (nkp_solver *s, int K, const double *const *src, const
 }
 
 // dst_k = A x_k (b NULL; times out_scale when given) or dst_k = b_k - A x_k (b_k times b_scale when given) for the K columns
-// of xi -- s->bz, or the own rows of s->dist.bxe, whose halo rows arrive here as spmv_op fetches them for one vector
+// of xi -- s->bz, or the own rows of s->dist.bxe (K >= 2: halo_fetch copies nothing), whose halo rows arrive here as spmv_op fetches them
 static void batch_operator (nkp_solver *s, int K, const double *xi, const double *const *b, const double *b_scale, const double *out_scale, double *const *dst)
 {
    const int64_t n = s->n;
@@ -173,23 +157,10 @@ static void batch_operator (nkp_solver *s, int K, const double *xi, const double
       else if (split) launch_csr_spmv_batch_split_range (K, s->A, rb0, rb1, xi, dst, st, out_scale);
       else launch_csr_spmv_batch (K, s->A, rb0, rb1, xi, s->bw, b ? s->bvin : nullptr, b ? 1 : 0, st, out_scale);
    };
-   if (!D.on) rows (0, s->A.nrowblk);
+   if (D.on && D.overlap) halo_product_overlapped (s, K, xi, rows);
    else {
-      double *halo = D.bxe + n * K;
-      if (D.nsend) launch_gather_batch (K, D.send_idx, xi, D.bsend, D.nsend, st);
-      if (D.overlap) {
-         (void) hipEventRecord (D.ev_packed, st);
-         (void) hipStreamWaitEvent (D.comm_stream, D.ev_packed, 0);
-         alltoallv_dev (s, D.bsend, D.send_counts_k.data (), halo, D.recv_counts_k.data (), D.comm_stream);
-         (void) hipEventRecord (D.ev_halo, D.comm_stream);
-         rows (D.seg_rb[1], D.seg_rb[2]);
-         (void) hipStreamWaitEvent (st, D.ev_halo, 0);
-         rows (D.seg_rb[0], D.seg_rb[1]);
-         rows (D.seg_rb[2], D.seg_rb[3]);
-      } else {
-         alltoallv_dev (s, D.bsend, D.send_counts_k.data (), halo, D.recv_counts_k.data (), st);
-         rows (0, s->A.nrowblk);
-      }
+      if (D.on) halo_fetch (s, K, xi, nullptr, st);
+      rows (0, s->A.nrowblk);
    }
    if (!split) launch_deinterleave (K, s->bw, dst, n, st);
 }
@@ -212,13 +183,6 @@ static void batch_step_apply (nkp_solver *s, int K, nkp_solver *const *mem, cons
       }
    const double *rinv = s->equil ? s->rinv : nullptr, *rscale = s->equil ? s->rscale : nullptr;
    double *zi = s->dist.on ? s->dist.bxe : s->bz;
-   if (s->dist.on) {
-      auto &D = s->dist;
-      D.send_counts_k.resize (D.send_counts.size ());
-      D.recv_counts_k.resize (D.recv_counts.size ());
-      for (size_t p = 0; p < D.send_counts.size (); p++) D.send_counts_k[p] = D.send_counts[p] * K;
-      for (size_t p = 0; p < D.recv_counts.size (); p++) D.recv_counts_k[p] = D.recv_counts[p] * K;
-   }
    batch_precond (s, K, src, rinv, zi, dz);
    for (int c = 1; c < steps; c++) {
       // The run-time guard of fg_restart is per system: one whose steps_now it has lowered takes no part in the further
@@ -315,17 +279,23 @@ static int fgmres_batch (nkp_solver *s, int K, int nact, nkp_solver *const *mem,
 }
 
 // all ranks leave a step together (solver_impl.h)
-int dist_agree (nkp_solver *s, int local_rc, const char *who, const char *where)
+int dist_allgather (nkp_solver *s, int local_rc, int64_t mine, std::vector<int64_t> &all, const char *who, const char *where)
 {
    const nkp_comm_ops &c = s->dist.ops;
-   std::vector<int64_t> all ((size_t) c.nranks + 1, 0);
-   const std::string mine = local_rc ? last_error_message () : std::string ();
-   const bool comm_ok = c.allgather_i64_host (c.ctx, local_rc ? 1 : 0, all.data ()) == 0;
-   if (local_rc) { restore_error_message (mine); return local_rc; }
+   all.assign ((size_t) c.nranks + 1, 0);
+   const std::string text = local_rc ? last_error_message () : std::string ();
+   const bool comm_ok = c.allgather_i64_host (c.ctx, local_rc ? -1 : mine, all.data ()) == 0;
+   if (local_rc) { restore_error_message (text); return local_rc; }
    if (!comm_ok) return fail (NKP_ECOMM, "%s: allgather failed (%s)", who, where);
-   for (int p = 0; p < c.nranks; p++)
-      if (all[(size_t) p]) return fail (NKP_ECOMM, "%s: rank %d failed (%s); see its message", who, p, where);
    return NKP_OK;
+}
+
+int dist_agree (nkp_solver *s, int local_rc, const char *who, const char *where)
+{
+   std::vector<int64_t> all;
+   if (const int rc = dist_allgather (s, local_rc, 0, all, who, where)) return rc;
+   const int p = failed_rank (all);
+   return p < 0 ? NKP_OK : fail (NKP_ECOMM, "%s: rank %d failed (%s); see its message", who, p, where);
 }
 
 extern "C" int nkp_solve_batch_device (nkp_solver *s, int nrhs, const void *d_B, void *d_X, int64_t ldb, double *berr, int *iters, double *relres)
@@ -374,16 +344,12 @@ extern "C" int nkp_solve_batch_device (nkp_solver *s, int nrhs, const void *d_B,
       if (s->dist.on && K_wanted > s->dist.agreed_K) {
          // the width is a collective decision: every rank takes the narrowest one any rank reached, so that all of them run the
          // same sequence of collectives; a rank with a hard failure returns its code, the others NKP_ECOMM naming it
-         const nkp_comm_ops &c = s->dist.ops;
-         std::vector<int64_t> all ((size_t) c.nranks + 1, 0);
-         const std::string mine = rc ? last_error_message () : std::string ();
-         const bool comm_ok = c.allgather_i64_host (c.ctx, rc ? -1 : K, all.data ()) == 0;
-         if (rc) { restore_error_message (mine); return rc; }
-         if (!comm_ok) return fail (NKP_ECOMM, "nkp_solve_batch: allgather failed (interleave width)");
-         for (int p = 0; p < c.nranks; p++) {
-            if (all[(size_t) p] < 0) return fail (NKP_ECOMM, "nkp_solve_batch: rank %d failed while preparing %d right-hand sides; see its message", p, K_wanted);
+         std::vector<int64_t> all;
+         if ((rc = dist_allgather (s, rc, K, all, "nkp_solve_batch", "interleave width"))) return rc;
+         const int bad = failed_rank (all);
+         if (bad >= 0) return fail (NKP_ECOMM, "nkp_solve_batch: rank %d failed while preparing %d right-hand sides; see its message", bad, K_wanted);
+         for (int p = 0; p < s->dist.ops.nranks; p++)
             if (all[(size_t) p] < K) K = (int) all[(size_t) p];
-         }
          if (K == K_wanted) s->dist.agreed_K = K;
       }
       if (rc) return rc;

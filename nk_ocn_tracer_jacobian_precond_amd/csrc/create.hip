@@ -468,7 +468,8 @@ int clone_impl (nkp_solver *src, nkp_solver **out, bool member)
    s->batch_members.clear ();
    s->bvin = s->bz = s->bw = nullptr;
    s->batch_K = 0;
-   s->dist.bxe = s->dist.bsend = s->dist.gmsg = s->dist.ghpin = s->dist.bras_send = s->dist.bras_recv = s->dist.bsmooth_send = s->dist.bsmooth_recv = nullptr;
+   s->dist.bxe = s->dist.gmsg = s->dist.ghpin = nullptr;
+   s->dist.each_exchange ([] (RowExchange &X, bool) { X.drop_wide (); });
    s->dist.bK = s->dist.agreed_K = 0;
    s->dplan = nullptr;
    s->trans = s->trans_of = nullptr;

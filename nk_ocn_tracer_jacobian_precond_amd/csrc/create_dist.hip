@@ -71,12 +71,8 @@ extern "C" int nkp_create_dist (nkp_solver **out, const nkp_options *opt, int64_
    s->dist.n_global = n_global;
    s->dist.fst = fst_row;
    s->dist.n_halo = D.n_halo;
-   s->dist.nsend = D.nsend;
-   s->dist.send_counts.assign (D.give.begin (), D.give.end ());
-   s->dist.recv_counts.assign (D.need.begin (), D.need.end ());
-   bool ok = dev_alloc (s, &s->dist.send_idx, (size_t) D.nsend) == NKP_OK && dev_alloc (s, &s->dist.sendbuf, (size_t) D.nsend) == NKP_OK &&
-             dev_alloc (s, &s->dist.xe, (size_t) (m_loc + D.n_halo)) == NKP_OK;
-   if (ok && D.nsend) ok = hipMemcpy (s->dist.send_idx, D.send_rows.data (), (size_t) D.nsend * sizeof (int), hipMemcpyHostToDevice) == hipSuccess;
+   // the SpMV halo: its rows land behind the own rows of xe (K wide: of bxe), so it has no receive buffer
+   bool ok = exchange_install (s, s->dist.x_halo, D.send_rows.data (), D.give, D.need, false, D.nsend, -1, -1) && dev_alloc (s, &s->dist.xe, (size_t) (m_loc + D.n_halo)) == NKP_OK;
    if (ok && D.ras) {
       s->dist.n_sel = D.n_sel;
       s->dist.n_ext = m_loc + D.n_sel;
@@ -87,12 +83,8 @@ extern "C" int nkp_create_dist (nkp_solver **out, const nkp_options *opt, int64_
          ok = ok && dev_alloc (s, &s->dist.sel_idx, (size_t) D.n_sel) == NKP_OK;
          if (ok && D.n_sel) ok = hipMemcpy (s->dist.sel_idx, D.sel_hpos.data (), (size_t) D.n_sel * sizeof (int), hipMemcpyHostToDevice) == hipSuccess;
       } else {
-         s->dist.ras_nsend = (int64_t) D.ras_send_rows.size ();
-         s->dist.ras_send_counts.assign (D.ras_give.begin (), D.ras_give.end ());
-         s->dist.ras_recv_counts.assign (D.ras_need.begin (), D.ras_need.end ());
-         ok = ok && dev_alloc (s, &s->dist.ras_send_idx, (size_t) s->dist.ras_nsend) == NKP_OK && dev_alloc (s, &s->dist.ras_sendbuf, (size_t) s->dist.ras_nsend) == NKP_OK;
-         if (ok && s->dist.ras_nsend)
-            ok = hipMemcpy (s->dist.ras_send_idx, D.ras_send_rows.data (), (size_t) s->dist.ras_nsend * sizeof (int), hipMemcpyHostToDevice) == hipSuccess;
+         // (one row wide the overlap rows arrive at rext + n, K wide in a buffer of the exchange)
+         ok = ok && exchange_install (s, s->dist.x_ras, D.ras_send_rows.data (), D.ras_give, D.ras_need, false, (int64_t) D.ras_send_rows.size (), -1, D.n_sel);
       }
       s->dist.ras = ok;
    }

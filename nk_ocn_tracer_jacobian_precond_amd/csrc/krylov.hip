@@ -16,18 +16,12 @@ void apply_precond_once (nkp_solver *s, const double *rin, double *zout)
 {
    if (s->opt.precond == NKP_PRECOND_NONE) launch_copy (rin, zout, s->n, s->stream);
    else if (s->opt.precond == NKP_PRECOND_MULTILEVEL && s->dist.ras) {
-      if (s->dist.ras_sep) {
-         // several rings: the overlap rows alone, straight into place behind the own rows
-         if (s->dist.ras_nsend) launch_gather (s->dist.ras_send_idx, rin, s->dist.ras_sendbuf, s->dist.ras_nsend, s->stream);
-         alltoallv_dev (s, s->dist.ras_sendbuf, s->dist.ras_send_counts.data (), s->dist.rext + s->n, s->dist.ras_recv_counts.data (), s->stream);
-         launch_copy (rin, s->dist.rext, s->n, s->stream);
-      } else {
-         // the residual on the overlap rows comes from their owners (same exchange pattern as the SpMV's halo)
-         if (s->dist.nsend) launch_gather (s->dist.send_idx, rin, s->dist.sendbuf, s->dist.nsend, s->stream);
-         alltoallv_dev (s, s->dist.sendbuf, s->dist.send_counts.data (), s->dist.xe + s->n, s->dist.recv_counts.data (), s->stream);
-         launch_copy (rin, s->dist.rext, s->n, s->stream);
-         if (s->dist.n_sel) launch_gather (s->dist.sel_idx, s->dist.xe + s->n, s->dist.rext + s->n, s->dist.n_sel, s->stream);
-      }
+      // the residual on the overlap rows comes from their owners: alone and straight into place (several rings), or as the SpMV's halo
+      RowExchange &X = s->dist.ras_sep ? s->dist.x_ras : s->dist.x_halo;
+      if (X.nsend) launch_gather (X.send_idx, rin, X.send, X.nsend, s->stream);
+      exchange_rows (s, X, 1, X.send, s->dist.ras_sep ? s->dist.rext + s->n : halo_rows_of (s, 1), s->stream);
+      launch_copy (rin, s->dist.rext, s->n, s->stream);
+      if (!s->dist.ras_sep && s->dist.n_sel) launch_gather (s->dist.sel_idx, s->dist.xe + s->n, s->dist.rext + s->n, s->dist.n_sel, s->stream);
       ml_apply (s->ml, s->dist.rext, s->dist.zext, s->stream, smooth_hook_of (s));      // (tuning dist_smooth_exchange: + 4 nu - 1 exchanges)
       launch_copy (s->dist.zext, zout, s->n, s->stream);
    } else if (s->opt.precond == NKP_PRECOND_MULTILEVEL) ml_apply (s->ml, rin, zout, s->stream);
@@ -48,24 +42,12 @@ void spmv_op (nkp_solver *s, const double *x, double *y, const double *b, int mo
 {
    const double *xin = x;
    if (s->dist.on) {
-      launch_copy (x, s->dist.xe, s->n, s->stream);
-      if (s->dist.nsend) launch_gather (s->dist.send_idx, x, s->dist.sendbuf, s->dist.nsend, s->stream);
       xin = s->dist.xe;
       if (s->dist.overlap) {
-         // the exchange runs on its own stream behind the packing; the interior rows (no off-rank column) are multiplied
-         // meanwhile, the boundary rows once the halo has landed -- every row is still summed in stored order, so the
-         // result is the bit pattern of the serial version
-         (void) hipEventRecord (s->dist.ev_packed, s->stream);
-         (void) hipStreamWaitEvent (s->dist.comm_stream, s->dist.ev_packed, 0);
-         alltoallv_dev (s, s->dist.sendbuf, s->dist.send_counts.data (), s->dist.xe + s->n, s->dist.recv_counts.data (), s->dist.comm_stream);
-         (void) hipEventRecord (s->dist.ev_halo, s->dist.comm_stream);
-         launch_csr_spmv_range (s->A, s->dist.seg_rb[1], s->dist.seg_rb[2], xin, y, b, mode, s->stream);
-         (void) hipStreamWaitEvent (s->stream, s->dist.ev_halo, 0);
-         launch_csr_spmv_range (s->A, s->dist.seg_rb[0], s->dist.seg_rb[1], xin, y, b, mode, s->stream);
-         launch_csr_spmv_range (s->A, s->dist.seg_rb[2], s->dist.seg_rb[3], xin, y, b, mode, s->stream);
+         halo_product_overlapped (s, 1, x, [&] (int rb0, int rb1) { launch_csr_spmv_range (s->A, rb0, rb1, xin, y, b, mode, s->stream); });
          return;
       }
-      alltoallv_dev (s, s->dist.sendbuf, s->dist.send_counts.data (), s->dist.xe + s->n, s->dist.recv_counts.data (), s->stream);
+      halo_fetch (s, 1, x, nullptr, s->stream);
    }
    if (mode == 2) launch_csr_abs_spmv (s->A, xin, b, y, s->stream);
    else if (s->A.dg_vald) launch_diag_spmv (s->A, xin, y, b, mode, s->stream);      // tuning spmv_diag: same bits, no column indices

@@ -83,25 +83,12 @@ void launch_smooth_unpack (int K, const int *idx, const double *in, double *x, i
 static void smooth_refresh (void *ctx, int c, double *x, int K, hipStream_t st)
 {
    nkp_solver *s = (nkp_solver *) ctx;
-   auto &D = s->dist;
-   const int64_t ns = (int64_t) D.h_smooth_send[c].size (), nr = (int64_t) D.h_smooth_recv[c].size ();
-   if (K == 1) {
-      launch_smooth_pack (1, D.smooth_send_idx[c], x, D.smooth_sendbuf, ns, st);
-      alltoallv_dev (s, D.smooth_sendbuf, D.smooth_send_counts[c].data (), D.smooth_recvbuf, D.smooth_recv_counts[c].data (), st);
-      launch_smooth_unpack (1, D.smooth_recv_idx[c], D.smooth_recvbuf, x, nr, st);
-      return;
-   }
-   // (K <= D.bK: batch_prepare_exchange made the K-wide buffers before the group's first step)
-   const size_t P = D.smooth_send_counts[c].size ();
-   D.smooth_send_counts_k[c].resize (P);
-   D.smooth_recv_counts_k[c].resize (P);
-   for (size_t p = 0; p < P; p++) {
-      D.smooth_send_counts_k[c][p] = D.smooth_send_counts[c][p] * K;
-      D.smooth_recv_counts_k[c][p] = D.smooth_recv_counts[c][p] * K;
-   }
-   launch_smooth_pack (K, D.smooth_send_idx[c], x, D.bsmooth_send, ns, st);
-   alltoallv_dev (s, D.bsmooth_send, D.smooth_send_counts_k[c].data (), D.bsmooth_recv, D.smooth_recv_counts_k[c].data (), st);
-   launch_smooth_unpack (K, D.smooth_recv_idx[c], D.bsmooth_recv, x, nr, st);
+   // both colours pass through the buffers of colour 0 (K <= dist.bK: batch_prepare_exchange made the K-wide ones before the
+   // group's first step)
+   RowExchange &X = s->dist.x_smooth[c], &B = s->dist.x_smooth[0];
+   launch_smooth_pack (K, X.send_idx, x, B.send_for (K), X.nsend, st);
+   exchange_rows (s, X, K, B.send_for (K), B.recv_for (K), st);
+   launch_smooth_unpack (K, X.recv_idx, B.recv_for (K), x, X.nrecv, st);
 }
 
 const MlSmoothHook *smooth_hook_of (nkp_solver *s)
@@ -114,17 +101,16 @@ const MlSmoothHook *smooth_hook_of (nkp_solver *s)
 bool smooth_install (nkp_solver *s, const DistPlan &D)
 {
    auto &S = s->dist;
-   for (int c = 0; c < 2; c++) {
+   // one send and one receive buffer, and their K-wide twins, sized for the larger colour: colour 0 has them.  The index lists
+   // are level-0 positions: smooth_build_lists fills them
+   const int64_t cap_send = (int64_t) std::max (D.smooth_send_rows[0].size (), D.smooth_send_rows[1].size ());
+   const int64_t cap_recv = (int64_t) std::max (D.smooth_recv_rows[0].size (), D.smooth_recv_rows[1].size ());
+   bool ok = true;
+   for (int c = 0; c < 2 && ok; c++) {
       S.h_smooth_send[c] = D.smooth_send_rows[c];
       S.h_smooth_recv[c] = D.smooth_recv_rows[c];
-      S.smooth_send_counts[c] = D.smooth_give[c];
-      S.smooth_recv_counts[c] = D.smooth_need[c];
-      S.smooth_nsend_max = std::max (S.smooth_nsend_max, (int64_t) S.h_smooth_send[c].size ());
-      S.smooth_nrecv_max = std::max (S.smooth_nrecv_max, (int64_t) S.h_smooth_recv[c].size ());
+      ok = exchange_install (s, S.x_smooth[c], nullptr, D.smooth_give[c], D.smooth_need[c], true, c ? -1 : cap_send, c ? -1 : cap_recv, c ? -1 : cap_recv);
    }
-   bool ok = dev_alloc (s, &S.smooth_sendbuf, (size_t) S.smooth_nsend_max) == NKP_OK && dev_alloc (s, &S.smooth_recvbuf, (size_t) S.smooth_nrecv_max) == NKP_OK;
-   for (int c = 0; c < 2 && ok; c++)
-      ok = dev_alloc (s, &S.smooth_send_idx[c], S.h_smooth_send[c].size ()) == NKP_OK && dev_alloc (s, &S.smooth_recv_idx[c], S.h_smooth_recv[c].size ()) == NKP_OK;
    return ok;
 }
 
@@ -146,7 +132,7 @@ int smooth_build_lists (nkp_solver *s)
    for (int c = 0; c < 2; c++)
       for (int side = 0; side < 2; side++) {
          const std::vector<int32_t> &rows = side ? S.h_smooth_recv[c] : S.h_smooth_send[c];
-         int *dst = side ? S.smooth_recv_idx[c] : S.smooth_send_idx[c];
+         int *dst = side ? S.x_smooth[c].recv_idx : S.x_smooth[c].send_idx;
          idx.resize (rows.size ());
          for (size_t k = 0; k < rows.size (); k++) {
             // own rows go out, overlap rows come in: an index outside its part would be a write outside the level's vectors
@@ -157,12 +143,4 @@ int smooth_build_lists (nkp_solver *s)
          if (!idx.empty () && hipMemcpy (dst, idx.data (), idx.size () * sizeof (int), hipMemcpyHostToDevice) != hipSuccess) return -3;
       }
    return 0;
-}
-
-void smooth_release (nkp_solver *s)
-{
-   auto &S = s->dist;
-   for (void *p : { (void *) S.smooth_send_idx[0], (void *) S.smooth_send_idx[1], (void *) S.smooth_recv_idx[0], (void *) S.smooth_recv_idx[1], (void *) S.smooth_sendbuf,
-                    (void *) S.smooth_recvbuf, (void *) S.bsmooth_send, (void *) S.bsmooth_recv })
-      if (p) (void) hipFree (p);
 }

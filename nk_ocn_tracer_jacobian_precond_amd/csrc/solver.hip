@@ -52,16 +52,8 @@ void solver_free (nkp_solver *s)
    ml_free (s->ml);
    if (s->rf) { rf_free (*s->rf); delete s->rf; }
    if (s->dplan) { rf_dist_free (*s->dplan); delete s->dplan; }
-   if (s->dist.send_idx) (void) hipFree (s->dist.send_idx);
-   if (s->dist.sendbuf) (void) hipFree (s->dist.sendbuf);
-   if (s->dist.xe) (void) hipFree (s->dist.xe);
-   if (s->dist.sel_idx) (void) hipFree (s->dist.sel_idx);
-   if (s->dist.ras_send_idx) (void) hipFree (s->dist.ras_send_idx);
-   if (s->dist.ras_sendbuf) (void) hipFree (s->dist.ras_sendbuf);
-   smooth_release (s);
-   if (s->dist.rext) (void) hipFree (s->dist.rext);
-   if (s->dist.zext) (void) hipFree (s->dist.zext);
-   for (double *p : { s->dist.bxe, s->dist.bsend, s->dist.gmsg, s->dist.bras_send, s->dist.bras_recv })
+   s->dist.each_exchange ([] (RowExchange &X, bool) { exchange_release (X); });
+   for (void *p : { (void *) s->dist.xe, (void *) s->dist.sel_idx, (void *) s->dist.rext, (void *) s->dist.zext, (void *) s->dist.bxe, (void *) s->dist.gmsg })
       if (p) (void) hipFree (p);
    if (s->dist.ghpin) (void) hipHostFree (s->dist.ghpin);
    if (s->dist.ev_packed) (void) hipEventDestroy (s->dist.ev_packed);

@@ -16,12 +16,14 @@
 #include "multilevel.h"
 #include "refactor.h"
 #include "dist_plan.h"
+#include "row_exchange.h"
 #include "krylov_host.h"
 
 #include <atomic>
 #include <initializer_list>
 #include <memory>
 #include <string>
+#include <utility>
 #include <vector>
 
 #define HIPCHK(call)                                                                             \
@@ -46,10 +48,12 @@ struct nkp_solver {
    struct {
       bool on = false;
       nkp_comm_ops ops;
-      int64_t n_global = 0, fst = 0, n_halo = 0, nsend = 0;
-      std::vector<int> send_counts, recv_counts;
-      int *send_idx = nullptr;        // local rows other ranks need, grouped by destination rank
-      double *sendbuf = nullptr;      // packed values for them
+      int64_t n_global = 0, fst = 0, n_halo = 0;
+      // the exchanges of rows between the ranks (row_exchange.h): each owns its index lists, counts and buffers; where the rows land
+      // (xe, bxe, rext, sel_idx) is the solver's.  x_halo: the local rows other ranks read as columns, to behind the own rows of xe / bxe,
+      // and the overlap residual of one ring; x_ras: that of more rings; x_smooth[c]: the fine-level exchange of colour c
+      RowExchange x_halo, x_ras, x_smooth[2];
+      template <class F> void each_exchange (F f) { f (x_halo, on); f (x_ras, ras_sep); f (x_smooth[0], smooth); f (x_smooth[1], smooth); }      // (exchange, in force)
       double *xe = nullptr;           // [n + n_halo] extended SpMV input: own rows then halo rows
       // overlap of the halo exchange with the SpMV of the interior rows (rows without off-rank columns): the row blocks
       // are built per segment [head boundary rows | interior | tail boundary rows]; seg_rb[q] = first row block of segment q
@@ -64,35 +68,23 @@ struct nkp_solver {
       int *sel_idx = nullptr;         // position in the halo of every overlap row (one ring)
       double *rext = nullptr, *zext = nullptr;
       // two or more rings (tuning dist_ras_rings): rows of ring 2 and beyond are not in the SpMV halo, so the overlap residual has
-      // an exchange of its own -- own rows sent (by destination), their packed values, per-rank counts; the rows arrive at
-      // rext + n in the hierarchy's order.  bras_send / bras_recv: the same K wide (batch_prepare)
+      // an exchange of its own (x_ras); the rows arrive at rext + n in the hierarchy's order, K wide in x_ras.brecv
       int ras_rings = 0;              // the depth the ranks agreed on, 0 without overlap
       bool ras_sep = false;
-      int64_t ras_nsend = 0;
-      int *ras_send_idx = nullptr;
-      double *ras_sendbuf = nullptr, *bras_send = nullptr, *bras_recv = nullptr;
-      std::vector<int> ras_send_counts, ras_recv_counts, ras_send_counts_k, ras_recv_counts_k;
       // fine-level exchange (tuning dist_smooth_exchange; smooth_exchange.hip): after a level-0 half sweep of colour c the overlap
       // rows of that colour take their owners' x.  Per colour: the plan's rows in host memory (own local rows sent by destination;
-      // overlap rows as rows of the hierarchy's matrix, in arrival order), the same as level-0 positions on the device (rebuilt
-      // with the hierarchy: perm0 changes), the per-rank counts; one send and one receive buffer for the larger colour, and
-      // their K-wide twins (batch_prepare_exchange)
+      // overlap rows of the hierarchy's matrix in arrival order); x_smooth[c] has them as level-0 positions (rebuilt with perm0)
       bool smooth = false;
       MlSmoothHook smooth_hook = { nullptr, nullptr };
       std::vector<int32_t> h_smooth_send[2], h_smooth_recv[2];
-      int *smooth_send_idx[2] = { nullptr, nullptr }, *smooth_recv_idx[2] = { nullptr, nullptr };
-      std::vector<int> smooth_send_counts[2], smooth_recv_counts[2], smooth_send_counts_k[2], smooth_recv_counts_k[2];
-      int64_t smooth_nsend_max = 0, smooth_nrecv_max = 0;
-      double *smooth_sendbuf = nullptr, *smooth_recvbuf = nullptr, *bsmooth_send = nullptr, *bsmooth_recv = nullptr;
       // K right-hand sides in lockstep: the K-interleaved operator input [own rows | halo rows] x K, the
-      // K-wide send rows, the plan's counts times K, and the group's Gram-Schmidt messages
+      // K-wide buffers of the exchanges, and the group's Gram-Schmidt messages
       // gmsg = dots [K x (m + 2)] | second pass [K x (m + 2)] | norms [K] | 1 / norms [K], ghpin its pinned host mirror
-      double *bxe = nullptr, *bsend = nullptr, *gmsg = nullptr, *ghpin = nullptr;
+      double *bxe = nullptr, *gmsg = nullptr, *ghpin = nullptr;
       int bK = 0;                     // width these buffers exist for
       int agreed_K = 0;               // widest interleave every rank is known to have buffers for
-      std::vector<int> send_counts_k, recv_counts_k;
       // nkp_transpose_dist: what nkp_create_dist was given and planned, in host memory -- the first rows of all ranks, the global
-      // rows of the halo, the own rows the peers hold as halo (send_idx), the caller's OWN block offsets and grid positions
+      // rows of the halo, the own rows the peers hold as halo (x_halo.send_idx), the caller's OWN block offsets and grid positions
       // (with overlap h_blk / h_col_* hold the extended [own | overlap] arrays)
       std::vector<int64_t> starts;
       std::vector<int32_t> h_halo_rows, h_send_rows, own_blk, own_ci, own_cj, own_ct;
@@ -244,12 +236,17 @@ inline int reserve (nkp_solver *s, std::initializer_list<Want> set, const char *
 inline int width_of (int nrhs) { return nrhs <= 1 ? 1 : nrhs <= 2 ? 2 : nrhs <= 4 ? 4 : 8; }
 
 // the two device collectives of a solve; a failure leaves stale data behind and is checked before any verdict is returned
-// (inline: they run on every Krylov step)
-inline void alltoallv_dev (nkp_solver *s, const double *send, const int *send_counts, double *recv, const int *recv_counts, hipStream_t st)
+// (inline: they run on every Krylov step).  sticky = false: the caller reports the failure itself (fetch_x_operand)
+inline int alltoallv_dev (nkp_solver *s, const double *send, const int *send_counts, double *recv, const int *recv_counts, hipStream_t st, bool sticky = true)
 {
    s->shared->alltoallv_calls++;
-   if (s->dist.ops.alltoallv (s->dist.ops.ctx, send, send_counts, recv, recv_counts, (void *) st)) s->comm_failed = true;
+   const int rc = s->dist.ops.alltoallv (s->dist.ops.ctx, send, send_counts, recv, recv_counts, (void *) st);
+   if (rc && sticky) s->comm_failed = true;
+   return rc;
 }
+// ONE alltoallv, always made and counted: the rows of exchange X, K wide in `packed`, arrive at `dest` on their receivers
+inline int exchange_rows (nkp_solver *s, RowExchange &X, int K, const double *packed, double *dest, hipStream_t st, bool sticky = true)
+{ return alltoallv_dev (s, packed, X.send_counts_for (K), dest, X.recv_counts_for (K), st, sticky); }
 
 inline void allreduce_dev (nkp_solver *s, double *dev, int count, int op)
 {
@@ -345,21 +342,51 @@ NKP_PRIVATE int backward_error (nkp_solver *s, double *berr);
 // falls back leaves at -D1
 NKP_PRIVATE const char *batch_unsupported (const nkp_solver *s);
 NKP_PRIVATE void note_fallback (const nkp_solver *s, const char *who, const char *why, int nrhs);
-// the K-wide exchange buffers of a row-distributed solver (bxe, bsend, gmsg, with several rings bras_send / bras_recv), all or
-// nothing: the part of the batched solve's preparation that nkp_value_gradient shares
+// the K-wide buffers of a row-distributed solver (bxe, gmsg and those of its exchanges), all or nothing: the part of the
+// batched solve's preparation that nkp_value_gradient shares
 NKP_PRIVATE int batch_prepare_exchange (nkp_solver *s, int K);
-// Row-distributed solvers: every rank learns whether any rank's step failed, and all leave together.  A rank whose own step
-// failed returns its code and message, every other rank NKP_ECOMM naming it; a failed allgather is NKP_ECOMM everywhere.
+// Row-distributed solvers: one number from every rank.  A rank whose own step failed (local_rc) contributes -1, keeps its message
+// and gets its code back; a failed allgather is NKP_ECOMM everywhere.  failed_rank: the first rank that contributed -1, or -1.
+// dist_agree: every rank learns whether any rank's step failed, and all leave together, the other ranks with NKP_ECOMM naming it
+NKP_PRIVATE int dist_allgather (nkp_solver *s, int local_rc, int64_t mine, std::vector<int64_t> &all, const char *who, const char *where);
+inline int failed_rank (const std::vector<int64_t> &all) { for (size_t p = 0; p < all.size (); p++) if (all[p] < 0) return (int) p; return -1; }
 NKP_PRIVATE int dist_agree (nkp_solver *s, int local_rc, const char *who, const char *where);
+// ---- defined in row_exchange.hip -------------------------------------------------------------------------------------------
+// exchange_install: counts and device memory of an exchange -- send_idx (`rows` uploaded unless NULL), recv_idx where it unpacks,
+// send / recv for cap_send / cap_recv rows, K wide later bsend for as many and brecv for wide_recv rows (-1: no such buffer).
+// push_wide: the K-wide buffers of an exchange in force into a buffer_set
+NKP_PRIVATE bool exchange_install (nkp_solver *s, RowExchange &X, const int32_t *rows, const std::vector<int> &give, const std::vector<int> &need,
+                                   bool unpacks, int64_t cap_send, int64_t cap_recv, int64_t wide_recv);
+NKP_PRIVATE void exchange_release (RowExchange &X);
+inline void push_wide (RowExchange &X, bool in_force, std::vector<std::pair<double **, size_t>> &set)
+{
+   if (in_force && X.wide_send >= 0) set.push_back ({ &X.bsend, (size_t) X.wide_send });
+   if (in_force && X.wide_recv >= 0) set.push_back ({ &X.brecv, (size_t) X.wide_recv });
+}
+inline double *halo_rows_of (nkp_solver *s, int K) { return K == 1 ? s->dist.xe + s->n : s->dist.bxe + s->n * K; }
+// The input of a product with A in xe (K = 1) / bxe: own rows into place, the rows the peers need packed, the halo exchanged behind
+// them on `comm` (dist.comm_stream: after the packing, ev_halo marks its end).  x: one vector, or the own rows of bxe; xp: K vectors
+NKP_PRIVATE int halo_fetch (nkp_solver *s, int K, const double *x, const double *const *xp, hipStream_t comm, bool sticky = true);
+// The product with the exchange under way (dist.overlap): the interior row blocks (no off-rank column) are multiplied while the
+// halo travels on its own stream, the boundary rows once it has landed -- every row is still summed in stored order, so the
+// result is the bit pattern of the serial version.  rows (rb0, rb1) multiplies row blocks [rb0, rb1)
+template <class Rows> inline void halo_product_overlapped (nkp_solver *s, int K, const double *x, Rows rows)
+{
+   auto &D = s->dist;
+   halo_fetch (s, K, x, nullptr, D.comm_stream);
+   rows (D.seg_rb[1], D.seg_rb[2]);
+   (void) hipStreamWaitEvent (s->stream, D.ev_halo, 0);
+   rows (D.seg_rb[0], D.seg_rb[1]);
+   rows (D.seg_rb[2], D.seg_rb[3]);
+}
 // ---- defined in smooth_exchange.hip ----------------------------------------------------------------------------------------
 // the fine-level exchange of a row-distributed solver (tuning dist_smooth_exchange).  smooth_install: the plan's lists, counts
-// and one-vector buffers into s->dist (nkp_create_dist; false = out of device memory).  smooth_build_lists: the device index
+// and one-vector buffers into s->dist.x_smooth (nkp_create_dist; false = out of device memory).  smooth_build_lists: the device index
 // lists in level-0 positions from the hierarchy s->ml holds now -- after ml_setup and after every rebuild (0, -2 no memory, -3 HIP
 // failure or a hierarchy that is not the plan's).  smooth_hook_of: what the cycle applications of s take (NULL when not in force)
 NKP_PRIVATE bool smooth_install (nkp_solver *s, const DistPlan &D);
 NKP_PRIVATE int smooth_build_lists (nkp_solver *s);
 NKP_PRIVATE const MlSmoothHook *smooth_hook_of (nkp_solver *s);
-NKP_PRIVATE void smooth_release (nkp_solver *s);
 // one thread per row: out[i] = x[idx[i]] / x[idx[i]] = in[i], K interleaved vectors (K = 1, 2, 4, 8)
 NKP_PRIVATE void launch_smooth_pack (int K, const int *idx, const double *x, double *out, int64_t nrows, hipStream_t st);
 NKP_PRIVATE void launch_smooth_unpack (int K, const int *idx, const double *in, double *x, int64_t nrows, hipStream_t st);
@@ -370,8 +397,8 @@ NKP_PRIVATE int valgrad_time_prepare (nkp_solver *s, int K);
 NKP_PRIVATE void valgrad_time_launch (nkp_solver *s, int K);
 // The operand x of a K-wide kernel on the pattern (xp = the vectors, own rows; pointers beyond them NULL): single-GPU the vectors
 // themselves (K = 1) or their K-interleaved copy in `il` (n * K doubles); row-distributed [own | halo] rows in dist.xe (K = 1) or
-// dist.bxe (K >= 2, batch_prepare_exchange done), the halo rows of all vectors fetched in ONE alltoallv, which is always made and
-// counted.  *x_in = what the kernel reads.  NKP_ECOMM when the exchange failed (the stream is then still to be synchronised).
+// dist.bxe (K >= 2, batch_prepare_exchange done), the halo rows of all vectors fetched in ONE alltoallv (halo_fetch), which is
+// always made and counted.  *x_in = what the kernel reads.  NKP_ECOMM when the exchange failed (the stream is then still to be synchronised).
 NKP_PRIVATE int fetch_x_operand (nkp_solver *s, int K, const double *const *xp, double *il, const double **x_in, const char *who);
 // ---- defined in valprod_api.hip --------------------------------------------------------------------------------------------
 NKP_PRIVATE void valprod_release (nkp_solver *s);

@@ -149,7 +149,7 @@ int td_local_transpose (nkp_solver *s, TransDistBuild &B)
    B.ent_send.assign ((size_t) B.P, 0);
    int64_t h = 0;
    for (int p = 0; p < B.P; p++)
-      for (int k = 0; k < s->dist.recv_counts[(size_t) p]; k++, h++) B.ent_send[(size_t) p] += B.cnt_send[(size_t) h];
+      for (int k = 0; k < s->dist.x_halo.recv_counts[(size_t) p]; k++, h++) B.ent_send[(size_t) p] += B.cnt_send[(size_t) h];
    if (h != B.n_halo) return fail (NKP_EINVAL, "nkp_transpose_dist: the halo plan of this solver is inconsistent");
    return NKP_OK;
 }
@@ -165,7 +165,7 @@ int td_plan_placement (nkp_solver *s, TransDistBuild &B)
    int64_t k = 0, total = 0;
    for (int p = 0; p < B.P; p++) {
       int64_t t = 0;
-      for (int q = 0; q < s->dist.send_counts[(size_t) p]; q++, k++) {
+      for (int q = 0; q < s->dist.x_halo.send_counts[(size_t) p]; q++, k++) {
          const int32_t cnt = B.cnt_recv[(size_t) k], c = rows[(size_t) k];
          if (cnt < 0 || c < 0 || c >= B.m_loc) return fail (NKP_ECOMM, "nkp_transpose_dist: rank %d sent an entry count this rank cannot place", p);
          t += cnt;
@@ -192,7 +192,7 @@ int td_plan_placement (nkp_solver *s, TransDistBuild &B)
             B.own_dst[(size_t) c] = cursor[(size_t) c];
             cursor[(size_t) c] += B.h_rpT[(size_t) c + 1] - B.h_rpT[(size_t) c];
          }
-      for (int q = 0; q < s->dist.send_counts[(size_t) p]; q++, k++) {
+      for (int q = 0; q < s->dist.x_halo.send_counts[(size_t) p]; q++, k++) {
          const int32_t c = rows[(size_t) k];
          B.seg_dst[(size_t) k] = cursor[(size_t) c];
          cursor[(size_t) c] += B.cnt_recv[(size_t) k];
@@ -322,7 +322,7 @@ extern "C" int nkp_transpose_dist (nkp_solver *s, nkp_solver **out)
    B.m_loc = s->n;
    B.n_halo = s->dist.n_halo;
    B.nnz = s->A.nnz;
-   B.nseg = s->dist.nsend;
+   B.nseg = s->dist.x_halo.nsend;
 
    // ---- the local transpose
    int rc = td_local_transpose (s, B);
@@ -330,7 +330,7 @@ extern "C" int nkp_transpose_dist (nkp_solver *s, nkp_solver **out)
 
    // ---- entry counts of the rows the peers hold as halo, then the plan of the assembled block
    B.cnt_recv.assign ((size_t) B.nseg + 1, 0);
-   if (c.alltoallv_i32_host (c.ctx, B.cnt_send.data (), s->dist.recv_counts.data (), B.cnt_recv.data (), s->dist.send_counts.data ()))
+   if (c.alltoallv_i32_host (c.ctx, B.cnt_send.data (), s->dist.x_halo.recv_counts.data (), B.cnt_recv.data (), s->dist.x_halo.send_counts.data ()))
       rc = fail (NKP_ECOMM, "nkp_transpose_dist: the exchange of the entry counts failed");
    else rc = td_plan_placement (s, B);
    if (!rc && B.recv_val.alloc ((size_t) B.n_recv) != hipSuccess) {      // a rank without its receive buffer must not enter the exchange

@@ -91,33 +91,14 @@ int value_gradient (nkp_solver *s, int nrhs, const double *h_lam, const double *
 int fetch_x_operand (nkp_solver *s, int K, const double *const *xp, double *il, const double **x_in, const char *who)
 {
    auto &D = s->dist;
-   const int64_t n = s->n;
-   hipStream_t st = s->stream;
    if (!D.on) {
       *x_in = xp[0];
-      if (K >= 2) { launch_interleave (K, xp, il, n, st); *x_in = il; }
+      if (K >= 2) { launch_interleave (K, xp, il, s->n, s->stream); *x_in = il; }
       return NKP_OK;
    }
-   int comm_rc;
-   s->shared->alltoallv_calls++;
-   if (K == 1) {
-      // as spmv_op fetches them: own rows copied, the rows the peers need packed, the halo behind the own rows
-      launch_copy (xp[0], D.xe, n, st);
-      if (D.nsend) launch_gather (D.send_idx, xp[0], D.sendbuf, D.nsend, st);
-      comm_rc = D.ops.alltoallv (D.ops.ctx, D.sendbuf, D.send_counts.data (), D.xe + n, D.recv_counts.data (), (void *) st);
-      *x_in = D.xe;
-   } else {
-      // K-wide rows, the plan's counts times K (the buffers and counts of the batched solve)
-      D.send_counts_k.resize (D.send_counts.size ());
-      D.recv_counts_k.resize (D.recv_counts.size ());
-      for (size_t p = 0; p < D.send_counts.size (); p++) D.send_counts_k[p] = D.send_counts[p] * K;
-      for (size_t p = 0; p < D.recv_counts.size (); p++) D.recv_counts_k[p] = D.recv_counts[p] * K;
-      launch_interleave (K, xp, D.bxe, n, st);
-      if (D.nsend) launch_pack_rows_split (K, D.send_idx, xp, D.bsend, D.nsend, st);
-      comm_rc = D.ops.alltoallv (D.ops.ctx, D.bsend, D.send_counts_k.data (), D.bxe + (size_t) n * (size_t) K, D.recv_counts_k.data (), (void *) st);
-      *x_in = D.bxe;
-   }
-   if (comm_rc) return fail (NKP_ECOMM, "%s: the exchange of the halo rows of x failed", who);
+   // as spmv_op fetches them; a failure is this call's alone (not sticky): the solver's later solves exchange anew
+   *x_in = K == 1 ? D.xe : D.bxe;
+   if (halo_fetch (s, K, nullptr, xp, s->stream, false)) return fail (NKP_ECOMM, "%s: the exchange of the halo rows of x failed", who);
    return NKP_OK;
 }
 

@@ -96,15 +96,11 @@ int values_product (nkp_solver *s, int nrhs, const double *h_val, const double *
 // (a rank without it would not join the exchange of the product, and the others would wait for it)
 int tangent_agree (nkp_solver *s, int local_rc, bool has_dval, const char *who)
 {
-   const nkp_comm_ops &c = s->dist.ops;
-   std::vector<int64_t> all ((size_t) c.nranks + 1, 0);
-   const std::string mine = local_rc ? last_error_message () : std::string ();
-   const bool comm_ok = c.allgather_i64_host (c.ctx, local_rc ? -1 : has_dval ? 2 : 1, all.data ()) == 0;
-   if (local_rc) { restore_error_message (mine); return local_rc; }
-   if (!comm_ok) return fail (NKP_ECOMM, "%s: allgather failed (arguments and work space)", who);
-   for (int p = 0; p < c.nranks; p++)
-      if (all[(size_t) p] < 0) return fail (NKP_ECOMM, "%s: rank %d failed (arguments and work space); see its message", who, p);
-   for (int p = 1; p < c.nranks; p++)
+   std::vector<int64_t> all;
+   if (const int rc = dist_allgather (s, local_rc, has_dval ? 2 : 1, all, who, "arguments and work space")) return rc;
+   const int bad = failed_rank (all);
+   if (bad >= 0) return fail (NKP_ECOMM, "%s: rank %d failed (arguments and work space); see its message", who, bad);
+   for (int p = 1; p < s->dist.ops.nranks; p++)
       if (all[(size_t) p] != all[0])
          return fail (NKP_EINVAL, "%s: rank %d passes d_dval %s and rank 0 %s: every rank must pass it or every rank NULL", who, p,
                       all[(size_t) p] == 2 ? "non-NULL" : "NULL", all[0] == 2 ? "non-NULL" : "NULL");

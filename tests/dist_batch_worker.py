@@ -115,7 +115,7 @@ def main():
 
     def guards(s):
         return dict(equil=s.get_int("equil"), precond_steps=s.get_int("precond_steps"), ras=s.get_int("dist_ras"), ras_rows=s.get_int("dist_ras_rows"),
-                    overlap=s.get_int("dist_overlap"))
+                    overlap=s.get_int("dist_overlap"), rings=s.get_int("dist_ras_rings"), smooth=s.get_int("dist_smooth_exchange"))
 
     res = dict(rank=rank, m_loc=m)
     cases = a.cases.split(",")
@@ -123,12 +123,20 @@ def main():
     s = make()
     res["guards"] = guards(s)
     single = {}
-    if any(c in cases for c in ("bits", "counts", "accuracy", "refactor")):
+    if any(c in cases for c in ("bits", "counts", "accuracy", "refactor", "narrow")):
         for c, one in enumerate(singles(s, range(a.nvec))):
             single[c] = one
         res["single"] = [dict(one["info"], delta=one["delta"]) for one in single.values()]
     if "bits" in cases:
         res["bits"] = {str(k): batched(s, list(range(k)), single)[0] for k in nrhs_list}
+    if "narrow" in cases:
+        # ONE solver through groups of 8, 2 and 4 right-hand sides, then a solve alone: the interleave narrows on live exchanges
+        groups = {str(k): batched(s, list(range(k)), single)[0] for k in (8, 2, 4)}
+        again = singles(s, (1,))[0]
+        # the host plan of the same create: the rows this rank sends and receives per colour of the fine-level exchange
+        pl = nd.overlap_plan_host(loc, n, comm, cnt, tuning=dict(opts["tuning"]))
+        rows = {k: int(pl[k].size) for k in ("smooth_send_rows0", "smooth_send_rows1", "smooth_recv_rows0", "smooth_recv_rows1")}
+        res["narrow"] = dict(groups=groups, smooth_rows=rows, again=dict(x_equal=bool(np.array_equal(again["x"], single[1]["x"])), iters=again["info"]["iters"], delta=again["delta"]))
     if "counts" in cases:
         res["counts"] = batched(s, [0, 1, 2, 3], single)[0]
     if "accuracy" in cases:

@@ -127,6 +127,39 @@ def test_bits_eight_per_sweep(tmp_path):
     assert all(r["bits"]["9"]["batch_width"] == 8 for r in res)
 
 
+def test_width_narrows_on_a_live_solver(tmp_path):
+    """Groups of 8, 2 and 4 right-hand sides and then a solve alone on ONE solver, two rings of overlap and the fine-level exchange
+    in force: the SpMV halo, the overlap residual's own exchange and both colours of the fine-level exchange go from 8-wide rows
+    to 2-wide, 4-wide and single rows.  Every column has the bits of its single solve, and a lockstep step makes the exchanges of
+    one system at every width: the SpMV's, the overlap residual's and the 11 of a V(3, 3) cycle."""
+    tuning = {"rhs_batch": 8, "dist_ras_rings": 2, "dist_smooth_exchange": 1, "ml_coarsest_rows": 4000}      # (level 0 smooths on every rank)
+    res = launch(2, str(tmp_path / "r"), "narrow", extra=("--nvec", "8"), opts={"tuning": tuning})
+    assert_batched_path(res)
+    e, a = 1 + 1 + 11, 2
+    for r in res:
+        assert r["guards"]["ras"] == 1 and r["guards"]["rings"] == 2 and r["guards"]["smooth"] == 1 and r["guards"]["ras_rows"] > 0, r["guards"]
+        S = [s["delta"]["dist_alltoallv_calls"] for s in r["single"]]
+        R = [s["delta"]["dist_allreduce_calls"] for s in r["single"]]
+        I = [s["iters"] for s in r["single"]]
+        assert list(r["narrow"]["groups"]) == ["8", "2", "4"]
+        assert all(v > 0 for v in r["narrow"]["smooth_rows"].values()), (r["rank"], r["narrow"]["smooth_rows"])      # both colours carry rows, both ways
+        for k, got in ((int(key), val) for key, val in r["narrow"]["groups"].items()):
+            assert len(got["columns"]) == k and got["batch_width"] == k
+            for c, col in enumerate(got["columns"]):
+                assert col["x_equal"] and col["iters"] == I[c] and col["relres_equal"] and col["berr_equal"], (r["rank"], k, c, col)
+                assert I[c] > 0 and S[c] >= e * I[c] and R[c] >= a * I[c], (r["rank"], c, S[c], R[c], I[c])
+            Sb, Rb, Tb = got["delta"]["dist_alltoallv_calls"], got["delta"]["dist_allreduce_calls"], got["delta"]["batch_steps"]
+            print(f"rank {r['rank']} group of {k}: I={I[:k]} S={S[:k]} R={R[:k]}  batched: steps={Tb} alltoallv={Sb} allreduce={Rb}")
+            assert max(I[:k]) <= Tb < sum(I[:k]), (k, Tb, I)
+            assert e * Tb <= Sb <= sum(S[c] - e * I[c] for c in range(k)) + e * Tb, (k, Sb, S, I, Tb)
+            assert Rb <= sum(R[c] - a * I[c] for c in range(k)) + a * Tb, (k, Rb, R, I, Tb)
+        again = r["narrow"]["again"]
+        assert again["x_equal"] and again["iters"] == I[1], (r["rank"], again)
+        assert again["delta"]["dist_alltoallv_calls"] == S[1] and again["delta"]["dist_allreduce_calls"] == R[1] and again["delta"]["batch_steps"] == 0, (r["rank"], again, S[1], R[1])
+    for k in ("8", "2", "4"):                             # every rank took the same global decisions
+        assert len({tuple(col["iters"] for col in r["narrow"]["groups"][k]["columns"]) for r in res}) == 1
+
+
 def test_bits_two_tracers_cell_major(tmp_path):
     res = launch(2, str(tmp_path / "r"), "bits", extra=("--partition", "cells", "--nrhs", "3,4"))
     assert_bits(res, "bits", (3, 4))
