@@ -378,15 +378,11 @@ void prolong_add_batch_kernel (const int *__restrict__ cmap, const double *__res
 
 template <int K>
 __global__ __launch_bounds__ (BT_THREADS)
-void gather_batch_kernel (const int *__restrict__ perm, const double *__restrict__ in, double *__restrict__ out, int64_t n, int scatter)
+void gather_batch_kernel (const int *__restrict__ perm, const double *__restrict__ in, double *__restrict__ out, int64_t n)
 {
    const int64_t stride = (int64_t) gridDim.x * BT_THREADS;
-   for (int64_t t = (int64_t) blockIdx.x * BT_THREADS + threadIdx.x; t < n * K; t += stride) {
-      const int64_t i = t / K;
-      const int k = (int) (t % K);
-      if (scatter) out[(int64_t) perm[i] * K + k] = in[t];
-      else out[t] = in[(int64_t) perm[i] * K + k];
-   }
+   for (int64_t t = (int64_t) blockIdx.x * BT_THREADS + threadIdx.x; t < n * K; t += stride)
+      out[t] = in[(int64_t) perm[t / K] * K + (t % K)];
 }
 
 // the entry and the exit of a batched cycle application, fused with the (de-)interleave of the per-system vectors:
@@ -563,11 +559,7 @@ void launch_prolong_add_batch (int K, const int *cmap, const double *coarse, dou
 }
 void launch_gather_batch (int K, const int *perm, const double *in, double *out, int64_t n, hipStream_t st)
 {
-   if (n > 0) with_k (K, [&] (auto k) { hipLaunchKernelGGL (gather_batch_kernel<decltype (k)::value>, dim3 (bt_grid (n * K)), dim3 (BT_THREADS), 0, st, perm, in, out, n, 0); });
-}
-void launch_scatter_batch (int K, const int *perm, const double *in, double *out, int64_t n, hipStream_t st)
-{
-   if (n > 0) with_k (K, [&] (auto k) { hipLaunchKernelGGL (gather_batch_kernel<decltype (k)::value>, dim3 (bt_grid (n * K)), dim3 (BT_THREADS), 0, st, perm, in, out, n, 1); });
+   if (n > 0) with_k (K, [&] (auto k) { hipLaunchKernelGGL (gather_batch_kernel<decltype (k)::value>, dim3 (bt_grid (n * K)), dim3 (BT_THREADS), 0, st, perm, in, out, n); });
 }
 void launch_gather_interleave (int K, const int *perm, const double *const *src, double *out, int64_t n, hipStream_t st, const double *scale)
 {

@@ -489,20 +489,16 @@ int clone_impl (nkp_solver *src, nkp_solver **out, bool member)
    s->device_bytes = 0;
    s->V = s->vcur = s->Z = s->w = s->r = s->x = s->b = s->t1 = s->t2 = s->p1 = s->p2 = s->eqtmp = s->partial = s->dscal = s->hpin = nullptr;
    s->dint = nullptr;
-   for (MlLevel &L : s->ml.lev) L.x = L.x2 = L.b = L.r = nullptr;
+   for (MlLevel &L : s->ml.lev) L.one = MlVecs ();
    int rc = NKP_OK;
    TRYHIP (hipStreamCreateWithFlags (&s->stream, hipStreamNonBlocking));
    s->own_stream = true;
    TRY (alloc_work_vectors (s, member));
    for (MlLevel &L : s->ml.lev) {
-      TRY (dev_alloc (s, &L.x, (size_t) L.n));
-      TRY (dev_alloc (s, &L.x2, (size_t) L.n));
-      TRY (dev_alloc (s, &L.b, (size_t) L.n));
-      TRY (dev_alloc (s, &L.r, (size_t) L.n));
-      TRYHIP (hipMemset (L.x, 0, (size_t) (L.n ? L.n : 1) * sizeof (double)));
-      TRYHIP (hipMemset (L.x2, 0, (size_t) (L.n ? L.n : 1) * sizeof (double)));
-      TRYHIP (hipMemset (L.b, 0, (size_t) (L.n ? L.n : 1) * sizeof (double)));
-      TRYHIP (hipMemset (L.r, 0, (size_t) (L.n ? L.n : 1) * sizeof (double)));
+      for (double **p : { &L.one.x, &L.one.x2, &L.one.b, &L.one.r }) {
+         TRY (dev_alloc (s, p, (size_t) L.n));
+         TRYHIP (hipMemset (*p, 0, (size_t) (L.n ? L.n : 1) * sizeof (double)));
+      }
    }
    *out = s;
    return NKP_OK;

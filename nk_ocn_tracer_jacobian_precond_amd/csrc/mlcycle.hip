@@ -1,75 +1,16 @@
-// Multilevel water-column preconditioner: the V(nu, nu) cycle on the hierarchy ml_setup built (multilevel.hip), for one
-// right-hand side and for K interleaved ones, and the measurement helpers of bench.py and the probes.  Launchers only: the
-// kernels are colblock.hip, col_lanes.hip, col_packed.hip, col_gs_fused.hip, col_gs_lanes.hip, diagop.hip, spmv.hip, blas1.hip,
-// batch.hip, dense.hip and mltail.hip.  The owner of the hierarchy may hang a hook behind the half sweeps of level 0
-// (MlSmoothHook in multilevel.h); without one -- every single-GPU cycle -- it is one pointer test per half sweep.
+// Multilevel water-column preconditioner: the V(nu, nu) cycle on the hierarchy ml_setup built (multilevel.hip), written once
+// for one right-hand side (K = 1) and for K interleaved ones, and the measurement helpers of bench.py and the probes.  The
+// skeleton (ml_cycle) knows levels, colours and sweeps; the helpers before it say which kernel serves each operation at which
+// width, on the level's vectors of that width (MlLevel::vec).  Launchers only: the kernels are colblock.hip, col_lanes.hip,
+// col_packed.hip, col_gs_fused.hip, col_gs_lanes.hip, diagop.hip, spmv.hip, blas1.hip, batch.hip, dense.hip and mltail.hip.
+// The owner of the hierarchy may hang a hook behind the half sweeps of level 0 (MlSmoothHook in multilevel.h); without one --
+// every single-GPU cycle -- it is one pointer test per half sweep.
 #include "nkp_dev.h"
 #include "multilevel.h"
 
-// ================================================================ cycle
-// one Gauss-Seidel half sweep over colour c.  Fused path (gs_wave_diag_kernel, gs_lanes_diag_kernel, gs_wave_kernel or
-// gs_fused_kernel): one launch, x ping-pongs between the level's two buffers (the new values of colour c go where the other
-// colour's current values are if the level is incoherent, else to the other buffer).  Two-kernel path: residual SpMV of the colour's rows, then the column solves accumulate into x in place.
-// column solves of colour c: levels with few columns run one column per WAVE (colblock_apply_kernel: one round trip for the
-// column's right-hand side and factors, the substitution by lane broadcasts) -- with thousands of idle wave slots its
-// ~5 us beat the 12-16 us latency floor of the lane-per-column kernels, which only win when the chip is full
-static void column_solves (const MlHierarchy &H, MlLevel &V, int c, const double *rhs, double *x, int accumulate, hipStream_t st)
-{
-   if (V.wave_columns) {
-      if (H.f32) launch_colblock_apply_range_r32 (V.B, V.color_blk[c], V.color_blk[c + 1], rhs, x, accumulate, st);
-      else launch_colblock_apply_range (V.B, V.color_blk[c], V.color_blk[c + 1], rhs, x, accumulate, st);
-   } else
-      launch_colblock_apply_lanes (V.B, V.color_grp[c], V.color_grp[c + 1], rhs, x, accumulate, st);
-}
-
-// The per-level hook behind a half sweep (MlSmoothHook): x holds the new values of colour c.  Level 0 only, and only while the
-// running cycle has level-0 half sweeps to come; nothing without a hook (every single-GPU cycle).
-static inline void after_half_sweep (MlHierarchy &H, const MlLevel &V, int c, double *x, int K, hipStream_t st)
-{
-   if (!H.hook || &V != &H.lev[0] || H.hook_left <= 0) return;
-   if (--H.hook_left > 0) H.hook->refresh (H.hook->ctx, c, x, K, st);
-}
-
-static void gs_half (MlHierarchy &H, MlLevel &V, int c, bool fused, hipStream_t st)
-{
-   if (fused) {
-      const int out = (V.cur[0] != V.cur[1]) ? V.cur[1 - c] : 1 - V.cur[c];
-      const int rows0 = (int) V.rows0;
-      // (the launchers cannot refuse: ml_setup clears gs_ok / wave_fused for a level whose storage they do not serve)
-      if (V.wave_diag) launch_gs_wave_diag (V.L, V.B, V.color_tile[c], V.color_tile[c + 1], V.xbuf (V.cur[0]), V.xbuf (V.cur[1]), rows0, V.b, V.xbuf (out), H.f32, st);
-      else if (V.lane_diag) launch_gs_lanes_diag (V.L, V.B, V.color_grp[c], V.color_grp[c + 1], V.xbuf (V.cur[0]), V.xbuf (V.cur[1]), rows0, V.b, V.xbuf (out), st);
-      else if (V.wave_fused) launch_gs_wave (V.L, V.B, V.color_blk[c], V.color_blk[c + 1], V.xbuf (V.cur[0]), V.xbuf (V.cur[1]), rows0, V.b, V.xbuf (out), H.f32, st);
-      else (void) launch_gs_fused (V.L, V.B, V.color_grp[c], V.color_grp[c + 1], V.xbuf (V.cur[0]), V.xbuf (V.cur[1]), rows0, V.b, V.xbuf (out), st);
-      V.cur[c] = out;
-      after_half_sweep (H, V, c, V.xbuf (out), 1, st);      // the buffer the next half sweep reads colour c from
-      return;
-   }
-   if (V.L.dg_val) launch_diag_residual (V.L, V.color_tile[c], V.color_tile[c + 1], V.x, V.b, V.r, st);
-   else launch_csr_residual_range (V.L, V.color_rb[c], V.color_rb[c + 1], V.x, V.b, V.r, st);
-   column_solves (H, V, c, V.r, V.x, 1, st);
-   after_half_sweep (H, V, c, V.x, 1, st);
-}
-
-static void gs_sweep (MlHierarchy &H, MlLevel &V, bool reverse, bool fused, hipStream_t st)
-{
-   for (int step = 0; step < 2; step++) gs_half (H, V, reverse ? 1 - step : step, fused, st);
-}
-
-// the first half sweep of a smoothed level from x = 0: the column solves of colour 0 straight from b (r = b there)
-static void first_half_sweep (MlHierarchy &H, MlLevel &V, bool fused, hipStream_t st)
-{
-   if (fused) {
-      // colour 0's first values go to the second buffer: the level starts incoherent, and the odd number of fused half
-      // sweeps that follows (colour 1, then nu - 1 full sweeps) ends coherent
-      if (V.wave_fused) column_solves (H, V, 0, V.b, V.x2, 0, st);
-      else launch_colblock_apply_lanes (V.B, V.color_grp[0], V.color_grp[1], V.b, V.x2, 0, st);
-      V.cur[0] = 1;
-      after_half_sweep (H, V, 0, V.x2, 1, st);
-   } else {
-      column_solves (H, V, 0, V.b, V.x, 0, st);
-      after_half_sweep (H, V, 0, V.x, 1, st);
-   }
-}
+// started: what of level l's cycle is already done -- ML_FILLED: x = 0 (with b); ML_SOLVED: the first half sweep too (level 0,
+// smoothed, no hook: ml_enter).  K = 1 only: a cycle on K >= 2 always starts fresh
+enum { ML_FRESH = 0, ML_FILLED = 1, ML_SOLVED = 2 };
 
 // level l starts its cycle with a fill of x that whoever wrote its b may do in the same pass (tuning step_glue bit 4): every level
 // but a dense last one and the head of a single-launch tail
@@ -79,62 +20,196 @@ static inline bool ml_level_fills_x (const MlHierarchy &H, int l)
    return !(l == (int) H.lev.size () - 1 && H.coarse_inv);
 }
 
-// started: what of level l's cycle is already done -- ML_FILLED: x = 0 (with b); ML_SOLVED: the first half sweep too (level 0,
-// smoothed, no hook: ml_enter)
-enum { ML_FRESH = 0, ML_FILLED = 1, ML_SOLVED = 2 };
+// ================================================================ which kernel serves (operation, level, K)
+// Every operation of the cycle once, both widths in its body.  K = 1 picks among the kernel families ml_setup planned for the
+// level; K >= 2 has one kernel per operation, which gives every column the bits any of those families gives it alone.
 
-static void ml_cycle (MlHierarchy &H, int l, hipStream_t st, int started = ML_FRESH)
+// the level's half sweeps are one launch each at this width, ping-pong between the two x buffers; else residual rows of the
+// colour, then its column solves accumulate into x in place
+static bool half_sweep_is_one_launch (const MlHierarchy &H, const MlLevel &V, int K) { return K == 1 ? ml_level_fused (H, V) : V.wave_fused != 0; }
+
+// column solves of colour c.  K = 1: levels with few columns run one column per WAVE (colblock_apply_kernel: one round trip for
+// the column's right-hand side and factors, the substitution by lane broadcasts) -- with thousands of idle wave slots its
+// ~5 us beat the 12-16 us latency floor of the lane-per-column kernels, which only win when the chip is full.  K >= 2: the
+// packed lane layout has kernels of its own; every other level takes the wave-per-column kernel (which reads the f64 factors
+// and rounds them like the f32 layouts store them: same values).  V.B.kern says which (col_plan.cpp)
+static void column_solves (const MlHierarchy &H, MlLevel &V, int K, int c, const double *rhs, double *x, int accumulate, hipStream_t st)
 {
-   MlLevel &V = H.lev[l];
-   if (started != ML_SOLVED) V.cur[0] = V.cur[1] = 0;
-   if (l == 0) H.hook_left = 0;
-   if (l == H.tail_from && H.coarse_inv && H.gamma_to <= H.gamma_from && ml_tail_launch (H, l, st) == 0) return;
-   if (l == (int) H.lev.size () - 1) {
-      if (H.coarse_inv) {
-         if (H.coarse_invf) launch_dense_matvec_f32 (H.coarse_invf, H.coarse_ldf, V.b, V.x, (int) V.n, st);
-         else launch_dense_matvec (H.coarse_inv, V.b, V.x, (int) V.n, st);
-         return;
-      }
-      // no dense inverse: many sweeps of the column smoother from x = 0 (what is left here is diagonally dominant)
-      const int sweeps = H.tune->ml_coarsest_sweeps > 0 ? H.tune->ml_coarsest_sweeps : 30;
-      if (started == ML_FRESH) launch_fill (V.x, 0.0, V.n, st);
-      column_solves (H, V, 0, V.b, V.x, 0, st);
-      gs_half (H, V, 1, false, st);
-      for (int s = 1; s < sweeps; s++) gs_sweep (H, V, s & 1, false, st);
-      return;
-   }
-   const bool fused = ml_level_fused (H, V);
-   const int nu = (l >= H.coarse_from) ? H.nu_coarse : H.nu;
-   if (l == 0 && H.hook) H.hook_left = 4 * nu;      // 2 nu half sweeps before and 2 nu after the coarse correction
-   // pre-smoothing from x = 0: the first half-sweep needs no SpMV (r = b on colour 0)
-   if (started == ML_FRESH) launch_fill (V.x, 0.0, V.n, st);
-   if (started != ML_SOLVED) first_half_sweep (H, V, fused, st);
-   gs_half (H, V, 1, fused, st);
-   for (int s = 1; s < nu; s++) gs_sweep (H, V, false, fused, st);
-   // coarse-grid correction; levels in [gamma_from, gamma_to) repeat it on the updated residual, which by the
-   // Galerkin property is the second coarse iteration of a W-cycle (NKP_ML_GAMMA_FROM / NKP_ML_GAMMA_TO, default off)
-   MlLevel &C = H.lev[l + 1];
-   const int gamma = (l >= H.gamma_from && l < H.gamma_to) ? 2 : 1;
-   for (int g = 0; g < gamma; g++) {
-      if (V.L.dg_val) launch_diag_residual (V.L, V.color_tile[0], V.color_tile[2], V.xnow (), V.b, V.r, st);
-      else launch_csr_spmv (V.L, V.xnow (), V.r, V.b, 1, st);
-      // tuning step_glue bit 4: the restriction zeroes the coarse x where the coarse cycle would start with that fill
-      const bool fill = (H.tune->step_glue & 4) && ml_level_fills_x (H, l + 1);
-      launch_restrict_sum (V.rptr, V.ridx, V.r, C.b, V.nc, st, fill ? C.x : nullptr);
-      ml_cycle (H, l + 1, st, fill ? ML_FILLED : ML_FRESH);
-      launch_prolong_add (V.cmap, C.xnow (), V.xnow (), V.n, H.omega, st);
-   }
-   for (int s = 0; s < nu; s++) gs_sweep (H, V, true, fused, st);
+   if (K != 1) {
+      if (launch_colblock_apply_lanes_batch (K, V.B, V.color_grp[c], V.color_grp[c + 1], rhs, x, accumulate, st) != 0)
+         launch_colblock_apply_wave_batch (K, V.B, V.color_blk[c], V.color_blk[c + 1], rhs, x, accumulate, H.f32, st);
+   } else if (V.wave_columns) {
+      if (H.f32) launch_colblock_apply_range_r32 (V.B, V.color_blk[c], V.color_blk[c + 1], rhs, x, accumulate, st);
+      else launch_colblock_apply_range (V.B, V.color_blk[c], V.color_blk[c + 1], rhs, x, accumulate, st);
+   } else
+      launch_colblock_apply_lanes (V.B, V.color_grp[c], V.color_grp[c + 1], rhs, x, accumulate, st);
 }
 
+// r = b - L x on the rows of colour c (K >= 2 reads CSR even where K = 1 reads the per-column diagonals)
+static void colour_residual (MlLevel &V, int K, int c, hipStream_t st)
+{
+   MlVecs &W = V.vec (K);
+   if (K != 1) launch_csr_spmv_batch (K, V.L, V.color_rb[c], V.color_rb[c + 1], W.x, W.r, W.b, 1, st);
+   else if (V.L.dg_val) launch_diag_residual (V.L, V.color_tile[c], V.color_tile[c + 1], W.x, W.b, W.r, st);
+   else launch_csr_residual_range (V.L, V.color_rb[c], V.color_rb[c + 1], W.x, W.b, W.r, st);
+}
+
+// the half sweep of colour c in one launch: reads each colour from the buffer that holds it, writes colour c to buffer `out`
+// (the launchers cannot refuse: ml_setup clears gs_ok / wave_fused for a level whose storage they do not serve)
+static void one_launch_half_sweep (const MlHierarchy &H, MlLevel &V, int K, int c, int out, hipStream_t st)
+{
+   MlVecs &W = V.vec (K);
+   const double *x0 = W.buf (W.cur[0]), *x1 = W.buf (W.cur[1]);
+   const int rows0 = (int) V.rows0;
+   if (K != 1) launch_gs_wave_batch (K, V.L, V.B, V.color_blk[c], V.color_blk[c + 1], x0, x1, rows0, W.b, W.buf (out), H.f32, st);
+   else if (V.wave_diag) launch_gs_wave_diag (V.L, V.B, V.color_tile[c], V.color_tile[c + 1], x0, x1, rows0, W.b, W.buf (out), H.f32, st);
+   else if (V.lane_diag) launch_gs_lanes_diag (V.L, V.B, V.color_grp[c], V.color_grp[c + 1], x0, x1, rows0, W.b, W.buf (out), st);
+   else if (V.wave_fused) launch_gs_wave (V.L, V.B, V.color_blk[c], V.color_blk[c + 1], x0, x1, rows0, W.b, W.buf (out), H.f32, st);
+   else (void) launch_gs_fused (V.L, V.B, V.color_grp[c], V.color_grp[c + 1], x0, x1, rows0, W.b, W.buf (out), st);
+}
+
+// r = b - L x on every row, before the restriction
+static void full_residual (MlLevel &V, int K, hipStream_t st)
+{
+   MlVecs &W = V.vec (K);
+   if (K != 1) launch_csr_spmv_batch (K, V.L, 0, V.L.nrowblk, W.now (), W.r, W.b, 1, st);
+   else if (V.L.dg_val) launch_diag_residual (V.L, V.color_tile[0], V.color_tile[2], W.now (), W.b, W.r, st);
+   else launch_csr_spmv (V.L, W.now (), W.r, W.b, 1, st);
+}
+
+// the coarse right-hand side from level l's residual; returns what of level l + 1's cycle that has done already.  K = 1, tuning
+// step_glue bit 4: the restriction zeroes the coarse x where the coarse cycle would start with that fill
+static int restrict_residual (MlHierarchy &H, int l, int K, hipStream_t st)
+{
+   MlLevel &V = H.lev[l];
+   MlVecs &W = V.vec (K), &WC = H.lev[l + 1].vec (K);
+   if (K != 1) {
+      launch_restrict_sum_batch (K, V.rptr, V.ridx, W.r, WC.b, V.nc, st);
+      return ML_FRESH;
+   }
+   const bool fill = (H.tune->step_glue & 4) && ml_level_fills_x (H, l + 1);
+   launch_restrict_sum (V.rptr, V.ridx, W.r, WC.b, V.nc, st, fill ? WC.x : nullptr);
+   return fill ? ML_FILLED : ML_FRESH;
+}
+
+// x += omega P x_coarse
+static void prolong_correction (MlHierarchy &H, int l, int K, hipStream_t st)
+{
+   MlLevel &V = H.lev[l];
+   MlVecs &W = V.vec (K), &WC = H.lev[l + 1].vec (K);
+   if (K != 1) launch_prolong_add_batch (K, V.cmap, WC.now (), W.now (), V.n, H.omega, st);
+   else launch_prolong_add (V.cmap, WC.now (), W.now (), V.n, H.omega, st);
+}
+
+static void fill_x (MlLevel &V, int K, hipStream_t st) { launch_fill (V.vec (K).x, 0.0, V.n * K, st); }
+
+// x = L^-1 b by the dense inverse of the last level
+static void dense_last_level (const MlHierarchy &H, MlLevel &V, int K, hipStream_t st)
+{
+   MlVecs &W = V.vec (K);
+   if (K != 1) {
+      if (H.coarse_invf) launch_dense_matvec_f32_batch (K, H.coarse_invf, H.coarse_ldf, W.b, W.x, (int) V.n, st);
+      else launch_dense_matvec_batch (K, H.coarse_inv, W.b, W.x, (int) V.n, st);
+   } else if (H.coarse_invf) launch_dense_matvec_f32 (H.coarse_invf, H.coarse_ldf, W.b, W.x, (int) V.n, st);
+   else launch_dense_matvec (H.coarse_inv, W.b, W.x, (int) V.n, st);
+}
+
+// ================================================================ the cycle
+// The per-level hook behind a half sweep (MlSmoothHook): x holds the new values of colour c.  Level 0 only, and only while the
+// running cycle has level-0 half sweeps to come; nothing without a hook (every single-GPU cycle).
+static inline void after_half_sweep (MlHierarchy &H, const MlLevel &V, int c, double *x, int K, hipStream_t st)
+{
+   if (!H.hook || &V != &H.lev[0] || H.hook_left <= 0) return;
+   if (--H.hook_left > 0) H.hook->refresh (H.hook->ctx, c, x, K, st);
+}
+
+// one Gauss-Seidel half sweep over colour c.  One launch: the new values of colour c go where the other colour's current values
+// are if the level is incoherent, else to the other buffer.  Two kernels: in place in x.
+static void gs_half (MlHierarchy &H, MlLevel &V, int K, int c, bool fused, hipStream_t st)
+{
+   MlVecs &W = V.vec (K);
+   if (fused) {
+      const int out = (W.cur[0] != W.cur[1]) ? W.cur[1 - c] : 1 - W.cur[c];
+      one_launch_half_sweep (H, V, K, c, out, st);
+      W.cur[c] = out;
+      after_half_sweep (H, V, c, W.buf (out), K, st);      // the buffer the next half sweep reads colour c from
+      return;
+   }
+   colour_residual (V, K, c, st);
+   column_solves (H, V, K, c, W.r, W.x, 1, st);
+   after_half_sweep (H, V, c, W.x, K, st);
+}
+
+// colour 0 then 1 before the coarse correction, 1 then 0 (reverse) after it
+static void gs_sweep (MlHierarchy &H, MlLevel &V, int K, bool reverse, bool fused, hipStream_t st)
+{
+   for (int step = 0; step < 2; step++) gs_half (H, V, K, reverse ? 1 - step : step, fused, st);
+}
+
+// the first half sweep of a smoothed level from x = 0: the column solves of colour 0 straight from b (r = b there)
+static void first_half_sweep (MlHierarchy &H, MlLevel &V, int K, bool fused, hipStream_t st)
+{
+   MlVecs &W = V.vec (K);
+   // one-launch half sweeps: colour 0's first values go to the second buffer -- the level starts incoherent, and the odd number
+   // of such half sweeps that follows (colour 1, then nu - 1 full sweeps) ends coherent
+   double *x = fused ? W.x2 : W.x;
+   // a level with one-launch half sweeps that is not wave_fused (K = 1 only) is a lane-per-column level
+   if (fused && !V.wave_fused) launch_colblock_apply_lanes (V.B, V.color_grp[0], V.color_grp[1], W.b, x, 0, st);
+   else column_solves (H, V, K, 0, W.b, x, 0, st);
+   if (fused) W.cur[0] = 1;
+   after_half_sweep (H, V, 0, x, K, st);
+}
+
+static void ml_cycle (MlHierarchy &H, int K, int l, hipStream_t st, int started = ML_FRESH)
+{
+   MlLevel &V = H.lev[l];
+   MlVecs &W = V.vec (K);
+   if (started != ML_SOLVED) W.cur[0] = W.cur[1] = 0;
+   if (l == 0) H.hook_left = 0;
+   // levels >= tail_from in one single-workgroup launch: K = 1 only
+   if (K == 1 && l == H.tail_from && H.coarse_inv && H.gamma_to <= H.gamma_from && ml_tail_launch (H, l, st) == 0) return;
+   const bool last = l == (int) H.lev.size () - 1;
+   if (last && H.coarse_inv) {
+      dense_last_level (H, V, K, st);
+      return;
+   }
+   // every other level smooths from x = 0: its first half sweep needs no SpMV (r = b on colour 0)
+   if (started == ML_FRESH) fill_x (V, K, st);
+   if (last) {
+      // no dense inverse: many sweeps of the column smoother (what is left here is diagonally dominant)
+      const int sweeps = H.tune->ml_coarsest_sweeps > 0 ? H.tune->ml_coarsest_sweeps : 30;
+      column_solves (H, V, K, 0, W.b, W.x, 0, st);
+      gs_half (H, V, K, 1, false, st);
+      for (int s = 1; s < sweeps; s++) gs_sweep (H, V, K, s & 1, false, st);
+      return;
+   }
+   const bool fused = half_sweep_is_one_launch (H, V, K);
+   const int nu = (l >= H.coarse_from) ? H.nu_coarse : H.nu;
+   if (l == 0 && H.hook) H.hook_left = 4 * nu;      // 2 nu half sweeps before and 2 nu after the coarse correction
+   if (started != ML_SOLVED) first_half_sweep (H, V, K, fused, st);
+   gs_half (H, V, K, 1, fused, st);
+   for (int s = 1; s < nu; s++) gs_sweep (H, V, K, false, fused, st);
+   // coarse-grid correction; levels in [gamma_from, gamma_to) repeat it on the updated residual, which by the
+   // Galerkin property is the second coarse iteration of a W-cycle (NKP_ML_GAMMA_FROM / NKP_ML_GAMMA_TO, default off)
+   const int gamma = (l >= H.gamma_from && l < H.gamma_to) ? 2 : 1;
+   for (int g = 0; g < gamma; g++) {
+      full_residual (V, K, st);
+      const int coarse_started = restrict_residual (H, l, K, st);
+      ml_cycle (H, K, l + 1, st, coarse_started);
+      prolong_correction (H, l, K, st);
+   }
+   for (int s = 0; s < nu; s++) gs_sweep (H, V, K, true, fused, st);
+}
+
+// ================================================================ entry points: gather, cycle, scatter
 void ml_apply (MlHierarchy &H, const double *r, double *z, hipStream_t st, const MlSmoothHook *hook)
 {
    MlLevel &V = H.lev[0];
-   launch_gather (H.perm0, r, V.b, V.n, st);
+   launch_gather (H.perm0, r, V.one.b, V.n, st);
    H.hook = hook;
-   ml_cycle (H, 0, st);
+   ml_cycle (H, 1, 0, st);
    H.hook = nullptr;
-   launch_scatter (H.perm0, V.xnow (), z, V.n, st);
+   launch_scatter (H.perm0, V.one.now (), z, V.n, st);
 }
 
 // The same cycle entered from the Krylov step (tuning step_glue bit 8): r = w * inv[0] is never stored on its own -- one kernel
@@ -144,12 +219,12 @@ void ml_apply (MlHierarchy &H, const double *r, double *z, hipStream_t st, const
 void ml_enter (MlHierarchy &H, const double *w, const double *inv, double *vnext, hipStream_t st)
 {
    MlLevel &V = H.lev[0];
-   launch_cycle_entry (H.perm0, w, inv, vnext, V.b, V.x, V.n, st);
+   launch_cycle_entry (H.perm0, w, inv, vnext, V.one.b, V.one.x, V.n, st);
    H.entered = ML_FILLED;
    if (H.lev.size () >= 2 && H.tail_from != 0) {
-      V.cur[0] = V.cur[1] = 0;
+      V.one.cur[0] = V.one.cur[1] = 0;
       H.hook_left = 0;
-      first_half_sweep (H, V, ml_level_fused (H, V), st);
+      first_half_sweep (H, V, 1, half_sweep_is_one_launch (H, V, 1), st);
       H.entered = ML_SOLVED;
    }
 }
@@ -159,11 +234,11 @@ void ml_finish (MlHierarchy &H, double *z, hipStream_t st)
    MlLevel &V = H.lev[0];
    const int started = H.entered;
    H.entered = ML_FRESH;
-   ml_cycle (H, 0, st, started);
-   launch_scatter (H.perm0, V.xnow (), z, V.n, st);
+   ml_cycle (H, 1, 0, st, started);
+   launch_scatter (H.perm0, V.one.now (), z, V.n, st);
 }
 
-// ================================================================ the cycle on K interleaved right-hand sides
+// the level vectors for K interleaved right-hand sides (MlLevel::wide); K = 2, 4 or 8
 int ml_batch_prepare (MlHierarchy &H, int K)
 {
    if (K != 2 && K != 4 && K != 8) return -1;
@@ -171,7 +246,7 @@ int ml_batch_prepare (MlHierarchy &H, int K)
    // all or nothing: the narrower vectors go first, and a failure leaves none behind (batch_K = 0 says so to the retry)
    auto drop = [&H] () {
       for (MlLevel &V : H.lev)
-         for (double **p : { &V.bx, &V.bx2, &V.bb, &V.br })
+         for (double **p : { &V.wide.x, &V.wide.x2, &V.wide.b, &V.wide.r })
             if (*p) {
                (void) hipFree (*p);
                *p = nullptr;
@@ -181,7 +256,7 @@ int ml_batch_prepare (MlHierarchy &H, int K)
    };
    drop ();
    for (MlLevel &V : H.lev) {
-      for (double **p : { &V.bx, &V.bx2, &V.bb, &V.br }) {
+      for (double **p : { &V.wide.x, &V.wide.x2, &V.wide.b, &V.wide.r }) {
          const size_t bytes = (size_t) (V.n ? V.n : 1) * (size_t) K * sizeof (double);
          void *q = nullptr;
          if (hipMalloc (&q, bytes) != hipSuccess || hipMemset (q, 0, bytes) != hipSuccess) {
@@ -200,96 +275,16 @@ int ml_batch_prepare (MlHierarchy &H, int K)
    return 0;
 }
 
-static void column_solves_batch (const MlHierarchy &H, MlLevel &V, int K, int c, const double *rhs, double *x, int accumulate, hipStream_t st)
-{
-   // the packed lane layout has kernels of its own; every other level takes the wave-per-column kernel (which reads the
-   // f64 factors and rounds them like the f32 layouts store them: same values).  V.B.kern says which (col_plan.cpp)
-   if (launch_colblock_apply_lanes_batch (K, V.B, V.color_grp[c], V.color_grp[c + 1], rhs, x, accumulate, st) != 0)
-      launch_colblock_apply_wave_batch (K, V.B, V.color_blk[c], V.color_blk[c + 1], rhs, x, accumulate, H.f32, st);
-}
-
-static void gs_half_batch (MlHierarchy &H, MlLevel &V, int K, int c, hipStream_t st)
-{
-   if (V.wave_fused) {
-      const int out = (V.bcur[0] != V.bcur[1]) ? V.bcur[1 - c] : 1 - V.bcur[c];
-      launch_gs_wave_batch (K, V.L, V.B, V.color_blk[c], V.color_blk[c + 1], V.bxbuf (V.bcur[0]), V.bxbuf (V.bcur[1]), (int) V.rows0, V.bb, V.bxbuf (out), H.f32, st);
-      V.bcur[c] = out;
-      after_half_sweep (H, V, c, V.bxbuf (out), K, st);
-      return;
-   }
-   launch_csr_spmv_batch (K, V.L, V.color_rb[c], V.color_rb[c + 1], V.bx, V.br, V.bb, 1, st);
-   column_solves_batch (H, V, K, c, V.br, V.bx, 1, st);
-   after_half_sweep (H, V, c, V.bx, K, st);
-}
-
-static void ml_cycle_batch (MlHierarchy &H, int K, int l, hipStream_t st)
-{
-   MlLevel &V = H.lev[l];
-   const int64_t nk = V.n * K;
-   V.bcur[0] = V.bcur[1] = 0;
-   if (l == 0) H.hook_left = 0;
-   if (l == (int) H.lev.size () - 1) {
-      if (H.coarse_inv) {
-         if (H.coarse_invf) launch_dense_matvec_f32_batch (K, H.coarse_invf, H.coarse_ldf, V.bb, V.bx, (int) V.n, st);
-         else launch_dense_matvec_batch (K, H.coarse_inv, V.bb, V.bx, (int) V.n, st);
-         return;
-      }
-      const int sweeps = H.tune->ml_coarsest_sweeps > 0 ? H.tune->ml_coarsest_sweeps : 30;
-      launch_fill (V.bx, 0.0, nk, st);
-      column_solves_batch (H, V, K, 0, V.bb, V.bx, 0, st);
-      launch_csr_spmv_batch (K, V.L, V.color_rb[1], V.color_rb[2], V.bx, V.br, V.bb, 1, st);
-      column_solves_batch (H, V, K, 1, V.br, V.bx, 1, st);
-      for (int s = 1; s < sweeps; s++)
-         for (int step = 0; step < 2; step++) {
-            const int c = (s & 1) ? 1 - step : step;
-            launch_csr_spmv_batch (K, V.L, V.color_rb[c], V.color_rb[c + 1], V.bx, V.br, V.bb, 1, st);
-            column_solves_batch (H, V, K, c, V.br, V.bx, 1, st);
-         }
-      return;
-   }
-   const int nu = (l >= H.coarse_from) ? H.nu_coarse : H.nu;
-   if (l == 0 && H.hook) H.hook_left = 4 * nu;
-   launch_fill (V.bx, 0.0, nk, st);
-   if (V.wave_fused) {
-      column_solves_batch (H, V, K, 0, V.bb, V.bx2, 0, st);
-      V.bcur[0] = 1;
-      after_half_sweep (H, V, 0, V.bx2, K, st);
-      gs_half_batch (H, V, K, 1, st);
-   } else {
-      column_solves_batch (H, V, K, 0, V.bb, V.bx, 0, st);
-      after_half_sweep (H, V, 0, V.bx, K, st);
-      gs_half_batch (H, V, K, 1, st);
-   }
-   for (int s = 1; s < nu; s++) { gs_half_batch (H, V, K, 0, st); gs_half_batch (H, V, K, 1, st); }
-   MlLevel &C = H.lev[l + 1];
-   const int gamma = (l >= H.gamma_from && l < H.gamma_to) ? 2 : 1;
-   for (int g = 0; g < gamma; g++) {
-      launch_csr_spmv_batch (K, V.L, 0, V.L.nrowblk, V.bxnow (), V.br, V.bb, 1, st);
-      launch_restrict_sum_batch (K, V.rptr, V.ridx, V.br, C.bb, V.nc, st);
-      ml_cycle_batch (H, K, l + 1, st);
-      launch_prolong_add_batch (K, V.cmap, C.bxnow (), V.bxnow (), V.n, H.omega, st);
-   }
-   for (int s = 0; s < nu; s++) { gs_half_batch (H, V, K, 1, st); gs_half_batch (H, V, K, 0, st); }
-}
-
-void ml_apply_batch (MlHierarchy &H, int K, const double *r, double *z, hipStream_t st)
-{
-   MlLevel &V = H.lev[0];
-   launch_gather_batch (K, H.perm0, r, V.bb, V.n, st);
-   ml_cycle_batch (H, K, 0, st);
-   launch_scatter_batch (K, H.perm0, V.bxnow (), z, V.n, st);
-}
-
-// the same from / to per-system vectors: src[k] = residual of system k (NULL: zeros), z = the K corrections interleaved,
-// dst[k] (may be NULL) = a plain copy of column k; src_scale (row-weighted iteration): the residuals are src[k] times it, row by row.
-// A Krylov step with chained cycles comes here several times: a cycle starts from its right-hand side V.bb alone (x is
-// filled, the buffer selectors reset), so nothing of the previous application is read.
+// the cycle on K interleaved right-hand sides from / to per-system vectors: src[k] = residual of system k (NULL: zeros), z = the
+// K corrections interleaved, dst[k] (may be NULL) = a plain copy of column k; src_scale (row-weighted iteration): the residuals
+// are src[k] times it, row by row.  A Krylov step with chained cycles comes here several times: a cycle starts from its
+// right-hand side alone (x is filled, the buffer selectors reset), so nothing of the previous application is read.
 void ml_apply_batch_split (MlHierarchy &H, int K, const double *const *src, double *z, double *const *dst, hipStream_t st, const double *src_scale)
 {
    MlLevel &V = H.lev[0];
-   launch_gather_interleave (K, H.perm0, src, V.bb, V.n, st, src_scale);
-   ml_cycle_batch (H, K, 0, st);
-   launch_scatter_split (K, H.perm0, V.bxnow (), z, dst, V.n, st);
+   launch_gather_interleave (K, H.perm0, src, V.wide.b, V.n, st, src_scale);
+   ml_cycle (H, K, 0, st);
+   launch_scatter_split (K, H.perm0, V.wide.now (), z, dst, V.n, st);
 }
 
 // the same on the extended rows of a rank of the row-distributed flavour: level 0 has n_own own rows followed by the overlap
@@ -299,12 +294,12 @@ void ml_apply_batch_split_ext (MlHierarchy &H, int K, const double *const *src, 
                                double *const *dst, hipStream_t st, const MlSmoothHook *hook)
 {
    MlLevel &V = H.lev[0];
-   if (sel) launch_gather_interleave_ext (K, H.perm0, src, halo, sel, n_own, V.bb, V.n, st);
-   else launch_gather_interleave_ext_block (K, H.perm0, src, halo, n_own, V.bb, V.n, st);
+   if (sel) launch_gather_interleave_ext (K, H.perm0, src, halo, sel, n_own, V.wide.b, V.n, st);
+   else launch_gather_interleave_ext_block (K, H.perm0, src, halo, n_own, V.wide.b, V.n, st);
    H.hook = hook;
-   ml_cycle_batch (H, K, 0, st);
+   ml_cycle (H, K, 0, st);
    H.hook = nullptr;
-   launch_scatter_split_own (K, H.perm0, V.bxnow (), z, dst, n_own, V.n, st);
+   launch_scatter_split_own (K, H.perm0, V.wide.now (), z, dst, n_own, V.n, st);
 }
 
 // ================================================================ measurement helpers (bench.py, probes)
@@ -312,12 +307,13 @@ void ml_apply_batch_split_ext (MlHierarchy &H, int K, const double *const *src, 
 void ml_time_piece (MlHierarchy &H, int which, hipStream_t st)
 {
    MlLevel &V = H.lev[0];
+   MlVecs &W = V.one;
    if (H.lev.size () < 2) return;
    if (which == 0) {
-      if (V.L.dg_val) launch_diag_residual (V.L, V.color_tile[0], V.color_tile[1], V.x, V.b, V.r, st);
-      else launch_csr_residual_range (V.L, V.color_rb[0], V.color_rb[1], V.x, V.b, V.r, st);
+      if (V.L.dg_val) launch_diag_residual (V.L, V.color_tile[0], V.color_tile[1], W.x, W.b, W.r, st);
+      else launch_csr_residual_range (V.L, V.color_rb[0], V.color_rb[1], W.x, W.b, W.r, st);
    }
-   else launch_colblock_apply_lanes (V.B, V.color_grp[0], V.color_grp[1], V.r, V.x, 1, st);
+   else launch_colblock_apply_lanes (V.B, V.color_grp[0], V.color_grp[1], W.r, W.x, 1, st);
 }
 
 // compulsory HBM bytes (every array element counted once per kernel that must touch it):

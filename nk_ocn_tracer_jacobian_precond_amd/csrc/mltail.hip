@@ -234,8 +234,8 @@ int ml_tail_launch (MlHierarchy &H, int l0, hipStream_t st)
       T.grp_nb = V.B.grp_nb; T.grp_maxlen = V.B.grp_maxlen; T.grp_row0 = V.B.grp_row0; T.col_slot = V.B.col_slot;
       T.grp_base = V.B.grp_base; T.fac_tf = V.B.fac_tf; T.fac_t = V.B.fac_t;
       T.cmap = V.cmap; T.rptr = V.rptr; T.ridx = V.ridx;
-      T.x = V.x; T.b = V.b; T.r = V.r;
-      V.cur[0] = V.cur[1] = 0;
+      T.x = V.one.x; T.b = V.one.b; T.r = V.one.r;
+      V.one.cur[0] = V.one.cur[1] = 0;
    }
    hipLaunchKernelGGL (ml_tail_kernel, dim3 (1), dim3 (TAIL_THREADS), 0, st, A);
    return 0;

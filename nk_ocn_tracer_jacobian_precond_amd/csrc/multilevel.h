@@ -4,6 +4,17 @@
 
 #include <vector>
 
+// One set of a level's vectors: the iterate, the right-hand side and the residual, n doubles each (n * K, element (row, k) at
+// row * K + k, in the set for K interleaved right-hand sides).  Half sweeps that are one launch ping-pong between x and x2:
+// buf (k) is buffer k, cur[c] the buffer that holds the current values of colour c's rows; the level's x is coherent (one
+// buffer) whenever cur[0] == cur[1].
+struct MlVecs {
+   double *x = nullptr, *x2 = nullptr, *b = nullptr, *r = nullptr;
+   int cur[2] = { 0, 0 };
+   double *buf (int k) { return k ? x2 : x; }
+   double *now () { return buf (cur[0]); }        // valid when coherent
+};
+
 struct MlLevel {
    int64_t n = 0;
    CsrDev L;                    // level operator, colour-major row order
@@ -20,21 +31,11 @@ struct MlLevel {
    int64_t nc = 0;              // rows of the next coarser level
    int *cmap = nullptr;         // fine row -> coarse row                 (prolongation)
    int *rptr = nullptr, *ridx = nullptr;   // coarse row -> its fine rows (restriction)
-   double *x = nullptr, *b = nullptr, *r = nullptr;
-   // fused half sweeps ping-pong between x and x2: xs[k] is buffer k, cur[c] the buffer that holds the current values
-   // of colour c's rows; the level's x is coherent (one buffer) whenever cur[0] == cur[1]
-   double *x2 = nullptr;
-   int cur[2] = { 0, 0 };
-   // K interleaved right-hand sides (batch.hip): the level's vectors once more, K times as long (allocated on first use)
-   double *bx = nullptr, *bx2 = nullptr, *bb = nullptr, *br = nullptr;
-   int bcur[2] = { 0, 0 };
-   double *bxbuf (int k) { return k ? bx2 : bx; }
-   double *bxnow () { return bxbuf (bcur[0]); }
+   MlVecs one, wide;            // the level's vectors for one right-hand side, and for K interleaved ones (ml_batch_prepare)
+   MlVecs &vec (int K) { return K == 1 ? one : wide; }
    // host: natural row of this level -> its colour-major row (levels >= 1; level 0 has perm0).  nkp_refactor sums the
    // Galerkin products in the natural order of the fine level, the order the setup used.
    std::vector<int> nat_inv;
-   double *xbuf (int k) { return k ? x2 : x; }
-   double *xnow () { return xbuf (cur[0]); }      // valid when coherent
 };
 
 // What the owner of a hierarchy may hang on one application of the cycle: `refresh` runs after every Gauss-Seidel half sweep of
@@ -68,7 +69,7 @@ struct MlHierarchy {
    double setup_seconds = 0.0;  // wall time of ml_setup
    int levels_on_device = 0;    // levels whose operator was built by the kernels of mlsetup.hip
    int inverse_pivoted = 0;     // coarse_inv came from the pivoted routine (ml_coarse_inverse returned 1); 0: blocked elimination or the host routine
-   int batch_K = 0;             // the level vectors of ml_apply_batch exist for this many right-hand sides
+   int batch_K = 0;             // every level's wide vectors (MlLevel::wide, ml_batch_prepare) hold this many right-hand sides
    int default_build = 0;       // built by the default construction (the one the setup kernels cover): nkp_refactor may keep the cells
 };
 
@@ -104,7 +105,6 @@ void ml_finish (MlHierarchy &H, double *z, hipStream_t st);
 // the same cycle on K interleaved right-hand sides (r, z: n * K doubles, element (row, k) at row * K + k; K = 2 or 4); every
 // column gets the bits ml_apply gives it alone.  ml_batch_prepare allocates the level vectors (0, or -2 = out of device memory).
 int ml_batch_prepare (MlHierarchy &H, int K);
-void ml_apply_batch (MlHierarchy &H, int K, const double *r, double *z, hipStream_t st);
 void ml_apply_batch_split (MlHierarchy &H, int K, const double *const *src, double *z, double *const *dst, hipStream_t st, const double *src_scale = nullptr);
 void ml_apply_batch_split_ext (MlHierarchy &H, int K, const double *const *src, const double *halo, const int *sel, int64_t n_own, double *z,
                                double *const *dst, hipStream_t st, const MlSmoothHook *hook = nullptr);

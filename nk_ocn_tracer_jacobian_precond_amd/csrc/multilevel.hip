@@ -178,10 +178,10 @@ int finalize_host_level (MlHierarchy &H, int l, int nlev, Nat &N, Nat *Cn, const
              upload_padded (&V.L.colind, pcol.data (), (size_t) prow[nl], 2, &H.device_bytes) &&
              upload_padded (&V.L.val, pval.data (), (size_t) prow[nl], 2, &H.device_bytes) &&
              upload (&V.L.rowblk, rb.data (), rb.size (), &H.device_bytes) &&
-             upload (&V.x, (const double *) nullptr, (size_t) nl, &H.device_bytes) &&
-             upload (&V.x2, (const double *) nullptr, (size_t) nl, &H.device_bytes) &&
-             upload (&V.b, (const double *) nullptr, (size_t) nl, &H.device_bytes) &&
-             upload (&V.r, (const double *) nullptr, (size_t) nl, &H.device_bytes);
+             upload (&V.one.x, (const double *) nullptr, (size_t) nl, &H.device_bytes) &&
+             upload (&V.one.x2, (const double *) nullptr, (size_t) nl, &H.device_bytes) &&
+             upload (&V.one.b, (const double *) nullptr, (size_t) nl, &H.device_bytes) &&
+             upload (&V.one.r, (const double *) nullptr, (size_t) nl, &H.device_bytes);
    if (ok) ok = attach_spmv_codes (V.L, prow.data (), pcol.data (), rb.data (), &H.device_bytes) == 0;
    if (ok && H.f32 && l < nlev - 1) {
       std::vector<float, RawAlloc<float>> vf;
@@ -332,8 +332,8 @@ int finalize_device_level (MlHierarchy &H, int l, DevLevel &D, Nat &N, const int
    }
    T.rb += secs_since (t0);
    t0 = setup_clk::now ();
-   bool ok = upload (&V.x, (const double *) nullptr, (size_t) nl, &H.device_bytes) && upload (&V.x2, (const double *) nullptr, (size_t) nl, &H.device_bytes) &&
-             upload (&V.b, (const double *) nullptr, (size_t) nl, &H.device_bytes) && upload (&V.r, (const double *) nullptr, (size_t) nl, &H.device_bytes);
+   bool ok = upload (&V.one.x, (const double *) nullptr, (size_t) nl, &H.device_bytes) && upload (&V.one.x2, (const double *) nullptr, (size_t) nl, &H.device_bytes) &&
+             upload (&V.one.b, (const double *) nullptr, (size_t) nl, &H.device_bytes) && upload (&V.one.r, (const double *) nullptr, (size_t) nl, &H.device_bytes);
    if (ok && H.f32) {
       ok = upload (&V.L.valf, (const float *) nullptr, (size_t) D.L.nnz + 2, &H.device_bytes) &&
            hipMemsetAsync (V.L.valf + D.L.nnz, 0, 2 * sizeof (float), st) == hipSuccess;
@@ -575,7 +575,7 @@ int ml_coarse_inverse (const MlHierarchy &H, int n, const int *prow, const int *
 void ml_free (MlHierarchy &H)
 {
    for (MlLevel &V : H.lev) {
-      void *ptrs[] = { V.L.rowptr, V.L.colind, V.L.val, V.L.valf, V.B.fac_tf, V.L.rowblk, V.L.codes, V.L.dict, V.L.dict_ptr, V.L.dg_ptr, V.L.dg_key, V.L.dg_voff, V.L.dg_val, V.L.dg_tile, V.L.dg_gptr, V.L.dg_grp, V.B.blk_start, V.B.fac, V.B.grp_b0, V.B.grp_nb, V.B.grp_maxlen, V.B.grp_base, V.B.grp_row0, V.B.col_slot, V.B.fac_t, V.B.gs_rb_ptr, V.B.gs_rb, V.B.wave_desc, V.B.grp_tile, V.cmap, V.rptr, V.ridx, V.x, V.x2, V.b, V.r, V.bx, V.bx2, V.bb, V.br };
+      void *ptrs[] = { V.L.rowptr, V.L.colind, V.L.val, V.L.valf, V.B.fac_tf, V.L.rowblk, V.L.codes, V.L.dict, V.L.dict_ptr, V.L.dg_ptr, V.L.dg_key, V.L.dg_voff, V.L.dg_val, V.L.dg_tile, V.L.dg_gptr, V.L.dg_grp, V.B.blk_start, V.B.fac, V.B.grp_b0, V.B.grp_nb, V.B.grp_maxlen, V.B.grp_base, V.B.grp_row0, V.B.col_slot, V.B.fac_t, V.B.gs_rb_ptr, V.B.gs_rb, V.B.wave_desc, V.B.grp_tile, V.cmap, V.rptr, V.ridx, V.one.x, V.one.x2, V.one.b, V.one.r, V.wide.x, V.wide.x2, V.wide.b, V.wide.r };
       for (void *p : ptrs)
          if (p) (void) hipFree (p);
       delete V.B.grp_cols;

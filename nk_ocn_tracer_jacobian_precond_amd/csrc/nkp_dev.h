@@ -412,7 +412,6 @@ void launch_csr_spmv_batch (int K, const CsrDev &A, int rb0, int rb1, const doub
 void launch_restrict_sum_batch (int K, const int *rptr, const int *ridx, const double *fine, double *coarse, int64_t nc, hipStream_t st);
 void launch_prolong_add_batch (int K, const int *cmap, const double *coarse, double *fine, int64_t nf, double omega, hipStream_t st);
 void launch_gather_batch (int K, const int *perm, const double *in, double *out, int64_t n, hipStream_t st);
-void launch_scatter_batch (int K, const int *perm, const double *in, double *out, int64_t n, hipStream_t st);
 void launch_gather_interleave (int K, const int *perm, const double *const *src, double *out, int64_t n, hipStream_t st, const double *scale = nullptr);
 void launch_scatter_split (int K, const int *perm, const double *in, double *z, double *const *dst, int64_t n, hipStream_t st);
 void launch_csr_spmv_batch_split (int K, const CsrDev &A, const double *x, double *const *dst, hipStream_t st, const double *scale = nullptr);

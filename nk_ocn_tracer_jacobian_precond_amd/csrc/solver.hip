@@ -24,7 +24,7 @@ void solver_free (nkp_solver *s)
       for (void *p : own)
          if (p) (void) hipFree (p);
       for (MlLevel &L : s->ml.lev) {
-         void *lv[] = { L.x, L.x2, L.b, L.r };
+         void *lv[] = { L.one.x, L.one.x2, L.one.b, L.one.r };
          for (void *p : lv)
             if (p) (void) hipFree (p);
       }

@@ -18,7 +18,7 @@ level but the last (which is solved densely) runs the kernel under test.
 
 Selection rule.  expected_kernel restates col_plan (csrc/col_plan.cpp), the one place where the library decides which layout a
 level gets and which instantiation serves it -- launch_colblock_apply_lanes, launch_colblock_apply_lanes_batch,
-column_solves_batch and finish_level_columns branch on its ColKernel.  tests/test_col_plan.py holds the two against each other
+column_solves (csrc/mlcycle.hip) and finish_level_columns branch on its ColKernel.  tests/test_col_plan.py holds the two against each other
 on the CPU; the GPU tests read the outcome through nkp_ml_level_array (.., "col_kernel").
 
   wave         only on a level without dropped entries (V.wave_columns)

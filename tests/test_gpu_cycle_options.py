@@ -8,7 +8,9 @@ the one above it through the identity that made it, L_{l+1} = P^T L_l P.  What i
       gs_wave_kernel (default), residual range + lane kernels (col_wave_max = 0), gs_fused_kernel (col_wave_max = 0, ml_fused = 1)
       and ml_tail_kernel (ml_tail_rows = 16000, which by design applies only with a dense last level and no W-level)
   (b) the hierarchy options, at the default cycle and at the combined case of (a), plus the structure of every level
-  (c) ml_cycle_batch: solve_many against solve, column by column, for the cases that change its control flow
+  (c) ml_cycle at K >= 2: solve_many against solve, column by column, for the cases that change its control flow, and at the
+      default and the combined case under each kernel family of (a) -- at K >= 2 every operation has one kernel, whatever
+      family serves the single cycle, so the single solves it is compared with take other kernels in every family
 
 Tolerances of (a) and (b), from the reference alone, computed here on the levels of the case at hand:
   f64 storage   ||z - z_ref|| <= max (1e-12, 4096 * d) ||z_ref||, d = reference with LU blocks against explicit inverses (the
@@ -258,7 +260,7 @@ def test_hierarchy_options_match_the_restated_cycle(name, f32, problems, default
         ref.check("%s / %s" % (name, case), case, z[case])
 
 
-# ================================================================ (c) the batched copy of the cycle
+# ================================================================ (c) the cycle on K interleaved right-hand sides
 def batch_against_single(prob, options, tuning, nrhs_list, nmax):
     B = np.random.default_rng(11).standard_normal((nmax, prob.p.flat_len))
     B[2] *= 1e-3                                            # systems of a group converge at different steps
@@ -274,13 +276,21 @@ def batch_against_single(prob, options, tuning, nrhs_list, nmax):
         assert s.get_int("batch_width") >= 2                 # the batched path ran
 
 
+# (case, kernel family of (a), widths): the cases that change the control flow under the default family, then the default and the
+# combined case under every family -- at K >= 2 each operation has one kernel whatever family serves the single cycle, so the
+# single solves of a column take other kernels there and must give the same bits
+BATCH_PARAMS = [pytest.param(case, "wave", (2, 3, 4, 5), id=case) for case in BATCH_CASES]
+BATCH_PARAMS += [pytest.param(case, family, (2, 3, 5), id="%s-%s" % (case, family))
+                 for case in ("default", "combined") for family, _ in FAMILIES if (case, family) != ("combined", "wave")]
+
+
 @pytest.mark.parametrize("f32", [0, 1], ids=["f64", "f32"])
-@pytest.mark.parametrize("case", BATCH_CASES)
-def test_batched_cycle_options_have_the_bits_of_single_solves(case, f32, problems):
+@pytest.mark.parametrize("case, family, nrhs_list", BATCH_PARAMS)
+def test_batched_cycle_options_have_the_bits_of_single_solves(case, family, nrhs_list, f32, problems):
     hierarchy, knobs = CASES[case]
     options, tuning, _ = CYCLE_HIERARCHIES[hierarchy]
     case_options, case_tuning = split_knobs(knobs)
-    batch_against_single(problems("one"), dict(options, **case_options), dict(tuning, ml_f32=f32, **case_tuning), (2, 3, 4, 5), 5)
+    batch_against_single(problems("one"), dict(options, **case_options), dict(tuning, ml_f32=f32, **case_tuning, **dict(FAMILIES)[family]), nrhs_list, 5)
 
 
 def test_eight_wide_batched_cycle_has_the_bits_of_single_solves(problems):
