@@ -367,7 +367,12 @@ int nkp_multi_dot (nkp_solver *s, const double *V, int64_t ld, int k, const doub
  * 16 K n, plus 8 K n when accumulating -- at K = 1 exactly the SpMV's); 7 = for comparison with 6, same arg: the composition
  * that kernel replaces, made of the SpMV kernels on the solver's own values -- the (batched) operator product into a temporary, its
  * de-interleave, one update pass over the K vectors (24 K n more bytes); 8 = the product y = A x on A's per-column diagonals
- * (tuning spmv_diag; NKP_EINVAL when A has none -- 0 stays the CSR kernel on the same matrix either way). */
+ * (tuning spmv_diag; NKP_EINVAL when A has none -- 0 stays the CSR kernel on the same matrix either way); 9 = the kernel of
+ * nkp_values_product_trans alone, operands and arg as for 6, on the transposed index (built by this call if the solver has none;
+ * its compulsory bytes: those of 6 + 4 nnz for the value map); 10 = for comparison with 9, same arg: the composition it replaces
+ * -- the values gathered through the map into a temporary of nnz doubles, then the kernel of 6 on the transposed pattern (16 nnz
+ * more bytes).  9 and 10: single-GPU solvers that own their pattern only (NKP_EINVAL on a row-distributed solver, a clone, a
+ * transposed handle, and for another arg). */
 int nkp_time_kernel (nkp_solver *s, int which, int arg, int reps, double *avg_ms);
 
 /* Introspection: key = "n", "nnz", "nblk", "band", "levels", "spmv_bytes" (compulsory bytes of the CSR product: 12 nnz +
@@ -392,7 +397,10 @@ int nkp_time_kernel (nkp_solver *s, int which, int arg, int reps, double *avg_ms
  * device collectives made by solves, single or batched, and the one alltoallv of every nkp_value_gradient*; 0 on a single-GPU
  * solver), "value_gradient_calls" (successful nkp_value_gradient* calls), "value_gradient_us" (wall time of the last one),
  * "values_product_calls" (successful products: nkp_values_product* calls and the one inside every nkp_solve_tangent_device with
- * d_dval), "values_product_us" (wall time of the last one), "tangent_calls" (nkp_solve_tangent_device calls that ran their solve), "batch_steps" (batched operator
+ * d_dval), "values_product_us" (wall time of the last one), "tangent_calls" (nkp_solve_tangent_device calls that ran their solve),
+ * "values_product_trans_calls" (successful nkp_values_product_trans* calls), "values_product_trans_us" (wall time of the last one),
+ * "trans_index_bytes" (device bytes of the transposed index those calls keep, 0 before the first; part of "device_bytes"),
+ * "trans_index_us" (wall time of building it), "batch_steps" (batched operator
  * applications = lockstep Krylov steps of a group of right-hand sides), "batch_width" (K of the last batched group, 0 if
  * none ran); "batch_member_bytes" (device bytes of the K - 1 further sets of work vectors a batched call has made and keeps:
  * Krylov bases, level vectors, with chained cycles the residual between two cycles; "device_bytes" counts the solver's own set
@@ -687,6 +695,39 @@ int nkp_value_gradient (nkp_solver *s, int nrhs, const double *lambda, const dou
  * row-distributed solver told to the other ranks through the first agreement); NKP_ENOMEM / NKP_EDEVICE; NKP_ECOMM. */
 int nkp_values_product_device (nkp_solver *s, int nrhs, const void *d_val, const void *d_x, int64_t ldx, double alpha, int accumulate, void *d_y, int64_t ldy);
 int nkp_values_product (nkp_solver *s, int nrhs, const double *val, const double *x, int64_t ldx, double alpha, int accumulate, double *y, int64_t ldy);
+
+/* The same product with the TRANSPOSED pattern, the values staying in A's order: with G the matrix that holds val on A's
+ * pattern, y_c (+)= alpha * G^T x_c.  nkp_value_gradient is bilinear in (lambda, x); its derivative with respect to lambda is a
+ * nkp_values_product, its derivative with respect to x is this product -- with it the solve, the transposed solve, the gradient and
+ * the two products are closed under differentiation (second and higher derivatives through a solve; torch_op.py).
+ * For every column j of A and vector c, t_c[j] starts at +0.0 and adds val[e] * x_c[row of e] over the stored entries e with
+ * colind[e] == j in ascending order of (row, stored position), each product and each sum rounded on its own (no fused
+ * multiply-add); then
+ *      y_c[j] = alpha * t_c[j]   (accumulate == 0; y is not read and may hold anything)      y_c[j] = y_c[j] + alpha * t_c[j]   (accumulate != 0)
+ * t_c has the bits nkp_spmv_device gives for x_c on a solver created from the host transpose of (pattern, val), taken stably (an
+ * entry of A^T's row j keeps its place among the entries of A in row-major order: repeated and unsorted entries of A have a
+ * defined place); a column of more than 2048 entries is summed in the SpMV's tree for such rows.  The bits are the same for every
+ * nrhs.  A column of A without entries gets alpha * (+0.0).
+ *   Buffers as for nkp_values_product: val holds nnz doubles in the CSR order of nkp_create (NOT transposed by the caller); x and
+ *   y hold nrhs vectors, vector c at c * ldx and c * ldy, ldx, ldy >= n, rows n .. ld - 1 neither read nor written; 1 <= nrhs <=
+ *   8; y == x is refused.  nkp_values_product_trans takes host buffers, nkp_values_product_trans_device buffers on the solver's
+ *   device.  The work runs on the solver's stream and has finished when the call returns.
+ *   The transposed index: the first call builds, on the device, the pattern of A^T (4 (n + 1) + 4 nnz bytes), the map from its
+ *   entries to A's (4 nnz bytes) and its row blocks -- the blocks a solver created from the host transpose has -- and the solver
+ *   keeps them: "trans_index_bytes", "trans_index_us", counted in "device_bytes".  While it is built the device transpose holds
+ *   16 nnz + 4 n bytes more. All or nothing: a failed allocation (NKP_ENOMEM) leaves the solver exactly as it was.  A refactor keeps
+ *   the pattern, with or without NKP_REFACTOR_REBUILD, so the index survives it.  The index is the solver's own: it neither uses nor
+ *   feeds a handle from nkp_transpose, and a solver that has both holds 8 nnz + 4 (n + 1) bytes twice.  Work space beyond it is
+ *   that of nkp_values_product, the same buffers (the K-interleaved copy of x, the staging of the host flavour).
+ *   Only the pattern is read: the call is allowed on a solver whose refactor failed after its commit point.
+ * Refused with NKP_EINVAL, the solver solving exactly as before: a clone (call it on the solver it was cloned from, as for
+ * nkp_transpose); a transposed handle (call it on its owner; on the handle nkp_values_product multiplies with A^T's pattern and
+ * values in A^T's order); a row-distributed solver, force_dist included -- the product sends rows back to their owners, a reverse
+ * exchange that is still to come -- refused on the calling rank without any collective.  A NULL solver or buffer is refused on the
+ * calling thread before the solver is looked at, the message names the argument; nrhs outside 1 .. 8, ldx or ldy < n, y == x
+ * are found before any HIP call.  NKP_ENOMEM / NKP_EDEVICE.  nkp_get_int: "values_product_trans_calls", "values_product_trans_us". */
+int nkp_values_product_trans_device (nkp_solver *s, int nrhs, const void *d_val, const void *d_x, int64_t ldx, double alpha, int accumulate, void *d_y, int64_t ldy);
+int nkp_values_product_trans (nkp_solver *s, int nrhs, const double *val, const double *x, int64_t ldx, double alpha, int accumulate, double *y, int64_t ldy);
 
 /* The tangent (forward mode) of a solve: dX = A^-1 (dB - dA X) for nrhs right-hand sides, device buffers.  R_c = dB_c - dA X_c is
  * formed in work space of the solver (8 nrhs ld bytes, at first use, kept, counted in "device_bytes") and has the bits of

@@ -155,7 +155,9 @@ extern "C" int nkp_time_kernel (nkp_solver *s, int which, int arg, int reps, dou
       const int prc = valgrad_time_prepare (s, arg);
       if (prc) return prc;
    }
-   if (which == 6 || which == 7) {      // the product kernel of nkp_values_product at interleave width arg, likewise; 7: what it replaces
+   // the product kernel of nkp_values_product at interleave width arg, likewise; 7: what it replaces; 9: the same kernel on the
+   // transposed index with gathered values (nkp_values_product_trans); 10: what that replaces
+   if (which == 6 || which == 7 || which == 9 || which == 10) {
       const int prc = valprod_time_prepare (s, arg, which);
       if (prc) return prc;
    }
@@ -196,6 +198,8 @@ extern "C" int nkp_time_kernel (nkp_solver *s, int which, int arg, int reps, dou
          else if (which == 5) valgrad_time_launch (s, arg);
          else if (which == 6) valprod_time_launch (s, arg);
          else if (which == 7) valprod_time_composition (s, arg);
+         else if (which == 9) valprod_time_launch_trans (s, arg);
+         else if (which == 10) valprod_time_composition_trans (s, arg);
          else if (s->opt.precond == NKP_PRECOND_MULTILEVEL) ml_time_piece (s->ml, which - 3, s->stream);   // 3: smoother residual rows, 4: column solves (level 0, colour 0)
       }
       HIPCHK (hipEventRecord (e1, s->stream));

@@ -109,6 +109,10 @@ void launch_value_gradient (int K, int nk, const CsrDev &A, const double *lam, c
 // with the bits of the SpMV kernels on a matrix that stores val.  K in {1, 2, 4, 8}: interleave width of x (1 = a plain vector), nk <= K;
 // y is column-major, vector c at c * ldy.  Every row is written, also of a matrix without entries
 void launch_values_product (int K, int nk, const CsrDev &A, const double *val, const double *x, double alpha, int accumulate, double *y, int64_t ldy, hipStream_t st);
+// nkp_values_product_trans (valprod.hip): the same kernel text on the pattern T of A^T (rowptr, colind, rowblk only), the value of its entry p
+// gathered from val[src[p]] -- val stays in A's order; the bits of the SpMV kernels on a matrix that stores the transposed values
+void launch_values_product_trans (int K, int nk, const CsrDev &T, const int *src, const double *val, const double *x, double alpha, int accumulate, double *y,
+                                  int64_t ldy, hipStream_t st);
 
 // ---------------------------------------------------------------- water-column blocks
 // Banded LU (no pivoting) of every diagonal block, half-bandwidth P in {1,2,4}; SoA by

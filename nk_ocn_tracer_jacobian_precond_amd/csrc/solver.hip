@@ -151,6 +151,10 @@ extern "C" int64_t nkp_get_int (nkp_solver *s, const char *key)
    if (!strcmp (key, "values_product_calls")) return s->vp.calls;
    if (!strcmp (key, "values_product_us")) return (int64_t) (s->vp.seconds * 1.0e6);
    if (!strcmp (key, "tangent_calls")) return s->vp.tangent_calls;
+   if (!strcmp (key, "values_product_trans_calls")) return s->vt.calls;
+   if (!strcmp (key, "values_product_trans_us")) return (int64_t) (s->vt.seconds * 1.0e6);
+   if (!strcmp (key, "trans_index_bytes")) return (int64_t) s->vt.bytes;
+   if (!strcmp (key, "trans_index_us")) return (int64_t) (s->vt.build_seconds * 1.0e6);
    if (!strcmp (key, "batch_steps")) return s->batch_steps;
    if (!strcmp (key, "batch_width")) return s->batch_width;
    if (!strcmp (key, "batch_member_bytes")) {      // the further sets of work vectors a batched group keeps (not part of device_bytes)

@@ -165,6 +165,18 @@ struct nkp_solver {
       int64_t calls = 0, tangent_calls = 0;
       double seconds = 0.0;        // wall time of the last product
    } vp;
+   // nkp_values_product_trans: the pattern of A^T as an index, no values and no solver -- T.rowptr [n + 1], T.colind [nnz], T.rowblk
+   // (the row blocks a solver created from the host transpose has) and src [nnz]: entry p of A^T takes its value from val[src[p]].
+   // Built at the first call that needs it, all four arrays or none, kept (a refactor keeps the pattern), counted in device_bytes.
+   // The owner's own: independent of trans / trans_src; a clone or a transposed handle never has one
+   struct {
+      CsrDev T;
+      int *src = nullptr;
+      size_t bytes = 0;
+      double build_seconds = 0.0;
+      int64_t calls = 0;
+      double seconds = 0.0;        // wall time of the last product
+   } vt;
    double *h_dev () { return dscal; }
    double *h2_dev () { return dscal + (m + 2); }
    double *misc_dev () { return dscal + 2 * (m + 2); }     // [0]=nrm2 [1]=inv [2]=dot out ...
@@ -407,6 +419,10 @@ NKP_PRIVATE void valprod_release (nkp_solver *s);
 NKP_PRIVATE int valprod_time_prepare (nkp_solver *s, int K, int which);
 NKP_PRIVATE void valprod_time_launch (nkp_solver *s, int K);
 NKP_PRIVATE void valprod_time_composition (nkp_solver *s, int K);
+// which = 9: the same kernel on the transposed index with gathered values (nkp_values_product_trans); which = 10: the composition
+// it replaces -- the values gathered into a temporary of nnz doubles, then the product kernel on the transposed pattern
+NKP_PRIVATE void valprod_time_launch_trans (nkp_solver *s, int K);
+NKP_PRIVATE void valprod_time_composition_trans (nkp_solver *s, int K);
 // ---- defined in transpose.hip ----------------------------------------------------------------------------------------------
 // the owner frees its transposed solver and the value map; a transposed solver that is destroyed leaves its owner
 NKP_PRIVATE void trans_release (nkp_solver *s);
@@ -416,6 +432,8 @@ NKP_PRIVATE void trans_set_stream (nkp_solver *s);
 NKP_PRIVATE int64_t trans_device_bytes (const nkp_solver *s);
 // valT = A.val[trans_src] on the owner's stream, into a buffer the owner keeps
 NKP_PRIVATE int trans_gather_values (nkp_solver *s, const double **d_valT);
+// out[p] = val[src[p]], p < nnz
+NKP_PRIVATE void launch_tr_gather (const double *val, const int *src, int64_t nnz, double *out, hipStream_t st);
 // ---- defined in transpose_dist.hip -----------------------------------------------------------------------------------------
 // collective: the values of A^T's row block from the owner's new values (gather, one alltoallv, placement), then the refactor
 // `refactor` (nkp_refactor_dist_device's sequence) on the transposed solver; non-zero on every rank when it could not follow

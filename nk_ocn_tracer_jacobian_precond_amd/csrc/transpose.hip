@@ -164,6 +164,11 @@ int64_t trans_device_bytes (const nkp_solver *s)
    return (int64_t) sum;
 }
 
+void launch_tr_gather (const double *val, const int *src, int64_t nnz, double *out, hipStream_t st)
+{
+   if (nnz > 0) hipLaunchKernelGGL (tr_gather_kernel, tr_grid (nnz), dim3 (TR_T), 0, st, val, src, nnz, out);
+}
+
 // ---------------------------------------------------------------- the refactor of the source reaches the transposed solver
 int trans_gather_values (nkp_solver *s, const double **d_valT)
 {
@@ -178,7 +183,7 @@ int trans_gather_values (nkp_solver *s, const double **d_valT)
       s->trans_val = (double *) q;
       s->trans_map_bytes += bytes;
    }
-   if (nnz > 0) hipLaunchKernelGGL (tr_gather_kernel, tr_grid (nnz), dim3 (TR_T), 0, s->stream, s->A.val, s->trans_src, nnz, s->trans_val);
+   launch_tr_gather (s->A.val, s->trans_src, nnz, s->trans_val, s->stream);
    HIPCHK (hipGetLastError ());
    *d_valT = s->trans_val;
    return NKP_OK;

@@ -14,15 +14,21 @@
 // Columns c >= nk of a width-K buffer take no part: nothing of them is summed and y has no such column, so a width serves fewer
 // vectors (3 in 4, 5 .. 7 in 8) with unchanged bits.  No atomics, no waiting between workgroups; a row block without entries
 // still writes alpha * (+0.0) to its rows.
+//
+// The same kernel text serves nkp_values_product_trans (GATHER): the pattern is then the transposed index the solver keeps
+// (rowptrT, colindT, its row blocks) and the value of entry p is val[src[p]], the caller's values staying in A's order.  The
+// staging step issues all its src loads (coalesced), then the val gathers that depend on them, then writes LDS; the long-row
+// walk gathers the same way.  Without GATHER src is not read and the instantiations are what they were.
 #include "nkp_dev.h"
 
 #define VP_THREADS 256
 #define VP_WAVES (VP_THREADS / NKP_WAVE)
 
-template <int K>
+template <int K, bool GATHER>
 __global__ __launch_bounds__ (VP_THREADS)
 void values_product_kernel (const int *__restrict__ rowblk, int nrowblk, int per_xcd, const int *__restrict__ rowptr, const int *__restrict__ colind,
-                            const double *__restrict__ val, const double *__restrict__ x, int nk, double alpha, int accumulate, double *y, int64_t ldy)
+                            const int *__restrict__ src, const double *__restrict__ val, const double *__restrict__ x, int nk, double alpha, int accumulate,
+                            double *y, int64_t ldy)
 {
    __shared__ double sv[NKP_SPMV_LDS_NNZ];
    __shared__ int sc[NKP_SPMV_LDS_NNZ];
@@ -41,7 +47,7 @@ void values_product_kernel (const int *__restrict__ rowblk, int nrowblk, int per
    if (cnt > NKP_SPMV_LDS_NNZ) {
       // a single long row, all K columns in one walk: per column the strided sums and the reduction of the SpMV kernels
       for (int e = e0 + tid; e < e1; e += VP_THREADS) {
-         const double v = val[e];
+         const double v = val[GATHER ? src[e] : e];
          const double *xr = x + (int64_t) colind[e] * K;
          double xv[K];
          if constexpr (K == 1) xv[0] = xr[0];
@@ -76,11 +82,17 @@ void values_product_kernel (const int *__restrict__ rowblk, int nrowblk, int per
    if (r < r1) { s0 = rowptr[r] - e0; s1 = rowptr[r + 1] - e0; }
    {
       double v[SLOTS];
-      int c[SLOTS];
+      int c[SLOTS], from[SLOTS];
 #pragma unroll
       for (int u = 0; u < SLOTS; u++) {
          const int k = tid + u * VP_THREADS;
-         v[u] = k < cnt ? val[e0 + k] : 0.0;
+         from[u] = e0 + k;
+         if constexpr (GATHER) from[u] = k < cnt ? src[e0 + k] : 0;
+      }
+#pragma unroll
+      for (int u = 0; u < SLOTS; u++) {
+         const int k = tid + u * VP_THREADS;
+         v[u] = k < cnt ? val[from[u]] : 0.0;
          c[u] = k < cnt ? colind[e0 + k] : 0;
       }
 #pragma unroll
@@ -127,15 +139,31 @@ void values_product_kernel (const int *__restrict__ rowblk, int nrowblk, int per
       }
 }
 
+// one launch for both products: a workgroup per row block of A, numbered XCD-contiguously
+template <bool GATHER>
+static void launch_product (int K, int nk, const CsrDev &A, const int *src, const double *val, const double *x, double alpha, int accumulate, double *y, int64_t ldy,
+                            hipStream_t st)
+{
+   if (A.nrowblk <= 0) return;
+   const int per_xcd = (A.nrowblk + 7) / 8;
+   with_int<1, 2, 4, 8> (K, [&] (auto k) {
+      hipLaunchKernelGGL ((values_product_kernel<decltype (k)::value, GATHER>), dim3 (per_xcd * 8), dim3 (VP_THREADS), 0, st, A.rowblk, A.nrowblk, per_xcd, A.rowptr,
+                          A.colind, src, val, x, nk < K ? nk : K, alpha, accumulate, y, ldy);
+   });
+}
+
 // y_c (+)= alpha * (pattern of A with the values val) x_c for c < nk, y column-major (vector c at c * ldy).  K in {1, 2, 4, 8} is
 // the interleave width of x (1: a plain vector), nk <= K.  x is indexed by A's columns (row-distributed: [own | halo] like the
 // SpMV's input).  Every row of A is written, also when A has no entries.
 void launch_values_product (int K, int nk, const CsrDev &A, const double *val, const double *x, double alpha, int accumulate, double *y, int64_t ldy, hipStream_t st)
 {
-   if (A.nrowblk <= 0) return;
-   const int per_xcd = (A.nrowblk + 7) / 8;
-   with_int<1, 2, 4, 8> (K, [&] (auto k) {
-      hipLaunchKernelGGL (values_product_kernel<decltype (k)::value>, dim3 (per_xcd * 8), dim3 (VP_THREADS), 0, st, A.rowblk, A.nrowblk, per_xcd, A.rowptr, A.colind,
-                          val, x, nk < K ? nk : K, alpha, accumulate, y, ldy);
-   });
+   launch_product<false> (K, nk, A, nullptr, val, x, alpha, accumulate, y, ldy, st);
+}
+
+// The same with the value of entry p of T taken from val[src[p]]: T holds the pattern of A^T (rowptr, colind, rowblk, nrowblk; no
+// values), val the caller's values in A's order, x is indexed by A's rows and y by A's columns
+void launch_values_product_trans (int K, int nk, const CsrDev &T, const int *src, const double *val, const double *x, double alpha, int accumulate, double *y,
+                                  int64_t ldy, hipStream_t st)
+{
+   launch_product<true> (K, nk, T, src, val, x, alpha, accumulate, y, ldy, st);
 }

@@ -3,16 +3,76 @@
 // dX = A^-1 (dB - dA X).  The kernel is valprod.hip; this unit checks the arguments, keeps the work space, fetches the halo rows
 // of x on a row-distributed solver (fetch_x_operand, shared with nkp_value_gradient) and keeps the ranks together.  Only the
 // pattern of the solver's matrix is read by the product.
+// nkp_values_product_trans*: the same product with the transposed pattern, y_c (+)= alpha * (pattern with val)^T x_c, val still in
+// A's order.  Same arguments, work space and kernel text; what it adds is the transposed index (solver_impl.h: vt) it builds at its
+// first call, and the refusals of the handles that do not hold A's pattern themselves.
 #include "solver_impl.h"
+#include "transpose.h"
 
+#include <stdlib.h>
 #include <time.h>
 
 namespace {
 
+double seconds_between (const struct timespec &a, const struct timespec &b) { return (double) (b.tv_sec - a.tv_sec) + 1e-9 * (double) (b.tv_nsec - a.tv_nsec); }
+
+// ---- the transposed index: the device transpose of the pattern (its values dropped), the row blocks from a host copy of rowptrT --
+// those a solver created from the host transpose has.  All four arrays or none: after a failure the solver holds what it held and
+// HIP's last error is cleared.  The ranking step of the device transpose reads A.val, which a solver keeps also when broken.
+int trans_index_build (nkp_solver *s, const char *who)
+{
+   auto &I = s->vt;
+   if (I.src) return NKP_OK;
+   const int64_t n = s->n, nnz = s->A.nnz;
+   hipStream_t st = s->stream;
+   struct timespec t0, t1;
+   clock_gettime (CLOCK_MONOTONIC, &t0);
+   mls::DBuf<int> rowptrT, colindT, src, rowblk;
+   {
+      mls::DBuf<double> valT;      // comes along with the transpose; freed here
+      const int trc = transpose_device (s->A, n, rowptrT, colindT, valT, src, st);
+      if (trc) {
+         (void) hipStreamSynchronize (st);
+         (void) hipGetLastError ();      // an out-of-memory error is sticky until read
+         if (trc == (int) hipErrorOutOfMemory) return fail (NKP_ENOMEM, "%s: no device memory for the transposed index (%lld entries); the solver is unchanged", who, (long long) nnz);
+         return fail (NKP_EDEVICE, "%s: the device transpose of the pattern failed (%s)", who, trc >= 1000 ? "inconsistent column counts" : hipGetErrorString ((hipError_t) trc));
+      }
+   }
+   std::vector<int> h_rp ((size_t) n + 1);
+   hipError_t e = hipMemcpy (h_rp.data (), rowptrT.p, h_rp.size () * sizeof (int), hipMemcpyDeviceToHost);
+   int *h_rb = nullptr;
+   int nrb = 0;
+   if (e == hipSuccess) {
+      build_rowblocks_host (n, h_rp.data (), &h_rb, &nrb);
+      e = rowblk.alloc ((size_t) nrb + 1);
+      if (e == hipSuccess) e = hipMemcpy (rowblk.p, h_rb, ((size_t) nrb + 1) * sizeof (int), hipMemcpyHostToDevice);
+      free (h_rb);
+   }
+   if (e != hipSuccess) {
+      (void) hipGetLastError ();
+      return fail (e == hipErrorOutOfMemory ? NKP_ENOMEM : NKP_EDEVICE, "%s: the row blocks of the transposed index failed: %s; the solver is unchanged", who, hipGetErrorString (e));
+   }
+   // as the allocations were made: a buffer of no element holds one
+   I.bytes = (((size_t) n + 1) + 2 * (size_t) (nnz ? nnz : 1) + ((size_t) nrb + 1)) * sizeof (int);
+   I.T.n = n;
+   I.T.nnz = nnz;
+   I.T.rowptr = rowptrT.release ();
+   I.T.colind = colindT.release ();
+   I.T.rowblk = rowblk.release ();
+   I.T.nrowblk = nrb;
+   I.src = src.release ();
+   s->device_bytes += I.bytes;
+   clock_gettime (CLOCK_MONOTONIC, &t1);
+   I.build_seconds = seconds_between (t0, t1);
+   msg (s, 1, "%s: transposed index of %lld entries, %d row blocks, %.1f MB, %.3f s\n", who, (long long) nnz, nrb, (double) I.bytes / 1.0e6, I.build_seconds);
+   return NKP_OK;
+}
+
 // ---- (b) the operand x (single-GPU: interleaved; row-distributed: the halo rows, all vectors in one exchange), the kernel, and on
 // a row-distributed solver the second agreement.  h_y: the host flavour's result, downloaded from Y (ld n) before the agreement
+// trans: the product with the transposed pattern (single-GPU only; the index exists)
 int product_run (nkp_solver *s, int nrhs, const double *val, const double *X, int64_t ldx, double alpha, int accumulate, double *Y, int64_t ldy,
-                 double *h_y, int64_t h_ldy, const char *who)
+                 double *h_y, int64_t h_ldy, const char *who, bool trans = false)
 {
    const int K = width_of (nrhs);
    const int64_t n = s->n;
@@ -24,7 +84,8 @@ int product_run (nkp_solver *s, int nrhs, const double *val, const double *X, in
    const double *x_in = X;
    int rc = fetch_x_operand (s, K, xp, s->vp.x, &x_in, who);
    if (!rc) {
-      launch_values_product (K, nrhs, s->A, val, x_in, alpha, accumulate, Y, ldy, st);
+      if (trans) launch_values_product_trans (K, nrhs, s->vt.T, s->vt.src, val, x_in, alpha, accumulate, Y, ldy, st);
+      else launch_values_product (K, nrhs, s->A, val, x_in, alpha, accumulate, Y, ldy, st);
       hipError_t e = hipSuccess;
       for (int c = 0; h_y && c < nrhs && e == hipSuccess && n; c++)
          e = hipMemcpyAsync (h_y + (size_t) c * (size_t) h_ldy, Y + (size_t) c * (size_t) ldy, (size_t) n * sizeof (double), hipMemcpyDeviceToHost, st);
@@ -37,16 +98,29 @@ int product_run (nkp_solver *s, int nrhs, const double *val, const double *X, in
    if (rc) return rc;
    struct timespec ts1;
    clock_gettime (CLOCK_MONOTONIC, &ts1);
-   s->vp.seconds = (double) (ts1.tv_sec - ts0.tv_sec) + 1e-9 * (double) (ts1.tv_nsec - ts0.tv_nsec);
-   s->vp.calls++;
+   if (trans) {
+      s->vt.seconds = seconds_between (ts0, ts1);
+      s->vt.calls++;
+   } else {
+      s->vp.seconds = seconds_between (ts0, ts1);
+      s->vp.calls++;
+   }
    return NKP_OK;
 }
 
 // Host flavour: h_* given, d_* NULL; device flavour the other way round.  The entry points have refused NULL arguments on the
-// calling rank, before the solver is looked at and before any collective.
+// calling rank, before the solver is looked at and before any collective.  trans: nkp_values_product_trans*, refused here on the
+// handles that do not hold A's pattern themselves and on row-distributed solvers (on the calling rank, no collective)
 int values_product (nkp_solver *s, int nrhs, const double *h_val, const double *h_x, const double *d_val, const double *d_x, int64_t ldx, double alpha,
-                    int accumulate, double *h_y, double *d_y, int64_t ldy, const char *who)
+                    int accumulate, double *h_y, double *d_y, int64_t ldy, const char *who, bool trans = false)
 {
+   if (trans) {
+      if (s->borrowed) return fail (NKP_EINVAL, "%s: a clone shares its matrix; call it on the solver it was cloned from", who);
+      if (s->trans_of)
+         return fail (NKP_EINVAL, "%s: this solver is itself a transposed handle; call it on the solver it was transposed from (or nkp_values_product here, with values in A^T's order)", who);
+      if (s->dist.on)
+         return fail (NKP_EINVAL, "%s: not available for the row-distributed flavour (the product with the transposed pattern sends rows back to their owners, a reverse exchange this library does not have yet); gather the vectors and use a single-GPU solver", who);
+   }
    const bool host = h_y != nullptr;
    const bool dist = s->dist.on;
    auto &W = s->vp;
@@ -63,6 +137,7 @@ int values_product (nkp_solver *s, int nrhs, const double *h_val, const double *
    const int K = width_of (nrhs);
    if (!rc && hipSetDevice (s->device) != hipSuccess) rc = fail (NKP_EDEVICE, "%s: hipSetDevice (%d) failed", who, s->device);
    const size_t vecs = rc ? 0 : (size_t) nrhs * (size_t) n;
+   if (!rc && trans) rc = trans_index_build (s, who);
    if (!rc)
       rc = reserve (s, { { &W.x, &W.x_cap, !dist && K >= 2 ? (size_t) n * (size_t) K : 0 },      // K = 1 reads x in place; row-distributed: dist.xe / dist.bxe
                          { &W.stage, &W.stage_cap, host ? (size_t) nnz + 2 * vecs : 0 } }, who);
@@ -89,7 +164,7 @@ int values_product (nkp_solver *s, int nrhs, const double *h_val, const double *
       return rc;
    }
    if (rc) return rc;
-   return product_run (s, nrhs, V, X, lx, alpha, accumulate, Y, ly, host ? h_y : nullptr, ldy, who);
+   return product_run (s, nrhs, V, X, lx, alpha, accumulate, Y, ly, host ? h_y : nullptr, ldy, who, trans);
 }
 
 // The first agreement of a tangent solve: every rank learns whether any rank's step failed AND whether all ranks pass d_dval alike
@@ -114,6 +189,10 @@ void valprod_release (nkp_solver *s)
    for (double **p : { &s->vp.x, &s->vp.stage, &s->vp.r })
       if (*p) { (void) hipFree (*p); *p = nullptr; }
    s->vp.x_cap = s->vp.stage_cap = s->vp.r_cap = 0;
+   for (int **p : { &s->vt.T.rowptr, &s->vt.T.colind, &s->vt.T.rowblk, &s->vt.src })
+      if (*p) { (void) hipFree (*p); *p = nullptr; }
+   s->vt.T.nrowblk = 0;
+   s->vt.bytes = 0;
 }
 
 int valprod_time_prepare (nkp_solver *s, int K, int which)
@@ -121,8 +200,13 @@ int valprod_time_prepare (nkp_solver *s, int K, int which)
    if (s->dist.on) return fail (NKP_EINVAL, "nkp_time_kernel: the product kernel (which = %d) is timed on single-GPU solvers only", which);
    if (K != 1 && K != 2 && K != 4 && K != 8) return fail (NKP_EINVAL, "nkp_time_kernel: which = %d takes arg = K in {1, 2, 4, 8}", which);
    const size_t kn = (size_t) K * (size_t) s->n, il = K >= 2 ? kn : 0, nnz = (size_t) s->A.nnz;
-   // values | y, and for the composition | the temporary product, interleaved | the same, one vector after the other
-   const int rc = reserve (s, { { &s->vp.x, &s->vp.x_cap, il }, { &s->vp.stage, &s->vp.stage_cap, nnz + (which == 7 ? 3 : 1) * kn } }, "nkp_time_kernel");
+   if (which == 9 || which == 10) {
+      if (s->borrowed || s->trans_of) return fail (NKP_EINVAL, "nkp_time_kernel: which = %d is timed on the solver that owns A's pattern, not on a clone or a transposed handle", which);
+      if (const int irc = trans_index_build (s, "nkp_time_kernel")) return irc;
+   }
+   // values | y, and for the composition | the temporary product, interleaved | the same, one vector after the other (7) or | the
+   // gathered values (10)
+   const int rc = reserve (s, { { &s->vp.x, &s->vp.x_cap, il }, { &s->vp.stage, &s->vp.stage_cap, nnz + (which == 7 ? 3 : 1) * kn + (which == 10 ? nnz : 0) } }, "nkp_time_kernel");
    if (rc) return rc;
    if (nnz) launch_fill (s->vp.stage, 1.0, (int64_t) nnz, s->stream);
    if (kn) launch_fill (s->vp.stage + nnz, 1.0, (int64_t) kn, s->stream);
@@ -153,6 +237,20 @@ void valprod_time_composition (nkp_solver *s, int K)
    launch_axpby (-1.0, t, 1.0, y, (int64_t) kn, st);
 }
 
+// which = 9: values = 1 in A's order, gathered by the kernel; which = 10: gathered into the temporary behind y first
+void valprod_time_launch_trans (nkp_solver *s, int K)
+{
+   launch_values_product_trans (K, K, s->vt.T, s->vt.src, s->vp.stage, K >= 2 ? s->vp.x : s->t1, -1.0, 0, s->vp.stage + (size_t) s->A.nnz, s->n, s->stream);
+}
+
+void valprod_time_composition_trans (nkp_solver *s, int K)
+{
+   const size_t nnz = (size_t) s->A.nnz;
+   double *y = s->vp.stage + nnz, *valT = y + (size_t) K * (size_t) s->n;
+   launch_tr_gather (s->vp.stage, s->vt.src, (int64_t) nnz, valT, s->stream);
+   launch_values_product (K, K, s->vt.T, valT, K >= 2 ? s->vp.x : s->t1, -1.0, 0, y, s->n, s->stream);
+}
+
 extern "C" int nkp_values_product_device (nkp_solver *s, int nrhs, const void *d_val, const void *d_x, int64_t ldx, double alpha, int accumulate, void *d_y, int64_t ldy)
 {
    if (!s) return fail (NKP_EINVAL, "nkp_values_product_device: NULL solver (argument s)");
@@ -169,6 +267,25 @@ extern "C" int nkp_values_product (nkp_solver *s, int nrhs, const double *val, c
    if (!x) return fail (NKP_EINVAL, "nkp_values_product: NULL argument x");
    if (!y) return fail (NKP_EINVAL, "nkp_values_product: NULL argument y");
    return values_product (s, nrhs, val, x, nullptr, nullptr, ldx, alpha, accumulate, y, nullptr, ldy, "nkp_values_product");
+}
+
+extern "C" int nkp_values_product_trans_device (nkp_solver *s, int nrhs, const void *d_val, const void *d_x, int64_t ldx, double alpha, int accumulate, void *d_y, int64_t ldy)
+{
+   if (!s) return fail (NKP_EINVAL, "nkp_values_product_trans_device: NULL solver (argument s)");
+   if (!d_val) return fail (NKP_EINVAL, "nkp_values_product_trans_device: NULL argument d_val");
+   if (!d_x) return fail (NKP_EINVAL, "nkp_values_product_trans_device: NULL argument d_x");
+   if (!d_y) return fail (NKP_EINVAL, "nkp_values_product_trans_device: NULL argument d_y");
+   return values_product (s, nrhs, nullptr, nullptr, (const double *) d_val, (const double *) d_x, ldx, alpha, accumulate, nullptr, (double *) d_y, ldy,
+                          "nkp_values_product_trans_device", true);
+}
+
+extern "C" int nkp_values_product_trans (nkp_solver *s, int nrhs, const double *val, const double *x, int64_t ldx, double alpha, int accumulate, double *y, int64_t ldy)
+{
+   if (!s) return fail (NKP_EINVAL, "nkp_values_product_trans: NULL solver (argument s)");
+   if (!val) return fail (NKP_EINVAL, "nkp_values_product_trans: NULL argument val");
+   if (!x) return fail (NKP_EINVAL, "nkp_values_product_trans: NULL argument x");
+   if (!y) return fail (NKP_EINVAL, "nkp_values_product_trans: NULL argument y");
+   return values_product (s, nrhs, val, x, nullptr, nullptr, ldx, alpha, accumulate, y, nullptr, ldy, "nkp_values_product_trans", true);
 }
 
 extern "C" int nkp_solve_tangent_device (nkp_solver *s, int nrhs, const void *d_dval, const void *d_x, int64_t ldx, const void *d_db, void *d_dx, int64_t ld,

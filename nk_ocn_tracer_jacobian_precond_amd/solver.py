@@ -33,6 +33,7 @@ ABI_SYMBOLS = [
     "nkp_refactor", "nkp_refactor_device", "nkp_refactor_dist", "nkp_refactor_dist_device", "nkp_transpose", "nkp_transpose_dist",
     "nkp_value_gradient", "nkp_value_gradient_device",
     "nkp_values_product", "nkp_values_product_device", "nkp_solve_tangent_device", "nkp_matrix_array",
+    "nkp_values_product_trans", "nkp_values_product_trans_device",
 ]
 
 _ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p)
@@ -135,6 +136,8 @@ def load_library(path=None):
     lib.nkp_value_gradient_device.argtypes = [vp, C.c_int, vp, vp, C.c_int64, C.c_double, C.c_int, vp]
     lib.nkp_values_product.argtypes = [vp, C.c_int, f64p, f64p, C.c_int64, C.c_double, C.c_int, f64p, C.c_int64]
     lib.nkp_values_product_device.argtypes = [vp, C.c_int, vp, vp, C.c_int64, C.c_double, C.c_int, vp, C.c_int64]
+    lib.nkp_values_product_trans.argtypes = lib.nkp_values_product.argtypes
+    lib.nkp_values_product_trans_device.argtypes = lib.nkp_values_product_device.argtypes
     lib.nkp_solve_tangent_device.argtypes = [vp, C.c_int, vp, vp, C.c_int64, vp, vp, C.c_int64, f64p, C.POINTER(C.c_int), f64p]
     lib.nkp_refactor.argtypes = [vp, f64p, C.c_int]
     lib.nkp_refactor_device.argtypes = [vp, vp, C.c_int]
@@ -378,6 +381,15 @@ class NkpSolver:
         """nkp_values_product: Y = alpha * (the solver's pattern with the values val) X, or Y += ... when Y is given.  val: nnz
         values in the CSR order the solver was created with; X (and Y): shape (n,) or (K, n), K <= 8.  Returns Y (a new array
         of X's shape).  Only the pattern is read.  Collective on a row-distributed solver (local values and rows)."""
+        return self._values_product_host(self._lib.nkp_values_product, self._check_collective, val, X, alpha, Y)
+
+    def values_product_trans(self, val, X, alpha=1.0, Y=None):
+        """nkp_values_product_trans: Y = alpha * (the solver's pattern with the values val)^T X, or Y += ... when Y is given; val
+        stays in the CSR order the solver was created with.  Arguments and result as for values_product.  The first call builds
+        the transposed index the solver then keeps.  Not on clones, transposed handles or row-distributed solvers."""
+        return self._values_product_host(self._lib.nkp_values_product_trans, self._check, val, X, alpha, Y)
+
+    def _values_product_host(self, fn, check, val, X, alpha, Y):
         val = np.ascontiguousarray(val, np.float64).reshape(-1)
         x = np.ascontiguousarray(np.atleast_2d(np.asarray(X, np.float64)))
         if val.size != self.nnz or x.ndim != 2 or x.shape[1] != self.n:
@@ -389,9 +401,14 @@ class NkpSolver:
             if y.shape != x.shape:
                 raise ValueError("Y must have the shape of X")
         v = val if val.size else np.zeros(1)
-        self._check_collective(self._lib.nkp_values_product(self._h, x.shape[0], _p(v, C.c_double), _p(x, C.c_double), self.n, float(alpha), acc,
-                                                            _p(y, C.c_double), self.n))
+        check(fn(self._h, x.shape[0], _p(v, C.c_double), _p(x, C.c_double), self.n, float(alpha), acc, _p(y, C.c_double), self.n))
         return y.reshape(np.shape(X))
+
+    def values_product_trans_device(self, d_val, d_x, nrhs, ldx, d_y, ldy, alpha=1.0, accumulate=False):
+        """nkp_values_product_trans_device: the arguments of values_product_device, d_val still in the solver's own CSR order; d_x is
+        indexed by A's rows, d_y by A's columns."""
+        self._check(self._lib.nkp_values_product_trans_device(self._h, int(nrhs), C.c_void_p(d_val), C.c_void_p(d_x), int(ldx), float(alpha),
+                                                              int(bool(accumulate)), C.c_void_p(d_y), int(ldy)))
 
     def values_product_device(self, d_val, d_x, nrhs, ldx, d_y, ldy, alpha=1.0, accumulate=False):
         """nkp_values_product_device: d_val = integer device address of nnz float64, d_x / d_y of nrhs vectors of n float64 each

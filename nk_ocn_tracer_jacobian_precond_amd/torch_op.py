@@ -9,9 +9,23 @@ tensors) is the tangent solve nkp_solve_tangent_device: with the tangents dB and
 
     dX = A^-1 (dB - dA X),      dA = dval on the pattern of A
 
+Second and higher derivatives: the backward pass is itself written with differentiable operations.  With V the matrix that holds
+values v on A's pattern, five operations are closed under differentiation -- the backward of each is made of the others:
+
+    Solve (B, val) -> X                  backward: Lambda = SolveT (G, val); grad B = Lambda; grad val = ValueGradient (Lambda, X, -1)
+    SolveT (G, val) -> Lambda            backward: M = Solve (Lbar, val); grad G = M; grad val = ValueGradient (Lambda, M, -1)
+    ValueGradient (Lambda, X, a) -> g    backward: grad Lambda = ValuesProduct (gbar, X, a); grad X = ValuesProductT (gbar, Lambda, a)
+    ValuesProduct (v, X, a) -> a V X     backward: grad v = ValueGradient (Ybar, X, a); grad X = ValuesProductT (v, Ybar, a)
+    ValuesProductT (v, L, a) -> a V^T L  backward: grad v = ValueGradient (L, Ybar, a); grad L = ValuesProduct (v, Ybar, a)
+
+(nkp_solve_batch_device on the solver and on its transposed handle, nkp_value_gradient_device, nkp_values_product_device,
+nkp_values_product_trans_device).  torch's own graph does the rest.
+
 torch is imported when NkpTorchSolver is constructed, not when this module is: the package stays importable without it.
 """
 from __future__ import annotations
+
+from types import SimpleNamespace
 
 from . import solver as _solver
 
@@ -33,7 +47,16 @@ class NkpTorchSolver:
     The backward pass calls transposed() once -- the handle is kept by the solver and follows set_values -- and runs one
     batched solve there.  Forward mode runs one product with dval on the pattern (only when val carries a tangent) and one batched
     solve on the solver itself.  A forward, backward or tangent solve that does not converge raises NkpError: no partial
-    gradient or tangent is returned.  Double backward is not supported.
+    gradient or tangent is returned.
+
+    Second and higher derivatives are supported: torch.autograd.grad(..., create_graph=True) records the backward pass, and a
+    Hessian-vector product (the gradient of <P, B.grad> + <q, val.grad>) then costs four batched solves in all -- the forward
+    solve, the adjoint solve of the first backward, and one solve with A and one with A^T in the second -- plus products and
+    value gradients on the pattern; the first product with the transposed pattern builds the solver's transposed index
+    (nkp_values_product_trans).  Without create_graph the backward pass records nothing and costs what it did: one adjoint solve and
+    one value gradient.  An inner solve that does not converge raises NkpError from the backward that needed it.  Differentiate
+    again under the matrix values the forward solve saw: set_values between a solve and a backward through it changes the matrix
+    every later solve of that backward uses.  Forward-over-reverse (dual tensors through a backward pass) is not supported.
     """
 
     def __init__(self, solver):
@@ -44,7 +67,8 @@ class NkpTorchSolver:
         self.solver = solver
         self.values = None
         solver.set_stream(torch.cuda.current_stream().cuda_stream)
-        self._fn = _make_function(torch)
+        self._ops = _make_functions(torch)
+        self._fn = self._ops.Solve
 
     def _check(self, t, shape, what):
         torch = self.torch
@@ -66,7 +90,13 @@ class NkpTorchSolver:
         return self._fn.apply(B, val, self)
 
 
-def _make_function(torch):
+def _make_functions(torch):
+    """The five operations of the module docstring.  Each has one output and takes `owner` (the NkpTorchSolver) last; alpha is a
+    Python float.  A backward runs only the library calls whose result is asked for (needs_input_grad)."""
+
+    def value_gradient(Lam, X, alpha, owner):
+        return _ValueGradient.apply(Lam, X, alpha, owner)
+
     class _Solve(torch.autograd.Function):
         @staticmethod
         def forward(ctx, B, val, owner):
@@ -74,7 +104,7 @@ def _make_function(torch):
             X = torch.empty_like(B)
             s.solve_batch_device(B.data_ptr(), X.data_ptr(), B.shape[0], s.n)      # raises NkpError unless every column converged
             ctx.owner = owner
-            ctx.save_for_backward(X)
+            ctx.save_for_backward(X, val)
             ctx.save_for_forward(X)
             # an input without a tangent reaches jvp as None, not as zeros: a dual on B alone makes no product with the values
             # (backward has one output and runs only with a gradient for it, so it never sees None)
@@ -95,17 +125,86 @@ def _make_function(torch):
             return dX
 
         @staticmethod
-        @torch.autograd.function.once_differentiable
         def backward(ctx, G):
-            s = ctx.owner.solver
-            (X,) = ctx.saved_tensors
-            G = G.contiguous()
-            Lam = torch.empty_like(G)
-            s.transposed().solve_batch_device(G.data_ptr(), Lam.data_ptr(), G.shape[0], s.n)
-            grad_val = None
-            if ctx.needs_input_grad[1]:
-                grad_val = torch.empty(s.nnz, dtype=torch.float64, device=G.device)
-                s.value_gradient_device(Lam.data_ptr(), X.data_ptr(), G.shape[0], s.n, grad_val.data_ptr(), alpha=-1.0)
+            # a forward that saved X alone (no values to differentiate again) still gets its first derivatives
+            X, *rest = ctx.saved_tensors
+            val = rest[0] if rest else X.new_empty(0)
+            Lam = _SolveT.apply(G.contiguous(), val, ctx.owner)
+            grad_val = value_gradient(Lam, X, -1.0, ctx.owner) if ctx.needs_input_grad[1] else None
             return (Lam if ctx.needs_input_grad[0] else None), grad_val, None
 
-    return _Solve
+    class _SolveT(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, G, val, owner):
+            s = owner.solver
+            Lam = torch.empty_like(G)
+            s.transposed().solve_batch_device(G.data_ptr(), Lam.data_ptr(), G.shape[0], s.n)
+            ctx.owner = owner
+            ctx.save_for_backward(Lam, val)
+            return Lam
+
+        @staticmethod
+        def backward(ctx, Lbar):
+            Lam, val = ctx.saved_tensors
+            M = _Solve.apply(Lbar.contiguous(), val, ctx.owner)
+            grad_val = value_gradient(Lam, M, -1.0, ctx.owner) if ctx.needs_input_grad[1] else None
+            return (M if ctx.needs_input_grad[0] else None), grad_val, None
+
+    class _ValueGradient(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, Lam, X, alpha, owner):
+            s = owner.solver
+            Lam, X = Lam.contiguous(), X.contiguous()
+            g = torch.empty(s.nnz, dtype=torch.float64, device=Lam.device)
+            s.value_gradient_device(Lam.data_ptr(), X.data_ptr(), Lam.shape[0], s.n, g.data_ptr(), alpha=alpha)
+            ctx.owner, ctx.alpha = owner, alpha
+            ctx.save_for_backward(Lam, X)
+            return g
+
+        @staticmethod
+        def backward(ctx, gbar):
+            Lam, X = ctx.saved_tensors
+            gbar = gbar.contiguous()
+            grad_lam = _ValuesProduct.apply(gbar, X, ctx.alpha, ctx.owner) if ctx.needs_input_grad[0] else None
+            grad_x = _ValuesProductT.apply(gbar, Lam, ctx.alpha, ctx.owner) if ctx.needs_input_grad[1] else None
+            return grad_lam, grad_x, None, None
+
+    class _ValuesProduct(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, v, X, alpha, owner):
+            s = owner.solver
+            v, X = v.contiguous(), X.contiguous()
+            Y = torch.empty_like(X)
+            s.values_product_device(v.data_ptr(), X.data_ptr(), X.shape[0], s.n, Y.data_ptr(), s.n, alpha=alpha, accumulate=False)
+            ctx.owner, ctx.alpha = owner, alpha
+            ctx.save_for_backward(v, X)
+            return Y
+
+        @staticmethod
+        def backward(ctx, Ybar):
+            v, X = ctx.saved_tensors
+            Ybar = Ybar.contiguous()
+            grad_v = value_gradient(Ybar, X, ctx.alpha, ctx.owner) if ctx.needs_input_grad[0] else None
+            grad_x = _ValuesProductT.apply(v, Ybar, ctx.alpha, ctx.owner) if ctx.needs_input_grad[1] else None
+            return grad_v, grad_x, None, None
+
+    class _ValuesProductT(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, v, Lam, alpha, owner):
+            s = owner.solver
+            v, Lam = v.contiguous(), Lam.contiguous()
+            Y = torch.empty_like(Lam)
+            s.values_product_trans_device(v.data_ptr(), Lam.data_ptr(), Lam.shape[0], s.n, Y.data_ptr(), s.n, alpha=alpha, accumulate=False)
+            ctx.owner, ctx.alpha = owner, alpha
+            ctx.save_for_backward(v, Lam)
+            return Y
+
+        @staticmethod
+        def backward(ctx, Ybar):
+            v, Lam = ctx.saved_tensors
+            Ybar = Ybar.contiguous()
+            grad_v = value_gradient(Lam, Ybar, ctx.alpha, ctx.owner) if ctx.needs_input_grad[0] else None
+            grad_lam = _ValuesProduct.apply(v, Ybar, ctx.alpha, ctx.owner) if ctx.needs_input_grad[1] else None
+            return grad_v, grad_lam, None, None
+
+    return SimpleNamespace(Solve=_Solve, SolveT=_SolveT, ValueGradient=_ValueGradient, ValuesProduct=_ValuesProduct, ValuesProductT=_ValuesProductT)
