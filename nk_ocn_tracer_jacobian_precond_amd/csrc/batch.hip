@@ -16,69 +16,198 @@
 
 static inline int bt_grid (int64_t n) { int64_t g = (n + BT_THREADS - 1) / BT_THREADS; return (int) (g < 1 ? 1 : g > 65535 * 16 ? 65535 * 16 : g); }
 
-// ---------------------------------------------------------------- interleave / de-interleave
-// X[i * K + k] = src_k[i]; systems without a vector (src_k == NULL) contribute zeros
-struct BatchPtrs { const double *p[NKP_BATCH_MAX]; };
-struct BatchOutPtrs { double *p[NKP_BATCH_MAX]; };
+// ---------------------------------------------------------------- per-system vectors <-> the interleaved layout
+// the K per-system vectors of a launch; a system without one (NULL) reads as zeros / is not written
+template <class T>
+struct BatchVecs {
+   T *p[NKP_BATCH_MAX] = {};
+   BatchVecs () = default;
+   BatchVecs (int K, T *const *v) { for (int k = 0; k < K; k++) p[k] = v[k]; }
+};
+using BatchPtrs = BatchVecs<const double>;
+using BatchOutPtrs = BatchVecs<double>;
 
-template <int K>
+// the launch line of the K-wide glue kernels: kernel_of (k tag) names the kernel, one thread per unit of work; no work, no launch
+template <class F, class... Args>
+static void bt_launch (int K, int64_t work, hipStream_t st, F &&kernel_of, Args... args)
+{
+   if (work > 0) with_k (K, [&] (auto k) { hipLaunchKernelGGL (kernel_of (k), dim3 (bt_grid (work)), dim3 (BT_THREADS), 0, st, args...); });
+}
+
+// GATHER, rows -> K wide: out[i * K + k] = src_k[row (i)] (* scale[row (i)]), zeros for a system without a vector.
+//   INDEXED  row (i) = idx[i] (a permutation, or the rows of a message), else i
+//   SCALED   row-weighted iteration: the value times scale[row], the product rounded like launch_vmul rounds it
+//   OVERLAP  row-distributed flavour, extended rows [own | overlap]: a row >= n_own is read from the K-interleaved rows that have
+//            just arrived -- OV_SEL: the halo, at position sel[row - n_own]; OV_BLOCK: row - n_own of a receive block that holds the
+//            overlap rows alone, in the hierarchy's order (two or more rings)
+// One message row carries the K systems' values of one matrix row (8 K bytes, consecutive lanes write consecutive rows:
+// coalesced 16- / 32- / 64-byte stores), so that ONE alltoallv with K times the plan's counts serves the whole group and
+// the receiver's halo part is K-interleaved as it arrives.
+enum { OV_NONE, OV_SEL, OV_BLOCK };
+template <int K, bool INDEXED, bool SCALED, int OVERLAP>
 __global__ __launch_bounds__ (BT_THREADS)
-void interleave_kernel (BatchPtrs src, double *__restrict__ X, int64_t n)
+void gather_rows_kernel (const int *__restrict__ idx, BatchPtrs src, const double *__restrict__ scale, const double *__restrict__ ext,
+                         const int *__restrict__ sel, int64_t n_own, double *__restrict__ out, int64_t n)
 {
    const int64_t stride = (int64_t) gridDim.x * BT_THREADS;
    for (int64_t i = (int64_t) blockIdx.x * BT_THREADS + threadIdx.x; i < n; i += stride) {
+      const int64_t r = INDEXED ? (int64_t) idx[i] : i;
+      if (OVERLAP != OV_NONE && r >= n_own) {
+         const double *h = ext + (OVERLAP == OV_SEL ? (int64_t) sel[r - n_own] : r - n_own) * K;
 #pragma unroll
-      for (int k = 0; k < K; k++) X[i * K + k] = src.p[k] ? src.p[k][i] : 0.0;
+         for (int k = 0; k < K; k++) out[i * K + k] = src.p[k] ? h[k] : 0.0;
+      } else if (SCALED) {
+         const double sc = scale[r];
+#pragma unroll
+         for (int k = 0; k < K; k++) out[i * K + k] = src.p[k] ? __dmul_rn (src.p[k][r], sc) : 0.0;
+      } else {
+#pragma unroll
+         for (int k = 0; k < K; k++) out[i * K + k] = src.p[k] ? src.p[k][r] : 0.0;
+      }
    }
 }
 
-// row-weighted iteration: X[i * K + k] = src_k[i] * scale[i], the product rounded like launch_vmul rounds it
-template <int K>
+// SCATTER, K wide -> rows: dst_k[row (i)] = in[i * K + k] for the systems that want their vector (dst_k != NULL).
+//   INDEXED  row (i) = perm[i], else i
+//   WIDE     the exit of a batched cycle: z[row (i) * K + k] = in[i * K + k] as well, for every k
+//   OWN      row-distributed flavour: rows < n_own only (the correction on the overlap rows belongs to their owners)
+template <int K, bool INDEXED, bool WIDE, bool OWN>
 __global__ __launch_bounds__ (BT_THREADS)
-void interleave_scaled_kernel (BatchPtrs src, const double *__restrict__ scale, double *__restrict__ X, int64_t n)
+void scatter_rows_kernel (const int *__restrict__ perm, const double *__restrict__ in, double *__restrict__ z, BatchOutPtrs dst, int64_t n_own, int64_t n)
 {
    const int64_t stride = (int64_t) gridDim.x * BT_THREADS;
    for (int64_t i = (int64_t) blockIdx.x * BT_THREADS + threadIdx.x; i < n; i += stride) {
-      const double sc = scale[i];
+      const int64_t r = INDEXED ? (int64_t) perm[i] : i;
+      if (OWN && r >= n_own) continue;
 #pragma unroll
-      for (int k = 0; k < K; k++) X[i * K + k] = src.p[k] ? __dmul_rn (src.p[k][i], sc) : 0.0;
+      for (int k = 0; k < K; k++) {
+         if (!WIDE && !dst.p[k]) continue;
+         const double v = in[i * K + k];
+         if (WIDE) z[r * K + k] = v;
+         if (dst.p[k]) dst.p[k][r] = v;
+      }
    }
 }
 
+// ADD, z_k += p_k between two chained cycles, on the interleaved z that feeds the operator and on the systems' own vectors at once:
+// z[i * K + k] = dst_k[i] = z[i * K + k] + p[i * K + k] for the systems that take part (dst_k != NULL); the others keep their z
 template <int K>
 __global__ __launch_bounds__ (BT_THREADS)
-void deinterleave_kernel (const double *__restrict__ X, BatchOutPtrs dst, int64_t n)
+void add_split_kernel (const double *__restrict__ p, double *__restrict__ z, BatchOutPtrs dst, int64_t n)
 {
    const int64_t stride = (int64_t) gridDim.x * BT_THREADS;
    for (int64_t i = (int64_t) blockIdx.x * BT_THREADS + threadIdx.x; i < n; i += stride) {
 #pragma unroll
       for (int k = 0; k < K; k++)
-         if (dst.p[k]) dst.p[k][i] = X[i * K + k];
+         if (dst.p[k]) {
+            const double v = z[i * K + k] + p[i * K + k];
+            z[i * K + k] = v;
+            dst.p[k][i] = v;
+         }
    }
 }
 
+// X[i * K + k] = src_k[i].  This one and launch_deinterleave have always launched for n = 0 too (one block that finds nothing to
+// do), so they ask for one unit of work at least
 void launch_interleave (int K, const double *const *src, double *X, int64_t n, hipStream_t st, const double *scale)
 {
-   BatchPtrs P;
-   for (int k = 0; k < NKP_BATCH_MAX; k++) P.p[k] = k < K ? src[k] : nullptr;
-   with_k (K, [&] (auto k) {
-      if (scale) hipLaunchKernelGGL (interleave_scaled_kernel<decltype (k)::value>, dim3 (bt_grid (n)), dim3 (BT_THREADS), 0, st, P, scale, X, n);
-      else hipLaunchKernelGGL (interleave_kernel<decltype (k)::value>, dim3 (bt_grid (n)), dim3 (BT_THREADS), 0, st, P, X, n);
+   with_bool (scale != nullptr, [&] (auto scaled) {
+      bt_launch (K, n > 0 ? n : 1, st, [] (auto k) { return gather_rows_kernel<decltype (k)::value, false, decltype (scaled)::value, OV_NONE>; },
+                 nullptr, BatchPtrs (K, src), scale, nullptr, nullptr, 0, X, n);
    });
 }
-
+// out[i * K + k] = src_k[idx[i]]: the entry of a batched cycle (idx = the hierarchy's permutation), a K-wide message (idx = its rows)
+void launch_gather_interleave (int K, const int *idx, const double *const *src, double *out, int64_t n, hipStream_t st, const double *scale)
+{
+   with_bool (scale != nullptr, [&] (auto scaled) {
+      bt_launch (K, n, st, [] (auto k) { return gather_rows_kernel<decltype (k)::value, true, decltype (scaled)::value, OV_NONE>; },
+                 idx, BatchPtrs (K, src), scale, nullptr, nullptr, 0, out, n);
+   });
+}
+// the entry on the extended rows of a rank: rows perm[i] >= n_own from ext, through sel or (sel NULL) as a block of their own
+void launch_gather_interleave_ext (int K, const int *perm, const double *const *src, const double *ext, const int *sel, int64_t n_own, double *out, int64_t n,
+                                   hipStream_t st)
+{
+   with_int<OV_SEL, OV_BLOCK> (sel ? OV_SEL : OV_BLOCK, [&] (auto ov) {
+      bt_launch (K, n, st, [] (auto k) { return gather_rows_kernel<decltype (k)::value, true, false, decltype (ov)::value>; },
+                 perm, BatchPtrs (K, src), nullptr, ext, sel, n_own, out, n);
+   });
+}
 void launch_deinterleave (int K, const double *X, double *const *dst, int64_t n, hipStream_t st)
 {
-   BatchOutPtrs P;
-   for (int k = 0; k < NKP_BATCH_MAX; k++) P.p[k] = k < K ? dst[k] : nullptr;
-   with_k (K, [&] (auto k) { hipLaunchKernelGGL (deinterleave_kernel<decltype (k)::value>, dim3 (bt_grid (n)), dim3 (BT_THREADS), 0, st, X, P, n); });
+   bt_launch (K, n > 0 ? n : 1, st, [] (auto k) { return scatter_rows_kernel<decltype (k)::value, false, false, false>; }, nullptr, X, nullptr, BatchOutPtrs (K, dst), 0, n);
+}
+// the exit of a batched cycle: z[perm[i] * K + k] = dst_k[perm[i]] = in[i * K + k]; _own: on the extended rows of a rank
+void launch_scatter_split (int K, const int *perm, const double *in, double *z, double *const *dst, int64_t n, hipStream_t st)
+{
+   bt_launch (K, n, st, [] (auto k) { return scatter_rows_kernel<decltype (k)::value, true, true, false>; }, perm, in, z, BatchOutPtrs (K, dst), 0, n);
+}
+void launch_scatter_split_own (int K, const int *perm, const double *in, double *z, double *const *dst, int64_t n_own, int64_t n, hipStream_t st)
+{
+   bt_launch (K, n, st, [] (auto k) { return scatter_rows_kernel<decltype (k)::value, true, true, true>; }, perm, in, z, BatchOutPtrs (K, dst), n_own, n);
+}
+void launch_add_split (int K, const double *p, double *z, double *const *dst, int64_t n, hipStream_t st)
+{
+   bt_launch (K, n, st, [] (auto k) { return add_split_kernel<decltype (k)::value>; }, p, z, BatchOutPtrs (K, dst), n);
 }
 
 // ---------------------------------------------------------------- CSR SpMV, K columns
+// A row block that is a single long row (more than NKP_SPMV_LDS_NNZ entries): the sums of the systems 2g, 2g + 1, accumulated
+// strided and reduced over the workgroup in the order of the single-vector kernel -- wave shuffles, then wsum in fixed order.
+// Thread 0 returns the pair; the caller puts a barrier behind its use of it, before wsum is written again.
+template <class VT, int K>
+__device__ __forceinline__ double2 long_row_pair (int e0, int e1, int tid, int g, const int *__restrict__ colind, const VT *__restrict__ val,
+                                                  const double *__restrict__ x, double2 *wsum)
+{
+   double2 acc = make_double2 (0.0, 0.0);
+   for (int e = e0 + tid; e < e1; e += BT_THREADS) {
+      const double v = (double) val[e];
+      const double2 xv = *reinterpret_cast<const double2 *> (x + (int64_t) colind[e] * K + 2 * g);
+      acc.x += v * xv.x;
+      acc.y += v * xv.y;
+   }
+   for (int off = NKP_WAVE / 2; off > 0; off >>= 1) { acc.x += __shfl_down (acc.x, off); acc.y += __shfl_down (acc.y, off); }
+   if ((tid & (NKP_WAVE - 1)) == 0) wsum[tid / NKP_WAVE] = acc;
+   __syncthreads ();
+   double2 s = make_double2 (0.0, 0.0);
+   if (tid == 0)
+      for (int w = 0; w < BT_WAVES; w++) { s.x += wsum[w].x; s.y += wsum[w].y; }
+   return s;
+}
+
+// The end of row r for the systems 2g, 2g + 1, the same text behind every sum of both kernels below.
+// MODE 0: y = A x   1: y = b - A x
+// SPLIT: the results go to the systems' own vectors (split.p[k][r]; NULL = dropped) instead of the interleaved y, and with MODE 1
+// the right-hand side comes from per-system vectors too (bsplit.p[k][r]; NULL = zero).
+// SCALED (row-weighted iteration): MODE 0 multiplies the finished sum by scale[r]; MODE 1 + SPLIT multiplies the right-hand side
+// it reads by scale[r].  Either is ONE rounded multiplication of a finished value, which is what launch_vmul does.
+// pair_rhs is the right-hand side finish_pair subtracts from (MODE 1; zero otherwise), read apart from it because the rows kernel
+// requests it ahead of its gathers.
+template <int MODE, bool SPLIT, bool SCALED, int K>
+__device__ __forceinline__ double2 pair_rhs (int64_t r, int g, const double *__restrict__ b, BatchPtrs bsplit, const double *__restrict__ scale)
+{
+   double2 bv = make_double2 (0.0, 0.0);
+   if (MODE == 1 && SPLIT) {
+      if (bsplit.p[2 * g]) bv.x = bsplit.p[2 * g][r];
+      if (bsplit.p[2 * g + 1]) bv.y = bsplit.p[2 * g + 1][r];
+      if (SCALED) { const double sc = scale[r]; bv.x = __dmul_rn (bv.x, sc); bv.y = __dmul_rn (bv.y, sc); }
+   } else if (MODE == 1) bv = *reinterpret_cast<const double2 *> (b + r * K + 2 * g);
+   return bv;
+}
+template <int MODE, bool SPLIT, bool SCALED, int K>
+__device__ __forceinline__ void finish_pair (double2 s, double2 bv /* pair_rhs */, int64_t r, int g, const double *__restrict__ scale, double *__restrict__ y,
+                                             BatchOutPtrs split)
+{
+   static_assert (!(MODE == 1 && SCALED && !SPLIT), "b - A x is scaled through its right-hand side, which only the split form reads scaled");
+   if (MODE == 1) { s.x = bv.x - s.x; s.y = bv.y - s.y; }
+   else if (SCALED) { const double sc = scale[r]; s.x = __dmul_rn (s.x, sc); s.y = __dmul_rn (s.y, sc); }
+   if (SPLIT) { if (split.p[2 * g]) split.p[2 * g][r] = s.x; if (split.p[2 * g + 1]) split.p[2 * g + 1][r] = s.y; }
+   else *reinterpret_cast<double2 *> (y + r * K + 2 * g) = s;
+}
+
 // csr_spmv_stream_kernel (spmv.hip) with the (value, column) stream of a row block read ONCE into registers and K / 2 passes
 // over it: a pass gathers the 16-byte pair (x[c][2g], x[c][2g + 1]), parks both products in LDS and sums every row's segment
-// in stored order.  MODE 0: y = A x   1: y = b - A x
-// SCALED (MODE 0, row-weighted iteration): every finished sum times scale[row], one rounded multiplication like launch_vmul's
+// in stored order.  MODE and SCALED (MODE 0 only) as in finish_pair; vectors interleaved on both sides.
 template <int MODE, class VT, int K, bool SCALED = false>
 __global__ __launch_bounds__ (BT_THREADS)
 void csr_spmv_batch_kernel (const int *__restrict__ rowblk_all, int rb0, int nrowblk, int per_xcd, const int *__restrict__ rowptr,
@@ -99,25 +228,9 @@ void csr_spmv_batch_kernel (const int *__restrict__ rowblk_all, int rb0, int nro
    int seg0 = 0, seg1 = 0;
    if (r0 + tid < r1) { seg0 = rowptr[r0 + tid]; seg1 = rowptr[r0 + tid + 1]; }
    if (cnt > NKP_SPMV_LDS_NNZ) {
-      // a single long row: strided accumulate + block reduction in the order of the single-vector kernel
       for (int g = 0; g < K / 2; g++) {
-         double2 acc = make_double2 (0.0, 0.0);
-         for (int e = e0 + tid; e < e1; e += BT_THREADS) {
-            const double v = (double) val[e];
-            const double2 xv = *reinterpret_cast<const double2 *> (x + (int64_t) colind[e] * K + 2 * g);
-            acc.x += v * xv.x;
-            acc.y += v * xv.y;
-         }
-         for (int off = NKP_WAVE / 2; off > 0; off >>= 1) { acc.x += __shfl_down (acc.x, off); acc.y += __shfl_down (acc.y, off); }
-         if ((tid & (NKP_WAVE - 1)) == 0) wsum[tid / NKP_WAVE] = acc;
-         __syncthreads ();
-         if (tid == 0) {
-            double2 s = make_double2 (0.0, 0.0);
-            for (int w = 0; w < BT_WAVES; w++) { s.x += wsum[w].x; s.y += wsum[w].y; }
-            if (MODE == 1) { const double2 bv = *reinterpret_cast<const double2 *> (b + (int64_t) r0 * K + 2 * g); s.x = bv.x - s.x; s.y = bv.y - s.y; }
-            if (SCALED) { const double sc = scale[r0]; s.x = __dmul_rn (s.x, sc); s.y = __dmul_rn (s.y, sc); }
-            *reinterpret_cast<double2 *> (y + (int64_t) r0 * K + 2 * g) = s;
-         }
+         const double2 s = long_row_pair<VT, K> (e0, e1, tid, g, colind, val, x, wsum);
+         if (tid == 0) finish_pair<MODE, false, SCALED, K> (s, pair_rhs<MODE, false, SCALED, K> (r0, g, b, BatchPtrs (), scale), r0, g, scale, y, BatchOutPtrs ());
          __syncthreads ();
       }
       return;
@@ -154,9 +267,7 @@ void csr_spmv_batch_kernel (const int *__restrict__ rowblk_all, int rb0, int nro
          double2 acc = make_double2 (0.0, 0.0);
 #pragma unroll 4
          for (int k = s0; k < s1; k++) { acc.x += prod[k].x; acc.y += prod[k].y; }
-         if (MODE == 1) { const double2 bv = *reinterpret_cast<const double2 *> (b + (int64_t) r * K + 2 * g); acc.x = bv.x - acc.x; acc.y = bv.y - acc.y; }
-         if (SCALED) { const double sc = scale[r]; acc.x = __dmul_rn (acc.x, sc); acc.y = __dmul_rn (acc.y, sc); }
-         *reinterpret_cast<double2 *> (y + (int64_t) r * K + 2 * g) = acc;
+         finish_pair<MODE, false, SCALED, K> (acc, pair_rhs<MODE, false, SCALED, K> (r, g, b, BatchPtrs (), scale), r, g, scale, y, BatchOutPtrs ());
       }
       if (g + 1 < K / 2) __syncthreads ();
    }
@@ -166,11 +277,8 @@ void csr_spmv_batch_kernel (const int *__restrict__ rowblk_all, int rb0, int nro
 // entry instead of 16 K of products: 16 KB per workgroup, twice the workgroups per CU), then every row's lane walks its own
 // segment, gathers the K-wide rows of x itself (GU entries in flight) and accumulates its K sums in registers -- same
 // products, same stored order, one pass for any K.
-// SPLIT: the K results of a row go to K separate vectors (split.p[k][r]; NULL = dropped) instead of the interleaved y -- the
-// operator product at the end of an Arnoldi step writes every system's w directly.  With MODE 1 the right-hand side is split
-// too (bsplit.p[k][r]; NULL = zero): the residual between two chained cycles, p1_k = v_k - A z_k, from and to per-system vectors.
-// SCALED (row-weighted iteration): MODE 0 multiplies every finished sum by scale[row]; MODE 1 + SPLIT multiplies the right-hand
-// side it reads by scale[row].  Either is ONE rounded multiplication of a finished value, which is what launch_vmul does.
+// SPLIT (finish_pair): the operator product at the end of an Arnoldi step writes every system's w directly; with MODE 1, the
+// residual between two chained cycles, p1_k = v_k - A z_k, from and to per-system vectors.
 template <int MODE, class VT, int K, bool SPLIT = false, bool SCALED = false>
 __global__ __launch_bounds__ (BT_THREADS)
 void csr_spmv_batch_rows_kernel (const int *__restrict__ rowblk_all, int rb0, int nrowblk, int per_xcd, const int *__restrict__ rowptr,
@@ -192,31 +300,8 @@ void csr_spmv_batch_rows_kernel (const int *__restrict__ rowblk_all, int rb0, in
    const int cnt = e1 - e0;
    if (cnt > NKP_SPMV_LDS_NNZ) {
       for (int g = 0; g < K / 2; g++) {
-         double2 acc = make_double2 (0.0, 0.0);
-         for (int e = e0 + tid; e < e1; e += BT_THREADS) {
-            const double v = (double) val[e];
-            const double2 xv = *reinterpret_cast<const double2 *> (x + (int64_t) colind[e] * K + 2 * g);
-            acc.x += v * xv.x;
-            acc.y += v * xv.y;
-         }
-         for (int off = NKP_WAVE / 2; off > 0; off >>= 1) { acc.x += __shfl_down (acc.x, off); acc.y += __shfl_down (acc.y, off); }
-         if ((tid & (NKP_WAVE - 1)) == 0) wsum[tid / NKP_WAVE] = acc;
-         __syncthreads ();
-         if (tid == 0) {
-            double2 s = make_double2 (0.0, 0.0);
-            for (int w = 0; w < BT_WAVES; w++) { s.x += wsum[w].x; s.y += wsum[w].y; }
-            if (MODE == 1) {
-               double2 bv;
-               if (SPLIT) {
-                  bv.x = bsplit.p[2 * g] ? bsplit.p[2 * g][r0] : 0.0;
-                  bv.y = bsplit.p[2 * g + 1] ? bsplit.p[2 * g + 1][r0] : 0.0;
-                  if (SCALED) { const double sc = scale[r0]; bv.x = __dmul_rn (bv.x, sc); bv.y = __dmul_rn (bv.y, sc); }
-               } else bv = *reinterpret_cast<const double2 *> (b + (int64_t) r0 * K + 2 * g);
-               s.x = bv.x - s.x; s.y = bv.y - s.y;
-            } else if (SCALED) { const double sc = scale[r0]; s.x = __dmul_rn (s.x, sc); s.y = __dmul_rn (s.y, sc); }
-            if (SPLIT) { if (split.p[2 * g]) split.p[2 * g][r0] = s.x; if (split.p[2 * g + 1]) split.p[2 * g + 1][r0] = s.y; }
-            else *reinterpret_cast<double2 *> (y + (int64_t) r0 * K + 2 * g) = s;
-         }
+         const double2 s = long_row_pair<VT, K> (e0, e1, tid, g, colind, val, x, wsum);
+         if (tid == 0) finish_pair<MODE, SPLIT, SCALED, K> (s, pair_rhs<MODE, SPLIT, SCALED, K> (r0, g, b, bsplit, scale), r0, g, scale, y, split);
          __syncthreads ();
       }
       return;
@@ -243,13 +328,7 @@ void csr_spmv_batch_rows_kernel (const int *__restrict__ rowblk_all, int rb0, in
 #pragma unroll
    for (int g = 0; g < K / 2; g++) {
       bv[g] = make_double2 (0.0, 0.0);
-      if (MODE == 1 && r < r1) {
-         if (SPLIT) {
-            if (bsplit.p[2 * g]) bv[g].x = bsplit.p[2 * g][r];
-            if (bsplit.p[2 * g + 1]) bv[g].y = bsplit.p[2 * g + 1][r];
-            if (SCALED) { const double sc = scale[r]; bv[g].x = __dmul_rn (bv[g].x, sc); bv[g].y = __dmul_rn (bv[g].y, sc); }
-         } else bv[g] = *reinterpret_cast<const double2 *> (b + (int64_t) r * K + 2 * g);
-      }
+      if (MODE == 1 && r < r1) bv[g] = pair_rhs<MODE, SPLIT, SCALED, K> (r, g, b, bsplit, scale);       // requested ahead of the gathers
    }
    __syncthreads ();
    if (r >= r1) return;
@@ -275,12 +354,7 @@ void csr_spmv_batch_rows_kernel (const int *__restrict__ rowblk_all, int rb0, in
          }
    }
 #pragma unroll
-   for (int g = 0; g < K / 2; g++) {
-      if (MODE == 1) { acc[g].x = bv[g].x - acc[g].x; acc[g].y = bv[g].y - acc[g].y; }
-      else if (SCALED) { const double sc = scale[r]; acc[g].x = __dmul_rn (acc[g].x, sc); acc[g].y = __dmul_rn (acc[g].y, sc); }
-      if (SPLIT) { if (split.p[2 * g]) split.p[2 * g][r] = acc[g].x; if (split.p[2 * g + 1]) split.p[2 * g + 1][r] = acc[g].y; }
-      else *reinterpret_cast<double2 *> (y + (int64_t) r * K + 2 * g) = acc[g];
-   }
+   for (int g = 0; g < K / 2; g++) finish_pair<MODE, SPLIT, SCALED, K> (acc[g], bv[g], r, g, scale, y, split);
 }
 
 // csr_spmv_batch_rows_kernel<MODE, storage of A, K, SPLIT, SCALED> on the row blocks [rb0, rb0 + cnt) of A
@@ -329,15 +403,9 @@ void launch_csr_spmv_batch (int K, const CsrDev &A, int rb0, int rb1, const doub
 void launch_csr_spmv_batch_split_range (int K, const CsrDev &A, int rb0, int rb1, const double *x, double *const *dst, hipStream_t st, const double *scale)
 {
    if (rb1 <= rb0) return;
-   BatchOutPtrs P;
-   for (int k = 0; k < NKP_BATCH_MAX; k++) P.p[k] = k < K ? dst[k] : nullptr;
+   const BatchOutPtrs P (K, dst);
    if (scale) launch_batch_rows<0, true, true> (K, A, rb0, rb1 - rb0, x, nullptr, nullptr, P, BatchPtrs (), scale, st);
    else launch_batch_rows<0, true, false> (K, A, rb0, rb1 - rb0, x, nullptr, nullptr, P, BatchPtrs (), nullptr, st);
-}
-
-void launch_csr_spmv_batch_split (int K, const CsrDev &A, const double *x, double *const *dst, hipStream_t st, const double *scale)
-{
-   launch_csr_spmv_batch_split_range (K, A, 0, A.nrowblk, x, dst, st, scale);
 }
 
 // dst_k = b_k - A x_k (b_k, times bscale when given, and dst_k per system; NULL: system takes no part), row blocks [rb0, rb1)
@@ -345,9 +413,8 @@ void launch_csr_residual_batch_split_range (int K, const CsrDev &A, int rb0, int
                                             double *const *dst, hipStream_t st)
 {
    if (rb1 <= rb0) return;
-   BatchOutPtrs P;
-   BatchPtrs Q;
-   for (int k = 0; k < NKP_BATCH_MAX; k++) { P.p[k] = k < K ? dst[k] : nullptr; Q.p[k] = k < K ? b[k] : nullptr; }
+   const BatchOutPtrs P (K, dst);
+   const BatchPtrs Q (K, b);
    if (bscale) launch_batch_rows<1, true, true> (K, A, rb0, rb1 - rb0, x, nullptr, nullptr, P, Q, bscale, st);
    else launch_batch_rows<1, true, false> (K, A, rb0, rb1 - rb0, x, nullptr, nullptr, P, Q, bscale, st);
 }
@@ -385,145 +452,6 @@ void gather_batch_kernel (const int *__restrict__ perm, const double *__restrict
       out[t] = in[(int64_t) perm[t / K] * K + (t % K)];
 }
 
-// the entry and the exit of a batched cycle application, fused with the (de-)interleave of the per-system vectors:
-//   entry: out[i * K + k] = src_k[perm[i]]        exit: z[perm[i] * K + k] = dst_k[perm[i]] = in[i * K + k]
-template <int K>
-__global__ __launch_bounds__ (BT_THREADS)
-void gather_interleave_kernel (const int *__restrict__ perm, BatchPtrs src, double *__restrict__ out, int64_t n)
-{
-   const int64_t stride = (int64_t) gridDim.x * BT_THREADS;
-   for (int64_t i = (int64_t) blockIdx.x * BT_THREADS + threadIdx.x; i < n; i += stride) {
-      const int64_t pi = perm[i];
-#pragma unroll
-      for (int k = 0; k < K; k++) out[i * K + k] = src.p[k] ? src.p[k][pi] : 0.0;
-   }
-}
-
-// the entry in the row-weighted iteration: out[i * K + k] = src_k[perm[i]] * scale[perm[i]] (launch_vmul's product, then the gather)
-template <int K>
-__global__ __launch_bounds__ (BT_THREADS)
-void gather_interleave_scaled_kernel (const int *__restrict__ perm, BatchPtrs src, const double *__restrict__ scale, double *__restrict__ out, int64_t n)
-{
-   const int64_t stride = (int64_t) gridDim.x * BT_THREADS;
-   for (int64_t i = (int64_t) blockIdx.x * BT_THREADS + threadIdx.x; i < n; i += stride) {
-      const int64_t pi = perm[i];
-      const double sc = scale[pi];
-#pragma unroll
-      for (int k = 0; k < K; k++) out[i * K + k] = src.p[k] ? __dmul_rn (src.p[k][pi], sc) : 0.0;
-   }
-}
-
-// z_k += p_k between two chained cycles, on the interleaved z that feeds the operator and on the systems' own vectors at once:
-// z[i * K + k] = dst_k[i] = z[i * K + k] + p[i * K + k] for the systems that take part (dst_k != NULL); the others keep their z
-template <int K>
-__global__ __launch_bounds__ (BT_THREADS)
-void add_split_kernel (const double *__restrict__ p, double *__restrict__ z, BatchOutPtrs dst, int64_t n)
-{
-   const int64_t stride = (int64_t) gridDim.x * BT_THREADS;
-   for (int64_t i = (int64_t) blockIdx.x * BT_THREADS + threadIdx.x; i < n; i += stride) {
-#pragma unroll
-      for (int k = 0; k < K; k++)
-         if (dst.p[k]) {
-            const double v = z[i * K + k] + p[i * K + k];
-            z[i * K + k] = v;
-            dst.p[k][i] = v;
-         }
-   }
-}
-
-template <int K>
-__global__ __launch_bounds__ (BT_THREADS)
-void scatter_split_kernel (const int *__restrict__ perm, const double *__restrict__ in, double *__restrict__ z, BatchOutPtrs dst, int64_t n)
-{
-   const int64_t stride = (int64_t) gridDim.x * BT_THREADS;
-   for (int64_t i = (int64_t) blockIdx.x * BT_THREADS + threadIdx.x; i < n; i += stride) {
-      const int64_t pi = perm[i];
-#pragma unroll
-      for (int k = 0; k < K; k++) {
-         const double v = in[i * K + k];
-         z[pi * K + k] = v;
-         if (dst.p[k]) dst.p[k][pi] = v;
-      }
-   }
-}
-
-// ---------------------------------------------------------------- row-distributed flavour: K-wide messages and the overlap rows
-// One message row carries the K systems' values of one matrix row (8 K bytes, consecutive lanes write consecutive rows:
-// coalesced 16- / 32- / 64-byte stores), so that ONE alltoallv with K times the plan's counts serves the whole group and
-// the receiver's halo part is K-interleaved as it arrives.
-//   out[i * K + k] = src_k[idx[i]]   (a system without a vector sends zeros)
-template <int K>
-__global__ __launch_bounds__ (BT_THREADS)
-void pack_rows_split_kernel (const int *__restrict__ idx, BatchPtrs src, double *__restrict__ out, int64_t nrows)
-{
-   const int64_t stride = (int64_t) gridDim.x * BT_THREADS;
-   for (int64_t i = (int64_t) blockIdx.x * BT_THREADS + threadIdx.x; i < nrows; i += stride) {
-      const int64_t r = idx[i];
-#pragma unroll
-      for (int k = 0; k < K; k++) out[i * K + k] = src.p[k] ? src.p[k][r] : 0.0;
-   }
-}
-
-// gather_interleave_kernel on the extended rows [own rows | overlap rows] of a rank's hierarchy: row perm[i] < n_own comes
-// from the systems' own vectors, the others from the K-interleaved halo rows that have just arrived (sel[.] = halo position)
-template <int K>
-__global__ __launch_bounds__ (BT_THREADS)
-void gather_interleave_ext_kernel (const int *__restrict__ perm, BatchPtrs src, const double *__restrict__ halo, const int *__restrict__ sel,
-                                   int64_t n_own, double *__restrict__ out, int64_t n)
-{
-   const int64_t stride = (int64_t) gridDim.x * BT_THREADS;
-   for (int64_t i = (int64_t) blockIdx.x * BT_THREADS + threadIdx.x; i < n; i += stride) {
-      const int64_t pi = perm[i];
-      if (pi < n_own) {
-#pragma unroll
-         for (int k = 0; k < K; k++) out[i * K + k] = src.p[k] ? src.p[k][pi] : 0.0;
-      } else {
-         const double *h = halo + (int64_t) sel[pi - n_own] * K;
-#pragma unroll
-         for (int k = 0; k < K; k++) out[i * K + k] = src.p[k] ? h[k] : 0.0;
-      }
-   }
-}
-
-// the same when the overlap rows arrive on their own, in the hierarchy's order (two or more rings): row perm[i] >= n_own is
-// row perm[i] - n_own of the K-interleaved receive block
-template <int K>
-__global__ __launch_bounds__ (BT_THREADS)
-void gather_interleave_ext_block_kernel (const int *__restrict__ perm, BatchPtrs src, const double *__restrict__ recv, int64_t n_own,
-                                         double *__restrict__ out, int64_t n)
-{
-   const int64_t stride = (int64_t) gridDim.x * BT_THREADS;
-   for (int64_t i = (int64_t) blockIdx.x * BT_THREADS + threadIdx.x; i < n; i += stride) {
-      const int64_t pi = perm[i];
-      if (pi < n_own) {
-#pragma unroll
-         for (int k = 0; k < K; k++) out[i * K + k] = src.p[k] ? src.p[k][pi] : 0.0;
-      } else {
-         const double *h = recv + (pi - n_own) * K;
-#pragma unroll
-         for (int k = 0; k < K; k++) out[i * K + k] = src.p[k] ? h[k] : 0.0;
-      }
-   }
-}
-
-// scatter_split_kernel that keeps the own rows only (the correction on the overlap rows belongs to their owners)
-template <int K>
-__global__ __launch_bounds__ (BT_THREADS)
-void scatter_split_own_kernel (const int *__restrict__ perm, const double *__restrict__ in, double *__restrict__ z, BatchOutPtrs dst, int64_t n_own, int64_t n)
-{
-   const int64_t stride = (int64_t) gridDim.x * BT_THREADS;
-   for (int64_t i = (int64_t) blockIdx.x * BT_THREADS + threadIdx.x; i < n; i += stride) {
-      const int64_t pi = perm[i];
-      if (pi >= n_own) continue;
-#pragma unroll
-      for (int k = 0; k < K; k++) {
-         const double v = in[i * K + k];
-         z[pi * K + k] = v;
-         if (dst.p[k]) dst.p[k][pi] = v;
-      }
-   }
-}
-
 // one wave per output row, the K columns one after the other (each summed like dense_matvec_kernel sums its one)
 template <int K>
 __global__ __launch_bounds__ (BT_THREADS)
@@ -551,75 +479,23 @@ void dense_matvec_batch_kernel (const double *__restrict__ M, const double *__re
 
 void launch_restrict_sum_batch (int K, const int *rptr, const int *ridx, const double *fine, double *coarse, int64_t nc, hipStream_t st)
 {
-   if (nc > 0) with_k (K, [&] (auto k) { hipLaunchKernelGGL (restrict_sum_batch_kernel<decltype (k)::value>, dim3 (bt_grid (nc * K)), dim3 (BT_THREADS), 0, st, rptr, ridx, fine, coarse, nc); });
+   bt_launch (K, nc * K, st, [] (auto k) { return restrict_sum_batch_kernel<decltype (k)::value>; }, rptr, ridx, fine, coarse, nc);
 }
 void launch_prolong_add_batch (int K, const int *cmap, const double *coarse, double *fine, int64_t nf, double omega, hipStream_t st)
 {
-   if (nf > 0) with_k (K, [&] (auto k) { hipLaunchKernelGGL (prolong_add_batch_kernel<decltype (k)::value>, dim3 (bt_grid (nf * K)), dim3 (BT_THREADS), 0, st, cmap, coarse, fine, nf, omega); });
+   bt_launch (K, nf * K, st, [] (auto k) { return prolong_add_batch_kernel<decltype (k)::value>; }, cmap, coarse, fine, nf, omega);
 }
 void launch_gather_batch (int K, const int *perm, const double *in, double *out, int64_t n, hipStream_t st)
 {
-   if (n > 0) with_k (K, [&] (auto k) { hipLaunchKernelGGL (gather_batch_kernel<decltype (k)::value>, dim3 (bt_grid (n * K)), dim3 (BT_THREADS), 0, st, perm, in, out, n); });
-}
-void launch_gather_interleave (int K, const int *perm, const double *const *src, double *out, int64_t n, hipStream_t st, const double *scale)
-{
-   BatchPtrs P;
-   for (int k = 0; k < NKP_BATCH_MAX; k++) P.p[k] = k < K ? src[k] : nullptr;
-   if (n <= 0) return;
-   if (scale) with_k (K, [&] (auto k) { hipLaunchKernelGGL (gather_interleave_scaled_kernel<decltype (k)::value>, dim3 (bt_grid (n)), dim3 (BT_THREADS), 0, st, perm, P, scale, out, n); });
-   else with_k (K, [&] (auto k) { hipLaunchKernelGGL (gather_interleave_kernel<decltype (k)::value>, dim3 (bt_grid (n)), dim3 (BT_THREADS), 0, st, perm, P, out, n); });
-}
-void launch_add_split (int K, const double *p, double *z, double *const *dst, int64_t n, hipStream_t st)
-{
-   BatchOutPtrs P;
-   for (int k = 0; k < NKP_BATCH_MAX; k++) P.p[k] = k < K ? dst[k] : nullptr;
-   if (n > 0) with_k (K, [&] (auto k) { hipLaunchKernelGGL (add_split_kernel<decltype (k)::value>, dim3 (bt_grid (n)), dim3 (BT_THREADS), 0, st, p, z, P, n); });
-}
-void launch_scatter_split (int K, const int *perm, const double *in, double *z, double *const *dst, int64_t n, hipStream_t st)
-{
-   BatchOutPtrs P;
-   for (int k = 0; k < NKP_BATCH_MAX; k++) P.p[k] = k < K ? dst[k] : nullptr;
-   if (n > 0) with_k (K, [&] (auto k) { hipLaunchKernelGGL (scatter_split_kernel<decltype (k)::value>, dim3 (bt_grid (n)), dim3 (BT_THREADS), 0, st, perm, in, z, P, n); });
-}
-void launch_pack_rows_split (int K, const int *idx, const double *const *src, double *out, int64_t nrows, hipStream_t st)
-{
-   BatchPtrs P;
-   for (int k = 0; k < NKP_BATCH_MAX; k++) P.p[k] = k < K ? src[k] : nullptr;
-   if (nrows > 0) with_k (K, [&] (auto k) { hipLaunchKernelGGL (pack_rows_split_kernel<decltype (k)::value>, dim3 (bt_grid (nrows)), dim3 (BT_THREADS), 0, st, idx, P, out, nrows); });
-}
-void launch_gather_interleave_ext (int K, const int *perm, const double *const *src, const double *halo, const int *sel, int64_t n_own, double *out, int64_t n,
-                                   hipStream_t st)
-{
-   BatchPtrs P;
-   for (int k = 0; k < NKP_BATCH_MAX; k++) P.p[k] = k < K ? src[k] : nullptr;
-   if (n > 0) with_k (K, [&] (auto k) { hipLaunchKernelGGL (gather_interleave_ext_kernel<decltype (k)::value>, dim3 (bt_grid (n)), dim3 (BT_THREADS), 0, st, perm, P, halo, sel, n_own, out, n); });
-}
-void launch_gather_interleave_ext_block (int K, const int *perm, const double *const *src, const double *recv, int64_t n_own, double *out, int64_t n, hipStream_t st)
-{
-   BatchPtrs P;
-   for (int k = 0; k < NKP_BATCH_MAX; k++) P.p[k] = k < K ? src[k] : nullptr;
-   if (n > 0) with_k (K, [&] (auto k) { hipLaunchKernelGGL (gather_interleave_ext_block_kernel<decltype (k)::value>, dim3 (bt_grid (n)), dim3 (BT_THREADS), 0, st, perm, P, recv, n_own, out, n); });
-}
-void launch_scatter_split_own (int K, const int *perm, const double *in, double *z, double *const *dst, int64_t n_own, int64_t n, hipStream_t st)
-{
-   BatchOutPtrs P;
-   for (int k = 0; k < NKP_BATCH_MAX; k++) P.p[k] = k < K ? dst[k] : nullptr;
-   if (n > 0) with_k (K, [&] (auto k) { hipLaunchKernelGGL (scatter_split_own_kernel<decltype (k)::value>, dim3 (bt_grid (n)), dim3 (BT_THREADS), 0, st, perm, in, z, P, n_own, n); });
+   bt_launch (K, n * K, st, [] (auto k) { return gather_batch_kernel<decltype (k)::value>; }, perm, in, out, n);
 }
 void launch_dense_matvec_batch (int K, const double *Minv, const double *x, double *y, int n, hipStream_t st)
 {
+   // a wave per row and no stride in the kernel: the grid is not clamped like bt_launch's
    if (n > 0) with_k (K, [&] (auto k) { hipLaunchKernelGGL (dense_matvec_batch_kernel<decltype (k)::value>, dim3 ((n + BT_WAVES - 1) / BT_WAVES), dim3 (BT_THREADS), 0, st, Minv, x, y, n); });
 }
 
 // ---------------------------------------------------------------- water columns, one per wave, K columns of right-hand sides
-__device__ __forceinline__ double bt_readlane_f64 (double v, int lane)
-{
-   int lo = __double2loint (v), hi = __double2hiint (v);
-   lo = __builtin_amdgcn_readlane (lo, lane);
-   hi = __builtin_amdgcn_readlane (hi, lane);
-   return __hiloint2double (hi, lo);
-}
-
 // band substitution of colblock_apply_kernel on K right-hand sides held in y[s][k] (lane = level, s = second register set of
 // columns longer than a wave); identical operations per column, the K chains interleave in the pipeline
 template <int P, int RPL, int K>
@@ -634,7 +510,7 @@ __device__ __forceinline__ void wave_band_solve (int len, int lane, double (&y)[
       for (int s = 0; s < RPL; s++)
          if (ks == s) {
 #pragma unroll
-            for (int q = 0; q < K; q++) yk[q] = bt_readlane_f64 (y[s][q], kl);
+            for (int q = 0; q < K; q++) yk[q] = readlane_f64 (y[s][q], kl);
          }
 #pragma unroll
       for (int s = 0; s < RPL; s++) {
@@ -658,7 +534,7 @@ __device__ __forceinline__ void wave_band_solve (int len, int lane, double (&y)[
 #pragma unroll
             for (int q = 0; q < K; q++) {
                if (lane == kl) y[s][q] *= invd[s];
-               xk[q] = bt_readlane_f64 (y[s][q], kl);
+               xk[q] = readlane_f64 (y[s][q], kl);
             }
          }
 #pragma unroll
@@ -674,6 +550,8 @@ __device__ __forceinline__ void wave_band_solve (int len, int lane, double (&y)[
    }
 }
 
+// the factors of the rows a lane holds, as the band solve takes them (colblock_apply_kernel and gs_wave_kernel load theirs in the
+// loop that loads their one right-hand side; taking this function there changes their code)
 template <int P, int RPL, bool R32>
 __device__ __forceinline__ void wave_load_factors (int64_t n, int64_t r0, int len, int lane, const double *__restrict__ fac, double (&invd)[RPL], double (&L)[RPL][P], double (&U)[RPL][P])
 {

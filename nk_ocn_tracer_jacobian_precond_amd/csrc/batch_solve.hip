@@ -125,7 +125,7 @@ static void batch_precond (nkp_solver *s, int K, const double *const *src, const
       // several rings: the overlap rows alone, K wide, in the hierarchy's order; one ring: the SpMV's halo, picked from by sel_idx
       RowExchange &X = D.ras_sep ? D.x_ras : D.x_halo;
       double *ext = D.ras_sep ? X.recv_for (K) : halo_rows_of (s, K);
-      if (X.nsend) launch_pack_rows_split (K, X.send_idx, src, X.send_for (K), X.nsend, st);
+      launch_gather_interleave (K, X.send_idx, src, X.send_for (K), X.nsend, st);
       exchange_rows (s, X, K, X.send_for (K), ext, st);
       ml_apply_batch_split_ext (s->ml, K, src, ext, D.ras_sep ? nullptr : D.sel_idx, n, zi, dz ? dz : none, st, smooth_hook_of (s));
    } else if (s->opt.precond == NKP_PRECOND_MULTILEVEL) {

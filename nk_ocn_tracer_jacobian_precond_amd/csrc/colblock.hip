@@ -21,14 +21,6 @@
 #define CB_THREADS 256
 #define CB_WAVES (CB_THREADS / NKP_WAVE)
 
-__device__ __forceinline__ double readlane_f64 (double v, int lane)
-{
-   int lo = __double2loint (v), hi = __double2hiint (v);
-   lo = __builtin_amdgcn_readlane (lo, lane);
-   hi = __builtin_amdgcn_readlane (hi, lane);
-   return __hiloint2double (hi, lo);
-}
-
 __device__ __forceinline__ int wave_block_id ()
 {
    // wave-uniform by construction; readfirstlane tells the compiler so (scalar loads, SGPR loop bounds)

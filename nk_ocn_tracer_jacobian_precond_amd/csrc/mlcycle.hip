@@ -294,8 +294,7 @@ void ml_apply_batch_split_ext (MlHierarchy &H, int K, const double *const *src, 
                                double *const *dst, hipStream_t st, const MlSmoothHook *hook)
 {
    MlLevel &V = H.lev[0];
-   if (sel) launch_gather_interleave_ext (K, H.perm0, src, halo, sel, n_own, V.wide.b, V.n, st);
-   else launch_gather_interleave_ext_block (K, H.perm0, src, halo, n_own, V.wide.b, V.n, st);
+   launch_gather_interleave_ext (K, H.perm0, src, halo, sel, n_own, V.wide.b, V.n, st);
    H.hook = hook;
    ml_cycle (H, K, 0, st);
    H.hook = nullptr;

@@ -206,6 +206,15 @@ __device__ __forceinline__ double readlane_const_f64 (double v)
    return __hiloint2double (hi, lo);
 }
 
+// the same for a wave-uniform lane that is no constant
+__device__ __forceinline__ double readlane_f64 (double v, int lane)
+{
+   int lo = __double2loint (v), hi = __double2hiint (v);
+   lo = __builtin_amdgcn_readlane (lo, lane);
+   hi = __builtin_amdgcn_readlane (hi, lane);
+   return __hiloint2double (hi, lo);
+}
+
 // y <- (LU)^-1 y for the column a wave holds: lane l owns row s * 64 + l in y[s][.] (RPL = 2: columns of 65-128 rows), K
 // right-hand sides side by side, L[s][q - 1] = l(r, r - q), U[s][q - 1] = u(r, r + q), invd = 1 / u(r, r), all zero behind
 // the column's end.  Both sweeps are written out step by step, so the lane a step broadcasts and the lanes it updates are
@@ -416,21 +425,20 @@ void launch_csr_spmv_batch (int K, const CsrDev &A, int rb0, int rb1, const doub
 void launch_restrict_sum_batch (int K, const int *rptr, const int *ridx, const double *fine, double *coarse, int64_t nc, hipStream_t st);
 void launch_prolong_add_batch (int K, const int *cmap, const double *coarse, double *fine, int64_t nf, double omega, hipStream_t st);
 void launch_gather_batch (int K, const int *perm, const double *in, double *out, int64_t n, hipStream_t st);
-void launch_gather_interleave (int K, const int *perm, const double *const *src, double *out, int64_t n, hipStream_t st, const double *scale = nullptr);
+// out[i * K + k] = src_k[idx[i]], the entry of a batched cycle or the rows of a K-wide message; the
+// exit: z[perm[i] * K + k] = dst_k[perm[i]] = in[i * K + k]
+void launch_gather_interleave (int K, const int *idx, const double *const *src, double *out, int64_t n, hipStream_t st, const double *scale = nullptr);
 void launch_scatter_split (int K, const int *perm, const double *in, double *z, double *const *dst, int64_t n, hipStream_t st);
-void launch_csr_spmv_batch_split (int K, const CsrDev &A, const double *x, double *const *dst, hipStream_t st, const double *scale = nullptr);
 void launch_csr_spmv_batch_split_range (int K, const CsrDev &A, int rb0, int rb1, const double *x, double *const *dst, hipStream_t st, const double *scale = nullptr);
 // chained cycles: dst_k = b_k - A x_k from and to per-system vectors (b_k times bscale when given; dst_k NULL: system k takes no
 // part), and z_k += p_k on the interleaved z and the systems' own vectors at once (dst_k NULL: column k of z stays as it is)
 void launch_csr_residual_batch_split_range (int K, const CsrDev &A, int rb0, int rb1, const double *x, const double *const *b, const double *bscale,
                                             double *const *dst, hipStream_t st);
 void launch_add_split (int K, const double *p, double *z, double *const *dst, int64_t n, hipStream_t st);
-// row-distributed flavour: K-wide message rows out[i * K + k] = src_k[idx[i]]; the entry / exit of a batched cycle on the
-// extended rows [own | overlap] (overlap rows read from the K-interleaved halo at sel[.], only own rows written back)
-void launch_pack_rows_split (int K, const int *idx, const double *const *src, double *out, int64_t nrows, hipStream_t st);
-void launch_gather_interleave_ext (int K, const int *perm, const double *const *src, const double *halo, const int *sel, int64_t n_own, double *out, int64_t n,
+// row-distributed flavour: the entry / exit of a batched cycle on the extended rows [own | overlap] (overlap rows read from the
+// K-interleaved rows ext: the halo at sel[.], or with sel NULL a block of the overlap rows alone; only own rows written back)
+void launch_gather_interleave_ext (int K, const int *perm, const double *const *src, const double *ext, const int *sel, int64_t n_own, double *out, int64_t n,
                                    hipStream_t st);
-void launch_gather_interleave_ext_block (int K, const int *perm, const double *const *src, const double *recv, int64_t n_own, double *out, int64_t n, hipStream_t st);
 void launch_scatter_split_own (int K, const int *perm, const double *in, double *z, double *const *dst, int64_t n_own, int64_t n, hipStream_t st);
 void launch_dense_matvec_batch (int K, const double *Minv, const double *x, double *y, int n, hipStream_t st);
 // water-column solves of blocks [b0, b1), one column per wave / the fused half sweep, K columns

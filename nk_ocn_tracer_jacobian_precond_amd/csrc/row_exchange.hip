@@ -32,7 +32,7 @@ int halo_fetch (nkp_solver *s, int K, const double *x, const double *const *xp, 
    if (K == 1) launch_copy (x, D.xe, s->n, st);
    else if (xp) launch_interleave (K, xp, D.bxe, s->n, st);
    if (X.nsend && K == 1) launch_gather (X.send_idx, x, X.send_for (K), X.nsend, st);
-   else if (X.nsend && xp) launch_pack_rows_split (K, X.send_idx, xp, X.send_for (K), X.nsend, st);
+   else if (X.nsend && xp) launch_gather_interleave (K, X.send_idx, xp, X.send_for (K), X.nsend, st);
    else if (X.nsend) launch_gather_batch (K, X.send_idx, x, X.send_for (K), X.nsend, st);
    if (comm != st) {
       (void) hipEventRecord (D.ev_packed, st);
