@@ -400,7 +400,9 @@ int nkp_time_kernel (nkp_solver *s, int which, int arg, int reps, double *avg_ms
  * d_dval), "values_product_us" (wall time of the last one), "tangent_calls" (nkp_solve_tangent_device calls that ran their solve),
  * "values_product_trans_calls" (successful nkp_values_product_trans* calls), "values_product_trans_us" (wall time of the last one),
  * "trans_index_bytes" (device bytes of the transposed index those calls keep, 0 before the first; part of "device_bytes"),
- * "trans_index_us" (wall time of building it), "batch_steps" (batched operator
+ * "trans_index_us" (wall time of building it), "trans_index_sent_entries" / "trans_index_recv_entries" (row-distributed: the entries
+ * whose products this rank ships to / receives from its peers in every nkp_values_product_trans_dist*; 0 without an index),
+ * "batch_steps" (batched operator
  * applications = lockstep Krylov steps of a group of right-hand sides), "batch_width" (K of the last batched group, 0 if
  * none ran); "batch_member_bytes" (device bytes of the K - 1 further sets of work vectors a batched call has made and keeps:
  * Krylov bases, level vectors, with chained cycles the residual between two cycles; "device_bytes" counts the solver's own set
@@ -722,12 +724,51 @@ int nkp_values_product (nkp_solver *s, int nrhs, const double *val, const double
  *   Only the pattern is read: the call is allowed on a solver whose refactor failed after its commit point.
  * Refused with NKP_EINVAL, the solver solving exactly as before: a clone (call it on the solver it was cloned from, as for
  * nkp_transpose); a transposed handle (call it on its owner; on the handle nkp_values_product multiplies with A^T's pattern and
- * values in A^T's order); a row-distributed solver, force_dist included -- the product sends rows back to their owners, a reverse
- * exchange that is still to come -- refused on the calling rank without any collective.  A NULL solver or buffer is refused on the
+ * values in A^T's order); a row-distributed solver, force_dist included -- the product sends products back to the owners of their
+ * columns, a collective of its own: nkp_values_product_trans_dist* below -- refused on the calling rank without any collective.  A
+ * NULL solver or buffer is refused on the
  * calling thread before the solver is looked at, the message names the argument; nrhs outside 1 .. 8, ldx or ldy < n, y == x
  * are found before any HIP call.  NKP_ENOMEM / NKP_EDEVICE.  nkp_get_int: "values_product_trans_calls", "values_product_trans_us". */
 int nkp_values_product_trans_device (nkp_solver *s, int nrhs, const void *d_val, const void *d_x, int64_t ldx, double alpha, int accumulate, void *d_y, int64_t ldy);
 int nkp_values_product_trans (nkp_solver *s, int nrhs, const double *val, const double *x, int64_t ldx, double alpha, int accumulate, double *y, int64_t ldy);
+
+/* The same product on a row-distributed solver: y_c (+)= alpha * G^T x_c, G the global matrix that holds every rank's values on the
+ * global pattern.  COLLECTIVE, with the same nrhs (1 .. 8) on every rank.  val_loc holds this rank's nnz_loc values in the order of
+ * the rowptr_loc / colind_glob it gave nkp_create_dist; x and y hold this rank's own rows of every vector, vector c at c * ldx and
+ * c * ldy, ldx, ldy >= m_loc, rows m_loc .. ld - 1 neither read nor written; y == x is refused.  For the own columns j,
+ * y_c[j] (+)= alpha * t_c[j] with t_c[j] as for nkp_values_product_trans: it starts at +0.0 and adds val[e] * x_c[row of e] over ALL
+ * stored entries of global column j, whichever rank stores them, in ascending (global row, stored position) order, each product
+ * and each sum rounded on its own; a column of more than 2048 entries is summed in the SpMV's tree.  Each rank's slice of y has
+ * the bits nkp_values_product_trans_device gives on a single-GPU solver of the whole matrix, whatever the number of ranks.
+ *   How: with a row partition "ascending global row" is rank 0's contributions, then rank 1's, ...  The PRODUCTS travel, not partial
+ *   sums: for every entry in one of its halo columns a rank ships val[e] * x_c[row of e] (one rounded product per vector) to the
+ *   owner of the column, 8 * K * (entries shipped) bytes per call (K = 1, 2, 4, 8 the interleave width that serves nrhs); the owner
+ *   walks the assembled row of G^T in order and adds own and received products alike, one rounded add each.
+ *   The transposed index is built collectively at the first call and kept: the local transpose of this rank's [own | halo]
+ *   rectangle (on the device, as nkp_transpose_dist makes it), the entry count of every halo row to its owner, and the placement
+ *   of every contribution; no source rows and no values travel.  Kept on the device, "trans_index_bytes": 4 (m_loc + 1) bytes of
+ *   row offsets, 8 bytes per assembled entry (own + received: where its value and its x row are), the row blocks, 8 bytes per
+ *   shipped entry.  All or nothing ACROSS ranks: if any rank could not build its part, every rank frees what it built and the
+ *   solvers are exactly as before.  The index survives nkp_refactor_dist*, with or without NKP_REFACTOR_REBUILD, and neither uses
+ *   nor feeds a handle from nkp_transpose_dist.  "trans_index_sent_entries" / "trans_index_recv_entries" count what this rank ships
+ *   and receives.  Work space: [ own rows | received products ] x K and the K-wide send buffer, made at first use for the K asked
+ *   for, grown when a wider K comes, counted in "device_bytes"; the host flavour stages val_loc, x and y like nkp_values_product.
+ *   Refused with NKP_EINVAL when 8 * (entries shipped or received) does not fit the int counts of the exchange.
+ * The callbacks, in this order on every rank whatever happens locally:
+ *      allgather_i64_host   agreement: arguments (nrhs, ldx, ldy, y != x), work space, staging; without an index also the local transpose
+ *    [ alltoallv_i32_host   entry counts of the halo rows        -- only in a call that builds the index ]
+ *    [ allgather_i64_host   agreement: placement, index, commit  -- only in a call that builds the index ]
+ *      alltoallv            the products (always made, also by a rank that ships and receives nothing; "dist_alltoallv_calls")
+ *      allgather_i64_host   agreement: exchange and kernel
+ * After a failed agreement every rank returns: the failing rank its own code and message, the others NKP_ECOMM naming it; y is
+ * undefined and the solvers solve as before.  Refused on the calling rank before any collective, NKP_EINVAL: a NULL solver or
+ * buffer (the message names the argument); a clone; a transposed handle (call it on its owner).  On a plain solver -- from
+ * nkp_create, or from nkp_create_dist for one rank without force_dist -- the calls ARE nkp_values_product_trans*; with force_dist on
+ * one rank the distributed path runs with empty exchanges.  nkp_get_int as on a single-GPU solver: "values_product_trans_calls",
+ * "values_product_trans_us", "trans_index_bytes", "trans_index_us". */
+int nkp_values_product_trans_dist_device (nkp_solver *s, int nrhs, const void *d_val_loc, const void *d_x, int64_t ldx, double alpha, int accumulate, void *d_y,
+                                          int64_t ldy);
+int nkp_values_product_trans_dist (nkp_solver *s, int nrhs, const double *val_loc, const double *x, int64_t ldx, double alpha, int accumulate, double *y, int64_t ldy);
 
 /* The tangent (forward mode) of a solve: dX = A^-1 (dB - dA X) for nrhs right-hand sides, device buffers.  R_c = dB_c - dA X_c is
  * formed in work space of the solver (8 nrhs ld bytes, at first use, kept, counted in "device_bytes") and has the bits of

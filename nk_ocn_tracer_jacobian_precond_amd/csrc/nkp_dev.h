@@ -113,6 +113,10 @@ void launch_values_product (int K, int nk, const CsrDev &A, const double *val, c
 // gathered from val[src[p]] -- val stays in A's order; the bits of the SpMV kernels on a matrix that stores the transposed values
 void launch_values_product_trans (int K, int nk, const CsrDev &T, const int *src, const double *val, const double *x, double alpha, int accumulate, double *y,
                                   int64_t ldy, hipStream_t st);
+// nkp_values_product_trans_dist (valprod.hip): the same on the row block of A^T a rank assembled; src[p] < 0 marks a product a peer shipped,
+// which sits in x at row T.colind[p] and takes the value 1.0
+void launch_values_product_trans_recv (int K, int nk, const CsrDev &T, const int *src, const double *val, const double *x, double alpha, int accumulate, double *y,
+                                       int64_t ldy, hipStream_t st);
 
 // ---------------------------------------------------------------- water-column blocks
 // Banded LU (no pivoting) of every diagonal block, half-bandwidth P in {1,2,4}; SoA by

@@ -155,6 +155,8 @@ extern "C" int64_t nkp_get_int (nkp_solver *s, const char *key)
    if (!strcmp (key, "values_product_trans_us")) return (int64_t) (s->vt.seconds * 1.0e6);
    if (!strcmp (key, "trans_index_bytes")) return (int64_t) s->vt.bytes;
    if (!strcmp (key, "trans_index_us")) return (int64_t) (s->vt.build_seconds * 1.0e6);
+   if (!strcmp (key, "trans_index_sent_entries")) return s->vt.n_ship;
+   if (!strcmp (key, "trans_index_recv_entries")) return s->vt.n_recv;
    if (!strcmp (key, "batch_steps")) return s->batch_steps;
    if (!strcmp (key, "batch_width")) return s->batch_width;
    if (!strcmp (key, "batch_member_bytes")) {      // the further sets of work vectors a batched group keeps (not part of device_bytes)

@@ -7,7 +7,7 @@
 //   batch_solve.hip     K right-hand sides in lockstep (nkp_solve_batch_device); the kernels are batch.hip
 //   smooth_exchange.hip the fine-level exchange of a row-distributed cycle (tuning dist_smooth_exchange): kernels, lists, the cycle's hook
 //   inspect.hip         entry points of tests and timing (arrays of the hierarchy and the matrix, single products, nkp_time_kernel)
-//   refactor_api.hip, transpose*.hip, valgrad_api.hip, valprod_api.hip      new values, A^T, gradient and product by values
+//   refactor_api.hip, transpose*.hip, valgrad_api.hip, valprod_api.hip, valprod_trans_dist.hip      new values, A^T, gradient and products by values
 // What crosses units is declared once, below, under the unit that defines it.  Private to the library: nothing here is part of
 // the C ABI.
 #pragma once
@@ -176,6 +176,16 @@ struct nkp_solver {
       double build_seconds = 0.0;
       int64_t calls = 0;
       double seconds = 0.0;        // wall time of the last product
+      // nkp_values_product_trans_dist on a row-distributed solver (valprod_trans_dist.hip): T is then the row block of A^T this rank
+      // assembles -- T.rowptr [m_loc + 1] and its row blocks, T.colind the x row of every assembled entry (a local row, or m_loc + q
+      // for the q-th received product) -- and src its origin (a position in val_loc, or -1 - q).  The ship list (position in val_loc
+      // and local row of every entry in a halo column, grouped by destination), the entries per rank, and the work space
+      // xe = [ own rows | received products ] x K and the K-wide send buffer, grown when a wider K comes
+      int *ship_e = nullptr, *ship_i = nullptr;
+      int64_t n_ship = 0, n_recv = 0;
+      std::vector<int> send_entries, recv_entries, send_k, recv_k;      // per rank; times the K of the last call
+      double *xe = nullptr, *send = nullptr;
+      size_t xe_cap = 0, send_cap = 0;
    } vt;
    double *h_dev () { return dscal; }
    double *h2_dev () { return dscal + (m + 2); }

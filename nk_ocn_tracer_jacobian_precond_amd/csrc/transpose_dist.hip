@@ -18,8 +18,9 @@
 // Kept on the device for refactors: origin (per entry of the assembled block: a position in the source's values, or -1 - a
 // position in the received values), the ship list (positions in the source's values, by destination) and, from the first
 // refactor on, the send / receive / assembled value buffers.
-#include "solver_impl.h"
-#include "transpose.h"
+// The local transpose, the exchange of the entry counts, the placement plan and the placing kernels are declared in
+// transpose_dist.h: the transposed index of nkp_values_product_trans_dist (valprod_trans_dist.hip) is built from the same steps.
+#include "transpose_dist.h"
 
 #include <stdio.h>
 #include <time.h>
@@ -40,32 +41,34 @@ __device__ static inline int td_seg_of (const int *__restrict__ ptr, int n, int 
    return lo;
 }
 
-// own part: entry e of row c < m_loc of the local transpose goes to own_dst[c] + (e - rowptrT[c]) with its global column
+// own part: entry e of row c < m_loc of the local transpose goes to own_dst[c] + (e - rowptrT[c]) with the column col_add + its
+// source row (col_add = the rank's first row: the global column; 0: the local row); valT / valF NULL: no values are placed
 __global__ __launch_bounds__ (TD_T)
 void td_place_own_kernel (const int *__restrict__ rowptrT, int m_loc, int n_own, const int *__restrict__ own_dst, const int *__restrict__ colindT,
-                          const int *__restrict__ src, const double *__restrict__ valT, int fst, int *__restrict__ colF, double *__restrict__ valF,
+                          const int *__restrict__ src, const double *__restrict__ valT, int col_add, int *__restrict__ colF, double *__restrict__ valF,
                           int *__restrict__ origin)
 {
    const int e = blockIdx.x * TD_T + threadIdx.x;
    if (e >= n_own) return;
    const int c = td_seg_of (rowptrT, m_loc, e);
    const int d = own_dst[c] + (e - rowptrT[c]);
-   colF[d] = fst + colindT[e];
-   valF[d] = valT[e];
+   colF[d] = col_add + colindT[e];
+   if (valF) valF[d] = valT[e];
    origin[d] = src[e];
 }
 
-// received part: entry i of segment k (one row a peer holds as halo) goes to seg_dst[k] + (i - seg_ptr[k])
+// received part: entry i of segment k (one row a peer holds as halo) goes to seg_dst[k] + (i - seg_ptr[k]); without recv_col its
+// column is col_add + i, its place in the received stream
 __global__ __launch_bounds__ (TD_T)
 void td_place_recv_kernel (const int *__restrict__ seg_ptr, int nseg, int n_recv, const int *__restrict__ seg_dst, const int *__restrict__ recv_col,
-                           const double *__restrict__ recv_val, int *__restrict__ colF, double *__restrict__ valF, int *__restrict__ origin)
+                           const double *__restrict__ recv_val, int col_add, int *__restrict__ colF, double *__restrict__ valF, int *__restrict__ origin)
 {
    const int i = blockIdx.x * TD_T + threadIdx.x;
    if (i >= n_recv) return;
    const int k = td_seg_of (seg_ptr, nseg, i);
    const int d = seg_dst[k] + (i - seg_ptr[k]);
-   colF[d] = recv_col[i];
-   valF[d] = recv_val[i];
+   colF[d] = recv_col ? recv_col[i] : col_add + i;
+   if (valF) valF[d] = recv_val[i];
    origin[d] = -1 - i;
 }
 
@@ -93,34 +96,19 @@ static double td_since (const struct timespec &t0)
    return (double) (t.tv_sec - t0.tv_sec) + 1e-9 * (double) (t.tv_nsec - t0.tv_nsec);
 }
 
-// a HIP call of a rank-local step: its failure becomes that step's code (the agreement after the step carries it to the peers)
+// a HIP call of a rank-local step of `who`: its failure becomes that step's code (the agreement after the step carries it to the peers)
 #define TDHIP(call)                                                                                          \
    do {                                                                                                      \
       hipError_t e_ = (call);                                                                                \
       if (e_ != hipSuccess) {                                                                                \
          (void) hipGetLastError ();                                                                          \
-         return fail (e_ == hipErrorOutOfMemory ? NKP_ENOMEM : NKP_EDEVICE, "nkp_transpose_dist: %s failed: %s", #call, hipGetErrorString (e_)); \
+         return fail (e_ == hipErrorOutOfMemory ? NKP_ENOMEM : NKP_EDEVICE, "%s: %s failed: %s", who, #call, hipGetErrorString (e_)); \
       }                                                                                                      \
    } while (0)
 
-namespace {
-
-// what one build holds between its steps; everything on the device is freed when it goes out of scope
-struct TransDistBuild {
-   int P = 1, me = 0;
-   int64_t m_loc = 0, n_halo = 0, nnz = 0, n_own = 0, n_ship = 0, n_recv = 0, nnzF = 0, nseg = 0;
-   mls::DBuf<int> rowptrT, colindT, src, colF, origin, ship;
-   mls::DBuf<double> valT, valF, recv_val;
-   std::vector<int32_t> h_rpT, cnt_send, cnt_recv, ship_glob, recv_col, rowptrF, own_dst, seg_ptr, seg_dst, h_colF;
-   std::vector<int> ent_send, ent_recv;
-   std::vector<double> h_valF;
-   double kernel_seconds = 0.0;
-};
-
-// step 1: the rectangular transpose, the entry count of every halo row and the global source rows of the entries to ship
-int td_local_transpose (nkp_solver *s, TransDistBuild &B)
+// ---------------------------------------------------------------- the steps shared with the transposed index (transpose_dist.h)
+int td_local_transpose (nkp_solver *s, TransDistBuild &B, const char *who)
 {
-   if (s->shared->broken) return fail (NKP_ESINGULAR, "nkp_transpose_dist: %s", s->shared->why.c_str ());
    hipStream_t st = s->stream;
    TDHIP (hipSetDevice (s->device));
    TDHIP (hipStreamSynchronize (st));
@@ -131,18 +119,15 @@ int td_local_transpose (nkp_solver *s, TransDistBuild &B)
    if (trc) {
       (void) hipStreamSynchronize (st);
       (void) hipGetLastError ();      // an out-of-memory error is sticky until read
-      if (trc == (int) hipErrorOutOfMemory) return fail (NKP_ENOMEM, "nkp_transpose_dist: no device memory for the transposed row block (%lld entries); the solver is unchanged", (long long) B.nnz);
-      return fail (NKP_EDEVICE, "nkp_transpose_dist: the device transpose failed (%s)", trc >= 1000 ? "inconsistent column counts" : hipGetErrorString ((hipError_t) trc));
+      if (trc == (int) hipErrorOutOfMemory) return fail (NKP_ENOMEM, "%s: no device memory for the transposed row block (%lld entries); the solver is unchanged", who, (long long) B.nnz);
+      return fail (NKP_EDEVICE, "%s: the device transpose failed (%s)", who, trc >= 1000 ? "inconsistent column counts" : hipGetErrorString ((hipError_t) trc));
    }
    B.kernel_seconds = td_since (t0);
    B.h_rpT.assign ((size_t) ncols + 1, 0);
    TDHIP (hipMemcpy (B.h_rpT.data (), B.rowptrT.p, B.h_rpT.size () * sizeof (int32_t), hipMemcpyDeviceToHost));
    B.n_own = B.h_rpT[(size_t) B.m_loc];
    B.n_ship = B.nnz - B.n_own;
-   if (B.h_rpT[(size_t) ncols] != B.nnz || B.n_own < 0 || B.n_ship < 0) return fail (NKP_EDEVICE, "nkp_transpose_dist: the device transpose returned inconsistent row offsets");
-   B.ship_glob.assign ((size_t) B.n_ship + 1, 0);
-   if (B.n_ship) TDHIP (hipMemcpy (B.ship_glob.data (), B.colindT.p + B.n_own, (size_t) B.n_ship * sizeof (int32_t), hipMemcpyDeviceToHost));
-   for (int64_t k = 0; k < B.n_ship; k++) B.ship_glob[(size_t) k] += (int32_t) s->dist.fst;
+   if (B.h_rpT[(size_t) ncols] != B.nnz || B.n_own < 0 || B.n_ship < 0) return fail (NKP_EDEVICE, "%s: the device transpose returned inconsistent row offsets", who);
    B.cnt_send.assign ((size_t) B.n_halo + 1, 0);
    for (int64_t h = 0; h < B.n_halo; h++) B.cnt_send[(size_t) h] = B.h_rpT[(size_t) (B.m_loc + h + 1)] - B.h_rpT[(size_t) (B.m_loc + h)];
    // the halo rows of owner p follow each other: recv_counts[p] of them
@@ -150,12 +135,20 @@ int td_local_transpose (nkp_solver *s, TransDistBuild &B)
    int64_t h = 0;
    for (int p = 0; p < B.P; p++)
       for (int k = 0; k < s->dist.x_halo.recv_counts[(size_t) p]; k++, h++) B.ent_send[(size_t) p] += B.cnt_send[(size_t) h];
-   if (h != B.n_halo) return fail (NKP_EINVAL, "nkp_transpose_dist: the halo plan of this solver is inconsistent");
+   if (h != B.n_halo) return fail (NKP_EINVAL, "%s: the halo plan of this solver is inconsistent", who);
    return NKP_OK;
 }
 
-// step 2 (after the counts arrived): row offsets of the assembled block and where every contribution starts
-int td_plan_placement (nkp_solver *s, TransDistBuild &B)
+int td_exchange_counts (nkp_solver *s, TransDistBuild &B, const char *who)
+{
+   const nkp_comm_ops &c = s->dist.ops;
+   B.cnt_recv.assign ((size_t) B.nseg + 1, 0);
+   if (c.alltoallv_i32_host (c.ctx, B.cnt_send.data (), s->dist.x_halo.recv_counts.data (), B.cnt_recv.data (), s->dist.x_halo.send_counts.data ()))
+      return fail (NKP_ECOMM, "%s: the exchange of the entry counts failed", who);
+   return NKP_OK;
+}
+
+int td_plan_placement (nkp_solver *s, TransDistBuild &B, const char *who)
 {
    const std::vector<int32_t> &rows = s->dist.h_send_rows;
    B.ent_recv.assign ((size_t) B.P, 0);
@@ -167,17 +160,17 @@ int td_plan_placement (nkp_solver *s, TransDistBuild &B)
       int64_t t = 0;
       for (int q = 0; q < s->dist.x_halo.send_counts[(size_t) p]; q++, k++) {
          const int32_t cnt = B.cnt_recv[(size_t) k], c = rows[(size_t) k];
-         if (cnt < 0 || c < 0 || c >= B.m_loc) return fail (NKP_ECOMM, "nkp_transpose_dist: rank %d sent an entry count this rank cannot place", p);
+         if (cnt < 0 || c < 0 || c >= B.m_loc) return fail (NKP_ECOMM, "%s: rank %d sent an entry count this rank cannot place", who, p);
          t += cnt;
          len[(size_t) c] += cnt;
       }
       total += t;
-      if (total >= 2147483647LL) return fail (NKP_EINVAL, "nkp_transpose_dist: the entries received exceed the int32 exchange counts");
+      if (total >= 2147483647LL) return fail (NKP_EINVAL, "%s: the entries received exceed the int32 exchange counts", who);
       B.ent_recv[(size_t) p] = (int) t;
    }
    B.n_recv = total;
    B.nnzF = B.n_own + B.n_recv;
-   if (B.nnzF >= 2147483647LL) return fail (NKP_EINVAL, "nkp_transpose_dist: the row block of A^T exceeds the int32 index schema");
+   if (B.nnzF >= 2147483647LL) return fail (NKP_EINVAL, "%s: the row block of A^T exceeds the int32 index schema", who);
    for (int64_t q = 0; q < B.nseg; q++) B.seg_ptr[(size_t) q + 1] = B.seg_ptr[(size_t) q] + B.cnt_recv[(size_t) q];
    B.rowptrF.assign ((size_t) B.m_loc + 1, 0);
    for (int64_t c = 0; c < B.m_loc; c++) B.rowptrF[(size_t) c + 1] = (int32_t) (B.rowptrF[(size_t) c] + len[(size_t) c]);
@@ -199,43 +192,49 @@ int td_plan_placement (nkp_solver *s, TransDistBuild &B)
       }
    }
    for (int64_t c = 0; c < B.m_loc; c++)
-      if (cursor[(size_t) c] != B.rowptrF[(size_t) c + 1]) return fail (NKP_EINVAL, "nkp_transpose_dist: a row of this rank is sent twice to one peer (inconsistent halo plan)");
+      if (cursor[(size_t) c] != B.rowptrF[(size_t) c + 1]) return fail (NKP_EINVAL, "%s: a row of this rank is sent twice to one peer (inconsistent halo plan)", who);
    return NKP_OK;
 }
 
 template <class T>
-int td_upload (mls::DBuf<T> &d, const std::vector<T> &h, size_t cnt)
+static int td_upload (mls::DBuf<T> &d, const std::vector<T> &h, size_t cnt, const char *who)
 {
    TDHIP (d.alloc (cnt));
    if (cnt) TDHIP (hipMemcpy (d.p, h.data (), cnt * sizeof (T), hipMemcpyHostToDevice));
    return NKP_OK;
 }
 
-// step 3 (after the source rows and the values arrived): the assembled block on the device, then on the host
-int td_place (nkp_solver *s, TransDistBuild &B)
+int td_place_entries (nkp_solver *s, TransDistBuild &B, bool values, int own_add, int recv_add, const char *who)
 {
    hipStream_t st = s->stream;
-   struct timespec t0;
-   clock_gettime (CLOCK_MONOTONIC, &t0);
    mls::DBuf<int> d_own_dst, d_seg_ptr, d_seg_dst, d_recv_col;
    int rc;
-   if ((rc = td_upload (d_own_dst, B.own_dst, (size_t) B.m_loc))) return rc;
-   if ((rc = td_upload (d_seg_ptr, B.seg_ptr, (size_t) B.nseg + 1))) return rc;
-   if ((rc = td_upload (d_seg_dst, B.seg_dst, (size_t) B.nseg))) return rc;
-   if ((rc = td_upload (d_recv_col, B.recv_col, (size_t) B.n_recv))) return rc;
+   if ((rc = td_upload (d_own_dst, B.own_dst, (size_t) B.m_loc, who))) return rc;
+   if ((rc = td_upload (d_seg_ptr, B.seg_ptr, (size_t) B.nseg + 1, who))) return rc;
+   if ((rc = td_upload (d_seg_dst, B.seg_dst, (size_t) B.nseg, who))) return rc;
+   if (values && (rc = td_upload (d_recv_col, B.recv_col, (size_t) B.n_recv, who))) return rc;
    TDHIP (B.colF.alloc ((size_t) B.nnzF));
-   TDHIP (B.valF.alloc ((size_t) B.nnzF));
+   if (values) TDHIP (B.valF.alloc ((size_t) B.nnzF));
    TDHIP (B.origin.alloc ((size_t) B.nnzF));
-   TDHIP (B.ship.alloc ((size_t) B.n_ship));
    if (B.n_own)
       hipLaunchKernelGGL (td_place_own_kernel, td_grid (B.n_own), dim3 (TD_T), 0, st, B.rowptrT.p, (int) B.m_loc, (int) B.n_own, d_own_dst.p, B.colindT.p, B.src.p,
-                          B.valT.p, (int) s->dist.fst, B.colF.p, B.valF.p, B.origin.p);
+                          values ? B.valT.p : nullptr, own_add, B.colF.p, B.valF.p, B.origin.p);
    if (B.n_recv)
       hipLaunchKernelGGL (td_place_recv_kernel, td_grid (B.n_recv), dim3 (TD_T), 0, st, d_seg_ptr.p, (int) B.nseg, (int) B.n_recv, d_seg_dst.p, d_recv_col.p,
-                          B.recv_val.p, B.colF.p, B.valF.p, B.origin.p);
-   if (B.n_ship) TDHIP (hipMemcpyAsync (B.ship.p, B.src.p + B.n_own, (size_t) B.n_ship * sizeof (int), hipMemcpyDeviceToDevice, st));
-   TDHIP (hipStreamSynchronize (st));
+                          B.recv_val.p, recv_add, B.colF.p, B.valF.p, B.origin.p);
+   TDHIP (hipStreamSynchronize (st));      // the uploaded plan is freed on return
    TDHIP (hipGetLastError ());
+   return NKP_OK;
+}
+
+// (after the source rows and the values arrived): the assembled block on the device, then on the host
+static int td_place (nkp_solver *s, TransDistBuild &B, const char *who)
+{
+   struct timespec t0;
+   clock_gettime (CLOCK_MONOTONIC, &t0);
+   if (const int rc = td_place_entries (s, B, true, (int) s->dist.fst, 0, who)) return rc;
+   TDHIP (B.ship.alloc ((size_t) B.n_ship));
+   if (B.n_ship) TDHIP (hipMemcpy (B.ship.p, B.src.p + B.n_own, (size_t) B.n_ship * sizeof (int), hipMemcpyDeviceToDevice));
    B.kernel_seconds += td_since (t0);
    B.h_colF.assign ((size_t) B.nnzF + 1, 0);
    B.h_valF.assign ((size_t) B.nnzF + 1, 0.0);
@@ -246,7 +245,14 @@ int td_place (nkp_solver *s, TransDistBuild &B)
    return NKP_OK;
 }
 
-}  // namespace
+// the global source rows of the entries to ship (nkp_transpose_dist alone: the index needs no columns)
+static int td_ship_rows (nkp_solver *s, TransDistBuild &B, const char *who)
+{
+   B.ship_glob.assign ((size_t) B.n_ship + 1, 0);
+   if (B.n_ship) TDHIP (hipMemcpy (B.ship_glob.data (), B.colindT.p + B.n_own, (size_t) B.n_ship * sizeof (int32_t), hipMemcpyDeviceToHost));
+   for (int64_t k = 0; k < B.n_ship; k++) B.ship_glob[(size_t) k] += (int32_t) s->dist.fst;
+   return NKP_OK;
+}
 
 // ---------------------------------------------------------------- the refactor of the source reaches the transposed solver
 int trans_dist_follow (nkp_solver *s, int flags, const char *who, int (*refactor) (nkp_solver *t, const void *d_val, int flags, const char *who))
@@ -316,23 +322,15 @@ extern "C" int nkp_transpose_dist (nkp_solver *s, nkp_solver **out)
    }
    struct timespec t0;
    clock_gettime (CLOCK_MONOTONIC, &t0);
-   TransDistBuild B;
-   B.P = P;
-   B.me = c.rank;
-   B.m_loc = s->n;
-   B.n_halo = s->dist.n_halo;
-   B.nnz = s->A.nnz;
-   B.nseg = s->dist.x_halo.nsend;
+   TransDistBuild B (s);
 
    // ---- the local transpose
-   int rc = td_local_transpose (s, B);
+   int rc = s->shared->broken ? fail (NKP_ESINGULAR, "nkp_transpose_dist: %s", s->shared->why.c_str ()) : td_local_transpose (s, B, who);
+   if (!rc) rc = td_ship_rows (s, B, who);
    if ((rc = dist_agree (s, rc, who, "local transpose"))) return rc;
 
    // ---- entry counts of the rows the peers hold as halo, then the plan of the assembled block
-   B.cnt_recv.assign ((size_t) B.nseg + 1, 0);
-   if (c.alltoallv_i32_host (c.ctx, B.cnt_send.data (), s->dist.x_halo.recv_counts.data (), B.cnt_recv.data (), s->dist.x_halo.send_counts.data ()))
-      rc = fail (NKP_ECOMM, "nkp_transpose_dist: the exchange of the entry counts failed");
-   else rc = td_plan_placement (s, B);
+   if (!(rc = td_exchange_counts (s, B, who))) rc = td_plan_placement (s, B, who);
    if (!rc && B.recv_val.alloc ((size_t) B.n_recv) != hipSuccess) {      // a rank without its receive buffer must not enter the exchange
       (void) hipGetLastError ();
       rc = fail (NKP_ENOMEM, "nkp_transpose_dist: no device memory for the %lld received values", (long long) B.n_recv);
@@ -349,7 +347,7 @@ extern "C" int nkp_transpose_dist (nkp_solver *s, nkp_solver **out)
       for (int64_t i = 0; i < B.n_recv && !rc; i++)
          if (B.recv_col[(size_t) i] < 0 || B.recv_col[(size_t) i] >= s->dist.n_global) rc = fail (NKP_ECOMM, "nkp_transpose_dist: a peer sent a source row outside the matrix");
    }
-   if (!rc) rc = td_place (s, B);
+   if (!rc) rc = td_place (s, B, who);
    if (rc) { (void) hipStreamSynchronize (s->stream); (void) hipGetLastError (); }
    if ((rc = dist_agree (s, rc, who, "exchange and placement"))) return rc;
 

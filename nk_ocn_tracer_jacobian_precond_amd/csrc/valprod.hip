@@ -19,12 +19,17 @@
 // (rowptrT, colindT, its row blocks) and the value of entry p is val[src[p]], the caller's values staying in A's order.  The
 // staging step issues all its src loads (coalesced), then the val gathers that depend on them, then writes LDS; the long-row
 // walk gathers the same way.  Without GATHER src is not read and the instantiations are what they were.
+//
+// And nkp_values_product_trans_dist (GATHER and RECV): the pattern is the row block of A^T a rank assembled from its own entries and
+// the products its peers shipped.  src[p] >= 0 is an own entry as above; src[p] < 0 is a received product, which sits in x at the
+// row colind[p] (behind the own rows) and takes the value 1.0 -- 1.0 * p is p exactly, signed zeros and non-finite values included,
+// so it enters the sum through the same rounded multiply and add as an own product.  Without RECV the sign of src is not looked at.
 #include "nkp_dev.h"
 
 #define VP_THREADS 256
 #define VP_WAVES (VP_THREADS / NKP_WAVE)
 
-template <int K, bool GATHER>
+template <int K, bool GATHER, bool RECV = false>
 __global__ __launch_bounds__ (VP_THREADS)
 void values_product_kernel (const int *__restrict__ rowblk, int nrowblk, int per_xcd, const int *__restrict__ rowptr, const int *__restrict__ colind,
                             const int *__restrict__ src, const double *__restrict__ val, const double *__restrict__ x, int nk, double alpha, int accumulate,
@@ -47,7 +52,12 @@ void values_product_kernel (const int *__restrict__ rowblk, int nrowblk, int per
    if (cnt > NKP_SPMV_LDS_NNZ) {
       // a single long row, all K columns in one walk: per column the strided sums and the reduction of the SpMV kernels
       for (int e = e0 + tid; e < e1; e += VP_THREADS) {
-         const double v = val[GATHER ? src[e] : e];
+         double v;
+         if constexpr (RECV) {
+            const int o = src[e];
+            v = o >= 0 ? val[o] : 1.0;
+         } else
+            v = val[GATHER ? src[e] : e];
          const double *xr = x + (int64_t) colind[e] * K;
          double xv[K];
          if constexpr (K == 1) xv[0] = xr[0];
@@ -87,12 +97,13 @@ void values_product_kernel (const int *__restrict__ rowblk, int nrowblk, int per
       for (int u = 0; u < SLOTS; u++) {
          const int k = tid + u * VP_THREADS;
          from[u] = e0 + k;
-         if constexpr (GATHER) from[u] = k < cnt ? src[e0 + k] : 0;
+         if constexpr (GATHER) from[u] = k < cnt ? src[e0 + k] : 0;      // RECV: a padded slot reads val[0] like an own entry and stores nothing
       }
 #pragma unroll
       for (int u = 0; u < SLOTS; u++) {
          const int k = tid + u * VP_THREADS;
-         v[u] = k < cnt ? val[from[u]] : 0.0;
+         if constexpr (RECV) v[u] = k < cnt ? (from[u] >= 0 ? val[from[u]] : 1.0) : 0.0;
+         else v[u] = k < cnt ? val[from[u]] : 0.0;
          c[u] = k < cnt ? colind[e0 + k] : 0;
       }
 #pragma unroll
@@ -140,14 +151,14 @@ void values_product_kernel (const int *__restrict__ rowblk, int nrowblk, int per
 }
 
 // one launch for both products: a workgroup per row block of A, numbered XCD-contiguously
-template <bool GATHER>
+template <bool GATHER, bool RECV = false>
 static void launch_product (int K, int nk, const CsrDev &A, const int *src, const double *val, const double *x, double alpha, int accumulate, double *y, int64_t ldy,
                             hipStream_t st)
 {
    if (A.nrowblk <= 0) return;
    const int per_xcd = (A.nrowblk + 7) / 8;
    with_int<1, 2, 4, 8> (K, [&] (auto k) {
-      hipLaunchKernelGGL ((values_product_kernel<decltype (k)::value, GATHER>), dim3 (per_xcd * 8), dim3 (VP_THREADS), 0, st, A.rowblk, A.nrowblk, per_xcd, A.rowptr,
+      hipLaunchKernelGGL ((values_product_kernel<decltype (k)::value, GATHER, RECV>), dim3 (per_xcd * 8), dim3 (VP_THREADS), 0, st, A.rowblk, A.nrowblk, per_xcd, A.rowptr,
                           A.colind, src, val, x, nk < K ? nk : K, alpha, accumulate, y, ldy);
    });
 }
@@ -166,4 +177,12 @@ void launch_values_product_trans (int K, int nk, const CsrDev &T, const int *src
                                   int64_t ldy, hipStream_t st)
 {
    launch_product<true> (K, nk, T, src, val, x, alpha, accumulate, y, ldy, st);
+}
+
+// The same on the row block of A^T a rank of a row-distributed solver assembled (nkp_values_product_trans_dist): src[p] >= 0 a
+// position in val, src[p] < 0 a product a peer shipped, found in x at row T.colind[p] and multiplied by 1.0
+void launch_values_product_trans_recv (int K, int nk, const CsrDev &T, const int *src, const double *val, const double *x, double alpha, int accumulate, double *y,
+                                       int64_t ldy, hipStream_t st)
+{
+   launch_product<true, true> (K, nk, T, src, val, x, alpha, accumulate, y, ldy, st);
 }

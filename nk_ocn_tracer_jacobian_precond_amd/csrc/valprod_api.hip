@@ -119,7 +119,7 @@ int values_product (nkp_solver *s, int nrhs, const double *h_val, const double *
       if (s->trans_of)
          return fail (NKP_EINVAL, "%s: this solver is itself a transposed handle; call it on the solver it was transposed from (or nkp_values_product here, with values in A^T's order)", who);
       if (s->dist.on)
-         return fail (NKP_EINVAL, "%s: not available for the row-distributed flavour (the product with the transposed pattern sends rows back to their owners, a reverse exchange this library does not have yet); gather the vectors and use a single-GPU solver", who);
+         return fail (NKP_EINVAL, "%s: not available for the row-distributed flavour (the product with the transposed pattern sends products back to the owners of their columns, a collective of its own); call nkp_values_product_trans_dist%s on every rank", who, h_y ? "" : "_device");
    }
    const bool host = h_y != nullptr;
    const bool dist = s->dist.on;
@@ -189,10 +189,13 @@ void valprod_release (nkp_solver *s)
    for (double **p : { &s->vp.x, &s->vp.stage, &s->vp.r })
       if (*p) { (void) hipFree (*p); *p = nullptr; }
    s->vp.x_cap = s->vp.stage_cap = s->vp.r_cap = 0;
-   for (int **p : { &s->vt.T.rowptr, &s->vt.T.colind, &s->vt.T.rowblk, &s->vt.src })
+   for (int **p : { &s->vt.T.rowptr, &s->vt.T.colind, &s->vt.T.rowblk, &s->vt.src, &s->vt.ship_e, &s->vt.ship_i })
+      if (*p) { (void) hipFree (*p); *p = nullptr; }
+   for (double **p : { &s->vt.xe, &s->vt.send })
       if (*p) { (void) hipFree (*p); *p = nullptr; }
    s->vt.T.nrowblk = 0;
-   s->vt.bytes = 0;
+   s->vt.bytes = s->vt.xe_cap = s->vt.send_cap = 0;
+   s->vt.n_ship = s->vt.n_recv = 0;
 }
 
 int valprod_time_prepare (nkp_solver *s, int K, int which)

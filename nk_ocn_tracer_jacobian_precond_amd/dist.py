@@ -412,6 +412,21 @@ class NkpDistSolver(_solver.NkpSolver):
         """nkp_solve_batch_device on this rank's device-resident rows (ldb >= m_loc); collective like solve_many."""
         return super().solve_batch_device(d_B, d_X, nrhs, ldb, raise_on_fail)
 
+    def values_product_trans_dist(self, val_loc, X, alpha=1.0, Y=None):
+        """nkp_values_product_trans_dist (collective: every rank calls it with the same number of vectors): this rank's rows of
+        Y = alpha * G^T X, or Y += ... when Y is given, G the global matrix that holds every rank's val_loc (nnz_loc values in the
+        order of the local rows it was created with).  X (and Y): shape (m_loc,) or (K, m_loc), K <= 8.  Every rank's slice has
+        the bits values_product_trans gives on a single-GPU solver of the whole matrix.  The first call builds, collectively, the
+        transposed index the solver then keeps."""
+        return self._values_product_host(self._lib.nkp_values_product_trans_dist, self._check_collective, val_loc, X, alpha, Y)
+
+    def values_product_trans_dist_device(self, d_val, d_x, nrhs, ldx, d_y, ldy, alpha=1.0, accumulate=False):
+        """nkp_values_product_trans_dist_device (collective): d_val = integer device address of this rank's nnz_loc float64, d_x /
+        d_y of nrhs vectors of this rank's m_loc rows each (vector c at + 8 * c * ldx / ldy); d_y is written (accumulate=False)
+        or added to.  Runs on the solver's stream."""
+        self._check_collective(self._lib.nkp_values_product_trans_dist_device(self._h, int(nrhs), C.c_void_p(d_val), C.c_void_p(d_x), int(ldx), float(alpha),
+                                                                              int(bool(accumulate)), C.c_void_p(d_y), int(ldy)))
+
     def refactor_dist(self, val_loc, rebuild=False):
         """nkp_refactor_dist (collective: every rank calls it): this rank's new values, nnz_loc of them in the order of the
         local rows it was created with.  The overlap rows' values come from their owners; get_int("refactor_halo_values")

@@ -34,6 +34,7 @@ ABI_SYMBOLS = [
     "nkp_value_gradient", "nkp_value_gradient_device",
     "nkp_values_product", "nkp_values_product_device", "nkp_solve_tangent_device", "nkp_matrix_array",
     "nkp_values_product_trans", "nkp_values_product_trans_device",
+    "nkp_values_product_trans_dist", "nkp_values_product_trans_dist_device",
 ]
 
 _ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p)
@@ -138,6 +139,8 @@ def load_library(path=None):
     lib.nkp_values_product_device.argtypes = [vp, C.c_int, vp, vp, C.c_int64, C.c_double, C.c_int, vp, C.c_int64]
     lib.nkp_values_product_trans.argtypes = lib.nkp_values_product.argtypes
     lib.nkp_values_product_trans_device.argtypes = lib.nkp_values_product_device.argtypes
+    lib.nkp_values_product_trans_dist.argtypes = lib.nkp_values_product.argtypes
+    lib.nkp_values_product_trans_dist_device.argtypes = lib.nkp_values_product_device.argtypes
     lib.nkp_solve_tangent_device.argtypes = [vp, C.c_int, vp, vp, C.c_int64, vp, vp, C.c_int64, f64p, C.POINTER(C.c_int), f64p]
     lib.nkp_refactor.argtypes = [vp, f64p, C.c_int]
     lib.nkp_refactor_device.argtypes = [vp, vp, C.c_int]
@@ -386,7 +389,8 @@ class NkpSolver:
     def values_product_trans(self, val, X, alpha=1.0, Y=None):
         """nkp_values_product_trans: Y = alpha * (the solver's pattern with the values val)^T X, or Y += ... when Y is given; val
         stays in the CSR order the solver was created with.  Arguments and result as for values_product.  The first call builds
-        the transposed index the solver then keeps.  Not on clones, transposed handles or row-distributed solvers."""
+        the transposed index the solver then keeps.  Not on clones, transposed handles or row-distributed solvers (there:
+        NkpDistSolver.values_product_trans_dist)."""
         return self._values_product_host(self._lib.nkp_values_product_trans, self._check, val, X, alpha, Y)
 
     def _values_product_host(self, fn, check, val, X, alpha, Y):

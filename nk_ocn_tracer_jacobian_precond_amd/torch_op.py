@@ -57,6 +57,9 @@ class NkpTorchSolver:
     one value gradient.  An inner solve that does not converge raises NkpError from the backward that needed it.  Differentiate
     again under the matrix values the forward solve saw: set_values between a solve and a backward through it changes the matrix
     every later solve of that backward uses.  Forward-over-reverse (dual tensors through a backward pass) is not supported.
+
+    Row-distributed solvers are not wrapped here, but all five operations now exist on them (the fifth as
+    NkpDistSolver.values_product_trans_dist*), so the same backward passes can be written over local slices.
     """
 
     def __init__(self, solver):
