@@ -203,7 +203,7 @@ typedef struct nkp_options {
    int restart;          /* FGMRES restart length m                                           */
    int max_iters;        /* total Krylov iterations allowed per right-hand side               */
    double rtol;          /* stop when ||b - A x||_2 <= rtol * ||b||_2 (true residual)         */
-   double atol;          /* ... or <= atol                                                    */
+   double atol;          /* ... or <= atol   (these three: nkp_set_solve_controls later on)   */
    int device;           /* HIP device ordinal; -1 = leave the current device                 */
    int verbose;          /* the reference's dbg_lvl: 0 silent, 1 progress, 2 per-iteration    */
    int rank;             /* printed as the "(rank)" message prefix (reference `iam`)          */
@@ -344,6 +344,66 @@ int nkp_solve_batch_device (nkp_solver *s, int nrhs, const void *d_B, void *d_X,
 int nkp_solve_device (nkp_solver *s, const void *d_b, void *d_x, int use_guess,
                       double *berr, int *iters, double *relres);
 
+/* rtol, atol and max_iters of an existing solver -- PETSc's KSPSetTolerances: an inexact Newton driver keeps ONE solver (matrix,
+ * hierarchy, work vectors) and loosens or tightens the linear solves from step to step instead of creating a solver per
+ * tolerance.  Restart length, Krylov method, precond_steps and equil size or shape what nkp_create builds (the basis, the chained
+ * cycles' vectors, the row scales) and stay what they were created as. */
+typedef struct nkp_solve_controls {
+   int struct_size;   /* = sizeof(nkp_solve_controls), ABI guard */
+   int max_iters;     /* > 0; 0 = leave as it is */
+   double rtol;       /* finite, >= 0; negative = leave as it is */
+   double atol;       /* finite, >= 0; negative = leave as it is */
+} nkp_solve_controls;
+
+/* After nkp_set_solve_controls (s, c) every solve entry on s -- nkp_solve, nkp_solve_device, nkp_solve_batch_device,
+ * nkp_solve_tangent_device, nkp_solve_batch_device_ex -- behaves BIT FOR BIT like the same call on a solver created with those
+ * three values in nkp_options and everything else equal: x, iters, relres, berr, the return code and the rtol printed in
+ * messages.  That covers target = max (rtol ||b||, atol) as rhs_verdict sees it (so the 2^-480 floor of nkp_solve follows the
+ * new target), the NKP_OK_BERR threshold max (1e-14, rtol / 100) and the stagnation logic: the drivers read the three values
+ * from the handle when a solve starts and nothing is sized by them.  c == NULL puts back the values the handle began with.
+ *   The controls belong to the handle.  A clone starts with its source's values of the moment of nkp_clone, a transposed
+ *   handle with its owner's of the moment nkp_transpose* built it (and those are what c == NULL gives back on it); afterwards
+ *   every handle has its own, nothing propagates.  nkp_refactor* keeps them, NKP_REFACTOR_REBUILD included.  The members of a
+ *   batched group are internal and follow their owner at every call.  No solve may be in flight on the handle.
+ *   Refused with NKP_EINVAL, nothing changed, without any HIP call: a NULL solver, a struct_size mismatch, a NaN or an Inf in
+ *   rtol / atol, max_iters < 0.
+ *   Row-distributed solvers: the call is COLLECTIVE and all ranks pass the same values -- ranks with different stopping tests
+ *   would part in their collectives.  The ranks agree on the bit patterns of what would be in force through three
+ *   allgather_i64_host calls, always all three and in this order whatever happens locally: rtol, atol, max_iters (a rank whose
+ *   own check failed sends -1).  On a mismatch, or when a rank's check failed, every rank returns NKP_EINVAL naming the lowest
+ *   rank that differs from rank 0 or failed, and no rank changes anything; a failed allgather is NKP_ECOMM.  A NULL solver is
+ *   refused on the calling rank before any collective.  On a plain solver (one rank without force_dist) there is no
+ *   collective.
+ * nkp_get_solve_controls: what is in force on the handle.  out->struct_size is set BY THE CALLER (the ABI guard; checked first,
+ * then the handle): NKP_EINVAL for NULL out, a mismatch -- the message gives the library's size --, a NULL solver.
+ * nkp_get_int: "max_iters". */
+int nkp_set_solve_controls (nkp_solver *s, const nkp_solve_controls *c);
+int nkp_get_solve_controls (nkp_solver *s, nkp_solve_controls *out);
+
+/* nkp_solve_batch_device with per-column controls and initial guesses -- a warm start on the batched path.  rtol / atol /
+ * max_iters: nrhs entries each or NULL (= the solver's, as set above); an entry "leave as it is" (negative, 0) also means the
+ * solver's.  use_guess: nrhs flags or NULL; where use_guess[c] != 0, column c of d_X holds x0 on entry.
+ *   Column c has the bits nkp_solve_device (s, b_c, x_c, use_guess[c], ...) gives alone on a solver whose controls are column
+ *   c's: solution, iters[c], relres[c], berr[c] and status -- the promise of nkp_solve_batch_device with the controls and the
+ *   guess added (on a row-distributed solver under that call's condition on the transport).  The return code is the worst of
+ *   the columns'.  Groups are formed exactly as there: in order, up to the width rhs_batch allows; a column with a guess and
+ *   one without may share a group.  The per-column values sit in the options of the systems' work sets while the call runs and
+ *   the solver's own are back when it returns, however it returns.  Controls and guesses are honoured on every path: the
+ *   batched groups, the single remainder of a group, and every fallback nkp_solve_batch_device lists (a clone, BiCGStab, an
+ *   f32 basis, equil on a row-distributed solver, rhs_batch = 0).
+ *   A non-finite guess in column c is that column's NKP_BREAKDOWN as documented at nkp_solve (iters 0, relres NaN, berr NaN,
+ *   x_c left as it was passed); the other columns are untouched.
+ *   Refused with NKP_EINVAL before any device work: a NULL solver or buffer (before the handle is looked at; the message names
+ *   the argument), nrhs < 0, ldb < n, a NaN or an Inf in rtol / atol, max_iters[c] < 0, d_X == d_B while any use_guess[c] != 0
+ *   (the guess and the right-hand side would be the same memory).
+ *   Row-distributed solvers: collective as nkp_solve_batch_device is, and the ranks must pass identical arrays.  The call
+ *   checks this with ONE allgather_i64_host of a 64-bit hash (FNV-1a over nrhs and the bytes of the four arrays, NULL-ness
+ *   included) before the solve's own collectives; it is always made, also by a rank that refuses its own arguments (which then
+ *   returns its own message).  A mismatch is NKP_EINVAL on every rank, naming a rank, with nothing solved and no alltoallv. */
+int nkp_solve_batch_device_ex (nkp_solver *s, int nrhs, const void *d_B, void *d_X, int64_t ldb,
+                               const double *rtol, const double *atol, const int *max_iters, const int *use_guess,
+                               double *berr, int *iters, double *relres);
+
 /* y = A x, exposed for parity and roofline tests (host and device flavours). */
 int nkp_spmv (nkp_solver *s, const double *x, double *y);
 int nkp_spmv_device (nkp_solver *s, const void *d_x, void *d_y);
@@ -402,6 +462,7 @@ int nkp_time_kernel (nkp_solver *s, int which, int arg, int reps, double *avg_ms
  * "trans_index_bytes" (device bytes of the transposed index those calls keep, 0 before the first; part of "device_bytes"),
  * "trans_index_us" (wall time of building it), "trans_index_sent_entries" / "trans_index_recv_entries" (row-distributed: the entries
  * whose products this rank ships to / receives from its peers in every nkp_values_product_trans_dist*; 0 without an index),
+ * "max_iters" (the iteration cap in force: nkp_options.max_iters or what nkp_set_solve_controls put in its place),
  * "batch_steps" (batched operator
  * applications = lockstep Krylov steps of a group of right-hand sides), "batch_width" (K of the last batched group, 0 if
  * none ran); "batch_member_bytes" (device bytes of the K - 1 further sets of work vectors a batched call has made and keeps:

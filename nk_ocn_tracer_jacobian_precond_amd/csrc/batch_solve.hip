@@ -302,18 +302,51 @@ extern "C" int nkp_solve_batch_device (nkp_solver *s, int nrhs, const void *d_B,
 {
    if (!s || nrhs < 0 || (nrhs > 0 && (!d_B || !d_X))) return fail (NKP_EINVAL, "nkp_solve_batch_device: NULL argument");
    if (nrhs > 0 && ldb < s->n) return fail (NKP_EINVAL, "nkp_solve_batch_device: ldb < n");
+   return solve_batch_columns (s, nrhs, d_B, d_X, ldb, nullptr, berr, iters, relres);
+}
+
+// The solver's own controls come back when the call ends, however it ends: the columns' values sit in s->opt (and in the members'
+// own options) only while their systems are solved
+namespace {
+struct ControlsGuard {
+   nkp_solver *s;
+   SolveControls own;
+   explicit ControlsGuard (nkp_solver *solver) : s (solver), own (controls_of (solver)) {}
+   ~ControlsGuard () { controls_into (s, own); }
+   // what column c runs at: its entries where they say something, else the solver's
+   SolveControls column (const ColumnControls *cc, int c) const
+   {
+      SolveControls v = own;
+      if (cc && cc->max_iters && cc->max_iters[c] > 0) v.max_iters = cc->max_iters[c];
+      if (cc && cc->rtol && cc->rtol[c] >= 0.0) v.rtol = cc->rtol[c];
+      if (cc && cc->atol && cc->atol[c] >= 0.0) v.atol = cc->atol[c];
+      return v;
+   }
+};
+}      // namespace
+
+int solve_batch_columns (nkp_solver *s, int nrhs, const void *d_B, void *d_X, int64_t ldb, const ColumnControls *cc, double *berr, int *iters, double *relres)
+{
    if (s->shared->broken) return refactor_broken (s);
    HIPCHK (hipSetDevice (s->device));
    const double *B = (const double *) d_B;
    double *X = (double *) d_X;
    const size_t bytes = (size_t) s->n * sizeof (double);
    int worst = NKP_OK;
+   ControlsGuard ctl (s);
+   auto guess_of = [cc] (int c) { return cc && cc->use_guess && cc->use_guess[c] != 0; };
+   // one system alone, at its column's controls and from its column's guess: the single remainder of a group, every fallback
+   auto alone = [&] (int c) {
+      controls_into (s, ctl.column (cc, c));
+      return nkp_solve_device (s, B + (size_t) c * (size_t) ldb, X + (size_t) c * (size_t) ldb, guess_of (c) ? 1 : 0, berr ? berr + c : nullptr, iters ? iters + c : nullptr,
+                               relres ? relres + c : nullptr);
+   };
    const char *why = batch_unsupported (s);
    if (why || nrhs < 2 || !s->tune.rhs_batch) {
       // one at a time (the reference's loop); `why` names what the batched path does not cover
       if (why && nrhs >= 2 && s->tune.rhs_batch) note_fallback (s, "nkp_solve_batch", why, nrhs);
       for (int c = 0; c < nrhs; c++) {
-         const int status = nkp_solve_device (s, B + (size_t) c * (size_t) ldb, X + (size_t) c * (size_t) ldb, 0, berr ? berr + c : nullptr, iters ? iters + c : nullptr, relres ? relres + c : nullptr);
+         const int status = alone (c);
          if (status < 0) return status;
          if (sev_of (status) > sev_of (worst)) worst = status;
       }
@@ -324,7 +357,7 @@ extern "C" int nkp_solve_batch_device (nkp_solver *s, int nrhs, const void *d_B,
    for (int c0 = 0; c0 < nrhs; c0 += nact) {
       nact = nrhs - c0 < kmax ? nrhs - c0 : kmax;
       if (nact == 1) {
-         const int status = nkp_solve_device (s, B + (size_t) c0 * (size_t) ldb, X + (size_t) c0 * (size_t) ldb, 0, berr ? berr + c0 : nullptr, iters ? iters + c0 : nullptr, relres ? relres + c0 : nullptr);
+         const int status = alone (c0);
          if (status < 0) return status;
          if (sev_of (status) > sev_of (worst)) worst = status;
          continue;
@@ -332,6 +365,7 @@ extern "C" int nkp_solve_batch_device (nkp_solver *s, int nrhs, const void *d_B,
       int K = nact <= 2 ? 2 : nact <= 4 ? 4 : 8;
       const int K_wanted = K;
       int rc = NKP_OK;
+      controls_into (s, ctl.own);      // (a member made now starts from the solver's own values)
       if (!s->dist.on || K > s->dist.agreed_K) {
          rc = batch_prepare (s, K);
          // every further system in flight costs a set of work vectors: out of device memory => narrower interleave, then one at a time
@@ -362,7 +396,10 @@ extern "C" int nkp_solve_batch_device (nkp_solver *s, int nrhs, const void *d_B,
       nkp_solver *mem[NKP_BATCH_MAX] = { s };
       for (int k = 1; k < K; k++) mem[k] = s->batch_members[(size_t) k - 1];
       for (int k = 0; k < nact; k++) {
-         HIPCHK (hipMemsetAsync (mem[k]->x, 0, bytes, s->stream));
+         // every system at its own column's controls (a member follows its owner at every call) and from its own start vector
+         controls_into (mem[k], ctl.column (cc, c0 + k));
+         if (guess_of (c0 + k)) HIPCHK (hipMemcpyAsync (mem[k]->x, X + (size_t) (c0 + k) * (size_t) ldb, bytes, hipMemcpyDeviceToDevice, s->stream));
+         else HIPCHK (hipMemsetAsync (mem[k]->x, 0, bytes, s->stream));
          HIPCHK (hipMemcpyAsync (mem[k]->b, B + (size_t) (c0 + k) * (size_t) ldb, bytes, hipMemcpyDeviceToDevice, s->stream));
          mem[k]->stagnated = false;
       }
@@ -380,14 +417,14 @@ extern "C" int nkp_solve_batch_device (nkp_solver *s, int nrhs, const void *d_B,
             if (q->comm_failed) return fail (NKP_ECOMM, "nkp_solve_batch: a collective of the distributed solve failed");
             if (berr) berr[c0 + k] = be;
          }
-         if (status == NKP_NOT_CONVERGED && q->stagnated && be <= fmax (NKP_BERR_ROUNDING_LEVEL, 1.0e-2 * s->opt.rtol)) status = NKP_OK_BERR;
+         if (status == NKP_NOT_CONVERGED && q->stagnated && be <= fmax (NKP_BERR_ROUNDING_LEVEL, 1.0e-2 * q->opt.rtol)) status = NKP_OK_BERR;
          if (iters) iters[c0 + k] = F[k].its;
          if (relres) relres[c0 + k] = F[k].relres;
          msg (s, 1, "nkp_solve_batch: right-hand side %d: %s after %d iterations, ||b-Ax||/||b|| = %.3e\n", c0 + k,
               status == NKP_OK ? "converged" : status == NKP_OK_BERR ? "at the attainable accuracy (backward error accepted)" : status == NKP_BREAKDOWN ? "breakdown" : "NOT converged", F[k].its, F[k].relres);
          if (q->rhs_class == RHS_NONFINITE || q->rhs_class == RHS_OUT_OF_RANGE) rhs_refused (q->rhs_class, ("nkp_solve_batch: right-hand side " + std::to_string (c0 + k)).c_str ());
          else if (status != NKP_OK) fail (status, "nkp_solve_batch: right-hand side %d: %s after %d iterations (relres %.3e, rtol %.1e)", c0 + k,
-                                     status == NKP_OK_BERR ? "stopped above rtol at the attainable accuracy" : status == NKP_BREAKDOWN ? "breakdown" : "not converged", F[k].its, F[k].relres, s->opt.rtol);
+                                     status == NKP_OK_BERR ? "stopped above rtol at the attainable accuracy" : status == NKP_BREAKDOWN ? "breakdown" : "not converged", F[k].its, F[k].relres, q->opt.rtol);
          if (sev_of (status) > sev_of (worst)) worst = status;
          HIPCHK (hipMemcpyAsync (X + (size_t) (c0 + k) * (size_t) ldb, q->x, bytes, hipMemcpyDeviceToDevice, s->stream));
       }

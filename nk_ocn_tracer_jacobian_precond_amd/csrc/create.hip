@@ -159,6 +159,7 @@ static int new_solver_on_device (const nkp_options &opt, const nkp_tuning &tune,
    if (hipGetDeviceCount (&ndev) != hipSuccess || ndev == 0) return fail (NKP_EDEVICE, "nkp_create: no HIP device available (this library has no CPU fallback)");
    nkp_solver *s = new nkp_solver;
    s->opt = opt;
+   s->created = controls_of (s);
    s->tune = tune;
    s->A.tune = &s->tune;
    s->B.tune = &s->tune;

@@ -116,6 +116,7 @@ extern "C" int64_t nkp_get_int (nkp_solver *s, const char *key)
    if (!strcmp (key, "precond_bytes")) return s->opt.precond == NKP_PRECOND_NONE ? 16 * s->n : (int64_t) (2 * s->B.P + 1) * 8 * s->n + 16 * s->n;
    if (!strcmp (key, "device_bytes")) return (int64_t) s->device_bytes;
    if (!strcmp (key, "precond_steps")) return s->precond_steps;
+   if (!strcmp (key, "max_iters")) return s->opt.max_iters;
    if (!strcmp (key, "equil")) return s->equil ? 1 : 0;
    if (!strcmp (key, "dist_overlap")) return s->dist.overlap ? 1 : 0;
    if (!strcmp (key, "dist_ras")) return s->dist.ras ? 1 : 0;

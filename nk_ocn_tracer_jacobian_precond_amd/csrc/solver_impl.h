@@ -5,6 +5,7 @@
 //   krylov.hip          one right-hand side: operator and preconditioner of a solve, FGMRES, BiCGStab, nkp_solve
 //   krylov_host.cpp     the host arithmetic of FGMRES (krylov_host.h): no HIP, no solver object
 //   batch_solve.hip     K right-hand sides in lockstep (nkp_solve_batch_device); the kernels are batch.hip
+//   solve_controls.hip  rtol, atol and max_iters after creation (nkp_set_solve_controls) and per column (nkp_solve_batch_device_ex)
 //   smooth_exchange.hip the fine-level exchange of a row-distributed cycle (tuning dist_smooth_exchange): kernels, lists, the cycle's hook
 //   inspect.hip         entry points of tests and timing (arrays of the hierarchy and the matrix, single products, nkp_time_kernel)
 //   refactor_api.hip, transpose*.hip, valgrad_api.hip, valprod_api.hip, valprod_trans_dist.hip      new values, A^T, gradient and products by values
@@ -32,8 +33,16 @@
       if (e_ != hipSuccess) return fail (NKP_EDEVICE, "%s failed: %s (%s:%d)", #call, hipGetErrorString (e_), __FILE__, __LINE__); \
    } while (0)
 
+// The three values of a solve that may change after creation (nkp_set_solve_controls).  They live in nkp_solver::opt, where every
+// driver reads them at the start of a solve; `created` keeps what nkp_create was given
+struct SolveControls {
+   int max_iters;
+   double rtol, atol;
+};
+
 struct nkp_solver {
    nkp_options opt;
+   SolveControls created = { 0, 0.0, 0.0 };
    nkp_tuning tune;             // resolved once in nkp_create; the matrix, column-block and hierarchy objects point at it
    int device = 0;
    bool stagnated = false;      // last solve stopped by the attainable-accuracy guard
@@ -359,7 +368,18 @@ NKP_PRIVATE int fg_end_cycle (nkp_solver *s, FgmresState &F);
 NKP_PRIVATE int rhs_refused (int verdict, const char *what);
 // componentwise backward error of s->x for s->b, like SuperLU's berr
 NKP_PRIVATE int backward_error (nkp_solver *s, double *berr);
+inline SolveControls controls_of (const nkp_solver *s) { return { s->opt.max_iters, s->opt.rtol, s->opt.atol }; }
+inline void controls_into (nkp_solver *s, const SolveControls &c) { s->opt.max_iters = c.max_iters; s->opt.rtol = c.rtol; s->opt.atol = c.atol; }
+
 // ---- defined in batch_solve.hip --------------------------------------------------------------------------------------------
+// per-column controls and guess flags of nkp_solve_batch_device_ex: nrhs entries each or NULL; an entry "leave as it is"
+// (negative rtol / atol, max_iters 0) is the solver's own value.  The entries have been validated by the caller
+struct ColumnControls {
+   const double *rtol, *atol;
+   const int *max_iters, *use_guess;
+};
+// nkp_solve_batch_device (cc NULL) and nkp_solve_batch_device_ex after their argument checks: groups, fallbacks, verdicts
+NKP_PRIVATE int solve_batch_columns (nkp_solver *s, int nrhs, const void *d_B, void *d_X, int64_t ldb, const ColumnControls *cc, double *berr, int *iters, double *relres);
 // what keeps a solver's right-hand sides out of the lockstep driver (NULL: nothing), and the one line a batched call that
 // falls back leaves at -D1
 NKP_PRIVATE const char *batch_unsupported (const nkp_solver *s);

@@ -398,15 +398,35 @@ class NkpDistSolver(_solver.NkpSolver):
     def _check_collective(self, rc):           # value_gradient*, values_product*: collective here, local slices in and out
         self._check_dist(rc)
 
-    def solve_many(self, B, raise_on_fail=True):
+    def set_solve_controls(self, rtol=None, atol=None, max_iters=None):
+        """nkp_set_solve_controls, COLLECTIVE: every rank calls it with the same values (three allgathers: rtol, atol, max_iters).
+        Ranks that differ, or one whose values are refused, make every rank raise NkpError (code -1) naming a rank, and no
+        rank's solver changes."""
+        super().set_solve_controls(rtol, atol, max_iters)
+
+    def reset_solve_controls(self):
+        """nkp_set_solve_controls (s, NULL), COLLECTIVE like set_solve_controls."""
+        super().reset_solve_controls()
+
+    def solve_batch_device_ex(self, d_B, d_X, nrhs, ldb, rtol=None, atol=None, max_iters=None, use_guess=None, raise_on_fail=True):
+        """nkp_solve_batch_device_ex on this rank's device-resident rows (ldb >= m_loc), collective: every rank passes the same
+        per-column rtol / atol / max_iters / use_guess (one allgather of their hash checks it before anything is solved)."""
+        return super().solve_batch_device_ex(d_B, d_X, nrhs, ldb, rtol, atol, max_iters, use_guess, raise_on_fail)
+
+    def _check_solve(self, rc, raise_on_fail):
+        if rc < 0 or (raise_on_fail and rc != 0):
+            self._check_dist(rc)
+
+    def solve_many(self, B, raise_on_fail=True, X0=None, rtol=None, atol=None, max_iters=None):
         """nkp_solve with nrhs = B.shape[0] right-hand sides, collective: every rank calls it with the same number of rows,
         each passing its own m_loc entries of every vector (ldb = m_loc).  Groups of 2 / 4 (8 with rhs_batch = 8) systems run in
         lockstep with the collectives of one system per Krylov step; get_int("batch_steps") / ("batch_width") /
-        ("dist_alltoallv_calls") / ("dist_allreduce_calls") count them.  Returns (X, infos) for the local rows."""
+        ("dist_alltoallv_calls") / ("dist_allreduce_calls") count them.  Returns (X, infos) for the local rows.
+        X0 (this rank's rows of the initial guesses) / rtol / atol / max_iters: as NkpSolver.solve_many, the same on every rank."""
         B = np.asarray(B, np.float64)
         if B.ndim != 2 or B.shape[1] != self.n:
             raise ValueError(f"B must have shape (nrhs, {self.n}): this rank's rows of every right-hand side")
-        return super().solve_many(B, raise_on_fail)
+        return super().solve_many(B, raise_on_fail, X0, rtol, atol, max_iters)
 
     def solve_batch_device(self, d_B, d_X, nrhs, ldb, raise_on_fail=True):
         """nkp_solve_batch_device on this rank's device-resident rows (ldb >= m_loc); collective like solve_many."""

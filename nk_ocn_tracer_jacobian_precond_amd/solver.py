@@ -35,6 +35,7 @@ ABI_SYMBOLS = [
     "nkp_values_product", "nkp_values_product_device", "nkp_solve_tangent_device", "nkp_matrix_array",
     "nkp_values_product_trans", "nkp_values_product_trans_device",
     "nkp_values_product_trans_dist", "nkp_values_product_trans_dist_device",
+    "nkp_set_solve_controls", "nkp_get_solve_controls", "nkp_solve_batch_device_ex",
 ]
 
 _ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p)
@@ -79,6 +80,12 @@ class NkpOptions(C.Structure):
     ]
 
 
+class NkpSolveControls(C.Structure):
+    """nkp_solve_controls (include/nkp.h): rtol, atol and max_iters of an existing solver; max_iters 0 and a negative tolerance
+    leave that value as it is."""
+    _fields_ = [("struct_size", C.c_int), ("max_iters", C.c_int), ("rtol", C.c_double), ("atol", C.c_double)]
+
+
 class NkpError(RuntimeError):
     def __init__(self, code, message):
         super().__init__(f"nkp error {code}: {message}")
@@ -107,6 +114,9 @@ def load_library(path=None):
     lib.nkp_solve.argtypes = [vp, f64p, C.c_int, C.c_int64, f64p, C.POINTER(C.c_int), f64p]
     lib.nkp_solve_device.argtypes = [vp, vp, vp, C.c_int, f64p, C.POINTER(C.c_int), f64p]
     lib.nkp_solve_batch_device.argtypes = [vp, C.c_int, vp, vp, C.c_int64, f64p, C.POINTER(C.c_int), f64p]
+    lib.nkp_set_solve_controls.argtypes = [vp, C.POINTER(NkpSolveControls)]
+    lib.nkp_get_solve_controls.argtypes = [vp, C.POINTER(NkpSolveControls)]
+    lib.nkp_solve_batch_device_ex.argtypes = [vp, C.c_int, vp, vp, C.c_int64, f64p, f64p, C.POINTER(C.c_int), C.POINTER(C.c_int), f64p, C.POINTER(C.c_int), f64p]
     lib.nkp_spmv.argtypes = [vp, f64p, f64p]
     lib.nkp_spmv_device.argtypes = [vp, vp, vp]
     lib.nkp_precond_apply.argtypes = [vp, f64p, f64p]
@@ -339,14 +349,92 @@ class NkpSolver:
         self._check(rc, (0,) if raise_on_fail else (0, 1, 2, 3))
         return [dict(status=rc, iters=iters[c], relres=relres[c], berr=berr[c]) for c in range(nrhs)]
 
-    def solve_many(self, B, raise_on_fail=True):
-        """nkp_solve with nrhs = B.shape[0] host right-hand sides (rows of B); returns (X, infos)."""
+    def set_solve_controls(self, rtol=None, atol=None, max_iters=None):
+        """nkp_set_solve_controls: from now on every solve on this handle runs bit for bit like one on a solver created with these
+        values; None leaves a value as it is.  Clones and the transposed handle keep their own.  Collective on a row-distributed
+        solver: the same values on every rank."""
+        c = NkpSolveControls(C.sizeof(NkpSolveControls), 0 if max_iters is None else int(max_iters), -1.0 if rtol is None else float(rtol),
+                             -1.0 if atol is None else float(atol))
+        if max_iters is not None and c.max_iters <= 0:
+            raise ValueError("max_iters must be positive (None leaves it as it is)")
+        if (rtol is not None and c.rtol < 0.0) or (atol is not None and c.atol < 0.0):
+            raise ValueError("rtol and atol must be >= 0 (None leaves them as they are)")
+        self._check_collective(self._lib.nkp_set_solve_controls(self._h, C.byref(c)))
+
+    def reset_solve_controls(self):
+        """nkp_set_solve_controls (s, NULL): back to the values the handle began with (those of its creation)."""
+        self._check_collective(self._lib.nkp_set_solve_controls(self._h, None))
+
+    def get_solve_controls(self):
+        """nkp_get_solve_controls: dict(rtol, atol, max_iters) in force on this handle."""
+        c = NkpSolveControls(C.sizeof(NkpSolveControls), 0, 0.0, 0.0)
+        self._check(self._lib.nkp_get_solve_controls(self._h, C.byref(c)))
+        return dict(rtol=c.rtol, atol=c.atol, max_iters=c.max_iters)
+
+    @staticmethod
+    def _per_column(values, nrhs, ctype, keep, what):
+        """one entry per right-hand side for nkp_solve_batch_device_ex: None = NULL, a scalar = that value for every column, None
+        inside a sequence = the solver's"""
+        if values is None:
+            return None
+        seq = [values] * nrhs if np.isscalar(values) else list(values)
+        if len(seq) != nrhs:
+            raise ValueError(f"{what} needs one entry per right-hand side ({nrhs}), got {len(seq)}")
+        return (ctype * nrhs)(*[keep if v is None else v for v in seq])
+
+    def solve_batch_device_ex(self, d_B, d_X, nrhs, ldb, rtol=None, atol=None, max_iters=None, use_guess=None, raise_on_fail=True):
+        """nkp_solve_batch_device_ex: solve_batch_device with per-column rtol / atol / max_iters (sequences of nrhs entries, a scalar
+        for all columns, or None = the solver's) and per-column initial guesses (use_guess[c] true: column c of d_X holds x0).
+        Returns one info dict per right-hand side."""
+        berr, relres, iters = (C.c_double * nrhs)(), (C.c_double * nrhs)(), (C.c_int * nrhs)()
+        rt = self._per_column(rtol, nrhs, C.c_double, -1.0, "rtol")
+        at = self._per_column(atol, nrhs, C.c_double, -1.0, "atol")
+        mi = self._per_column(max_iters, nrhs, C.c_int, 0, "max_iters")
+        ug = self._per_column(None if use_guess is None else [int(bool(g)) for g in use_guess], nrhs, C.c_int, 0, "use_guess")
+        rc = self._lib.nkp_solve_batch_device_ex(self._h, nrhs, C.c_void_p(d_B), C.c_void_p(d_X), ldb, rt, at, mi, ug, berr, iters, relres)
+        self._check_solve(rc, raise_on_fail)
+        return [dict(status=rc, iters=iters[c], relres=relres[c], berr=berr[c]) for c in range(nrhs)]
+
+    def _check_solve(self, rc, raise_on_fail):
+        self._check(rc, (0,) if raise_on_fail else (0, 1, 2, 3))
+
+    def solve_many(self, B, raise_on_fail=True, X0=None, rtol=None, atol=None, max_iters=None):
+        """nkp_solve with nrhs = B.shape[0] host right-hand sides (rows of B); returns (X, infos).  With initial guesses X0 (rows
+        like B's; a row of None = start from zero) or per-column rtol / atol / max_iters (as for solve_batch_device_ex) the
+        vectors are staged on the device through the HIP runtime the library links and nkp_solve_batch_device_ex runs."""
+        if X0 is not None or rtol is not None or atol is not None or max_iters is not None:
+            return self._solve_many_ex(B, X0, rtol, atol, max_iters, raise_on_fail)
         X = np.array(B, np.float64, order="C", copy=True)
         nrhs = X.shape[0]
         berr, relres, iters = (C.c_double * nrhs)(), (C.c_double * nrhs)(), (C.c_int * nrhs)()
         rc = self._lib.nkp_solve(self._h, _p(X, C.c_double), nrhs, X.shape[1], berr, iters, relres)
         self._check(rc, (0,) if raise_on_fail else (0, 1, 2, 3))
         return X, [dict(status=rc, iters=iters[c], relres=relres[c], berr=berr[c]) for c in range(nrhs)]
+
+    def _solve_many_ex(self, B, X0, rtol, atol, max_iters, raise_on_fail):
+        B = np.ascontiguousarray(np.asarray(B, np.float64))
+        if B.ndim != 2 or B.shape[1] != self.n:
+            raise ValueError(f"B must have shape (nrhs, {self.n})")
+        nrhs, n = B.shape
+        X = np.zeros_like(B)
+        guess = None
+        if X0 is not None:
+            if len(X0) != nrhs:
+                raise ValueError(f"X0 needs one row per right-hand side ({nrhs})")
+            guess = [x0 is not None for x0 in X0]
+            for c, x0 in enumerate(X0):
+                if x0 is not None:
+                    X[c] = np.asarray(x0, np.float64).reshape(n)
+        bufs = []
+        try:
+            d_b, d_x = _device_array(bufs, B), _device_array(bufs, X)
+            infos = self.solve_batch_device_ex(d_b, d_x, nrhs, n, rtol, atol, max_iters, guess, raise_on_fail)
+            if X.nbytes:
+                _hip_check(_hip().hipMemcpy(C.c_void_p(X.ctypes.data), C.c_void_p(d_x), C.c_size_t(X.nbytes), 2))
+        finally:
+            for q in bufs:
+                _hip().hipFree(C.c_void_p(q))
+        return X, infos
 
     def refactor(self, val, rebuild=False):
         """nkp_refactor: new values (nnz, in the CSR order the solver was created with) on the same pattern.  The hierarchy keeps

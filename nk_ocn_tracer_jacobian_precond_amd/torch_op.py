@@ -69,6 +69,7 @@ class NkpTorchSolver:
         self.torch = torch
         self.solver = solver
         self.values = None
+        self._controls = {}                  # what set_solve_controls was given, for a transposed handle that is made later
         solver.set_stream(torch.cuda.current_stream().cuda_stream)
         self._ops = _make_functions(torch)
         self._fn = self._ops.Solve
@@ -83,6 +84,30 @@ class NkpTorchSolver:
         self._check(val, (self.solver.nnz,), "val")
         self.solver.refactor_device(val.data_ptr())
         self.values = val
+
+    def set_solve_controls(self, rtol=None, atol=None, max_iters=None):
+        """nkp_set_solve_controls on the forward solver and on its transposed handle -- now when it exists, else once the first
+        backward pass makes it -- so the solves of a backward pass run at the tolerance the driver chose for the forward ones.
+        None leaves a value as it is on either handle."""
+        self.solver.set_solve_controls(rtol, atol, max_iters)
+        self._controls.update({k: v for k, v in (("rtol", rtol), ("atol", atol), ("max_iters", max_iters)) if v is not None})
+        t = getattr(self.solver, "_trans", None)
+        if t is not None:
+            t.set_solve_controls(rtol, atol, max_iters)
+            t._controls_seen = dict(self._controls)
+
+    def get_solve_controls(self):
+        """dict(forward=..., transposed=...) of NkpSolver.get_solve_controls; transposed is None while there is no such handle."""
+        t = getattr(self.solver, "_trans", None)
+        return dict(forward=self.solver.get_solve_controls(), transposed=None if t is None else t.get_solve_controls())
+
+    def transposed(self):
+        """the solver's transposed handle (made at the first call) at the controls this wrapper was given"""
+        t = self.solver.transposed()
+        if self._controls and getattr(t, "_controls_seen", None) != self._controls:
+            t.set_solve_controls(**self._controls)
+            t._controls_seen = dict(self._controls)
+        return t
 
     def solve(self, B):
         """X = A^-1 B for the K rows of B, differentiable with respect to B and to the tensor given to set_values."""
@@ -141,7 +166,7 @@ def _make_functions(torch):
         def forward(ctx, G, val, owner):
             s = owner.solver
             Lam = torch.empty_like(G)
-            s.transposed().solve_batch_device(G.data_ptr(), Lam.data_ptr(), G.shape[0], s.n)
+            owner.transposed().solve_batch_device(G.data_ptr(), Lam.data_ptr(), G.shape[0], s.n)
             ctx.owner = owner
             ctx.save_for_backward(Lam, val)
             return Lam
