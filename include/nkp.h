@@ -519,7 +519,19 @@ int nkp_refactor_dist (nkp_solver *s, const double *val_loc, int flags);
 int nkp_refactor_dist_device (nkp_solver *s, const void *d_val_loc, int flags);
 
 /* Use an externally owned HIP stream (hipStream_t cast to void*) instead of the solver's own;
- * NULL = the device's default stream. */
+ * NULL = the device's default stream.  The contract (tests/test_gpu_stream_order.py pins it down on a non-blocking stream
+ * behind pending work of the caller's):
+ *   - every device entry point reads its device operands in order on that stream: work the caller enqueued there before the
+ *     call, the producer of an operand included, has run before the library reads anything, and the caller needs no
+ *     synchronisation of its own in front of the call.  No operand of the caller's is read on another stream, the null stream
+ *     included (where a synchronous copy would run), nor before the stream has reached the call;
+ *   - results are complete on return: a device result (X, Y, g, dX) may be read at once from any stream or from the host;
+ *   - the batch members of nkp_solve_batch_device* and the transposed handle of nkp_transpose (with its own batch members)
+ *     follow the owner's stream, whether they were made before or after this call, and across a refactor that remakes them;
+ *   - a clone (nkp_clone) keeps a stream of its own until it is given one with this call;
+ *   - the solver must be idle when it is moved: no call in flight on it, on its transposed handle or (row-distributed) on its
+ *     peers, and the caller keeps the stream alive for as long as the solver uses it.
+ * NKP_EINVAL on a transposed handle: set the stream of the solver it was transposed from. */
 int nkp_set_stream (nkp_solver *s, void *hip_stream);
 
 void nkp_destroy (nkp_solver *s);

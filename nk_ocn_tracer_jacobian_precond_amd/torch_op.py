@@ -42,7 +42,9 @@ class NkpTorchSolver:
 
     Streams: the constructor puts the solver (and with it its transposed solver) on torch's current stream,
     set_stream(torch.cuda.current_stream().cuda_stream), so the library's kernels are ordered with the caller's own and no
-    extra synchronisation is needed.  Use the wrapper under the stream it was constructed under.
+    extra synchronisation is needed.  Use the wrapper under the stream it was constructed under.  Side streams are covered by a
+    test: tests/test_gpu_stream_order.py runs set_values, solve, backward, a Hessian-vector product and a forward-mode tangent
+    under torch.cuda.stream(S) with every operand still being produced on S when the library is entered.
 
     The backward pass calls transposed() once -- the handle is kept by the solver and follows set_values -- and runs one
     batched solve there.  Forward mode runs one product with dval on the pattern (only when val carries a tangent) and one batched
