@@ -10,23 +10,27 @@ comparison allows 100 times that (FMA contraction, the reduction tree):
   f64_cgs2   f64, two                        4.86e-15   n524291-none-k2-reorth1-f32_0-m20         5.0e-15   5.0e-13
   f32_cgs1   f32, one                        4.75e-11   n513-none-k17-reorth0-f32_1-m20           5.0e-11   5.0e-09
   f32_cgs2   f32, two                        3.24e-11   n513-none-k17-reorth1-f32_1-m20           3.5e-11   3.5e-09
-  equil      row equilibration (any basis)   3.96e-15   n2001_rows-jacobi-k9-reorth0-f32_1-m20    4.0e-15   4.0e-13
+  equil      row equilibration (any basis)   9.57e-15   n524291_rows-jacobi-k2-reorth0-f32_0-m20  1.0e-14   1.0e-12
   bicgstab   BiCGStab                        1.32e-15   n2001-jacobi-k1-bicgstab                  1.5e-15   1.5e-13
+  clamp510   f64, two, one cycle of 510      4.97e-12   diag1025-none-k510-reorth1-f32_0-m510     5.0e-12   5.0e-10
 
 (An f32 basis is orthonormal to 6e-8 only; by k = 17 without a preconditioner that has grown into 5e-11 of x.  Below k = 10 the
-f32 classes measure 5e-15.)  Measured on an MI355X, the largest ||dx|| / ||x|| of a run is 1.5 % of its tolerance.
+f32 classes measure 5e-15.  The equil class measured 3.96e-15 at n2001_rows-jacobi-k9-reorth0-f32_1-m20 before the runs on
+n524291_rows joined it.)  Measured on an MI355X, the largest ||dx|| / ||x|| of a run is 1.5 % of its tolerance.
 
 Matrices.  column_grid (n, seed): ragged water columns (1 .. 12 rows) on a lattice, rows numbered column by column; a row
 couples to its vertical neighbours and to the same level of the four neighbouring columns with positive, unsymmetric entries
 and a_ii = -((1 + shift) sum_j |a_ij| + (0.05 .. 0.15)): the sign convention of a tracer tendency Jacobian (what the
 hierarchy's low-order twin expects), -A a strictly diagonally dominant M-matrix, so every preconditioner of the library works on it and restart 30 needs a few tens of iterations to 1e-10.  The last column is cut so that n is met exactly.
+column_lattice (ni, nj, seed): the same matrix on ni x nj columns of one depth (2), the last one a row shorter.
 
 Sizes, from the kernels of csrc/blas1.hip (B1_THREADS = 256, two elements per thread):
   n = 1, 2, 3          one element; the scalar tail of an odd n (i + 1 < n fails); a pair and a tail
   n = 511, 513         one block of 512 elements short of one, and just over (a second block with one element)
   n = 2001             ld = (n + 63) & ~63 = 2048 padding, four blocks, odd tail
   n = 524 291          red_grid caps at NKP_RED_BLOCKS = 1024 blocks of 512 elements = 524 288: the first odd n whose
-                       grid-stride loop takes a second pass
+                       grid-stride loop takes a second pass; the streams of one element per thread (axpby, vmul, gather) run
+                       on twice as many blocks and wrap at the same n
   k = 1, 3, 4, 5, 8, 9, 16, 17   update_w unrolls by 4 (remainders 1, 3, 0, 1); NKP_DOT_CHUNK = 8 gives one chunk, two, three
 """
 from __future__ import annotations
@@ -71,16 +75,11 @@ class Case:
                 + 2.0 * (self.n + 2) * 2.0 ** -53 * relres_ref)
 
 
-def column_grid(n, seed, shift=0.35, kmax=12):
-    """(A, blk_start, col_i, col_j) of the module docstring."""
-    rng = np.random.default_rng(seed)
-    depths = rng.integers(1, kmax + 1, size=n)
-    ends = np.cumsum(depths)
-    ncol = int(np.searchsorted(ends, n)) + 1
-    depths = depths[:ncol].copy()
-    depths[-1] -= ends[ncol - 1] - n
+def _columns_matrix(depths, ni, rng, shift):
+    """(A, blk_start, col_i, col_j) of water columns of the given depths, ni to a lattice row (module docstring)."""
+    ncol = depths.size
+    n = int(depths.sum())
     blk = np.concatenate([[0], np.cumsum(depths)]).astype(np.int64)
-    ni = max(1, int(np.sqrt(ncol)))
     col_of = np.repeat(np.arange(ncol), depths)
     rows = np.arange(n)
     lev = rows - blk[col_of]
@@ -109,6 +108,26 @@ def column_grid(n, seed, shift=0.35, kmax=12):
     return A, blk.astype(np.int32), (cols % ni).astype(np.int32), (cols // ni).astype(np.int32)
 
 
+def column_grid(n, seed, shift=0.35, kmax=12):
+    """(A, blk_start, col_i, col_j) of the module docstring."""
+    rng = np.random.default_rng(seed)
+    depths = rng.integers(1, kmax + 1, size=n)
+    ends = np.cumsum(depths)
+    ncol = int(np.searchsorted(ends, n)) + 1
+    depths = depths[:ncol].copy()
+    depths[-1] -= ends[ncol - 1] - n
+    return _columns_matrix(depths, max(1, int(np.sqrt(ncol))), rng, shift)
+
+
+def column_lattice(ni, nj, seed, shift=0.35, depth=2):
+    """column_grid's matrix on ni x nj water columns of one depth, the last column cut to depth - 1: n = ni nj depth - 1, odd
+    for an even depth (the scalar tail of the kernels that take two elements per thread).  The smallest shape whose hierarchy
+    has two levels beyond the grid caps of csrc/blas1.hip (tests/test_gpu_grid_caps.py)."""
+    depths = np.full(ni * nj, depth, np.int64)
+    depths[-1] -= 1
+    return _columns_matrix(depths, ni, np.random.default_rng(seed), shift)
+
+
 # ---------------------------------------------------------------- the matrices
 SHIFT = 0.15          # restart 30 to 1e-10: 54 iterations without preconditioner, 25 with column Jacobi (n = 513 and 2001)
 
@@ -127,9 +146,9 @@ def case(name):
         d = np.array([1.0, 2.5, 4.0])[np.arange(n) % 3]
         b = _rhs(n, 31)
         return Case(name, sp.diags(d).tocsr(), np.arange(n + 1), b, exact=b / d)
-    if name == "n2001_rows":
-        # the rows of n2001 scaled by 10^(-2 .. 2): what row equilibration is for
-        base = case("n2001")
+    if name in ("n2001_rows", "n524291_rows"):
+        # the rows of n2001 (n524291) scaled by 10^(-2 .. 2): what row equilibration is for
+        base = case(name[:-len("_rows")])
         D = 10.0 ** np.random.default_rng(41).uniform(-2.0, 2.0, size=base.n)
         return Case(name, sp.diags(D) @ base.A, base.blk, D * base.b, base.col_i, base.col_j)
     if name == "n2001_fast":
@@ -137,6 +156,16 @@ def case(name):
         # f32 basis with one Gram-Schmidt pass runs 1e-4 ahead of the true residual (INNER_SCALE_RUN)
         A, blk, ci, cj = column_grid(2001, seed=7, shift=0.6)
         return Case(name, A, blk, _rhs(2001, 1), ci, cj)
+    if name == "diag1025":
+        # a diagonal of 1025 values spread geometrically over six decades, b with a component in every one: GMRES (510) is still
+        # converging at step 510 (relres 5e-3), so the last basis vectors carry weight in x (clamp_runs)
+        n = 1025
+        return Case(name, sp.diags(np.geomspace(1.0, 1.0e6, n)).tocsr(), np.arange(n + 1), _rhs(n, 31))
+    if name == "lattice1026":
+        # 1026 x 1026 columns of depth 2, the last one of depth 1: n = 2 105 351 (odd).  With col_i / col_j the hierarchy merges
+        # 2 x 2 columns per level: 526 338 rows on level 1, both beyond the grid caps (tests/test_gpu_grid_caps.py)
+        A, blk, ci, cj = column_lattice(1026, 1026, seed=7, shift=SHIFT)
+        return Case(name, A, blk, _rhs(A.shape[0], 1), ci, cj)
     n = int(name[1:])
     A, blk, ci, cj = column_grid(n, seed=7, shift=SHIFT)
     return Case(name, A, blk, _rhs(n, 1), ci, cj)
@@ -185,9 +214,10 @@ ML_SMOOTH = 1
 class Run:
     """One solve: case, preconditioner, options and where it is cut (k = None: to convergence)."""
 
-    def __init__(self, case, precond, k, reorth=0, f32=0, equil=0, steps=1, restart=20, krylov="fgmres", rtol=1e-10):
+    def __init__(self, case, precond, k, reorth=0, f32=0, equil=0, steps=1, restart=20, krylov="fgmres", rtol=1e-10, cls=None):
         self.case, self.precond, self.k, self.reorth, self.f32 = case, precond, k, reorth, f32
         self.equil, self.steps, self.restart, self.krylov, self.rtol = equil, steps, restart, krylov, rtol
+        self.own_cls = cls
 
     @property
     def max_iters(self):
@@ -195,6 +225,8 @@ class Run:
 
     @property
     def cls(self):
+        if self.own_cls:
+            return self.own_cls
         if self.krylov == "bicgstab":
             return "bicgstab"
         if self.equil:
@@ -248,6 +280,10 @@ def truncated_runs():
     pairs("n2001", JACOBI, [9, 17], restart=4)              # cut inside the third and the fifth restart cycle
     pairs("n524291", JACOBI, [9])
     pairs("n524291", NONE, [2], [(0, 1), (1, 0)])
+    # the streams of one element per thread (axpby_kernel, vmul_kernel) on a grid of 2 * NKP_RED_BLOCKS blocks wrap from
+    # n = 524 289 on: the defect-correction axpby of chained cycles, and row equilibration on w, on v_j and on the restart residual
+    pairs("n524291", JACOBI, [2], steps=2)
+    pairs("n524291_rows", JACOBI, [2], [(0, 0), (1, 1)], equil=1)
     return runs
 
 
@@ -273,7 +309,26 @@ def bicgstab_runs():
     runs = [Run("n2001", JACOBI, k, krylov="bicgstab", restart=2) for k in (1, 2, 3, 5, None)]
     runs += [Run("n2001", MULTILEVEL, k, krylov="bicgstab", restart=2) for k in (1, 2, 3, None)]
     runs.append(Run("n513", JACOBI, 3, krylov="bicgstab", restart=2, steps=2))
+    runs.append(Run("n524291", JACOBI, 2, krylov="bicgstab", restart=2))          # axpby_kernel in every call form, launch_fill of p and v, wrapped
     return runs
+
+
+RESTART_CLAMP = 510          # NKP_MAX_K - 2 (csrc/create.hip, check_arguments)
+
+
+def clamp_runs():
+    """One restart cycle of the longest length nkp_create allows, run to its end: update_w_kernel and launch_axpy_multi with
+    k = 510 (hs[NKP_MAX_K]), 64 multi-dot chunks.  rtol is out of reach but inside the range of a solve (rtol = 0 is refused:
+    a target below 2^-480).  Candidates measured on the CPU (largest ||dx|| / ||x|| between the two arithmetics of
+    tests/test_krylov_reference.py; what leaving basis vector 509 out of the update of w changes in x):
+      n513, n2001 (column_grid, no preconditioner)      2.3e-16, 2.2e-16    0       at rounding level by step 100
+      diagonal 1 .. 513 linear, n = 513                 6.3e-16             0       at rounding level before step 300
+      diagonal 1 .. 1e6 geometric, n = 513              3.7e-12             0       at rounding level before step 500
+      diagonal 1 .. 1e9 geometric, n = 513              9.2e-10             0       at rounding level before step 500
+      diagonal 1 .. 1e6 geometric, n = 2001             3.3e-12             3.0e-3  relres 0.11 at step 510
+      diagonal 1 .. 1e6 geometric, n = 1025             3.3e-12             3.7e-4  relres 5.3e-3 at step 510: taken (diag1025)
+    Every one is determined to better than 1e-8; only the last two still use their last basis vectors."""
+    return [Run("diag1025", NONE, RESTART_CLAMP, reorth=1, f32=0, restart=RESTART_CLAMP, rtol=1e-100, cls="clamp510")]
 
 
 def reference(run, A, M, arith=None, pythagoras=False, x0=None):
@@ -294,8 +349,9 @@ TOL = {
     "f64_cgs2": (5.0e-15, 5.0e-13),
     "f32_cgs1": (5.0e-11, 5.0e-09),
     "f32_cgs2": (3.5e-11, 3.5e-09),
-    "equil": (4.0e-15, 4.0e-13),
+    "equil": (1.0e-14, 1.0e-12),
     "bicgstab": (1.5e-15, 1.5e-13),
+    "clamp510": (5.0e-12, 5.0e-10),
 }
 
 

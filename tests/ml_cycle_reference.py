@@ -18,7 +18,12 @@ Two further modes exist only to size tolerances: blocks="inverse" solves the col
 instead of LU (the same mathematics in another rounding), factors="f32" rounds the LU factors of every block and the coarsest
 inverse to f32 and widens them again (what f32 storage of the factors does to a solve).  With f32 storage the device factors
 the blocks of the f64 operator BEFORE it rounds operator and factors to f32, each on its own: a level that carries that f64
-operator (with_exact_blocks) factors its blocks likewise in the factors="f32" mode."""
+operator (with_exact_blocks) factors its blocks likewise in the factors="f32" mode.
+
+Two evaluations of the same half sweep: the per-column one (a Python loop over the water columns; every mode) and, with
+grouped=True, one that stacks the blocks of a colour by size and solves each stack in one call (np.linalg.solve, or the
+stacked explicit inverses for blocks="inverse"), applied with one scatter -- the same blocks, the same LAPACK routines, for
+hierarchies of 10^5 to 10^6 columns (tests/test_gpu_grid_caps.py).  The grouped one has no factors="f32" mode."""
 import numpy as np
 import scipy.linalg as sla
 import scipy.sparse as sp
@@ -112,55 +117,116 @@ class CycleLevel:
             self._solvers[key] = parts
         return self._solvers[key]
 
+    def grouped_solver(self, c, blocks):
+        """The blocks of colour c stacked by size: [(idx, B)], idx (nb, s) the rows of nb columns of s rows each, B (nb, s, s)
+        their dense blocks, or the inverses of those for blocks="inverse".  What blocks() cuts out of Bd, without the loop."""
+        key = (c, blocks, "grouped")
+        if key not in self._solvers:
+            parts = []
+            R = self.rows[c]
+            if R.size:
+                cols = self.col_of[R]
+                o = np.argsort(cols, kind="stable")
+                Rs = R[o]
+                start = np.concatenate([[0], np.flatnonzero(np.diff(cols[o])) + 1])
+                size = np.diff(np.concatenate([start, [Rs.size]]))
+                blk_of = np.repeat(np.arange(start.size), size)              # of every entry of Rs
+                pos = np.full(self.n, -1, np.int64)                          # place of a row inside its block; -1: another colour
+                pos[Rs] = np.arange(Rs.size) - start[blk_of]
+                blk = np.full(self.n, -1, np.int64)
+                blk[Rs] = blk_of
+                E = self.Bd.tocoo()
+                keep = (blk[E.row] >= 0) & (blk[E.row] == blk[E.col])
+                er, ec, ev = E.row[keep], E.col[keep], E.data[keep]
+                for s in np.unique(size):
+                    which = np.flatnonzero(size == s)
+                    slot = np.full(start.size, -1, np.int64)
+                    slot[which] = np.arange(which.size)
+                    idx = Rs[start[which][:, None] + np.arange(s)[None, :]]
+                    B = np.zeros((which.size, s, s))
+                    e = slot[blk[er]] >= 0
+                    np.add.at(B, (slot[blk[er[e]]], pos[er[e]], pos[ec[e]]), ev[e])      # Bd sums repeated entries too
+                    parts.append((idx, np.linalg.inv(B) if blocks == "inverse" else B))
+            self._solvers[key] = parts
+        return self._solvers[key]
 
-def _half(lv, x, b, c, blocks, factors):
+
+def _half(lv, x, b, c, blocks, factors, grouped=False):
     R = lv.rows[c]
     if not R.size:
         return
     res = b - lv.L @ x                                  # only the rows of colour c are used: they do not change below
+    if grouped:
+        assert factors == "f64"
+        for idx, B in lv.grouped_solver(c, blocks):
+            rhs = res[idx][:, :, None]
+            x[idx] += ((B @ rhs) if blocks == "inverse" else np.linalg.solve(B, rhs))[:, :, 0]
+        return
     for idx, f in lv.solver(c, blocks, factors):
         x[idx] += f @ res[idx] if blocks == "inverse" else sla.lu_solve(f, res[idx], check_finite=False)
 
 
-def _sweep(lv, x, b, reverse, blocks, factors):
+def _sweep(lv, x, b, reverse, blocks, factors, grouped=False):
     for c in ((1, 0) if reverse else (0, 1)):
-        _half(lv, x, b, c, blocks, factors)
+        _half(lv, x, b, c, blocks, factors, grouped)
+
+
+class Glue:
+    """The vector operations between the cycle's sweeps, one method per launch of csrc/mlcycle.hip (launch_gather,
+    launch_scatter, launch_restrict_sum, launch_prolong_add, fill_x; l is the FINE level of a transfer), so that a test can
+    restate one of them wrongly and see what its tolerance sees (tests/test_gpu_grid_caps.py)."""
+
+    def gather(self, r, perm0):
+        return r[perm0]
+
+    def scatter(self, x, perm0):
+        z = np.empty_like(x)
+        z[perm0] = x
+        return z
+
+    def restrict(self, l, P, res):
+        return P.T @ res
+
+    def prolong(self, l, P, xc, omega, x):
+        x += omega * (P @ xc)
+
+    def fill(self, l, n):
+        return np.zeros(n)
 
 
 def cycle(levels, r, nu=3, nu_coarse=0, coarse_from=2, gamma_from=0, gamma_to=0, omega=1.1, coarsest_sweeps=30, blocks="lu",
-          factors="f64"):
-    assert blocks in ("lu", "inverse") and factors in ("f64", "f32")
+          factors="f64", grouped=False, glue=None):
+    assert blocks in ("lu", "inverse") and factors in ("f64", "f32") and not (grouped and factors == "f32")
     last = len(levels) - 1
+    glue = glue or Glue()
 
     def cyc(l, b):
         lv = levels[l]
-        x = np.zeros(lv.n)
+        if l == last and lv.coarse_inv is not None:
+            inv = lv.coarse_inv
+            if factors == "f32":
+                inv = inv.astype(np.float32).astype(np.float64)
+            return inv @ b
+        x = glue.fill(l, lv.n)
         if l == last:
-            if lv.coarse_inv is not None:
-                inv = lv.coarse_inv
-                if factors == "f32":
-                    inv = inv.astype(np.float32).astype(np.float64)
-                return inv @ b
             for s in range(coarsest_sweeps if coarsest_sweeps > 0 else 30):
-                _sweep(lv, x, b, s % 2 == 1, blocks, factors)
+                _sweep(lv, x, b, s % 2 == 1, blocks, factors, grouped)
             return x
         nu_l = nu_coarse if (nu_coarse >= 1 and l >= coarse_from) else nu
         for _ in range(nu_l):
-            _sweep(lv, x, b, False, blocks, factors)
+            _sweep(lv, x, b, False, blocks, factors, grouped)
         for _ in range(2 if gamma_from <= l < gamma_to else 1):
-            rc = lv.P.T @ (b - lv.L @ x)
-            x += omega * (lv.P @ cyc(l + 1, rc))
+            rc = glue.restrict(l, lv.P, b - lv.L @ x)
+            glue.prolong(l, lv.P, cyc(l + 1, rc), omega, x)
         for _ in range(nu_l):
-            _sweep(lv, x, b, True, blocks, factors)
+            _sweep(lv, x, b, True, blocks, factors, grouped)
         return x
 
     r = np.asarray(r, np.float64)
     perm0 = levels[0].perm0
     if perm0 is None:
         return cyc(0, r.copy())
-    z = np.empty_like(r)
-    z[perm0] = cyc(0, r[perm0])
-    return z
+    return glue.scatter(cyc(0, glue.gather(r, perm0)), perm0)
 
 
 def relative_difference(a, b):
@@ -171,14 +237,15 @@ class Reference:
     """(tests/test_gpu_cycle_options.py, tests/test_gpu_colsolve_families.py)  The restated cycle on the levels of one hierarchy in one storage mode, for a set of option cases: z_ref per case and the
     yardstick of the tolerance (d per case with f64 storage, e over the cases with f32 storage).  Computed once per module."""
 
-    def __init__(self, levels, r, f32, cases):
+    def __init__(self, levels, r, f32, cases, grouped=False):
+        assert not (grouped and f32)
         self.levels, self.f32 = levels, f32
         self.rows = [lv.n for lv in levels]
         self.z, self.yard = {}, {}
         for name, knobs in cases.items():
             kw = cycle_kwargs(**knobs)
-            self.z[name] = cycle(levels, r, **kw)
-            other = cycle(levels, r, factors="f32", **kw) if f32 else cycle(levels, r, blocks="inverse", **kw)
+            self.z[name] = cycle(levels, r, grouped=grouped, **kw)
+            other = cycle(levels, r, factors="f32", **kw) if f32 else cycle(levels, r, blocks="inverse", grouped=grouped, **kw)
             self.yard[name] = relative_difference(other, self.z[name])
         self.e = max(self.yard.values())
 

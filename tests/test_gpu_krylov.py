@@ -8,20 +8,42 @@ which GMRES fixes uniquely: the comparison is at the tolerance of the run's clas
 correct implementations differ by, measured on the CPU in tests/test_krylov_reference.py), orders of magnitude below what a
 dropped tail element, a skipped basis vector or a mis-taken f32 copy changes (shown there too).
 
-Which test reaches which kernel of blas1.hip:
-  multi_dot_kernel <double> / <float>, multi_dot_finish_kernel     test_multi_dot, test_truncated (f64 / f32 basis)
-  update_w_kernel <double> / <float>, sum_partials_kernel          test_truncated (also as launch_axpy_multi: x += Z y)
-  scale_to_kernel (f64, and its f32 twin yf)                       test_truncated
+Which test reaches which kernel of blas1.hip, and the smallest n of the suite at which the kernel's grid has reached its cap and
+its grid-stride loop takes a second pass (red_grid: 1024 blocks of 256 threads for the kernels of two elements per thread,
+2048 for the streams of one element per thread; both wrap from n = 524 289 on, zero_kernel from n = 1 048 577 on):
+  multi_dot_kernel <double> / <float>, multi_dot_finish_kernel     test_multi_dot, test_truncated (f64 / f32 basis); wrapped at
+                                                                    n524291; 64 chunks in grid.y: test_multi_dot_at_the_restart_clamp
+  update_w_kernel <double> / <float>, sum_partials_kernel          test_truncated (also as launch_axpy_multi: x += Z y); wrapped at
+                                                                    n524291; k = 510 of hs[NKP_MAX_K = 512]: test_restart_clamp_cycle
+  scale_to_kernel (f64, and its f32 twin yf)                       test_truncated; wrapped at n524291
   finish_column_kernel (plain norm, h += h2)                       test_truncated (reorth 0 / 1)
   finish_column_pythagoras_kernel                                  test_gpu_krylov_dist.py (one reduction per step)
-  dot_kernel                                                       test_truncated (||b||, true residuals), test_bicgstab
-  axpby_kernel                                                     test_bicgstab, test_truncated with precond_steps = 2
-  vmul_kernel                                                      test_truncated with equil
-  zero_kernel                                                      test_truncated (b = 0 in test_zero_rhs; bicgstab's p, v)
+  dot_kernel                                                       test_truncated (||b||, true residuals), test_bicgstab; wrapped at
+                                                                    n524291
+  axpby_kernel                                                     test_bicgstab (every call form of the driver), test_truncated with
+                                                                    precond_steps = 2 (the defect correction between two cycles);
+                                                                    wrapped at n524291-jacobi-k2-bicgstab and n524291-...-steps2
+  vmul_kernel                                                      test_truncated with equil (on w, on v_j, on the restart residual);
+                                                                    wrapped at n524291_rows-...-equil
+  zero_kernel                                                      test_truncated (b = 0 in test_zero_rhs; bicgstab's p, v: two
+                                                                    passes of 2048 blocks only from n = 1 048 577 on, which
+                                                                    tests/test_gpu_grid_caps.py reaches on its level 0; at n524291
+                                                                    the grid is at its cap and every thread has its pair)
   berr_kernel, max_partials_kernel                                 every solve () (info["berr"]), checked in test_full_solves
   count_entries_kernel, and NaN / Inf through the above            test_gpu_vector_range.py
   multi_dot_group, multi_dot_finish_group, update_w_group, sum_partials_group, scale_to_group, finish_column_group
-                                                                    test_batched_bits (against the single solves)
+                                                                    test_batched_bits (against the single solves); wrapped at n524291
+  gather_kernel, cycle_entry_kernel, restrict_sum_kernel, restrict_sum_fill_kernel, prolong_add_kernel (the cycle's glue)
+                                                                    tests/test_gpu_grid_caps.py (its table), wrapped at n = 2 105 351
+
+Measured on an MI355X, ||dx|| / ||x|| and its share of the tolerance of the class, for the runs on wrapped grids and at the clamp:
+  n524291-jacobi-k2-bicgstab                          0          (tolerance 1.5e-13)
+  n524291-jacobi-k2-*-steps2 (four option pairs)      at most 6.8e-17 with an f32 basis (2e-8 of the tolerance), 7.3e-19 with an
+                                                      f64 basis (1.5e-6 of it)
+  n524291_rows-jacobi-k2-*-equil (two option pairs)   at most 4.0e-18 = 4e-6 of 1.0e-12
+  diag1025-none-k510-reorth1-f32_0-m510               1.66e-12 = 0.33 % of 5.0e-10; relres 5.321964e-03 on both sides (diff 4.1e-14)
+  multi_dot at k = 505 and 511, restart 510 and 100000 (clamped): worst error 0.000 of its bound with an f64 basis, 0.065 with an
+  f32 basis; w.w 0.004 of its bound
 """
 import ctypes
 import functools
@@ -205,6 +227,52 @@ def test_multi_dot(n):
                 # against the operands as the kernel reads them the rounding of V is no part of the bound
                 assert np.all(np.abs(out[:k] - exact_r[:k]) <= gamma * vn[:k] * (1.0 + 2.0 ** -24) * wn), (n, f32, k)
                 assert abs(out[k] - wn * wn) <= gamma * wn * wn, (n, f32, k)          # slot k is w.w
+
+
+@pytest.mark.parametrize("restart", [kc.RESTART_CLAMP, 100000], ids=lambda m: f"restart{m}")
+def test_multi_dot_at_the_restart_clamp(restart):
+    """nkp_create clamps restart to NKP_MAX_K - 2 = 510 and does not refuse a longer one.  k = 511 = m + 1 is 64 chunks of
+    NKP_DOT_CHUNK in grid.y, the last one with 7 vectors, and fills `partial` and h_dev () as create.hip sizes them; k = 505 ends
+    on a chunk of one vector.  k = 512 is beyond the basis of either solver."""
+    n, m = 513, kc.RESTART_CLAMP
+    V, w = _dot_operands(n, m + 2)
+    c = kc.case(f"n{n}")
+    gamma = (n + 2) * U / (1.0 - (n + 2) * U)
+    wn = float(np.sqrt(_ld_dot(w, w)))
+    exact = np.array([float(_ld_dot(V[j], w)) for j in range(m + 1)])
+    vn = np.array([float(np.sqrt(_ld_dot(V[j], V[j]))) for j in range(m + 1)])
+    for f32 in (0, 1):
+        Vr = V.astype(np.float32) if f32 else V        # what the kernel reads
+        exact_r = np.array([float(_ld_dot(Vr[j], w)) for j in range(m + 1)])
+        with solver.NkpSolver(c.rowptr, c.colind, c.val, None, precond=kc.NONE, restart=restart, basis_f32=f32) as s:
+            for k in (505, m + 1):
+                out = s.multi_dot(V[:k], w)
+                again = s.multi_dot(V[:k], w)
+                assert out.shape == (k + 1,)
+                assert np.array_equal(out.view(np.uint64), again.view(np.uint64)), (restart, f32, k)
+                err = np.abs(out[:k] - exact[:k])
+                bound = (gamma + (2.0 ** -24 if f32 else 0.0)) * vn[:k] * wn
+                print(f"multi_dot restart {restart} f32 {f32} k {k}: worst error / bound {float((err / bound).max()):.3f}, "
+                      f"w.w error {abs(out[k] - wn * wn) / (gamma * wn * wn):.3f} of its bound")
+                assert np.all(err <= bound), (restart, f32, k, err, bound)
+                assert np.all(np.abs(out[:k] - exact_r[:k]) <= gamma * vn[:k] * (1.0 + 2.0 ** -24) * wn), (restart, f32, k)
+                assert abs(out[k] - wn * wn) <= gamma * wn * wn, (restart, f32, k)          # slot k is w.w
+            with pytest.raises(solver.NkpError) as e:
+                s.multi_dot(V[:m + 2], w)
+            assert e.value.code == -1 and "restart+1" in str(e.value), (restart, f32, e.value)          # NKP_EINVAL
+
+
+# ---------------------------------------------------------------- one restart cycle of the longest length
+@pytest.mark.parametrize("run", kc.clamp_runs(), ids=lambda r: r.id)
+def test_restart_clamp_cycle(run):
+    """update_w_kernel with k = 1 .. 510 and launch_axpy_multi with k = 510 (kc.clamp_runs: the case still uses its last basis
+    vector); a solver asked for a longer restart is the same solver"""
+    c = kc.case(run.case)
+    ref, info, x = check(run)
+    assert info["iters"] == run.k == kc.RESTART_CLAMP and info["status"] == kr.NOT_CONVERGED
+    with make_solver(run, restart=100000) as s:
+        x2, info2 = s.solve(c.b, raise_on_fail=False)
+    assert kc.same_bits(x, x2) and info2["iters"] == info["iters"] and info2["relres"] == info["relres"], (info, info2)
 
 
 # ---------------------------------------------------------------- batched

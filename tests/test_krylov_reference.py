@@ -60,7 +60,7 @@ def noise(run):
     return d
 
 
-ALL_RUNS = kc.truncated_runs() + kc.full_runs() + kc.bicgstab_runs()
+ALL_RUNS = kc.truncated_runs() + kc.full_runs() + kc.bicgstab_runs() + kc.clamp_runs()
 CPU_RUNS = [r for r in ALL_RUNS if r.precond != kc.MULTILEVEL]          # the oracle has no twin of the library's hierarchy
 CLASSES = sorted(kc.TOL)
 TABLE_K = [1, 3, 4, 5, 8, 9, 16, 17]
@@ -251,6 +251,31 @@ def test_wrong_restatements_are_seen(run, wrong):
     d = rel(kc.reference(run, A, M, arith=wrong()).x, a.x)
     print(f"{run.id} {wrong.__name__}: {d:.2e} = {d / tol:.1e} tolerances")
     assert d > 1000.0 * tol, (run, wrong.__name__, d, tol)
+
+
+class SkipsVector509(kr.Arith):
+    def update(self, w, V, h, sign=-1.0):
+        if len(V) <= 509:
+            return super().update(w, V, h, sign)
+        keep = [j for j in range(len(V)) if j != 509]
+        return super().update(w, [V[j] for j in keep], [h[j] for j in keep], sign)
+
+
+def test_the_restart_clamp_case_is_determined_and_uses_its_last_vector():
+    """kc.clamp_runs: x_510 is determined to better than 1e-8 between the arithmetics, the cycle runs to its end without
+    converging, and basis vector 509 (the last one update_w_kernel reads at k = 510) left out of the update of w and of
+    x += Z y moves x by 3.7e-4: more than a thousand tolerances of the class"""
+    (run,) = kc.clamp_runs()
+    c = kc.case(run.case)
+    assert run.k == run.restart == kc.RESTART_CLAMP and np.unique(c.val).size == c.n >= kc.RESTART_CLAMP + 1
+    a = solved(run)
+    assert a.iters == run.k and a.status == kr.NOT_CONVERGED and a.relres > 1e-3
+    assert [d.taken for d in a.log if d.kind == "estimate"] == [False] * run.k
+    assert noise(run) <= 1e-8
+    A, M = oracle_operators(c, run.precond)
+    d = rel(kc.reference(run, A, M, arith=SkipsVector509()).x, a.x)
+    print(f"{run.id} without basis vector 509: {d:.2e} = {d / kc.TOL[run.cls][1]:.1e} tolerances")
+    assert d > 1000.0 * kc.TOL[run.cls][1]
 
 
 # ---------------------------------------------------------------- no decision within rounding of its threshold

@@ -2,7 +2,8 @@
 cycle that tests/test_gpu_cycle_options.py holds the HIP cycle against, so it has to (1) agree with the older restatement at the
 defaults, (2) react to every option that test sets -- otherwise the GPU test could pass with a knob ignored on both sides -- and
 (3) react to an off-by-one in any of them by far more than the tolerances of the GPU test (1e-12 with f64 storage, at most 2e-5
-with f32 storage).
+with f32 storage); and (4) its grouped evaluation of the half sweeps, which tests/test_gpu_grid_caps.py runs at two million rows,
+has to be the per-column one.
 
 Rounding sizes of the reference itself on these levels, recorded, not asserted (the GPU test recomputes both on the device's levels and
 sizes its tolerances from them): blocks="lu" against blocks="inverse" at most 2.9e-16 relative over the option cases;
@@ -136,3 +137,24 @@ def test_rounding_sizes_of_the_reference(problem, hierarchies):
         print("%-20s lu/inverse %.1e   f32 factors %.1e   f32 factors of the unrounded blocks %.1e" % (name, d, e1, e2[-1]))
     print("lu/inverse at most %.1e; f32 factors %.1e to %.1e, of the unrounded blocks %.1e to %.1e" % (max(d_all), min(e), max(e), min(e2), max(e2)))
     assert np.isfinite(d_all).all() and np.isfinite(e).all() and np.isfinite(e2).all()
+
+
+@pytest.mark.parametrize("name,hierarchy,knobs", mcr.OPTION_CASES, ids=lambda v: v if isinstance(v, str) else "")
+def test_grouped_half_sweeps_are_the_per_column_ones(name, hierarchy, knobs, problem, hierarchies):
+    """The evaluation that stacks a colour's blocks by size (tests/test_gpu_grid_caps.py runs it at two million rows) against
+    the per-column loop, LU blocks and explicit inverses each: within d, the difference between the per-column reference with LU
+    blocks and with explicit inverses, which is what the f64 tolerance of the GPU tests is a multiple of.  Measured: 0 in every
+    case, LU blocks and explicit inverses (the same LAPACK factorisation of the same block; d is 1.6e-16 to 2.9e-16)."""
+    r = problem[1]
+    kw = mcr.cycle_kwargs(**knobs)
+    levels = hierarchies[hierarchy]
+    sizes = {int(s) for lv in levels if lv.col_of is not None for s in np.bincount(lv.col_of)}
+    assert len(sizes) >= 3                                               # several stacks per colour
+    z = {(b, g): mcr.cycle(levels, r, blocks=b, grouped=g, **kw) for b in ("lu", "inverse") for g in (False, True)}
+    d = mcr.relative_difference(z["inverse", False], z["lu", False])
+    got = {b: mcr.relative_difference(z[b, True], z[b, False]) for b in ("lu", "inverse")}
+    print("%-20s d %.2e   grouped against per-column: lu %.2e, inverse %.2e" % (name, d, got["lu"], got["inverse"]))
+    assert d > 0.0
+    assert got["lu"] <= d and got["inverse"] <= d, (name, d, got)
+    with pytest.raises(AssertionError):
+        mcr.cycle(levels, r, factors="f32", grouped=True, **kw)
