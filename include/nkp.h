@@ -432,7 +432,11 @@ int nkp_multi_dot (nkp_solver *s, const double *V, int64_t ld, int k, const doub
  * its compulsory bytes: those of 6 + 4 nnz for the value map); 10 = for comparison with 9, same arg: the composition it replaces
  * -- the values gathered through the map into a temporary of nnz doubles, then the kernel of 6 on the transposed pattern (16 nnz
  * more bytes).  9 and 10: single-GPU solvers that own their pattern only (NKP_EINVAL on a row-distributed solver, a clone, a
- * transposed handle, and for another arg). */
+ * transposed handle, and for another arg); 11 = the kernel of nkp_residual_batch alone (its per-column finish included) with K =
+ * arg in {1, 2, 4, 8} vectors, B and X scratch of the solver, R not written (single-GPU solvers only, NKP_EINVAL elsewhere and
+ * for another arg; its compulsory bytes: 12 nnz + 4 (n + 1) + 16 K n); 12 = for comparison with 11, same arg: what a caller had
+ * to compose before, column by column -- the b - A x and |A||x| + |b| products of a solve's backward error, its berr pass, and
+ * two dots for the norms (2 K sweeps over A). */
 int nkp_time_kernel (nkp_solver *s, int which, int arg, int reps, double *avg_ms);
 
 /* Introspection: key = "n", "nnz", "nblk", "band", "levels", "spmv_bytes" (compulsory bytes of the CSR product: 12 nnz +
@@ -462,6 +466,7 @@ int nkp_time_kernel (nkp_solver *s, int which, int arg, int reps, double *avg_ms
  * "trans_index_bytes" (device bytes of the transposed index those calls keep, 0 before the first; part of "device_bytes"),
  * "trans_index_us" (wall time of building it), "trans_index_sent_entries" / "trans_index_recv_entries" (row-distributed: the entries
  * whose products this rank ships to / receives from its peers in every nkp_values_product_trans_dist*; 0 without an index),
+ * "residual_batch_calls" (successful nkp_residual_batch* calls), "residual_batch_us" (wall time of the last one),
  * "max_iters" (the iteration cap in force: nkp_options.max_iters or what nkp_set_solve_controls put in its place),
  * "batch_steps" (batched operator
  * applications = lockstep Krylov steps of a group of right-hand sides), "batch_width" (K of the last batched group, 0 if
@@ -856,6 +861,62 @@ int nkp_values_product_trans_dist (nkp_solver *s, int nrhs, const double *val_lo
  * handle is read). */
 int nkp_solve_tangent_device (nkp_solver *s, int nrhs, const void *d_dval, const void *d_x, int64_t ldx, const void *d_db, void *d_dx, int64_t ld,
                               double *berr, int *iters, double *relres);
+
+/* How good are nrhs given solutions under the matrix the handle solves with now?  For every column c, from ONE pass over A:
+ *      r_c = b_c - A x_c (stored in R when R is not NULL),   rnorm[c] = sqrt (sum_i r_c[i]^2),   bnorm[c] = sqrt (sum_i b_c[i]^2),
+ *      berr[c] = max_i |r_c[i]| / (|A||x_c| + |b_c|)[i]      -- the componentwise backward error the solves report.
+ * An inexact Newton driver asks this first after every nkp_refactor*: the forcing term needs ||b - A x|| and ||b||, and a column
+ * whose old solution is still good enough needs no solve.  The call does not judge convergence and returns 0 on success: relres =
+ * rnorm / bnorm is the caller's to form (bnorm may be 0).
+ *   Per row i and column c the pass keeps t = +0.0; t += val[e] * x_c[colind[e]] and d = +0.0; d += fabs (val[e] * x_c[colind[e]])
+ *   over the stored entries of the row in stored order, every product and every sum rounded on its own (no fused multiply-add): the
+ *   bits of nkp_spmv_device and of the |A||x| pass of the solves; a row of more than 2048 entries is summed in the SpMV's tree for
+ *   such rows, t and d alike.  Then r = b - t, den = d + fabs (b) and q = fabs (r) / den, where den == 0 gives q = 0 for r == 0 and
+ *   1e300 otherwise, and a NaN of r or den (or Inf / Inf) gives NaN.  berr[c] is the maximum of q, NaN sticky: it has the bits of the
+ *   berr nkp_solve_device reports for the same x and b.  r^2 and b^2 are one rounded product each; they are summed per CSR row block
+ *   of A in a fixed tree and the row blocks in a fixed order, so rnorm and bnorm depend on A's pattern alone: the same bits for
+ *   every nrhs, every position of a vector among the columns, and every repetition of the call.  No atomics.
+ *   A is read from its CSR values, never from per-column diagonals (tuning spmv_diag): a padded slot times a non-finite x would
+ *   differ, and the check is meant for suspect vectors.  A non-finite entry of x_c or b_c makes that column's numbers NaN or Inf by
+ *   the rules above, does not disturb the other columns, and is not an error.
+ *   Which matrix: the one the handle solves with now -- after nkp_refactor* the new values; the unscaled system whatever equil is
+ *   (the row scaling of the row-weighted iteration is applied to vectors, A's values are never stored scaled); on a transposed
+ *   handle A^T.  A clone is allowed and reads the shared matrix.  A solver whose refactor failed after its commit point is refused
+ *   like the solves (NKP_ESINGULAR).
+ *   Buffers: B, X and R hold nrhs vectors, column-major, vector c at c * ldb, c * ldx and c * ldr, every ld >= n; rows n .. ld - 1
+ *   are neither read nor written and columns behind nrhs are untouched.  1 <= nrhs <= 8 (more vectors: call again).  R may be NULL
+ *   (no residual is stored; ldr is then ignored).  R == X is refused, because other rows still gather x; R == B with ldr == ldb is
+ *   allowed (every row reads its b before its r is written); any other overlap of R with B or X is the caller's error.  rnorm,
+ *   bnorm and berr are host arrays of nrhs doubles each, or NULL; asking for nothing (R and all three NULL) is refused.
+ *   nkp_residual_batch takes host buffers, nkp_residual_batch_device buffers on the solver's device; B and X are not modified.
+ *   The work runs on the solver's stream (nkp_set_stream), reads the caller's operands in order on that stream and has finished
+ *   when the call returns.  Compulsory bytes: 12 nnz + 4 (n + 1) + 16 nrhs n, plus 8 nrhs n when R is written.
+ *   Work space -- the K-interleaved copy of X for nrhs >= 2 (8 K n bytes, K = 2, 4 or 8), the partial sums (24 K bytes per row
+ *   block of A), the device staging of the host flavour (8 nrhs n bytes each for B, X and, when asked for, R) -- is allocated at
+ *   first use, all or nothing, kept, and counted in "device_bytes"; a failed allocation leaves the solver exactly as it was.
+ *   nkp_get_int: "residual_batch_calls" (successful calls), "residual_batch_us" (wall time of the last one).
+ * Row-distributed solvers: the same entry points, COLLECTIVE, with the same nrhs on every rank; each rank passes its own rows of
+ * every vector (every ld >= m_loc) and gets its own rows of R; rnorm, bnorm and berr are global and identical on all ranks (berr
+ * with the bits of a single-GPU solver of the whole matrix; what the transport's max makes of a NaN is the transport's business,
+ * as for nkp_solve).  The callbacks, in this order on every rank:
+ *      allgather_i64_host   agreement: arguments, work space, staging of the host arrays
+ *      alltoallv            the halo rows of X, K wide, in ONE exchange (always made; "dist_alltoallv_calls")
+ *      allreduce (sum)      2 K doubles: the squared norms            ("dist_allreduce_calls")
+ *      allreduce (max)      K doubles: the backward errors            ("dist_allreduce_calls")
+ *      allgather_i64_host   agreement: exchange, kernel, reductions
+ *   A rank whose own arguments or work space fail still makes the first agreement; when it fails every rank returns after it --
+ *   the failing rank its own code and message, the others NKP_ECOMM naming it -- and nothing else is exchanged.  Once the first
+ *   agreement has passed, the remaining four callbacks are reached on every rank whatever happens locally, and the second
+ *   agreement tells a local failure to all in the same way.  The outputs are then undefined; the solvers solve as before.  On a
+ *   plain solver there is no collective.
+ * Returns 0; NKP_EINVAL for a NULL solver, B or X (refused on the calling rank before the solver is looked at and before any
+ * collective; the message names the argument), nrhs outside 1 .. 8, an ld < n, R == X, nothing asked for (found before any HIP
+ * call; on a row-distributed solver told to the other ranks through the first agreement); NKP_ESINGULAR; NKP_ENOMEM / NKP_EDEVICE;
+ * NKP_ECOMM. */
+int nkp_residual_batch_device (nkp_solver *s, int nrhs, const void *d_B, int64_t ldb, const void *d_X, int64_t ldx,
+                               void *d_R, int64_t ldr, double *rnorm, double *bnorm, double *berr);
+int nkp_residual_batch        (nkp_solver *s, int nrhs, const double *B, int64_t ldb, const double *X, int64_t ldx,
+                               double *R, int64_t ldr, double *rnorm, double *bnorm, double *berr);
 
 /* hipSetDevice for host programs that do not link HIP themselves (call before nkp_comm_rccl_init). */
 int nkp_set_device (int device);

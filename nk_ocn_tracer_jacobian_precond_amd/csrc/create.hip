@@ -482,6 +482,7 @@ int clone_impl (nkp_solver *src, nkp_solver **out, bool member)
    s->vg = decltype (s->vg) ();      // nkp_value_gradient's work space and counters are per handle
    s->vp = decltype (s->vp) ();      // and nkp_values_product's
    s->vt = decltype (s->vt) ();      // the transposed index stays with the owner
+   s->rb = decltype (s->rb) ();      // nkp_residual_batch's work space and counters are per handle too
    s->A.tune = &s->tune;
    s->B.tune = &s->tune;
    s->ml.tune = &s->tune;

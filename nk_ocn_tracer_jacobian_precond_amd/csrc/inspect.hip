@@ -161,6 +161,11 @@ extern "C" int nkp_time_kernel (nkp_solver *s, int which, int arg, int reps, dou
       const int prc = valprod_time_prepare (s, arg, which);
       if (prc) return prc;
    }
+   // 11: the kernel of nkp_residual_batch alone at interleave width arg, R not written; 12: the composition it replaces
+   if (which == 11 || which == 12) {
+      const int prc = residual_time_prepare (s, arg, which);
+      if (prc) return prc;
+   }
    StepEvent step_ev;
    if (which == 2) {
       const int erc = step_ev.make (s);
@@ -200,6 +205,8 @@ extern "C" int nkp_time_kernel (nkp_solver *s, int which, int arg, int reps, dou
          else if (which == 7) valprod_time_composition (s, arg);
          else if (which == 9) valprod_time_launch_trans (s, arg);
          else if (which == 10) valprod_time_composition_trans (s, arg);
+         else if (which == 11) residual_time_launch (s, arg);
+         else if (which == 12) residual_time_composition (s, arg);
          else if (s->opt.precond == NKP_PRECOND_MULTILEVEL) ml_time_piece (s->ml, which - 3, s->stream);   // 3: smoother residual rows, 4: column solves (level 0, colour 0)
       }
       HIPCHK (hipEventRecord (e1, s->stream));

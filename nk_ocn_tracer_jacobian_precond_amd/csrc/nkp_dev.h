@@ -117,6 +117,12 @@ void launch_values_product_trans (int K, int nk, const CsrDev &T, const int *src
 // which sits in x at row T.colind[p] and takes the value 1.0
 void launch_values_product_trans_recv (int K, int nk, const CsrDev &T, const int *src, const double *val, const double *x, double alpha, int accumulate, double *y,
                                        int64_t ldy, hipStream_t st);
+// nkp_residual_batch (residual.hip): one pass over A for c < nk: r_c = b_c - A x_c into R (column-major, vector c at c * ldr; NULL: not
+// stored; may be B, never x) and out[c] = sum r_c^2, out[K + c] = sum b_c^2, out[2 K + c] = max_or_nan over the rows of |r| / (|A||x| + |b|)
+// by berr_kernel's rule; the rows' sums have the bits of the SpMV kernels (modes 0 and 2).  K in {1, 2, 4, 8}: interleave width of x
+// (1 = a plain vector), nk <= K; columns c >= nk of out get +0.0.  partial: 3 K doubles per row block of A
+void launch_residual_batch (int K, int nk, const CsrDev &A, const double *x, const double *B, int64_t ldb, double *R, int64_t ldr, double *partial, double *out,
+                            hipStream_t st);
 
 // ---------------------------------------------------------------- water-column blocks
 // Banded LU (no pivoting) of every diagonal block, half-bandwidth P in {1,2,4}; SoA by

@@ -30,6 +30,7 @@ void solver_free (nkp_solver *s)
       }
       valgrad_release (s);
       valprod_release (s);
+      residual_release (s);
       if (s->hpin) (void) hipHostFree (s->hpin);
       if (s->own_stream && s->stream) (void) hipStreamDestroy (s->stream);
       s->shared->clones--;
@@ -40,6 +41,7 @@ void solver_free (nkp_solver *s)
    if (s->trans) trans_release (s);      // before the stream it shares goes
    valgrad_release (s);
    valprod_release (s);
+   residual_release (s);
    for (nkp_solver *c : s->batch_members) solver_free (c);
    s->batch_members.clear ();
    for (double *p : { s->bvin, s->bz, s->bw })
@@ -152,6 +154,8 @@ extern "C" int64_t nkp_get_int (nkp_solver *s, const char *key)
    if (!strcmp (key, "values_product_calls")) return s->vp.calls;
    if (!strcmp (key, "values_product_us")) return (int64_t) (s->vp.seconds * 1.0e6);
    if (!strcmp (key, "tangent_calls")) return s->vp.tangent_calls;
+   if (!strcmp (key, "residual_batch_calls")) return s->rb.calls;
+   if (!strcmp (key, "residual_batch_us")) return (int64_t) (s->rb.seconds * 1.0e6);
    if (!strcmp (key, "values_product_trans_calls")) return s->vt.calls;
    if (!strcmp (key, "values_product_trans_us")) return (int64_t) (s->vt.seconds * 1.0e6);
    if (!strcmp (key, "trans_index_bytes")) return (int64_t) s->vt.bytes;

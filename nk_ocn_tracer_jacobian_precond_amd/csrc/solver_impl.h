@@ -9,6 +9,7 @@
 //   smooth_exchange.hip the fine-level exchange of a row-distributed cycle (tuning dist_smooth_exchange): kernels, lists, the cycle's hook
 //   inspect.hip         entry points of tests and timing (arrays of the hierarchy and the matrix, single products, nkp_time_kernel)
 //   refactor_api.hip, transpose*.hip, valgrad_api.hip, valprod_api.hip, valprod_trans_dist.hip      new values, A^T, gradient and products by values
+//   residual_api.hip    residual, norms and backward error of K given solutions (nkp_residual_batch); the kernel is residual.hip
 // What crosses units is declared once, below, under the unit that defines it.  Private to the library: nothing here is part of
 // the C ABI.
 #pragma once
@@ -196,6 +197,14 @@ struct nkp_solver {
       double *xe = nullptr, *send = nullptr;
       size_t xe_cap = 0, send_cap = 0;
    } vt;
+   // nkp_residual_batch: the K-interleaved copy of X (single-GPU, nrhs >= 2), the partials of the reductions (3 K doubles per row
+   // block of A, the 3 K results behind them), the device staging of the host flavour (B | X | R) -- like vp made at first use and kept
+   struct {
+      double *x = nullptr, *partial = nullptr, *stage = nullptr;
+      size_t x_cap = 0, partial_cap = 0, stage_cap = 0;
+      int64_t calls = 0;
+      double seconds = 0.0;        // wall time of the last call
+   } rb;
    double *h_dev () { return dscal; }
    double *h2_dev () { return dscal + (m + 2); }
    double *misc_dev () { return dscal + 2 * (m + 2); }     // [0]=nrm2 [1]=inv [2]=dot out ...
@@ -453,6 +462,13 @@ NKP_PRIVATE void valprod_time_composition (nkp_solver *s, int K);
 // it replaces -- the values gathered into a temporary of nnz doubles, then the product kernel on the transposed pattern
 NKP_PRIVATE void valprod_time_launch_trans (nkp_solver *s, int K);
 NKP_PRIVATE void valprod_time_composition_trans (nkp_solver *s, int K);
+// ---- defined in residual_api.hip -------------------------------------------------------------------------------------------
+NKP_PRIVATE void residual_release (nkp_solver *s);
+// nkp_time_kernel, which = 11: scratch operands for the residual kernel at interleave width K (1, 2, 4, 8), then one launch (R not
+// written); which = 12: the composition it replaces, per column the mode-1 and mode-2 SpMV launches, launch_berr and two launch_dot
+NKP_PRIVATE int residual_time_prepare (nkp_solver *s, int K, int which);
+NKP_PRIVATE void residual_time_launch (nkp_solver *s, int K);
+NKP_PRIVATE void residual_time_composition (nkp_solver *s, int K);
 // ---- defined in transpose.hip ----------------------------------------------------------------------------------------------
 // the owner frees its transposed solver and the value map; a transposed solver that is destroyed leaves its owner
 NKP_PRIVATE void trans_release (nkp_solver *s);

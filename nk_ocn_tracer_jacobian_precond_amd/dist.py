@@ -447,6 +447,16 @@ class NkpDistSolver(_solver.NkpSolver):
         self._check_collective(self._lib.nkp_values_product_trans_dist_device(self._h, int(nrhs), C.c_void_p(d_val), C.c_void_p(d_x), int(ldx), float(alpha),
                                                                               int(bool(accumulate)), C.c_void_p(d_y), int(ldy)))
 
+    def residual_batch_device(self, d_B, ldb, d_X, ldx, nrhs, d_R=None, ldr=0):
+        """nkp_residual_batch_device, COLLECTIVE: every rank calls it with the same nrhs and its own m_loc rows of every vector
+        (every ld >= m_loc).  d_R receives this rank's rows of B - A X; rnorm, bnorm and berr are global and the same on every rank.
+        One alltoallv (the halo rows of X), two allreduces, between two agreements."""
+        return super().residual_batch_device(d_B, ldb, d_X, ldx, nrhs, d_R, ldr)
+
+    def residual_batch(self, B, X, want_residual=False):
+        """nkp_residual_batch, COLLECTIVE like residual_batch_device: B, X of shape (m_loc,) or (K, m_loc), this rank's rows."""
+        return super().residual_batch(B, X, want_residual)
+
     def refactor_dist(self, val_loc, rebuild=False):
         """nkp_refactor_dist (collective: every rank calls it): this rank's new values, nnz_loc of them in the order of the
         local rows it was created with.  The overlap rows' values come from their owners; get_int("refactor_halo_values")

@@ -7,6 +7,7 @@ is missing or no GPU is visible, construction raises.
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import os
 
@@ -36,6 +37,7 @@ ABI_SYMBOLS = [
     "nkp_values_product_trans", "nkp_values_product_trans_device",
     "nkp_values_product_trans_dist", "nkp_values_product_trans_dist_device",
     "nkp_set_solve_controls", "nkp_get_solve_controls", "nkp_solve_batch_device_ex",
+    "nkp_residual_batch", "nkp_residual_batch_device",
 ]
 
 _ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p)
@@ -84,6 +86,9 @@ class NkpSolveControls(C.Structure):
     """nkp_solve_controls (include/nkp.h): rtol, atol and max_iters of an existing solver; max_iters 0 and a negative tolerance
     leave that value as it is."""
     _fields_ = [("struct_size", C.c_int), ("max_iters", C.c_int), ("rtol", C.c_double), ("atol", C.c_double)]
+
+
+ResidualBatch = collections.namedtuple("ResidualBatch", "rnorm bnorm berr relres R")
 
 
 class NkpError(RuntimeError):
@@ -152,6 +157,8 @@ def load_library(path=None):
     lib.nkp_values_product_trans_dist.argtypes = lib.nkp_values_product.argtypes
     lib.nkp_values_product_trans_dist_device.argtypes = lib.nkp_values_product_device.argtypes
     lib.nkp_solve_tangent_device.argtypes = [vp, C.c_int, vp, vp, C.c_int64, vp, vp, C.c_int64, f64p, C.POINTER(C.c_int), f64p]
+    lib.nkp_residual_batch_device.argtypes = [vp, C.c_int, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, f64p, f64p, f64p]
+    lib.nkp_residual_batch.argtypes = [vp, C.c_int, f64p, C.c_int64, f64p, C.c_int64, f64p, C.c_int64, f64p, f64p, f64p]
     lib.nkp_refactor.argtypes = [vp, f64p, C.c_int]
     lib.nkp_refactor_device.argtypes = [vp, vp, C.c_int]
     lib.nkp_refactor_dist.argtypes = [vp, f64p, C.c_int]
@@ -541,6 +548,36 @@ class NkpSolver:
             for q in bufs:
                 _hip().hipFree(C.c_void_p(q))
         return out.reshape(np.shape(X)), infos
+
+    def residual_batch_device(self, d_B, ldb, d_X, ldx, nrhs, d_R=None, ldr=0):
+        """nkp_residual_batch_device: d_B / d_X = integer device addresses of nrhs vectors of n float64 each (vector c at + 8 * c *
+        ldb / ldx); d_R the same for the residuals B - A X (vector c at + 8 * c * ldr), or None: not stored.  One pass over the
+        matrix the handle solves with now.  Returns (rnorm, bnorm, berr), three arrays of nrhs float64.  Runs on the solver's
+        stream.  Collective on a row-distributed solver (local rows in, global numbers out)."""
+        nrhs = int(nrhs)
+        out = np.full((3, max(nrhs, 1)), np.nan)
+        self._check_collective(self._lib.nkp_residual_batch_device(self._h, nrhs, C.c_void_p(d_B or None), int(ldb), C.c_void_p(d_X or None), int(ldx),
+                                                                   C.c_void_p(d_R or None), int(ldr), _p(out[0], C.c_double), _p(out[1], C.c_double),
+                                                                   _p(out[2], C.c_double)))
+        return out[0, :nrhs], out[1, :nrhs], out[2, :nrhs]
+
+    def residual_batch(self, B, X, want_residual=False):
+        """nkp_residual_batch from host arrays: B, X of shape (n,) or (K, n), K <= 8; neither is modified.  Returns
+        ResidualBatch(rnorm, bnorm, berr, relres, R): arrays of K float64 (of one for shape (n,)), relres = rnorm / bnorm (NaN
+        where both are 0, Inf where only bnorm is), R = B - A X in B's shape or None.  Collective on a row-distributed solver."""
+        b = np.ascontiguousarray(np.atleast_2d(np.asarray(B, np.float64)))
+        x = np.ascontiguousarray(np.atleast_2d(np.asarray(X, np.float64)))
+        if b.ndim != 2 or b.shape != x.shape or b.shape[1] != self.n:
+            raise ValueError(f"B and X must both have shape ({self.n},) or (K, {self.n})")
+        K = b.shape[0]
+        out = np.full((3, max(K, 1)), np.nan)
+        r = np.empty_like(b) if want_residual else None
+        self._check_collective(self._lib.nkp_residual_batch(self._h, K, _p(b, C.c_double), self.n, _p(x, C.c_double), self.n,
+                                                            None if r is None else _p(r, C.c_double), self.n, _p(out[0], C.c_double), _p(out[1], C.c_double),
+                                                            _p(out[2], C.c_double)))
+        with np.errstate(divide="ignore", invalid="ignore"):
+            relres = out[0, :K] / out[1, :K]
+        return ResidualBatch(out[0, :K], out[1, :K], out[2, :K], relres, None if r is None else r.reshape(np.shape(B)))
 
     def _check_collective(self, rc):
         self._check(rc)
