@@ -146,26 +146,29 @@ extern "C" int nkp_multi_dot (nkp_solver *s, const double *V, int64_t ld, int k,
    return NKP_OK;
 }
 
+// The kernels of the K-vector calls on the pattern (operand_call.h), each at interleave width arg on scratch operands of its own:
+// prepare checks the solver and arg and makes the operands, launch queues the kernel once.  A new kernel adds one row
+struct TimedKernel { int which; int (*prepare) (nkp_solver *, int K, int which); void (*launch) (nkp_solver *, int K); };
+const TimedKernel timed_kernels[] = {
+   { 5, valgrad_time_prepare, valgrad_time_launch },                  // the gradient kernel of nkp_value_gradient
+   { 6, valprod_time_prepare, valprod_time_launch },                  // the product kernel of nkp_values_product
+   { 7, valprod_time_prepare, valprod_time_composition },             // what it replaces
+   { 9, valprod_time_prepare, valprod_time_launch_trans },            // the same kernel on the transposed index with gathered values
+   { 10, valprod_time_prepare, valprod_time_composition_trans },      // what that replaces
+   { 11, residual_time_prepare, residual_time_launch },               // the kernel of nkp_residual_batch alone, R not written
+   { 12, residual_time_prepare, residual_time_composition },          // the composition it replaces
+};
+
 extern "C" int nkp_time_kernel (nkp_solver *s, int which, int arg, int reps, double *avg_ms)
 {
    if (!s || !avg_ms || reps < 1) return fail (NKP_EINVAL, "nkp_time_kernel: bad argument");
    if (which == 8 && !s->A.dg_vald) return fail (NKP_EINVAL, "nkp_time_kernel: the matrix has no per-column diagonals (tuning spmv_diag)");
    HIPCHK (hipSetDevice (s->device));
-   if (which == 5) {      // the gradient kernel of nkp_value_gradient at interleave width arg, on scratch operands of its own
-      const int prc = valgrad_time_prepare (s, arg);
-      if (prc) return prc;
-   }
-   // the product kernel of nkp_values_product at interleave width arg, likewise; 7: what it replaces; 9: the same kernel on the
-   // transposed index with gathered values (nkp_values_product_trans); 10: what that replaces
-   if (which == 6 || which == 7 || which == 9 || which == 10) {
-      const int prc = valprod_time_prepare (s, arg, which);
-      if (prc) return prc;
-   }
-   // 11: the kernel of nkp_residual_batch alone at interleave width arg, R not written; 12: the composition it replaces
-   if (which == 11 || which == 12) {
-      const int prc = residual_time_prepare (s, arg, which);
-      if (prc) return prc;
-   }
+   const TimedKernel *tk = nullptr;
+   for (const TimedKernel &row : timed_kernels)
+      if (row.which == which) tk = &row;
+   if (tk)
+      if (const int prc = tk->prepare (s, arg, which)) return prc;
    StepEvent step_ev;
    if (which == 2) {
       const int erc = step_ev.make (s);
@@ -200,13 +203,7 @@ extern "C" int nkp_time_kernel (nkp_solver *s, int which, int arg, int reps, dou
             const int src = arnoldi_hand_over (s, arg, step_ev.ev);
             if (src) { s->ml.entered = 0; return src; }
          }
-         else if (which == 5) valgrad_time_launch (s, arg);
-         else if (which == 6) valprod_time_launch (s, arg);
-         else if (which == 7) valprod_time_composition (s, arg);
-         else if (which == 9) valprod_time_launch_trans (s, arg);
-         else if (which == 10) valprod_time_composition_trans (s, arg);
-         else if (which == 11) residual_time_launch (s, arg);
-         else if (which == 12) residual_time_composition (s, arg);
+         else if (tk) tk->launch (s, arg);
          else if (s->opt.precond == NKP_PRECOND_MULTILEVEL) ml_time_piece (s->ml, which - 3, s->stream);   // 3: smoother residual rows, 4: column solves (level 0, colour 0)
       }
       HIPCHK (hipEventRecord (e1, s->stream));

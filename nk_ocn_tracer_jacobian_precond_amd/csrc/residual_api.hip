@@ -4,10 +4,9 @@
 // on a row-distributed solver (fetch_x_operand, shared with nkp_value_gradient and nkp_values_product), reduces the norms and the
 // backward errors across the ranks and keeps the ranks together.  A.val is the unscaled matrix whatever equil is: the row scaling of
 // the row-weighted iteration lives in vectors of its own (rscale, rinv) and is applied to vectors only.
-#include "solver_impl.h"
+#include "operand_call.h"
 
 #include <math.h>
-#include <time.h>
 
 namespace {
 
@@ -16,64 +15,48 @@ namespace {
 int residual_batch (nkp_solver *s, int nrhs, const double *h_B, const double *h_X, double *h_R, const double *d_B, const double *d_X, double *d_R, int64_t ldb,
                     int64_t ldx, int64_t ldr, double *rnorm, double *bnorm, double *berr, const char *who)
 {
-   const bool host = h_B != nullptr, dist = s->dist.on;
+   OperandCall c (s, who, nrhs, h_B != nullptr);
+   const bool host = c.host, dist = c.dist;
    const bool want_r = host ? h_R != nullptr : d_R != nullptr;
    auto &W = s->rb;
    const int64_t n = s->n;
    hipStream_t st = s->stream;
-   struct timespec ts0, ts1;
-   clock_gettime (CLOCK_MONOTONIC, &ts0);
 
-   // ---- (a) this rank's arguments (no HIP call), its work space, the host arrays staged on the device
-   int rc = NKP_OK;
-   if (nrhs < 1 || nrhs > NKP_BATCH_MAX) rc = fail (NKP_EINVAL, "%s: nrhs = %d, must be 1 .. %d (more vectors: call again)", who, nrhs, NKP_BATCH_MAX);
-   else if (ldb < n) rc = fail (NKP_EINVAL, "%s: ldb = %lld < n = %lld", who, (long long) ldb, (long long) n);
-   else if (ldx < n) rc = fail (NKP_EINVAL, "%s: ldx = %lld < n = %lld", who, (long long) ldx, (long long) n);
-   else if (want_r && ldr < n) rc = fail (NKP_EINVAL, "%s: ldr = %lld < n = %lld", who, (long long) ldr, (long long) n);
-   else if (want_r && (host ? (const double *) h_R == h_X : (const double *) d_R == d_X))
+   // ---- (a) this rank's arguments, its work space, the host arrays staged on the device (B | X | R, ld n)
+   int rc = refuse_nrhs (who, nrhs, " (more vectors: call again)");
+   if (!rc) rc = refuse_ld (who, "ldb", ldb, "n", n);
+   if (!rc) rc = refuse_ld (who, "ldx", ldx, "n", n);
+   if (!rc && want_r) rc = refuse_ld (who, "ldr", ldr, "n", n);
+   if (!rc && want_r && (host ? (const double *) h_R == h_X : (const double *) d_R == d_X))
       rc = fail (NKP_EINVAL, "%s: R and X are the same buffer (other rows still gather x; R may be B)", who);
-   else if (!want_r && !rnorm && !bnorm && !berr) rc = fail (NKP_EINVAL, "%s: R, rnorm, bnorm and berr are all NULL: nothing is asked for", who);
-   else if (s->shared->broken) rc = refactor_broken (s);
-   if (rc && !dist) return rc;
-   const int K = width_of (nrhs);
-   if (!rc && hipSetDevice (s->device) != hipSuccess) rc = fail (NKP_EDEVICE, "%s: hipSetDevice (%d) failed", who, s->device);
-   const size_t vecs = rc ? 0 : (size_t) nrhs * (size_t) n;
-   if (!rc)
-      rc = reserve (s, { { &W.x, &W.x_cap, !dist && K >= 2 ? (size_t) n * (size_t) K : 0 },      // K = 1 reads x in place; row-distributed: dist.xe / dist.bxe
-                         { &W.partial, &W.partial_cap, 3 * (size_t) K * ((size_t) (s->A.nrowblk > 0 ? s->A.nrowblk : 0) + 1) },
-                         { &W.stage, &W.stage_cap, host ? (want_r ? 3 : 2) * vecs : 0 } }, who);
-   if (!rc && dist && K >= 2 && s->dist.bK < K) rc = batch_prepare_exchange (s, K);
+   if (!rc && !want_r && !rnorm && !bnorm && !berr) rc = fail (NKP_EINVAL, "%s: R, rnorm, bnorm and berr are all NULL: nothing is asked for", who);
+   if (!rc && s->shared->broken) rc = refactor_broken (s);
+   if (c.begin (rc)) return c.rc;
+   const int K = c.K;
+   const size_t vecs = c.rc ? 0 : (size_t) nrhs * (size_t) n, nrb = (size_t) (s->A.nrowblk > 0 ? s->A.nrowblk : 0);
+   c.reserve ({ { &W.x, &W.x_cap, !dist && K >= 2 ? (size_t) n * (size_t) K : 0 },      // K = 1 reads x in place; row-distributed: dist.xe / dist.bxe
+                { &W.partial, &W.partial_cap, 3 * (size_t) K * (nrb + 1) }, { &W.stage, &W.stage_cap, host ? (want_r ? 3 : 2) * vecs : 0 } }, true);
    const double *B = d_B, *X = d_X;
    double *R = d_R;
    int64_t lb = ldb, lx = ldx, lr = ldr;
-   if (!rc && host) {
-      const size_t bytes = (size_t) n * sizeof (double);
+   if (!c.rc && host) {
       double *sb = W.stage, *sx = sb + vecs;
-      hipError_t e = hipSuccess;
-      for (int c = 0; c < nrhs && e == hipSuccess && bytes; c++) {
-         e = hipMemcpyAsync (sb + (size_t) c * (size_t) n, h_B + (size_t) c * (size_t) ldb, bytes, hipMemcpyHostToDevice, st);
-         if (e == hipSuccess) e = hipMemcpyAsync (sx + (size_t) c * (size_t) n, h_X + (size_t) c * (size_t) ldx, bytes, hipMemcpyHostToDevice, st);
-      }
-      if (e != hipSuccess) rc = fail (NKP_EDEVICE, "%s: upload of the host arrays failed: %s", who, hipGetErrorString (e));
       B = sb; X = sx; R = want_r ? sx + vecs : nullptr;
       lb = lx = lr = n;
+      hipError_t e = upload_columns (sb, h_B, ldb, nrhs, n, st);
+      if (e == hipSuccess) e = upload_columns (sx, h_X, ldx, nrhs, n, st);
+      c.uploaded (e, "arrays");
    }
-   if (dist && (rc = dist_agree (s, rc, who, "arguments, work space, staging"))) {
-      // a rank whose K-wide exchange buffers are gone is not a rank "known to have buffers": the next batched solve agrees anew
-      s->dist.agreed_K = 0;
-      (void) hipStreamSynchronize (st);
-      return rc;
-   }
-   if (rc) return rc;
+   if (c.agree ("arguments, work space, staging")) return c.rc;
 
    // ---- (b) the operand x (single-GPU: interleaved; row-distributed: the halo rows, all vectors in one exchange), the kernel, the
    // reductions across the ranks, the results; on a row-distributed solver every callback is reached whatever happened locally
-   double *out = W.partial + 3 * (size_t) K * (size_t) (s->A.nrowblk > 0 ? s->A.nrowblk : 0);
+   double *out = W.partial + 3 * (size_t) K * nrb;
    const double *xp[NKP_BATCH_MAX] = {};
-   for (int c = 0; c < nrhs; c++) xp[c] = X + (size_t) c * (size_t) lx;
+   for (int k = 0; k < nrhs; k++) xp[k] = X + (size_t) k * (size_t) lx;
    const double *x_in = X;
-   rc = fetch_x_operand (s, K, xp, W.x, &x_in, who);
-   if (!rc) launch_residual_batch (K, nrhs, s->A, x_in, B, lb, R, lr, W.partial, out, st);
+   c.rc = fetch_x_operand (s, K, xp, W.x, &x_in, who);
+   if (!c.rc) launch_residual_batch (K, nrhs, s->A, x_in, B, lb, R, lr, W.partial, out, st);
    if (dist) {
       // like allreduce_dev, but a failure is this call's alone (not sticky): the solver's later solves reduce anew
       auto &ops = s->dist.ops;
@@ -81,28 +64,20 @@ int residual_batch (nkp_solver *s, int nrhs, const double *h_B, const double *h_
       const int c1 = ops.allreduce (ops.ctx, out, 2 * K, 0, (void *) st);
       s->shared->allreduce_calls++;
       const int c2 = ops.allreduce (ops.ctx, out + 2 * K, K, 1, (void *) st);
-      if (!rc && (c1 || c2)) rc = fail (NKP_ECOMM, "%s: the allreduce of the %s failed", who, c1 ? "squared norms" : "backward errors");
+      if (!c.rc && (c1 || c2)) c.rc = fail (NKP_ECOMM, "%s: the allreduce of the %s failed", who, c1 ? "squared norms" : "backward errors");
    }
    double res[3 * NKP_BATCH_MAX] = {};
-   if (!rc) {
-      hipError_t e = hipMemcpyAsync (res, out, 3 * (size_t) K * sizeof (double), hipMemcpyDeviceToHost, st);
-      for (int c = 0; host && want_r && c < nrhs && e == hipSuccess && n; c++)
-         e = hipMemcpyAsync (h_R + (size_t) c * (size_t) ldr, R + (size_t) c * (size_t) n, (size_t) n * sizeof (double), hipMemcpyDeviceToHost, st);
-      if (e == hipSuccess) e = hipStreamSynchronize (st);
-      if (e == hipSuccess) e = hipGetLastError ();
-      if (e != hipSuccess) rc = fail (NKP_EDEVICE, "%s: the residual kernel or its copies failed: %s", who, hipGetErrorString (e));
-   } else
-      (void) hipStreamSynchronize (st);
-   if (dist) rc = dist_agree (s, rc, who, "exchange, kernel, reductions");
-   if (rc) return rc;
-   for (int c = 0; c < nrhs; c++) {
-      if (rnorm) rnorm[c] = sqrt (res[c]);
-      if (bnorm) bnorm[c] = sqrt (res[K + c]);
-      if (berr) berr[c] = res[2 * K + c];
+   hipError_t e = hipSuccess;
+   if (!c.rc) {
+      e = hipMemcpyAsync (res, out, 3 * (size_t) K * sizeof (double), hipMemcpyDeviceToHost, st);
+      if (e == hipSuccess && host && want_r) e = download_columns (h_R, ldr, R, nrhs, n, st);
    }
-   clock_gettime (CLOCK_MONOTONIC, &ts1);
-   W.seconds = (double) (ts1.tv_sec - ts0.tv_sec) + 1e-9 * (double) (ts1.tv_nsec - ts0.tv_nsec);
-   W.calls++;
+   if (c.finish (e, "residual", "exchange, kernel, reductions", W.seconds, W.calls)) return c.rc;
+   for (int k = 0; k < nrhs; k++) {
+      if (rnorm) rnorm[k] = sqrt (res[k]);
+      if (bnorm) bnorm[k] = sqrt (res[K + k]);
+      if (berr) berr[k] = res[2 * K + k];
+   }
    return NKP_OK;
 }
 
@@ -110,17 +85,15 @@ int residual_batch (nkp_solver *s, int nrhs, const double *h_B, const double *h_
 
 void residual_release (nkp_solver *s)
 {
-   for (double **p : { &s->rb.x, &s->rb.partial, &s->rb.stage })
-      if (*p) { (void) hipFree (*p); *p = nullptr; }
-   s->rb.x_cap = s->rb.partial_cap = s->rb.stage_cap = 0;
+   auto &W = s->rb;
+   release_buffers (s, { { &W.x, &W.x_cap, 0 }, { &W.partial, &W.partial_cap, 0 }, { &W.stage, &W.stage_cap, 0 } });
 }
 
 // B (K vectors) in the staging buffer, for the composition the K plain vectors of X behind them; the kernel reads the interleaved
 // copy, K = 1 the solver's work vector t1 (filled by nkp_time_kernel)
 int residual_time_prepare (nkp_solver *s, int K, int which)
 {
-   if (s->dist.on) return fail (NKP_EINVAL, "nkp_time_kernel: the residual kernel (which = %d) is timed on single-GPU solvers only", which);
-   if (K != 1 && K != 2 && K != 4 && K != 8) return fail (NKP_EINVAL, "nkp_time_kernel: which = %d takes arg = K in {1, 2, 4, 8}", which);
+   if (const int rc = time_width_ok (s, K, which, "residual")) return rc;
    const size_t kn = (size_t) K * (size_t) s->n, il = K >= 2 ? kn : 0, nrb = (size_t) (s->A.nrowblk > 0 ? s->A.nrowblk : 0);
    const int rc = reserve (s, { { &s->rb.x, &s->rb.x_cap, il }, { &s->rb.partial, &s->rb.partial_cap, 3 * (size_t) K * (nrb + 1) },
                                 { &s->rb.stage, &s->rb.stage_cap, 2 * kn } }, "nkp_time_kernel");

@@ -10,6 +10,8 @@
 //   inspect.hip         entry points of tests and timing (arrays of the hierarchy and the matrix, single products, nkp_time_kernel)
 //   refactor_api.hip, transpose*.hip, valgrad_api.hip, valprod_api.hip, valprod_trans_dist.hip      new values, A^T, gradient and products by values
 //   residual_api.hip    residual, norms and backward error of K given solutions (nkp_residual_batch); the kernel is residual.hip
+//   operand_call.h      what valgrad_api, valprod_api, valprod_trans_dist and residual_api share: the envelope of a K-vector call on the
+//                       pattern (OperandCall: arguments, work space, the two agreements), column staging, Stopwatch, release_buffers
 // What crosses units is declared once, below, under the unit that defines it.  Private to the library: nothing here is part of
 // the C ABI.
 #pragma once
@@ -442,16 +444,18 @@ NKP_PRIVATE const MlSmoothHook *smooth_hook_of (nkp_solver *s);
 NKP_PRIVATE void launch_smooth_pack (int K, const int *idx, const double *x, double *out, int64_t nrows, hipStream_t st);
 NKP_PRIVATE void launch_smooth_unpack (int K, const int *idx, const double *in, double *x, int64_t nrows, hipStream_t st);
 // ---- defined in valgrad_api.hip --------------------------------------------------------------------------------------------
+// (the *_release and *_time_prepare functions of the next three units rest on release_buffers and time_width_ok, operand_call.h;
+// the *_time_* pairs are the rows of nkp_time_kernel's table, inspect.hip)
 NKP_PRIVATE void valgrad_release (nkp_solver *s);
 // nkp_time_kernel, which = 5: scratch operands for the gradient kernel at interleave width K (1, 2, 4, 8), then one launch
-NKP_PRIVATE int valgrad_time_prepare (nkp_solver *s, int K);
+NKP_PRIVATE int valgrad_time_prepare (nkp_solver *s, int K, int which);
 NKP_PRIVATE void valgrad_time_launch (nkp_solver *s, int K);
 // The operand x of a K-wide kernel on the pattern (xp = the vectors, own rows; pointers beyond them NULL): single-GPU the vectors
 // themselves (K = 1) or their K-interleaved copy in `il` (n * K doubles); row-distributed [own | halo] rows in dist.xe (K = 1) or
 // dist.bxe (K >= 2, batch_prepare_exchange done), the halo rows of all vectors fetched in ONE alltoallv (halo_fetch), which is
 // always made and counted.  *x_in = what the kernel reads.  NKP_ECOMM when the exchange failed (the stream is then still to be synchronised).
 NKP_PRIVATE int fetch_x_operand (nkp_solver *s, int K, const double *const *xp, double *il, const double **x_in, const char *who);
-// ---- defined in valprod_api.hip --------------------------------------------------------------------------------------------
+// ---- defined in valprod_api.hip (product_stage, shared with valprod_trans_dist.hip: operand_call.h) ------------------------
 NKP_PRIVATE void valprod_release (nkp_solver *s);
 // nkp_time_kernel, which = 6: scratch operands for the product kernel at interleave width K (1, 2, 4, 8), then one launch;
 // which = 7: the composition of SpMV kernels it replaces (product into a temporary, de-interleave, update pass)

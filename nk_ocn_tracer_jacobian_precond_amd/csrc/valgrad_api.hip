@@ -2,9 +2,7 @@
 // g[e] (+)= alpha * sum_c lambda_c[row of e] * x_c[colind[e]], on single-GPU and row-distributed solvers.  The kernel is
 // valgrad.hip; this unit checks the arguments, keeps the work space, fetches the halo rows of x on a row-distributed solver
 // and keeps the ranks together.  Only the pattern of the solver's matrix is read.
-#include "solver_impl.h"
-
-#include <time.h>
+#include "operand_call.h"
 
 namespace {
 
@@ -13,77 +11,49 @@ namespace {
 int value_gradient (nkp_solver *s, int nrhs, const double *h_lam, const double *h_x, const double *d_lam, const double *d_x, int64_t ld, double alpha,
                     int accumulate, double *h_g, double *d_g, const char *who)
 {
-   const bool host = h_g != nullptr;
-   const bool dist = s->dist.on;
-   auto &D = s->dist;
+   OperandCall c (s, who, nrhs, h_g != nullptr);
    auto &W = s->vg;
    const int64_t n = s->n, nnz = s->A.nnz;
    hipStream_t st = s->stream;
-   struct timespec ts0;
-   clock_gettime (CLOCK_MONOTONIC, &ts0);
 
-   // ---- (a) this rank's arguments (no HIP call), its work space, the host vectors staged on the device
-   int rc = NKP_OK;
-   if (nrhs < 1 || nrhs > NKP_BATCH_MAX) rc = fail (NKP_EINVAL, "%s: nrhs = %d, must be 1 .. %d (more right-hand sides: call again with accumulate = 1)", who, nrhs, NKP_BATCH_MAX);
-   else if (ld < n) rc = fail (NKP_EINVAL, "%s: ld = %lld < n = %lld", who, (long long) ld, (long long) n);
-   if (rc && !dist) return rc;
-   const int K = width_of (nrhs);
-   if (!rc && hipSetDevice (s->device) != hipSuccess) rc = fail (NKP_EDEVICE, "%s: hipSetDevice (%d) failed", who, s->device);
-   if (!rc) {
-      const size_t il = K >= 2 ? (size_t) n * (size_t) K : 0;      // K = 1 reads the vectors in place
-      rc = reserve (s, { { &W.lam, &W.lam_cap, il }, { &W.x, &W.x_cap, dist ? 0 : il },      // row-distributed: x interleaved is dist.bxe
-                         { &W.stage, &W.stage_cap, host ? 2 * (size_t) nrhs * (size_t) n : 0 }, { &W.g, &W.g_cap, host ? (size_t) nnz : 0 } }, who);
-   }
-   if (!rc && dist && K >= 2 && D.bK < K) rc = batch_prepare_exchange (s, K);
+   // ---- (a) this rank's arguments, its work space, the host vectors staged on the device (lambda | x, ld n)
+   int rc = refuse_nrhs (who, nrhs, " (more right-hand sides: call again with accumulate = 1)");
+   if (!rc) rc = refuse_ld (who, "ld", ld, "n", n);
+   if (c.begin (rc)) return c.rc;
+   const int K = c.K;
+   const size_t il = K >= 2 ? (size_t) n * (size_t) K : 0;      // K = 1 reads the vectors in place
+   c.reserve ({ { &W.lam, &W.lam_cap, il }, { &W.x, &W.x_cap, c.dist ? 0 : il },      // row-distributed: x interleaved is dist.bxe
+                { &W.stage, &W.stage_cap, c.host ? 2 * (size_t) nrhs * (size_t) n : 0 }, { &W.g, &W.g_cap, c.host ? (size_t) nnz : 0 } }, true);
    const double *L = d_lam, *X = d_x;
    double *G = d_g;
    int64_t ldv = ld;
-   if (!rc && host) {
-      const size_t bytes = (size_t) n * sizeof (double);
-      hipError_t e = hipSuccess;
-      for (int c = 0; c < nrhs && e == hipSuccess && bytes; c++) {
-         e = hipMemcpyAsync (W.stage + (size_t) c * (size_t) n, h_lam + (size_t) c * (size_t) ld, bytes, hipMemcpyHostToDevice, st);
-         if (e == hipSuccess) e = hipMemcpyAsync (W.stage + (size_t) (nrhs + c) * (size_t) n, h_x + (size_t) c * (size_t) ld, bytes, hipMemcpyHostToDevice, st);
-      }
-      if (e == hipSuccess && accumulate && nnz) e = hipMemcpyAsync (W.g, h_g, (size_t) nnz * sizeof (double), hipMemcpyHostToDevice, st);
-      if (e != hipSuccess) rc = fail (NKP_EDEVICE, "%s: upload of the host vectors failed: %s", who, hipGetErrorString (e));
+   if (!c.rc && c.host) {
       L = W.stage;
       X = W.stage + (size_t) nrhs * (size_t) n;
       G = W.g;
       ldv = n;
+      hipError_t e = upload_columns (W.stage, h_lam, ld, nrhs, n, st);
+      if (e == hipSuccess) e = upload_columns (W.stage + (size_t) nrhs * (size_t) n, h_x, ld, nrhs, n, st);
+      if (e == hipSuccess && accumulate && nnz) e = hipMemcpyAsync (W.g, h_g, (size_t) nnz * sizeof (double), hipMemcpyHostToDevice, st);
+      c.uploaded (e, "vectors");
    }
-   if (dist && (rc = dist_agree (s, rc, who, "arguments and work space"))) {
-      // a rank whose K-wide exchange buffers are gone is not a rank "known to have buffers": the next batched solve agrees anew
-      D.agreed_K = 0;
-      return rc;
-   }
-   if (rc) return rc;
+   if (c.agree ("arguments and work space")) return c.rc;
 
    // ---- (b) the halo rows of x, all K vectors in one exchange; then the kernel
    const double *lp[NKP_BATCH_MAX] = {}, *xp[NKP_BATCH_MAX] = {};
-   for (int c = 0; c < nrhs; c++) { lp[c] = L + (size_t) c * (size_t) ldv; xp[c] = X + (size_t) c * (size_t) ldv; }
+   for (int k = 0; k < nrhs; k++) { lp[k] = L + (size_t) k * (size_t) ldv; xp[k] = X + (size_t) k * (size_t) ldv; }
    const double *lam_in = L, *x_in = X;
    if (K >= 2) {
       launch_interleave (K, lp, W.lam, n, st);
       lam_in = W.lam;
    }
-   rc = fetch_x_operand (s, K, xp, W.x, &x_in, who);
-   if (!rc) {
+   c.rc = fetch_x_operand (s, K, xp, W.x, &x_in, who);
+   hipError_t e = hipSuccess;
+   if (!c.rc) {
       launch_value_gradient (K, nrhs, s->A, lam_in, x_in, alpha, accumulate, G, st);
-      hipError_t e = hipSuccess;
-      if (host && nnz) e = hipMemcpyAsync (h_g, W.g, (size_t) nnz * sizeof (double), hipMemcpyDeviceToHost, st);
-      if (e == hipSuccess) e = hipStreamSynchronize (st);
-      if (e == hipSuccess) e = hipGetLastError ();
-      if (e != hipSuccess) rc = fail (NKP_EDEVICE, "%s: the gradient kernel or its copies failed: %s", who, hipGetErrorString (e));
-   } else
-      (void) hipStreamSynchronize (st);
-   if (dist) rc = dist_agree (s, rc, who, "exchange and kernel");
-   if (rc) return rc;
-   struct timespec ts1;
-   clock_gettime (CLOCK_MONOTONIC, &ts1);
-   W.seconds = (double) (ts1.tv_sec - ts0.tv_sec) + 1e-9 * (double) (ts1.tv_nsec - ts0.tv_nsec);
-   W.calls++;
-   return NKP_OK;
+      if (c.host && nnz) e = hipMemcpyAsync (h_g, W.g, (size_t) nnz * sizeof (double), hipMemcpyDeviceToHost, st);
+   }
+   return c.finish (e, "gradient", "exchange and kernel", W.seconds, W.calls);
 }
 
 }   // namespace
@@ -104,18 +74,15 @@ int fetch_x_operand (nkp_solver *s, int K, const double *const *xp, double *il, 
 
 void valgrad_release (nkp_solver *s)
 {
-   for (double **p : { &s->vg.lam, &s->vg.x, &s->vg.stage, &s->vg.g })
-      if (*p) { (void) hipFree (*p); *p = nullptr; }
-   s->vg.lam_cap = s->vg.x_cap = s->vg.stage_cap = s->vg.g_cap = 0;
+   auto &W = s->vg;
+   release_buffers (s, { { &W.lam, &W.lam_cap, 0 }, { &W.x, &W.x_cap, 0 }, { &W.stage, &W.stage_cap, 0 }, { &W.g, &W.g_cap, 0 } });
 }
 
-int valgrad_time_prepare (nkp_solver *s, int K)
+int valgrad_time_prepare (nkp_solver *s, int K, int which)
 {
-   if (s->dist.on) return fail (NKP_EINVAL, "nkp_time_kernel: the gradient kernel (which = 5) is timed on single-GPU solvers only");
-   if (K != 1 && K != 2 && K != 4 && K != 8) return fail (NKP_EINVAL, "nkp_time_kernel: which = 5 takes arg = K in {1, 2, 4, 8}");
+   if (const int rc = time_width_ok (s, K, which, "gradient")) return rc;
    const size_t il = K >= 2 ? (size_t) s->n * (size_t) K : 0;
-   const int rc = reserve (s, { { &s->vg.lam, &s->vg.lam_cap, il }, { &s->vg.x, &s->vg.x_cap, il }, { &s->vg.g, &s->vg.g_cap, (size_t) s->A.nnz } }, "nkp_time_kernel");
-   if (rc) return rc;
+   if (const int rc = reserve (s, { { &s->vg.lam, &s->vg.lam_cap, il }, { &s->vg.x, &s->vg.x_cap, il }, { &s->vg.g, &s->vg.g_cap, (size_t) s->A.nnz } }, "nkp_time_kernel")) return rc;
    if (il) {
       launch_fill (s->vg.lam, 1.0, (int64_t) il, s->stream);
       launch_fill (s->vg.x, 1.0, (int64_t) il, s->stream);

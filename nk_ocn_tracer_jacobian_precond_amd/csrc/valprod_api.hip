@@ -6,15 +6,12 @@
 // nkp_values_product_trans*: the same product with the transposed pattern, y_c (+)= alpha * (pattern with val)^T x_c, val still in
 // A's order.  Same arguments, work space and kernel text; what it adds is the transposed index (solver_impl.h: vt) it builds at its
 // first call, and the refusals of the handles that do not hold A's pattern themselves.
-#include "solver_impl.h"
+#include "operand_call.h"
 #include "transpose.h"
 
 #include <stdlib.h>
-#include <time.h>
 
 namespace {
-
-double seconds_between (const struct timespec &a, const struct timespec &b) { return (double) (b.tv_sec - a.tv_sec) + 1e-9 * (double) (b.tv_nsec - a.tv_nsec); }
 
 // ---- the transposed index: the device transpose of the pattern (its values dropped), the row blocks from a host copy of rowptrT --
 // those a solver created from the host transpose has.  All four arrays or none: after a failure the solver holds what it held and
@@ -25,8 +22,7 @@ int trans_index_build (nkp_solver *s, const char *who)
    if (I.src) return NKP_OK;
    const int64_t n = s->n, nnz = s->A.nnz;
    hipStream_t st = s->stream;
-   struct timespec t0, t1;
-   clock_gettime (CLOCK_MONOTONIC, &t0);
+   const Stopwatch watch;
    mls::DBuf<int> rowptrT, colindT, src, rowblk;
    {
       mls::DBuf<double> valT;      // comes along with the transpose; freed here
@@ -62,50 +58,31 @@ int trans_index_build (nkp_solver *s, const char *who)
    I.T.nrowblk = nrb;
    I.src = src.release ();
    s->device_bytes += I.bytes;
-   clock_gettime (CLOCK_MONOTONIC, &t1);
-   I.build_seconds = seconds_between (t0, t1);
+   I.build_seconds = watch.seconds ();
    msg (s, 1, "%s: transposed index of %lld entries, %d row blocks, %.1f MB, %.3f s\n", who, (long long) nnz, nrb, (double) I.bytes / 1.0e6, I.build_seconds);
    return NKP_OK;
 }
 
 // ---- (b) the operand x (single-GPU: interleaved; row-distributed: the halo rows, all vectors in one exchange), the kernel, and on
-// a row-distributed solver the second agreement.  h_y: the host flavour's result, downloaded from Y (ld n) before the agreement
-// trans: the product with the transposed pattern (single-GPU only; the index exists)
-int product_run (nkp_solver *s, int nrhs, const double *val, const double *X, int64_t ldx, double alpha, int accumulate, double *Y, int64_t ldy,
-                 double *h_y, int64_t h_ldy, const char *who, bool trans = false)
+// a row-distributed solver the second agreement; the time of a product runs from here.  h_y: the host flavour's result, downloaded
+// from Y (ld n) before the agreement.  trans: the product with the transposed pattern (single-GPU only; the index exists)
+int product_run (OperandCall &c, const double *val, const double *X, int64_t ldx, double alpha, int accumulate, double *Y, int64_t ldy, double *h_y,
+                 int64_t h_ldy, bool trans = false)
 {
-   const int K = width_of (nrhs);
-   const int64_t n = s->n;
+   nkp_solver *s = c.s;
    hipStream_t st = s->stream;
-   struct timespec ts0;
-   clock_gettime (CLOCK_MONOTONIC, &ts0);
+   c.watch.start ();
    const double *xp[NKP_BATCH_MAX] = {};
-   for (int c = 0; c < nrhs; c++) xp[c] = X + (size_t) c * (size_t) ldx;
+   for (int k = 0; k < c.nrhs; k++) xp[k] = X + (size_t) k * (size_t) ldx;
    const double *x_in = X;
-   int rc = fetch_x_operand (s, K, xp, s->vp.x, &x_in, who);
-   if (!rc) {
-      if (trans) launch_values_product_trans (K, nrhs, s->vt.T, s->vt.src, val, x_in, alpha, accumulate, Y, ldy, st);
-      else launch_values_product (K, nrhs, s->A, val, x_in, alpha, accumulate, Y, ldy, st);
-      hipError_t e = hipSuccess;
-      for (int c = 0; h_y && c < nrhs && e == hipSuccess && n; c++)
-         e = hipMemcpyAsync (h_y + (size_t) c * (size_t) h_ldy, Y + (size_t) c * (size_t) ldy, (size_t) n * sizeof (double), hipMemcpyDeviceToHost, st);
-      if (e == hipSuccess) e = hipStreamSynchronize (st);
-      if (e == hipSuccess) e = hipGetLastError ();
-      if (e != hipSuccess) rc = fail (NKP_EDEVICE, "%s: the product kernel or its copies failed: %s", who, hipGetErrorString (e));
-   } else
-      (void) hipStreamSynchronize (st);
-   if (s->dist.on) rc = dist_agree (s, rc, who, "exchange and kernel");
-   if (rc) return rc;
-   struct timespec ts1;
-   clock_gettime (CLOCK_MONOTONIC, &ts1);
-   if (trans) {
-      s->vt.seconds = seconds_between (ts0, ts1);
-      s->vt.calls++;
-   } else {
-      s->vp.seconds = seconds_between (ts0, ts1);
-      s->vp.calls++;
+   c.rc = fetch_x_operand (s, c.K, xp, s->vp.x, &x_in, c.who);
+   hipError_t e = hipSuccess;
+   if (!c.rc) {
+      if (trans) launch_values_product_trans (c.K, c.nrhs, s->vt.T, s->vt.src, val, x_in, alpha, accumulate, Y, ldy, st);
+      else launch_values_product (c.K, c.nrhs, s->A, val, x_in, alpha, accumulate, Y, ldy, st);
+      if (h_y) e = download_columns (h_y, h_ldy, Y, c.nrhs, s->n, st);
    }
-   return NKP_OK;
+   return c.finish (e, "product", "exchange and kernel", trans ? s->vt.seconds : s->vp.seconds, trans ? s->vt.calls : s->vp.calls);
 }
 
 // Host flavour: h_* given, d_* NULL; device flavour the other way round.  The entry points have refused NULL arguments on the
@@ -121,50 +98,21 @@ int values_product (nkp_solver *s, int nrhs, const double *h_val, const double *
       if (s->dist.on)
          return fail (NKP_EINVAL, "%s: not available for the row-distributed flavour (the product with the transposed pattern sends products back to the owners of their columns, a collective of its own); call nkp_values_product_trans_dist%s on every rank", who, h_y ? "" : "_device");
    }
-   const bool host = h_y != nullptr;
-   const bool dist = s->dist.on;
-   auto &W = s->vp;
-   const int64_t n = s->n, nnz = s->A.nnz;
-   hipStream_t st = s->stream;
+   OperandCall c (s, who, nrhs, h_y != nullptr);
+   const int64_t n = s->n;
 
-   // ---- (a) this rank's arguments (no HIP call), its work space, the host arrays staged on the device
-   int rc = NKP_OK;
-   if (nrhs < 1 || nrhs > NKP_BATCH_MAX) rc = fail (NKP_EINVAL, "%s: nrhs = %d, must be 1 .. %d (more vectors: call again)", who, nrhs, NKP_BATCH_MAX);
-   else if (ldx < n) rc = fail (NKP_EINVAL, "%s: ldx = %lld < n = %lld", who, (long long) ldx, (long long) n);
-   else if (ldy < n) rc = fail (NKP_EINVAL, "%s: ldy = %lld < n = %lld", who, (long long) ldy, (long long) n);
-   else if (host ? (const double *) h_y == h_x : (const double *) d_y == d_x) rc = fail (NKP_EINVAL, "%s: y and x are the same buffer (the product is not done in place)", who);
-   if (rc && !dist) return rc;
-   const int K = width_of (nrhs);
-   if (!rc && hipSetDevice (s->device) != hipSuccess) rc = fail (NKP_EDEVICE, "%s: hipSetDevice (%d) failed", who, s->device);
-   const size_t vecs = rc ? 0 : (size_t) nrhs * (size_t) n;
-   if (!rc && trans) rc = trans_index_build (s, who);
-   if (!rc)
-      rc = reserve (s, { { &W.x, &W.x_cap, !dist && K >= 2 ? (size_t) n * (size_t) K : 0 },      // K = 1 reads x in place; row-distributed: dist.xe / dist.bxe
-                         { &W.stage, &W.stage_cap, host ? (size_t) nnz + 2 * vecs : 0 } }, who);
-   if (!rc && dist && K >= 2 && s->dist.bK < K) rc = batch_prepare_exchange (s, K);
-   const double *V = d_val, *X = d_x;
-   double *Y = d_y;
-   int64_t lx = ldx, ly = ldy;
-   if (!rc && host) {
-      const size_t bytes = (size_t) n * sizeof (double);
-      double *sx = W.stage + (size_t) nnz, *sy = sx + vecs;
-      hipError_t e = hipSuccess;
-      if (nnz) e = hipMemcpyAsync (W.stage, h_val, (size_t) nnz * sizeof (double), hipMemcpyHostToDevice, st);
-      for (int c = 0; c < nrhs && e == hipSuccess && bytes; c++) {
-         e = hipMemcpyAsync (sx + (size_t) c * (size_t) n, h_x + (size_t) c * (size_t) ldx, bytes, hipMemcpyHostToDevice, st);
-         if (e == hipSuccess && accumulate) e = hipMemcpyAsync (sy + (size_t) c * (size_t) n, h_y + (size_t) c * (size_t) ldy, bytes, hipMemcpyHostToDevice, st);
-      }
-      if (e != hipSuccess) rc = fail (NKP_EDEVICE, "%s: upload of the host arrays failed: %s", who, hipGetErrorString (e));
-      V = W.stage; X = sx; Y = sy;
-      lx = ly = n;
-   }
-   if (dist && (rc = dist_agree (s, rc, who, "arguments and work space"))) {
-      // a rank whose K-wide exchange buffers are gone is not a rank "known to have buffers": the next batched solve agrees anew
-      s->dist.agreed_K = 0;
-      return rc;
-   }
-   if (rc) return rc;
-   return product_run (s, nrhs, V, X, lx, alpha, accumulate, Y, ly, host ? h_y : nullptr, ldy, who, trans);
+   // ---- (a) this rank's arguments, for the transposed product its index, the work space, the host arrays staged on the device
+   int rc = refuse_nrhs (who, nrhs, " (more vectors: call again)");
+   if (!rc) rc = refuse_ld (who, "ldx", ldx, "n", n);
+   if (!rc) rc = refuse_ld (who, "ldy", ldy, "n", n);
+   if (!rc && (c.host ? (const double *) h_y == h_x : (const double *) d_y == d_x)) rc = fail (NKP_EINVAL, "%s: y and x are the same buffer (the product is not done in place)", who);
+   if (c.begin (rc)) return c.rc;
+   if (!c.rc && trans) c.rc = trans_index_build (s, who);
+   ProductOperands o = { d_val, d_x, d_y, ldx, ldy };
+   product_stage (c, { &s->vp.x, &s->vp.x_cap, !c.dist && c.K >= 2 ? (size_t) n * (size_t) c.K : 0 },      // K = 1 reads x in place; row-distributed: dist.xe / dist.bxe
+                  h_val, h_x, h_y, accumulate, o, true);
+   if (c.agree ("arguments and work space")) return c.rc;
+   return product_run (c, o.val, o.x, o.ldx, alpha, accumulate, o.y, o.ldy, h_y, ldy, trans);
 }
 
 // The first agreement of a tangent solve: every rank learns whether any rank's step failed AND whether all ranks pass d_dval alike
@@ -184,24 +132,38 @@ int tangent_agree (nkp_solver *s, int local_rc, bool has_dval, const char *who)
 
 }   // namespace
 
+void product_stage (OperandCall &c, Want xbuf, const double *h_val, const double *h_x, const double *h_y, int accumulate, ProductOperands &o, bool fetch)
+{
+   nkp_solver *s = c.s;
+   auto &W = s->vp;
+   const int64_t n = s->n;
+   const size_t nnz = (size_t) s->A.nnz, vecs = c.rc ? 0 : (size_t) c.nrhs * (size_t) n;
+   c.reserve ({ xbuf, { &W.stage, &W.stage_cap, c.host ? nnz + 2 * vecs : 0 } }, fetch);
+   if (c.rc || !c.host) return;
+   double *sx = W.stage + nnz, *sy = sx + vecs;
+   hipError_t e = nnz ? hipMemcpyAsync (W.stage, h_val, nnz * sizeof (double), hipMemcpyHostToDevice, s->stream) : hipSuccess;
+   if (e == hipSuccess) e = upload_columns (sx, h_x, o.ldx, c.nrhs, n, s->stream);
+   if (e == hipSuccess && accumulate) e = upload_columns (sy, h_y, o.ldy, c.nrhs, n, s->stream);
+   c.uploaded (e, "arrays");
+   o = { W.stage, sx, sy, n, n };
+}
+
 void valprod_release (nkp_solver *s)
 {
-   for (double **p : { &s->vp.x, &s->vp.stage, &s->vp.r })
+   auto &W = s->vp;
+   auto &I = s->vt;
+   release_buffers (s, { { &W.x, &W.x_cap, 0 }, { &W.stage, &W.stage_cap, 0 }, { &W.r, &W.r_cap, 0 }, { &I.xe, &I.xe_cap, 0 }, { &I.send, &I.send_cap, 0 } });
+   for (int **p : { &I.T.rowptr, &I.T.colind, &I.T.rowblk, &I.src, &I.ship_e, &I.ship_i })
       if (*p) { (void) hipFree (*p); *p = nullptr; }
-   s->vp.x_cap = s->vp.stage_cap = s->vp.r_cap = 0;
-   for (int **p : { &s->vt.T.rowptr, &s->vt.T.colind, &s->vt.T.rowblk, &s->vt.src, &s->vt.ship_e, &s->vt.ship_i })
-      if (*p) { (void) hipFree (*p); *p = nullptr; }
-   for (double **p : { &s->vt.xe, &s->vt.send })
-      if (*p) { (void) hipFree (*p); *p = nullptr; }
-   s->vt.T.nrowblk = 0;
-   s->vt.bytes = s->vt.xe_cap = s->vt.send_cap = 0;
+   s->device_bytes -= I.bytes;      // the index, counted when it was built
+   I.T.nrowblk = 0;
+   I.bytes = 0;
    s->vt.n_ship = s->vt.n_recv = 0;
 }
 
 int valprod_time_prepare (nkp_solver *s, int K, int which)
 {
-   if (s->dist.on) return fail (NKP_EINVAL, "nkp_time_kernel: the product kernel (which = %d) is timed on single-GPU solvers only", which);
-   if (K != 1 && K != 2 && K != 4 && K != 8) return fail (NKP_EINVAL, "nkp_time_kernel: which = %d takes arg = K in {1, 2, 4, 8}", which);
+   if (const int wrc = time_width_ok (s, K, which, "product")) return wrc;
    const size_t kn = (size_t) K * (size_t) s->n, il = K >= 2 ? kn : 0, nnz = (size_t) s->A.nnz;
    if (which == 9 || which == 10) {
       if (s->borrowed || s->trans_of) return fail (NKP_EINVAL, "nkp_time_kernel: which = %d is timed on the solver that owns A's pattern, not on a clone or a transposed handle", which);
@@ -299,38 +261,30 @@ extern "C" int nkp_solve_tangent_device (nkp_solver *s, int nrhs, const void *d_
    if (!d_dx) return fail (NKP_EINVAL, "%s: NULL argument d_dx", who);
    if (!d_dval && !d_db) return fail (NKP_EINVAL, "%s: d_dval and d_db are both NULL: there is no tangent to solve for", who);
    if (d_dval && !d_x) return fail (NKP_EINVAL, "%s: NULL argument d_x (needed with d_dval)", who);
-   const bool dist = s->dist.on, has_dval = d_dval != nullptr;
+   OperandCall c (s, who, nrhs, false);
+   const bool has_dval = d_dval != nullptr;
    auto &W = s->vp;
    const int64_t n = s->n;
    hipStream_t st = s->stream;
 
-   // ---- (a) arguments (no HIP call), work space, R = dB (or zero) in the solver's work space
-   int rc = NKP_OK;
-   if (nrhs < 1 || nrhs > NKP_BATCH_MAX) rc = fail (NKP_EINVAL, "%s: nrhs = %d, must be 1 .. %d", who, nrhs, NKP_BATCH_MAX);
-   else if (ld < n) rc = fail (NKP_EINVAL, "%s: ld = %lld < n = %lld", who, (long long) ld, (long long) n);
-   else if (has_dval && ldx < n) rc = fail (NKP_EINVAL, "%s: ldx = %lld < n = %lld", who, (long long) ldx, (long long) n);
-   if (rc && !dist) return rc;
-   const int K = width_of (nrhs);
-   if (!rc && hipSetDevice (s->device) != hipSuccess) rc = fail (NKP_EDEVICE, "%s: hipSetDevice (%d) failed", who, s->device);
-   if (!rc)
-      rc = reserve (s, { { &W.x, &W.x_cap, has_dval && !dist && K >= 2 ? (size_t) n * (size_t) K : 0 }, { &W.r, &W.r_cap, (size_t) nrhs * (size_t) ld } }, who);
-   if (!rc && has_dval && dist && K >= 2 && s->dist.bK < K) rc = batch_prepare_exchange (s, K);
-   if (!rc) {
+   // ---- (a) arguments, work space, R = dB (or zero) in the solver's work space
+   int rc = refuse_nrhs (who, nrhs, "");
+   if (!rc) rc = refuse_ld (who, "ld", ld, "n", n);
+   if (!rc && has_dval) rc = refuse_ld (who, "ldx", ldx, "n", n);
+   if (c.begin (rc)) return c.rc;
+   c.reserve ({ { &W.x, &W.x_cap, has_dval && !c.dist && c.K >= 2 ? (size_t) n * (size_t) c.K : 0 }, { &W.r, &W.r_cap, (size_t) nrhs * (size_t) ld } }, has_dval);
+   if (!c.rc) {
       const size_t bytes = (size_t) n * sizeof (double);
       hipError_t e = hipSuccess;
-      for (int c = 0; c < nrhs && e == hipSuccess && bytes; c++) {
-         double *rc_ = W.r + (size_t) c * (size_t) ld;
-         e = d_db ? hipMemcpyAsync (rc_, (const double *) d_db + (size_t) c * (size_t) ld, bytes, hipMemcpyDeviceToDevice, st) : hipMemsetAsync (rc_, 0, bytes, st);
+      for (int k = 0; k < nrhs && e == hipSuccess && bytes; k++) {
+         double *rk = W.r + (size_t) k * (size_t) ld;
+         e = d_db ? hipMemcpyAsync (rk, (const double *) d_db + (size_t) k * (size_t) ld, bytes, hipMemcpyDeviceToDevice, st) : hipMemsetAsync (rk, 0, bytes, st);
       }
-      if (e != hipSuccess) rc = fail (NKP_EDEVICE, "%s: the copy of dB failed: %s", who, hipGetErrorString (e));
+      if (e != hipSuccess) c.rc = fail (NKP_EDEVICE, "%s: the copy of dB failed: %s", who, hipGetErrorString (e));
    }
-   if (dist && (rc = tangent_agree (s, rc, has_dval, who))) {
-      s->dist.agreed_K = 0;
-      return rc;
-   }
-   if (rc) return rc;
+   if (c.agreed (c.dist ? tangent_agree (s, c.rc, has_dval, who) : c.rc)) return c.rc;
    // ---- (b) R -= dA X: nkp_values_product_device (alpha = -1, accumulate = 1) on R; then the batched solve R -> dX
-   if (has_dval && (rc = product_run (s, nrhs, (const double *) d_dval, (const double *) d_x, ldx, -1.0, 1, W.r, ld, nullptr, 0, who))) return rc;
+   if (has_dval && product_run (c, (const double *) d_dval, (const double *) d_x, ldx, -1.0, 1, W.r, ld, nullptr, 0)) return c.rc;
    rc = nkp_solve_batch_device (s, nrhs, W.r, d_dx, ld, berr, iters, relres);
    if (rc >= 0) W.tangent_calls++;
    return rc;

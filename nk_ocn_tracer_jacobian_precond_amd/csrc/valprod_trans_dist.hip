@@ -13,11 +13,11 @@
 //   q) and its x row (a local row, or m_loc + q), and the ship list (position in val_loc and local row, grouped by destination).
 //   A call: x interleaved into xe = [ own rows | received products ] x K, the pack kernel below, ONE alltoallv straight into the
 //   receive area of xe, and the product kernel of valprod.hip in its RECV mode (a received product takes the value 1.0).
+#include "operand_call.h"
 #include "transpose_dist.h"
 
 #include <limits.h>
 #include <stdlib.h>
-#include <time.h>
 
 #include <memory>
 
@@ -50,13 +50,6 @@ void vtd_pack_kernel (int64_t n, const int *__restrict__ ship_e, const int *__re
 
 namespace {
 
-double seconds_since (const struct timespec &a)
-{
-   struct timespec b;
-   clock_gettime (CLOCK_MONOTONIC, &b);
-   return (double) (b.tv_sec - a.tv_sec) + 1e-9 * (double) (b.tv_nsec - a.tv_nsec);
-}
-
 // xe and the K-wide send buffer for width K, both or neither (a buffer of no element holds one)
 int work_reserve (nkp_solver *s, int K, int64_t n_ship, int64_t n_recv, const char *who)
 {
@@ -67,11 +60,7 @@ int work_reserve (nkp_solver *s, int K, int64_t n_ship, int64_t n_recv, const ch
 
 void work_release (nkp_solver *s)
 {
-   auto &I = s->vt;
-   s->device_bytes -= (I.xe_cap + I.send_cap) * sizeof (double);
-   for (double **p : { &I.xe, &I.send })
-      if (*p) { (void) hipFree (*p); *p = nullptr; }
-   I.xe_cap = I.send_cap = 0;
+   release_buffers (s, { { &s->vt.xe, &s->vt.xe_cap, 0 }, { &s->vt.send, &s->vt.send_cap, 0 } });
 }
 
 // what the index build holds beside the steps of transpose_dist.h until every rank has built its part
@@ -79,8 +68,8 @@ struct IndexBuild {
    TransDistBuild B;
    mls::DBuf<int> rowptrF, rowblk, ship_e, ship_i;
    int nrb = 0;
-   struct timespec t0;
-   explicit IndexBuild (const nkp_solver *s) : B (s) { clock_gettime (CLOCK_MONOTONIC, &t0); }
+   Stopwatch watch;
+   explicit IndexBuild (const nkp_solver *s) : B (s) {}
 };
 
 #define VTDHIP(call)                                                                                         \
@@ -142,7 +131,7 @@ void index_commit (nkp_solver *s, IndexBuild &X, const char *who)
    I.send_k.clear ();
    I.recv_k.clear ();
    s->device_bytes += I.bytes;
-   I.build_seconds = seconds_since (X.t0);
+   I.build_seconds = X.watch.seconds ();
    msg (s, 1, "%s: transposed index of rows [%lld, %lld): %lld entries, %lld shipped, %lld received, %d row blocks, %.1f MB, %.3f s\n", who, (long long) s->dist.fst,
         (long long) (s->dist.fst + B.m_loc), (long long) B.nnzF, (long long) B.n_ship, (long long) B.n_recv, X.nrb, (double) I.bytes / 1.0e6, I.build_seconds);
 }
@@ -152,47 +141,29 @@ void index_commit (nkp_solver *s, IndexBuild &X, const char *who)
 int product_trans_dist (nkp_solver *s, int nrhs, const double *h_val, const double *h_x, const double *d_val, const double *d_x, int64_t ldx, double alpha,
                         int accumulate, double *h_y, double *d_y, int64_t ldy, const char *who)
 {
-   const bool host = h_y != nullptr;
+   OperandCall c (s, who, nrhs, h_y != nullptr, false);      // its own exchange: the K-wide halo buffers are not touched
    auto &I = s->vt;
-   auto &W = s->vp;
-   const int64_t n = s->n, nnz = s->A.nnz;
+   const int64_t n = s->n;
    hipStream_t st = s->stream;
 
-   // ---- (a) this rank's arguments (no HIP call), without an index the local transpose, the work space, the host arrays staged
-   int rc = NKP_OK;
-   if (nrhs < 1 || nrhs > NKP_BATCH_MAX) rc = fail (NKP_EINVAL, "%s: nrhs = %d, must be 1 .. %d (more vectors: call again)", who, nrhs, NKP_BATCH_MAX);
-   else if (ldx < n) rc = fail (NKP_EINVAL, "%s: ldx = %lld < m_loc = %lld", who, (long long) ldx, (long long) n);
-   else if (ldy < n) rc = fail (NKP_EINVAL, "%s: ldy = %lld < m_loc = %lld", who, (long long) ldy, (long long) n);
-   else if (host ? (const double *) h_y == h_x : (const double *) d_y == d_x) rc = fail (NKP_EINVAL, "%s: y and x are the same buffer (the product is not done in place)", who);
-   const int K = width_of (nrhs);
-   if (!rc && hipSetDevice (s->device) != hipSuccess) rc = fail (NKP_EDEVICE, "%s: hipSetDevice (%d) failed", who, s->device);
+   // ---- (a) this rank's arguments, without an index the local transpose, the work space, the host arrays staged
+   int rc = refuse_nrhs (who, nrhs, " (more vectors: call again)");
+   if (!rc) rc = refuse_ld (who, "ldx", ldx, "m_loc", n);
+   if (!rc) rc = refuse_ld (who, "ldy", ldy, "m_loc", n);
+   if (!rc && (c.host ? (const double *) h_y == h_x : (const double *) d_y == d_x)) rc = fail (NKP_EINVAL, "%s: y and x are the same buffer (the product is not done in place)", who);
+   c.begin (rc);      // row-distributed: never returns here
+   const int K = c.K;
    const bool building = !I.src;      // all ranks or none: the index is committed after an agreement
    std::unique_ptr<IndexBuild> X;
    if (building) {
       X.reset (new IndexBuild (s));
-      if (!rc) rc = td_local_transpose (s, X->B, who);
+      if (!c.rc) c.rc = td_local_transpose (s, X->B, who);
       X->B.valT.reset ();      // comes along with the transpose; the index holds no values
-   } else if (!rc)
-      rc = work_reserve (s, K, I.n_ship, I.n_recv, who);
-   const size_t vecs = rc ? 0 : (size_t) nrhs * (size_t) n;
-   if (!rc) rc = reserve (s, { { &W.stage, &W.stage_cap, host ? (size_t) nnz + 2 * vecs : 0 } }, who);
-   const double *V = d_val, *Xd = d_x;
-   double *Y = d_y;
-   int64_t lx = ldx, ly = ldy;
-   if (!rc && host) {
-      const size_t bytes = (size_t) n * sizeof (double);
-      double *sx = W.stage + (size_t) nnz, *sy = sx + vecs;
-      hipError_t e = hipSuccess;
-      if (nnz) e = hipMemcpyAsync (W.stage, h_val, (size_t) nnz * sizeof (double), hipMemcpyHostToDevice, st);
-      for (int c = 0; c < nrhs && e == hipSuccess && bytes; c++) {
-         e = hipMemcpyAsync (sx + (size_t) c * (size_t) n, h_x + (size_t) c * (size_t) ldx, bytes, hipMemcpyHostToDevice, st);
-         if (e == hipSuccess && accumulate) e = hipMemcpyAsync (sy + (size_t) c * (size_t) n, h_y + (size_t) c * (size_t) ldy, bytes, hipMemcpyHostToDevice, st);
-      }
-      if (e != hipSuccess) rc = fail (NKP_EDEVICE, "%s: upload of the host arrays failed: %s", who, hipGetErrorString (e));
-      V = W.stage; Xd = sx; Y = sy;
-      lx = ly = n;
-   }
-   if ((rc = dist_agree (s, rc, who, building ? "arguments, local transpose and work space" : "arguments and work space"))) return rc;
+   } else if (!c.rc)
+      c.rc = work_reserve (s, K, I.n_ship, I.n_recv, who);
+   ProductOperands o = { d_val, d_x, d_y, ldx, ldy };
+   product_stage (c, { &s->vp.x, &s->vp.x_cap, 0 }, h_val, h_x, h_y, accumulate, o, false);
+   if (c.agree (building ? "arguments, local transpose and work space" : "arguments and work space")) return c.rc;
 
    // ---- (b) only in a call that builds the index: the entry counts, then placement, arrays and work space; all ranks or none
    if (building) {
@@ -206,42 +177,34 @@ int product_trans_dist (nkp_solver *s, int nrhs, const double *h_val, const doub
       X.reset ();
    }
 
-   // ---- (c) x into xe, the products to ship, ONE alltoallv into the receive area of xe (always made), the kernel, the agreement
-   struct timespec ts0;
-   clock_gettime (CLOCK_MONOTONIC, &ts0);
+   // ---- (c) x into xe, the products to ship, ONE alltoallv into the receive area of xe (always made), the kernel, the agreement;
+   // the time of a product runs from here
+   c.watch.start ();
    I.send_k = I.send_entries;
    I.recv_k = I.recv_entries;
    for (int &v : I.send_k) v *= K;
    for (int &v : I.recv_k) v *= K;
    hipError_t e = hipSuccess;
    if (K == 1) {
-      if (n) e = hipMemcpyAsync (I.xe, Xd, (size_t) n * sizeof (double), hipMemcpyDeviceToDevice, st);
+      if (n) e = hipMemcpyAsync (I.xe, o.x, (size_t) n * sizeof (double), hipMemcpyDeviceToDevice, st);
    } else {
       const double *xp[NKP_BATCH_MAX] = {};
-      for (int c = 0; c < nrhs; c++) xp[c] = Xd + (size_t) c * (size_t) lx;
+      for (int k = 0; k < nrhs; k++) xp[k] = o.x + (size_t) k * (size_t) o.ldx;
       launch_interleave (K, xp, I.xe, n, st);
    }
    if (e == hipSuccess && I.n_ship)
       with_int<1, 2, 4, 8> (K, [&] (auto k) {
          hipLaunchKernelGGL ((vtd_pack_kernel<decltype (k)::value>), dim3 ((unsigned) ((I.n_ship + VTD_T - 1) / VTD_T)), dim3 (VTD_T), 0, st, I.n_ship,
-                             (const int *) I.ship_e, (const int *) I.ship_i, V, (const double *) I.xe, I.send);
+                             (const int *) I.ship_e, (const int *) I.ship_i, o.val, (const double *) I.xe, I.send);
       });
-   if (e != hipSuccess) rc = fail (NKP_EDEVICE, "%s: the copy of x failed: %s", who, hipGetErrorString (e));
+   if (e != hipSuccess) c.rc = fail (NKP_EDEVICE, "%s: the copy of x failed: %s", who, hipGetErrorString (e));
    if (alltoallv_dev (s, I.send, I.send_k.data (), I.xe + (size_t) n * (size_t) K, I.recv_k.data (), st, false)) {
-      if (!rc) rc = fail (NKP_ECOMM, "%s: the exchange of the products failed", who);
-   } else if (!rc) {
-      launch_values_product_trans_recv (K, nrhs, I.T, I.src, V, I.xe, alpha, accumulate, Y, ly, st);
-      for (int c = 0; host && c < nrhs && e == hipSuccess && n; c++)
-         e = hipMemcpyAsync (h_y + (size_t) c * (size_t) ldy, Y + (size_t) c * (size_t) ly, (size_t) n * sizeof (double), hipMemcpyDeviceToHost, st);
-      if (e == hipSuccess) e = hipStreamSynchronize (st);
-      if (e == hipSuccess) e = hipGetLastError ();
-      if (e != hipSuccess) rc = fail (NKP_EDEVICE, "%s: the product kernel or its copies failed: %s", who, hipGetErrorString (e));
+      if (!c.rc) c.rc = fail (NKP_ECOMM, "%s: the exchange of the products failed", who);
+   } else if (!c.rc) {
+      launch_values_product_trans_recv (K, nrhs, I.T, I.src, o.val, I.xe, alpha, accumulate, o.y, o.ldy, st);
+      if (c.host) e = download_columns (h_y, ldy, o.y, nrhs, n, st);
    }
-   if (rc) (void) hipStreamSynchronize (st);
-   if ((rc = dist_agree (s, rc, who, "exchange and kernel"))) return rc;
-   I.seconds = seconds_since (ts0);
-   I.calls++;
-   return NKP_OK;
+   return c.finish (e, "product", "exchange and kernel", I.seconds, I.calls);
 }
 
 // refused on the calling rank, before any collective

@@ -13,40 +13,11 @@ import types
 
 import numpy as np
 
+from comm_trace import traced
 from dist_values_product_worker import GRID, Device, bits
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-
-
-def traced(solver, ops, log):
-    """a copy of ops whose four callbacks append their name (and the reduction's count and op) to log and call the transport's"""
-    orig = solver.NkpCommOps()
-    C.memmove(C.byref(orig), C.byref(ops), C.sizeof(solver.NkpCommOps))
-
-    def allreduce(ctx, buf, count, op, st):
-        log.append(f"allreduce {'max' if op else 'sum'} {count}")
-        return orig.allreduce(ctx, buf, count, op, st)
-
-    def alltoallv(ctx, send, sc, recv, rc, st):
-        log.append("alltoallv")
-        return orig.alltoallv(ctx, send, sc, recv, rc, st)
-
-    def alltoallv_i32(ctx, send, sc, recv, rc):
-        log.append("alltoallv_i32_host")
-        return orig.alltoallv_i32_host(ctx, send, sc, recv, rc)
-
-    def allgather(ctx, mine, out):
-        log.append("allgather_i64_host")
-        return orig.allgather_i64_host(ctx, mine, out)
-
-    w = solver.NkpCommOps()
-    w.ctx, w.rank, w.nranks = ops.ctx, ops.rank, ops.nranks
-    w.allreduce = solver._ALLREDUCE_FN(allreduce)
-    w.alltoallv = solver._ALLTOALLV_FN(alltoallv)
-    w.alltoallv_i32_host = solver._ALLTOALLV_I32_FN(alltoallv_i32)
-    w.allgather_i64_host = solver._ALLGATHER_I64_FN(allgather)
-    return w, orig
 
 
 def main():

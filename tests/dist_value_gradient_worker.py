@@ -14,6 +14,8 @@ import types
 import numpy as np
 import scipy.sparse as sp
 
+from comm_trace import Recorder, traced
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 GRID = (40, 46, 20)
@@ -58,7 +60,7 @@ def main():
     ap.add_argument("--out", required=True)
     ap.add_argument("--file-dir", required=True)
     ap.add_argument("--precond", default="none")
-    ap.add_argument("--cases", default="bits,transposed,refuse")
+    ap.add_argument("--cases", default="bits,transposed,refuse,trace")
     a = ap.parse_args()
     rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
     from nk_ocn_tracer_jacobian_precond_amd import dist as nd
@@ -143,6 +145,41 @@ def main():
         out["next_equal"] = bits(got, restate(p.rowptr, p.colind, lam[:4], x[:4], -1.0)[e0:e1])
         res["refuse"] = out
     s.close()
+    if "trace" in cases:
+        # the order of the transport's callbacks and the counters, on a solver of its own whose first K = 4 call is the one recorded
+        log = []
+        wrapped, orig = traced(solver, ops, log)
+        tcomm = types.SimpleNamespace(ops=wrapped, errors=comm.errors, keep=orig)
+        rec = Recorder(log, "value_gradient_calls")
+        ld, e = m + 3, e1 - e0
+        bad = rank == world - 1
+
+        def padded(v):
+            out = np.full((v.shape[0], ld), np.nan)
+            out[:, :m] = v
+            return out
+
+        with nd.NkpDistSolver(loc, n, tcomm, **opts) as h:
+            out = {}
+            dl, dx = Device(padded(lam_loc)), Device(padded(x_loc))
+            for K in (1, 3):
+                dg = Device(np.full(e, np.nan))
+                out[f"device{K}"], _ = rec.run(h, lambda: h.value_gradient_device(dl.ptr, dx.ptr, K, ld, dg.ptr))
+                out[f"device{K}"]["equal"] = bits(dg.get(), restate(p.rowptr, p.colind, lam[:K], x[:K], -1.0)[e0:e1])
+                if K == 3:
+                    first = dg.get()
+                dg.free()
+            out["host3"], got = rec.run(h, lambda: h.value_gradient(lam_loc[:3], x_loc[:3]))
+            out["host3"]["equal"] = bits(got, first)
+            dg = Device(np.full(e, 2.5))
+            c, info = rec.run(h, lambda: code_of(lambda: h.value_gradient_device(dl.ptr, dx.ptr, 9 if bad else 3, ld, dg.ptr)))
+            c.update(info, bad=bad, bad_rank=world - 1, g_untouched=bool(np.all(dg.get() == 2.5)))
+            h.value_gradient_device(dl.ptr, dx.ptr, 3, ld, dg.ptr)
+            c["next_equal"] = bits(dg.get(), first)
+            out["refuse"] = c
+            for d in (dl, dx, dg):
+                d.free()
+        res["trace"] = out
     res["comm_errors"] = comm.errors
     with open(f"{a.out}.{rank}", "w") as fh:
         json.dump(res, fh)

@@ -15,6 +15,7 @@ import types
 
 import numpy as np
 
+from comm_trace import traced
 from dist_values_product_worker import GRID, SENTINEL, Device, bits, restate_rows
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -107,7 +108,9 @@ def main():
     lib.nkp_comm_file_free.restype = None
     ops = solver.NkpCommOps()
     assert lib.nkp_comm_file_init(C.byref(ops), a.file_dir.encode(), rank, world) == 0
-    comm = types.SimpleNamespace(ops=ops, errors=[])
+    log = []
+    wrapped, orig = traced(solver, ops, log)
+    comm = types.SimpleNamespace(ops=wrapped, errors=[], keep=orig)
 
     p = synth.generate(imt=GRID[0], jmt=GRID[1], km=GRID[2], adv="upwind3", hmix="isop", seed=2, u_scale=3.0, ah=4.0e6, isop_k33=True)
     n = p.flat_len
@@ -150,14 +153,19 @@ def main():
         """the two device calls of the issue: 0.37 accumulated on a seeded y with sentinel tails, -1 written over NaN"""
         dx, dy = Device(rows(X[:K])), Device(rows(Y0[:K], SENTINEL))
         c0 = counters(s)
+        del log[:]
         s.values_product_trans_dist_device(dv.ptr, dx.ptr, K, ld, dy.ptr, ld, alpha=0.37, accumulate=True)
+        out.update(trace=list(log))
         c1 = counters(s)
         got = dy.get()
         out.update(acc_equal=bits(got[:, :m], Y0[:K, f:f + m] + 0.37 * T_[:K, f:f + m]), tail=bool(np.all(got[:, m:] == SENTINEL)),
                    x_untouched=bits(dx.get()[:, :m], X[:K, f:f + m]) and bool(np.all(np.isnan(dx.get()[:, m:]))),
-                   alltoallv=c1["alltoallv"] - c0["alltoallv"], calls=c1["calls"] - c0["calls"], index_before=c0["index"], index_after=c1["index"])
+                   alltoallv=c1["alltoallv"] - c0["alltoallv"], allreduce=c1["allreduce"] - c0["allreduce"], calls=c1["calls"] - c0["calls"],
+                   index_before=c0["index"], index_after=c1["index"])
         dn = Device(np.full((K, ld), np.nan))
+        del log[:]
         s.values_product_trans_dist_device(dv.ptr, dx.ptr, K, ld, dn.ptr, ld, alpha=-1.0, accumulate=False)
+        out.update(write_trace=list(log))
         got = dn.get()
         out.update(write_equal=bits(got[:, :m], -1.0 * T_[:K, f:f + m]), write_tail=bool(np.all(np.isnan(got[:, m:]))))
         for d in (dx, dy, dn):
@@ -171,11 +179,13 @@ def main():
     res["index_bytes_at_start"] = s.get_int("trans_index_bytes")
     res["bits"] = {str(K): device_bits(s, dv, K, T, {}) for K in (1, 3, 4, 8)}
     c0 = counters(s)
+    del log[:]
     host = s.values_product_trans_dist(dval_loc, np.ascontiguousarray(X[:3, f:f + m]), alpha=0.37, Y=np.ascontiguousarray(Y0[:3, f:f + m]))
+    host_trace = list(log)
     c1 = counters(s)
     host_w = s.values_product_trans_dist(dval_loc, np.ascontiguousarray(X[:3, f:f + m]), alpha=-1.0)
     res["host"] = dict(acc_equal=bits(host, Y0[:3, f:f + m] + 0.37 * T[:3, f:f + m]), write_equal=bits(host_w, -1.0 * T[:3, f:f + m]),
-                       alltoallv=c1["alltoallv"] - c0["alltoallv"], calls=c1["calls"] - c0["calls"])
+                       alltoallv=c1["alltoallv"] - c0["alltoallv"], calls=c1["calls"] - c0["calls"], trace=host_trace)
     res["sent_entries"], res["recv_entries"] = s.get_int("trans_index_sent_entries"), s.get_int("trans_index_recv_entries")
     idx = s.get_int("trans_index_bytes")
     s.refactor_dist(loc["val"] * 0.75)
@@ -224,22 +234,26 @@ def main():
     bad = rank == world - 1
     sm = nd.NkpDistSolver(loc, n, comm, rtol=1e-10, restart=60, max_iters=3000)
     dv, db, dx, dy = Device(dval_loc), Device(rows(Y0[:2])), Device(rows(np.vstack([X, X[:1]]))), Device(np.zeros((9, ld)))
-    d1, d2 = Device(np.zeros((2, ld))), Device(np.zeros((2, ld)))
+    d1, d2, ys = Device(np.zeros((2, ld))), Device(np.zeros((2, ld))), Device(np.full((9, ld), 2.5))
     sm.solve_batch_device(db.ptr, d1.ptr, 2, ld, raise_on_fail=False)
     res["refuse"] = []
     for has_index in (False, True):
         c0 = counters(sm)
-        out = code_of(lambda: sm.values_product_trans_dist_device(dv.ptr, dx.ptr, 9 if bad else 4, ld, dy.ptr, ld))
+        del log[:]
+        out = code_of(lambda: sm.values_product_trans_dist_device(dv.ptr, dx.ptr, 9 if bad else 4, ld, ys.ptr, ld))
         c1 = counters(sm)
+        out.update(trace=list(log), exchanges=c1["alltoallv"] - c0["alltoallv"] + c1["allreduce"] - c0["allreduce"], y_untouched=bool(np.all(ys.get() == 2.5)))
         out.update(bad=bad, bad_rank=world - 1, calls_unchanged=c1["calls"] == c0["calls"], index_unchanged=c1["index"] == c0["index"],
                    had_index=c0["index"] > 0, want_index=has_index)
         sm.solve_batch_device(db.ptr, d2.ptr, 2, ld, raise_on_fail=False)
         out["next_solve_equal"] = bits(d1.get(), d2.get())
         res["refuse"].append(out)
+        del log[:]
+        sm.values_product_trans_dist_device(dv.ptr, dx.ptr, 4, ld, dy.ptr, ld)
+        out.update(next_trace=list(log), next_equal=bits(dy.get()[:4, :m], T[:4, f:f + m]))
         if not has_index:
-            sm.values_product_trans_dist_device(dv.ptr, dx.ptr, 4, ld, dy.ptr, ld)
-            res["multilevel_equal"] = bits(dy.get()[:4, :m], T[:4, f:f + m])
-    for d in (dv, db, dx, dy, d1, d2):
+            res["multilevel_equal"] = out["next_equal"]
+    for d in (dv, db, dx, dy, d1, d2, ys):
         d.free()
     sm.close()
 
@@ -273,7 +287,7 @@ def main():
     res["comm_errors"] = comm.errors
     with open(f"{a.out}.{rank}", "w") as fh:
         json.dump(res, fh)
-    lib.nkp_comm_file_free(C.byref(comm.ops))
+    lib.nkp_comm_file_free(C.byref(ops))
 
 
 if __name__ == "__main__":

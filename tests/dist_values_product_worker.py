@@ -71,7 +71,10 @@ def main():
     lib.nkp_comm_file_free.restype = None
     ops = solver.NkpCommOps()
     assert lib.nkp_comm_file_init(C.byref(ops), a.file_dir.encode(), rank, world) == 0
-    comm = types.SimpleNamespace(ops=ops, errors=[])
+    from comm_trace import Recorder, traced
+    log = []
+    wrapped, orig = traced(solver, ops, log)
+    comm = types.SimpleNamespace(ops=wrapped, errors=[], keep=orig)
 
     p = synth.generate(imt=GRID[0], jmt=GRID[1], km=GRID[2], adv="upwind3", hmix="isop", seed=2, u_scale=3.0, ah=4.0e6, isop_k33=True)
     n = p.flat_len
@@ -108,6 +111,36 @@ def main():
     s = nd.NkpDistSolver(loc, n, comm, rtol=1e-10, restart=60, max_iters=3000)
     res["halo_rows"] = s.get_int("dist_halo_rows")
     dv = Device(dval_loc)
+
+    # ---- the order of the transport's callbacks and the counters, before anything else so that nrhs = 3 is the solver's first call
+    # at width 4: the product in both flavours, a refused call, then the tangent solve up to the first callback of its batched solve
+    rec, bad = Recorder(log, "values_product_calls"), rank == world - 1
+    out = {}
+    dx9, ys = Device(rows(X)), Device(np.full((9, ld), 2.5))
+    for K in (1, 3):
+        dy = Device(np.full((K, ld), np.nan))
+        out[f"device{K}"], _ = rec.run(s, lambda: s.values_product_device(dv.ptr, dx9.ptr, K, ld, dy.ptr, ld, alpha=0.37))
+        if K == 3:
+            first = dy.get()
+        dy.free()
+    out["host3"], host = rec.run(s, lambda: s.values_product(dval_loc, np.ascontiguousarray(X[:3, f:f + m]), alpha=0.37))
+    out["host3"]["equal"] = bits(host, first[:, :m])
+    c, info = rec.run(s, lambda: code_of(lambda: s.values_product_device(dv.ptr, dx9.ptr, 9 if bad else 3, ld, ys.ptr, ld, alpha=0.37)))
+    c.update(info, bad=bad, bad_rank=world - 1, y_untouched=bool(np.all(ys.get() == 2.5)))
+    dy = Device(np.full((3, ld), np.nan))
+    s.values_product_device(dv.ptr, dx9.ptr, 3, ld, dy.ptr, ld, alpha=0.37)
+    c["next_equal"] = bits(dy.get()[:, :m], first[:, :m])
+    out["refuse"] = c
+    db = Device(rows(dB[:3]))
+    for K in (1, 3):
+        got, _ = rec.run(s, lambda: s.solve_tangent_device(dv.ptr, dx9.ptr, ld, db.ptr, dy.ptr, K, ld, raise_on_fail=False))
+        out[f"tangent{K}"] = dict(trace=got["trace"][:4], calls=got["counters"]["calls"])
+    c, info = rec.run(s, lambda: code_of(lambda: s.solve_tangent_device(dv.ptr, dx9.ptr, ld, db.ptr, ys.ptr, 9 if bad else 3, ld)))
+    c.update(info, bad=bad, bad_rank=world - 1, y_untouched=bool(np.all(ys.get() == 2.5)))
+    out["tangent_refuse"] = c
+    res["trace"] = out
+    for d in (dx9, ys, dy, db):
+        d.free()
 
     # ---- bits: every rank's slice of y against the restatement on its local CSR, one alltoallv per product
     res["bits"] = {}
@@ -170,7 +203,7 @@ def main():
     res["comm_errors"] = comm.errors
     with open(f"{a.out}.{rank}", "w") as fh:
         json.dump(res, fh)
-    lib.nkp_comm_file_free(C.byref(comm.ops))
+    lib.nkp_comm_file_free(C.byref(ops))
 
 
 if __name__ == "__main__":

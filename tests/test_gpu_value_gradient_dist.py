@@ -9,6 +9,8 @@ import sys
 
 import pytest
 
+from comm_trace import GOOD_CALL, REFUSED_CALL
+
 pytestmark = pytest.mark.gpu
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -65,6 +67,24 @@ def test_a_bad_argument_on_one_rank_is_told_to_all(bands):
         else:
             assert c["code"] == -5 and f"rank {c['bad_rank']}" in c["message"], c
         assert c["calls_unchanged"] and c["next_equal"], c
+
+
+def test_the_callbacks_are_agreement_exchange_agreement(bands):
+    """K = 1, the first call at K = 4 (which makes the K-wide exchange buffers) and the host flavour make the same three calls; a
+    rank with nine pairs makes the first agreement and every rank leaves after it, with nothing written and nothing counted"""
+    for r in bands:
+        t = r["trace"]
+        for key in ("device1", "device3", "host3"):
+            assert t[key]["trace"] == GOOD_CALL, (key, t[key])
+            assert t[key]["counters"] == dict(alltoallv=1, allreduce=0, calls=1) and t[key]["equal"], (key, t[key])
+        c = t["refuse"]
+        if c["bad"]:
+            assert c["code"] == -1 and "nrhs" in c["message"], c
+        else:
+            assert c["code"] == -5 and f"rank {c['bad_rank']}" in c["message"], c
+        assert c["trace"] == REFUSED_CALL, c["trace"]
+        assert c["counters"] == dict(alltoallv=0, allreduce=0, calls=0), c["counters"]
+        assert c["g_untouched"] and c["next_equal"], c
 
 
 def test_multilevel_solver_with_overlap(tmp_path):

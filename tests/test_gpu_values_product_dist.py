@@ -9,7 +9,11 @@ import sys
 
 import pytest
 
+from comm_trace import AGREE, GOOD_CALL, REFUSED_CALL
+
 pytestmark = pytest.mark.gpu
+# what nkp_solve_batch_device calls first, by nrhs (recorded from the library before the envelope of these calls was shared)
+TANGENT_SOLVE_FIRST = {1: ["allreduce sum 1"], 3: [AGREE]}
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -44,6 +48,39 @@ def test_every_rank_has_the_bits_of_the_restatement_on_its_local_rows(bands):
             c = r["bits"][K]
             assert c["equal"] and c["tail"] and c["host_equal"], (K, c)
             assert c["alltoallv"] == 1 and c["host_alltoallv"] == 1 and c["calls"] == 1, (K, c)      # one exchange per product, for any nrhs
+
+
+def _assert_refused(c, output):
+    if c["bad"]:
+        assert c["code"] == -1 and "nrhs" in c["message"], c
+    else:
+        assert c["code"] == -5 and f"rank {c['bad_rank']}" in c["message"], c
+    assert c["trace"] == REFUSED_CALL, c["trace"]                              # the first agreement, made by the failing rank too
+    assert c["counters"] == dict(alltoallv=0, allreduce=0, calls=0), c["counters"]
+    assert c[output], c
+
+
+def test_the_callbacks_are_agreement_exchange_agreement(bands):
+    """nrhs = 1, the solver's first call at width 4 (which makes the K-wide exchange buffers) and the host flavour make the same
+    three calls; a rank with nine vectors makes the first agreement and every rank leaves after it, nothing written or counted"""
+    for r in bands:
+        t = r["trace"]
+        for key in ("device1", "device3", "host3"):
+            assert t[key]["trace"] == GOOD_CALL, (key, t[key])
+            assert t[key]["counters"] == dict(alltoallv=1, allreduce=0, calls=1), (key, t[key])
+        assert t["host3"]["equal"], t["host3"]
+        _assert_refused(t["refuse"], "y_untouched")
+        assert t["refuse"]["next_equal"], t["refuse"]
+
+
+def test_the_tangent_solve_makes_the_products_calls_then_the_batched_solves(bands):
+    """its own first agreement, the product's exchange and second agreement, then the first callback of nkp_solve_batch_device: at
+    nrhs = 1 the reduction of the first norms, at the first width 4 the agreement on the interleave width"""
+    for r in bands:
+        t = r["trace"]
+        assert t["tangent1"] == dict(trace=GOOD_CALL + TANGENT_SOLVE_FIRST[1], calls=1), t["tangent1"]
+        assert t["tangent3"] == dict(trace=GOOD_CALL + TANGENT_SOLVE_FIRST[3], calls=1), t["tangent3"]
+        _assert_refused(t["tangent_refuse"], "y_untouched")
 
 
 def test_tangent_solve_is_the_composition_on_every_rank(bands):

@@ -10,7 +10,11 @@ import sys
 
 import pytest
 
+from comm_trace import AGREE, GOOD_CALL, REFUSED_CALL
+
 pytestmark = pytest.mark.gpu
+# the call that builds the transposed index (recorded from the library before the envelope of these calls was shared)
+BUILDING_CALL = [AGREE, "alltoallv_i32_host", AGREE] + GOOD_CALL[1:]
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -71,6 +75,18 @@ def test_index_is_built_once_kept_and_counted(bands):
     assert any(r["sent_entries"] > 0 for r in bands)
 
 
+def test_the_callbacks_of_the_building_call_and_of_the_steady_state(bands):
+    """the first call agrees, exchanges the entry counts of the index on the host, agrees that every rank built its part, and goes on
+    as every later call does, device or host flavour and whatever nrhs is: agreement, ONE exchange, agreement"""
+    for r in bands:
+        assert r["bits"]["1"]["trace"] == BUILDING_CALL, r["bits"]["1"]["trace"]
+        assert r["bits"]["1"]["write_trace"] == GOOD_CALL, r["bits"]["1"]["write_trace"]
+        for K in ("3", "4", "8"):
+            assert r["bits"][K]["trace"] == GOOD_CALL and r["bits"][K]["write_trace"] == GOOD_CALL, (K, r["bits"][K])
+        assert all(r["bits"][K]["allreduce"] == 0 for K in ("1", "3", "4", "8")), r["bits"]
+        assert r["host"]["trace"] == GOOD_CALL, r["host"]["trace"]
+
+
 def test_adjoint_of_the_values_product(bands):
     """<G^T x, z> and <x, G z> are sums of the same nnz products val[e] x[i] z[j] in different orders: they differ by a few thousand
     roundings of 1e-16 at the most"""
@@ -98,6 +114,9 @@ def test_a_bad_argument_on_one_rank_is_told_to_all(bands):
             else:
                 assert c["code"] == -5 and f"rank {c['bad_rank']}" in c["message"], c
             assert c["calls_unchanged"] and c["index_unchanged"] and c["next_solve_equal"], c
+            assert c["trace"] == REFUSED_CALL and c["exchanges"] == 0, c        # the first agreement, made by the failing rank too
+            assert c["y_untouched"] and c["next_equal"], c
+            assert c["next_trace"] == (GOOD_CALL if c["want_index"] else BUILDING_CALL), c
 
 
 def test_transposed_handle_is_refused_without_a_collective(bands):
